@@ -10,10 +10,13 @@ One "step" = one pass of the hot path over one synthetic batch already resident 
 shard by batch (one process per GPU, weights + priors replicated, NO data-path collective:
 inference is embarrassingly parallel); scaling is weak (B per GPU fixed).
 
-Rank 0 prints ONE JSON line with the whole-job images/sec, the roofline of the dominant
-kernel family (fp32 MFMA implicit-GEMM conv, measured live with hipEvents on the launch
-stream) and, at N=1, the CPU baseline (torch-CPU/oneDNN port of the same graph + the plain-C
-decode/NMS oracle on the host cores; the literal TF-CPU path cannot run here).
+Rank 0 prints ONE JSON line with the whole-job images/sec of exactly K timed steps.  With
+--full the line also carries the roofline of the dominant kernel family (fp32 MFMA
+implicit-GEMM conv, measured live with hipEvents on the launch stream, in a leg of its own),
+the other launch mode, the pinned-host legs, the median of 5 timed regions and, at N=1, the
+CPU baseline (torch-CPU/oneDNN port of the same graph + the plain-C decode/NMS oracle on the
+host cores; the literal TF-CPU path cannot run here) and the other single-GPU BASELINE configs.
+--dump-outputs DIR writes what the last timed step returned, for output-by-output comparisons.
 """
 import argparse
 import json
@@ -89,19 +92,32 @@ def main():
                          "and epilogues; activations stay fp32 in HBM)")
     ap.add_argument("--inputs", type=int, default=4,
                     help="distinct resident input batches rotated through the timed steps (config.inputs_rotated)")
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the K-step timed region is run this many times (barrier + synchronize around each); `value` / "
-                         "`ms_per_step` come from the MEDIAN region, `timing_spread` reports min / median / max")
+                         "`ms_per_step` come from the MEDIAN region, `timing_spread` reports min / median / max "
+                         "(default: 1, so that exactly K steps are timed; 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: the other launch mode, the pinned-host legs, the "
+                         "per-layer roofline leg (--layers), the CPU baseline and the other BASELINE configs.  Without it a "
+                         "run sets up, warms up, times the K steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned to DIR/<name>.npy in float32: boxes, "
+                         "labels, scores and valid detection counts (--train: the per-image localisation / confidence "
+                         "losses); rank 0 only.  The inputs are seeded, so equal arguments give equal inputs")
     ap.add_argument("--other-configs", default="auto", choices=["auto", "on", "off"],
                     help="after the headline (BASELINE configs[1]) also time the other single-GPU BASELINE configs -- VGG16 B=32 fp32 "
                          "(configs[2]), the 512x512 B=16 shard in fp32 and bf16 (configs[4]), the training step B=32 in fp32 and bf16 "
                          "(configs[3]), the MobileNetV2 B=64 step in bf16 and the reference's own batch 32 -- each in a fresh process "
                          "(3 regions x >= 10 steps) and append them to the JSON line as `other_configs`; `value` stays configs[1].  "
-                         "auto = only for the default workload at N = 1")
+                         "auto = only for the default workload at N = 1 (--full runs only)")
     ap.add_argument("--force-dist", action="store_true",
                     help="take the N > 1 code paths at world size 1: RCCL communicator alive (init, first collective, barriers, "
                          "MAX-reduce of the time; --train: bucketed gradient all-reduce on the communication stream)")
     args = ap.parse_args()
+    if not args.full and (args.layers or args.other_configs == "on"):
+        ap.error("--layers and --other-configs on need --full")
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: re-launch under torchrun, one rank per GPU (RCCL)
@@ -195,7 +211,9 @@ def main():
     # a step = one full pass (forward + decode/NMS) over one batch.  Default (--lanes 3): consecutive steps run on three
     # replicas of the net, each on its own in-order stream / hardware queue, so a step may start before the previous
     # one has finished; every one of the K steps is complete at the synchronize that closes the timed region.
-    # --lanes 1: strictly one step at a time on the caller's stream.  The other mode is always reported beside it.
+    # --lanes 1: strictly one step at a time on the caller's stream.  --full reports the other mode beside it.
+    last_out = [None]
+
     def run_steps(dm, n, lanes):
         if lanes > 1:
             for _ in range(n):
@@ -204,6 +222,7 @@ def main():
         else:
             for _ in range(n):
                 out = dm(next_x())
+        last_out[0] = out
         return out
 
     def region(dm, lanes):
@@ -241,172 +260,178 @@ def main():
 
     regions = timed(decoder_model, args.lanes, args.repeats, keep_local=True)
     elapsed = sorted(regions)[len(regions) // 2]            # the median region is the headline
-    # the other mode beside it (informational): two batches in flight when the headline is one step at a time,
-    # one step at a time when the headline keeps two in flight
-    other = None
-    if not args.no_other_leg:
-        if args.lanes == 1:
-            dm2 = get_decoder_model(model, priors, hp, lanes=3)
-            e2 = sorted(timed(dm2, 3, 3))[1]
-            other = {"mode": "three batches in flight (three net replicas on three in-order streams, DecoderModel.submit)",
-                     "ms_per_step": 1e3 * e2 / args.steps, "images_per_sec": world * B * args.steps / e2,
-                     "lane_calibration": getattr(dm2, "lane_calibration", None)}
-            del dm2
-        else:
-            r1 = sorted(timed(decoder_model, 1, 3))
-            e1 = r1[1]
-            other = {"mode": "one step at a time", "ms_per_step": 1e3 * e1 / args.steps,
-                     "images_per_sec": world * B * args.steps / e1,
-                     "ms_per_step_min_median_max": [1e3 * v / args.steps for v in (r1[0], r1[1], r1[-1])]}
+    if args.dump_outputs and rank == 0:
+        boxes, labels, scores = last_out[0]
+        dump_outputs(args.dump_outputs, {"boxes": boxes, "labels": labels, "scores": scores,
+                                         "valid_detections": decoder_model.decoder.last_valid_detections})
     valid = decoder_model.decoder.last_valid_detections
     mean_det = float(valid.float().mean().item())
 
-    # ---- separately labelled (never `value`): the same K steps fed from PINNED HOST batches -- every step's 4 B S S 3
-    # bytes cross PCIe inside the timed region, copied by the lane's own stream beside the other lanes' kernels
-    # (DecoderModel.submit of an ssd_hip.pinned_empty buffer); what a predictor.py-style caller with host data gets
-    h2d = None
-    if args.h2d and args.lanes > 1:
-        hosts = []
-        for k in range(args.lanes + 1):
-            hb = ssd_hip.pinned_empty((B, hp["img_size"], hp["img_size"], 3))
-            hb.copy_(x.cpu() if k == 0 else torch.from_numpy(data_utils.synthetic_images(B, hp["img_size"], seed=100 + rank + k)))
-            hosts.append(hb)
+    if args.full:
+        # the other mode beside it (informational): two batches in flight when the headline is one step at a time,
+        # one step at a time when the headline keeps two in flight
+        other = None
+        if not args.no_other_leg:
+            if args.lanes == 1:
+                dm2 = get_decoder_model(model, priors, hp, lanes=3)
+                e2 = sorted(timed(dm2, 3, 3))[1]
+                other = {"mode": "three batches in flight (three net replicas on three in-order streams, DecoderModel.submit)",
+                         "ms_per_step": 1e3 * e2 / args.steps, "images_per_sec": world * B * args.steps / e2,
+                         "lane_calibration": getattr(dm2, "lane_calibration", None)}
+                del dm2
+            else:
+                r1 = sorted(timed(decoder_model, 1, 3))
+                e1 = r1[1]
+                other = {"mode": "one step at a time", "ms_per_step": 1e3 * e1 / args.steps,
+                         "images_per_sec": world * B * args.steps / e1,
+                         "ms_per_step_min_median_max": [1e3 * v / args.steps for v in (r1[0], r1[1], r1[-1])]}
 
-        def h2d_steps(n):
-            for i in range(n):
-                decoder_model.submit(hosts[i % len(hosts)])
-            decoder_model.wait()
+        # ---- separately labelled (never `value`): the same K steps fed from PINNED HOST batches -- every step's 4 B S S 3
+        # bytes cross PCIe inside the timed region, copied by the lane's own stream beside the other lanes' kernels
+        # (DecoderModel.submit of an ssd_hip.pinned_empty buffer); what a predictor.py-style caller with host data gets
+        h2d = None
+        if args.h2d and args.lanes > 1:
+            hosts = []
+            for k in range(args.lanes + 1):
+                hb = ssd_hip.pinned_empty((B, hp["img_size"], hp["img_size"], 3))
+                hb.copy_(x.cpu() if k == 0 else torch.from_numpy(data_utils.synthetic_images(B, hp["img_size"], seed=100 + rank + k)))
+                hosts.append(hb)
 
-        h2d_steps(2 * args.lanes)
-        rs = []
-        for _ in range(3):
-            torch.cuda.synchronize()
-            barrier()
-            t0 = time.perf_counter()
-            h2d_steps(args.steps)
-            torch.cuda.synchronize()
-            barrier()
-            rs.append(reduce_max(time.perf_counter() - t0))
-        e = sorted(rs)[1]
-        h2d = {"mode": "pinned host batches, H2D copy on each lane's stream inside the timed region (PCIe-inclusive)",
-               "ms_per_step": 1e3 * e / args.steps, "images_per_sec": world * B * args.steps / e,
-               "bytes_per_step": 4 * B * hp["img_size"] * hp["img_size"] * 3,
-               "h2d_GB_per_s": 4e-9 * B * hp["img_size"] * hp["img_size"] * 3 * args.steps / e}
+            def h2d_steps(n):
+                for i in range(n):
+                    decoder_model.submit(hosts[i % len(hosts)])
+                decoder_model.wait()
 
-        # the same steps fed from pinned UINT8 batches (the reference's images before `preprocessing`): a quarter of the
-        # bytes over PCIe, converted (x 1/255; same-size resize = identity) by ssd_preprocess on the lane's stream
-        hosts8 = []
-        for k in range(args.lanes + 1):
-            hb = ssd_hip.pinned_empty((B, hp["img_size"], hp["img_size"], 3), dtype=torch.uint8)
-            hb.copy_((hosts[k] * 255.0 + 0.5).to(torch.uint8))
-            hosts8.append(hb)
-        hosts_f = hosts
-        hosts = hosts8
-        h2d_steps(2 * args.lanes)
-        rs = []
-        for _ in range(3):
-            torch.cuda.synchronize()
-            barrier()
-            t0 = time.perf_counter()
-            h2d_steps(args.steps)
-            torch.cuda.synchronize()
-            barrier()
-            rs.append(reduce_max(time.perf_counter() - t0))
-        e = sorted(rs)[1]
-        h2d["uint8"] = {"mode": "pinned host UINT8 batches: H2D copy + ssd_preprocess (x 1/255) on each lane's stream inside the "
-                                "timed region (PCIe-inclusive)",
-                        "ms_per_step": 1e3 * e / args.steps, "images_per_sec": world * B * args.steps / e,
-                        "bytes_per_step": B * hp["img_size"] * hp["img_size"] * 3,
-                        "h2d_GB_per_s": 1e-9 * B * hp["img_size"] * hp["img_size"] * 3 * args.steps / e}
-        hosts = hosts_f
-        del hosts8
+            h2d_steps(2 * args.lanes)
+            rs = []
+            for _ in range(3):
+                torch.cuda.synchronize()
+                barrier()
+                t0 = time.perf_counter()
+                h2d_steps(args.steps)
+                torch.cuda.synchronize()
+                barrier()
+                rs.append(reduce_max(time.perf_counter() - t0))
+            e = sorted(rs)[1]
+            h2d = {"mode": "pinned host batches, H2D copy on each lane's stream inside the timed region (PCIe-inclusive)",
+                   "ms_per_step": 1e3 * e / args.steps, "images_per_sec": world * B * args.steps / e,
+                   "bytes_per_step": 4 * B * hp["img_size"] * hp["img_size"] * 3,
+                   "h2d_GB_per_s": 4e-9 * B * hp["img_size"] * hp["img_size"] * 3 * args.steps / e}
 
-    # ---- roofline leg: same K steps with per-layer hipEvents on the launch stream
-    model.set_timing(True)
-    for _ in range(args.steps):
-        decoder_model(next_x())
-    info, nfw = model.read_timing(B)
-    model.set_timing(False)
-    # the dense-conv family on the fp32 matrix cores: implicit-GEMM tiles and Winograd F(2x2,3x3) tiles
-    mfma = [r for r in info if r["kind"] == "conv" and r["config"].startswith(("mfma_", "mfma3_", "bf16_", "wino_", "skinny_", "dma3_", "dmab_")) and r["flops"] > 0]
-    mfma_ms = sum(r["ms"] for r in mfma)
-    mfma_flops = sum(r["flops"] for r in mfma)
-    mfma_exec = sum(r["executed_flops"] for r in mfma)
-    wino = [r for r in mfma if r["config"].startswith("wino_")]
-    total_ms = sum(r["ms"] for r in info if r["flops"] > 0 or r["bytes"] > 0 or r["kind"] == "nms")
-    kinds = {}
-    for r in info:
-        if r["flops"] == 0 and r["bytes"] == 0 and r["kind"] != "nms":
-            continue                      # layer replaced by a fused kernel (only event overhead)
-        k = r["kind"]
-        if k == "conv" and r["config"].startswith("wino_"):
-            k = "conv_winograd"
-        elif k == "conv" and r["config"].startswith("mfma3_"):
-            k = "conv_split_bf16"
-        elif k == "conv" and r["config"].startswith("dma3_"):
-            k = "conv_split_bf16_ldsdma"
-        elif k == "conv" and r["config"].startswith("bf16_"):
-            k = "conv_bf16"
-        elif k == "conv" and r["config"].startswith("dmab_"):
-            k = "conv_bf16_ldsdma"
-        elif k == "conv" and not r["config"].startswith(("mfma_", "skinny_")):
-            k = "conv_direct"
-        kinds[k] = kinds.get(k, 0.0) + r["ms"]
-    achieved = mfma_flops / (mfma_ms * 1e-3) / 1e12 if mfma_ms > 0 else 0.0
-    executed = mfma_exec / (mfma_ms * 1e-3) / 1e12 if mfma_ms > 0 else 0.0
-    # time the matrix cores would need at their peak (each layer against the peak of ITS instruction: fp32 MFMA, or
-    # six bf16 MFMAs per product) over the time the launches took: a fraction, never above 1
-    ideal_ms = sum(r["executed_flops"] / (matrix_peak(r["config"]) * 1e12) * 1e3 for r in mfma)
-    frac = ideal_ms / mfma_ms if mfma_ms > 0 else 0.0
-    peak_eff = executed / frac if frac > 0 else PEAK_FP32_MFMA_TFLOPS
-    split = [r for r in mfma if r["config"].startswith(("mfma3_", "dma3_"))]
-    # the single most expensive launch of the family: what `rocprofv3 --kernel-trace --stats` of
-    # `bench.py --no-overlap --no-other-leg` lists as that kernel's average duration (profiles/)
-    dom = max(mfma, key=lambda r: r["ms"]) if mfma else None
-    fused = [r for r in info if r["kind"] == "fused" and r["flops"] > 0]
-    fused_ms = sum(r["ms"] for r in fused)
-    fused_flops = sum(r["flops"] for r in fused)
-    # each fused block priced at the peak of ITS matrix instruction (split-bf16 forms: band3 = row-band kernel of blocks 3-6,
-    # image_split = whole-image kernel where it won the race, stem_split)
-    fused_ideal_ms = sum(r["flops"] / (fused_peak(r["config"]) * 1e12) * 1e3 for r in fused)
-    fused_split = [r for r in fused if fused_peak(r["config"]) != PEAK_FP32_MFMA_TFLOPS]
-    step_flops = sum(r["flops"] for r in info)           # algorithmic conv FLOPs of the whole step
-    step_tflops = step_flops / (elapsed / args.steps) / 1e12
-    if args.layers and rank == 0:
+            # the same steps fed from pinned UINT8 batches (the reference's images before `preprocessing`): a quarter of the
+            # bytes over PCIe, converted (x 1/255; same-size resize = identity) by ssd_preprocess on the lane's stream
+            hosts8 = []
+            for k in range(args.lanes + 1):
+                hb = ssd_hip.pinned_empty((B, hp["img_size"], hp["img_size"], 3), dtype=torch.uint8)
+                hb.copy_((hosts[k] * 255.0 + 0.5).to(torch.uint8))
+                hosts8.append(hb)
+            hosts_f = hosts
+            hosts = hosts8
+            h2d_steps(2 * args.lanes)
+            rs = []
+            for _ in range(3):
+                torch.cuda.synchronize()
+                barrier()
+                t0 = time.perf_counter()
+                h2d_steps(args.steps)
+                torch.cuda.synchronize()
+                barrier()
+                rs.append(reduce_max(time.perf_counter() - t0))
+            e = sorted(rs)[1]
+            h2d["uint8"] = {"mode": "pinned host UINT8 batches: H2D copy + ssd_preprocess (x 1/255) on each lane's stream inside the "
+                                    "timed region (PCIe-inclusive)",
+                            "ms_per_step": 1e3 * e / args.steps, "images_per_sec": world * B * args.steps / e,
+                            "bytes_per_step": B * hp["img_size"] * hp["img_size"] * 3,
+                            "h2d_GB_per_s": 1e-9 * B * hp["img_size"] * hp["img_size"] * 3 * args.steps / e}
+            hosts = hosts_f
+            del hosts8
+
+        # ---- roofline leg: same K steps with per-layer hipEvents on the launch stream
+        model.set_timing(True)
+        for _ in range(args.steps):
+            decoder_model(next_x())
+        info, nfw = model.read_timing(B)
+        model.set_timing(False)
+        # the dense-conv family on the fp32 matrix cores: implicit-GEMM tiles and Winograd F(2x2,3x3) tiles
+        mfma = [r for r in info if r["kind"] == "conv" and r["config"].startswith(("mfma_", "mfma3_", "bf16_", "wino_", "skinny_", "dma3_", "dmab_")) and r["flops"] > 0]
+        mfma_ms = sum(r["ms"] for r in mfma)
+        mfma_flops = sum(r["flops"] for r in mfma)
+        mfma_exec = sum(r["executed_flops"] for r in mfma)
+        wino = [r for r in mfma if r["config"].startswith("wino_")]
+        total_ms = sum(r["ms"] for r in info if r["flops"] > 0 or r["bytes"] > 0 or r["kind"] == "nms")
+        kinds = {}
         for r in info:
-            sys.stderr.write("%-28s %-8s %-22s %8.4f ms %8.2f GFLOP %7.1f MB  %6.1f TF/s %6.0f GB/s\n" % (
-                r["name"], r["kind"], r["config"], r["ms"], r["flops"] / 1e9, r["bytes"] / 1e6,
-                r["flops"] / max(r["ms"], 1e-9) / 1e9, r["bytes"] / max(r["ms"], 1e-9) / 1e6))
+            if r["flops"] == 0 and r["bytes"] == 0 and r["kind"] != "nms":
+                continue                      # layer replaced by a fused kernel (only event overhead)
+            k = r["kind"]
+            if k == "conv" and r["config"].startswith("wino_"):
+                k = "conv_winograd"
+            elif k == "conv" and r["config"].startswith("mfma3_"):
+                k = "conv_split_bf16"
+            elif k == "conv" and r["config"].startswith("dma3_"):
+                k = "conv_split_bf16_ldsdma"
+            elif k == "conv" and r["config"].startswith("bf16_"):
+                k = "conv_bf16"
+            elif k == "conv" and r["config"].startswith("dmab_"):
+                k = "conv_bf16_ldsdma"
+            elif k == "conv" and not r["config"].startswith(("mfma_", "skinny_")):
+                k = "conv_direct"
+            kinds[k] = kinds.get(k, 0.0) + r["ms"]
+        achieved = mfma_flops / (mfma_ms * 1e-3) / 1e12 if mfma_ms > 0 else 0.0
+        executed = mfma_exec / (mfma_ms * 1e-3) / 1e12 if mfma_ms > 0 else 0.0
+        # time the matrix cores would need at their peak (each layer against the peak of ITS instruction: fp32 MFMA, or
+        # six bf16 MFMAs per product) over the time the launches took: a fraction, never above 1
+        ideal_ms = sum(r["executed_flops"] / (matrix_peak(r["config"]) * 1e12) * 1e3 for r in mfma)
+        frac = ideal_ms / mfma_ms if mfma_ms > 0 else 0.0
+        peak_eff = executed / frac if frac > 0 else PEAK_FP32_MFMA_TFLOPS
+        split = [r for r in mfma if r["config"].startswith(("mfma3_", "dma3_"))]
+        # the single most expensive launch of the family: what `rocprofv3 --kernel-trace --stats` of
+        # `bench.py --no-overlap --no-other-leg` lists as that kernel's average duration (profiles/)
+        dom = max(mfma, key=lambda r: r["ms"]) if mfma else None
+        fused = [r for r in info if r["kind"] == "fused" and r["flops"] > 0]
+        fused_ms = sum(r["ms"] for r in fused)
+        fused_flops = sum(r["flops"] for r in fused)
+        # each fused block priced at the peak of ITS matrix instruction (split-bf16 forms: band3 = row-band kernel of blocks 3-6,
+        # image_split = whole-image kernel where it won the race, stem_split)
+        fused_ideal_ms = sum(r["flops"] / (fused_peak(r["config"]) * 1e12) * 1e3 for r in fused)
+        fused_split = [r for r in fused if fused_peak(r["config"]) != PEAK_FP32_MFMA_TFLOPS]
+        step_flops = sum(r["flops"] for r in info)           # algorithmic conv FLOPs of the whole step
+        step_tflops = step_flops / (elapsed / args.steps) / 1e12
+        if args.layers and rank == 0:
+            for r in info:
+                sys.stderr.write("%-28s %-8s %-22s %8.4f ms %8.2f GFLOP %7.1f MB  %6.1f TF/s %6.0f GB/s\n" % (
+                    r["name"], r["kind"], r["config"], r["ms"], r["flops"] / 1e9, r["bytes"] / 1e6,
+                    r["flops"] / max(r["ms"], 1e-9) / 1e9, r["bytes"] / max(r["ms"], 1e-9) / 1e6))
 
-    # HBM-side traffic of the family, per launch: PMC counters cannot be read from inside this
-    # process, so the value comes from the committed rocprofv3 --pmc passes of this same command
-    # (profiles/traffic_<backbone>_b<B>.json, written by profiles/collect.sh); null if absent.
-    traffic, traffic_detail = None, None
-    tpath = os.path.join(REPO, "profiles", "traffic_%s_b%d.json" % (args.backbone, B))
-    if os.path.exists(tpath) and hp["img_size"] == 300:
-        try:
-            fams = json.load(open(tpath))["families"]
-            fam_names = [k for k in ("conv_mfma_kernel", "conv_mfma3_kernel", "conv_bf16_kernel", "conv_dma_kernel", "conv_wino_kernel", "conv_skinny_kernel") if k in fams]
-            nl = sum(fams[k]["FETCH_SIZE"]["launches"] for k in fam_names)
-            # launch-weighted mean over the family's kernels (implicit-GEMM + Winograd tiles)
-            fetch = 2.0 * 1024.0 * sum(fams[k]["FETCH_SIZE"]["KB_per_launch_reported"] * fams[k]["FETCH_SIZE"]["launches"]
-                                       for k in fam_names) / nl      # gfx950: x2 for wide reads
-            write = 1024.0 * sum(fams[k]["WRITE_SIZE"]["KB_per_launch_reported"] * fams[k]["WRITE_SIZE"]["launches"]
-                                 for k in fam_names) / sum(fams[k]["WRITE_SIZE"]["launches"] for k in fam_names)
-            traffic = fetch + write
-            tj = json.load(open(tpath))
-            traffic_detail = {"fetch_bytes_per_launch_x2_corrected": fetch, "write_bytes_per_launch": write,
-                              "algorithmic_bytes_per_launch": sum(r["bytes"] for r in mfma) / max(len(mfma), 1),
-                              "source": "profiles/" + os.path.basename(tpath),
-                              "collected_at_commit": tj.get("commit"),
-                              "kernel_sources_sha16": tj.get("kernel_sources_sha16")}
-            # the PMC pass is only evidence for THESE kernels: a kernel-source change since the
-            # collection (profiles/collect.sh) makes the figure stale -> report null
-            if tj.get("kernel_sources_sha16") != kernel_sources_sha16():
-                traffic_detail["stale"] = "kernel sources changed since the PMC pass; re-run profiles/collect.sh"
-                traffic = None
-        except (KeyError, ValueError):
-            pass
+        # HBM-side traffic of the family, per launch: PMC counters cannot be read from inside this
+        # process, so the value comes from the committed rocprofv3 --pmc passes of this same command
+        # (profiles/traffic_<backbone>_b<B>.json, written by profiles/collect.sh); null if absent.
+        traffic, traffic_detail = None, None
+        tpath = os.path.join(REPO, "profiles", "traffic_%s_b%d.json" % (args.backbone, B))
+        if os.path.exists(tpath) and hp["img_size"] == 300:
+            try:
+                fams = json.load(open(tpath))["families"]
+                fam_names = [k for k in ("conv_mfma_kernel", "conv_mfma3_kernel", "conv_bf16_kernel", "conv_dma_kernel", "conv_wino_kernel", "conv_skinny_kernel") if k in fams]
+                nl = sum(fams[k]["FETCH_SIZE"]["launches"] for k in fam_names)
+                # launch-weighted mean over the family's kernels (implicit-GEMM + Winograd tiles)
+                fetch = 2.0 * 1024.0 * sum(fams[k]["FETCH_SIZE"]["KB_per_launch_reported"] * fams[k]["FETCH_SIZE"]["launches"]
+                                           for k in fam_names) / nl      # gfx950: x2 for wide reads
+                write = 1024.0 * sum(fams[k]["WRITE_SIZE"]["KB_per_launch_reported"] * fams[k]["WRITE_SIZE"]["launches"]
+                                     for k in fam_names) / sum(fams[k]["WRITE_SIZE"]["launches"] for k in fam_names)
+                traffic = fetch + write
+                tj = json.load(open(tpath))
+                traffic_detail = {"fetch_bytes_per_launch_x2_corrected": fetch, "write_bytes_per_launch": write,
+                                  "algorithmic_bytes_per_launch": sum(r["bytes"] for r in mfma) / max(len(mfma), 1),
+                                  "source": "profiles/" + os.path.basename(tpath),
+                                  "collected_at_commit": tj.get("commit"),
+                                  "kernel_sources_sha16": tj.get("kernel_sources_sha16")}
+                # the PMC pass is only evidence for THESE kernels: a kernel-source change since the
+                # collection (profiles/collect.sh) makes the figure stale -> report null
+                if tj.get("kernel_sources_sha16") != kernel_sources_sha16():
+                    traffic_detail["stale"] = "kernel sources changed since the PMC pass; re-run profiles/collect.sh"
+                    traffic = None
+            except (KeyError, ValueError):
+                pass
 
     result = {
         "metric": "images/sec SSD%d (%s) fwd+NMS" % (hp["img_size"], "MobileNetV2" if args.backbone == "mobilenet_v2" else "VGG16"),
@@ -421,9 +446,6 @@ def main():
                           "ms_per_step_median": 1e3 * elapsed / args.steps, "ms_per_step_max": 1e3 * max(regions) / args.steps,
                           "images_per_sec_min_median_max": [world * B * args.steps / max(regions), world * B * args.steps / elapsed,
                                                             world * B * args.steps / min(regions)]},
-        # informational: the same K steps in the OTHER launch mode (see --lanes)
-        "other_mode": other,
-        "h2d_overlapped_predict": h2d,
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -445,69 +467,75 @@ def main():
                    # ssd_build_id() of the loaded library recomputed from the checked-out sources (csrc/*.hip|*.h +
                    # include/ssd_hip.h + the compile flags): equal = the library was built from these sources
                    "build_id_from_sources": build_id_from_sources()},
-        "roofline": {"bound": "mfma", "kernel": "conv_mfma3_kernel (implicit-GEMM tiles, every fp32 product as six v_mfma_f32_16x16x32_bf16 of an exact "
-                                                 "3-way operand split; conv_dma_kernel: the same tiles with both operands copied global -> LDS by LDS-DMA from pre-split / bf16 planes) "
-                                                 "+ conv_mfma_kernel / conv_wino_kernel / conv_skinny_kernel (fp32 v_mfma_f32_16x16x4: "
-                                                 "implicit-GEMM, Winograd F(2x2,3x3), in-workgroup-split-K tiles), all configs",
-                     # `achieved` / `frac` count the FLOPs the matrix cores actually ISSUED (Winograd layers: 16
-                     # multiplies per 2x2 output tile instead of 36, whole border tiles) over the hipEvent time of
-                     # the family's launches on their stream: a fraction of the peak, never above 1.  The
-                     # ALGORITHMIC figure (MACs x 2 of the direct convolution) is reported beside
-                     # it as `achieved_algorithmic`; for Winograd layers it is an "effective" rate and may exceed
-                     # the peak.
-                     # `peak` is the family's blended fp32-equivalent peak: each layer's executed FLOPs priced at the
-                     # peak of the instruction it runs on (fp32 MFMA 157.3; split-bf16 = dense bf16 2516.8 / 6 products
-                     # = 419.5), so that achieved / peak == frac == matrix time at peak / measured time.
-                     "achieved": executed, "peak": peak_eff, "unit": "TFLOP/s",
-                     "frac": frac, "frac_kind": "sum(executed FLOPs / peak of the layer's matrix instruction) / measured time",
-                     "peak_detail": {"fp32_mfma": PEAK_FP32_MFMA_TFLOPS, "bf16_mfma_dense": PEAK_BF16_MFMA_TFLOPS,
-                                     "split_bf16_fp32_equivalent": PEAK_SPLIT_BF16_TFLOPS,
-                                     "bf16_layers": len([r for r in mfma if r["config"].startswith(("bf16_", "dmab_"))]),
-                                     "lds_dma_layers": len([r for r in mfma if r["config"].startswith(("dma3_", "dmab_"))]),
-                                     "split_bf16_layers": len(split), "split_bf16_ms_per_step": sum(r["ms"] for r in split),
-                                     "split_bf16_executed_gflop_per_step": sum(r["executed_flops"] for r in split) / 1e9},
-                     "achieved_algorithmic": achieved, "frac_algorithmic_vs_fp32_mfma_peak": achieved / PEAK_FP32_MFMA_TFLOPS,
-                     "winograd_layers": len(wino), "winograd_ms_per_step": sum(r["ms"] for r in wino),
-                     "traffic": traffic, "traffic_detail": traffic_detail,
-                     "launches_per_step": len(mfma), "kernel_ms_per_step": mfma_ms,
-                     "algorithmic_gflop_per_step": mfma_flops / 1e9, "executed_gflop_per_step": mfma_exec / 1e9,
-                     "dominant_kernel": None if dom is None else {
-                         "layer": dom["name"], "config": dom["config"], "ms_per_launch": dom["ms"],
-                         "algorithmic_gflop": dom["flops"] / 1e9, "executed_gflop": dom["executed_flops"] / 1e9,
-                         "achieved": dom["executed_flops"] / (dom["ms"] * 1e-3) / 1e12,
-                         "peak": matrix_peak(dom["config"]),
-                         "frac": dom["executed_flops"] / (dom["ms"] * 1e-3) / 1e12 / matrix_peak(dom["config"]),
-                         "achieved_algorithmic": dom["flops"] / (dom["ms"] * 1e-3) / 1e12},
-                     # the whole step (every kernel, incl. softmax/decode/NMS time) against the same peak, algorithmic FLOPs
-                     "achieved_step": step_tflops, "frac_step_vs_fp32_mfma_peak": step_tflops / PEAK_FP32_MFMA_TFLOPS,
-                     # ... and against the peak of the instruction most of the step's FLOPs now run on (six bf16 MFMAs per product)
-                     "frac_step_vs_split_bf16_peak": step_tflops / PEAK_SPLIT_BF16_TFLOPS,
-                     "frac_step_vs_bf16_peak": step_tflops / PEAK_BF16_MFMA_TFLOPS,
-                     "algorithmic_gflop_per_step_all": step_flops / 1e9},
-        # the other half of the step: whole-block / depthwise+project / stem kernels (MFMA + VALU depthwise)
-        # `frac` = matrix time at peak / measured time with every block priced at the peak of its instruction (the
-        # split-bf16 forms -- row-band kernel of blocks 3-6, whole-image kernel where it won the race, stem -- at 419.5, the fp32-MFMA kernels at 157.3); `peak` is the blend
-        "roofline_fused": {"bound": "mfma", "kernel": "mbv2_stem_kernel + mbv2_band_block_kernel + mbv2_band3_block_kernel + mbv2_image_block_kernel + mbv2_image16_block_kernel + dwproj8_kernel (fused inverted-residual family)",
-                           "achieved": fused_flops / (fused_ms * 1e-3) / 1e12 if fused_ms > 0 else None,
-                           "peak": (fused_flops / (fused_ideal_ms * 1e-3) / 1e12) if fused_ideal_ms > 0 else PEAK_FP32_MFMA_TFLOPS,
-                           "unit": "TFLOP/s",
-                           "frac": (fused_ideal_ms / fused_ms) if fused_ms > 0 else None,
-                           "frac_vs_fp32_mfma_peak": (fused_flops / (fused_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS) if fused_ms > 0 else None,
-                           "split_bf16_blocks": [r["name"] for r in fused_split],
-                           "launches_per_step": len(fused), "kernel_ms_per_step": fused_ms,
-                           "algorithmic_gflop_per_step": fused_flops / 1e9},
-        "gpu_ms_per_step_by_kind": {k: round(v, 4) for k, v in sorted(kinds.items())},
-        "gpu_ms_per_step_sum": total_ms,
     }
+    if args.full:
+        result.update({
+            # informational: the same K steps in the OTHER launch mode (see --lanes)
+            "other_mode": other,
+            "h2d_overlapped_predict": h2d,
+            "roofline": {"bound": "mfma", "kernel": "conv_mfma3_kernel (implicit-GEMM tiles, every fp32 product as six v_mfma_f32_16x16x32_bf16 of an exact "
+                                                     "3-way operand split; conv_dma_kernel: the same tiles with both operands copied global -> LDS by LDS-DMA from pre-split / bf16 planes) "
+                                                     "+ conv_mfma_kernel / conv_wino_kernel / conv_skinny_kernel (fp32 v_mfma_f32_16x16x4: "
+                                                     "implicit-GEMM, Winograd F(2x2,3x3), in-workgroup-split-K tiles), all configs",
+                         # `achieved` / `frac` count the FLOPs the matrix cores actually ISSUED (Winograd layers: 16
+                         # multiplies per 2x2 output tile instead of 36, whole border tiles) over the hipEvent time of
+                         # the family's launches on their stream: a fraction of the peak, never above 1.  The
+                         # ALGORITHMIC figure (MACs x 2 of the direct convolution) is reported beside
+                         # it as `achieved_algorithmic`; for Winograd layers it is an "effective" rate and may exceed
+                         # the peak.
+                         # `peak` is the family's blended fp32-equivalent peak: each layer's executed FLOPs priced at the
+                         # peak of the instruction it runs on (fp32 MFMA 157.3; split-bf16 = dense bf16 2516.8 / 6 products
+                         # = 419.5), so that achieved / peak == frac == matrix time at peak / measured time.
+                         "achieved": executed, "peak": peak_eff, "unit": "TFLOP/s",
+                         "frac": frac, "frac_kind": "sum(executed FLOPs / peak of the layer's matrix instruction) / measured time",
+                         "peak_detail": {"fp32_mfma": PEAK_FP32_MFMA_TFLOPS, "bf16_mfma_dense": PEAK_BF16_MFMA_TFLOPS,
+                                         "split_bf16_fp32_equivalent": PEAK_SPLIT_BF16_TFLOPS,
+                                         "bf16_layers": len([r for r in mfma if r["config"].startswith(("bf16_", "dmab_"))]),
+                                         "lds_dma_layers": len([r for r in mfma if r["config"].startswith(("dma3_", "dmab_"))]),
+                                         "split_bf16_layers": len(split), "split_bf16_ms_per_step": sum(r["ms"] for r in split),
+                                         "split_bf16_executed_gflop_per_step": sum(r["executed_flops"] for r in split) / 1e9},
+                         "achieved_algorithmic": achieved, "frac_algorithmic_vs_fp32_mfma_peak": achieved / PEAK_FP32_MFMA_TFLOPS,
+                         "winograd_layers": len(wino), "winograd_ms_per_step": sum(r["ms"] for r in wino),
+                         "traffic": traffic, "traffic_detail": traffic_detail,
+                         "launches_per_step": len(mfma), "kernel_ms_per_step": mfma_ms,
+                         "algorithmic_gflop_per_step": mfma_flops / 1e9, "executed_gflop_per_step": mfma_exec / 1e9,
+                         "dominant_kernel": None if dom is None else {
+                             "layer": dom["name"], "config": dom["config"], "ms_per_launch": dom["ms"],
+                             "algorithmic_gflop": dom["flops"] / 1e9, "executed_gflop": dom["executed_flops"] / 1e9,
+                             "achieved": dom["executed_flops"] / (dom["ms"] * 1e-3) / 1e12,
+                             "peak": matrix_peak(dom["config"]),
+                             "frac": dom["executed_flops"] / (dom["ms"] * 1e-3) / 1e12 / matrix_peak(dom["config"]),
+                             "achieved_algorithmic": dom["flops"] / (dom["ms"] * 1e-3) / 1e12},
+                         # the whole step (every kernel, incl. softmax/decode/NMS time) against the same peak, algorithmic FLOPs
+                         "achieved_step": step_tflops, "frac_step_vs_fp32_mfma_peak": step_tflops / PEAK_FP32_MFMA_TFLOPS,
+                         # ... and against the peak of the instruction most of the step's FLOPs now run on (six bf16 MFMAs per product)
+                         "frac_step_vs_split_bf16_peak": step_tflops / PEAK_SPLIT_BF16_TFLOPS,
+                         "frac_step_vs_bf16_peak": step_tflops / PEAK_BF16_MFMA_TFLOPS,
+                         "algorithmic_gflop_per_step_all": step_flops / 1e9},
+            # the other half of the step: whole-block / depthwise+project / stem kernels (MFMA + VALU depthwise)
+            # `frac` = matrix time at peak / measured time with every block priced at the peak of its instruction (the
+            # split-bf16 forms -- row-band kernel of blocks 3-6, whole-image kernel where it won the race, stem -- at 419.5, the fp32-MFMA kernels at 157.3); `peak` is the blend
+            "roofline_fused": {"bound": "mfma", "kernel": "mbv2_stem_kernel + mbv2_band_block_kernel + mbv2_band3_block_kernel + mbv2_image_block_kernel + mbv2_image16_block_kernel + dwproj8_kernel (fused inverted-residual family)",
+                               "achieved": fused_flops / (fused_ms * 1e-3) / 1e12 if fused_ms > 0 else None,
+                               "peak": (fused_flops / (fused_ideal_ms * 1e-3) / 1e12) if fused_ideal_ms > 0 else PEAK_FP32_MFMA_TFLOPS,
+                               "unit": "TFLOP/s",
+                               "frac": (fused_ideal_ms / fused_ms) if fused_ms > 0 else None,
+                               "frac_vs_fp32_mfma_peak": (fused_flops / (fused_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS) if fused_ms > 0 else None,
+                               "split_bf16_blocks": [r["name"] for r in fused_split],
+                               "launches_per_step": len(fused), "kernel_ms_per_step": fused_ms,
+                               "algorithmic_gflop_per_step": fused_flops / 1e9},
+            "gpu_ms_per_step_by_kind": {k: round(v, 4) for k, v in sorted(kinds.items())},
+            "gpu_ms_per_step_sum": total_ms,
+        })
 
     if dist is not None:
         result["multi_gpu"] = ranks_report(dist, sorted(local_regions)[len(local_regions) // 2], args.steps)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args.backbone, hp, weights, priors.cpu().numpy(), args.cpu_sample)
     decoder_model.close()
     default_workload = (args.backbone == "mobilenet_v2" and hp["img_size"] == 300 and args.dtype == "f32" and B == 64
                         and not args.opt and not args.no_overlap)
-    if rank == 0 and world == 1 and dist is None and (args.other_configs == "on" or (args.other_configs == "auto" and default_workload)):
+    if args.full and rank == 0 and world == 1 and dist is None and (args.other_configs == "on" or (args.other_configs == "auto" and default_workload)):
         del decoder_model, model, xs, x                   # the sub-runs get the whole device
         torch.cuda.empty_cache()
         result["other_configs"] = other_configs(args)
@@ -536,7 +564,7 @@ def other_configs(args):
     out = []
     for label, extra in OTHER_CONFIGS:
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(steps), "--warmup", "3", "--repeats", "3",
-               "--no-cpu-baseline", "--no-h2d", "--other-configs", "off"] + extra
+               "--full", "--no-cpu-baseline", "--no-h2d", "--other-configs", "off"] + extra
         t0 = time.perf_counter()
         rec = {"workload": label, "args": " ".join(extra)}
         try:
@@ -634,6 +662,8 @@ def train_bench(args, hp, get_model, rank, world, dist):
             e = float(t.item())
         regions.append(e)
     elapsed = sorted(regions)[len(regions) // 2]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loc_loss": loc, "conf_loss": conf})
     last = float((loc + conf).mean().item())
     fwd_gflop = (2.026 if args.backbone == "mobilenet_v2" else 62.747) * B     # conv MACs x 2 per image (forward)
     step_tflops = 3.0 * fwd_gflop * 1e9 / (elapsed / args.steps) / 1e12      # forward + backward-data + backward-weights
@@ -680,7 +710,7 @@ def train_bench(args, hp, get_model, rank, world, dist):
                      "frac_algorithmic_vs_fp32_mfma_peak": step_tflops / PEAK_FP32_MFMA_TFLOPS,
                      "algorithmic_gflop_per_step": 3.0 * fwd_gflop},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the oracle's training step (torch-CPU autograd graph of the identical network in training mode + loss;
         # oracle/train_oracle.py) on the host cores: a bounded sample of the same workload
         import numpy as np
@@ -737,6 +767,14 @@ def emit(result, rank, dist):
         dist.destroy_process_group()
     if rank == 0:
         print(json.dumps(result), flush=True)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy in float32 (labels and counts are small integers: exact)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def kernel_sources_sha16():

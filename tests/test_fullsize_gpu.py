@@ -470,7 +470,7 @@ def test_bench_line_contract(extra, tmp_path):
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SSD_HIP_TUNE_CACHE=str(tmp_path))
     env.pop("GPU_MAX_HW_QUEUES", None)          # (the suite pins the runtime's default in conftest; bench.py chooses its own: one queue per lane)
-    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--steps", "4", "--warmup", "2", "--batch", "8", "--no-cpu-baseline"] + extra
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--steps", "4", "--warmup", "2", "--batch", "8", "--full", "--no-cpu-baseline"] + extra
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -521,6 +521,51 @@ def test_bench_line_contract(extra, tmp_path):
         assert kt["source"] in ("shipped", "cache", "memo", "autotune") and len(kt["table_sha16"]) == 16
     else:
         assert 0 < r["roofline"]["frac"] < 1
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain `bench.py --steps K --warmup W` times exactly K steps in one region and carries none of the --full
+    legs; --dump-outputs writes what its last timed step returned, which is the decoder's result for one of the
+    seeded resident batches, recomputed here."""
+    import json, subprocess, sys
+    from models.decoder import get_decoder_model
+    from models.ssd_mobilenet_v2 import get_model
+    from utils import bbox_utils, data_utils, train_utils
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, SSD_HIP_TUNE_CACHE=str(tmp_path))
+    env.pop("GPU_MAX_HW_QUEUES", None)
+    dump = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--steps", "4", "--warmup", "2", "--batch", "8",
+           "--dump-outputs", str(dump)]
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    r = json.loads(lines[0])
+    assert r["steps"] == 4 and r["warmup"] == 2 and r["timing_spread"]["repeats"] == 1 and r["dtype"] == "f32"
+    assert r["unit"] == "images/sec" and r["higher_is_better"] is True
+    assert abs(r["value"] - 8 / (r["ms_per_step"] * 1e-3)) <= 1e-6 * r["value"]
+    for k in ("roofline", "roofline_fused", "other_mode", "h2d_overlapped_predict", "cpu_baseline", "other_configs"):
+        assert k not in r, k
+    got = {n: np.load(str(dump / (n + ".npy"))) for n in ("boxes", "labels", "scores", "valid_detections")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["boxes"].shape == (8, 200, 4) and got["labels"].shape == got["scores"].shape == (8, 200)
+    assert got["valid_detections"].shape == (8,) and got["valid_detections"].sum() > 0
+
+    hp = dict(train_utils.get_hyper_params("mobilenet_v2"))
+    hp["total_labels"] = 21
+    m = get_model(hp, max_batch=8)
+    data_utils.synthetic_weights(m, seed=1)
+    priors = bbox_utils.generate_prior_boxes(hp["feature_map_shapes"], hp["aspect_ratios"])
+    dm = get_decoder_model(m, priors, hp, lanes=1)
+    matches = 0
+    for k in range(r["config"]["inputs_rotated"]):
+        b, l, s = dm.predict_on_batch(data_utils.synthetic_images(8, 300, seed=1000 * k))
+        v = dm.decoder.last_valid_detections.cpu().numpy()
+        if np.array_equal(l, got["labels"]) and np.array_equal(v, got["valid_detections"]):
+            assert np.abs(b - got["boxes"]).max() <= 1e-5 and np.abs(s - got["scores"]).max() <= 1e-5
+            matches += 1
+    assert matches == 1
 
 
 def test_predict_ascending_batch_sizes():

@@ -92,7 +92,14 @@ def test_host_logic_vs_executed_reference(tmp_path, monkeypatch):
     import copy, json
     from utils import train_utils, io_utils
     g = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "host_logic.json")))
-    pristine = copy.deepcopy(train_utils.SSD)
+    # the table as the module defines it: entry points run earlier in the process (predictor.main / trainer.main set
+    # total_labels on it, like the reference) leave the shared entries mutated
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_train_utils_pristine", train_utils.__file__)
+    fresh = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(fresh)
+    pristine = copy.deepcopy(fresh.SSD)
+    found = copy.deepcopy(train_utils.SSD)
     try:
         for case in g["get_hyper_params"]:
             train_utils.SSD.clear()
@@ -106,7 +113,7 @@ def test_host_logic_vs_executed_reference(tmp_path, monkeypatch):
         assert train_utils.get_hyper_params("mobilenet_v2") == g["sticky_img_size_after_override"]
     finally:
         train_utils.SSD.clear()
-        train_utils.SSD.update(pristine)
+        train_utils.SSD.update(found)
     for e, lr in g["scheduler"]:
         assert train_utils.scheduler(e) == lr, e
     for t, b, n in g["get_step_size"]:
@@ -387,6 +394,18 @@ def test_make_tf_golden_tool_stays_runnable():
     consumer = open(os.path.join(REPO, "tests", "test_tf_golden.py")).read()
     read = set(re.findall(r'_tf\("(tf_[a-z_%]+\.npz)"', consumer))
     assert written == read and len(written) >= 6, (written, read)
+
+
+def test_bench_extra_figures_need_full():
+    """A plain bench run measures only the headline: asking for a figure of the --full legs without --full is an
+    argparse error (before any device work), not a silently missing figure."""
+    import subprocess
+    bench = os.path.join(REPO, "bench.py")
+    r = subprocess.run([sys.executable, bench, "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    for extra in (["--layers"], ["--other-configs", "on"]):
+        r = subprocess.run([sys.executable, bench] + extra, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "need --full" in r.stderr, r.stderr[-500:]
 
 
 def test_shipped_kernel_tables_were_measured_at_this_build():

@@ -5,7 +5,7 @@ OUT=gpurun_out/${TAG:-rep}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for i in $(seq 1 $N); do
-  timeout 600 python bench.py --no-cpu-baseline --no-h2d "$@" > $OUT/b$i.json 2> $OUT/b$i.err
+  timeout 600 python bench.py --full --no-cpu-baseline --no-h2d "$@" > $OUT/b$i.json 2> $OUT/b$i.err
   python - <<PY
 import json
 d=json.loads(open("$OUT/b$i.json").read().strip().splitlines()[-1]); lc=d["config"].get("lane_calibration") or {}

@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 case $WHAT in
   bench)
     n=$(ls "$OUT"/bench_*.json 2>/dev/null | wc -l)
-    python bench.py "$@" > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.err"; tail -3 "$OUT/bench_$n.err"
+    python bench.py --full "$@" > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.err"; tail -3 "$OUT/bench_$n.err"
     python - "$OUT/bench_$n.json" <<'PY'
 import json, sys
 r = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -25,7 +25,7 @@ PY
     ;;
   layers)
     n=$(ls "$OUT"/layers_*.txt 2>/dev/null | wc -l)
-    python bench.py --lanes 1 --no-overlap --no-other-leg --no-h2d --no-cpu-baseline --layers "$@" > "$OUT/layers_$n.json" 2> "$OUT/layers_$n.txt"
+    python bench.py --full --lanes 1 --no-overlap --no-other-leg --no-h2d --no-cpu-baseline --layers "$@" > "$OUT/layers_$n.json" 2> "$OUT/layers_$n.txt"
     cat "$OUT/layers_$n.txt" | tail -90
     ;;
   pytest) ( time timeout 2700 python -m pytest tests -m gpu -q -rA --durations=15 "$@" ) > "$OUT/gputest.log" 2>&1; echo "pytest rc=$?" >> "$OUT/gputest.log"

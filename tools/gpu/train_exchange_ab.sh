@@ -3,7 +3,7 @@
 OUT=gpurun_out/r5i; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 run() { tag=$1; shift
-  env "$@" python bench.py --no-cpu-baseline $BARGS > $OUT/$tag.json 2> $OUT/$tag.err
+  env "$@" python bench.py --full --no-cpu-baseline $BARGS > $OUT/$tag.json 2> $OUT/$tag.err
   python - $OUT/$tag.json $tag <<'PY'
 import json, sys
 try:
