@@ -358,9 +358,6 @@ double ssd_net_layer_executed_flops(const ssd_net* net, int i, int B);
  * the box math stay fp32, activations stay fp32 in HBM; the training step then runs its forward / backward-data convs
  * on the bf16 tiles (fp32 master weights, weight gradients and Adam).  Takes effect at the next finalize. */
 int ssd_net_set_option(ssd_net* net, const char* name, int value);
-/* Diagnostics: per-phase mean cycles per wave of one fused block layer (clock64 inside the
- * kernel): prologue, expand, depthwise, project, weight staging, epilogue. */
-int ssd_net_profile_fused(ssd_net* net, const char* layer, int B, double* cycles_out6);
 /* Live per-layer hipEvent timing of ssd_net_forward / ssd_net_predict on their stream.
  * read_timing sums the durations (ms) of the forwards recorded since the last read into
  * ms_sum_out[num_layers + 1] (last entry: decode+NMS of predict) and reports their count. */

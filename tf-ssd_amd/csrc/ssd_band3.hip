@@ -10,7 +10,6 @@
 //   * project: K = 32 = TWO consecutive 16-channel chunks: the depthwise output of the even chunk waits in registers,
 //     after the odd chunk the lane's 8 values are split and 6 x NT MFMAs run (k-slot (g4, j): j < 4 -> even chunk channel
 //     g4*4 + j, j >= 4 -> odd chunk; the pre-split project weights are packed in that order, split3_wp_kernel)
-#include <cstdlib>
 
 #include "ssd_bf16x3.h"
 #include "ssd_conv.h"
@@ -336,7 +335,6 @@ struct Band3Cfg {
 };
 #define B3CFG(CIN, NT, T, TO, S, P) {CIN, NT, T, TO, S, P, mbv2_band3_block_kernel<CIN, NT, T, TO, S, P, 3>, mbv2_band3_block_kernel<CIN, NT, T, TO, S, P, 1>, \
                                      mbv2_band3_block_kernel<CIN, NT, T, TO, S, P, 3, true>, mbv2_band3_block_kernel<CIN, NT, T, TO, S, P, 1, true>}
-#define B3DCFG(CIN, NT, T, TO, S, P) {CIN, NT, T, TO, S, P, nullptr, nullptr, mbv2_band3_block_kernel<CIN, NT, T, TO, S, P, 3, true>, nullptr}
 #define B1CFG(CIN, NT, T, TO, S, P) {CIN, NT, T, TO, S, P, nullptr, mbv2_band3_block_kernel<CIN, NT, T, TO, S, P, 1>, nullptr, mbv2_band3_block_kernel<CIN, NT, T, TO, S, P, 1, true>}
 const Band3Cfg kBand3[] = {
     B1CFG(16, 2, 9, 2, 2, 152),   // bf16 form only: block 1 (16 -> 96 -> 24, 150x150 -> 75x75) and block 2 (75x75), the
@@ -344,11 +342,6 @@ const Band3Cfg kBand3[] = {
     B1CFG(24, 2, 8, 6, 1, 136),   // block 2 of the 512x512 graph
     // blocks 1-2 (Cin 16 / 24, T = 9 / 6 tiles per wave) stay on the fp32 band kernel: the three split X planes cost
     // 12 registers per tile, the kernel spilled (9 / 46 registers) and measured 149-158 / 162-172 us against 143 / 105
-    // round 6: with the weight fragments in LDS the split form of blocks 1-2 fits (second form only; block 1 with 8 tile slots per
-    // wave = 2 output rows per band, so that E + the weight stages stay below 160 KB)
-    B3DCFG(16, 2, 8, 2, 2, 152),
-    B3DCFG(24, 2, 7, 5, 1, 80),
-    B3DCFG(24, 2, 6, 4, 1, 80),
     B3CFG(24, 2, 7, 2, 2, 80),    // block 3
     B3CFG(32, 2, 4, 4, 1, 40),    // blocks 4-5
     B3CFG(32, 4, 4, 1, 2, 40),    // block 6
@@ -365,9 +358,7 @@ int band3_max_rows(const Band3Cfg& c, const FusedBlockParams& p) {
     return r;
 }
 
-size_t band3_lds_bytes(const Band3Cfg& c, const FusedBlockParams& p);
 const Band3Cfg* pick_band3(const FusedBlockParams& p, bool bf16) {
-    static const int split12 = getenv("SSD_BAND3_SPLIT12") ? atoi(getenv("SSD_BAND3_SPLIT12")) : 0;   // blocks 1-2 on the split form (experiment; 2: block 2's smaller band)
     if (p.Ce % kB3C != 0 || p.Cout % 8 != 0 || p.Cin > 32) return nullptr;
     if (p.stride == 1 && (p.H != p.Ho || p.W != p.Wo || p.pad_t != 1 || p.pad_l != 1)) return nullptr;
     if (p.stride == 2 && (p.residual || p.Ho != (p.H + 1) / 2 || p.Wo != (p.W + 1) / 2 || p.pad_t > 1 || p.pad_l > 1 ||
@@ -377,9 +368,7 @@ const Band3Cfg* pick_band3(const FusedBlockParams& p, bool bf16) {
     if (p.e_out) return nullptr;
     for (const auto& c : kBand3) {
         if (c.cin != p.Cin || c.stride != p.stride || (p.Cout + 15) / 16 != c.nt || p.npad_p < c.nt * 16) continue;
-        if (bf16 ? !c.fn1 : !(c.fn || (split12 && p.form2 && c.fn_d))) continue;
-        if (!bf16 && !c.fn && split12 == 2 && c.cin == 24 && c.t == 7) continue;
-        if (!bf16 && !c.fn && band3_lds_bytes(c, p) + (size_t)3 * (2 + c.nt) * 1024 > 160 * 1024) continue;
+        if (bf16 ? !c.fn1 : !c.fn) continue;
         if (p.W + 1 > c.pitch || p.W + 8 < c.pitch) continue;
         if (p.stride == 2 && 2 * (p.Wo - 1) - p.pad_l + 2 >= c.pitch) continue;
         if (band3_max_rows(c, p) < 1) continue;

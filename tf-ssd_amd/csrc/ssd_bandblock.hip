@@ -27,7 +27,6 @@
 //
 // Only the two (stride 1) or one (stride 2) halo rows between bands are expanded twice (1.2-1.3x of the
 // expand, nothing of the depthwise / project) where the 8x8 tiles of ssd_fused.hip recompute 1.56x.
-#include <cstdlib>
 
 #include "ssd_conv.h"
 
@@ -51,7 +50,7 @@ constexpr int band_ne(int T) { return 8 + T * 8 * 16; }
 // and Wp rows; 1 KB blocks of 16 rows x 16 floats, quad-swizzled through the per-lane source offset) instead of waiting in
 // registers one chunk ahead
 typedef __attribute__((address_space(3))) void* band_lds_dst_t;
-template <int CIN, int NT, int T, int TO, int S, int P, bool DBG, bool WDMA>
+template <int CIN, int NT, int T, int TO, int S, int P, bool WDMA>
 __device__ __forceinline__ void band_body(const FusedBlockParams& p, char* __restrict__ smem) {
     static_assert(P % 8 == 0, "the dy tap offsets must keep the quad swizzle");
     constexpr int KC = CIN / 16;                  // 16-wide k blocks of the expand
@@ -80,12 +79,6 @@ __device__ __forceinline__ void band_body(const FusedBlockParams& p, char* __res
     // tiles are dealt round-robin: tile = t * 8 + wave; this wave's counts
     const int nti = npt > wave ? (npt - wave + 7) >> 3 : 0;
     const int nto = npo > wave ? (npo - wave + 7) >> 3 : 0;
-
-    // diagnostics (ssd_net_profile_fused): per-wave cycles of 0 prologue, 1 barrier wait, 2 depthwise,
-    // 3 project, 4 expand, 5 epilogue
-    long long tacc[6] = {0, 0, 0, 0, 0, 0};
-    long long tk0 = DBG ? clock64() : 0;
-#define BTICK(i) do { if (DBG) { const long long t1_ = clock64(); tacc[i] += t1_ - tk0; tk0 = t1_; } } while (0)
 
     // ---- per-channel parameters -> LDS; leading zero rows of both E buffers
     for (int u = tid; u < 11 * (Ce / 4); u += kBThreads) {
@@ -197,20 +190,18 @@ __device__ __forceinline__ void band_body(const FusedBlockParams& p, char* __res
             if (t0 >= nti) break;                 // scalar
             f32x4 acc0 = sh, acc1 = sh;
             const bool two = t0 + 1 < T;
-            if (!(DBG && (p.ablate & 1))) {
 #pragma unroll
-                for (int kc = 0; kc < KC; ++kc)
+            for (int kc = 0; kc < KC; ++kc)
 #pragma unroll
-                    for (int s = 0; s < 4; ++s) {
-                        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kc][s], xb[t0][kc][s], acc0, 0, 0, 0);
-                        if (two) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kc][s], xb[t0 + 1 < T ? t0 + 1 : t0][kc][s], acc1, 0, 0, 0);
-                    }
-                if (TAIL) {
+                for (int s = 0; s < 4; ++s) {
+                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kc][s], xb[t0][kc][s], acc0, 0, 0, 0);
+                    if (two) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kc][s], xb[t0 + 1 < T ? t0 + 1 : t0][kc][s], acc1, 0, 0, 0);
+                }
+            if (TAIL) {
 #pragma unroll
-                    for (int s = 0; s < 2; ++s) {
-                        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(at[s], xt[t0][s], acc0, 0, 0, 0);
-                        if (two) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(at[s], xt[t0 + 1 < T ? t0 + 1 : t0][s], acc1, 0, 0, 0);
-                    }
+                for (int s = 0; s < 2; ++s) {
+                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(at[s], xt[t0][s], acc0, 0, 0, 0);
+                    if (two) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(at[s], xt[t0 + 1 < T ? t0 + 1 : t0][s], acc1, 0, 0, 0);
                 }
             }
             const float hi0 = (realm >> t0) & 1u ? 6.0f : 0.0f;           // relu6 at real pixels, 0 at pad positions
@@ -247,23 +238,18 @@ __device__ __forceinline__ void band_body(const FusedBlockParams& p, char* __res
         for (int t = 0; t < TO; ++t) {
             if (t >= nto) break;                  // scalar
             f32x4 d = dh;
-            if (!(DBG && (p.ablate & 2))) {
 #pragma unroll
-                for (int dy = 0; dy < 3; ++dy)
+            for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
-                    for (int dx = 0; dx < 3; ++dx)
-                        d += *reinterpret_cast<const f32x4*>(eb + ea[t][dx] + dy * P * 64) * w[dy * 3 + dx];
-            }
+                for (int dx = 0; dx < 3; ++dx)
+                    d += *reinterpret_cast<const f32x4*>(eb + ea[t][dx] + dy * P * 64) * w[dy * 3 + dx];
 #pragma unroll
             for (int e = 0; e < 4; ++e) d[e] = __builtin_amdgcn_fmed3f(d[e], 0.0f, 6.0f);
-            BTICK(2);
-            if (!(DBG && (p.ablate & 4)))
 #pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4)
+            for (int s4 = 0; s4 < 4; ++s4)
 #pragma unroll
-                    for (int ni = 0; ni < NT; ++ni)
-                        acc[t][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(wpc[ni][s4], d[s4], acc[t][ni], 0, 0, 0);
-            BTICK(3);
+                for (int ni = 0; ni < NT; ++ni)
+                    acc[t][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(wpc[ni][s4], d[s4], acc[t][ni], 0, 0, 0);
         }
     };
 
@@ -273,11 +259,9 @@ __device__ __forceinline__ void band_body(const FusedBlockParams& p, char* __res
     if constexpr (WDMA) {
         load_we(wa, wat, 0);
         expand(0, wa, wat);
-        BTICK(0);
         for (int i = 0; i < nchunk; ++i) {
             dma_wait();                 // the copies of an iteration ago have landed ...
             band_lds_barrier();         // ... and are visible; E(i) is complete; everyone is done reading E(i - 1)
-            BTICK(1);
             if (i + 2 < nchunk) dma_we(i + 2, i & 1);           // the stage expand(i) read before this barrier
             if (i + 1 < nchunk) dma_wp(i + 1, (i + 1) & 1);     // the stage dwproject(i - 1) read before this barrier
             load_wp(wp, i);
@@ -286,15 +270,12 @@ __device__ __forceinline__ void band_body(const FusedBlockParams& p, char* __res
                 load_we(wa, wat, i + 1);
                 expand(i + 1, wa, wat);
             }
-            BTICK(4);
         }
     } else {
     expand(0, wa, wat);
     if (nchunk > 1) load_we(wan, watn, 1);
-    BTICK(0);
     for (int i = 0; i < nchunk; ++i) {
         band_lds_barrier();         // E(i) is complete; everyone is done reading E(i - 1)
-        BTICK(1);
         if (i + 1 < nchunk) load_wp(wpn, i + 1);      // in flight across the depthwise / project
         dwproject(i, wp);
         if (i + 1 < nchunk) {
@@ -303,7 +284,6 @@ __device__ __forceinline__ void band_body(const FusedBlockParams& p, char* __res
 #pragma unroll
             for (int ni = 0; ni < NT; ++ni) wp[ni] = wpn[ni];
         }
-        BTICK(4);
     }
 
     }
@@ -323,26 +303,22 @@ __device__ __forceinline__ void band_body(const FusedBlockParams& p, char* __res
             *reinterpret_cast<f32x4*>(yp + ni * 16) = v;
         }
     }
-    BTICK(5);
-    if (DBG && p.dbg && lane == 0)
-        for (int i_ = 0; i_ < 6; ++i_) p.dbg[((long)blockIdx.x * 8 + wave) * 6 + i_] = tacc[i_];
-#undef BTICK
 }
 
-template <int CIN, int NT, int T, int TO, int S, int P, bool DBG, bool WDMA = false>
+template <int CIN, int NT, int T, int TO, int S, int P, bool WDMA>
 __global__ __launch_bounds__(kBThreads) void mbv2_band_block_kernel(const FusedBlockParams p) {
     extern __shared__ __attribute__((aligned(1024))) char smem_band[];
-    band_body<CIN, NT, T, TO, S, P, DBG, WDMA>(p, smem_band);
+    band_body<CIN, NT, T, TO, S, P, WDMA>(p, smem_band);
 }
 
 typedef void (*band_kernel_t)(const FusedBlockParams);
 struct BandCfg {
     int cin, nt, t, to, stride, pitch;
-    band_kernel_t fn, fn_dbg;       // fn_dbg: cycle counters + phase ablation (ssd_net_profile_fused)
+    band_kernel_t fn;
     band_kernel_t fn_d;             // weights staged by LDS-DMA (FusedBlockParams.form2)
 };
-#define BCFG(CIN, NT, T, TO, S, P) {CIN, NT, T, TO, S, P, mbv2_band_block_kernel<CIN, NT, T, TO, S, P, false>, mbv2_band_block_kernel<CIN, NT, T, TO, S, P, true>, \
-                                    mbv2_band_block_kernel<CIN, NT, T, TO, S, P, false, true>}
+#define BCFG(CIN, NT, T, TO, S, P) {CIN, NT, T, TO, S, P, mbv2_band_block_kernel<CIN, NT, T, TO, S, P, false>, \
+                                    mbv2_band_block_kernel<CIN, NT, T, TO, S, P, true>}
 const BandCfg kBand[] = {
     BCFG(16, 2, 9, 2, 2, 152),   // block 1: 16 -> 96 -> 24, 150x150 -> 75x75
     BCFG(24, 2, 8, 6, 1, 80),    // block 2: 24 -> 144 -> 24 (+x) at 75x75
@@ -403,18 +379,16 @@ int launch_band_block(FusedBlockParams p, hipStream_t st) {
         return SSD_E_UNSUPPORTED;
     }
     if (p.B == 0) return SSD_OK;
-    static const int ablate = getenv("SSD_BAND_ABLATE") ? atoi(getenv("SSD_BAND_ABLATE")) : 0;
-    if (!p.ablate) p.ablate = ablate;
     const int rmax = band_max_rows(*c, p);
     p.bands = (p.Ho + rmax - 1) / rmax;          // band b = output rows [b * Ho / bands, (b + 1) * Ho / bands)
     const size_t lds = band_lds_bytes(*c, p);
     SSD_UNSUPPORTED_IF(lds > 160 * 1024, "band block: needs %zu B of LDS", lds);
     if (lds > 64 * 1024)
         SSD_HIP(hipFuncSetAttribute((const void*)c->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    band_kernel_t fn = (p.dbg || p.ablate) ? c->fn_dbg : c->fn;
+    band_kernel_t fn = c->fn;
     size_t lds_use = lds;
     const size_t lds_d = lds + (size_t)2 * (c->cin / 16 + ((c->cin % 16) == 8 ? 1 : 0) + c->nt) * 1024;     // + two stages of We and Wp blocks
-    if (p.form2 && fn == c->fn && lds_d <= 160 * 1024) {
+    if (p.form2 && lds_d <= 160 * 1024) {
         fn = c->fn_d;
         lds_use = lds_d;
     }

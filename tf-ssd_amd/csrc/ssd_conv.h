@@ -79,8 +79,6 @@ struct FusedBlockParams {
     long e_plane;
     int planes_np;
     int form2;                  // whole-image kernel: 1 = take the second form (csrc/ssd_imgblock2.hip) where it has a configuration
-    long long* dbg;             // optional per-phase cycle counters [blocks][8] (profiling builds)
-    int ablate;                 // diagnostics: 1 skip expand MFMAs, 2 skip depthwise math, 4 skip project MFMAs, 8 skip expand epilogue math
 };
 // Fused MobileNetV2 stem (Conv1 -> expanded_conv_depthwise -> expanded_conv_project).
 struct StemParams {
@@ -94,7 +92,6 @@ struct StemParams {
     const float *sp, *hp;       // folded project BN [16]
     int B, H, W, H1, W1, pad_t, pad_l, kpad1, kpadp;
     int tiles_y, tiles_x;
-    int ablate;                 // diagnostics (SSD_STEM_ABLATE): 1 skip Conv1 math, 2 depthwise, 4 project MFMAs, 8 patch loads
     int bf16;                   // the net's precision: 1 = Conv1 / project operands rounded once to bf16
 };
 // Depthwise 3x3 + BN + ReLU6 -> project 1x1 + BN (+ residual) of one MobileNetV2 block
@@ -110,7 +107,6 @@ struct DwProjParams {
     int B, H, W, Ce, Cout, Ho, Wo, stride, pad_t, pad_l;
     int kpad_p, npad_p;
     int tiles_y, tiles_x;       // filled by the launcher
-    int ablate;                 // diagnostics (SSD_DWPROJ_ABLATE): 1 skip depthwise math, 2 skip MFMAs, 4 skip chunk loads
     int bf16;                   // the net's precision-1 mode: project on the bf16 matrix cores (operands rounded once, fp32 accumulation)
 };
 bool dwproj_supported(const DwProjParams& p);
@@ -134,7 +130,6 @@ bool image_block_split_fits(FusedBlockParams p);     // the split-bf16 form's LD
 int image_block_groups(const FusedBlockParams& p, int B);
 size_t image_block_slab_floats(const FusedBlockParams& p, int B);
 int launch_image_block(FusedBlockParams p, hipStream_t st);
-int stem_form(int precision);        // 0 fp32-MFMA, 3 split-bf16 (fp32 results), 1 bf16 operands
 
 inline int round_up(int v, int a) { return (v + a - 1) / a * a; }
 inline int conv_kpad(int K) { return round_up(K, 32); }

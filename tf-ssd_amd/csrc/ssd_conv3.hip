@@ -55,9 +55,6 @@ const Conv3Cfg kCfg3[] = {
 };
 constexpr int kNumCfg3 = sizeof(kCfg3) / sizeof(kCfg3[0]);
 int c3_lds_bytes(const Conv3Cfg& g, int planes) {
-#if SSD_C3_VARIANT & 2
-    if (g.threads == 256) return planes * (g.BM + g.BN) * 64;       // experiment: one LDS stage for the 4-wave tiles
-#endif
     return 2 * planes * (g.BM + g.BN) * 64;
 }
 

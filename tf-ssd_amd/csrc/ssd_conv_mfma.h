@@ -121,14 +121,6 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x4 (&acc)[
     }
 }
 
-// Diagnostic builds only (tests/micro/conv_ablate.py): -DSSD_CONV_ABLATE=bits removes one phase
-// of the main loop -- 1 global loads, 2 LDS stores, 4 MFMAs (+ fragment reads), 8 barriers,
-// 16 MFMAs only (fragment reads kept),
-// 64 LDS-only raw barrier.  0 = the production kernel.
-#ifndef SSD_CONV_ABLATE
-#define SSD_CONV_ABLATE 0
-#endif
-
 template <int MT, int NT, int WM, int WN, int BK, bool GEMM1X1, int NP>
 __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* __restrict__ smem) {
     // NP: 0 = fp32 MFMA tiles; 3 = split-bf16 tiles (exact three-way split, six bf16 MFMAs per product, fp32 results);
@@ -285,7 +277,6 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* __res
         0x00020000);
     f32x4 xr[XP], wr[WP];
     auto load_tile = [&]() {                   // the tile described by the l_* state
-        if (SSD_CONV_ABLATE & 1) return;
 #pragma unroll
         for (int ps = 0; ps < XP; ++ps) {
             if (GEMM1X1) {
@@ -302,13 +293,6 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* __res
             // the last tile) re-reads the first half, 128 bytes back (finite values; the matching
             // X columns are zero) instead of running past the row / the buffer
             const int koff = (BK <= 32 || l_k0 + kq4 < p.Kpad) ? l_k0 * 4 : -128;
-            if (GEMM1X1 && (SSD_CONV_ABLATE & 256)) {
-                const int u = tid + ps * NTHR;
-                const int n = n0 + u / UPR;
-                wr[ps] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (u < WU && n < p.Npad && l_k0 + kq4 < p.Kpad)
-                    wr[ps] = *reinterpret_cast<const f32x4*>(p.w + (long)n * p.Kpad + l_k0 + kq4);
-            } else
             wr[ps] = *reinterpret_cast<const f32x4*>(wbase + (unsigned)(woff[ps] + koff));
         }
     };
@@ -317,7 +301,6 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* __res
     const int st_row0 = tid / UPR;
     const int st_col = SWZ ? ((((kq4 >> 2) ^ (BK == 32 ? (st_row0 >> 1) & 7 : st_row0 & 15)) << 2)) : kq4;
     auto store_tile = [&](int stage) {
-        if (SSD_CONV_ABLATE & 2) return;
         float* Xs = smem + stage * STAGE_FLOATS;
         float* Ws = Xs + BM * LDK;
 #pragma unroll
@@ -347,21 +330,6 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* __res
 #pragma unroll
     for (int kc = 0; kc < BK / 16; ++kc)
         fcol[kc] = SWZ ? (((kc * 4 + (lane >> 4)) ^ (BK == 32 ? (frow >> 1) & 7 : frow)) << 2) : kc * 16 + fk;
-#ifdef SSD_C3_PROF
-    long long c3tp[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    long long c3t0 = clock64();
-#endif
-#ifndef SSD_C3_VARIANT
-#define SSD_C3_VARIANT 0      // experiments (tools/gpu/build_c3var.sh + tests/micro/conv3_variants.py); 0 = the production kernel
-#endif
-#ifdef SSD_C3_PROF            // diagnostics (tests/micro/conv3_prof.py): per-wave cycles of the loop's phases, dumped by one workgroup
-#define C3T(i) do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const long long t_ = clock64(); c3tp[i] += t_ - c3t0; c3t0 = t_; } while (0)
-#else
-#define C3T(i) do {} while (0)
-#endif
-#ifndef SSD_C3_ABLATE
-#define SSD_C3_ABLATE 0       // diagnostics (tests/micro/conv3_ablate.py): 1 no MFMA, 2 no fragment reads, 4 no split, 8 no global loads, 16 no LDS stores
-#endif
     if constexpr (SPLIT3) {
         // ---- split-bf16 main loop (same two-stage pipeline; a deeper global prefetch measured slower: the loop is
         // bound by the L2 -> CU bytes per tile, hence the 8-wave 256-row tiles, not by load latency)
@@ -370,7 +338,6 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* __res
         unsigned vm0 = 0;
         auto load3 = [&](f32x4 (&X)[XP], bf16x8 (&W)[WP3], unsigned& vm) {      // the tile described by the l_* state
             vm = 0;
-            if (SSD_C3_ABLATE & 8) return;
 #pragma unroll
             for (int ps = 0; ps < XP; ++ps) {
                 const bool ok = x_is_valid(ps);
@@ -393,33 +360,6 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* __res
         auto store3 = [&](int stage, const f32x4 (&X)[XP], const bf16x8 (&W)[WP3], const unsigned vm) {
             char* Xs = reinterpret_cast<char*>(smem + stage * STAGE_FLOATS);
             char* Ws = Xs + NP * BM * 64;
-#ifdef SSD_C3_PROF
-            if constexpr (NP == 3 && XU % NTHR == 0 && WU3 % NTHR == 0) {      // phases timed apart: load wait / split / store issue / drain
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                C3T(5);
-                uint2 hh[XP], mm[XP], ll[XP];
-#pragma unroll
-                for (int ps = 0; ps < XP; ++ps) {
-                    const f32x4 v = (GEMM1X1 || BUFZ || ((vm >> ps) & 1u)) ? X[ps] : f32x4{0.f, 0.f, 0.f, 0.f};
-                    split4(v, hh[ps], mm[ps], ll[ps]);
-                    asm volatile("" : "+v"(hh[ps]), "+v"(mm[ps]), "+v"(ll[ps]));
-                }
-                C3T(6);
-#pragma unroll
-                for (int ps = 0; ps < XP; ++ps) {
-                    char* d = Xs + ((tid + ps * NTHR) / UPR) * 64 + xcol;
-                    *reinterpret_cast<uint2*>(d) = hh[ps];
-                    *reinterpret_cast<uint2*>(d + BM * 64) = mm[ps];
-                    *reinterpret_cast<uint2*>(d + 2 * BM * 64) = ll[ps];
-                }
-#pragma unroll
-                for (int ps = 0; ps < WP3; ++ps) *reinterpret_cast<bf16x8*>(Ws + w3dst[ps]) = W[ps];
-                asm volatile("" ::: "memory");
-                { const long long t_ = clock64(); c3tp[7] += t_ - c3t0; c3t0 = t_; }      // issue only (no lgkmcnt wait)
-                C3T(8);                                                                  // drain
-                return;
-            }
-#endif
 #pragma unroll
             for (int ps = 0; ps < XP; ++ps) {
                 const int u = tid + ps * NTHR;
@@ -431,27 +371,18 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* __res
                         continue;
                     }
                     uint2 h, m, l;
-                    if (SSD_C3_ABLATE & 4) {
-                        h = make_uint2(__float_as_uint(v[0]), __float_as_uint(v[1]));
-                        m = make_uint2(__float_as_uint(v[2]), __float_as_uint(v[3]));
-                        l = h;
-                    } else
                     split4(v, h, m, l);
-                    if (SSD_C3_ABLATE & 16) { asm volatile("" ::"v"(h), "v"(m), "v"(l)); continue; }
                     *reinterpret_cast<uint2*>(d) = h;
                     *reinterpret_cast<uint2*>(d + BM * 64) = m;
                     *reinterpret_cast<uint2*>(d + 2 * BM * 64) = l;
                 }
             }
 #pragma unroll
-            for (int ps = 0; ps < WP3; ++ps) {
-                if (SSD_C3_ABLATE & 16) { asm volatile("" ::"v"(W[ps])); continue; }
+            for (int ps = 0; ps < WP3; ++ps)
                 if (WU3 % NTHR == 0 || tid + ps * NTHR < WU3) *reinterpret_cast<bf16x8*>(Ws + w3dst[ps]) = W[ps];
-            }
         };
         const int fq = ((lane >> 4) ^ ((frow >> 1) & 3)) << 4;
         auto mma_tile = [&](int stage) {
-            if (SSD_C3_ABLATE & 2) return;
             const char* Xb = reinterpret_cast<const char*>(smem + stage * STAGE_FLOATS);
             const char* Wb = Xb + NP * BM * 64;
             BP<NP> b[MT];
@@ -461,44 +392,12 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* __res
 #pragma unroll
                 for (int pl = 0; pl < NP; ++pl) b[mi].p[pl] = *reinterpret_cast<const bf16x8*>(r + pl * BM * 64);
             }
-#if SSD_C3_VARIANT & 1
-            // variant 1: two weight fragments at a time -> 2 * MT independent accumulator chains per product term (the
-            // per-accumulator order of the six terms is unchanged: same bits)
-            constexpr int NT2 = (NP == 3) ? (NT & ~1) : 0;
 #pragma unroll
-            for (int ni = 0; ni < NT2; ni += 2) {
-                const char* r0 = Wb + ((wn * NT + ni) * 16 + frow) * 64 + fq;
-                BP<NP> a0, a1;
-#pragma unroll
-                for (int pl = 0; pl < NP; ++pl) {
-                    a0.p[pl] = *reinterpret_cast<const bf16x8*>(r0 + pl * BN * 64);
-                    a1.p[pl] = *reinterpret_cast<const bf16x8*>(r0 + 16 * 64 + pl * BN * 64);
-                }
-                constexpr int TW[6] = {1, 0, 2, 0, 1, 0}, TX[6] = {1, 2, 0, 1, 0, 0};
-#pragma unroll
-                for (int t = 0; t < 6; ++t)
-#pragma unroll
-                    for (int mi = 0; mi < MT; ++mi) {
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0.p[TW[t]], b[mi].p[TX[t]], acc[mi][ni], 0, 0, 0);
-                        acc[mi][ni + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1.p[TW[t]], b[mi].p[TX[t]], acc[mi][ni + 1], 0, 0, 0);
-                    }
-            }
-#else
-            constexpr int NT2 = 0;
-#endif
-#pragma unroll
-            for (int ni = NT2; ni < NT; ++ni) {
+            for (int ni = 0; ni < NT; ++ni) {
                 const char* r = Wb + ((wn * NT + ni) * 16 + frow) * 64 + fq;
                 BP<NP> a;
 #pragma unroll
                 for (int pl = 0; pl < NP; ++pl) a.p[pl] = *reinterpret_cast<const bf16x8*>(r + pl * BN * 64);
-                if (SSD_C3_ABLATE & 1) {
-#pragma unroll
-                    for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-                        for (int pl = 0; pl < NP; ++pl) asm volatile("" ::"v"(a.p[pl]), "v"(b[mi].p[pl]));
-                    continue;
-                }
                 // (issuing the six products term by term across the MT accumulators measured no faster than the chains)
 #pragma unroll
                 for (int mi = 0; mi < MT; ++mi) acc[mi][ni] = mmaN<NP>(a, b[mi], acc[mi][ni]);
@@ -523,91 +422,18 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* __res
                 load3(xs0, ws0, vm0);
             }
         }
-#if SSD_C3_VARIANT & 8
-        // variant 8: the PIXELS (streamed from HBM / the Infinity Cache: the long latency) are fetched TWO K tiles ahead into
-        // two register sets, the weight planes (L2-resident) stay one tile ahead.  Set A holds tile kt + 1 and set B tile
-        // kt + 2 when an even iteration starts; the loop is unrolled by two so that both sets are named statically.
-        {
-            f32x4 xsB[XP];
-            unsigned vmB = 0;
-            auto loadX = [&](f32x4 (&X)[XP], unsigned& vm) {
-                vm = 0;
-#pragma unroll
-                for (int ps = 0; ps < XP; ++ps) {
-                    const bool ok = x_is_valid(ps);
-                    vm |= (ok ? 1u : 0u) << ps;
-                    if (GEMM1X1) {
-                        X[ps] = f32x4{0.f, 0.f, 0.f, 0.f};
-                        if (ok) X[ps] = *reinterpret_cast<const f32x4*>(xrow1[ps] + l_k0);
-                    } else {
-                        X[ps] = *reinterpret_cast<const f32x4*>(xbase + (unsigned)(ok ? xoff[ps] + l_xtile : 0));
-                    }
-                }
-            };
-            auto loadW = [&](bf16x8 (&W)[WP3], int k0) {
-#pragma unroll
-                for (int ps = 0; ps < WP3; ++ps) W[ps] = *reinterpret_cast<const bf16x8*>(w3base + w3off[ps] + (long)k0 * p.Npad);
-            };
-            // state here: tile kt_begin stored in stage 0; (xs0, ws0) hold tile kt_begin + 1 (if any), l_* describe it
-            int k0_next = l_k0;                          // k offset of the tile whose WEIGHTS are loaded next (tile kt + 2)
-            if (kt_begin + 2 < kt_end) {
-                tile_advance();
-                k0_next = l_k0;
-                loadX(xsB, vmB);                         // pixels of tile kt_begin + 2
-            }
-            __syncthreads();
-            auto step = [&](int kt, f32x4 (&XA)[XP], unsigned& vmA) {      // XA holds tile kt + 1; refilled with tile kt + 3
-                const int stage = (kt - kt_begin) & 1;
-                if (!late) mma_tile(stage);
-                if (kt + 1 < kt_end) store3(stage ^ 1, XA, ws0, vmA);
-                if (kt + 2 < kt_end) loadW(ws0, k0_next);                  // weights of tile kt + 2
-                if (kt + 3 < kt_end) {
-                    tile_advance();
-                    k0_next = l_k0;
-                    loadX(XA, vmA);                                        // pixels of tile kt + 3
-                }
-                if (late) mma_tile(stage);
-                __syncthreads();
-            };
-            for (int kt = kt_begin; kt < kt_end; kt += 2) {
-                step(kt, xs0, vm0);
-                if (kt + 1 < kt_end) step(kt + 1, xsB, vmB);
-            }
-        }
-        if (false)
-#else
         __syncthreads();
-#endif
-#if SSD_C3_VARIANT & 2
-        // variant 2 (4-wave tiles): ONE LDS stage, two barriers per K tile -- half the LDS, so two or three workgroups
-        // share a CU and fill each other's barrier / staging phases (instead of the in-workgroup double buffer)
-        if constexpr (NTHR == 256) {
-            for (int kt = kt_begin; kt < kt_end; ++kt) {
-                mma_tile(0);
-                __syncthreads();
-                if (kt + 1 < kt_end) store3(0, xs0, ws0, vm0);
-                if (kt + 2 < kt_end) {
-                    tile_advance();
-                    load3(xs0, ws0, vm0);
-                }
-                __syncthreads();
-            }
-        } else
-#endif
         for (int kt = kt_begin; kt < kt_end; ++kt) {
             const int stage = (kt - kt_begin) & 1;
-            if (!late && !mid) { mma_tile(stage); C3T(0); }
+            if (!late && !mid) mma_tile(stage);
             if (kt + 1 < kt_end) store3(stage ^ 1, xs0, ws0, vm0);
-            C3T(1);
             if (NTHR >= 768 && mid) mma_tile(stage);
             if (kt + 2 < kt_end) {
                 tile_advance();
                 load3(xs0, ws0, vm0);          // in flight across the barrier and the next tile's MFMAs
             }
-            C3T(2);
-            if (late) { mma_tile(stage); C3T(3); }
+            if (late) mma_tile(stage);
             __syncthreads();
-            C3T(4);
         }
     } else {
     if (kt_begin < kt_end) {
@@ -625,9 +451,8 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* __res
             tile_advance();
             load_tile();
         }
-        {
 #pragma unroll
-        for (int kc = 0; kc < ((SSD_CONV_ABLATE & 4) ? 0 : BK / 16); ++kc) {
+        for (int kc = 0; kc < BK / 16; ++kc) {
             f32x4 a[NT], b[MT];
 #pragma unroll
             for (int ni = 0; ni < NT; ++ni)
@@ -635,13 +460,6 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* __res
 #pragma unroll
             for (int mi = 0; mi < MT; ++mi)
                 b[mi] = *reinterpret_cast<const f32x4*>(Xs + ((wm * MT + mi) * 16 + frow) * LDK + fcol[kc]);
-            if (SSD_CONV_ABLATE & 16) {
-#pragma unroll
-                for (int ni = 0; ni < NT; ++ni) asm volatile("" ::"v"(a[ni]));
-#pragma unroll
-                for (int mi = 0; mi < MT; ++mi) asm volatile("" ::"v"(b[mi]));
-                continue;
-            }
 #pragma unroll
             for (int s = 0; s < 4; ++s)
 #pragma unroll
@@ -650,24 +468,12 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* __res
                     for (int ni = 0; ni < NT; ++ni)
                         acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ni][s], b[mi][s], acc[mi][ni], 0, 0, 0);
         }
-        }
         if (more) store_tile(stage ^ 1);
-        if (SSD_CONV_ABLATE & 64) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // LDS-only barrier
-        else if (!(SSD_CONV_ABLATE & 8)) __syncthreads();
+        __syncthreads();
     }
     }
 
     conv_epilogue<MT, NT>(p, acc, m0, n0, wm, wn, lane, HoWo);
-#ifdef SSD_C3_PROF
-    if constexpr (SPLIT3) {
-        __syncthreads();
-        if (blockIdx.x == gridDim.x / 3 && lane == 0 && p.split_k <= 1) {
-            float* d = p.out + m0 * p.out_pixel_stride + n0 + wave * 12;
-            for (int i = 0; i < 9; ++i) d[i] = (float)c3tp[i];
-            d[9] = (float)(kt_end - kt_begin);
-        }
-    }
-#endif
 }
 
 
@@ -680,13 +486,8 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvParams p) {
 }
 
 // split-bf16 variant: dynamic LDS, 2 * 3 * 16 * (MT*WM + NT*WN) * 64 bytes
-#if SSD_C3_VARIANT & 2
-#define SSD_C3_BOUNDS(WM, WN) __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? ((SSD_C3_VARIANT & 4) ? 3 : 2) : 1)
-#else
-#define SSD_C3_BOUNDS(WM, WN) __launch_bounds__(64 * WM * WN)
-#endif
 template <int MT, int NT, int WM, int WN, bool GEMM1X1>
-__global__ SSD_C3_BOUNDS(WM, WN) void conv_mfma3_kernel(const ConvParams p) {
+__global__ __launch_bounds__(64 * WM * WN) void conv_mfma3_kernel(const ConvParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem3[];
     conv_mfma_body<MT, NT, WM, WN, 32, GEMM1X1, 3>(p, smem3);
 }

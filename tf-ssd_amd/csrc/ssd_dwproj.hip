@@ -20,7 +20,6 @@
 // BN scales are folded into Wd / Wp on the host side of the library (ssd_net.hip), so the
 // kernel only adds the shifts.  With few pixels per image the grid can additionally split the
 // output channels (gridDim.y): each half recomputes the (cheap, VALU) depthwise.
-#include <cstdlib>
 
 #include "ssd_bf16x3.h"
 #include "ssd_conv.h"
@@ -72,182 +71,11 @@ struct DwProjShape {
     static constexpr size_t lds_floats = (size_t)HP * LD + (size_t)PG * 16 * LD + (size_t)NTB * 16 * LD + 10 * kCK;
     static_assert(WM * WN == 4, "4 waves");
     static_assert(STRIPS * kCQ <= 256, "depthwise mapping needs STRIPS * 12 <= 256 threads");
+    static constexpr size_t lds_bytes = 2 * lds_floats * sizeof(float);     // every tile double-buffered
+    static_assert(lds_bytes <= 160 * 1024, "the double-buffered tiles fit the 160 KB of LDS");
 };
 
-template <int S, int TH, int TW, int SL, int WM, int WN, int NTW>
-__global__ __launch_bounds__(256) void dwproj_kernel(const DwProjParams p) {
-    using Sh = DwProjShape<S, TH, TW, SL, WM, WN, NTW>;
-    constexpr int PT = Sh::PT, PG = Sh::PG, MTW = Sh::MTW, NTB = Sh::NTB, IW = Sh::IW, HP = Sh::HP, kLD = Sh::LD;
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float* Es = sm;                                  // [HP][kLD]
-    float* Ds = Es + HP * kLD;                       // [PG*16][kLD]
-    float* Ws = Ds + PG * 16 * kLD;                  // [NTB*16][kLD]
-    float* Wd = Ws + NTB * 16 * kLD;                 // [10][kCK]: 9 taps + shift
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WN, wn = wave % WN;
-    const int tiles_per_img = p.tiles_y * p.tiles_x;
-    const int b = blockIdx.x / tiles_per_img;
-    const int rem = blockIdx.x - b * tiles_per_img;
-    const int ty = rem / p.tiles_x, tx = rem - ty * p.tiles_x;
-    const int oy0 = ty * TH, ox0 = tx * TW;
-    const int iy0 = oy0 * S - p.pad_t, ix0 = ox0 * S - p.pad_l;
-    const int nt0 = blockIdx.y * NTB;                // first 16-channel output tile of this workgroup
-    const float* eb = p.e + (long)b * p.H * p.W * p.Ce;
-
-    f32x4 acc[MTW][NTW];
-#pragma unroll
-    for (int mi = 0; mi < MTW; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NTW; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // depthwise mapping: thread = (strip of SL output pixels in one row, channel quad)
-    const int cq = tid % kCQ, strip = tid / kCQ;
-    const bool dw_on = strip < Sh::STRIPS;
-    const int sr = strip / Sh::NSX, sx0 = (strip - sr * Sh::NSX) * SL;
-    const int frow = lane & 15, fk = (lane >> 4) * 4;
-
-    // ---- staging: chunk c+1 travels global -> registers while chunk c is computed.  Indices are
-    // clamped, not predicated: every lane loads from a valid address; the LDS writes drop the
-    // lanes that are out of range and zero the halo pixels outside the image.
-    constexpr int E_U = HP * kCQ, W_U = NTB * 16 * kCQ;
-    constexpr int E_R = (E_U + 255) / 256, W_R = (W_U + 255) / 256;
-    f32x4 er[E_R], wr[W_R], dr[1];
-    const float* eptr[E_R];     // address of this lane's E elements at channel 0 of the chunk
-    bool ein[E_R];
-#pragma unroll
-    for (int i = 0; i < E_R; ++i) {
-        const int u = min(tid + i * 256, E_U - 1);
-        const int hp = u / kCQ, k4 = (u - hp * kCQ) * 4;
-        const int r = hp / IW, cc = hp - r * IW;
-        const int iy = iy0 + r, ix = ix0 + cc;
-        ein[i] = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-        eptr[i] = eb + ((long)min(max(iy, 0), p.H - 1) * p.W + min(max(ix, 0), p.W - 1)) * p.Ce + k4;
-    }
-    const float* wptr[W_R];
-#pragma unroll
-    for (int i = 0; i < W_R; ++i) {
-        const int u = min(tid + i * 256, W_U - 1);
-        const int row = u / kCQ, k4 = (u - row * kCQ) * 4;
-        wptr[i] = p.wp + (long)min(nt0 * 16 + row, p.npad_p - 1) * p.kpad_p + k4;
-    }
-    const int dt = min(tid, 10 * kCQ - 1) / kCQ, dk4 = (min(tid, 10 * kCQ - 1) % kCQ) * 4;
-    const float* dptr = (dt < 9 ? p.wd + (long)dt * p.Ce : p.dh) + dk4;
-    auto load_chunk = [&](int ch0) {
-#pragma unroll
-        for (int i = 0; i < E_R; ++i) er[i] = gload16_async(eptr[i] + ch0);
-#pragma unroll
-        for (int i = 0; i < W_R; ++i) wr[i] = gload16_async(wptr[i] + ch0);
-        dr[0] = gload16_async(dptr + ch0);
-    };
-    auto store_chunk = [&]() {
-        wait_prefetch(er);
-        wait_prefetch(wr);
-        wait_prefetch(dr);
-#pragma unroll
-        for (int i = 0; i < E_R; ++i) {
-            const int u = tid + i * 256;
-            const int hp = u / kCQ, k4 = (u - hp * kCQ) * 4;
-            if (u < E_U) *reinterpret_cast<f32x4*>(Es + hp * kLD + k4) = ein[i] ? er[i] : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-#pragma unroll
-        for (int i = 0; i < W_R; ++i) {
-            const int u = tid + i * 256;
-            const int row = u / kCQ, k4 = (u - row * kCQ) * 4;
-            if (u < W_U) *reinterpret_cast<f32x4*>(Ws + row * kLD + k4) = wr[i];
-        }
-        if (tid < 10 * kCQ) *reinterpret_cast<f32x4*>(Wd + dt * kCK + dk4) = dr[0];
-    };
-
-    const int nchunks = p.Ce / kCK;
-    load_chunk(0);
-    store_chunk();
-    lds_barrier();
-    for (int c = 0; c < nchunks; ++c) {
-        const bool more = c + 1 < nchunks;
-        if (more && !(p.ablate & 4)) load_chunk((c + 1) * kCK);
-        // ---- B: depthwise 3x3 + shift + ReLU6 -> Ds
-        if (dw_on && !(p.ablate & 1)) {
-            f32x4 o[SL];
-            const f32x4 sh = *reinterpret_cast<const f32x4*>(Wd + 9 * kCK + cq * 4);
-#pragma unroll
-            for (int j = 0; j < SL; ++j) o[j] = sh;
-#pragma unroll
-            for (int dy = 0; dy < 3; ++dy) {
-                f32x4 win[Sh::WIN];
-                const float* erow = Es + ((sr * S + dy) * IW) * kLD + cq * 4;
-#pragma unroll
-                for (int i = 0; i < Sh::WIN; ++i)
-                    win[i] = *reinterpret_cast<const f32x4*>(erow + min(sx0 * S + i, IW - 1) * kLD);
-#pragma unroll
-                for (int dx = 0; dx < 3; ++dx) {
-                    const f32x4 w = *reinterpret_cast<const f32x4*>(Wd + (dy * 3 + dx) * kCK + cq * 4);
-#pragma unroll
-                    for (int j = 0; j < SL; ++j) o[j] += win[j * S + dx] * w;
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < SL; ++j) {
-                if (sx0 + j < TW) {
-                    f32x4 v = o[j];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) v[q] = relu6f(v[q]);
-                    *reinterpret_cast<f32x4*>(Ds + (sr * TW + sx0 + j) * kLD + cq * 4) = v;
-                }
-            }
-        }
-        lds_barrier();
-        // ---- C: project on the MFMA (weights = A operand, pixels = B operand)
-#pragma unroll
-        for (int kc = 0; kc < ((p.ablate & 2) ? 0 : kCK / 16); ++kc) {
-            f32x4 a[NTW], bb[MTW];
-#pragma unroll
-            for (int ni = 0; ni < NTW; ++ni)
-                a[ni] = *reinterpret_cast<const f32x4*>(Ws + ((wn * NTW + ni) * 16 + frow) * kLD + kc * 16 + fk);
-#pragma unroll
-            for (int mi = 0; mi < MTW; ++mi)
-                bb[mi] = *reinterpret_cast<const f32x4*>(Ds + ((wm * MTW + mi) * 16 + frow) * kLD + kc * 16 + fk);
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-#pragma unroll
-                for (int mi = 0; mi < MTW; ++mi)
-#pragma unroll
-                    for (int ni = 0; ni < NTW; ++ni)
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ni][s], bb[mi][s], acc[mi][ni], 0, 0, 0);
-        }
-        lds_barrier();
-        if (more && !(p.ablate & 4)) {
-            store_chunk();
-            lds_barrier();
-        }
-    }
-
-    // ---- epilogue: lane holds y[pixel = group*16 + (lane & 15)][n = tile*16 + (lane >> 4)*4 + 0..3]
-    f32x4 shv[NTW];
-#pragma unroll
-    for (int ni = 0; ni < NTW; ++ni) {
-        const int n = (nt0 + wn * NTW + ni) * 16 + (lane >> 4) * 4;
-        shv[ni] = n < p.Cout ? *reinterpret_cast<const f32x4*>(p.ph + n) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-#pragma unroll
-    for (int mi = 0; mi < MTW; ++mi) {
-        const int px = (wm * MTW + mi) * 16 + (lane & 15);
-        const int r = px / TW, cc = px - r * TW;
-        const int oy = oy0 + r, ox = ox0 + cc;
-        if (px >= PT || oy >= p.Ho || ox >= p.Wo) continue;
-        const long o = (((long)b * p.Ho + oy) * p.Wo + ox) * p.Cout;
-#pragma unroll
-        for (int ni = 0; ni < NTW; ++ni) {
-            const int n = (nt0 + wn * NTW + ni) * 16 + (lane >> 4) * 4;
-            if (n >= p.Cout) continue;
-            f32x4 v = acc[mi][ni] + shv[ni];
-            if (p.res) v = v + *reinterpret_cast<const f32x4*>(p.res + o + n);
-            *reinterpret_cast<f32x4*>(p.y + o + n) = v;
-        }
-    }
-}
-
-// 8-wave variant: waves 0-3 ("producers") stage chunks and run the depthwise, waves 4-7
+// 8 waves: waves 0-3 ("producers") stage chunks and run the depthwise, waves 4-7
 // ("consumers") run the project MFMAs of the previous chunk at the same time; E / D / Wp / Wd
 // tiles are double-buffered in LDS and one workgroup barrier per chunk hands them over.
 // At the start of iteration i:   Ds[i&1] = D(i),  Ws[i&1] = Wp(i),  Es/Wd[(i+1)&1] = E/wd(i+1),
@@ -256,13 +84,13 @@ __global__ __launch_bounds__(256) void dwproj_kernel(const DwProjParams p) {
 //                            registers -> Es/Wd[i&1] (E/wd(i+2)), Ws[(i+1)&1] (Wp(i+1));
 //                            issue loads of E/wd(i+3), Wp(i+2)
 //   consumers, iteration i:  acc += Ds[i&1] x Ws[i&1]
-// (a phase ablation of the 4-wave kernel showed its depthwise, MFMA and staging times simply add
-// up: 6.4 + 8.5 + 4.3 us of a 33 us block_7 launch, 10.9 + 20.4 + 9.7 of 55 us for block_11.)
+// (in a 4-wave kernel that ran the phases one after the other their times simply added up:
+// 6.4 + 8.5 + 4.3 us of a 33 us block_7 launch, 10.9 + 20.4 + 9.7 of 55 us for block_11.)
 // BF16 (the net's precision-1 mode): the project runs on the bf16 matrix cores -- the consumer waves round their D and
 // Wp fragments (fp32 in LDS, as the producers wrote them) to bf16 on the fly, 8 k-values per lane, and issue TWO
 // v_mfma_f32_16x16x32_bf16 per (pixel group, output tile) and 48-channel chunk (k 0-31, k 32-47 + zeros) instead of
 // twelve v_mfma_f32_16x16x4_f32; depthwise, BatchNorm shifts, ReLU6 and the residual add stay fp32.
-template <int S, int TH, int TW, int SL, int WM, int WN, int NTW, int NOPS, bool BF16 = false>
+template <int S, int TH, int TW, int SL, int WM, int WN, int NTW, bool BF16>
 __global__ __launch_bounds__(512) void dwproj8_kernel(const DwProjParams p) {
     using Sh = DwProjShape<S, TH, TW, SL, WM, WN, NTW>;
     constexpr int PT = Sh::PT, PG = Sh::PG, MTW = Sh::MTW, NTB = Sh::NTB, IW = Sh::IW, HP = Sh::HP, kLD = Sh::LD;
@@ -345,7 +173,7 @@ __global__ __launch_bounds__(512) void dwproj8_kernel(const DwProjParams p) {
             }
         };
         auto depthwise = [&](int buf) {          // Es/Wd[buf] -> Ds[buf]
-            if (!dw_on || (p.ablate & 1)) return;
+            if (!dw_on) return;
             const float* E = Es + buf * ES;
             const float* Wt = Wd + buf * WD;
             float* D = Ds + buf * DS;
@@ -387,19 +215,15 @@ __global__ __launch_bounds__(512) void dwproj8_kernel(const DwProjParams p) {
         // prologue 2: D(0); E/wd(1) -> Es/Wd[1]; loads of E/wd(2), Wp(1) in flight
         depthwise(0);
         if (nchunks > 1) store_e(1);
-        if (!(p.ablate & 4)) {
-            if (nchunks > 2) load_e(2);
-            if (nchunks > 1) load_w(1);
-        }
+        if (nchunks > 2) load_e(2);
+        if (nchunks > 1) load_w(1);
         lds_barrier();
         for (int i = 0; i < nchunks; ++i) {
             if (i + 1 < nchunks) depthwise((i + 1) & 1);
-            if (!(p.ablate & 4)) {
-                if (i + 2 < nchunks) store_e(i & 1);
-                if (i + 1 < nchunks) store_w((i + 1) & 1);
-                if (i + 3 < nchunks) load_e(i + 3);
-                if (i + 2 < nchunks) load_w(i + 2);
-            }
+            if (i + 2 < nchunks) store_e(i & 1);
+            if (i + 1 < nchunks) store_w((i + 1) & 1);
+            if (i + 3 < nchunks) load_e(i + 3);
+            if (i + 2 < nchunks) load_w(i + 2);
             lds_barrier();
         }
         return;
@@ -452,7 +276,7 @@ __global__ __launch_bounds__(512) void dwproj8_kernel(const DwProjParams p) {
             continue;
         }
 #pragma unroll
-        for (int kc = 0; kc < ((p.ablate & 2) ? 0 : kCK / 16); ++kc) {
+        for (int kc = 0; kc < kCK / 16; ++kc) {
             f32x4 a[NTW], bb[MTW];
 #pragma unroll
             for (int ni = 0; ni < NTW; ++ni)
@@ -465,13 +289,8 @@ __global__ __launch_bounds__(512) void dwproj8_kernel(const DwProjParams p) {
 #pragma unroll
                 for (int mi = 0; mi < MTW; ++mi)
 #pragma unroll
-                    for (int ni = 0; ni < NTW; ++ni) {
+                    for (int ni = 0; ni < NTW; ++ni)
                         acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ni][s], bb[mi][s], acc[mi][ni], 0, 0, 0);
-                        // A wave whose NEXT MFMA waits in the issue stage for the matrix pipe blocks every
-                        // other wave of its SIMD (tests/micro/mfma_valu_overlap.hip): idle through the
-                        // 8-pass shadow instead, so that the producer wave sharing the SIMD can issue.
-                        if (NOPS > 0) asm volatile("s_nop %0" ::"n"(NOPS));
-                    }
         }
         lds_barrier();
     }
@@ -498,16 +317,11 @@ struct DwProjCfg {
     int stride, cout_min, cout_max, th, tw, ntb, n_split;
     size_t lds;
     dwproj_fn fn;
-    size_t lds8;
-    dwproj_fn fn8[4];       // s_nop 0 (none) / 3 / 5 / 6 after each consumer MFMA
-    dwproj_fn fn8b;         // the project on the bf16 matrix cores (precision 1)
+    dwproj_fn fn_bf16;      // the project on the bf16 matrix cores (precision 1)
 };
 #define DCFG(S, TH, TW, SL, WM, WN, NTW, CMIN, CMAX, NSPLIT)                                               \
-    {S, CMIN, CMAX, TH, TW, NTW * WN, NSPLIT, DwProjShape<S, TH, TW, SL, WM, WN, NTW>::lds_floats * 4,       \
-     dwproj_kernel<S, TH, TW, SL, WM, WN, NTW>, DwProjShape<S, TH, TW, SL, WM, WN, NTW>::lds_floats * 8,      \
-     {dwproj8_kernel<S, TH, TW, SL, WM, WN, NTW, 0>, dwproj8_kernel<S, TH, TW, SL, WM, WN, NTW, 3>,              \
-      dwproj8_kernel<S, TH, TW, SL, WM, WN, NTW, 5>, dwproj8_kernel<S, TH, TW, SL, WM, WN, NTW, 6>},              \
-     dwproj8_kernel<S, TH, TW, SL, WM, WN, NTW, 0, true>}
+    {S, CMIN, CMAX, TH, TW, NTW * WN, NSPLIT, DwProjShape<S, TH, TW, SL, WM, WN, NTW>::lds_bytes,            \
+     dwproj8_kernel<S, TH, TW, SL, WM, WN, NTW, false>, dwproj8_kernel<S, TH, TW, SL, WM, WN, NTW, true>}
 const DwProjCfg kDwProj[] = {
     // stride 1, 19-wide row bands (blocks 7-12 of SSD300): 6 pixel groups x Cout/16 tiles on 2x2 waves
     DCFG(1, 5, 19, 5, 2, 2, 2, 1, 64, 1),
@@ -542,20 +356,9 @@ int launch_dwproj(DwProjParams p, hipStream_t st) {
     p.tiles_x = (p.Wo + c->tw - 1) / c->tw;
     const long tiles = (long)p.B * p.tiles_y * p.tiles_x;
     SSD_UNSUPPORTED_IF(tiles > 0x7fffffffL, "dw+project: grid too large");
-    static const int ablate = getenv("SSD_DWPROJ_ABLATE") ? atoi(getenv("SSD_DWPROJ_ABLATE")) : 0;
-    p.ablate = ablate;
-    static const int waves = getenv("SSD_DWPROJ_WAVES") ? atoi(getenv("SSD_DWPROJ_WAVES")) : 8;     // diagnostics knob
-    static const int nopsel = getenv("SSD_DWPROJ_NOP") ? atoi(getenv("SSD_DWPROJ_NOP")) & 3 : 0;     // diagnostics knob
-    if (waves == 8 && c->lds8 <= 160 * 1024) {
-        dwproj_fn fn8 = p.bf16 ? c->fn8b : c->fn8[nopsel];
-        SSD_HIP(hipFuncSetAttribute((const void*)fn8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds8));
-        hipLaunchKernelGGL(fn8, dim3((unsigned)tiles, c->n_split), dim3(512), c->lds8, st, p);
-        SSD_LAUNCH_CHECK();
-        return SSD_OK;
-    }
-    if (c->lds > 64 * 1024)
-        SSD_HIP(hipFuncSetAttribute((const void*)c->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds));
-    hipLaunchKernelGGL(c->fn, dim3((unsigned)tiles, c->n_split), dim3(256), c->lds, st, p);
+    const dwproj_fn fn = p.bf16 ? c->fn_bf16 : c->fn;
+    SSD_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds));
+    hipLaunchKernelGGL(fn, dim3((unsigned)tiles, c->n_split), dim3(512), c->lds, st, p);
     SSD_LAUNCH_CHECK();
     return SSD_OK;
 }

@@ -71,7 +71,7 @@ template <int NP, int CINP, int IW, int IPX>
 __device__ __forceinline__ void expand_px_tiles(const float* Xs, const float* Wes, float* Es, const float* Ps,
                                                 const int Ce, const int ce0, const int pt0, const int pt1,
                                                 const int lane, const int iy0, const int ix0, const int H,
-                                                const int W, const int ablate = 0) {
+                                                const int W) {
     constexpr int LDX = ldx_for(CINP);
     const int frow = lane & 15, fk = (lane >> 4) * 4;
     const int pts[2] = {pt0, pt1};
@@ -83,7 +83,6 @@ __device__ __forceinline__ void expand_px_tiles(const float* Xs, const float* We
 #pragma unroll
         for (int q = 0; q < NP; ++q) ea[q][ct] = sh;
     }
-    if (!(ablate & 1))
 #pragma unroll
     for (int kc = 0; kc < CINP / 16; ++kc) {
         f32x4 xb4[NP], wa[3];
@@ -101,7 +100,7 @@ __device__ __forceinline__ void expand_px_tiles(const float* Xs, const float* We
                 for (int ct = 0; ct < 3; ++ct)
                     ea[q][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[ct][s], xb4[q][s], ea[q][ct], 0, 0, 0);
     }
-    if (CINP % 16 == 8 && !(ablate & 1)) {
+    if (CINP % 16 == 8) {
         // K tail of 8 (Cin = 24): lane group g reads k = 16*(CINP/16) + 2g + {0, 1} with one
         // ds_read_b64, i.e. 2 MFMA k-steps instead of the 4 a zero-padded 16-wide unit would cost
         typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -135,7 +134,6 @@ __device__ __forceinline__ void expand_px_tiles(const float* Xs, const float* We
             f32x4 v = ea[q][ct];
             // relu6 inside the image, 0 outside it (the depthwise pads E): one v_med3 with a
             // per-lane upper bound of 6 or 0 instead of med3 + select
-            if (!(ablate & 8))
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[j] = __builtin_amdgcn_fmed3f(v[j], 0.0f, hi);
             *reinterpret_cast<f32x4*>(Es + hp * kLDE + cl) = v;
@@ -175,10 +173,6 @@ __global__ __launch_bounds__(256, 2) void mbv2_block_kernel(const FusedBlockPara
     float* Ps = Wps + NTC * 16 * kLDE;      // [13][Ce]: es, eh, wd[9], ds, dh; then [2][NTC*16]: ps, ph
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    long long tacc[6] = {0, 0, 0, 0, 0, 0};
-    long long t0 = p.dbg ? clock64() : 0;
-#define TICK(i) do { if (p.dbg) { const long long t1 = clock64(); tacc[i] += t1 - t0; t0 = t1; } } while (0)
-    const bool getenv_dbg_split = p.dbg != nullptr;
     const int Ce = p.Ce;
     const int tiles_per_img = p.tiles_y * p.tiles_x;
     const long total_tiles = (long)p.B * tiles_per_img;
@@ -269,7 +263,6 @@ __global__ __launch_bounds__(256, 2) void mbv2_block_kernel(const FusedBlockPara
     store_x(tile);
     store_w();
     __syncthreads();
-    TICK(0);
 
     const int frow = lane & 15, fk = (lane >> 4) * 4;
     const int wpx = wave % WPX, wn = wave / WPX;     // phase C wave coordinates
@@ -308,16 +301,14 @@ __global__ __launch_bounds__(256, 2) void mbv2_block_kernel(const FusedBlockPara
             {
                 int pt = wave;
                 for (; pt + 4 < NPT; pt += 8)
-                    expand_px_tiles<2, CINP, IW, IPX>(Xs, Wes, Es, Ps, Ce, ce0, pt, pt + 4, lane, iy0, ix0, p.H, p.W, p.ablate);
+                    expand_px_tiles<2, CINP, IW, IPX>(Xs, Wes, Es, Ps, Ce, ce0, pt, pt + 4, lane, iy0, ix0, p.H, p.W);
                 if (pt < NPT)
-                    expand_px_tiles<1, CINP, IW, IPX>(Xs, Wes, Es, Ps, Ce, ce0, pt, pt, lane, iy0, ix0, p.H, p.W, p.ablate);
+                    expand_px_tiles<1, CINP, IW, IPX>(Xs, Wes, Es, Ps, Ce, ce0, pt, pt, lane, iy0, ix0, p.H, p.W);
             }
-            if (getenv_dbg_split) TICK(4);      // diagnostics: slot 4 = expand compute (+ weight staging), slot 1 = its barrier wait
-            if (!(p.ablate & 16)) lds_barrier();
-            TICK(1);
+            lds_barrier();
 
             // ---- phase B: depthwise 3x3 + BN + ReLU6 (VALU, LDS -> LDS), sliding register window
-            if (tid < NSTRIP * (kCK / 4) && !(p.ablate & 2)) {
+            if (tid < NSTRIP * (kCK / 4)) {
                 f32x4 a[SL];
                 {
                     const f32x4 sh = *reinterpret_cast<const f32x4*>(Ps + 12 * Ce + ce0 + bc4);
@@ -347,11 +338,9 @@ __global__ __launch_bounds__(256, 2) void mbv2_block_kernel(const FusedBlockPara
                     *reinterpret_cast<f32x4*>(Ds + (boy * TW + box0 + t) * kLDE + bc4) = v;
                 }
             }
-            if (!(p.ablate & 16)) lds_barrier();
-            TICK(2);
+            lds_barrier();
 
             // ---- phase C: project (MFMA), accumulators stay in registers across chunks
-            if (!(p.ablate & 4))
 #pragma unroll
             for (int kc = 0; kc < kCK / 16; ++kc) {
                 const f32x4 db = *reinterpret_cast<const f32x4*>(Ds + (wpx * 16 + frow) * kLDE + kc * 16 + fk);
@@ -365,13 +354,11 @@ __global__ __launch_bounds__(256, 2) void mbv2_block_kernel(const FusedBlockPara
                     for (int ni = 0; ni < NTW; ++ni)
                         acc[ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[ni][s], db[s], acc[ni], 0, 0, 0);
             }
-            if (!(p.ablate & 16)) lds_barrier();
-            TICK(3);
+            lds_barrier();
             if (ch + 1 < nchunk) {
                 store_w();
-                if (!(p.ablate & 16)) lds_barrier();
+                lds_barrier();
             }
-            TICK(4);
         }
 
         // ---- epilogue: project BN (+ residual from the X tile), 16-byte stores
@@ -394,15 +381,12 @@ __global__ __launch_bounds__(256, 2) void mbv2_block_kernel(const FusedBlockPara
             }
         }
         if (next < total_tiles) {
-            if (!(p.ablate & 16)) lds_barrier();          // every wave is done with Xs (residual) before it is replaced
+            lds_barrier();          // every wave is done with Xs (residual) before it is replaced
             store_x(next);
             store_w();
-            if (!(p.ablate & 16)) lds_barrier();
+            lds_barrier();
         }
-        TICK(5);
     }
-    if (p.dbg && (tid & 63) == 0)
-        for (int i = 0; i < 6; ++i) p.dbg[((long)blockIdx.x * 4 + wave) * 6 + i] = tacc[i];
 }
 
 template <int CINP, int NTC, int S, int TH, int TW>
@@ -464,12 +448,7 @@ int launch_fused_block(FusedBlockParams p, hipStream_t st) {
         if (hipDeviceGetAttribute(&num_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || num_cu <= 0)
             num_cu = 256;
     }
-    static int per_cu = 0;
-    if (!per_cu) {
-        const char* e = getenv("SSD_FUSED_BLOCKS_PER_CU");      // diagnostics knob
-        per_cu = e ? atoi(e) : 2;
-        if (per_cu < 1) per_cu = 2;
-    }
+    constexpr int per_cu = 2;
     const long blocks = tiles < (long)per_cu * num_cu ? tiles : (long)per_cu * num_cu;   // persistent workgroups
     const size_t lds = (c->static_floats + (size_t)13 * p.Ce + (size_t)2 * c->ntc * 16) * sizeof(float);
     SSD_UNSUPPORTED_IF(lds > 160 * 1024, "fused block: needs %zu B of LDS", lds);
@@ -488,16 +467,16 @@ int launch_fused_block(FusedBlockParams p, hipStream_t st) {
 // pixels: image patch -> LDS, Conv1 on the 10 x 18 halo (VALU, weights broadcast from LDS,
 // zero outside the feature map because the depthwise pads Conv1's OUTPUT), depthwise from LDS
 // (sliding window), project on the fp32 MFMA (K = 32), 16-byte stores.
-// NP selects the matrix instruction of Conv1 and the project: 0 = v_mfma_f32_16x16x4_f32 (exact fp32 products), 3 = the
-// exact three-way bf16 split on v_mfma_f32_16x16x32_bf16 (fp32 results: K = 27 / 32 is ONE k-step, six instructions of
-// 16 cycles instead of eight of 32 per 16 x 16 tile), 1 = operands rounded once to bf16 (the net's bf16 mode).
+// NP selects the operands of Conv1's and the project's v_mfma_f32_16x16x32_bf16: 3 = the exact three-way bf16 split (fp32
+// results: K = 27 / 32 is ONE k-step, six instructions of 16 cycles instead of the fp32 MFMA's eight of 32 per 16 x 16 tile),
+// 1 = operands rounded once to bf16 (the net's bf16 mode).
 constexpr int kSTH = 8, kSTW = 16;
 constexpr int kSIH = kSTH + 2, kSIW = kSTW + 2;           // Conv1 halo tile 10 x 18
 constexpr int kSPH = 2 * (kSIH - 1) + 3, kSPW = 2 * (kSIW - 1) + 3;   // image patch 21 x 37
 constexpr int kSLD = 40;                                  // LDS row stride of the 32-channel tiles (10 quads: conflict-free b128 fragment reads)
 // DMA form of the patch (round 5): rows start at a 16-byte aligned float (up to 3 floats left of the patch's first), 29 quads =
 // 116 floats per row, TWO stages: tile t + 1's rows are copied global -> LDS by `buffer_load_dwordx4 ... lds` while tile t is
-// computed (the register-staged patch load cost 20 of the kernel's 112 us: tests/micro/stem_ablate.py, SSD_STEM_ABLATE = 8 / 16)
+// computed (the register-staged patch load cost 20 of the kernel's 112 us: profiles/HISTORY.md, round 5)
 constexpr int kSPQ = (kSPW * 3 + 3 + 3) / 4, kSPR = kSPQ * 4;
 constexpr int kSPS = (kSPH * kSPQ + 63) / 64 * 256;       // floats per patch stage: whole 64-lane instructions (640 units)
 
@@ -505,54 +484,37 @@ template <bool DMA>
 constexpr int stem_patch_floats() { return DMA ? 2 * kSPS : kSPH * kSPW * 3 + 5; }
 template <bool DMA>
 constexpr int stem_lds_floats() {
-    return stem_patch_floats<DMA>() + kSIH * kSIW * kSLD + kSTH * kSTW * kSLD + 27 * 32 + 9 * 32 + 16 * kSLD + 32 * 2 + 32 * 2 + 16 * 2;
+    return stem_patch_floats<DMA>() + kSIH * kSIW * kSLD + kSTH * kSTW * kSLD + 27 * 32 + 9 * 32 + 32 * 2 + 32 * 2 + 16 * 2;
 }
 // (a __device__ body: a __global__ function that declares buffer resources loses its host stub)
 template <int NP, bool DMA>
 __device__ __forceinline__ void stem_body(const StemParams& p, float* __restrict__ sm) {
+    static_assert(NP == 1 || NP == 3, "bf16 or split-bf16 operands");
     constexpr int RP = DMA ? kSPR : kSPW * 3;                  // floats between two patch rows in LDS
     float* patch = sm;                                         // [21*37*3] image patch (+5 pad); DMA: [2][640 units of 4]
     float* C1 = patch + stem_patch_floats<DMA>();              // [180][36] Conv1 output (halo), 16-byte aligned
     float* D = C1 + kSIH * kSIW * kSLD;                        // [128][36] depthwise output
     float* W1 = D + kSTH * kSTW * kSLD;                        // [27][32] Conv1 weights * BN scale
     float* Wd = W1 + 27 * 32;                                  // [9][32]  depthwise weights * BN scale
-    float* Wp = Wd + 9 * 32;                                   // [16][36] project weights * BN scale
-    float* H1 = Wp + 16 * kSLD;                                // [32] Conv1 BN shift
+    float* H1 = Wd + 9 * 32;                                   // [32] Conv1 BN shift
     float* Hd = H1 + 32;                                       // [32] depthwise BN shift
     float* Hp = Hd + 32;                                       // [16] project BN shift
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // weights (BatchNorm scale folded in) are staged once per persistent workgroup
-    // Conv1 on the MFMA: K = 27 taps x channels padded to 32 = 2 k-blocks of 16; lane (ch = l15, g4) holds
-    // the A fragments W[ch][k = kb*16 + g4*4 + s] * BN scale of both 16-channel tiles for the whole
-    // persistent loop (16 VGPRs; the VALU form held 27 x 4 weights per thread and ran at 36 % of the
-    // packed-FMA rate: 63 of the kernel's 131 us), and the patch offsets of ITS four k per k-block
-    f32x4 w1a[2][2];
+    // Conv1 on the MFMA: K = 27 taps x channels padded to 32 = one 32-wide k-step; lane (ch = l15, g4) holds the A fragments
+    // W[ch][k = g4*8 .. +7] * BN scale of both 16-channel tiles as bf16 planes for the whole persistent loop (the VALU form held
+    // 27 x 4 weights per thread and ran at 36 % of the packed-FMA rate: 63 of the kernel's 131 us), the patch offsets of ITS
+    // eight k, and the project's A fragment (row n = l15) the same way
     int koff[2][4];
     int kcol[2][4];            // kx * 3 + ci of the lane's k values (DMA form: the right-edge mask)
-    // NP > 0: one 32-wide k-step; lane (ch = l15, g4) holds k = g4*8 .. +7 of both channel tiles as bf16 planes, and the
-    // project's A fragment (row n = l15) the same way
-    BP<NP ? NP : 1> w1b[2], wpb;
-    if (NP == 0) {
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) {
-                const int k = kb * 16 + (lane >> 4) * 4 + s4;
-                koff[kb][s4] = k < 27 ? (k / 9) * RP + (k % 9) : 0;      // (ky, kx*3 + ci) inside the patch
-                kcol[kb][s4] = k < 27 ? k % 9 : 0;
-#pragma unroll
-                for (int ct = 0; ct < 2; ++ct) {
-                    const int ch = ct * 16 + (lane & 15);
-                    w1a[ct][kb][s4] = k < 27 ? p.w1[(long)ch * p.kpad1 + k] * p.s1[ch] : 0.f;
-                }
-            }
-    } else {
+    BP<NP> w1b[2], wpb;
+    {
         f32x4 wl[2][2];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int k = (lane >> 4) * 8 + j;
-            koff[j >> 2][j & 3] = k < 27 ? (k / 9) * RP + (k % 9) : 0;
+            koff[j >> 2][j & 3] = k < 27 ? (k / 9) * RP + (k % 9) : 0;      // (ky, kx*3 + ci) inside the patch
             kcol[j >> 2][j & 3] = k < 27 ? k % 9 : 0;
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct) {
@@ -561,17 +523,13 @@ __device__ __forceinline__ void stem_body(const StemParams& p, float* __restrict
             }
         }
 #pragma unroll
-        for (int ct = 0; ct < 2; ++ct) w1b[ct] = splitN<NP ? NP : 1>(wl[ct][0], wl[ct][1]);
+        for (int ct = 0; ct < 2; ++ct) w1b[ct] = splitN<NP>(wl[ct][0], wl[ct][1]);
         const int n = lane & 15;
         const float* wr = p.wp + (long)n * p.kpadp + (lane >> 4) * 8;
         f32x4 lo = *reinterpret_cast<const f32x4*>(wr), hi = *reinterpret_cast<const f32x4*>(wr + 4);
-        wpb = splitN<NP ? NP : 1>(lo * p.sp[n], hi * p.sp[n]);
+        wpb = splitN<NP>(lo * p.sp[n], hi * p.sp[n]);
     }
     for (int e = tid; e < 9 * 32; e += 256) Wd[e] = p.wd[e] * p.sd[e & 31];
-    for (int e = tid; e < 16 * 32; e += 256) {
-        const int n = e >> 5, k = e & 31;
-        Wp[n * kSLD + k] = p.wp[(long)n * p.kpadp + k] * p.sp[n];
-    }
     if (tid < 32) { H1[tid] = p.h1[tid]; Hd[tid] = p.hd[tid]; }
     if (tid < 16) Hp[tid] = p.hp[tid];
 
@@ -645,7 +603,7 @@ __device__ __forceinline__ void stem_body(const StemParams& p, float* __restrict
                 const int r = e / (kSPW * 3), j = e - r * (kSPW * 3);
                 const int iy = iy0 + r, ixc = ix0 * 3 + j;         // ixc = ix * 3 + channel
                 tmp[i] = 0.f;
-                if (!(p.ablate & 8) && e < kSPH * kSPW * 3 && (unsigned)iy < (unsigned)p.H && ixc >= 0 && ixc < p.W * 3)
+                if (e < kSPH * kSPW * 3 && (unsigned)iy < (unsigned)p.H && ixc >= 0 && ixc < p.W * 3)
                     tmp[i] = img[(long)iy * p.W * 3 + ixc];
             }
 #pragma unroll
@@ -663,7 +621,7 @@ __device__ __forceinline__ void stem_body(const StemParams& p, float* __restrict
 
         // ---- Conv1 on the halo (MFMA): 12 pixel tiles of 16 halo pixels, 3 per wave; B fragment = the
         //      lane's pixel x its 4 k of the k-block, gathered from the patch with 4 ds_read_b32
-        if (!(p.ablate & 1)) {
+        {
             constexpr int NHP = kSIH * kSIW;                       // 180 halo pixels
             int hp[3], rr[3], cc[3];
             const float* pp[3];
@@ -678,45 +636,24 @@ __device__ __forceinline__ void stem_body(const StemParams& p, float* __restrict
                 a0[q] = *reinterpret_cast<const f32x4*>(H1 + (lane >> 4) * 4);
                 a1[q] = *reinterpret_cast<const f32x4*>(H1 + 16 + (lane >> 4) * 4);
             }
-            // six independent accumulator chains (3 pixel tiles x 2 channel tiles) keep the matrix pipe issuing
-            if (NP == 0) {
 #pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
+            for (int q = 0; q < 3; ++q) {
+                f32x4 lo, hi;
 #pragma unroll
-                    for (int s4 = 0; s4 < 4; ++s4) {
-                        float bq[3];
-#pragma unroll
-                        for (int q = 0; q < 3; ++q) bq[q] = pp[q][koff[kb][s4]];
-                        if (xedge)
-#pragma unroll
-                            for (int q = 0; q < 3; ++q)
-                                if (cc[q] * 6 + kcol[kb][s4] >= xlim) bq[q] = 0.f;
-#pragma unroll
-                        for (int q = 0; q < 3; ++q) {
-                            a0[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1a[0][kb][s4], bq[q], a0[q], 0, 0, 0);
-                            a1[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1a[1][kb][s4], bq[q], a1[q], 0, 0, 0);
-                        }
-                    }
-            } else {
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    f32x4 lo, hi;
+                for (int j = 0; j < 4; ++j) {
+                    lo[j] = pp[q][koff[0][j]];
+                    hi[j] = pp[q][koff[1][j]];
+                }
+                if (xedge) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        lo[j] = pp[q][koff[0][j]];
-                        hi[j] = pp[q][koff[1][j]];
+                        if (cc[q] * 6 + kcol[0][j] >= xlim) lo[j] = 0.f;
+                        if (cc[q] * 6 + kcol[1][j] >= xlim) hi[j] = 0.f;
                     }
-                    if (xedge) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            if (cc[q] * 6 + kcol[0][j] >= xlim) lo[j] = 0.f;
-                            if (cc[q] * 6 + kcol[1][j] >= xlim) hi[j] = 0.f;
-                        }
-                    }
-                    const BP<NP ? NP : 1> b = splitN<NP ? NP : 1>(lo, hi);
-                    a0[q] = mmaN<NP ? NP : 1>(w1b[0], b, a0[q]);
-                    a1[q] = mmaN<NP ? NP : 1>(w1b[1], b, a1[q]);
                 }
+                const BP<NP> b = splitN<NP>(lo, hi);
+                a0[q] = mmaN<NP>(w1b[0], b, a0[q]);
+                a1[q] = mmaN<NP>(w1b[1], b, a1[q]);
             }
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
@@ -738,7 +675,7 @@ __device__ __forceinline__ void stem_body(const StemParams& p, float* __restrict
         else __syncthreads();
 
         // ---- depthwise: thread = 4 channels x 4 consecutive columns (8 rows x 4 strips x 8 groups = 256)
-        if (!(p.ablate & 2)) {
+        {
             const int c4 = (tid & 7) * 4, strip = tid >> 3;
             const int oy = strip >> 2, ox = (strip & 3) * 4;
             f32x4 a[4];
@@ -771,28 +708,14 @@ __device__ __forceinline__ void stem_body(const StemParams& p, float* __restrict
         else __syncthreads();
 
         // ---- project 32 -> 16 on the MFMA: wave handles pixel tiles wave, wave + 4 (8 tiles of 16 px)
-        const int frow = lane & 15, fk = (lane >> 4) * 4;
+        const int frow = lane & 15;
         f32x4 acc[2];
         acc[0] = acc[1] = *reinterpret_cast<const f32x4*>(Hp + (lane >> 4) * 4);
-        if (NP == 0) {
 #pragma unroll
-            for (int kc = 0; kc < ((p.ablate & 4) ? 0 : 2); ++kc) {
-                const f32x4 wa = *reinterpret_cast<const f32x4*>(Wp + frow * kSLD + kc * 16 + fk);
-                f32x4 db[2];
-#pragma unroll
-                for (int q = 0; q < 2; ++q) db[q] = *reinterpret_cast<const f32x4*>(D + ((wave + 4 * q) * 16 + frow) * kSLD + kc * 16 + fk);
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[s], db[q][s], acc[q], 0, 0, 0);
-            }
-        } else if (!(p.ablate & 4)) {
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const float* dr = D + ((wave + 4 * q) * 16 + frow) * kSLD + (lane >> 4) * 8;
-                const BP<NP ? NP : 1> b = splitN<NP ? NP : 1>(*reinterpret_cast<const f32x4*>(dr), *reinterpret_cast<const f32x4*>(dr + 4));
-                acc[q] = mmaN<NP ? NP : 1>(wpb, b, acc[q]);
-            }
+        for (int q = 0; q < 2; ++q) {
+            const float* dr = D + ((wave + 4 * q) * 16 + frow) * kSLD + (lane >> 4) * 8;
+            const BP<NP> b = splitN<NP>(*reinterpret_cast<const f32x4*>(dr), *reinterpret_cast<const f32x4*>(dr + 4));
+            acc[q] = mmaN<NP>(wpb, b, acc[q]);
         }
         // DMA form: the next tile's patch (issued at the top of this tile, a whole tile of work ago) must have LANDED before this wave
         // reaches the barrier that opens the next tile -- waited for here, in front of this tile's stores, so that the wait does not
@@ -817,27 +740,18 @@ __global__ __launch_bounds__(256) void mbv2_stem_kernel(const StemParams p) {
 
 bool stem_supported(const StemParams& p) { return p.H1 >= 1 && p.W1 >= 1; }
 
-// Which form of the stem kernel runs for a net of this precision: 1 = bf16 operands (precision 1), 3 = the split-bf16
-// form (fp32 nets; 115 -> 105 us at B = 64), 0 = the fp32-MFMA form (SSD_STEM_FORM=0: diagnostics)
-int stem_form(int precision) {
-    static const int form = getenv("SSD_STEM_FORM") ? atoi(getenv("SSD_STEM_FORM")) : 3;
-    return precision == 1 ? 1 : (form == 3 ? 3 : 0);
-}
-
 int launch_stem(StemParams p, hipStream_t st) {
     if (p.B == 0) return SSD_OK;
     p.tiles_y = (p.H1 + kSTH - 1) / kSTH;
     p.tiles_x = (p.W1 + kSTW - 1) / kSTW;
     const long tiles = (long)p.B * p.tiles_y * p.tiles_x;
     const long blocks = tiles < 512 ? tiles : 512;           // persistent: 2 workgroups per CU
-    static const int ablate = getenv("SSD_STEM_ABLATE") ? atoi(getenv("SSD_STEM_ABLATE")) : 0;
-    p.ablate = ablate;
-    const int form = stem_form(p.bf16);
-    // the DMA form's source rows must start 16-byte aligned: W % 4 == 0 and a 16-byte aligned batch (SSD_STEM_DMA=0: diagnostics)
-    static const bool want_dma = !(getenv("SSD_STEM_DMA") && atoi(getenv("SSD_STEM_DMA")) == 0);
-    const bool dma = want_dma && p.W % 4 == 0 && (((uintptr_t)p.x) & 15) == 0 && (long)p.H * p.W * 12 < 0x7fffffffL;
-    const auto fn = dma ? (form == 1 ? mbv2_stem_kernel<1, true> : form == 3 ? mbv2_stem_kernel<3, true> : mbv2_stem_kernel<0, true>)
-                        : (form == 1 ? mbv2_stem_kernel<1, false> : form == 3 ? mbv2_stem_kernel<3, false> : mbv2_stem_kernel<0, false>);
+    // operands: bf16 (precision 1) or the split-bf16 form (fp32 nets; 115 -> 105 us at B = 64 against the fp32 MFMA)
+    const bool bf16 = p.bf16 == 1;
+    // the DMA form's source rows must start 16-byte aligned: W % 4 == 0 and a 16-byte aligned batch
+    const bool dma = p.W % 4 == 0 && (((uintptr_t)p.x) & 15) == 0 && (long)p.H * p.W * 12 < 0x7fffffffL;
+    const auto fn = dma ? (bf16 ? mbv2_stem_kernel<1, true> : mbv2_stem_kernel<3, true>)
+                        : (bf16 ? mbv2_stem_kernel<1, false> : mbv2_stem_kernel<3, false>);
     hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(256), 0, st, p);
     SSD_LAUNCH_CHECK();
     return SSD_OK;

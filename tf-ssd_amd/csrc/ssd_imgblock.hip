@@ -28,7 +28,6 @@
 //   acquire by the last arriver; cdna_hip_programming.md "in-launch split-K reduction") -- correct for
 //   any placement, but the one combining CU per image reads its 370-550 KB at ~30 GB/s (14-21 us).
 //   G = 1 (B >= #CUs): direct epilogue, no slabs.
-#include <cstdlib>
 
 #include "ssd_bf16x3.h"
 #include "ssd_conv.h"
@@ -91,13 +90,6 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image_block_kernel(const Fused
     float* Wps = Wes + 2 * kIC * LDW;             // [2][NT*16][kILD]
     float* Ps = Wps + 2 * NT * 16 * kILD;         // [11][CeG]: expand shift, depthwise taps [9], depthwise shift
     int* flag = reinterpret_cast<int*>(Ps + 11 * CeG);
-
-    // diagnostics (ssd_net_profile_fused): per-wave cycles of 0 prologue, 1 barrier wait, 2 depthwise,
-    // 3 project, 4 expand + weight staging, 5 epilogue / combine
-    long long tacc[6] = {0, 0, 0, 0, 0, 0};
-    long long t0 = p.dbg ? clock64() : 0;
-#define ITICK(i) do { if (p.dbg) { const long long t1 = clock64(); tacc[i] += t1 - t0; t0 = t1; } } while (0)
-#define IDUMP() do { if (p.dbg && lane == 0) for (int i_ = 0; i_ < 6; ++i_) p.dbg[((long)blockIdx.x * 8 + wave) * 6 + i_] = tacc[i_]; } while (0)
 
     // ---- weight chunk prefetch (global -> registers -> LDS), one "set" = { Wp(j), We(j + 1) }
     f32x4 wer[WE_R], wpr[WP_R];
@@ -209,7 +201,6 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image_block_kernel(const Fused
             if (NCH == 2) ea[t][NCH - 1] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
         const float* wes = Wes + ((j & 1) * kIC + l15) * LDW + g4 * 4;
-        if (!(p.ablate & 1))
 #pragma unroll
         for (int kc = 0; kc < KC; ++kc) {
             const f32x4 wa = *reinterpret_cast<const f32x4*>(wes + kc * 16);
@@ -243,7 +234,6 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image_block_kernel(const Fused
         for (int ni = 0; ni < NT; ++ni) acc[t][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     expand(0);
-    ITICK(0);
     if (nchunk > 1) {           // set 1 = { Wp(1), We(2) } -> registers
         load_wp(1);
         if (nchunk > 2) load_we(2);
@@ -251,7 +241,6 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image_block_kernel(const Fused
 
     for (int i = 0; i < nchunk; ++i) {
         lds_barrier();          // E(i) and weight set i are visible; everyone is done with interval i - 1
-        ITICK(1);
         if (i + 1 < nchunk) {
             wait_prefetch(wpr);
             store_wp((i + 1) & 1);
@@ -262,13 +251,9 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image_block_kernel(const Fused
                 if (i + 3 < nchunk) load_we(i + 3);
             }
         }
-        ITICK(4);
         // ---- depthwise in MFMA-fragment layout
         f32x4 a[TO];
-        if (p.ablate & 2) {
-#pragma unroll
-            for (int t = 0; t < TO; ++t) a[t] = f32x4{1.f, 1.f, 1.f, 1.f};
-        } else {
+        {
             const f32x4 dh = *reinterpret_cast<const f32x4*>(Ps + 10 * CeG + i * kIC + g4 * 4);
 #pragma unroll
             for (int t = 0; t < TO; ++t) a[t] = dh;
@@ -290,9 +275,8 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image_block_kernel(const Fused
                 for (int e = 0; e < 4; ++e) a[t][e] = __builtin_amdgcn_fmed3f(a[t][e], 0.0f, 6.0f);
         }
         __builtin_amdgcn_sched_barrier(0);
-        ITICK(2);
         // ---- project
-        if (!(p.ablate & 4)) {
+        {
             const float* wps = Wps + ((i & 1) * NT * 16 + l15) * kILD + g4 * 4;
 #pragma unroll
             for (int ni = 0; ni < NT; ++ni) {
@@ -305,9 +289,7 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image_block_kernel(const Fused
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-        ITICK(3);
         if (i + 1 < nchunk) expand(i + 1);
-        ITICK(4);
     }
 
     // ---- epilogue
@@ -326,11 +308,8 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image_block_kernel(const Fused
                 if (p.y_planes) store_planes4(p.y_planes, p.y_plane, p.planes_np, (long)img * Ho * Wo + opo[t], g4 * 4 + ni * 16, (long)B * Ho * Wo, v);
             }
         }
-        ITICK(5);
-        IDUMP();
         return;
     }
-    if (p.ablate & 16) return;
     const long slab_stride = (long)B * Ho * Wo * p.Cout;              // between groups
     {
         float* sp = p.slabs + (long)grp * slab_stride + img_off + g4 * 4;
@@ -343,11 +322,7 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image_block_kernel(const Fused
                 else *reinterpret_cast<f32x4*>(sp + (long)opo[t] * p.Cout + ni * 16) = acc[t][ni];
         }
     }
-    if (!p.tickets) {        // combine by the follow-up kernel (image_combine_kernel): the launch boundary publishes the slabs
-        ITICK(5);
-        IDUMP();
-        return;
-    }
+    if (!p.tickets) return;  // combine by the follow-up kernel (image_combine_kernel): the launch boundary publishes the slabs
     // publish the slab, draw a ticket; the last arriver of the image combines
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -361,11 +336,7 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image_block_kernel(const Fused
         flag[0] = last;
     }
     __syncthreads();
-    if (!flag[0] || (p.ablate & 8)) {
-        ITICK(5);
-        IDUMP();
-        return;
-    }
+    if (!flag[0]) return;
     // last arriver: y = shift + sum of the G partial sums in GROUP order (deterministic whoever
     // arrives last) + residual, as one coalesced pass over the image.  (Measured: this pass runs at
     // ~30 GB/s -- one CU's outstanding-miss budget at the loaded ~2-3 us latency -- whichever way
@@ -394,8 +365,6 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image_block_kernel(const Fused
             *reinterpret_cast<f32x4*>(yo + (long)e * 4) = v;
         }
     }
-    ITICK(5);
-    IDUMP();
 }
 
 
@@ -418,13 +387,6 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image_block_kernel(const Fused
 //     fragment is one ds_read_b128 (reading them straight from L2, the first form of this kernel, measured 72.0 k against
 //     82.0 k images/s in the bf16 mode and spilled 44-730 registers in the NP = 3 form)
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
-#ifdef SSD_IMAGE16_PROF
-#define I16TICK(i) ITICK(i)
-#define I16DUMP() IDUMP()
-#else
-#define I16TICK(i) do {} while (0)
-#define I16DUMP() do {} while (0)
-#endif
 template <int CIN, int NT, int T, int S, int NP>
 __global__ __launch_bounds__(kIThreads) void mbv2_image16_block_kernel(const FusedBlockParams p) {
     static_assert(CIN % 32 == 0, "whole 32-channel k-steps");
@@ -445,10 +407,6 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image16_block_kernel(const Fus
     const int NE = npt * 16 + 2 * P + 2;          // E rows: index q + P + 1, zero rows above / below
     const int CeG = p.Ce / G, cbeg = grp * CeG, nchunk = CeG / kIC;
 
-#ifdef SSD_IMAGE16_PROF                          // diagnostics build only (phases as in the kernel above): the counters cost registers
-    long long tacc[6] = {0, 0, 0, 0, 0, 0};
-    long long t0 = p.dbg ? clock64() : 0;
-#endif
     float* Es = sm;                               // [2][NE][kILD]
     float* Ps = Es + 2 * NE * kILD;               // [11][CeG]: expand shift, depthwise taps [9], depthwise shift
     short* Wes = reinterpret_cast<short*>(Ps + 11 * CeG);      // [2][NP][16][SEH]
@@ -603,14 +561,11 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image16_block_kernel(const Fus
 #pragma unroll
         for (int ni = 0; ni < NT; ++ni) acc[t][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    I16TICK(0);
     expand(0);
     f32x4 dprev[TO];
-    I16TICK(4);
 
     for (int i = 0; i < nchunk; ++i) {
         lds_barrier();          // E(i) is visible; everyone is done with E(i - 1)
-        I16TICK(1);
         const bool odd = i & 1;
         const bool flush = odd || i + 1 == nchunk;
         {
@@ -624,7 +579,6 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image16_block_kernel(const Fus
                 if (i + 2 < nchunk) stage_wp_load((i >> 1) + 1);
             }
         }
-        I16TICK(4);
         // ---- depthwise in MFMA-fragment layout
         f32x4 a[TO];
         {
@@ -648,7 +602,6 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image16_block_kernel(const Fus
 #pragma unroll
                 for (int e = 0; e < 4; ++e) a[t][e] = __builtin_amdgcn_fmed3f(a[t][e], 0.0f, 6.0f);
         }
-        I16TICK(2);
         // ---- project (every second chunk: K = 32)
         if (!flush) {
 #pragma unroll
@@ -669,7 +622,6 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image16_block_kernel(const Fus
                 for (int t = 0; t < TO; ++t) acc[t][ni] = mmaN<NP>(wa, d[t], acc[t][ni]);
             }
         }
-        I16TICK(3);
         if (odd && i + 2 == nchunk) {     // the next chunk is a lone last one: its project reads Wps in its own iteration
             lds_barrier();
             stage_wp_store();
@@ -677,7 +629,6 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image16_block_kernel(const Fus
         if (i + 1 < nchunk) {
             expand(i + 1);
         }
-        I16TICK(4);
     }
 
     // ---- epilogue (fp32): G = 1 direct; G > 1 partial-sum slab, combined by image_combine_kernel
@@ -696,8 +647,6 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image16_block_kernel(const Fus
                 if (p.y_planes) store_planes4(p.y_planes, p.y_plane, p.planes_np, (long)img * Ho * Wo + opo[t], g4 * 4 + ni * 16, (long)B * Ho * Wo, v);
             }
         }
-        I16TICK(5);
-        I16DUMP();
         return;
     }
     const long slab_stride = (long)B * Ho * Wo * p.Cout;
@@ -708,13 +657,7 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image16_block_kernel(const Fus
 #pragma unroll
         for (int ni = 0; ni < NT; ++ni) *reinterpret_cast<f32x4*>(sp + (long)opo[t] * p.Cout + ni * 16) = acc[t][ni];
     }
-    I16TICK(5);
-    I16DUMP();
 }
-#undef ITICK
-#undef IDUMP
-#undef I16TICK
-#undef I16DUMP
 
 // y = shift + sum of the G slabs in group order (+ residual): the combine as its own launch
 __global__ __launch_bounds__(256) void image_combine_kernel(const float* __restrict__ slabs, const float* __restrict__ ph,
@@ -809,8 +752,7 @@ int image_block_groups(const FusedBlockParams& p, int B) {
     }
     const int units = p.Ce / kIC;
     int best = 1;
-    static const int cap = getenv("SSD_IMAGE_GROUPS_CAP") ? atoi(getenv("SSD_IMAGE_GROUPS_CAP")) : 12;   // diagnostics
-    for (int g = 1; g <= 12 && g <= units && g <= cap; ++g) {
+    for (int g = 1; g <= 12 && g <= units; ++g) {
         if (units % g) continue;
         best = g;
         if ((long)B * g * 8 >= (long)num_cu * 7) break;
@@ -831,8 +773,6 @@ int launch_image_block(FusedBlockParams p, hipStream_t st) {
     }
     if (p.B == 0) return SSD_OK;
     if (p.groups < 1) p.groups = 1;
-    static const int ablate = getenv("SSD_IMAGE_ABLATE") ? atoi(getenv("SSD_IMAGE_ABLATE")) : 0;
-    if (!p.ablate) p.ablate = ablate;
     SSD_CHECK_ARG((p.Ce / kIC) % p.groups == 0, "image block: %d groups do not divide Ce/16 = %d", p.groups, p.Ce / kIC);
     SSD_CHECK_ARG(p.groups == 1 || p.slabs, "image block: %d groups need the slab workspace", p.groups);
     if (p.bf16 == 3 && image_lds_bytes(*c, p, p.groups) > 160 * 1024) p.bf16 = 0;      // split form's weight tiles do not fit: fp32 form
@@ -841,7 +781,7 @@ int launch_image_block(FusedBlockParams p, hipStream_t st) {
     SSD_CHECK_ARG(!p.bf16 || (p.we3 && p.wp3), "image block: the bf16 form needs the weights' bf16 planes");
     SSD_CHECK_ARG(!p.bf16 || !p.tickets, "image block: the bf16 form combines by the second launch only");
     const image_kernel_t fn = p.bf16 == 3 ? c->fn3 : p.bf16 ? c->fn16 : c->fn;
-    const bool second = p.form2 && p.bf16 && !p.tickets && !p.ablate && image_block2_supported(p);
+    const bool second = p.form2 && p.bf16 && !p.tickets && image_block2_supported(p);
     if (second) {
         const int rc = launch_image_block2(p, st);
         if (rc) return rc;
@@ -855,7 +795,7 @@ int launch_image_block(FusedBlockParams p, hipStream_t st) {
         hipLaunchKernelGGL(fn, dim3((unsigned)((long)p.B * p.groups)), dim3(kIThreads), lds, st, p);
         SSD_LAUNCH_CHECK();
     }
-    if (p.groups > 1 && !p.tickets && !(p.ablate & 24)) {
+    if (p.groups > 1 && !p.tickets) {
         const long nvec = (long)p.B * p.Ho * p.Wo * p.Cout / 4;
         const int blocks = (int)((nvec + 255) / 256 < 4096 ? (nvec + 255) / 256 : 4096);
         hipLaunchKernelGGL(image_combine_kernel, dim3(blocks), dim3(256), 0, st, p.slabs, p.ph, p.residual ? p.x : nullptr, p.y,

@@ -23,7 +23,6 @@
 // Stride 1, and stride 2 for block 13 (one output pixel per lane, its expanded map -- SSD feature map 1 -- written to HBM from
 // the expand's epilogue); a group takes whole chunk PAIRS (the Ce / 32 pairs dealt as evenly as they go over the groups: no lone last
 // chunk); everything else keeps the first form.
-#include <cstdlib>
 
 #include "ssd_bf16x3.h"
 #include "ssd_conv.h"
@@ -44,8 +43,8 @@ __device__ __forceinline__ void lds_barrier2() { asm volatile("s_waitcnt lgkmcnt
 // Measured and NOT kept (profiles/HISTORY.md, round 6): 12 waves x 2 pixels and 4 waves x 6 pixels (one wave per SIMD, 512
 // registers: 500+ v_accvgpr moves per pair), the pair loop with fenced phases + sched_group_barrier interleave, the two waves
 // of a SIMD walking an iteration in opposite order -- all equal or slower; the loop's time stays the SUM of its matrix, vector
-// and LDS time (phase ablation: tests/micro/imgblock2_prof.py on a -DSSD_IMAGE2_ABLATE build)
-template <int CIN, int NT, int NW, int T, int H, int W, int NP, int LOOP, int ABL, int S = 1>
+// and LDS time (phase timings and phase-removed builds, profiles/HISTORY.md round 6)
+template <int CIN, int NT, int NW, int T, int H, int W, int NP, int LOOP, int S = 1>
 __device__ __forceinline__ void image16v2_body(const FusedBlockParams& p, float* __restrict__ sm2) {
     static_assert(CIN % 32 == 0, "whole 32-channel k-steps");
     constexpr int NTH = NW * 64;
@@ -76,10 +75,6 @@ __device__ __forceinline__ void image16v2_body(const FusedBlockParams& p, float*
     const int npairs = pq + (grp < pr ? 1 : 0), pair0 = grp * pq + min(grp, pr);
     const int cbeg = pair0 * 2 * kC, nchunk = 2 * npairs, CeG = nchunk * kC;
     const int CeGmax = (pq + (pr ? 1 : 0)) * 2 * kC;              // (the LDS layout is the same in every group)
-
-    // diagnostics (ssd_net_profile_fused, p.dbg): shader-clock stamps at the phase boundaries, scalar registers only
-    const long long tk0 = p.dbg ? (long long)__builtin_amdgcn_s_memtime() : 0;
-    long long tk1 = 0, tk2 = 0, tk3 = 0;
 
     float* Es = sm2;                               // [2][NE][ROW]
     float* Ps = Es + 2 * EBUF;                     // [nchunk][11][16]
@@ -150,9 +145,7 @@ __device__ __forceinline__ void image16v2_body(const FusedBlockParams& p, float*
         *reinterpret_cast<f32x4*>(Ps + (j * 11 + row) * kC + r) = *reinterpret_cast<const f32x4*>(src + cbeg + c4);
     }
     dma_wait();
-    if (p.dbg) tk3 = (long long)__builtin_amdgcn_s_memtime();        // own loads + copies landed
     __syncthreads();
-    if (p.dbg) tk1 = (long long)__builtin_amdgcn_s_memtime();
 
     // one address register each: the lane's E row of pixel q0 (+ the buffer / tap / pixel offsets as immediates), its
     // parameter vector, its fragment slot inside a 1 KB weight block
@@ -193,7 +186,7 @@ __device__ __forceinline__ void image16v2_body(const FusedBlockParams& p, float*
 #pragma unroll
             for (int pl = 0; pl < NP; ++pl) wea.p[pl] = *reinterpret_cast<const bf16x8*>(wl + (pl * KS + ks) * 512);
 #pragma unroll
-            for (int t = 0; t < T; ++t) if (!(ABL & 1)) ea[t] = mmaN<NP>(wea, xs[t][ks], ea[t]);
+            for (int t = 0; t < T; ++t) ea[t] = mmaN<NP>(wea, xs[t][ks], ea[t]);
         }
         float* ew = e_wr + pb * EBUF;
 #pragma unroll
@@ -223,14 +216,11 @@ __device__ __forceinline__ void image16v2_body(const FusedBlockParams& p, float*
             for (int dx = 0; dx < 3; ++dx) w[dx] = *reinterpret_cast<const f32x4*>(pc + (1 + (dy + 1) * 3 + dx) * kC);
 #pragma unroll
             for (int j = 0; j < TO + 2; ++j)
-                e[j] = (ABL & 16) ? w[j % 3] : *reinterpret_cast<const f32x4*>(es + (dy * P + j - 1) * ROW);
+                e[j] = *reinterpret_cast<const f32x4*>(es + (dy * P + j - 1) * ROW);
 #pragma unroll
             for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
-                for (int t = 0; t < TO; ++t) {
-                    if (ABL & 2) a[t] += e[t + dx];
-                    else a[t] += e[t + dx] * w[dx];
-                }
+                for (int t = 0; t < TO; ++t) a[t] += e[t + dx] * w[dx];
         }
 #pragma unroll
         for (int t = 0; t < TO; ++t)
@@ -246,21 +236,14 @@ __device__ __forceinline__ void image16v2_body(const FusedBlockParams& p, float*
     auto project = [&](const f32x4 (&a0)[TO], const f32x4 (&a1)[TO]) {
         BP<NP> d[TO];
 #pragma unroll
-        for (int t = 0; t < TO; ++t) d[t] = (ABL & 8) ? xs[t][0] : splitN<NP>(a0[t], a1[t]);
-        if (ABL & 8) {
-#pragma unroll
-            for (int t = 0; t < TO; ++t) asm volatile("" :: "v"(a0[t]), "v"(a1[t]));
-        }
+        for (int t = 0; t < TO; ++t) d[t] = splitN<NP>(a0[t], a1[t]);
 #pragma unroll
         for (int ni = 0; ni < NT; ++ni) {
             BP<NP> wa;
 #pragma unroll
             for (int pl = 0; pl < NP; ++pl) wa.p[pl] = *reinterpret_cast<const bf16x8*>(wp_l + (pl * NT + ni) * 512);
 #pragma unroll
-            for (int t = 0; t < TO; ++t) {
-                if (!(ABL & 4)) acc[t][ni] = mmaN<NP>(wa, d[t], acc[t][ni]);
-                else asm volatile("" :: "v"(d[t].p[0]), "v"(wa.p[0]));
-            }
+            for (int t = 0; t < TO; ++t) acc[t][ni] = mmaN<NP>(wa, d[t], acc[t][ni]);
         }
     };
 
@@ -302,15 +285,6 @@ __device__ __forceinline__ void image16v2_body(const FusedBlockParams& p, float*
         }
     }
 
-    if (p.dbg) tk2 = (long long)__builtin_amdgcn_s_memtime();
-    auto dump = [&]() {          // 0 prologue (own part), 1 prologue barrier wait, 2 first expand + chunk loop, 3 epilogue
-        if (p.dbg && lane == 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            const long long tk4 = (long long)__builtin_amdgcn_s_memtime();
-            long long* o = p.dbg + ((long)blockIdx.x * NW + wave) * 6;
-            o[0] = tk3 - tk0; o[1] = tk1 - tk3; o[2] = tk2 - tk1; o[3] = tk4 - tk2; o[4] = 0; o[5] = 1;
-        }
-    };
     // ---- epilogue (fp32): G = 1 direct; G > 1 partial-sum slab, combined by image_combine_kernel
     const long img_off = (long)img * (Ho * Wo) * p.Cout;
     if (G == 1) {
@@ -327,7 +301,6 @@ __device__ __forceinline__ void image16v2_body(const FusedBlockParams& p, float*
                 if (p.y_planes) store_planes4(p.y_planes, p.y_plane, p.planes_np, (long)img * (Ho * Wo) + opo[t], g4 * 4 + ni * 16, (long)B * (Ho * Wo), v);
             }
         }
-        dump();
         return;
     }
     const long slab_stride = (long)B * (Ho * Wo) * p.Cout;
@@ -338,13 +311,12 @@ __device__ __forceinline__ void image16v2_body(const FusedBlockParams& p, float*
 #pragma unroll
         for (int ni = 0; ni < NT; ++ni) *reinterpret_cast<f32x4*>(sp + (long)opo[t] * p.Cout + ni * 16) = acc[t][ni];
     }
-    dump();
 }
 
-template <int CIN, int NT, int NW, int T, int H, int W, int NP, int LOOP, int ABL = 0, int S = 1>
+template <int CIN, int NT, int NW, int T, int H, int W, int NP, int LOOP, int S = 1>
 __global__ __launch_bounds__(NW * 64) void mbv2_image16v2_kernel(const FusedBlockParams p) {
     extern __shared__ __attribute__((aligned(1024))) float sm2[];
-    image16v2_body<CIN, NT, NW, T, H, W, NP, LOOP, ABL, S>(p, sm2);
+    image16v2_body<CIN, NT, NW, T, H, W, NP, LOOP, S>(p, sm2);
 }
 
 typedef void (*image2_kernel_t)(const FusedBlockParams);
@@ -353,23 +325,14 @@ struct Image2Cfg {
     image2_kernel_t fn1, fn3;       // bf16 mode (NP = 1), split-bf16 form (NP = 3)
 };
 #define I2CFG(CIN, NT, NW, T, H, W, LOOP) {CIN, NT, NW, T, H, W, 1, mbv2_image16v2_kernel<CIN, NT, NW, T, H, W, 1, LOOP>, mbv2_image16v2_kernel<CIN, NT, NW, T, H, W, 3, LOOP>}
-#define I2ABL(A) {64, 4, 8, 3, 19, 19, 1, mbv2_image16v2_kernel<64, 4, 8, 3, 19, 19, 1, 0, A>, mbv2_image16v2_kernel<64, 4, 8, 3, 19, 19, 3, 0, A>}
-#define I2CFG2(CIN, NT, NW, T, H, W, LOOP) {CIN, NT, NW, T, H, W, 2, mbv2_image16v2_kernel<CIN, NT, NW, T, H, W, 1, LOOP, 0, 2>, mbv2_image16v2_kernel<CIN, NT, NW, T, H, W, 3, LOOP, 0, 2>}
-const Image2Cfg kImage2[] = {       // (the first configuration of a shape is the default; SSD_IMAGE2_VARIANT=n picks the n-th: A/B runs)
+#define I2CFG2(CIN, NT, NW, T, H, W, LOOP) {CIN, NT, NW, T, H, W, 2, mbv2_image16v2_kernel<CIN, NT, NW, T, H, W, 1, LOOP, 2>, mbv2_image16v2_kernel<CIN, NT, NW, T, H, W, 3, LOOP, 2>}
+const Image2Cfg kImage2[] = {       // (one loop form per shape)
     I2CFG(64, 4, 8, 3, 19, 19, 1),     // blocks 7-9:   64 -> 384 -> 64 at 19x19
-    I2CFG(64, 4, 8, 3, 19, 19, 0),
-#ifdef SSD_IMAGE2_ABLATE               // diagnostics build: variants 2 .. 7 = the single-chunk loop with phases removed (wrong results)
-    I2ABL(1), I2ABL(2), I2ABL(4), I2ABL(8), I2ABL(16), I2ABL(31),
-#endif
     I2CFG(64, 6, 8, 3, 19, 19, 1),     // block 10:     64 -> 384 -> 96
-    I2CFG(64, 6, 8, 3, 19, 19, 0),
     I2CFG(96, 6, 8, 3, 19, 19, 0),     // blocks 11-12: 96 -> 576 -> 96 (the pair loop spills 84 registers here: 86 us against 52)
     I2CFG2(96, 10, 8, 3, 19, 19, 0),   // block 13:     96 -> 576 -> 160, depthwise stride 2 (19x19 -> 10x10), E written out
-    I2CFG2(96, 10, 8, 3, 19, 19, 1),
     I2CFG(160, 10, 8, 1, 10, 10, 1),   // blocks 14-15: 160 -> 960 -> 160 at 10x10
-    I2CFG(160, 10, 8, 1, 10, 10, 0),
     I2CFG(160, 20, 8, 1, 10, 10, 1),   // block 16:     160 -> 960 -> 320
-    I2CFG(160, 20, 8, 1, 10, 10, 0),
 };
 
 
@@ -381,30 +344,27 @@ size_t image2_lds_bytes(const Image2Cfg& c, const FusedBlockParams& p, int G) {
     return ((size_t)2 * NE * row + (size_t)11 * cmax) * sizeof(float) + w;
 }
 
-const Image2Cfg* pick_image2(const FusedBlockParams& p, int variant) {
+const Image2Cfg* pick_image2(const FusedBlockParams& p) {
     if (!p.bf16 || p.Ce % (2 * kC) != 0 || p.kpad_e % 32 != 0 || p.kpad_p % 32 != 0) return nullptr;
     if (p.stride == 1 && (p.e_out || p.H != p.Ho || p.W != p.Wo)) return nullptr;
     if (p.stride == 2 && (p.residual || p.Ho != (p.H + 1) / 2 || p.Wo != (p.W + 1) / 2 || p.pad_t < 0 || p.pad_t > 1 || p.pad_l < 0 || p.pad_l > 1)) return nullptr;
     if (p.stride != 1 && p.stride != 2) return nullptr;
     if (p.residual && p.Cin != p.Cout) return nullptr;
-    int seen = 0;
     for (const auto& c : kImage2)
-        if (c.cin == p.Cin && c.nt * 16 == p.Cout && c.h == p.H && c.w == p.W && c.stride == p.stride && p.kpad_e == c.cin && p.npad_p >= c.nt * 16 && seen++ == variant) return &c;
+        if (c.cin == p.Cin && c.nt * 16 == p.Cout && c.h == p.H && c.w == p.W && c.stride == p.stride && p.kpad_e == c.cin && p.npad_p >= c.nt * 16) return &c;
     return nullptr;
 }
 
 }  // namespace
 
 bool image_block2_supported(const FusedBlockParams& p) {
-    const Image2Cfg* c = pick_image2(p, 0);
+    const Image2Cfg* c = pick_image2(p);
     const int G = p.groups < 1 ? 1 : p.groups;
     return c && p.we3 && p.wp3 && G <= p.Ce / (2 * kC) && image2_lds_bytes(*c, p, G) <= 160 * 1024;
 }
 
 int launch_image_block2(FusedBlockParams p, hipStream_t st) {
-    static const int variant = getenv("SSD_IMAGE2_VARIANT") ? atoi(getenv("SSD_IMAGE2_VARIANT")) : 0;
-    const Image2Cfg* c = pick_image2(p, variant);
-    if (!c) c = pick_image2(p, 0);
+    const Image2Cfg* c = pick_image2(p);
     if (!c) {
         set_error("image block (second form): unsupported shape Cin=%d Ce=%d Cout=%d %dx%d stride=%d", p.Cin, p.Ce, p.Cout, p.H, p.W, p.stride);
         return SSD_E_UNSUPPORTED;

@@ -39,7 +39,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("SSD_HIP_LIBRARY") or os.path.join(_HERE, "libssd_hip.so")   # override: diagnostic builds
+LIB_PATH = os.environ.get("SSD_HIP_LIBRARY") or os.path.join(_HERE, "libssd_hip.so")   # override: another build of the library
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 c_int_p = ctypes.POINTER(ctypes.c_int)
@@ -139,7 +139,6 @@ _SIGNATURES = {
     "ssd_net_layer_bytes": (ctypes.c_double, [vp, ctypes.c_int, ctypes.c_int]),
     "ssd_net_layer_executed_flops": (ctypes.c_double, [vp, ctypes.c_int, ctypes.c_int]),
     "ssd_net_set_option": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_int]),
-    "ssd_net_profile_fused": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     "ssd_net_set_timing": (ctypes.c_int, [vp, ctypes.c_int]),
     "ssd_net_read_timing": (ctypes.c_int, [vp, c_float_p, c_int_p]),
     "ssd_net_profile_layers": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_float_p, vp]),
