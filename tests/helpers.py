@@ -47,6 +47,16 @@ def images(B, S=300, seed=0):
     return np.random.default_rng(seed).random((B, S, S, 3), dtype=np.float32)
 
 
+def block_test_images(B, S=300, seed=29, gain=1.0):
+    """Inputs of the block-oracle tests, built as the fused-block tests build theirs: 8 seeded images, tiled up to B and
+    scaled per image (0.5 .. 1.0) so that no two images of a batch are equal; ``gain`` multiplies the whole batch (8: the
+    upper clamp of every ReLU6 fires, stem and blocks 1-2 included)."""
+    x = images(min(B, 8), S, seed=seed)
+    if B > 8:
+        x = np.concatenate([x] * ((B + 7) // 8))[:B] * np.linspace(0.5, 1.0, B, dtype=np.float32)[:, None, None, None]
+    return x * np.float32(gain) if gain != 1.0 else x
+
+
 _WCACHE = {}
 
 

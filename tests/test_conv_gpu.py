@@ -767,8 +767,8 @@ def test_image_block_split_form_vs_layer_kernels(B, second):
     """(``second`` = option image_v2: the kernel's second form, csrc/ssd_imgblock2.hip -- compile-time geometry, adjacent
     pixels per lane, LDS-DMA weight chunks, chunk pairs dealt unevenly over the groups: B = 3 / 24 give 12 / 8 groups of
     2 - 4 pairs, B = 232 the direct one-group epilogue with the residual -- or the first form for every block; block 13,
-    stride 2, keeps the first form either way.  The two forms agree within tolerance, not bitwise: the k-slot order inside
-    the project MFMAs differs.)
+    stride 2, has a second-form configuration of its own (kImage2's stride-2 entry) and follows the option like the
+    rest.  The two forms agree within tolerance, not bitwise: the k-slot order inside the project MFMAs differs.)
     The whole-image kernel's split-bf16 form (img_choice 2: both 1x1 convolutions as exact three-way bf16 splits,
     six v_mfma_f32_16x16x32_bf16 per product, fp32 results; weights staged through LDS) pinned on every block it can
     run -- the finalize-time race only keeps it where it wins -- against the layer kernels, to the fp32 kernels' own
