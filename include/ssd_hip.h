@@ -112,6 +112,25 @@ int ssd_match_encode(const float* priors_dev, const float* gt_boxes_dev,
                      int* label_idx_out_dev, int* match_idx_out_dev, float* onehot_out_dev,
                      void* stream);
 
+/* ---- detection scoring: utils/eval_utils.py:20-50 (N2), the per-image part of update_stats ----
+ * det_boxes [B,T,4], det_labels [B,T] (float class id, 0 = padding row), det_scores [B,T],
+ * gt_boxes [B,G,4], gt_labels [B,G] int32 (-1 = padding), all device.  Per image: best IoU and
+ * FIRST arg-max over the G boxes (running maximum from -inf, strict >: a NaN IoU never wins; the
+ * IoU bits are ssd_iou_map's); detections visited in descending best IoU, equal keys by ascending
+ * index; label-0 rows leave no record; a record is a true positive iff best IoU >= iou_thr, its
+ * label equals the label of its best box and no earlier-visited record took that box.
+ * Outputs (device, fully overwritten, rows at or after the count are zero): rec_class_out [B,T]
+ * int32, rec_score_out [B,T], rec_tp_out [B,T] int32 (1 = TP, 0 = FP) in visit order;
+ * rec_det_out (nullable) [B,T] int32 the detection index behind each record; rec_count_out [B]
+ * int32 records per image.
+ * Supported: 0 <= T <= 1024, 1 <= G <= 256 (one workgroup per image, all keys in LDS); anything
+ * else returns SSD_E_UNSUPPORTED before any launch.  B == 0 is a no-op. */
+int ssd_eval_match(const float* det_boxes_dev, const float* det_labels_dev,
+                   const float* det_scores_dev, const float* gt_boxes_dev,
+                   const int* gt_labels_dev, int B, int T, int G, float iou_thr,
+                   int* rec_class_out, float* rec_score_out, int* rec_tp_out, int* rec_det_out,
+                   int* rec_count_out, void* stream);
+
 /* ---- input pipeline: utils/data_utils.py:22-23 (N4) ---------------------------------------
  * tf.image.convert_image_dtype(uint8 -> float32, x 1/255) + tf.image.resize(bilinear, TF2
  * half-pixel centres, no antialias) in one kernel.  image_u8 [B,H,W,C] uint8 (device) ->

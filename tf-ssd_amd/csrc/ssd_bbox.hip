@@ -500,6 +500,92 @@ __global__ __launch_bounds__(256) void match_encode_kernel(
     }
 }
 
+// ------------------------------------------------------------------ detection scoring (N2)
+// utils/eval_utils.py:20-50 for one image per 256-thread block.  The reference walks the detections serially in
+// descending best-IoU order and remembers the ground-truth boxes already taken; here every detection finds its own
+// place in that walk by counting (its record index = the number of non-padding detections visited before it) and the
+// "already taken" test becomes "am I the first ELIGIBLE record on my box" (eligible: IoU >= thr and labels agree),
+// resolved by an integer atomicMin on the record index in LDS -- order-independent, so the result is deterministic.
+// LDS: G * 24 B (boxes, labels, first record) + T * 16 B (key, label, arg-max, record index).
+constexpr int kEvalMaxT = 1024;
+constexpr int kEvalMaxG = 256;
+
+__global__ __launch_bounds__(256) void eval_match_kernel(
+    const float4* __restrict__ det, const float* __restrict__ det_labels, const float* __restrict__ det_scores,
+    const float4* __restrict__ gt, const int* __restrict__ gt_labels, const int T, const int G, const float iou_thr,
+    int* __restrict__ rec_class, float* __restrict__ rec_score, int* __restrict__ rec_tp, int* __restrict__ rec_det,
+    int* __restrict__ rec_count) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float4* s_gt = reinterpret_cast<float4*>(smem);          // [G]
+    int* s_glab = reinterpret_cast<int*>(s_gt + G);          // [G]
+    int* s_first = s_glab + G;                               // [G] record index of the first eligible detection
+    float* s_key = reinterpret_cast<float*>(s_first + G);    // [T] best IoU
+    float* s_lab = s_key + T;                                // [T] detection label
+    int* s_arg = reinterpret_cast<int*>(s_lab + T);          // [T] arg-max ground-truth box
+    int* s_pos = s_arg + T;                                  // [T] record index
+    __shared__ int s_count;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    for (int g = tid; g < G; g += 256) {
+        s_gt[g] = gt[(size_t)b * G + g];
+        s_glab[g] = gt_labels[(size_t)b * G + g];
+        s_first[g] = T;
+    }
+    if (tid == 0) s_count = 0;
+    __syncthreads();
+    // :20-22 [3P] tf.reduce_max / tf.argmax (Eigen reducers): start at -inf, strict >: first max, NaN never selected
+    for (int t = tid; t < T; t += 256) {
+        const float4 p = det[(size_t)b * T + t];
+        int am = 0;
+        float best = -__builtin_inff();
+        for (int g = 0; g < G; ++g) {
+            const float v = pair_iou(p, s_gt[g]);
+            if (v > best) { best = v; am = g; }
+        }
+        s_key[t] = best;
+        s_arg[t] = am;
+        s_lab[t] = det_labels[(size_t)b * T + t];
+    }
+    __syncthreads();
+    // :23 argsort DESCENDING (equal keys by ascending index), :35-36 label 0 skipped
+    for (int t = tid; t < T; t += 256) {
+        const float lab = s_lab[t];
+        if (lab == 0.0f) continue;
+        const float kt = s_key[t];
+        int pos = 0;
+        for (int u = 0; u < T; ++u) {
+            const float ku = s_key[u];
+            const bool before = ku > kt || (ku == kt && u < t);
+            pos += (before && s_lab[u] != 0.0f) ? 1 : 0;
+        }
+        s_pos[t] = pos;
+        const int am = s_arg[t];
+        if (kt >= iou_thr && (int)lab == s_glab[am]) atomicMin(&s_first[am], pos);
+        atomicAdd(&s_count, 1);
+    }
+    __syncthreads();
+    const int count = s_count;
+    if (tid == 0) rec_count[b] = count;
+    // :37-50
+    for (int t = tid; t < T; t += 256) {
+        const float lab = s_lab[t];
+        if (lab == 0.0f) continue;
+        const int pos = s_pos[t], am = s_arg[t];
+        const bool hit = s_key[t] >= iou_thr && (int)lab == s_glab[am] && s_first[am] == pos;
+        const size_t o = (size_t)b * T + pos;
+        rec_class[o] = (int)lab;
+        rec_score[o] = det_scores[(size_t)b * T + t];
+        rec_tp[o] = hit ? 1 : 0;
+        if (rec_det) rec_det[o] = t;
+    }
+    for (int r = count + tid; r < T; r += 256) {
+        const size_t o = (size_t)b * T + r;
+        rec_class[o] = 0;
+        rec_score[o] = 0.0f;
+        rec_tp[o] = 0;
+        if (rec_det) rec_det[o] = 0;
+    }
+}
+
 // ------------------------------------------------------------------ host side
 struct NmsWs {
     int* cand_count;
@@ -763,6 +849,26 @@ int ssd_match_encode(const float* priors_dev, const float* gt_boxes_dev, const i
                        (hipStream_t)stream, (const float4*)priors_dev, (const float4*)gt_boxes_dev,
                        gt_labels_dev, v4, iou_thr, N, G, L, (float4*)deltas_out_dev, label_idx_out_dev,
                        match_idx_out_dev, onehot_out_dev);
+    SSD_LAUNCH_CHECK();
+    return SSD_OK;
+}
+
+int ssd_eval_match(const float* det_boxes_dev, const float* det_labels_dev, const float* det_scores_dev,
+                   const float* gt_boxes_dev, const int* gt_labels_dev, int B, int T, int G, float iou_thr,
+                   int* rec_class_out, float* rec_score_out, int* rec_tp_out, int* rec_det_out, int* rec_count_out,
+                   void* stream) {
+    SSD_CHECK_ARG(B >= 0 && T >= 0 && G >= 0, "ssd_eval_match: B=%d T=%d G=%d", B, T, G);
+    SSD_UNSUPPORTED_IF(T > kEvalMaxT, "ssd_eval_match: T=%d exceeds %d detections per image", T, kEvalMaxT);
+    SSD_UNSUPPORTED_IF(G < 1 || G > kEvalMaxG, "ssd_eval_match: G=%d outside 1..%d ground-truth boxes per image", G,
+                       kEvalMaxG);
+    if (B == 0) return SSD_OK;
+    SSD_CHECK_ARG(gt_boxes_dev && gt_labels_dev && rec_count_out, "ssd_eval_match: NULL pointer");
+    SSD_CHECK_ARG(T == 0 || (det_boxes_dev && det_labels_dev && det_scores_dev && rec_class_out && rec_score_out &&
+                             rec_tp_out), "ssd_eval_match: NULL pointer");
+    hipLaunchKernelGGL(eval_match_kernel, dim3(B), dim3(256), (size_t)G * 24 + (size_t)T * 16, (hipStream_t)stream,
+                       (const float4*)det_boxes_dev, det_labels_dev, det_scores_dev, (const float4*)gt_boxes_dev,
+                       gt_labels_dev, T, G, iou_thr, rec_class_out, rec_score_out, rec_tp_out, rec_det_out,
+                       rec_count_out);
     SSD_LAUNCH_CHECK();
     return SSD_OK;
 }

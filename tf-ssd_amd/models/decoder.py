@@ -258,8 +258,12 @@ class DecoderModel(object):
         batch): the lane then does not wait for the caller's stream.  (Measured: the per-step event that
         ``wait_stream`` records on the caller's -- legacy NULL -- stream costs the whole gain of the second
         lane, 1.81 vs 1.62 ms per step at B=64.)"""
+        return self._submit(images, sync_input)[:3]
+
+    def _submit(self, images, sync_input=True):
+        """``submit`` plus the stream the step was enqueued on (None: the caller's current stream)."""
         if self.lanes == 1 or not hasattr(self.base_model, "predict_on_device"):
-            return self(images)
+            return tuple(self(images)) + (None,)
         d = self.decoder
         # a PINNED host batch (torch CPU tensor, ``ssd_hip.pinned_empty``) is copied by the lane itself: the H2D DMA is
         # queued on the lane's stream in front of its step, so it runs beside the other lanes' kernels and the host
@@ -324,7 +328,7 @@ class DecoderModel(object):
         for t in (x, b, l, s, v):
             t.record_stream(st)
         d.last_valid_detections = v
-        return b, l, s
+        return b, l, s, st
 
     def _resident_float(self, images_u8):
         from utils import data_utils
@@ -421,6 +425,71 @@ class DecoderModel(object):
             T = int(self.decoder.max_total_size)
             return (np.zeros((0, T, 4), np.float32), np.zeros((0, T), np.float32), np.zeros((0, T), np.float32))
         return tuple(np.concatenate(a, 0) for a in outs)
+
+    @staticmethod
+    def _upload_ground_truth(gt_boxes, gt_labels):
+        """Ground truth of one batch as device tensors, the upload queued on the current stream: host arrays go through
+        page-locked staging blocks (torch's caching host allocator recycles a block once its copy ran), so the host
+        does not wait for the stream; device tensors are used where they are."""
+        out = []
+        for a, dt in ((gt_boxes, torch.float32), (gt_labels, torch.int32)):
+            if isinstance(a, torch.Tensor) and a.is_cuda:
+                a = a.to(dtype=dt).contiguous()
+            else:
+                h = torch.as_tensor(np.ascontiguousarray(np.asarray(a))).to(dt)
+                stage = torch.empty(h.shape, dtype=dt, pin_memory=True)
+                stage.copy_(h)
+                a = torch.empty(h.shape, dtype=dt, device=_h.device())
+                a.copy_(stage, non_blocking=True)
+            out.append(a)
+        return out
+
+    def evaluate(self, dataset, labels, steps=None, verbose=0):
+        """Streaming VOC07 mAP over ``dataset``, an iterable of ``(images, gt_boxes, gt_labels)`` padded batches
+        (reference predictor.py:43-55 in one pass); ``labels`` is the class-name list, background first.  Every step
+        goes the way ``predict`` sends it (lanes when they are in use, else one step at a time); the batch's ground
+        truth is uploaded and ``ssd_eval_match`` enqueued on the stream that produced the detections, on the device
+        tensors of that step.  Detections and IoUs never reach the host: the record arrays are copied out after the
+        last batch, appended with ``eval_utils.stats_from_records`` and scored by ``calculate_mAP``.
+        Returns ``(stats, mAP)``."""
+        from utils import eval_utils
+        try:
+            n_batches = len(dataset)
+        except TypeError:
+            n_batches = None
+        if steps is not None:
+            n_batches = steps if n_batches is None else min(n_batches, steps)
+        use_lanes = self.lanes > 1 and not (self.auto_lanes and n_batches is not None and n_batches < 2 * self.lanes)
+        stats = eval_utils.init_stats(labels)
+        pending, gt_seen = [], []
+        done = 0
+        cur = torch.cuda.current_stream()
+        for images, gt_boxes, gt_labels in dataset:
+            if steps is not None and done >= steps:
+                break
+            b, l, s, st = self._submit(images) if use_lanes else (tuple(self(images)) + (None,))
+            if st is None:
+                st = cur
+            elif any(isinstance(a, torch.Tensor) and a.is_cuda for a in (gt_boxes, gt_labels)):
+                st.wait_stream(cur)                    # resident ground truth was produced on the caller's stream
+            with torch.cuda.stream(st):
+                g, gl = self._upload_ground_truth(gt_boxes, gt_labels)
+                rec = eval_utils.match_detections(b, l, s, g, gl)
+            for t in (g, gl) + tuple(rec):
+                t.record_stream(st)
+            pending.append(rec)
+            gt_seen.append(gt_labels)
+            done += 1
+            if verbose:
+                print("\r%d/%s" % (done, steps if steps is not None else "?"), end="", flush=True)
+        if verbose:
+            print()
+        if pending:
+            self.wait()
+            cur.synchronize()
+            host = [np.concatenate([r[k].cpu().numpy() for r in pending], 0) for k in range(4)]
+            eval_utils.stats_from_records(host[0], host[1], host[2], host[3], gt_seen, stats)
+        return eval_utils.calculate_mAP(stats)
 
 
 def default_lanes():

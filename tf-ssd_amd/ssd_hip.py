@@ -74,6 +74,7 @@ _SIGNATURES = {
     "ssd_encode_deltas": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]),
     "ssd_match_encode": (ctypes.c_int, [vp, vp, vp, c_float_p, ctypes.c_float] + [ctypes.c_int] * 4 +
                          [vp, vp, vp, vp, vp]),
+    "ssd_eval_match": (ctypes.c_int, [vp] * 5 + [ctypes.c_int] * 3 + [ctypes.c_float] + [vp] * 6),
     "ssd_preprocess": (ctypes.c_int, [vp] + [ctypes.c_int] * 6 + [vp, vp]),
     "ssd_image_mean": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp, vp, vp]),
     "ssd_augment_geometry": (ctypes.c_int, [vp] + [ctypes.c_int] * 6 + [vp, vp, vp, vp]),
@@ -163,6 +164,10 @@ class SsdHipError(RuntimeError):
     pass
 
 
+class SsdHipUnsupported(SsdHipError):
+    """SSD_E_UNSUPPORTED: valid in the reference, outside this build's limits (nothing was launched)."""
+
+
 def lib():
     """Load libssd_hip.so (no GPU needed for loading).  Raises if it was not built."""
     global _lib
@@ -185,6 +190,8 @@ def check(rc, what=""):
         msg = lib().ssd_last_error().decode()
         if rc == -1:
             raise ValueError("%s: %s" % (what, msg))
+        if rc == -3:
+            raise SsdHipUnsupported("%s failed (%d): %s" % (what, rc, msg))
         raise SsdHipError("%s failed (%d): %s" % (what, rc, msg))
 
 
