@@ -15,6 +15,11 @@ namespace ssd {
 enum LayerKind { LK_CONV = 0, LK_DW, LK_POOL, LK_L2NORM, LK_SOFTMAX, LK_FUSED };
 static const char* kKindName[] = {"conv", "dw", "pool", "l2norm", "softmax", "fused"};
 
+// Which kernel runs a layer.  RT_OFF: none (a fused layer that is switched off or whose shape no fused kernel takes; a
+// member of a fused layer that runs).  RT_LAYER: the layer's own kernel (conv / dw / pool / l2norm / softmax).  The
+// rest are the kernel families of an LK_FUSED layer; the precision suffix of their names follows ssd_net::precision.
+enum Route { RT_OFF = 0, RT_LAYER, RT_STEM, RT_DWPROJ, RT_TILE, RT_BAND, RT_BAND3, RT_IMAGE, RT_IMAGE_SPLIT };
+
 struct Param {
     std::string name;
     std::vector<int> shape;
@@ -32,7 +37,7 @@ struct Tensor {
     // the same activation as bf16 planes [planes_np][plane_stride] for the LDS-DMA conv tiles of its consumers
     // (csrc/ssd_convdma.hip): allocated at finalize for every tensor a dense conv with Cin % 32 == 0 reads (option
     // "conv_dma"), WRITTEN -- by the producer's epilogue or by split_planes_kernel -- only while a running consumer's
-    // chosen configuration is an LDS-DMA tile (planes_live, recomputed per forward)
+    // chosen configuration is an LDS-DMA tile (planes_live, recomputed with the launch plan)
     short* planes = nullptr;
     long plane_stride = 0;    // elements between planes
     int planes_np = 0;        // 3: exact split h, m, l (fp32 nets); 1: bf16 rounding (the bf16 mode)
@@ -66,15 +71,28 @@ struct Layer {
     int f_type = 0;                 // 0: inverted-residual block, 1: stem (Conv1 -> dw -> project),
                                     // 2: depthwise + project (the expand conv stays a GEMM of its own)
     int fused_by = -1;
- int e_out = -1;                 // whole-block LK_FUSED layer that must ALSO materialise its expanded map: that tensor
+    int e_out = -1;                 // whole-block LK_FUSED layer that must ALSO materialise its expanded map: that tensor
+                                    // (block 13, whose expanded map is SSD feature map #1)
     int img_choice = -1;            // whole-block LK_FUSED layers the image kernel can run: 1 / 2 = its fp32-MFMA / split-bf16 form won the finalize-time race against the layer kernels, 0 = it lost, -1 = not timed
     int fused_by2 = -1;             // depthwise / project members: their type-2 LK_FUSED layer
+    Route route = RT_OFF;           // what runs this layer under the current options and tuning choices (resolve_routes, ssd_net.hip)
     float* splitk_part = nullptr;   // this layer's own split-K slab (layers may run concurrently)
     // LK_FUSED: weight copies with the folded BatchNorm scale multiplied in (per output channel)
     float *fz_we = nullptr, *fz_wd = nullptr, *fz_wp = nullptr;
     float *fz_we3 = nullptr, *fz_wp3 = nullptr;      // bf16 planes of fz_we / fz_wp for the split-bf16 band kernel (ssd_band3.hip)
     int side = 0;                   // 1, 2: runs on that side stream (SSD head convs)
     hipEvent_t ev_ready = nullptr;  // recorded on the main stream when this layer's OUTPUT is complete
+};
+
+// One launch of the forward's plan (plan_steps, ssd_net.hip): a pure function of the graph, the options, the
+// routes and `timing`, built at the first forward that needs it and kept until ssd_net::drop_graphs().
+struct Step {
+    int layer = -1;
+    int sid = -1;                   // stream: -1 the caller's (main), 0 / 1 ssd_net::side[]
+    int wait[2] = {-1, -1};         // layers on another stream that produce its input / residual: wait for their ev_ready
+    bool after_main = false;        // first work of a side stream whose input no layer produces: ordered behind the main stream
+    bool publishes = false;         // a consumer runs on another stream: record ev_ready behind it
+    bool join_first = false;        // the softmax: the side streams join the main stream in front of it
 };
 
 }  // namespace ssd
@@ -99,7 +117,6 @@ struct ssd_net {
     int fuse_band = 2;              // blocks 1-6: 2 row-band kernel with the 1x1 convs on the bf16 matrix cores through an exact 3-way split (ssd_band3.hip), 1 row-band kernel on the fp32 MFMA (ssd_bandblock.hip), 0 the 8x8-tile kernel
     int fuse_image = 1;             // whole-image block kernel (ssd_imgblock.hip): 0 never, 1 where it won the finalize-time race, 2 wherever it applies
     int lanes_hint = 1;             // replicas of this net running concurrently (lanes): the whole-image kernel then splits an image's expanded channels over fewer workgroups (B x groups x lanes fills the CUs; fewer slab passes)
-    int tail_prio = 0;              // 1: extras tail on side[2] (highest priority); 2: its small heads too
     bool tail_on_side = false;      // diagnostics: big heads on the main stream, extras tail + small heads on the side streams
     bool image_split = true;        // fp32 nets: the finalize-time race also times the image kernel's split-bf16 form (img_choice 2; option "image_split" 0: leave it out)
     bool image_v2 = true;           // whole-image kernel: the second form (ssd_imgblock2.hip: compile-time geometry, adjacent pixels per lane) where it has a configuration; 0 = the first form (A/B; equal within tolerance, not bitwise: the k-slot order inside the project MFMAs differs)
@@ -122,7 +139,6 @@ struct ssd_net {
     int nms_ws_batch = 0;           // the batch the workspace was carved (and its candidate counters zeroed) for
     int nms_ws_total = 0;           // ... and the max_total it was carved for
     int scratch_batch = 0;          // batch capacity deltas/probs were allocated for
-    // optional per-layer hipEvent timing of forward()/predict() (bench.py roofline leg)
     std::map<std::string, std::pair<std::string, int>> preset;   // layer -> (config name, split_k)
     int n_preset = 0;               // conv layers the last finalize took from preset lines
     int n_autotuned = 0;            // choices the last finalize timed on the device (0 = fully reproducible table)
@@ -146,11 +162,12 @@ struct ssd_net {
     // the head convs only depend on their feature map: they run on `side` concurrently with the
     // rest of the backbone / extras (fork after the producer, join before the softmax)
     bool overlap_heads = true;
-    static constexpr int kSides = 3;       // [2]: highest-priority stream for the latency-bound extras tail (option tail_prio)
-    hipStream_t side[kSides] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev_side_done[kSides] = {nullptr, nullptr, nullptr};
+    static constexpr int kSides = 2;
+    hipStream_t side[kSides] = {nullptr, nullptr};
+    hipEvent_t ev_side_done[kSides] = {nullptr, nullptr};
+    std::vector<ssd::Step> steps;       // the forward's launch plan (empty: not built for the current state)
     float* splitk_layers = nullptr;     // per-layer split-K slabs (post-autotune)
-    bool timing = false;
+    bool timing = false;                // optional per-layer hipEvent timing of forward()/predict() (bench.py roofline leg)
     ssd_train_state* train = nullptr;    // training step state (csrc/ssd_train.hip), lazily created
     std::vector<std::vector<hipEvent_t>> timing_events;   // one vector of (layers + 2) events per forward
 
@@ -177,7 +194,9 @@ struct ssd_net {
             if (l.ev_ready) (void)hipEventDestroy(l.ev_ready);
         if (splitk_layers) (void)hipFree(splitk_layers);
     }
+    // whatever a captured graph bakes in has changed: drop the graphs, and the launch plan with them
     void drop_graphs() {
+        steps.clear();
         for (auto& g : graphs) {
             if (g.exec) (void)hipGraphExecDestroy(g.exec);
             if (g.graph) (void)hipGraphDestroy(g.graph);
