@@ -139,6 +139,37 @@ int ssd_eval_match(const float* det_boxes_dev, const float* det_labels_dev,
 int ssd_preprocess(const unsigned char* image_u8_dev, int B, int H, int W, int C, int out_h, int out_w,
                    float* out_dev, void* stream);
 
+/* ---- custom images: utils/data_utils.py:93-108 (PIL Image.resize(..., Image.LANCZOS) + convert_image_dtype) ----------
+ * [3P] Pillow's 8-bit resampler (ImagingResample, 8bpc), reproduced bit for bit: a separable two-pass filter in 22-bit
+ * fixed point.  Horizontal pass first (skipped when W == out_w), vertical pass second (skipped when H == out_h), each
+ *     u8 = clamp((2^21 + sum_x px[xmin + x] * k[x]) >> 22, 0, 255),  x in [0, xmax)        (int32, arithmetic shift)
+ * with a uint8 intermediate between them; then out = (float)u8 * (float)(1.0 / 255.0), what ssd_preprocess writes at
+ * equal sizes.  The coefficients are the caller's (float64 on the host, as Pillow computes them:
+ * utils/data_utils.lanczos_coefficients): per axis and (in, out) pair a table bounds [out][2] int32 = {xmin, xmax} and
+ * k [out][ksize] int32, anywhere in tables_dev [tables_ints] int32.
+ * One call resizes B images of DIFFERENT sizes (uint8 [H,W,3], packed at desc[b].src_offset of src_dev [src_bytes]) into
+ * out_dev [B,out_h,out_w,3] float32 and, when out_u8_dev is not NULL, out_u8_dev [B,out_h,out_w,3] uint8.  desc_host and
+ * desc_dev are the same B descriptors in host and in device memory (the host copy sizes the grids and is checked; the
+ * kernels read the device copy).  h_* are ignored when W == out_w, v_* when H == out_h.  tmp_offset: where the image's
+ * intermediate (H rows of ssd_resize_lanczos_pitch(out_w) bytes) lives in the workspace, a multiple of 16, images not
+ * overlapping (ignored when W == out_w); ssd_resize_lanczos_workspace_bytes is the size when they are packed in order,
+ * each rounded up to 16 bytes.
+ * Supported: C == 3, every side (H, W, out_h, out_w) in 1..16384, B <= 65535; anything else returns SSD_E_UNSUPPORTED
+ * before any launch.  B == 0 is a no-op.  Table rows are clipped to the image inside the kernels. */
+struct ssd_resize_desc {
+    long long src_offset; /* byte offset of the image in src_dev                                       */
+    long long tmp_offset; /* byte offset of its intermediate in the workspace                          */
+    int H, W;
+    int h_bounds, h_k, h_ksize; /* int32 offsets into tables_dev of bounds [out_w][2], k [out_w][h_ksize] */
+    int v_bounds, v_k, v_ksize; /* ... of bounds [out_h][2], k [out_h][v_ksize]                           */
+};
+int ssd_resize_lanczos_pitch(int out_w);
+size_t ssd_resize_lanczos_workspace_bytes(const struct ssd_resize_desc* desc_host, int B, int out_h, int out_w);
+int ssd_resize_lanczos(const unsigned char* src_dev, size_t src_bytes, const int* tables_dev, size_t tables_ints,
+                       const struct ssd_resize_desc* desc_host, const struct ssd_resize_desc* desc_dev, int B, int C,
+                       int out_h, int out_w, float* out_dev, unsigned char* out_u8_dev, void* workspace_dev,
+                       size_t workspace_bytes, void* stream);
+
 /* ---- augmentation: augmentation.py:4-183 (used at trainer.py:42), the deterministic pieces; the random draws of the
  * reference's tf.random.uniform / sample_distorted_bounding_box calls are INPUTS (host side: tf-ssd_amd/augmentation.py).
  * Images float32 [B,H,W,C] in [0,1] (the reference augments after convert + resize).

@@ -7,6 +7,8 @@
 // src = (dst + 0.5) * scale - 0.5; lower = max(floor(src), 0); upper = min(ceil(src), in - 1);
 // lerp = src - floor(src); out = top + (bottom - top) * y_lerp with top = tl + (tr - tl) * x_lerp.
 // Compiled with -ffp-contract=off: every multiply/add rounds separately like the reference's ops.
+#include <algorithm>
+
 #include "common.h"
 
 namespace ssd {
@@ -180,6 +182,121 @@ __global__ __launch_bounds__(256) void augment_color_kernel(float* __restrict__ 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Custom images (reference utils/data_utils.py:93-108: PIL Image.resize(..., Image.LANCZOS), then convert_image_dtype).
+// [3P] Pillow's 8-bit resampler, bit for bit: two separable passes in 22-bit fixed point, int32 accumulators, a uint8
+// image between the passes; coefficient tables from the host (float64 there, like Pillow's).  One launch per pass covers
+// a ragged batch: blockIdx.y is the image, blockIdx.x strides over its (row, 4 output bytes) items.  A thread owns FOUR
+// consecutive bytes of an output row (channel-interleaved, so 1 1/3 pixels): the intermediate rows are padded to a
+// multiple of 4 bytes, every store of the horizontal pass and every load of the vertical pass is one aligned dword, and a
+// wave reads / writes 256 contiguous bytes per instruction.  The horizontal pass gathers its taps with byte loads at
+// stride 3: neighbouring lanes' windows overlap almost entirely, so these are L1 hits on lines fetched once.
+
+__device__ __forceinline__ int lanczos_clip8(const int acc) { return min(max(acc >> 22, 0), 255); }
+
+__global__ __launch_bounds__(256) void lanczos_horizontal_kernel(const unsigned char* __restrict__ src,
+                                                                const int* __restrict__ tables,
+                                                                const ssd_resize_desc* __restrict__ desc, const int out_w,
+                                                                const int pitch, unsigned char* __restrict__ tmp) {
+    const ssd_resize_desc d = desc[blockIdx.y];
+    if (d.W == out_w) return;                                   // pass skipped: the vertical pass reads the source
+    const int W = d.W, rowb = out_w * 3, qpr = pitch >> 2;
+    const long total = (long)d.H * qpr;
+    const unsigned char* img = src + d.src_offset;
+    unsigned char* dst = tmp + d.tmp_offset;
+    const int* bounds = tables + d.h_bounds;
+    const int* kk = tables + d.h_k;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+        const int y = (int)(e / qpr), q = (int)(e - (long)y * qpr);
+        const unsigned char* row = img + (long)y * W * 3;
+        unsigned packed = 0;                                    // bytes past the row's end (padding) are written as 0
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = q * 4 + j;
+            if (i < rowb) {
+                const int ox = i / 3, c = i - ox * 3;
+                const int xmin = min(max(bounds[ox * 2], 0), W);
+                const int xmax = min(min(max(bounds[ox * 2 + 1], 0), W - xmin), d.h_ksize);   // clipped to the image
+                const int* k = kk + (long)ox * d.h_ksize;
+                const unsigned char* p = row + xmin * 3 + c;
+                int acc = 1 << 21;
+                for (int x = 0; x < xmax; ++x) acc += (int)p[x * 3] * k[x];
+                packed |= (unsigned)lanczos_clip8(acc) << (8 * j);
+            }
+        }
+        *reinterpret_cast<unsigned*>(dst + (long)y * pitch + q * 4) = packed;
+    }
+}
+
+// vertical pass + epilogue.  Input: the intermediate (pitch bytes per row) or, when the horizontal pass was skipped, the
+// source itself (W == out_w; dword loads only when its rows happen to be 4-byte aligned).  H == out_h: the pass is skipped,
+// i.e. the one tap (row oy, weight 2^22) that leaves the byte as it is.
+__global__ __launch_bounds__(256) void lanczos_vertical_kernel(const unsigned char* __restrict__ src,
+                                                              const int* __restrict__ tables,
+                                                              const ssd_resize_desc* __restrict__ desc, const int out_h,
+                                                              const int out_w, const int pitch,
+                                                              const unsigned char* __restrict__ tmp, float* __restrict__ out,
+                                                              unsigned char* __restrict__ out_u8) {
+    const int b = blockIdx.y;
+    const ssd_resize_desc d = desc[b];
+    const bool hpass = d.W != out_w, vpass = d.H != out_h;
+    const unsigned char* in = hpass ? tmp + d.tmp_offset : src + d.src_offset;
+    const int rowb = out_w * 3, qpr = pitch >> 2;
+    const int in_pitch = hpass ? pitch : rowb;
+    const bool wide_in = (in_pitch & 3) == 0 && (reinterpret_cast<size_t>(in) & 3) == 0;
+    const long total = (long)out_h * qpr;
+    float* o = out + (long)b * out_h * rowb;
+    unsigned char* o8 = out_u8 ? out_u8 + (long)b * out_h * rowb : nullptr;
+    const bool wide_out = (rowb & 3) == 0 && (reinterpret_cast<size_t>(o) & 15) == 0;
+    const int* bounds = tables + d.v_bounds;
+    const int* kk = tables + d.v_k;
+    const float inv255 = (float)(1.0 / 255.0);
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+        const int oy = (int)(e / qpr), q = (int)(e - (long)oy * qpr);
+        const int i0 = q * 4, n = min(4, rowb - i0);            // n: bytes of this item inside the row
+        int ymin = oy, ymax = 1;
+        const int* k = nullptr;
+        if (vpass) {
+            ymin = min(max(bounds[oy * 2], 0), d.H);
+            ymax = min(min(max(bounds[oy * 2 + 1], 0), d.H - ymin), d.v_ksize);               // clipped to the image
+            k = kk + (long)oy * d.v_ksize;
+        }
+        const unsigned char* p = in + (long)ymin * in_pitch + i0;
+        int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21, a3 = 1 << 21;
+        for (int y = 0; y < ymax; ++y, p += in_pitch) {
+            unsigned v;
+            if (wide_in) {
+                v = *reinterpret_cast<const unsigned*>(p);
+            } else {
+                v = p[0];
+                if (n > 1) v |= (unsigned)p[1] << 8;
+                if (n > 2) v |= (unsigned)p[2] << 16;
+                if (n > 3) v |= (unsigned)p[3] << 24;
+            }
+            const int kv = vpass ? k[y] : (1 << 22);
+            a0 += (int)(v & 255u) * kv;
+            a1 += (int)((v >> 8) & 255u) * kv;
+            a2 += (int)((v >> 16) & 255u) * kv;
+            a3 += (int)(v >> 24) * kv;
+        }
+        const int u[4] = {lanczos_clip8(a0), lanczos_clip8(a1), lanczos_clip8(a2), lanczos_clip8(a3)};
+        float* po = o + (long)oy * rowb + i0;
+        if (wide_out) {
+            *reinterpret_cast<float4*>(po) = make_float4((float)u[0] * inv255, (float)u[1] * inv255, (float)u[2] * inv255,
+                                                         (float)u[3] * inv255);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (j < n) po[j] = (float)u[j] * inv255;
+        }
+        if (o8) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (j < n) o8[(long)oy * rowb + i0 + j] = (unsigned char)u[j];
+        }
+    }
+}
+
 }  // namespace ssd
 
 using namespace ssd;
@@ -229,6 +346,71 @@ extern "C" int ssd_preprocess(const unsigned char* image_u8_dev, int B, int H, i
     const long blocks = (total + 255) / 256;
     hipLaunchKernelGGL(preprocess_kernel, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0,
                        (hipStream_t)stream, image_u8_dev, B, H, W, C, out_h, out_w, out_dev);
+    SSD_LAUNCH_CHECK();
+    return SSD_OK;
+}
+
+static const int kResizeMaxSide = 16384;
+static inline bool resize_side_ok(const int v) { return v >= 1 && v <= kResizeMaxSide; }
+static inline size_t round16(const size_t v) { return (v + 15) & ~(size_t)15; }
+
+extern "C" int ssd_resize_lanczos_pitch(int out_w) { return resize_side_ok(out_w) ? (out_w * 3 + 3) & ~3 : 0; }
+
+extern "C" size_t ssd_resize_lanczos_workspace_bytes(const struct ssd_resize_desc* desc_host, int B, int out_h, int out_w) {
+    if (!desc_host || B <= 0 || !resize_side_ok(out_h) || !resize_side_ok(out_w)) return 0;
+    const size_t pitch = (size_t)ssd_resize_lanczos_pitch(out_w);
+    size_t total = 0;
+    for (int b = 0; b < B; ++b)
+        if (desc_host[b].W != out_w && resize_side_ok(desc_host[b].H)) total += round16((size_t)desc_host[b].H * pitch);
+    return total;
+}
+
+extern "C" int ssd_resize_lanczos(const unsigned char* src_dev, size_t src_bytes, const int* tables_dev, size_t tables_ints,
+                                  const struct ssd_resize_desc* desc_host, const struct ssd_resize_desc* desc_dev, int B,
+                                  int C, int out_h, int out_w, float* out_dev, unsigned char* out_u8_dev,
+                                  void* workspace_dev, size_t workspace_bytes, void* stream) {
+    SSD_CHECK_ARG(B >= 0, "ssd_resize_lanczos: bad batch");
+    SSD_UNSUPPORTED_IF(C != 3, "ssd_resize_lanczos: C = %d (3 only)", C);
+    SSD_UNSUPPORTED_IF(!resize_side_ok(out_h) || !resize_side_ok(out_w), "ssd_resize_lanczos: output %d x %d outside 1..%d",
+                       out_h, out_w, kResizeMaxSide);
+    SSD_UNSUPPORTED_IF(B > 65535, "ssd_resize_lanczos: B = %d (at most 65535)", B);
+    if (B == 0) return SSD_OK;
+    SSD_CHECK_ARG(src_dev && tables_dev && desc_host && desc_dev && out_dev, "ssd_resize_lanczos: NULL pointer");
+    const int pitch = ssd_resize_lanczos_pitch(out_w);
+    const long qpr = pitch >> 2;
+    long h_items = 0;
+    size_t tmp_end = 0;
+    for (int b = 0; b < B; ++b) {
+        const ssd_resize_desc& d = desc_host[b];
+        SSD_UNSUPPORTED_IF(!resize_side_ok(d.H) || !resize_side_ok(d.W), "ssd_resize_lanczos: image %d is %d x %d, outside 1..%d",
+                           b, d.H, d.W, kResizeMaxSide);
+        SSD_CHECK_ARG(d.src_offset >= 0 && (size_t)d.src_offset + (size_t)d.H * d.W * 3 <= src_bytes,
+                      "ssd_resize_lanczos: image %d lies outside the source buffer", b);
+        if (d.W != out_w) {
+            SSD_CHECK_ARG(d.h_ksize >= 1 && d.h_bounds >= 0 && (size_t)d.h_bounds + (size_t)out_w * 2 <= tables_ints &&
+                              d.h_k >= 0 && (size_t)d.h_k + (size_t)out_w * d.h_ksize <= tables_ints,
+                          "ssd_resize_lanczos: image %d: horizontal tables lie outside tables_dev", b);
+            SSD_CHECK_ARG(workspace_dev && d.tmp_offset >= 0 && (d.tmp_offset & 15) == 0 && (size_t)d.tmp_offset >= tmp_end &&
+                              (size_t)d.tmp_offset + (size_t)d.H * pitch <= workspace_bytes,
+                          "ssd_resize_lanczos: image %d: intermediate outside the workspace, misaligned or overlapping", b);
+            tmp_end = (size_t)d.tmp_offset + (size_t)d.H * pitch;
+            h_items = std::max(h_items, (long)d.H * qpr);
+        }
+        if (d.H != out_h)
+            SSD_CHECK_ARG(d.v_ksize >= 1 && d.v_bounds >= 0 && (size_t)d.v_bounds + (size_t)out_h * 2 <= tables_ints &&
+                              d.v_k >= 0 && (size_t)d.v_k + (size_t)out_h * d.v_ksize <= tables_ints,
+                          "ssd_resize_lanczos: image %d: vertical tables lie outside tables_dev", b);
+    }
+    if (h_items > 0) {
+        const long blocks = (h_items + 255) / 256;
+        hipLaunchKernelGGL(lanczos_horizontal_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192), B), dim3(256), 0,
+                           (hipStream_t)stream, src_dev, tables_dev, desc_dev, out_w, pitch, (unsigned char*)workspace_dev);
+        SSD_LAUNCH_CHECK();
+    }
+    const long blocks = ((long)out_h * qpr + 255) / 256;
+    hipLaunchKernelGGL(lanczos_vertical_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192), B), dim3(256), 0,
+                       (hipStream_t)stream, src_dev, tables_dev, desc_dev, out_h, out_w, pitch,
+                       (const unsigned char*)workspace_dev, out_dev, out_u8_dev);
     SSD_LAUNCH_CHECK();
     return SSD_OK;
 }

@@ -7,7 +7,8 @@ Offline differences: VOC through tfds is not available, so the test split is a s
 for its items (``SSD_SYNTHETIC_ITEMS`` uint8 images of VOC-like sizes with boxes / labels / difficult flags,
 default 128; VOC2007 test has 4952) that goes through the same ``preprocessing`` (GPU convert + bilinear
 resize) -> padded batches -> ``predict`` -> optional ``evaluate_predictions``; ``use_custom_images`` reads
-``custom_image_path`` like the reference (PIL + LANCZOS);
+``custom_image_path`` like the reference (PIL decodes; the LANCZOS resize, Pillow's bit for bit, and the float
+conversion run on the GPU, one upload and one ``ssd_resize_lanczos`` call per batch: ``data_utils.custom_data_batches``);
 trained weights are loaded when ``trained/ssd_<backbone>_model_weights.h5`` exists, otherwise
 seeded synthetic weights are used and that is said on stdout."""
 import os
@@ -68,13 +69,13 @@ def main(argv=None, **knobs):
     if custom:                                            # predictor.py:35-39
         img_paths = data_utils.get_custom_imgs(custom_path)
         total_items = len(img_paths)
-        items = data_utils.custom_data_generator(img_paths, img_size, img_size)
+        test_data = list(data_utils.custom_data_batches(img_paths, img_size, img_size, bs))
     else:                                                 # predictor.py:22-23, 40-41 (voc/2007 test through tfds there)
         total_items = int(os.environ.get("SSD_SYNTHETIC_ITEMS", "128"))
         raw = data_utils.synthetic_voc_items(total_items, len(labels))
         items = (data_utils.preprocessing(x, img_size, img_size, evaluate=do_eval) for x in raw)
-    # predictor.py:43 -- materialised: predict() and evaluate_predictions() both walk it
-    test_data = list(data_utils.padded_batch(items, bs, padding_values))
+        # predictor.py:43 -- materialised: predict() and evaluate_predictions() both walk it
+        test_data = list(data_utils.padded_batch(items, bs, padding_values))
 
     ssd_model = _model_factory(args.backbone)(hyper_params, max_batch=bs)
     _load_or_synthesise_weights(ssd_model, args.backbone)

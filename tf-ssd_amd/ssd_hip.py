@@ -53,6 +53,12 @@ class ConvDesc(ctypes.Structure):
         "pad_t", "pad_l", "pad_b", "pad_r", "act", "has_residual")]
 
 
+class ResizeDesc(ctypes.Structure):
+    """struct ssd_resize_desc (include/ssd_hip.h); ``RESIZE_DESC_DTYPE`` is the same record for NumPy."""
+    _fields_ = [("src_offset", ctypes.c_longlong), ("tmp_offset", ctypes.c_longlong)] + [(n, ctypes.c_int) for n in (
+        "H", "W", "h_bounds", "h_k", "h_ksize", "v_bounds", "v_k", "v_ksize")]
+
+
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
 MOBILENET_V2, VGG16 = 0, 1
 
@@ -76,6 +82,10 @@ _SIGNATURES = {
                          [vp, vp, vp, vp, vp]),
     "ssd_eval_match": (ctypes.c_int, [vp] * 5 + [ctypes.c_int] * 3 + [ctypes.c_float] + [vp] * 6),
     "ssd_preprocess": (ctypes.c_int, [vp] + [ctypes.c_int] * 6 + [vp, vp]),
+    "ssd_resize_lanczos_pitch": (ctypes.c_int, [ctypes.c_int]),
+    "ssd_resize_lanczos_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "ssd_resize_lanczos": (ctypes.c_int, [vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp] + [ctypes.c_int] * 4 +
+                           [vp, vp, vp, ctypes.c_size_t, vp]),
     "ssd_image_mean": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp, vp, vp]),
     "ssd_augment_geometry": (ctypes.c_int, [vp] + [ctypes.c_int] * 6 + [vp, vp, vp, vp]),
     "ssd_augment_color": (ctypes.c_int, [vp] + [ctypes.c_int] * 3 + [vp, vp, vp, vp]),
@@ -154,6 +164,10 @@ _SIGNATURES = {
     "ssd_net_train_matrix_flops": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_double)]),
     "ssd_net_train_fetch": (ctypes.c_long, [vp, ctypes.c_char_p, ctypes.c_int, c_float_p, ctypes.c_size_t]),
 }
+
+RESIZE_DESC_DTYPE = np.dtype([("src_offset", "<i8"), ("tmp_offset", "<i8")] + [(n, "<i4") for n in (
+    "H", "W", "h_bounds", "h_k", "h_ksize", "v_bounds", "v_k", "v_ksize")])
+assert RESIZE_DESC_DTYPE.itemsize == ctypes.sizeof(ResizeDesc) == 48
 
 _lib = None
 _inited = False

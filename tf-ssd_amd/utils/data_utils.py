@@ -1,8 +1,12 @@
 """Data side of the drop-in.  The reference's ``utils/data_utils.py`` loads PASCAL VOC via
 tensorflow_datasets (not available offline: ``get_dataset`` raises) and converts / resizes every
 image with TF ops; here ``preprocessing`` runs that conversion + bilinear resize as one HIP kernel
-(SURVEY.md 8f N4).  Also kept: the VOC label list, the padded-batch conventions (gt boxes padded with 0, labels with
+(SURVEY.md 8f N4), and custom images -- PIL + LANCZOS in the reference -- are only decoded by PIL: the resize is
+Pillow's 8-bit resampler restated as HIP kernels (``ssd_resize_lanczos``), a ragged batch per call.  Also kept: the VOC label list, the padded-batch conventions (gt boxes padded with 0, labels with
 -1), and seeded synthetic generators shaped like the reference's batches."""
+import functools
+import math
+
 import numpy as np
 
 VOC_LABELS = ["aeroplane", "bicycle", "bird", "boat", "bottle", "bus", "car", "cat", "chair", "cow",
@@ -95,21 +99,190 @@ def get_custom_imgs(custom_image_path):
     return img_paths
 
 
-def custom_data_generator(img_paths, final_height, final_width):
-    """reference utils/data_utils.py:93-108: every image opened with PIL and resized with LANCZOS on the host
-    (the reference's choice for custom images -- dataset images take the bilinear ``preprocessing`` path),
-    then uint8 -> float32 [0,1] (``tf.image.convert_image_dtype``) on the GPU (``ssd_preprocess`` at equal
-    sizes is exactly that conversion).  ``*.npy`` files (uint8 [H,W,3]) are accepted as well.  Yields
-    ``(img [final_height, final_width, 3] device tensor, gt_boxes [0,4], gt_labels [0])``."""
+@functools.lru_cache(maxsize=4096)
+def lanczos_coefficients(in_size, out_size):
+    """[3P] The fixed-point tables of Pillow's 8-bit LANCZOS resampler for one axis (Resample.c ``precompute_coeffs`` +
+    ``normalize_coeffs_8bpc``), computed in float64 in Pillow's order: ``scale = in / out``, ``fs = max(scale, 1)``,
+    ``support = 3 fs``, ``ksize = ceil(support) * 2 + 1``; for output ``i``: ``center = (i + 0.5) scale``, ``xmin =
+    max(int(center - support + 0.5), 0)``, ``xmax = min(int(center + support + 0.5), in) - xmin``, ``w[x] = L((x + xmin -
+    center + 0.5) * (1 / fs))`` with ``L(t) = sinc(t) sinc(t / 3)`` on ``-3 <= t < 3``, normalised by the running sum in index
+    order, then ``k = (int)(+-0.5 + w * 2**22)``.  Returns read-only ``(bounds [out,2] int32 = (xmin, xmax), k
+    [out,ksize] int32)``; host only, cached per ``(in_size, out_size)``."""
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size < 1 or out_size < 1:
+        raise ValueError("sizes must be positive, got %d -> %d" % (in_size, out_size))
+    scale = in_size / out_size
+    fs = max(scale, 1.0)
+    support = 3.0 * fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / fs
+    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)               # astype: truncation, like the C cast
+    xmax = np.minimum((center + support + 0.5).astype(np.int64), in_size) - xmin
+    x = np.arange(ksize, dtype=np.int64)[None, :]
+    t = ((x + xmin[:, None]).astype(np.float64) - center[:, None] + 0.5) * ss
+    inside = (x < xmax[:, None]) & (t >= -3.0) & (t < 3.0)
+
+    def sinc(v):
+        if v == 0.0:
+            return 1.0
+        v = v * math.pi
+        return math.sin(v) / v                                                    # libm's sin, the one Pillow calls
+    w = np.zeros(t.shape, np.float64)
+    w[inside] = [sinc(v) * sinc(v / 3) for v in t[inside].tolist()]
+    ww = np.cumsum(w, axis=1)[:, -1:]                                             # sequential sum, index order
+    w = np.where(ww != 0.0, w / np.where(ww != 0.0, ww, 1.0), w)
+    k = np.where(w < 0.0, -0.5 + w * 4194304.0, 0.5 + w * 4194304.0).astype(np.int32)
+    bounds = np.stack([xmin, xmax], 1).astype(np.int32)
+    bounds.setflags(write=False)
+    k.setflags(write=False)
+    return bounds, k
+
+
+_resize_staging = {}
+
+
+def resize_lanczos_batch(images, final_height, final_width, out=None, out_u8=None):
+    """``PIL.Image.resize((final_width, final_height), Image.LANCZOS)`` + uint8 -> float32 ``* 1/255`` of a list of uint8
+    ``[H,W,3]`` arrays / tensors of ANY sizes, on the GPU, bit for bit (``ssd_resize_lanczos``).  One packed upload
+    (descriptors, coefficient tables, pixels: one pinned staging buffer, one copy) and one call per batch.  Returns the
+    float32 device tensor ``[B,final_height,final_width,3]`` (``out`` when given: a contiguous float32 device tensor of
+    that shape, e.g. a slice of a larger batch); ``out_u8`` (uint8, same shape) also receives the resized bytes."""
+    import torch
+    import ssd_hip as _h
+    fh, fw = int(final_height), int(final_width)
+    arrays = []
+    for im in images:
+        a = im.detach().cpu().numpy() if isinstance(im, torch.Tensor) else np.asarray(im)
+        if a.dtype != np.uint8 or a.ndim != 3:
+            raise ValueError("images must be uint8 [H,W,3], got %s %s" % (a.dtype, tuple(a.shape)))
+        arrays.append(a)
+    B = len(arrays)
+    C = arrays[0].shape[2] if B else 3
+    if any(a.shape[2] != C for a in arrays):
+        raise ValueError("images of one batch must have the same number of channels")
+    dev = _h.device()
+    for name, t in (("out", out), ("out_u8", out_u8)):
+        want = torch.float32 if name == "out" else torch.uint8
+        if t is not None and (tuple(t.shape) != (B, fh, fw, C) or t.dtype != want or t.device != dev or not t.is_contiguous()):
+            raise ValueError("%s must be a contiguous %s device tensor %s" % (name, want, (B, fh, fw, C)))
+    if out is None:
+        out = torch.empty((B, fh, fw, C), dtype=torch.float32, device=dev)
+    lib = _h.lib()
+    if B == 0 or C != 3 or not (1 <= fh <= 16384 and 1 <= fw <= 16384):           # nothing to pack: the library answers
+        _h.check(lib.ssd_resize_lanczos(None, 0, None, 0, None, None, B, C, fh, fw, _h.ptr(out), _h.ptr(out_u8), None, 0,
+                                        _h.stream()), "resize_lanczos_batch")
+        return out
+    layout = _lanczos_layout(arrays, fh, fw)
+    st = _resize_staging.get(dev.index)
+    if st is None or st[0].numel() < layout["total"]:
+        size = max(1 << (layout["total"] - 1).bit_length(), 1 << 20)
+        st = _resize_staging[dev.index] = [_h.pinned_empty((size,), torch.uint8), None]
+    if st[1] is not None:
+        st[1].synchronize()                                                       # the previous batch's copy has left the buffer
+    _lanczos_fill(st[0].numpy(), arrays, layout)
+    packed = torch.empty(layout["total"], dtype=torch.uint8, device=dev)
+    packed.copy_(st[0][:layout["total"]], non_blocking=True)
+    st[1] = torch.cuda.Event()
+    st[1].record()
+    _lanczos_launch(packed, layout, out, out_u8)
+    return out
+
+
+def _lanczos_layout(arrays, fh, fw):
+    """Where everything one ``ssd_resize_lanczos`` call reads sits in ONE buffer: descriptors | coefficient tables (int32,
+    one per distinct (in, out) pair of the batch) | images, each part at a multiple of 16 bytes."""
+    import ssd_hip as _h
+    B = len(arrays)
+    desc = np.zeros(B, _h.RESIZE_DESC_DTYPE)
+    tables, table_at, n_ints = [], {}, 0
+
+    def table(in_size, out_size):
+        nonlocal n_ints
+        key = (in_size, out_size)
+        if key not in table_at:
+            bounds, k = lanczos_coefficients(in_size, out_size)
+            table_at[key] = (n_ints, n_ints + bounds.size, k.shape[1])
+            tables.extend((bounds, k))
+            n_ints += bounds.size + k.size
+        return table_at[key]
+    pitch = _h.lib().ssd_resize_lanczos_pitch(fw)
+    tmp_bytes = 0
+    for b, a in enumerate(arrays):
+        H, W = a.shape[:2]
+        desc[b]["H"], desc[b]["W"] = H, W
+        if min(H, W) < 1 or max(H, W) > 16384:
+            continue                                                              # the library reports it (unsupported)
+        if W != fw:
+            desc[b]["h_bounds"], desc[b]["h_k"], desc[b]["h_ksize"] = table(W, fw)
+            desc[b]["tmp_offset"] = tmp_bytes
+            tmp_bytes += (H * pitch + 15) & ~15
+        if H != fh:
+            desc[b]["v_bounds"], desc[b]["v_k"], desc[b]["v_ksize"] = table(H, fh)
+    tables_at = (desc.nbytes + 15) & ~15
+    src_at = (tables_at + 4 * n_ints + 15) & ~15
+    total = src_at
+    for b, a in enumerate(arrays):
+        desc[b]["src_offset"] = total - src_at
+        total += (a.size + 15) & ~15
+    assert tmp_bytes == _h.lib().ssd_resize_lanczos_workspace_bytes(desc.ctypes.data, B, fh, fw)
+    return {"desc": desc, "tables": tables, "n_ints": n_ints, "tables_at": tables_at, "src_at": src_at, "total": total,
+            "tmp_bytes": tmp_bytes, "size": (fh, fw)}
+
+
+def _lanczos_fill(host, arrays, layout):
+    """Write the batch into ``host`` (uint8 NumPy view of at least ``layout["total"]`` bytes)."""
+    desc = layout["desc"]
+    host[:desc.nbytes] = desc.view(np.uint8)
+    at = layout["tables_at"]
+    for tb in layout["tables"]:
+        host[at:at + tb.nbytes] = tb.reshape(-1).view(np.uint8)
+        at += tb.nbytes
+    for b, a in enumerate(arrays):
+        at = layout["src_at"] + int(desc[b]["src_offset"])
+        host[at:at + a.size].reshape(a.shape)[...] = a
+
+
+def _lanczos_launch(packed, layout, out, out_u8=None):
+    """``ssd_resize_lanczos`` on a device copy ``packed`` of the filled buffer, on the current stream."""
+    import ssd_hip as _h
+    desc, (fh, fw) = layout["desc"], layout["size"]
+    ws = _h.workspace(max(layout["tmp_bytes"], 16))
+    base, src_at = packed.data_ptr(), layout["src_at"]
+    _h.check(_h.lib().ssd_resize_lanczos(base + src_at, layout["total"] - src_at, base + layout["tables_at"], layout["n_ints"],
+                                         desc.ctypes.data, base, len(desc), 3, fh, fw, _h.ptr(out), _h.ptr(out_u8),
+                                         _h.ptr(ws), ws.numel(), _h.stream()), "resize_lanczos_batch")
+
+
+def _decode_custom_image(img_path):
+    """One custom image as uint8 [H,W,3]: PIL decodes (``.convert("RGB")``); ``*.npy`` files hold the array itself."""
+    if img_path.endswith(".npy"):
+        return np.ascontiguousarray(np.load(img_path))
     from PIL import Image
+    return np.asarray(Image.open(img_path).convert("RGB"), dtype=np.uint8)
+
+
+def custom_data_generator(img_paths, final_height, final_width):
+    """reference utils/data_utils.py:93-108: every image opened with PIL, resized with LANCZOS, then uint8 -> float32
+    [0,1] (``tf.image.convert_image_dtype``).  PIL only decodes here: the resize (Pillow's, bit for bit) and the
+    conversion run on the GPU (``resize_lanczos_batch``); there is no host resize path.  ``*.npy`` files (uint8 [H,W,3])
+    are accepted as well.  Yields ``(img [final_height, final_width, 3] device tensor, gt_boxes [0,4], gt_labels [0])``;
+    ``custom_data_batches`` resizes a whole batch per call."""
     for img_path in img_paths:
-        if img_path.endswith(".npy"):
-            image = Image.fromarray(np.load(img_path))
-        else:
-            image = Image.open(img_path).convert("RGB")
-        resized = np.ascontiguousarray(np.array(image.resize((final_width, final_height), Image.LANCZOS), dtype=np.uint8))
-        img = preprocess_batch(resized[None], final_height, final_width)[0]
+        img = resize_lanczos_batch([_decode_custom_image(img_path)], final_height, final_width)[0]
         yield img, np.zeros((0, 4), np.float32), np.zeros((0,), np.int32)
+
+
+def custom_data_batches(img_paths, final_height, final_width, batch_size):
+    """``custom_data_generator`` + ``padded_batch`` with one upload and one resize call per batch: yields ``(imgs
+    [b,final_height,final_width,3] device tensor, gt_boxes [b,1,4] zeros, gt_labels [b,1] of -1)``, what
+    ``padded_batch`` makes of the generator's items (no ground truth: one padding row)."""
+    pv = get_padding_values()
+    img_paths = list(img_paths)
+    for i in range(0, len(img_paths), int(batch_size)):
+        arrays = [_decode_custom_image(p) for p in img_paths[i:i + int(batch_size)]]
+        imgs = resize_lanczos_batch(arrays, final_height, final_width)
+        yield imgs, np.full((len(arrays), 1, 4), pv[1], np.float32), np.full((len(arrays), 1), pv[2], np.int32)
 
 
 def padded_batch(items, batch_size, padding_values=None):
