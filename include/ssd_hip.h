@@ -187,6 +187,48 @@ int ssd_augment_geometry(const float* img_dev, int B, int H, int W, int C, int o
 int ssd_augment_color(float* img_dev, int B, int H, int W, const float* params_dev, const int* flags_dev,
                       const float* mean_dev, void* stream);
 
+/* ---- drawing: utils/drawing_utils.py:6-85 (draw_grid_map, draw_bboxes, draw_bboxes_with_labels) ---------------------
+ * ssd_image_minmax: minmax_out [B][2] = {min, max} over H, W, C of each image of img_dev [B,H,W,3] float32: the two numbers
+ *   of [3P] Keras array_to_img(scale=True).  NaN pixels are ignored.  workspace: ssd_image_minmax_workspace_bytes(B) bytes,
+ *   4-byte aligned (partial results; two launches, no atomics).
+ * ssd_draw_detections: out_dev [B,H,W,3] uint8 = array_to_img of every image, then the reference's PIL loop on it -- for
+ *   each box in index order ImageDraw.text((x1 + 4, y1 + 2), text) in the legacy bitmap font and
+ *   ImageDraw.rectangle((x1, y1, x2, y2), outline, width) -- reproduced to the byte ([3P] Pillow, pinned by
+ *   tests/golden/drawing.npz) in one pass that writes each output byte once: a pixel takes the colour of the LAST box
+ *   whose frame or text inks it.
+ *     array_to_img, every step a separately rounded fp32 op: v = x - min; if (max - min != 0) v = v / (max - min);
+ *       v = v * 255; uint8(v) truncates.  minmax_dev NULL: no scaling, out = uint8(x) saturated to 0..255 (float images
+ *       that already hold bytes: draw_grid_map).
+ *     boxes_dev [B,T,4] int32 = (y1, x1, y2, x2) in pixels, corners inclusive, 16-byte aligned; they may lie partly or
+ *       wholly outside the image.  A box with x2 - x1 <= 0 or y2 - y1 <= 0 is skipped (drawing_utils.py:63), and so is a
+ *       box whose label is outside [0, L).  Boxes thinner than 2 * outline_width paint outside their rectangle exactly
+ *       as Pillow's strokes do.
+ *     labels_dev [B,T] int32 index colors_dev [L][3] uint8.  text_dev [B,T,maxlen] bytes with text_len_dev [B,T] (clamped
+ *       to 0..maxlen); bytes outside 32..126 draw nothing (the Python surface raises ValueError for them).  atlas_dev
+ *       [96][4] uint32: per glyph (95 printable ASCII, then a blank) 11 row bytes, bit k = column k - 1 of the 6-wide
+ *       cell, byte 11 unused, then a word {first box row, end box row << 8, has column -1 << 16}
+ *       (utils/drawing_utils.glyph_atlas builds it from Pillow's font).
+ *     fill != 0: boxes are filled rectangles instead (ImageDraw.rectangle(fill=): draw_grid_map), drawn down to one
+ *       pixel (only x2 < x1 or y2 < y1 is skipped); no text.  text_dev / text_len_dev / atlas_dev may be NULL then and
+ *       when maxlen == 0.
+ *   B == 0 is a no-op; T == 0 writes the plain converted images.
+ * ssd_draw_bounding_boxes: [3P] tf.image.draw_bounding_boxes (TF 2.0 DrawBoundingBoxesOp restated; unpinned): img_dev /
+ *   out_dev [B,H,W,3] float32 (out != img), boxes_dev [B,T,4] float32 normalised (y1, x1, y2, x2), colors_dev [L][3]
+ *   float32 cycled by box index.  Corners are int64(float(coord) * (size - 1)); an inverted box and a box entirely
+ *   outside are skipped; each 1-pixel edge is drawn only when that edge lies inside; later boxes overwrite earlier ones.
+ * Supported: C == 3, H and W in 1..16384, B <= 65535, T <= 4096 (ssd_draw_detections) / 1024 (ssd_draw_bounding_boxes),
+ *   maxlen <= 64; anything else returns SSD_E_UNSUPPORTED before any launch and leaves the output untouched.
+ *   outline_width outside 1..64 and NULL pointers are SSD_E_INVALID. */
+size_t ssd_image_minmax_workspace_bytes(int B);
+int ssd_image_minmax(const float* img_dev, int B, int H, int W, int C, float* minmax_out_dev, void* workspace_dev,
+                     size_t workspace_bytes, void* stream);
+int ssd_draw_detections(const float* img_dev, const float* minmax_dev, int B, int H, int W, int C, const int* boxes_dev,
+                        const int* labels_dev, const unsigned char* text_dev, const int* text_len_dev, int T, int maxlen,
+                        const unsigned char* colors_dev, int L, const unsigned* atlas_dev, int outline_width, int fill,
+                        unsigned char* out_dev, void* stream);
+int ssd_draw_bounding_boxes(const float* img_dev, int B, int H, int W, int C, const float* boxes_dev, int T,
+                            const float* colors_dev, int L, float* out_dev, void* stream);
+
 /* ---- training loss: ssd_loss.py:8-65 (N1) ----------------------------------------------
  * CustomLoss.loc_loss_fn + conf_loss_fn in one kernel per image.
  *   actual_deltas / pred_deltas [B,N,4]; actual_labels (one-hot) / pred_labels (probabilities)

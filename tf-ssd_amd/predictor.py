@@ -1,7 +1,8 @@
 """Host-side mirror of the reference's ``predictor.py`` (predictor.py:5-57): the same CLI
 (``-handle-gpu``, ``--backbone``), the same knobs (batch 32, ``evaluate`` switch, "bg" + VOC
 labels) and the same call order -- hyper-parameters, model, weights, priors, decoder model,
-``predict`` over the test split, optional VOC07 mAP.
+``predict`` over the test split, optional VOC07 mAP, optional drawing (``draw=True``: ``drawing_utils.draw_predictions``
+on the GPU, PNGs into ``draw_dir``).
 
 Offline differences: VOC through tfds is not available, so the test split is a seeded synthetic stand-in
 for its items (``SSD_SYNTHETIC_ITEMS`` uint8 images of VOC-like sizes with boxes / labels / difficult flags,
@@ -21,7 +22,7 @@ if _HERE not in sys.path:
 
 import ssd_hip  # noqa: E402
 ssd_hip.configure_serving()        # the serving entry point opts in to three lanes / three hardware queues before the runtime starts
-from utils import bbox_utils, data_utils, eval_utils, io_utils, train_utils  # noqa: E402
+from utils import bbox_utils, data_utils, drawing_utils, eval_utils, io_utils, train_utils  # noqa: E402
 from models.decoder import get_decoder_model  # noqa: E402
 
 # the reference's script-level knobs (predictor.py:9-12), same names and defaults
@@ -29,6 +30,10 @@ batch_size = 32
 evaluate = False
 use_custom_images = False
 custom_image_path = "data/images/"
+# additions: the reference always draws when it does not evaluate (and blocks in plt.show()); here drawing is opt-in and
+# writes draw_dir/img_%05d.png when draw_dir is set
+draw = False
+draw_dir = None
 
 
 def _model_factory(backbone):
@@ -50,7 +55,7 @@ def _load_or_synthesise_weights(model, backbone):
 
 def main(argv=None, **knobs):
     """``knobs`` override the module-level switches for one call (``evaluate``, ``use_custom_images``,
-    ``custom_image_path``, ``batch_size``)."""
+    ``custom_image_path``, ``batch_size``, ``draw``, ``draw_dir``)."""
     args = io_utils.handle_args(argv)
     if args.handle_gpu:
         io_utils.handle_gpu_compatibility()
@@ -59,6 +64,8 @@ def main(argv=None, **knobs):
     do_eval = bool(knobs.get("evaluate", evaluate))
     custom = bool(knobs.get("use_custom_images", use_custom_images))
     custom_path = knobs.get("custom_image_path", custom_image_path)
+    do_draw = bool(knobs.get("draw", draw))
+    out_dir = knobs.get("draw_dir", draw_dir)
 
     labels = ["bg"] + data_utils.get_labels()
     hyper_params = train_utils.get_hyper_params(args.backbone)
@@ -92,7 +99,9 @@ def main(argv=None, **knobs):
     if do_eval:                                           # predictor.py:54-55
         stats = eval_utils.evaluate_predictions(test_data, boxes, classes, scores, labels, bs)
         return boxes, classes, scores, stats
-    # predictor.py:56-57 draws the boxes (utils/drawing_utils.py: out of scope)
+    if do_draw:                                           # predictor.py:56-57, on the GPU; PNGs instead of plt.show()
+        for _ in drawing_utils.draw_predictions(test_data, boxes, classes, scores, labels, bs, out_dir=out_dir):
+            pass
     return boxes, classes, scores
 
 
