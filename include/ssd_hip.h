@@ -134,10 +134,26 @@ int ssd_eval_match(const float* det_boxes_dev, const float* det_labels_dev,
 /* ---- input pipeline: utils/data_utils.py:22-23 (N4) ---------------------------------------
  * tf.image.convert_image_dtype(uint8 -> float32, x 1/255) + tf.image.resize(bilinear, TF2
  * half-pixel centres, no antialias) in one kernel.  image_u8 [B,H,W,C] uint8 (device) ->
- * out [B,out_h,out_w,C] float32 in [0,1].  Images of different sizes go one call each (B = 1)
- * into their slot of the batch tensor. */
+ * out [B,out_h,out_w,C] float32 in [0,1].  Images of different sizes go through
+ * ssd_preprocess_ragged: one call per batch, bitwise the same values. */
 int ssd_preprocess(const unsigned char* image_u8_dev, int B, int H, int W, int C, int out_h, int out_w,
                    float* out_dev, void* stream);
+
+/* The ragged form: B uint8 [H_b,W_b,3] images of different sizes, packed in src_dev [src_bytes], to
+ * out_dev [B,out_h,out_w,3] float32 in ONE launch; image b's result is bitwise what
+ * ssd_preprocess(B = 1) writes for it.  desc_host and desc_dev are the same B descriptors in host
+ * and in device memory (the host copy is checked before any launch; the kernel reads the device
+ * copy).  No workspace; every output element is written once.
+ * SSD_E_INVALID: NULL pointers, a src_offset that is negative or not a multiple of 16, an image
+ * that does not lie inside [0, src_bytes).  SSD_E_UNSUPPORTED: C != 3, a side (H, W, out_h, out_w)
+ * outside 1..16384, B > 65535.  B == 0 is a no-op. */
+struct ssd_image_desc {
+    long long src_offset; /* byte offset of the image in src_dev, a multiple of 16 */
+    int H, W;
+};
+int ssd_preprocess_ragged(const unsigned char* src_dev, size_t src_bytes,
+                          const struct ssd_image_desc* desc_host, const struct ssd_image_desc* desc_dev,
+                          int B, int C, int out_h, int out_w, float* out_dev, void* stream);
 
 /* ---- custom images: utils/data_utils.py:93-108 (PIL Image.resize(..., Image.LANCZOS) + convert_image_dtype) ----------
  * [3P] Pillow's 8-bit resampler (ImagingResample, 8bpc), reproduced bit for bit: a separable two-pass filter in 22-bit

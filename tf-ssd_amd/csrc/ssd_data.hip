@@ -42,6 +42,70 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const unsigned char* __
     }
 }
 
+// The ragged form of preprocess_kernel: B images of different sizes, packed in one buffer, in ONE launch (blockIdx.y is the
+// image, its size comes from the device descriptor).  Per output value the arithmetic is preprocess_kernel's, expression
+// for expression, so image b's result is bitwise what ssd_preprocess(B = 1) writes for it.  A thread owns FOUR consecutive
+// floats of the image's output (channel-interleaved, so they belong to at most two neighbouring pixels): one aligned
+// 16-byte store per thread, a wave writes 1 KiB contiguous along the output rows.  The taps are byte loads; neighbouring
+// lanes read neighbouring source bytes (L1 / L2 hits on lines fetched once).
+struct bilinear_taps {
+    int tl, tr, bl, br;     // byte offsets of the four source pixels
+    float lx, ly;
+};
+
+__device__ __forceinline__ bilinear_taps preprocess_taps(const int pix, const int W, const int H, const int Wo, const float sy,
+                                                         const float sx) {
+    const int oy = pix / Wo, ox = pix - oy * Wo;
+    const float fy = ((float)oy + 0.5f) * sy - 0.5f, fx = ((float)ox + 0.5f) * sx - 0.5f;
+    const float fyf = floorf(fy), fxf = floorf(fx);
+    const int y0 = max((int)fyf, 0), y1 = min((int)ceilf(fy), H - 1);
+    const int x0 = max((int)fxf, 0), x1 = min((int)ceilf(fx), W - 1);
+    bilinear_taps t;
+    t.tl = (y0 * W + x0) * 3; t.tr = (y0 * W + x1) * 3;       // < 16384 * 16384 * 3 < 2^31 (host check)
+    t.bl = (y1 * W + x0) * 3; t.br = (y1 * W + x1) * 3;
+    t.lx = fx - fxf; t.ly = fy - fyf;
+    return t;
+}
+
+__global__ __launch_bounds__(256) void preprocess_ragged_kernel(const unsigned char* __restrict__ src,
+                                                               const ssd_image_desc* __restrict__ desc, const int Ho,
+                                                               const int Wo, float* __restrict__ out) {
+    const ssd_image_desc d = desc[blockIdx.y];
+    const int H = d.H, W = d.W;
+    const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
+    const float inv255 = (float)(1.0 / 255.0);
+    const int npix = Ho * Wo, n = npix * 3;                     // floats of one output image (< 2^31: host check)
+    const int items = (n + 3) >> 2;
+    const unsigned char* img = src + d.src_offset;
+    float* o = out + (long)blockIdx.y * n;
+    const bool wide = (reinterpret_cast<size_t>(o) & 15) == 0;
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < items; e += gridDim.x * 256) {
+        const int i0 = e * 4;
+        const int p0 = i0 / 3, c0 = i0 - p0 * 3;
+        const bilinear_taps ta = preprocess_taps(p0, W, H, Wo, sy, sx);
+        const bilinear_taps tb = preprocess_taps(min(p0 + 1, npix - 1), W, H, Wo, sy, sx);
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool second = c0 + j >= 3;                    // the value belongs to pixel p0 + 1
+            const int c = second ? c0 + j - 3 : c0 + j;
+            const bilinear_taps& t = second ? tb : ta;
+            const float tl = (float)img[t.tl + c] * inv255, tr = (float)img[t.tr + c] * inv255;
+            const float bl = (float)img[t.bl + c] * inv255, br = (float)img[t.br + c] * inv255;
+            const float top = tl + (tr - tl) * t.lx;
+            const float bot = bl + (br - bl) * t.lx;
+            v[j] = top + (bot - top) * t.ly;
+        }
+        if (wide && i0 + 4 <= n) {
+            *reinterpret_cast<float4*>(o + i0) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (i0 + j < n) o[i0 + j] = v[j];
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Augmentation (reference augmentation.py, used at trainer.py:42), the deterministic pieces with the random draws as
 // inputs: per-channel image mean (expand's fill colour, contrast's pivot), the geometric chain expand -> crop -> bilinear
@@ -353,6 +417,32 @@ extern "C" int ssd_preprocess(const unsigned char* image_u8_dev, int B, int H, i
 static const int kResizeMaxSide = 16384;
 static inline bool resize_side_ok(const int v) { return v >= 1 && v <= kResizeMaxSide; }
 static inline size_t round16(const size_t v) { return (v + 15) & ~(size_t)15; }
+
+extern "C" int ssd_preprocess_ragged(const unsigned char* src_dev, size_t src_bytes, const struct ssd_image_desc* desc_host,
+                                     const struct ssd_image_desc* desc_dev, int B, int C, int out_h, int out_w,
+                                     float* out_dev, void* stream) {
+    SSD_CHECK_ARG(B >= 0, "ssd_preprocess_ragged: bad batch");
+    SSD_UNSUPPORTED_IF(C != 3, "ssd_preprocess_ragged: C = %d (3 only)", C);
+    SSD_UNSUPPORTED_IF(!resize_side_ok(out_h) || !resize_side_ok(out_w), "ssd_preprocess_ragged: output %d x %d outside 1..%d",
+                       out_h, out_w, kResizeMaxSide);
+    SSD_UNSUPPORTED_IF(B > 65535, "ssd_preprocess_ragged: B = %d (at most 65535)", B);
+    if (B == 0) return SSD_OK;
+    SSD_CHECK_ARG(src_dev && desc_host && desc_dev && out_dev, "ssd_preprocess_ragged: NULL pointer");
+    for (int b = 0; b < B; ++b) {
+        const ssd_image_desc& d = desc_host[b];
+        SSD_UNSUPPORTED_IF(!resize_side_ok(d.H) || !resize_side_ok(d.W), "ssd_preprocess_ragged: image %d is %d x %d, outside 1..%d",
+                           b, d.H, d.W, kResizeMaxSide);
+        SSD_CHECK_ARG(d.src_offset >= 0 && (d.src_offset & 15) == 0, "ssd_preprocess_ragged: image %d: offset not a multiple of 16", b);
+        SSD_CHECK_ARG((size_t)d.src_offset + (size_t)d.H * d.W * 3 <= src_bytes,
+                      "ssd_preprocess_ragged: image %d lies outside the source buffer", b);
+    }
+    const long items = ((long)out_h * out_w * 3 + 3) / 4;
+    const long blocks = (items + 255) / 256;
+    hipLaunchKernelGGL(preprocess_ragged_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192), B), dim3(256), 0,
+                       (hipStream_t)stream, src_dev, desc_dev, out_h, out_w, out_dev);
+    SSD_LAUNCH_CHECK();
+    return SSD_OK;
+}
 
 extern "C" int ssd_resize_lanczos_pitch(int out_w) { return resize_side_ok(out_w) ? (out_w * 3 + 3) & ~3 : 0; }
 

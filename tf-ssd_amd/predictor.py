@@ -4,9 +4,14 @@ labels) and the same call order -- hyper-parameters, model, weights, priors, dec
 ``predict`` over the test split, optional VOC07 mAP, optional drawing (``draw=True``: ``drawing_utils.draw_predictions``
 on the GPU, PNGs into ``draw_dir``).
 
-Offline differences: VOC through tfds is not available, so the test split is a seeded synthetic stand-in
-for its items (``SSD_SYNTHETIC_ITEMS`` uint8 images of VOC-like sizes with boxes / labels / difficult flags,
-default 128; VOC2007 test has 4952) that goes through the same ``preprocessing`` (GPU convert + bilinear
+Data: with ``SSD_VOC_DIR`` set to a directory that holds a VOCdevkit, the reference's own calls run
+(predictor.py:22-25, 40-43): ``get_dataset("voc/2007", "test")``, ``get_total_item_size``,
+``get_labels(info)``, then ``data_utils.voc_batches`` (threaded decode, one upload and one resize launch
+per batch); ``SSD_SYNTHETIC_ITEMS``, when set, caps the items.  The preprocessed split is held on the
+device, since ``predict`` and then ``evaluate_predictions`` / ``draw_predictions`` walk it: 1.08 MB per
+image at 300x300, 5.3 GB for the 4952 images of VOC2007 test (15.6 GB at 512x512).  Without the variable
+the test split is a seeded synthetic stand-in for its items (``SSD_SYNTHETIC_ITEMS`` uint8 images of
+VOC-like sizes with boxes / labels / difficult flags, default 128) that goes through the same ``preprocessing`` (GPU convert + bilinear
 resize) -> padded batches -> ``predict`` -> optional ``evaluate_predictions``; ``use_custom_images`` reads
 ``custom_image_path`` like the reference (PIL decodes; the LANCZOS resize, Pillow's bit for bit, and the float
 conversion run on the GPU, one upload and one ``ssd_resize_lanczos`` call per batch: ``data_utils.custom_data_batches``);
@@ -77,7 +82,17 @@ def main(argv=None, **knobs):
         img_paths = data_utils.get_custom_imgs(custom_path)
         total_items = len(img_paths)
         test_data = list(data_utils.custom_data_batches(img_paths, img_size, img_size, bs))
-    else:                                                 # predictor.py:22-23, 40-41 (voc/2007 test through tfds there)
+    elif os.environ.get("SSD_VOC_DIR"):                   # predictor.py:22-25, 40-43
+        test_data, info = data_utils.get_dataset("voc/2007", "test", os.environ["SSD_VOC_DIR"])
+        total_items = data_utils.get_total_item_size(info, "test")
+        labels = ["bg"] + data_utils.get_labels(info)
+        if os.environ.get("SSD_SYNTHETIC_ITEMS"):
+            total_items = min(total_items, int(os.environ["SSD_SYNTHETIC_ITEMS"]))
+            test_data = test_data.take(total_items)
+        # materialised like the synthetic split below: predict() and evaluate_predictions() / draw_predictions() both
+        # walk it (1.08 MB of device memory per 300x300 image: 5.3 GB for all of VOC2007 test)
+        test_data = list(data_utils.voc_batches(test_data, bs, img_size, img_size, evaluate=do_eval))
+    else:                                                 # no devkit: a synthetic stand-in for voc/2007 test
         total_items = int(os.environ.get("SSD_SYNTHETIC_ITEMS", "128"))
         raw = data_utils.synthetic_voc_items(total_items, len(labels))
         items = (data_utils.preprocessing(x, img_size, img_size, evaluate=do_eval) for x in raw)

@@ -82,6 +82,7 @@ _SIGNATURES = {
                          [vp, vp, vp, vp, vp]),
     "ssd_eval_match": (ctypes.c_int, [vp] * 5 + [ctypes.c_int] * 3 + [ctypes.c_float] + [vp] * 6),
     "ssd_preprocess": (ctypes.c_int, [vp] + [ctypes.c_int] * 6 + [vp, vp]),
+    "ssd_preprocess_ragged": (ctypes.c_int, [vp, ctypes.c_size_t, vp, vp] + [ctypes.c_int] * 4 + [vp, vp]),
     "ssd_resize_lanczos_pitch": (ctypes.c_int, [ctypes.c_int]),
     "ssd_resize_lanczos_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "ssd_resize_lanczos": (ctypes.c_int, [vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp] + [ctypes.c_int] * 4 +
@@ -173,6 +174,8 @@ _SIGNATURES = {
 RESIZE_DESC_DTYPE = np.dtype([("src_offset", "<i8"), ("tmp_offset", "<i8")] + [(n, "<i4") for n in (
     "H", "W", "h_bounds", "h_k", "h_ksize", "v_bounds", "v_k", "v_ksize")])
 assert RESIZE_DESC_DTYPE.itemsize == ctypes.sizeof(ResizeDesc) == 48
+IMAGE_DESC_DTYPE = np.dtype([("src_offset", "<i8"), ("H", "<i4"), ("W", "<i4")])        # struct ssd_image_desc
+assert IMAGE_DESC_DTYPE.itemsize == 16
 
 _lib = None
 _inited = False

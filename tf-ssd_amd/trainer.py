@@ -7,9 +7,13 @@ and a scalar log in place of TensorBoard.
 
 Every step is native: GPU target assignment -> training-mode forward -> HIP loss -> backward ->
 (RCCL all-reduce of the flat gradient when launched with torchrun, one rank per GPU) -> Adam.
-Offline differences: VOC through tfds is unavailable, so the splits are seeded synthetic padded
-batches (``SSD_TRAINER_ITEMS`` training images per epoch); ``SSD_TRAINER_EPOCHS`` /
-``SSD_TRAINER_STEPS`` / ``SSD_TRAINER_BATCH`` shorten a run (tests, smoke)."""
+Data: with ``SSD_VOC_DIR`` set to a directory that holds a VOCdevkit, the reference's own calls run
+(trainer.py:27-48): ``get_dataset("voc/2007", "train+validation")`` and ``"test"``, voc/2012 added
+when that year is there, ``shuffle(batch_size * 4)``, then ``data_utils.voc_batches`` (threaded
+decode, one upload and one resize launch per batch, batched augmentation).  Without it the splits are
+seeded synthetic padded batches (``SSD_TRAINER_ITEMS`` training images per epoch, default 512).
+``SSD_TRAINER_ITEMS`` / ``SSD_TRAINER_EPOCHS`` / ``SSD_TRAINER_STEPS`` / ``SSD_TRAINER_BATCH`` shorten
+a run in both modes (tests, smoke)."""
 import json
 import os
 import sys
@@ -21,7 +25,32 @@ if _HERE not in sys.path:
 
 import parallel  # noqa: E402
 from ssd_loss import CustomLoss  # noqa: E402
-from utils import bbox_utils, data_utils, io_utils, train_utils  # noqa: E402
+from utils import bbox_utils, data_utils, io_utils, train_utils, voc_utils  # noqa: E402
+
+with_voc_2012 = True
+
+
+def _voc_splits(voc_dir, batch_size, rank, world):
+    """reference trainer.py:27-38 on the devkit under ``voc_dir`` -> (train dataset, validation dataset, info, training
+    items, validation items); ``SSD_TRAINER_ITEMS`` caps the training items (and the validation items as in the
+    synthetic mode), every rank reads its own shard."""
+    train_data, info = data_utils.get_dataset("voc/2007", "train+validation", voc_dir)
+    val_data, _ = data_utils.get_dataset("voc/2007", "test", voc_dir)
+    train_total_items = data_utils.get_total_item_size(info, "train+validation")
+    val_total_items = data_utils.get_total_item_size(info, "test")
+    if with_voc_2012 and voc_utils.has_year(voc_dir, "voc/2012"):
+        voc_2012_data, voc_2012_info = data_utils.get_dataset("voc/2012", "train+validation", voc_dir)
+        train_total_items += data_utils.get_total_item_size(voc_2012_info, "train+validation")
+        train_data = train_data.concatenate(voc_2012_data)
+    if world > 1:
+        train_data, val_data = train_data.shard(world, rank), val_data.shard(world, rank)
+        train_total_items, val_total_items = len(train_data), len(val_data)
+    cap = int(os.environ.get("SSD_TRAINER_ITEMS", "0"))
+    if cap:
+        train_total_items = min(train_total_items, cap)
+        val_total_items = min(val_total_items, max(batch_size, train_total_items // 8))
+        train_data, val_data = train_data.take(train_total_items), val_data.take(val_total_items)
+    return train_data, val_data, info, train_total_items, val_total_items
 
 
 def fit(model, train_feed, steps_per_epoch, val_feed, validation_steps, epochs, model_path, log_path, rank=0):
@@ -82,19 +111,37 @@ def main(argv=None):
     else:
         from models.ssd_vgg16 import get_model, init_model
     hyper_params = train_utils.get_hyper_params(backbone)
-    labels = ["bg"] + data_utils.get_labels()
-    hyper_params["total_labels"] = len(labels)
-    img_size = hyper_params["img_size"]
+    voc_dir = os.environ.get("SSD_VOC_DIR")
+    augment = os.environ.get("SSD_TRAINER_AUGMENT", "1") != "0"
+    if voc_dir:
+        import augmentation
+        train_data, val_data, info, train_total_items, val_total_items = _voc_splits(voc_dir, batch_size, rank, world)
+        labels = ["bg"] + data_utils.get_labels(info)
+        hyper_params["total_labels"] = len(labels)
+        img_size = hyper_params["img_size"]
+        step_size_train = int(os.environ.get("SSD_TRAINER_STEPS", "0")) or train_utils.get_step_size(train_total_items, batch_size)
+        step_size_val = train_utils.get_step_size(val_total_items, batch_size)
+        if augment:
+            augmentation.seed(4242 + rank)
+        # trainer.py:42-48: preprocessing (+ augmentation on the training stream), shuffle, padded batches
+        train_data = data_utils.voc_batches(train_data.shuffle(batch_size * 4, seed=rank), batch_size, img_size, img_size,
+                                            augmentation_fn=augmentation.apply_batch if augment else None)
+        val_data = data_utils.voc_batches(val_data, batch_size, img_size, img_size)
+        augment = False                                   # done inside the batches
+    else:
+        labels = ["bg"] + data_utils.get_labels()
+        hyper_params["total_labels"] = len(labels)
+        img_size = hyper_params["img_size"]
 
-    train_total_items = int(os.environ.get("SSD_TRAINER_ITEMS", "512"))
-    val_total_items = max(batch_size, train_total_items // 8)
-    step_size_train = int(os.environ.get("SSD_TRAINER_STEPS", "0")) or train_utils.get_step_size(train_total_items, batch_size)
-    step_size_val = min(2, train_utils.get_step_size(val_total_items, batch_size))
-    # every rank draws its own shard of the synthetic stream (batch data-parallel)
-    train_data = list(data_utils.synthetic_dataset(step_size_train * batch_size, batch_size, img_size, len(labels),
-                                                   seed=1000 * rank))
-    val_data = list(data_utils.synthetic_dataset(step_size_val * batch_size, batch_size, img_size, len(labels),
-                                                 seed=777 + 1000 * rank))
+        train_total_items = int(os.environ.get("SSD_TRAINER_ITEMS", "512"))
+        val_total_items = max(batch_size, train_total_items // 8)
+        step_size_train = int(os.environ.get("SSD_TRAINER_STEPS", "0")) or train_utils.get_step_size(train_total_items, batch_size)
+        step_size_val = min(2, train_utils.get_step_size(val_total_items, batch_size))
+        # every rank draws its own shard of the synthetic stream (batch data-parallel)
+        train_data = list(data_utils.synthetic_dataset(step_size_train * batch_size, batch_size, img_size, len(labels),
+                                                       seed=1000 * rank))
+        val_data = list(data_utils.synthetic_dataset(step_size_val * batch_size, batch_size, img_size, len(labels),
+                                                     seed=777 + 1000 * rank))
 
     ssd_model = get_model(hyper_params, max_batch=batch_size)
     ssd_custom_losses = CustomLoss(hyper_params["neg_pos_ratio"], hyper_params["loc_loss_alpha"])
@@ -107,7 +154,7 @@ def main(argv=None):
     prior_boxes = bbox_utils.generate_prior_boxes(hyper_params["feature_map_shapes"], hyper_params["aspect_ratios"])
     # reference trainer.py:42: the TRAINING stream is augmented (fresh draws every epoch), the validation stream is not.
     # SSD_TRAINER_AUGMENT=0 turns it off (deterministic smoke runs).
-    if os.environ.get("SSD_TRAINER_AUGMENT", "1") != "0":
+    if augment:
         import augmentation
         augmentation.seed(4242 + rank)
         train_data = augmentation.augmented(train_data)

@@ -1,17 +1,20 @@
 """Data side of the drop-in.  The reference's ``utils/data_utils.py`` loads PASCAL VOC via
-tensorflow_datasets (not available offline: ``get_dataset`` raises) and converts / resizes every
-image with TF ops; here ``preprocessing`` runs that conversion + bilinear resize as one HIP kernel
-(SURVEY.md 8f N4), and custom images -- PIL + LANCZOS in the reference -- are only decoded by PIL: the resize is
-Pillow's 8-bit resampler restated as HIP kernels (``ssd_resize_lanczos``), a ragged batch per call.  Also kept: the VOC label list, the padded-batch conventions (gt boxes padded with 0, labels with
--1), and seeded synthetic generators shaped like the reference's batches."""
+tensorflow_datasets and converts / resizes every image with TF ops; here ``get_dataset`` reads a
+VOCdevkit directory from disk (``utils/voc_utils.py``; without one it raises as before),
+``preprocessing`` runs that conversion + bilinear resize as one HIP kernel,
+``voc_batches`` does it for a whole ragged batch per launch (``ssd_preprocess_ragged``) behind a
+decoding thread pool, and custom images -- PIL + LANCZOS in the reference -- are only decoded by
+PIL: the resize is Pillow's 8-bit resampler restated as HIP kernels (``ssd_resize_lanczos``), a
+ragged batch per call.  Also kept: the VOC label list, the padded-batch conventions (gt boxes
+padded with 0, labels with -1), and seeded synthetic generators shaped like the reference's
+batches."""
 import functools
 import math
 
 import numpy as np
 
-VOC_LABELS = ["aeroplane", "bicycle", "bird", "boat", "bottle", "bus", "car", "cat", "chair", "cow",
-              "diningtable", "dog", "horse", "motorbike", "person", "pottedplant", "sheep", "sofa",
-              "train", "tvmonitor"]
+from . import voc_utils
+from .voc_utils import VOC_LABELS  # noqa: F401  (the 20 class names, alphabetical)
 
 
 def preprocessing(image_data, final_height, final_width, augmentation_fn=None, evaluate=False):
@@ -32,14 +35,21 @@ def preprocessing(image_data, final_height, final_width, augmentation_fn=None, e
     out = torch.empty((int(final_height), int(final_width), C), dtype=torch.float32, device=src.device)
     _h.check(_h.lib().ssd_preprocess(_h.ptr(src), 1, H, W, C, int(final_height), int(final_width), _h.ptr(out),
                                      _h.stream()), "preprocessing")
+    gt_boxes, gt_labels = _ground_truth(image_data, evaluate)
+    if augmentation_fn:
+        out, gt_boxes = augmentation_fn(out, gt_boxes)
+    return out, gt_boxes, gt_labels
+
+
+def _ground_truth(image_data, evaluate):
+    """``preprocessing``'s ground truth of one item: float32 boxes, labels + 1 as int32, difficult objects dropped
+    when ``evaluate``."""
     gt_boxes = np.asarray(image_data["objects"]["bbox"], np.float32)
     gt_labels = (np.asarray(image_data["objects"]["label"]) + 1).astype(np.int32)
     if evaluate:
         not_diff = np.logical_not(np.asarray(image_data["objects"]["is_difficult"], bool))
         gt_boxes, gt_labels = gt_boxes[not_diff], gt_labels[not_diff]
-    if augmentation_fn:
-        out, gt_boxes = augmentation_fn(out, gt_boxes)
-    return out, gt_boxes, gt_labels
+    return gt_boxes, gt_labels
 
 
 def preprocess_batch(images_u8, final_height, final_width):
@@ -66,10 +76,12 @@ def get_labels(info=None):
 
 
 def get_dataset(name, split, data_dir="~/tensorflow_datasets"):
-    """reference utils/data_utils.py:32-45 -- tfds is not available in this build."""
+    """reference utils/data_utils.py:32-45.  tfds is not available in this build: ``voc/2007`` and ``voc/2012`` are read
+    from a VOCdevkit directory under ``data_dir`` (``voc_utils.get_dataset``: a lazy ``VocDataset`` and an info object
+    ``get_total_item_size`` / ``get_labels`` accept); without that directory this raises ``RuntimeError`` as it always
+    did, naming the path it looked for.  Nothing is downloaded."""
     assert split in ["train", "train+validation", "validation", "test"]
-    raise RuntimeError("tensorflow_datasets is not available; use synthetic_dataset() or feed arrays "
-                       "[B,S,S,3] float32 in [0,1] directly")
+    return voc_utils.get_dataset(name, split, data_dir)
 
 
 def get_total_item_size(info, split):
@@ -174,19 +186,28 @@ def resize_lanczos_batch(images, final_height, final_width, out=None, out_u8=Non
                                         _h.stream()), "resize_lanczos_batch")
         return out
     layout = _lanczos_layout(arrays, fh, fw)
+    packed = _upload_packed(dev, layout["total"], lambda host: _lanczos_fill(host, arrays, layout))
+    _lanczos_launch(packed, layout, out, out_u8)
+    return out
+
+
+def _upload_packed(dev, total, fill):
+    """``fill(host)`` writes ``total`` bytes into the device's pinned staging buffer (grown in powers of two, reused once
+    the previous batch's copy has left it); ONE asynchronous copy on the current stream makes the device buffer."""
+    import torch
+    import ssd_hip as _h
     st = _resize_staging.get(dev.index)
-    if st is None or st[0].numel() < layout["total"]:
-        size = max(1 << (layout["total"] - 1).bit_length(), 1 << 20)
+    if st is None or st[0].numel() < total:
+        size = max(1 << (total - 1).bit_length(), 1 << 20)
         st = _resize_staging[dev.index] = [_h.pinned_empty((size,), torch.uint8), None]
     if st[1] is not None:
         st[1].synchronize()                                                       # the previous batch's copy has left the buffer
-    _lanczos_fill(st[0].numpy(), arrays, layout)
-    packed = torch.empty(layout["total"], dtype=torch.uint8, device=dev)
-    packed.copy_(st[0][:layout["total"]], non_blocking=True)
+    fill(st[0].numpy())
+    packed = torch.empty(total, dtype=torch.uint8, device=dev)
+    packed.copy_(st[0][:total], non_blocking=True)
     st[1] = torch.cuda.Event()
     st[1].record()
-    _lanczos_launch(packed, layout, out, out_u8)
-    return out
+    return packed
 
 
 def _lanczos_layout(arrays, fh, fw):
@@ -254,6 +275,159 @@ def _lanczos_launch(packed, layout, out, out_u8=None):
                                          _h.ptr(ws), ws.numel(), _h.stream()), "resize_lanczos_batch")
 
 
+def _ragged_arrays(images):
+    import torch
+    arrays = []
+    for im in images:
+        a = im.detach().cpu().numpy() if isinstance(im, torch.Tensor) else np.asarray(im)
+        if a.dtype != np.uint8 or a.ndim != 3:
+            raise ValueError("images must be uint8 [H,W,3], got %s %s" % (a.dtype, tuple(a.shape)))
+        arrays.append(a)
+    return arrays
+
+
+def _ragged_layout(arrays):
+    """Where one ``ssd_preprocess_ragged`` call's input sits in ONE buffer: descriptors | images, each part at a multiple
+    of 16 bytes (``src_offset`` counts from the first image)."""
+    import ssd_hip as _h
+    desc = np.zeros(len(arrays), _h.IMAGE_DESC_DTYPE)
+    src_at = (desc.nbytes + 15) & ~15
+    total = src_at
+    for b, a in enumerate(arrays):
+        desc[b]["H"], desc[b]["W"] = a.shape[:2]
+        desc[b]["src_offset"] = total - src_at
+        total += (a.size + 15) & ~15
+    return {"desc": desc, "src_at": src_at, "total": total}
+
+
+def _ragged_fill(host, arrays, layout):
+    desc = layout["desc"]
+    host[:desc.nbytes] = desc.view(np.uint8)
+    for b, a in enumerate(arrays):
+        at = layout["src_at"] + int(desc[b]["src_offset"])
+        host[at:at + a.size].reshape(a.shape)[...] = a
+
+
+def _ragged_launch(packed, layout, fh, fw, out):
+    """``ssd_preprocess_ragged`` on a device copy ``packed`` of the filled buffer, on the current stream."""
+    import ssd_hip as _h
+    desc, base, src_at = layout["desc"], packed.data_ptr(), layout["src_at"]
+    _h.check(_h.lib().ssd_preprocess_ragged(base + src_at, layout["total"] - src_at, desc.ctypes.data, base, len(desc), 3,
+                                            fh, fw, _h.ptr(out), _h.stream()), "preprocess_ragged_batch")
+
+
+def preprocess_ragged_batch(images, final_height, final_width, out=None):
+    """``preprocessing``'s image half for a whole batch: a list of uint8 ``[H,W,3]`` arrays / tensors of ANY sizes ->
+    float32 ``[B,final_height,final_width,3]`` on the GPU, image b bitwise what ``preprocessing`` makes of it alone.  One
+    packed upload (descriptors, pixels: one pinned staging buffer, one asynchronous copy) and ONE launch
+    (``ssd_preprocess_ragged``) per batch.  ``out``: a contiguous float32 device tensor of that shape to write into
+    (e.g. a slice of a larger batch)."""
+    import torch
+    import ssd_hip as _h
+    fh, fw = int(final_height), int(final_width)
+    arrays = _ragged_arrays(images)
+    B = len(arrays)
+    C = arrays[0].shape[2] if B else 3
+    if any(a.shape[2] != C for a in arrays):
+        raise ValueError("images of one batch must have the same number of channels")
+    dev = _h.device()
+    if out is not None and (tuple(out.shape) != (B, fh, fw, C) or out.dtype != torch.float32 or out.device != dev
+                            or not out.is_contiguous()):
+        raise ValueError("%s must be a contiguous %s device tensor %s" % ("out", torch.float32, (B, fh, fw, C)))
+    if out is None:
+        out = torch.empty((B, fh, fw, C), dtype=torch.float32, device=dev)
+    if B == 0 or C != 3 or not (1 <= fh <= 16384 and 1 <= fw <= 16384):           # nothing to pack: the library answers
+        _h.check(_h.lib().ssd_preprocess_ragged(None, 0, None, None, B, C, fh, fw, _h.ptr(out), _h.stream()),
+                 "preprocess_ragged_batch")
+        return out
+    layout = _ragged_layout(arrays)
+    packed = _upload_packed(dev, layout["total"], lambda host: _ragged_fill(host, arrays, layout))
+    _ragged_launch(packed, layout, fh, fw, out)
+    return out
+
+
+def data_workers(workers=None):
+    """Size of the decoding pool: ``workers``, else ``SSD_DATA_WORKERS``, else 8; always within 1..16 (never the
+    machine's CPU count: the pool shares the host with the training loop and with other jobs)."""
+    import os
+    n = int(workers) if workers else int(os.environ.get("SSD_DATA_WORKERS", "0") or 0) or 8
+    return max(1, min(n, 16))
+
+
+class voc_batches(object):
+    """The reference's ``dataset.map(preprocessing).padded_batch(batch_size)`` (trainer.py:42-48, predictor.py:40-43) with
+    one upload and one launch per batch: iterating yields ``(imgs device float32 [b,h,w,3], gt_boxes [b,G,4], gt_labels
+    [b,G])``, bitwise what ``padded_batch(preprocessing(item, h, w, evaluate=evaluate) for item in dataset)`` yields.
+    ``dataset``: a ``voc_utils.VocDataset`` (its images are decoded by a pool of ``data_workers(workers)`` threads --
+    Pillow releases the GIL while it decodes -- at most ``prefetch`` batches ahead of the one the consumer is about to
+    get, so up to ``prefetch + 1`` batches of decoded images are held) or any iterable of tfds-shaped dicts (already
+    decoded).  A pass that is abandoned half-way (``train_utils.generator`` after the last step) shuts its pool down
+    when the generator is closed or collected: decodes not yet started are cancelled, the few in flight are waited
+    for.  The order is the dataset's whatever the worker count.  ``augmentation_fn``: the batched
+    ``augmentation.apply_batch``, applied after the resize as the reference does.  Every ``iter()`` is a fresh pass (a
+    shuffled dataset draws a new order), so ``train_utils.generator`` can cycle it."""
+
+    def __init__(self, dataset, batch_size, final_height, final_width, evaluate=False, augmentation_fn=None, workers=None,
+                 prefetch=2):
+        if int(batch_size) < 1:
+            raise ValueError("batch_size must be positive, got %r" % (batch_size,))
+        self.dataset, self.batch_size = dataset, int(batch_size)
+        self.size = (int(final_height), int(final_width))
+        self.evaluate, self.augmentation_fn = bool(evaluate), augmentation_fn
+        self.workers, self.prefetch = data_workers(workers), max(int(prefetch), 0)
+
+    def _decode_jobs(self):
+        """``(callable, argument)`` per item, in order: calling it gives the decoded tfds-shaped dict."""
+        if hasattr(self.dataset, "iter_records"):
+            return ((self.dataset.load, r) for r in self.dataset.iter_records())
+        return ((_identity, item) for item in self.dataset)
+
+    def __iter__(self):
+        import collections
+        import itertools
+        from concurrent.futures import ThreadPoolExecutor
+        jobs = self._decode_jobs()
+        pending = collections.deque()
+        pool = ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix="ssd-data")
+        try:
+            def submit_next():
+                chunk = list(itertools.islice(jobs, self.batch_size))
+                if chunk:
+                    pending.append([pool.submit(fn, arg) for fn, arg in chunk])
+                return bool(chunk)
+            more = submit_next()
+            while pending:
+                while more and len(pending) <= self.prefetch:
+                    more = submit_next()
+                items = [f.result() for f in pending.popleft()]
+                yield self._batch(items)
+        finally:
+            pool.shutdown(wait=True, cancel_futures=True)
+
+    def _batch(self, items):
+        imgs = preprocess_ragged_batch([it["image"] for it in items], self.size[0], self.size[1])
+        gt_boxes, gt_labels = _pad_ground_truth([_ground_truth(it, self.evaluate) for it in items], get_padding_values())
+        if self.augmentation_fn:
+            imgs, gt_boxes = self.augmentation_fn(imgs, gt_boxes, gt_labels)
+        return imgs, gt_boxes, gt_labels
+
+
+def _identity(x):
+    return x
+
+
+def _pad_ground_truth(pairs, pv):
+    """``padded_batch``'s ground truth: ``(boxes [g,4], labels [g])`` pairs padded to the longest (at least 1) with
+    ``pv[1]`` / ``pv[2]``."""
+    g = max([len(bb) for bb, _ in pairs] + [1])
+    gt = np.full((len(pairs), g, 4), pv[1], np.float32)
+    gl = np.full((len(pairs), g), pv[2], np.int32)
+    for i, (bb, ll) in enumerate(pairs):
+        gt[i, :len(bb)] = np.asarray(bb, np.float32).reshape(-1, 4)
+        gl[i, :len(ll)] = np.asarray(ll, np.int32)
+    return gt, gl
+
+
 def _decode_custom_image(img_path):
     """One custom image as uint8 [H,W,3]: PIL decodes (``.convert("RGB")``); ``*.npy`` files hold the array itself."""
     if img_path.endswith(".npy"):
@@ -295,12 +469,7 @@ def padded_batch(items, batch_size, padding_values=None):
     batch = []
 
     def flush():
-        g = max([len(b[1]) for b in batch] + [1])
-        gt = np.full((len(batch), g, 4), pv[1], np.float32)
-        gl = np.full((len(batch), g), pv[2], np.int32)
-        for i, (_, bb, ll) in enumerate(batch):
-            gt[i, :len(bb)] = np.asarray(bb, np.float32).reshape(-1, 4)
-            gl[i, :len(ll)] = np.asarray(ll, np.int32)
+        gt, gl = _pad_ground_truth([(bb, ll) for _, bb, ll in batch], pv)
         imgs = [b[0] for b in batch]
         x = torch.stack(imgs) if isinstance(imgs[0], torch.Tensor) else np.stack(imgs)
         return x, gt, gl
