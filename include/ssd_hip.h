@@ -524,6 +524,28 @@ int ssd_net_regularization_loss(ssd_net* net, float* host_out);
  * "mean:<layer>", "var:<layer>".  Returns the element count (host_out NULL: query). */
 long ssd_net_train_fetch(ssd_net* net, const char* what, int B, float* host_out, size_t cap);
 
+/* Test / bench hooks of the training backward kernels on caller-owned memory (the kernels and launch plans of
+ * ssd_net_train_forward_backward, outside a net).
+ *
+ * Weight gradient of a dense conv: dW [kh,kw,Cin,N] (Keras HWIO) = im2col(x)^T * g, x [B,H,W,Cin] the forward input
+ * of geometry `d` (d->Cout, act and has_residual are not used), g [B*Ho*Wo][ldg] the gradient of the conv output of
+ * which the first N columns are taken (ldg >= N: a head conv's padded dY; g_dev may point at a column offset).
+ * `config` selects one of ssd_conv_wgrad_num_configs() MFMA tile shapes, -1 the padded-area heuristic.  The M chunks'
+ * partial sums need ssd_conv_wgrad_workspace_floats(d, N) floats of workspace (enough for every config; more than
+ * kh*kw*Cin*N floats means more than one chunk).  SSD_E_INVALID, nothing launched: NULL pointers, bad geometry, a
+ * config out of range, ldg < N, a workspace that is too small. */
+int ssd_conv_wgrad_num_configs(void);
+size_t ssd_conv_wgrad_workspace_floats(const ssd_conv_desc* d, int N);
+int ssd_conv2d_wgrad_ex(const ssd_conv_desc* d, const float* x_dev, const float* g_dev, int ldg, int N, int config,
+                        float* dW_dev, float* workspace_dev, size_t workspace_floats, void* stream);
+/* Backward of the 3x3 depthwise conv (pads after = 1, as TF SAME and keras correct_pad give for k = 3:
+ * Ho = (H + pad_t + 1 - 3) / stride + 1): dw [3,3,C] from x [B,H,W,C] and g [B,Ho,Wo,C]; dx [B,H,W,C] = (accumulate ?
+ * dx : 0) + the data gradient under w [3,3,C].  C % 4 == 0, stride 1 or 2, pads 0 or 1, 16-byte aligned tensors;
+ * 9 * C * ceil(B*Ho*Wo / 64) floats of workspace always suffice.  Anything else is SSD_E_INVALID, nothing launched. */
+int ssd_dwconv3x3_backward(const float* x_dev, const float* g_dev, const float* w_dev, int B, int H, int W, int C, int stride,
+                           int pad_t, int pad_l, int accumulate, float* dx_dev, float* dw_dev, float* workspace_dev,
+                           size_t workspace_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -346,6 +346,40 @@ def test_new_entry_points_validate_without_a_device():
     l.ssd_net_destroy(net)
 
 
+def test_backward_test_hooks_validate_without_a_device():
+    """ssd_conv2d_wgrad_ex / ssd_dwconv3x3_backward refuse bad arguments with SSD_E_INVALID before anything is launched."""
+    import ssd_hip
+    l = ssd_hip.lib()
+    one = ctypes.c_void_p(4096)            # non-NULL, aligned, never dereferenced: the checks fail first
+    n = l.ssd_conv_wgrad_num_configs()
+    assert n == 12
+    d = ssd_hip.ConvDesc(3, 38, 38, 64, 64, 3, 3, 1, 1, 1, 1, 1, 1, 0, 0)
+    need = l.ssd_conv_wgrad_workspace_floats(ctypes.byref(d), 64)
+    assert need > 9 * 64 * 64 and need % (9 * 64 * 64) == 0            # more than one M chunk
+    assert l.ssd_conv_wgrad_workspace_floats(None, 64) == 0 and l.ssd_conv_wgrad_workspace_floats(ctypes.byref(d), 0) == 0
+    for cfg in range(-1, n):               # a workspace that is too small, for every tile shape
+        assert l.ssd_conv2d_wgrad_ex(ctypes.byref(d), one, one, 64, 64, cfg, one, one, 9 * 64 * 64 - 1, None) == -1
+        assert b"workspace" in l.ssd_last_error()
+    for cfg in (-2, n, n + 5):             # a config out of range
+        assert l.ssd_conv2d_wgrad_ex(ctypes.byref(d), one, one, 64, 64, cfg, one, one, need, None) == -1
+        assert b"config" in l.ssd_last_error()
+    assert l.ssd_conv2d_wgrad_ex(ctypes.byref(d), one, one, 60, 64, 0, one, one, need, None) == -1            # ldg < N
+    assert l.ssd_conv2d_wgrad_ex(ctypes.byref(d), None, one, 64, 64, 0, one, one, need, None) == -1
+    assert l.ssd_conv2d_wgrad_ex(ctypes.byref(d), one, one, 64, 64, 0, one, None, need, None) == -1
+    assert l.ssd_conv2d_wgrad_ex(None, one, one, 64, 64, 0, one, one, need, None) == -1
+    bad = ssd_hip.ConvDesc(1, 2, 2, 64, 64, 3, 3, 1, 1, 0, 0, 0, 0, 0, 0)                                        # empty output
+    assert l.ssd_conv2d_wgrad_ex(ctypes.byref(bad), one, one, 64, 64, 0, one, one, need, None) == -1
+    big = 1 << 30
+    dw = lambda **k: l.ssd_dwconv3x3_backward(*[{**dict(x=one, g=one, w=one, B=2, H=19, W=19, C=96, stride=1, pad_t=1, pad_l=1,
+                                                         acc=0, dx=one, dwo=one, ws=one, wsf=big, st=None), **k}[a]
+                                                  for a in ("x", "g", "w", "B", "H", "W", "C", "stride", "pad_t", "pad_l", "acc",
+                                                            "dx", "dwo", "ws", "wsf", "st")])
+    assert dw(C=66) == -1 and b"multiple of 4" in l.ssd_last_error()                                             # C % 4
+    assert dw(wsf=9 * 96 - 1) == -1 and b"workspace" in l.ssd_last_error()
+    assert dw(stride=3) == -1 and dw(pad_t=2) == -1 and dw(x=None) == -1 and dw(ws=None) == -1 and dw(B=0) == -1
+    assert dw(dx=ctypes.c_void_p(4100)) == -1                                                                    # alignment
+
+
 def test_data_utils_padded_batch_and_custom_image_listing(tmp_path):
     """Host logic of the reference's dataset plumbing (utils/data_utils.py:47-59, 80-91, 117-122; predictor.py:43):
     padded batches (ground truth padded with 0 / -1 to the longest of the batch, ragged last batch), the listing

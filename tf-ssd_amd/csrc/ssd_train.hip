@@ -262,9 +262,13 @@ __global__ __launch_bounds__(256) void col_reduce_kernel(const RedParams p) {
 
 // 16-byte form of col_reduce_kernel for C % 4 == 0 (every tensor of both graphs): thread = 4
 // consecutive channels; block = CQ channel quads x (256 / CQ) row lanes.  RED_STATS: one pass for
-// the batch statistics -- sums of (x - K) and (x - K)^2 with the per-column shift K = x[0][c] common to
-// every chunk (a sample of the column, so (mean - K)^2 ~ var: no cancellation in s2/M - (s1/M)^2).
+// the batch statistics -- sums of (x - K) and (x - K)^2 with a per-column shift K common to every chunk.
+// K = mean of four samples of the column from the interior of the tensor (rows (2j + 1) M / 8): (mean - K)^2 is
+// ~ var / 4, so s2/M - (s1/M)^2 cancels at most a fraction of var.  (A single sample is not enough: K = x[0][c], a
+// zero-padded corner pixel, lay up to several sigma off the mean and cost the variance ~80 u sum (|x| + |mean|)^2 / M.)
+// Every thread of every chunk and col_finalize_kernel form K with the same expression: bit-identical.
 typedef float tf32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ long stats_shift_row(const long M, const int j) { return (2 * j + 1) * M / 8; }
 template <int OP>
 __global__ __launch_bounds__(256) void col_reduce4_kernel(const RedParams p) {
     __shared__ tf32x4 sh[2][256];
@@ -277,7 +281,13 @@ __global__ __launch_bounds__(256) void col_reduce4_kernel(const RedParams p) {
     if (c < p.C) {
         tf32x4 mean = s1, istd = s1, gamma = s1, beta = s1;
         if (OP == RED_SQDEV || OP == RED_BN_BWD) mean = *reinterpret_cast<const tf32x4*>(p.mean + c);
-        if (OP == RED_STATS) mean = *reinterpret_cast<const tf32x4*>(p.a + c);          // the shift K
+        if (OP == RED_STATS) {                                                          // the shift K
+            const tf32x4 k0 = *reinterpret_cast<const tf32x4*>(p.a + stats_shift_row(p.M, 0) * p.lda + c);
+            const tf32x4 k1 = *reinterpret_cast<const tf32x4*>(p.a + stats_shift_row(p.M, 1) * p.lda + c);
+            const tf32x4 k2 = *reinterpret_cast<const tf32x4*>(p.a + stats_shift_row(p.M, 2) * p.lda + c);
+            const tf32x4 k3 = *reinterpret_cast<const tf32x4*>(p.a + stats_shift_row(p.M, 3) * p.lda + c);
+            mean = ((k0 + k1) + (k2 + k3)) * 0.25f;
+        }
         if (OP == RED_BN_BWD) {
             istd = *reinterpret_cast<const tf32x4*>(p.istd + c);
             gamma = *reinterpret_cast<const tf32x4*>(p.gamma + c);
@@ -323,13 +333,14 @@ __global__ __launch_bounds__(256) void col_reduce4_kernel(const RedParams p) {
     }
 }
 // out1[c] = scale * sum_chunks partial[.][0][c]; out2 likewise (nullable); mode 1: out2 = rsqrt(out1 + eps);
-// mode 2 (batch statistics from RED_STATS partials, shift row `shift`): out1 = mean, out2 = biased variance,
+// mode 2 (batch statistics from RED_STATS partials of the [shift_M][C] tensor `shift`): out1 = mean, out2 = biased variance,
 // out3 = rsqrt(var + eps), and the Keras moving averages mm / mv move towards them
 __global__ __launch_bounds__(256) void col_finalize_kernel(const float* __restrict__ partial, const int chunks, const int C,
                                                           const float scale, float* out1, float* out2, const int mode,
                                                           const float eps, const float* shift = nullptr, float* out3 = nullptr,
                                                           float* mm = nullptr, float* mv = nullptr,
-                                                          const float one_minus_momentum = 0.f, const float bessel = 1.f) {
+                                                          const float one_minus_momentum = 0.f, const float bessel = 1.f,
+                                                          const long shift_M = 0) {
     // block = 16 columns x 16 chunk lanes (lane k sums chunks k, k+16, ... in order; the 16 lane
     // sums are combined in a fixed order: deterministic).  The data is tiny; the kernel is latency
     // bound, hence many short dependent chains instead of few long ones.
@@ -369,7 +380,9 @@ __global__ __launch_bounds__(256) void col_finalize_kernel(const float* __restri
     s1 *= scale;
     s2 *= scale;
     if (mode == 2) {
-        const float mean = shift[c] + s1;
+        const float K = ((shift[stats_shift_row(shift_M, 0) * C + c] + shift[stats_shift_row(shift_M, 1) * C + c]) +
+                         (shift[stats_shift_row(shift_M, 2) * C + c] + shift[stats_shift_row(shift_M, 3) * C + c])) * 0.25f;
+        const float mean = K + s1;
         const float var = fmaxf(s2 - s1 * s1, 0.0f);
         out1[c] = mean;
         out2[c] = var;
@@ -1038,7 +1051,7 @@ static int bn_stats(ssd_train_state& s, TrainLayer& t, long M, int C, float* mov
         if (rc) return rc;
         hipLaunchKernelGGL(col_finalize_kernel, dim3((C + 15) / 16), dim3(256), 0, st, s.partial, (int)chunks, C,
                            1.0f / (float)M, t.mean, t.var, 2, kBnEps, t.pre, t.istd, moving_mean, moving_var,
-                           1.0f - kBnMomentum, bessel);
+                           1.0f - kBnMomentum, bessel, M);
         SSD_LAUNCH_CHECK();
         return SSD_OK;
     }
@@ -1159,9 +1172,28 @@ static int launch_conv(ConvParams& p, hipStream_t st) {
     return conv_launch(p, cfg, st);
 }
 
-// dW [K][N] (row-major, = Keras HWIO) = im2col(X)^T * G with tile shape `cfg`
-static int wgrad_with(ssd_train_state& s, const Layer& l, int B, const float* x, const float* g, int ldg, int N, float* dW,
-                      hipStream_t st, const WgradCfg* cfg, bool count) {
+// dW [K][N] (row-major, = Keras HWIO) = im2col(X)^T * G with tile shape `cfg`.  The M chunks' partial sums go to the
+// caller's slab `partial` (`partial_floats` floats, wgrad_chunks * K * N are needed: too small a slab is an argument error).
+static long wgrad_chunks(const Layer& l, int B, int N, const WgradCfg* cfg, long* rows_per_chunk, long* tiles_out) {
+    const bool im2col = l.Cin % 4 != 0;
+    const int rows = im2col ? l.kh * l.kw * l.Cin : l.Cin;
+    const long ctiles = (rows + cfg->tc - 1) / cfg->tc, ntiles = (N + cfg->tn - 1) / cfg->tn;
+    const long tiles = (im2col ? 1L : (long)l.kh * l.kw) * ctiles * ntiles;
+    const long M = (long)B * l.Ho * l.Wo;
+    long rpc = 0;
+    long chunks = chunks_for(M, tiles, &rpc, 128, 1024);
+    // bound the slab: chunks * K * N floats
+    const size_t kn = (size_t)l.kh * l.kw * l.Cin * N;
+    while (chunks > 1 && (size_t)chunks * kn > ((size_t)96 << 20)) {
+        rpc *= 2;
+        chunks = (M + rpc - 1) / rpc;
+    }
+    *rows_per_chunk = rpc;
+    if (tiles_out) *tiles_out = tiles;
+    return chunks;
+}
+static int wgrad_with(const Layer& l, int B, const float* x, const float* g, int ldg, int N, float* dW, hipStream_t st,
+                      const WgradCfg* cfg, bool count, float* partial, size_t partial_floats) {
     WgradParams p{};
     p.x = x; p.g = g;
     p.B = B; p.H = l.H; p.W = l.W; p.Cin = l.Cin; p.Ho = l.Ho; p.Wo = l.Wo;
@@ -1174,28 +1206,68 @@ static int wgrad_with(ssd_train_state& s, const Layer& l, int B, const float* x,
     p.ntiles = (N + cfg->tn - 1) / cfg->tn;
     p.vec_x = (l.Cin % 4 == 0) && (((uintptr_t)x & 15) == 0);
     p.vec_g = (ldg % 4 == 0) && (((uintptr_t)g & 15) == 0);
-    const long tiles = (p.im2col ? 1L : (long)l.kh * l.kw) * p.ctiles * p.ntiles;
-    long rpc = 0;
-    long chunks = chunks_for(p.M, tiles, &rpc, 128, 1024);
-    // bound the slab: chunks * K * N floats
+    long rpc = 0, tiles = 0;
+    const long chunks = wgrad_chunks(l, B, N, cfg, &rpc, &tiles);
     const size_t kn = (size_t)p.K * N;
-    while (chunks > 1 && (size_t)chunks * kn > ((size_t)96 << 20)) {
-        rpc *= 2;
-        chunks = (p.M + rpc - 1) / rpc;
-    }
-    if ((size_t)chunks * kn > s.partial_w_floats) {      // grow-only, own slab (weight gradients may run beside the reductions of the main chain)
-        float* np = nullptr;
-        int rca = talloc(s, (size_t)chunks * kn, &np);
-        if (rca) return rca;
-        s.partial_w = np;
-        s.partial_w_floats = (size_t)chunks * kn;
-    }
+    SSD_CHECK_ARG((size_t)chunks * kn <= partial_floats, "weight gradient: the workspace holds %zu floats, %zu are needed",
+                  partial_floats, (size_t)chunks * kn);
     p.rows_per_chunk = rpc;
-    p.partial = s.partial_w;
+    p.partial = partial;
     hipLaunchKernelGGL(cfg->fn, dim3((unsigned)tiles, (unsigned)chunks), dim3(256), 0, st, p);
     SSD_LAUNCH_CHECK();
     if (count) g_step_flops[2] += 2.0 * (double)p.M * p.K * N;
-    return chunk_sum(s.partial_w, chunks, (long)kn, dW, st);
+    return chunk_sum(partial, chunks, (long)kn, dW, st);
+}
+// the training step's slab: grow-only, its own (weight gradients may run beside the reductions of the main chain)
+static int wgrad_with(ssd_train_state& s, const Layer& l, int B, const float* x, const float* g, int ldg, int N, float* dW,
+                      hipStream_t st, const WgradCfg* cfg, bool count) {
+    long rpc = 0;
+    const size_t need = (size_t)wgrad_chunks(l, B, N, cfg, &rpc, nullptr) * l.kh * l.kw * l.Cin * N;
+    if (need > s.partial_w_floats) {
+        float* np = nullptr;
+        int rca = talloc(s, need, &np);
+        if (rca) return rca;
+        s.partial_w = np;
+        s.partial_w_floats = need;
+    }
+    return wgrad_with(l, B, x, g, ldg, N, dW, st, cfg, count, s.partial_w, s.partial_w_floats);
+}
+
+// Heuristic tile shape: least padded tile area first (MFMA work); among equals the shape that stages the fewest floats
+// per M row (see wgrad below)
+static const WgradCfg* wgrad_heuristic(const Layer& l, int N) {
+    const bool im2col = l.Cin % 4 != 0;
+    const int rows = im2col ? l.kh * l.kw * l.Cin : l.Cin;
+    const WgradCfg* cfg = &kWgrad[0];
+    long best_area = -1, best_staged = -1;
+    for (const auto& c : kWgrad) {
+        const long ct = (rows + c.tc - 1) / c.tc, nt = (N + c.tn - 1) / c.tn;
+        const long area = ct * c.tc * nt * c.tn, staged = ct * nt * (c.tc + c.tn);
+        if (best_area < 0 || area < best_area || (area == best_area && staged < best_staged)) {
+            best_area = area; best_staged = staged; cfg = &c;
+        }
+    }
+    return cfg;
+}
+
+// Depthwise 3x3 backward: weight gradient (M chunks into dp.partial [chunks][9][C], then their sum) and data gradient
+// (stride 1: the four-column form).  dw_bwd_chunks sets dp.rows_per_chunk and returns the chunk count.
+static long dw_bwd_chunks(DwBwdParams& dp) {
+    long rpc = 0;
+    const long chunks = chunks_for(dp.M, (dp.C + 63) / 64, &rpc, 64, 2048);
+    dp.rows_per_chunk = rpc;
+    return chunks;
+}
+static int dw_bwd_launch(const DwBwdParams& dp, long chunks, float* dw_out, hipStream_t st) {
+    hipLaunchKernelGGL(dw_wgrad_kernel, dim3((dp.C + 63) / 64, (unsigned)chunks), dim3(256), 0, st, dp);
+    int rc = chunk_sum(dp.partial, chunks, 9L * dp.C, dw_out, st);
+    if (rc) return rc;
+    if (dp.stride == 1)
+        hipLaunchKernelGGL(dw_dgrad4_kernel, dim3(grid_for((long)dp.B * dp.H * ((dp.W + 3) / 4) * (dp.C / 4))), dim3(256), 0, st, dp);
+    else
+        hipLaunchKernelGGL(dw_dgrad_kernel, dim3(grid_for((long)dp.B * dp.H * dp.W * (dp.C / 4))), dim3(256), 0, st, dp);
+    SSD_LAUNCH_CHECK();
+    return SSD_OK;
 }
 
 // Tile shape of a weight gradient.  Heuristic: least padded tile area first (MFMA work); among equals the shape that
@@ -1206,19 +1278,7 @@ static int wgrad_with(ssd_train_state& s, const Layer& l, int B, const float* x,
 // accumulated: running it repeatedly is harmless) and the fastest kept for the process.
 static int wgrad(ssd_train_state& s, const Layer& l, int B, const float* x, const float* g, int ldg, int N, float* dW,
                  hipStream_t st) {
-    const bool im2col = l.Cin % 4 != 0;
-    const int rows = im2col ? l.kh * l.kw * l.Cin : l.Cin;
-    const WgradCfg* cfg = &kWgrad[0];
-    {
-        long best_area = -1, best_staged = -1;
-        for (const auto& c : kWgrad) {
-            const long ct = (rows + c.tc - 1) / c.tc, nt = (N + c.tn - 1) / c.tn;
-            const long area = ct * c.tc * nt * c.tn, staged = ct * nt * (c.tc + c.tn);
-            if (best_area < 0 || area < best_area || (area == best_area && staged < best_staged)) {
-                best_area = area; best_staged = staged; cfg = &c;
-            }
-        }
-    }
+    const WgradCfg* cfg = wgrad_heuristic(l, N);
     static const int tune = getenv("SSD_HIP_TRAIN_AUTOTUNE") ? atoi(getenv("SSD_HIP_TRAIN_AUTOTUNE")) : 1;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(st, &cs);
@@ -1741,21 +1801,12 @@ int ssd_net_train_forward_backward(ssd_net* net, const float* image_dev, int B, 
             dp.stride = l.stride; dp.pad_t = l.pt; dp.pad_l = l.pl;
             dp.M = M;
             dp.accumulate = s.gwritten[l.in];
-            const int ctiles = (l.Cin + 63) / 64;
-            long rpc = 0;
-            const long chunks = chunks_for(M, ctiles, &rpc, 64, 2048);
+            const long chunks = dw_bwd_chunks(dp);
             rc = ensure_partial(s, (size_t)chunks * 9 * l.Cin);
             if (rc) return rc;
-            dp.rows_per_chunk = rpc;
             dp.partial = s.partial;
-            hipLaunchKernelGGL(dw_wgrad_kernel, dim3(ctiles, (unsigned)chunks), dim3(256), 0, st, dp);
-            rc = chunk_sum(s.partial, chunks, 9L * l.Cin, grads_flat_dev + t.g_kernel, st);
+            rc = dw_bwd_launch(dp, chunks, grads_flat_dev + t.g_kernel, st);
             if (rc) return rc;
-            if (l.stride == 1)
-                hipLaunchKernelGGL(dw_dgrad4_kernel, dim3(grid_for((long)B * l.H * ((l.W + 3) / 4) * (l.Cin / 4))), dim3(256), 0, st, dp);
-            else
-                hipLaunchKernelGGL(dw_dgrad_kernel, dim3(grid_for((long)B * l.H * l.W * (l.Cin / 4))), dim3(256), 0, st, dp);
-            SSD_LAUNCH_CHECK();
             s.gwritten[l.in] = 1;
             continue;
         }
@@ -1960,6 +2011,75 @@ long ssd_net_train_fetch(ssd_net* net, const char* what, int B, float* host_out,
         return SSD_E_HIP;
     }
     return (long)n;
+}
+
+// ---------------------------------------------------------------------- test / bench hooks of the backward kernels
+int ssd_conv_wgrad_num_configs(void) { return (int)(sizeof(kWgrad) / sizeof(kWgrad[0])); }
+
+static bool wgrad_desc_layer(const ssd_conv_desc* d, int N, Layer* out) {
+    if (!d || d->B < 1 || d->H < 1 || d->W < 1 || d->Cin < 1 || N < 1 || d->kh < 1 || d->kw < 1 || d->stride < 1 ||
+        d->dilation < 1 || d->pad_t < 0 || d->pad_l < 0 || d->pad_b < 0 || d->pad_r < 0)
+        return false;
+    Layer l;
+    l.kind = LK_CONV;
+    l.H = d->H; l.W = d->W; l.Cin = d->Cin; l.Cout = N;
+    l.kh = d->kh; l.kw = d->kw; l.stride = d->stride; l.dil = d->dilation;
+    l.pt = d->pad_t; l.pb = d->pad_b; l.pl = d->pad_l; l.pr = d->pad_r;
+    l.Ho = ssd_conv_out_size(d->H, d->kh, d->stride, d->dilation, d->pad_t, d->pad_b);
+    l.Wo = ssd_conv_out_size(d->W, d->kw, d->stride, d->dilation, d->pad_l, d->pad_r);
+    if (l.Ho < 1 || l.Wo < 1) return false;
+    *out = l;
+    return true;
+}
+
+size_t ssd_conv_wgrad_workspace_floats(const ssd_conv_desc* d, int N) {
+    Layer l;
+    if (!wgrad_desc_layer(d, N, &l)) return 0;
+    size_t need = 0;
+    for (const auto& c : kWgrad) {           // the chunk count follows the tile count: the largest over the table
+        long rpc = 0;
+        const size_t f = (size_t)wgrad_chunks(l, d->B, N, &c, &rpc, nullptr) * l.kh * l.kw * l.Cin * N;
+        need = f > need ? f : need;
+    }
+    return need;
+}
+
+int ssd_conv2d_wgrad_ex(const ssd_conv_desc* d, const float* x_dev, const float* g_dev, int ldg, int N, int config,
+                        float* dW_dev, float* workspace_dev, size_t workspace_floats, void* stream) {
+    Layer l;
+    SSD_CHECK_ARG(wgrad_desc_layer(d, N, &l), "ssd_conv2d_wgrad_ex: bad geometry");
+    SSD_CHECK_ARG(x_dev && g_dev && dW_dev && workspace_dev, "ssd_conv2d_wgrad_ex: NULL argument");
+    SSD_CHECK_ARG(ldg >= N, "ssd_conv2d_wgrad_ex: ldg %d is below N %d", ldg, N);
+    SSD_CHECK_ARG(config >= -1 && config < ssd_conv_wgrad_num_configs(), "ssd_conv2d_wgrad_ex: config %d is outside -1..%d",
+                  config, ssd_conv_wgrad_num_configs() - 1);
+    const WgradCfg* cfg = config < 0 ? wgrad_heuristic(l, N) : &kWgrad[config];
+    return wgrad_with(l, d->B, x_dev, g_dev, ldg, N, dW_dev, (hipStream_t)stream, cfg, false, workspace_dev,
+                      workspace_floats);
+}
+
+int ssd_dwconv3x3_backward(const float* x_dev, const float* g_dev, const float* w_dev, int B, int H, int W, int C, int stride,
+                           int pad_t, int pad_l, int accumulate, float* dx_dev, float* dw_dev, float* workspace_dev,
+                           size_t workspace_floats, void* stream) {
+    SSD_CHECK_ARG(x_dev && g_dev && w_dev && dx_dev && dw_dev && workspace_dev, "ssd_dwconv3x3_backward: NULL argument");
+    SSD_CHECK_ARG(B >= 1 && H >= 1 && W >= 1 && C >= 4 && C % 4 == 0, "ssd_dwconv3x3_backward: bad shape (C = %d must be a multiple of 4)", C);
+    SSD_CHECK_ARG((stride == 1 || stride == 2) && (pad_t == 0 || pad_t == 1) && (pad_l == 0 || pad_l == 1),
+                  "ssd_dwconv3x3_backward: stride %d / pads (%d, %d) unsupported", stride, pad_t, pad_l);
+    SSD_CHECK_ARG(((((uintptr_t)x_dev | (uintptr_t)g_dev | (uintptr_t)w_dev | (uintptr_t)dx_dev) & 15) == 0),
+                  "ssd_dwconv3x3_backward: tensors must be 16-byte aligned");
+    DwBwdParams dp{};
+    dp.x = x_dev; dp.g = g_dev; dp.w = w_dev; dp.dx = dx_dev;
+    dp.B = B; dp.H = H; dp.W = W; dp.C = C;
+    dp.Ho = ssd_conv_out_size(H, 3, stride, 1, pad_t, 1);
+    dp.Wo = ssd_conv_out_size(W, 3, stride, 1, pad_l, 1);
+    SSD_CHECK_ARG(dp.Ho >= 1 && dp.Wo >= 1, "ssd_dwconv3x3_backward: empty output");
+    dp.stride = stride; dp.pad_t = pad_t; dp.pad_l = pad_l;
+    dp.M = (long)B * dp.Ho * dp.Wo;
+    dp.accumulate = accumulate ? 1 : 0;
+    const long chunks = dw_bwd_chunks(dp);
+    SSD_CHECK_ARG((size_t)chunks * 9 * C <= workspace_floats, "ssd_dwconv3x3_backward: the workspace holds %zu floats, %zu are needed",
+                  workspace_floats, (size_t)chunks * 9 * C);
+    dp.partial = workspace_dev;
+    return dw_bwd_launch(dp, chunks, dw_dev, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -169,6 +169,11 @@ _SIGNATURES = {
     "ssd_net_train_steps": (ctypes.c_long, [vp]),
     "ssd_net_train_matrix_flops": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_double)]),
     "ssd_net_train_fetch": (ctypes.c_long, [vp, ctypes.c_char_p, ctypes.c_int, c_float_p, ctypes.c_size_t]),
+    "ssd_conv_wgrad_num_configs": (ctypes.c_int, []),
+    "ssd_conv_wgrad_workspace_floats": (ctypes.c_size_t, [ctypes.POINTER(ConvDesc), ctypes.c_int]),
+    "ssd_conv2d_wgrad_ex": (ctypes.c_int, [ctypes.POINTER(ConvDesc), vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           vp, vp, ctypes.c_size_t, vp]),
+    "ssd_dwconv3x3_backward": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 8 + [vp, vp, vp, ctypes.c_size_t, vp]),
 }
 
 RESIZE_DESC_DTYPE = np.dtype([("src_offset", "<i8"), ("tmp_offset", "<i8")] + [(n, "<i4") for n in (
