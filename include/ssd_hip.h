@@ -186,6 +186,95 @@ int ssd_resize_lanczos(const unsigned char* src_dev, size_t src_bytes, const int
                        int out_h, int out_w, float* out_dev, unsigned char* out_u8_dev, void* workspace_dev,
                        size_t workspace_bytes, void* stream);
 
+/* ---- JPEG decoding: what PIL.Image.open(...).convert("RGB") does for the reference (utils/data_utils.py:93-108 and the
+ * tfds VOC reader), for baseline files, split in two.  [3P] libjpeg-turbo's arithmetic (the decoder inside Pillow),
+ * restated from its published algorithms; every stage is integer, so the bytes are Pillow's exactly.
+ *
+ * HOST HALF (ssd_jpeg_parse, ssd_jpeg_entropy_decode): marker parsing and Huffman decoding.  Plain C++: no HIP call, no
+ * device needed, no global state, thread-safe (the error text is thread-local); callers may run them on many threads.
+ * No byte outside [data, data + n) is read and none outside [coef_out, coef_out + coef_bytes) is written, whatever the
+ * file holds.
+ *   Supported: SOF0 (baseline, 8-bit), ONE interleaved scan, Huffman tables from any number of DHT segments (codes up to 16
+ *   bits), byte stuffing, DRI / RSTn (the counter wraps past 7), APPn / COM segments (skipped); 1 component (grey) or 3
+ *   components that libjpeg's rules call YCbCr (a JFIF marker; else Adobe transform != 0; else component ids other than
+ *   'R','G','B'); chroma sampled 1x1 with luma 1x1, 2x1 or 2x2 (4:4:4, 4:2:2, 4:2:0); sides 1..16384.
+ *   SSD_E_UNSUPPORTED (with a text): progressive, arithmetic, 12-bit, lossless and extended-sequential files, scans that
+ *   do not hold all components in frame order, any other sampling (4:4:0, 4:1:1, ...), RGB / CMYK / YCCK files, table
+ *   indices above 3, sides above 16384.
+ *   SSD_E_INVALID: a truncated or damaged header, a table a component needs and the file does not define, a code that is
+ *   not in its Huffman table, a coefficient index past 63, a missing or wrong restart marker, data that ends before the
+ *   last MCU, an info that does not describe this stream, a coef_out that is too small.
+ * Coefficient storage of one image: the components' planes one after the other (coef_offset[c], bytes), every plane
+ * padded to whole MCUs: blocks_h[c] x blocks_w[c] blocks in raster order, 64 int16 per block in NATURAL (de-zigzagged)
+ * order, still quantised.  Blocks the stream never reaches stay zero.  quant[c] is component c's quantisation table in the
+ * same natural order.  A one-component file is laid out as 1x1-sampled whatever its frame header says.
+ * coef_out may be pinned memory: the decode then lands in the staging buffer of the upload. */
+struct ssd_jpeg_info {
+    int width, height, components;              /* components: 1 or 3                                         */
+    int h_samp[3], v_samp[3], quant_index[3];   /* per component: sampling factors, the file's table index    */
+    int restart_interval;                       /* MCUs between RSTn markers, 0: none                         */
+    int mcus_x, mcus_y;
+    int blocks_w[3], blocks_h[3];               /* the padded plane of each component, in 8x8 blocks          */
+    int reserved;
+    long long coef_offset[3];                   /* byte offset of each component's plane in the storage       */
+    long long coef_bytes;                       /* bytes of coefficient storage the image needs               */
+    unsigned short quant[3][64];                /* per component, natural order                               */
+};
+int ssd_jpeg_parse(const unsigned char* data, size_t n, struct ssd_jpeg_info* out);
+int ssd_jpeg_entropy_decode(const unsigned char* data, size_t n, const struct ssd_jpeg_info* info, short* coef_out,
+                            size_t coef_bytes);
+
+/* DEVICE HALF (ssd_jpeg_decode): coefficients -> uint8 [H_b,W_b,3] RGB for a ragged batch of B images, one call, two
+ * launches, asynchronous on `stream`; the pixels never exist in host memory.  packed_dev [bytes] holds, per image, its
+ * coefficient storage (kind SSD_JPEG_COEFFICIENTS: the layout above for components / h_samp x v_samp luma sampling, the
+ * sizes derived from H, W and the sampling exactly as ssd_jpeg_parse derives them; quant_offset: 3 x 64 uint16, natural
+ * order, one table per component) or its decoded pixels (kind SSD_JPEG_RAW: uint8 [H,W,3] at coef_offset -- an image
+ * the host had to decode itself, copied through by the same call so a batch may mix both kinds).  The output images are
+ * packed in rgb_dev [rgb_bytes] at out_desc[b].src_offset: a following ssd_preprocess_ragged / ssd_resize_lanczos reads
+ * them in place.  desc_host / desc_dev and out_desc_host / out_desc_dev are the same descriptors in host and device
+ * memory (the host copies are checked and size the grids; the kernels read the device copies).
+ * Workspace: the uint8 component planes between the launches, (blocks of all components) x 64 bytes per coefficient image
+ * at plane_offset; ssd_jpeg_decode_workspace_bytes is the size when they are packed in order, each rounded up to 16.
+ * block_start / item_start: the running sums over the batch of 8x8 blocks (raw images: 0) and of ceil(H*W / 4) -- the
+ * two kernels index ONE space each over the whole batch, so small and large images share a grid.
+ * Arithmetic (int32 throughout):
+ *   IDCT       JDCT_ISLOW: dequantise (coef * quant), column pass then row pass of the 8-point Loeffler-Ligtenberg-
+ *              Moschytz flow graph with 13-bit constants (FIX_0_298631336 = 2446 ... FIX_3_072711026 = 25172), PASS1_BITS =
+ *              2: pass 1 descales by 11 bits, pass 2 by 18, each (v + 2^(n-1)) >> n.
+ *   range      sample = T[(v >> 18 after rounding) & 1023] with libjpeg's post-IDCT table as a function of the masked
+ *              index i: i < 128 -> i + 128, i < 512 -> 255, i < 896 -> 0, else i - 896.  It WRAPS for values far out of
+ *              range (reachable at quality 1 and 100); it is not a clamp.
+ *   upsampling "fancy" triangle filters over the cw x ch = ceil(W*h/hmax) x ceil(H*v/vmax) REAL samples of a chroma plane.
+ *              h2v1: out[2i] = (3 s[i] + s[i-1] + 1) >> 2, out[2i+1] = (3 s[i] + s[i+1] + 2) >> 2, out[0] = s[0],
+ *              out[2cw-1] = s[cw-1].  h2v2: t[i] = 3 near[i] + far[i] with near = row y>>1 and far = the row above (even
+ *              y) or below (odd y), the first and the last REAL row replicated past the edges; out[2i] = (3 t[i] + t[i-1]
+ *              + 8) >> 4, out[2i+1] = (3 t[i] + t[i+1] + 7) >> 4, out[0] = (4 t[0] + 8) >> 4, out[2cw-1] = (4 t[cw-1] + 7)
+ *              >> 4.  cw <= 2: plain replication, as the library chooses.
+ *   colour     R = clamp(Y + ((91881 Cr' + 32768) >> 16)), B = clamp(Y + ((116130 Cb' + 32768) >> 16)),
+ *              G = clamp(Y + ((-22554 Cb' - 46802 Cr' + 32768) >> 16)) with Cb' = Cb - 128, Cr' = Cr - 128; grey: R = G =
+ *              B = Y, as convert("RGB") does.
+ * SSD_E_INVALID, nothing launched: NULL pointers, packed_dev / rgb_dev / workspace_dev not 16-byte aligned, a kind other
+ * than the two, offsets that are negative or no multiple of 16, regions outside their buffer, outputs or planes that
+ * overlap or are out of order, an output descriptor of another size, wrong running sums.  SSD_E_UNSUPPORTED, nothing
+ * launched: a side outside 1..16384, components / sampling other than above, B > 65535, more than 2^31 blocks or
+ * items.  B == 0 is a no-op.  Never launched on coefficients the entropy decoder refused. */
+#define SSD_JPEG_COEFFICIENTS 0
+#define SSD_JPEG_RAW 1
+struct ssd_jpeg_desc {
+    long long coef_offset;  /* byte offset in packed_dev of the coefficient storage (or the raw pixels), a multiple of 16 */
+    long long quant_offset; /* ... of the three quantisation tables, a multiple of 16 (ignored for raw pixels)           */
+    long long plane_offset; /* byte offset in the workspace of the component planes, a multiple of 16 (ignored for raw)  */
+    int kind;               /* SSD_JPEG_COEFFICIENTS or SSD_JPEG_RAW                                                      */
+    int H, W, components;   /* components 1 or 3 (ignored for raw)                                                        */
+    int h_samp, v_samp;     /* luma sampling: 1x1, 2x1 or 2x2 (1x1 for one component)                                     */
+    int block_start, item_start;
+};
+size_t ssd_jpeg_decode_workspace_bytes(const struct ssd_jpeg_desc* desc_host, int B);
+int ssd_jpeg_decode(const unsigned char* packed_dev, size_t bytes, const struct ssd_jpeg_desc* desc_host,
+                    const struct ssd_jpeg_desc* desc_dev, int B, unsigned char* rgb_dev, size_t rgb_bytes,
+                    const struct ssd_image_desc* out_desc_host, const struct ssd_image_desc* out_desc_dev,
+                    void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- augmentation: augmentation.py:4-183 (used at trainer.py:42), the deterministic pieces; the random draws of the
  * reference's tf.random.uniform / sample_distorted_bounding_box calls are INPUTS (host side: tf-ssd_amd/augmentation.py).
  * Images float32 [B,H,W,C] in [0,1] (the reference augments after convert + resize).

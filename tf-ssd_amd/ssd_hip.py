@@ -59,6 +59,17 @@ class ResizeDesc(ctypes.Structure):
         "H", "W", "h_bounds", "h_k", "h_ksize", "v_bounds", "v_k", "v_ksize")]
 
 
+class JpegInfo(ctypes.Structure):
+    """struct ssd_jpeg_info (include/ssd_hip.h): what ``ssd_jpeg_parse`` fills in for one baseline JPEG."""
+    _fields_ = [("width", ctypes.c_int), ("height", ctypes.c_int), ("components", ctypes.c_int),
+                ("h_samp", ctypes.c_int * 3), ("v_samp", ctypes.c_int * 3), ("quant_index", ctypes.c_int * 3),
+                ("restart_interval", ctypes.c_int), ("mcus_x", ctypes.c_int), ("mcus_y", ctypes.c_int),
+                ("blocks_w", ctypes.c_int * 3), ("blocks_h", ctypes.c_int * 3), ("reserved", ctypes.c_int),
+                ("coef_offset", ctypes.c_longlong * 3), ("coef_bytes", ctypes.c_longlong),
+                ("quant", (ctypes.c_ushort * 64) * 3)]
+
+
+JPEG_COEFFICIENTS, JPEG_RAW = 0, 1
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
 MOBILENET_V2, VGG16 = 0, 1
 
@@ -87,6 +98,11 @@ _SIGNATURES = {
     "ssd_resize_lanczos_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "ssd_resize_lanczos": (ctypes.c_int, [vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp] + [ctypes.c_int] * 4 +
                            [vp, vp, vp, ctypes.c_size_t, vp]),
+    "ssd_jpeg_parse": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(JpegInfo)]),
+    "ssd_jpeg_entropy_decode": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(JpegInfo), vp, ctypes.c_size_t]),
+    "ssd_jpeg_decode_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int]),
+    "ssd_jpeg_decode": (ctypes.c_int, [vp, ctypes.c_size_t, vp, vp, ctypes.c_int, vp, ctypes.c_size_t, vp, vp, vp,
+                                        ctypes.c_size_t, vp]),
     "ssd_image_mean": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp, vp, vp]),
     "ssd_augment_geometry": (ctypes.c_int, [vp] + [ctypes.c_int] * 6 + [vp, vp, vp, vp]),
     "ssd_augment_color": (ctypes.c_int, [vp] + [ctypes.c_int] * 3 + [vp, vp, vp, vp]),
@@ -181,6 +197,9 @@ RESIZE_DESC_DTYPE = np.dtype([("src_offset", "<i8"), ("tmp_offset", "<i8")] + [(
 assert RESIZE_DESC_DTYPE.itemsize == ctypes.sizeof(ResizeDesc) == 48
 IMAGE_DESC_DTYPE = np.dtype([("src_offset", "<i8"), ("H", "<i4"), ("W", "<i4")])        # struct ssd_image_desc
 assert IMAGE_DESC_DTYPE.itemsize == 16
+JPEG_DESC_DTYPE = np.dtype([("coef_offset", "<i8"), ("quant_offset", "<i8"), ("plane_offset", "<i8")] + [(n, "<i4") for n in (
+    "kind", "H", "W", "components", "h_samp", "v_samp", "block_start", "item_start")])     # struct ssd_jpeg_desc
+assert JPEG_DESC_DTYPE.itemsize == 56 and ctypes.sizeof(JpegInfo) == 504
 
 _lib = None
 _inited = False

@@ -346,6 +346,248 @@ def preprocess_ragged_batch(images, final_height, final_width, out=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Baseline JPEGs decoded on the GPU behind a host entropy decoder (include/ssd_hip.h, "JPEG decoding"; DESIGN.md
+# section 7).  The host parses the markers and decodes the Huffman stream (``ssd_jpeg_parse`` / ``ssd_jpeg_entropy_decode``:
+# plain C++, the GIL is released around them); dequantisation, inverse DCT, chroma upsampling and colour conversion run on
+# the device (``ssd_jpeg_decode``), Pillow's bytes exactly, and the pixels never exist in host memory.
+
+def jpeg_gpu_enabled():
+    """Whether ``voc_batches`` and the custom-image generators decode baseline JPEGs this way: yes unless
+    ``SSD_JPEG_GPU=0``.  On by default since the measurement (profiles/HISTORY.md): 2.1x the
+    images/s of the Pillow pool at 8 workers, the same bits."""
+    import os
+    return os.environ.get("SSD_JPEG_GPU", "1") != "0"
+
+
+class JpegCoefficients(object):
+    """One baseline JPEG after the host half: ``info`` (``ssd_hip.JpegInfo``) and ``coef`` (int16, the library's
+    coefficient storage), or, while ``coef`` is None, the bytes still to be entropy-decoded (``blob``)."""
+    __slots__ = ("info", "coef", "blob")
+
+    def __init__(self, info, coef=None, blob=None):
+        self.info, self.coef, self.blob = info, coef, blob
+
+
+def _pillow_rgb(blob):
+    """What the loaders did before: ``Image.open(...).convert("RGB")`` (raises what it raised before)."""
+    import io
+    from PIL import Image
+    return np.asarray(Image.open(io.BytesIO(blob)).convert("RGB"), dtype=np.uint8)
+
+
+def _jpeg_parse(blob):
+    """``ssd_hip.JpegInfo`` of a stream the library decodes, else None (unsupported or malformed: Pillow's business)."""
+    import ctypes
+    import ssd_hip as _h
+    info = _h.JpegInfo()
+    rc = _h.lib().ssd_jpeg_parse(blob, len(blob), ctypes.byref(info))
+    return info if rc == 0 else None
+
+
+def _jpeg_entropy_into(blob, info, address, nbytes):
+    import ctypes
+    import ssd_hip as _h
+    return _h.lib().ssd_jpeg_entropy_decode(blob, len(blob), ctypes.byref(info), address, nbytes) == 0
+
+
+def jpeg_host_decode(blob, fallback=_pillow_rgb):
+    """The host half for one file's bytes, for a worker thread: ``JpegCoefficients`` with the coefficients decoded into
+    memory of its own, or -- a stream the library calls unsupported or invalid, or no JPEG at all -- ``fallback(blob)``'s
+    uint8 ``[H,W,3]`` pixels."""
+    blob = bytes(blob)
+    info = _jpeg_parse(blob) if blob[:2] == b"\xff\xd8" else None
+    if info is None:
+        return fallback(blob)
+    coef = np.empty(int(info.coef_bytes) // 2, np.int16)
+    if not _jpeg_entropy_into(blob, info, coef.ctypes.data, coef.nbytes):
+        return fallback(blob)
+    return JpegCoefficients(info, coef)
+
+
+def _jpeg_items(blobs, fallback):
+    """Every entry as ``JpegCoefficients`` (decoded already, or parsed with the entropy decode still to do) or a uint8
+    ``[H,W,3]`` array (raw pixels)."""
+    items = []
+    for x in blobs:
+        if isinstance(x, JpegCoefficients):
+            items.append(x)
+        elif isinstance(x, (bytes, bytearray, memoryview)):
+            x = bytes(x)
+            info = _jpeg_parse(x) if x[:2] == b"\xff\xd8" else None
+            items.append(JpegCoefficients(info, None, x) if info is not None else fallback(x))
+        else:
+            items.append(x)
+    for i, x in enumerate(items):
+        if not isinstance(x, JpegCoefficients):
+            a = np.asarray(x)
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError("raw images must be uint8 [H,W,3], got %s %s" % (a.dtype, tuple(a.shape)))
+            items[i] = a
+    return items
+
+
+def _jpeg_layout(items):
+    """Where one ``ssd_jpeg_decode`` call's input sits in ONE buffer: jpeg descriptors | output descriptors | quantisation
+    tables | per image its coefficients or raw pixels, each part at a multiple of 16 bytes; and where the output images
+    and the component planes go."""
+    import ssd_hip as _h
+    B = len(items)
+    desc = np.zeros(B, _h.JPEG_DESC_DTYPE)
+    out_desc = np.zeros(B, _h.IMAGE_DESC_DTYPE)
+    out_at = (desc.nbytes + 15) & ~15
+    quant_at = (out_at + out_desc.nbytes + 15) & ~15
+    total = quant_at + 384 * B
+    blocks = n_items = rgb_bytes = plane_bytes = 0
+    for b, x in enumerate(items):
+        d = desc[b]
+        d["coef_offset"], d["block_start"], d["item_start"] = total, blocks, n_items
+        if isinstance(x, JpegCoefficients):
+            i = x.info
+            d["kind"], d["H"], d["W"], d["components"] = _h.JPEG_COEFFICIENTS, i.height, i.width, i.components
+            d["h_samp"], d["v_samp"] = i.h_samp[0], i.v_samp[0]
+            d["quant_offset"], d["plane_offset"] = quant_at + 384 * b, plane_bytes
+            total += (int(i.coef_bytes) + 15) & ~15
+            blocks += int(i.coef_bytes) // 128
+            plane_bytes += (int(i.coef_bytes) // 2 + 15) & ~15
+        else:
+            d["kind"], d["H"], d["W"], d["components"], d["h_samp"], d["v_samp"] = _h.JPEG_RAW, x.shape[0], x.shape[1], 3, 1, 1
+            total += (x.size + 15) & ~15
+        out_desc[b]["H"], out_desc[b]["W"], out_desc[b]["src_offset"] = d["H"], d["W"], rgb_bytes
+        rgb_bytes += (int(d["H"]) * int(d["W"]) * 3 + 15) & ~15
+        n_items += (int(d["H"]) * int(d["W"]) + 3) // 4
+    assert plane_bytes == _h.lib().ssd_jpeg_decode_workspace_bytes(desc.ctypes.data, B)
+    return {"desc": desc, "out_desc": out_desc, "out_at": out_at, "total": total, "rgb_bytes": rgb_bytes,
+            "plane_bytes": plane_bytes}
+
+
+def _jpeg_fill(host, items, layout, failed):
+    """Write the batch into ``host``; a stream still to be entropy-decoded is decoded straight into its place (the
+    staging buffer is pinned memory).  Indices of streams the decoder refuses are appended to ``failed``."""
+    desc, out_desc = layout["desc"], layout["out_desc"]
+    host[:desc.nbytes] = desc.view(np.uint8)
+    host[layout["out_at"]:layout["out_at"] + out_desc.nbytes] = out_desc.view(np.uint8)
+    for b, x in enumerate(items):
+        at = int(desc[b]["coef_offset"])
+        if isinstance(x, JpegCoefficients):
+            q = int(desc[b]["quant_offset"])
+            host[q:q + 384] = np.frombuffer(x.info, np.uint8)[120:504]          # struct ssd_jpeg_info.quant
+            n = int(x.info.coef_bytes)
+            if x.coef is not None:
+                host[at:at + n] = x.coef.view(np.uint8)
+            elif not _jpeg_entropy_into(x.blob, x.info, host.ctypes.data + at, n):
+                failed.append(b)
+        else:
+            host[at:at + x.size].reshape(x.shape)[...] = x
+
+
+class JpegBatch(object):
+    """What ``decode_jpeg_batch`` returns: ``images`` (uint8 device views ``[H_b,W_b,3]`` into ``rgb``), ``rgb`` (the
+    packed device buffer), ``desc`` (its ``ssd_image_desc`` layout, host) and ``desc_ptr`` (the same descriptors in
+    device memory, inside ``packed``, which is kept alive here)."""
+    __slots__ = ("images", "rgb", "desc", "desc_ptr", "packed", "kinds")
+
+    def __init__(self, images, rgb, desc, desc_ptr, packed, kinds):
+        self.images, self.rgb, self.desc, self.desc_ptr, self.packed, self.kinds = images, rgb, desc, desc_ptr, packed, kinds
+
+
+def decode_jpeg_batch(blobs, out_u8=False, fallback=_pillow_rgb):
+    """A list of JPEG files' ``bytes`` -> their pixels on the GPU, bitwise ``PIL.Image.open(...).convert("RGB")``'s, as a
+    ``JpegBatch``.  Per batch: parse, lay out, entropy-decode straight into the pinned staging buffer, ONE upload, ONE
+    ``ssd_jpeg_decode`` call (two launches).  A stream the library calls unsupported (progressive, CMYK, ...) or
+    malformed is decoded by ``fallback`` -- Pillow, exactly as before, raising what it raised before -- and travels as raw
+    pixels in the same upload; entries may also be ``JpegCoefficients`` from ``jpeg_host_decode`` (the data pool's
+    threads) or uint8 ``[H,W,3]`` arrays.  ``out_u8``: a contiguous 1-D uint8 device tensor, 16-byte aligned and large
+    enough (``sum(round16(H*W*3))``), to decode into instead of a fresh buffer; nothing outside the images is written."""
+    import torch
+    import ssd_hip as _h
+    dev = _h.device()
+    items = _jpeg_items(blobs, fallback)
+    B = len(items)
+    if B == 0:
+        _h.check(_h.lib().ssd_jpeg_decode(None, 0, None, None, 0, None, 0, None, None, None, 0, _h.stream()), "decode_jpeg_batch")
+        return JpegBatch([], torch.empty(0, dtype=torch.uint8, device=dev), np.zeros(0, _h.IMAGE_DESC_DTYPE), 0, None, [])
+    while True:
+        layout = _jpeg_layout(items)
+        failed = []
+        packed = _upload_packed(dev, layout["total"], lambda host: _jpeg_fill(host, items, layout, failed))
+        if not failed:
+            break
+        for b in failed:                                                          # malformed past the header: Pillow's business
+            items[b] = np.asarray(fallback(items[b].blob))
+    if out_u8 is None or out_u8 is False:
+        rgb = torch.empty(max(layout["rgb_bytes"], 16), dtype=torch.uint8, device=dev)
+    else:
+        rgb = out_u8
+        if (not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8 or rgb.device != dev or rgb.dim() != 1
+                or not rgb.is_contiguous() or rgb.numel() < layout["rgb_bytes"] or rgb.data_ptr() % 16):
+            raise ValueError("out_u8 must be a contiguous 1-D uint8 device tensor of at least %d bytes, 16-byte aligned"
+                             % layout["rgb_bytes"])
+    ws = _h.workspace(max(layout["plane_bytes"], 16))
+    desc, out_desc, base = layout["desc"], layout["out_desc"], packed.data_ptr()
+    _h.check(_h.lib().ssd_jpeg_decode(base, layout["total"], desc.ctypes.data, base, B, _h.ptr(rgb), rgb.numel(),
+                                      out_desc.ctypes.data, base + layout["out_at"], _h.ptr(ws), ws.numel(), _h.stream()),
+             "decode_jpeg_batch")
+    images = [rgb[int(o["src_offset"]):int(o["src_offset"]) + int(o["H"]) * int(o["W"]) * 3].view(int(o["H"]), int(o["W"]), 3)
+              for o in out_desc]
+    return JpegBatch(images, rgb, out_desc, base + layout["out_at"], packed, [int(k) for k in desc["kind"]])
+
+
+def _check_out(out, shape, dtype, dev, name="out"):
+    if out is not None and (tuple(out.shape) != shape or out.dtype != dtype or out.device != dev or not out.is_contiguous()):
+        raise ValueError("%s must be a contiguous %s device tensor %s" % (name, dtype, shape))
+
+
+def preprocess_jpeg_batch(blobs, final_height, final_width, out=None, fallback=_pillow_rgb):
+    """``preprocess_ragged_batch`` of the decoded files without the pixels ever being on the host: ``decode_jpeg_batch``,
+    then ``ssd_preprocess_ragged`` on the device-resident images.  Bitwise ``preprocess_ragged_batch([Pillow's decode of
+    each], ...)``."""
+    import torch
+    import ssd_hip as _h
+    fh, fw = int(final_height), int(final_width)
+    dev = _h.device()
+    B = len(blobs)
+    _check_out(out, (B, fh, fw, 3), torch.float32, dev)
+    if out is None:
+        out = torch.empty((B, fh, fw, 3), dtype=torch.float32, device=dev)
+    jb = decode_jpeg_batch(blobs, fallback=fallback)
+    _h.check(_h.lib().ssd_preprocess_ragged(_h.ptr(jb.rgb), jb.rgb.numel(), jb.desc.ctypes.data, jb.desc_ptr, B, 3, fh, fw,
+                                            _h.ptr(out), _h.stream()), "preprocess_jpeg_batch")
+    return out
+
+
+def resize_lanczos_jpeg_batch(blobs, final_height, final_width, out=None, out_u8=None, fallback=_pillow_rgb):
+    """``resize_lanczos_batch`` of the decoded files: ``decode_jpeg_batch``, then ``ssd_resize_lanczos`` on the
+    device-resident images (a second, small upload carries the coefficient tables).  Bitwise ``resize_lanczos_batch([Pillow's
+    decode of each], ...)``."""
+    import torch
+    import ssd_hip as _h
+    fh, fw = int(final_height), int(final_width)
+    dev = _h.device()
+    B = len(blobs)
+    _check_out(out, (B, fh, fw, 3), torch.float32, dev)
+    _check_out(out_u8, (B, fh, fw, 3), torch.uint8, dev, "out_u8")
+    if out is None:
+        out = torch.empty((B, fh, fw, 3), dtype=torch.float32, device=dev)
+    lib = _h.lib()
+    if B == 0 or not (1 <= fh <= 16384 and 1 <= fw <= 16384):
+        _h.check(lib.ssd_resize_lanczos(None, 0, None, 0, None, None, B, 3, fh, fw, _h.ptr(out), _h.ptr(out_u8), None, 0,
+                                        _h.stream()), "resize_lanczos_jpeg_batch")
+        return out
+    jb = decode_jpeg_batch(blobs, fallback=fallback)
+    shapes = [np.broadcast_to(np.uint8(0), (int(o["H"]), int(o["W"]), 3)) for o in jb.desc]    # sizes only: no pixels
+    layout = _lanczos_layout(shapes, fh, fw)
+    layout["desc"]["src_offset"] = jb.desc["src_offset"]
+    layout["total"] = layout["src_at"]                                             # descriptors and tables only
+    packed = _upload_packed(dev, layout["total"], lambda host: _lanczos_fill(host, [], layout))
+    ws = _h.workspace(max(layout["tmp_bytes"], 16))
+    base = packed.data_ptr()
+    _h.check(lib.ssd_resize_lanczos(_h.ptr(jb.rgb), jb.rgb.numel(), base + layout["tables_at"], layout["n_ints"],
+                                    layout["desc"].ctypes.data, base, B, 3, fh, fw, _h.ptr(out), _h.ptr(out_u8), _h.ptr(ws),
+                                    ws.numel(), _h.stream()), "resize_lanczos_jpeg_batch")
+    return out
+
+
 def data_workers(workers=None):
     """Size of the decoding pool: ``workers``, else ``SSD_DATA_WORKERS``, else 8; always within 1..16 (never the
     machine's CPU count: the pool shares the host with the training loop and with other jobs)."""
@@ -379,7 +621,8 @@ class voc_batches(object):
     def _decode_jobs(self):
         """``(callable, argument)`` per item, in order: calling it gives the decoded tfds-shaped dict."""
         if hasattr(self.dataset, "iter_records"):
-            return ((self.dataset.load, r) for r in self.dataset.iter_records())
+            load = self._load_encoded if jpeg_gpu_enabled() and hasattr(self.dataset, "load_encoded") else self.dataset.load
+            return ((load, r) for r in self.dataset.iter_records())
         return ((_identity, item) for item in self.dataset)
 
     def __iter__(self):
@@ -404,8 +647,19 @@ class voc_batches(object):
         finally:
             pool.shutdown(wait=True, cancel_futures=True)
 
+    def _load_encoded(self, record):
+        """The pool's job unless ``SSD_JPEG_GPU=0``: read the file, parse it, entropy-decode it (no pixels yet)."""
+        item = self.dataset.load_encoded(record)
+        if "image" not in item:
+            item["image"] = jpeg_host_decode(item.pop("image_bytes"))
+        return item
+
     def _batch(self, items):
-        imgs = preprocess_ragged_batch([it["image"] for it in items], self.size[0], self.size[1])
+        images = [it["image"] for it in items]
+        if any(isinstance(im, JpegCoefficients) for im in images):
+            imgs = preprocess_jpeg_batch(images, self.size[0], self.size[1])
+        else:
+            imgs = preprocess_ragged_batch(images, self.size[0], self.size[1])
         gt_boxes, gt_labels = _pad_ground_truth([_ground_truth(it, self.evaluate) for it in items], get_padding_values())
         if self.augmentation_fn:
             imgs, gt_boxes = self.augmentation_fn(imgs, gt_boxes, gt_labels)
@@ -436,6 +690,16 @@ def _decode_custom_image(img_path):
     return np.asarray(Image.open(img_path).convert("RGB"), dtype=np.uint8)
 
 
+def _encoded_custom_image(img_path):
+    """Unless ``SSD_JPEG_GPU=0``: a JPEG file's bytes (decoded on the GPU); ``*.npy`` and every other format as before."""
+    if not img_path.endswith(".npy"):
+        with open(img_path, "rb") as f:
+            blob = f.read()
+        if blob[:2] == b"\xff\xd8":
+            return blob
+    return _decode_custom_image(img_path)
+
+
 def custom_data_generator(img_paths, final_height, final_width):
     """reference utils/data_utils.py:93-108: every image opened with PIL, resized with LANCZOS, then uint8 -> float32
     [0,1] (``tf.image.convert_image_dtype``).  PIL only decodes here: the resize (Pillow's, bit for bit) and the
@@ -443,7 +707,10 @@ def custom_data_generator(img_paths, final_height, final_width):
     are accepted as well.  Yields ``(img [final_height, final_width, 3] device tensor, gt_boxes [0,4], gt_labels [0])``;
     ``custom_data_batches`` resizes a whole batch per call."""
     for img_path in img_paths:
-        img = resize_lanczos_batch([_decode_custom_image(img_path)], final_height, final_width)[0]
+        if jpeg_gpu_enabled():
+            img = resize_lanczos_jpeg_batch([_encoded_custom_image(img_path)], final_height, final_width)[0]
+        else:
+            img = resize_lanczos_batch([_decode_custom_image(img_path)], final_height, final_width)[0]
         yield img, np.zeros((0, 4), np.float32), np.zeros((0,), np.int32)
 
 
@@ -454,8 +721,12 @@ def custom_data_batches(img_paths, final_height, final_width, batch_size):
     pv = get_padding_values()
     img_paths = list(img_paths)
     for i in range(0, len(img_paths), int(batch_size)):
-        arrays = [_decode_custom_image(p) for p in img_paths[i:i + int(batch_size)]]
-        imgs = resize_lanczos_batch(arrays, final_height, final_width)
+        if jpeg_gpu_enabled():
+            arrays = [_encoded_custom_image(p) for p in img_paths[i:i + int(batch_size)]]
+            imgs = resize_lanczos_jpeg_batch(arrays, final_height, final_width)
+        else:
+            arrays = [_decode_custom_image(p) for p in img_paths[i:i + int(batch_size)]]
+            imgs = resize_lanczos_batch(arrays, final_height, final_width)
         yield imgs, np.full((len(arrays), 1, 4), pv[1], np.float32), np.full((len(arrays), 1), pv[2], np.int32)
 
 

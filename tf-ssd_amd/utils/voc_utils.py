@@ -185,6 +185,19 @@ class VocDataset(object):
                 "objects": {"bbox": record["bbox"], "label": record["label"], "is_difficult": record["is_difficult"],
                             "is_truncated": record["is_truncated"]}}
 
+    @staticmethod
+    def load_encoded(record):
+        """``load`` without the decode: ``"image_bytes"`` (the file as it is on disk) takes the place of ``"image"`` when
+        the file is a JPEG stream; any other file is decoded here as ``load`` does.  ``data_utils.voc_batches`` hands the
+        bytes to the GPU decoder (unless ``SSD_JPEG_GPU=0``)."""
+        with open(record["image_path"], "rb") as f:
+            blob = f.read()
+        if blob[:2] != b"\xff\xd8":
+            return VocDataset.load(record)
+        return {"image_bytes": blob, "image/filename": record["filename"],
+                "objects": {"bbox": record["bbox"], "label": record["label"], "is_difficult": record["is_difficult"],
+                            "is_truncated": record["is_truncated"]}}
+
     def __iter__(self):
         for r in self.iter_records():
             yield self.load(r)
