@@ -275,6 +275,77 @@ int ssd_jpeg_decode(const unsigned char* packed_dev, size_t bytes, const struct 
                     const struct ssd_image_desc* out_desc_host, const struct ssd_image_desc* out_desc_dev,
                     void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- JPEG encoding: PIL.Image.fromarray(a).save(f, "JPEG", quality=q, subsampling=s) for uint8 [H,W,3] RGB, the mirror
+ * image of the decoder above, split at the same place.  [3P] libjpeg-turbo's baseline encoder (the one inside Pillow),
+ * restated from its published algorithms; every stage is integer, so the bytes are Pillow's exactly.
+ *
+ * DEVICE HALF (ssd_jpeg_forward): uint8 [H_b,W_b,3] RGB -> quantised int16 coefficients for a ragged batch of B images, one
+ * call, two launches, asynchronous on `stream`.  Image b is read at src_offset of rgb_dev [rgb_bytes] (any alignment: the
+ * [B,H,W,3] tensor ssd_draw_detections writes is the case src_offset = b*H*W*3) and written at coef_offset of coef_dev
+ * [coef_bytes] in exactly the coefficient storage of struct ssd_jpeg_info for 3 components with h_samp x v_samp luma
+ * sampling (every block of the padded planes is written; only the REAL blocks, ceil(cw/8) x ceil(ch/8) of a component of
+ * cw x ch real samples, are specified, and the host half reads no other).  quant_offset: 2 x 64 uint16 in tables_dev
+ * [tables_bytes], natural order, luma then the table Cb and Cr share.  desc_host / desc_dev are the same descriptors in
+ * host and device memory (the host copy is checked and sizes the grids; the kernels read the device copy).
+ * Workspace: the uint8 component planes between the launches, (blocks of all components) x 64 bytes per image at
+ * plane_offset; ssd_jpeg_forward_workspace_bytes is the size when they are packed in order, each rounded up to 16.
+ * block_start / item_start: the running sums over the batch of 8x8 blocks and of 16 x mcus_x x mcus_y (an item is four
+ * chroma samples) -- the two kernels index ONE space each over the whole batch, so small and large images share a grid.
+ * Arithmetic (int32 throughout), with FIX(x) = int(x * 65536 + 0.5):
+ *   colour     Y = (FIX(.299) R + FIX(.587) G + FIX(.114) B + 32768) >> 16,
+ *              Cb = (-FIX(.16874) R - FIX(.33126) G + FIX(.5) B + (128 << 16) + 32767) >> 16,
+ *              Cr = (FIX(.5) R - FIX(.41869) G - FIX(.08131) B + (128 << 16) + 32767) >> 16.
+ *   edges      the last real column is replicated out to the MCU width BEFORE downsampling.  The last real row is
+ *              replicated only up to a whole row group (a multiple of v_samp); after downsampling the last DOWNSAMPLED row
+ *              is replicated to the MCU height (padding the input rows to the MCU height first gives other chroma whenever
+ *              H is not a multiple of 8 v_samp).
+ *   downsample h2v1: (a + b + bias) >> 1, bias 0, 1, 0, 1, ... by output column; h2v2: (a + b + c + d + bias) >> 2, bias
+ *              1, 2, 1, 2, ...
+ *   FDCT       samples - 128; JDCT_ISLOW forward: row pass then column pass of the 8-point Loeffler-Ligtenberg-Moschytz
+ *              flow graph with the decoder's 13-bit constants, PASS1_BITS = 2: rows, DC terms << 2, the others descaled by
+ *              11 bits; columns, DC terms (v + 2) >> 2, the others descaled by 15; each descale (v + 2^(n-1)) >> n.
+ *   quantise   sign(d) * ((|d| + 4 q) / (8 q)), a true integer division.
+ * SSD_E_INVALID, nothing launched: NULL pointers, tables_dev / coef_dev / workspace_dev not 16-byte aligned, offsets that
+ * are negative or (coef, quant, plane) no multiple of 16, regions outside their buffer, coefficients or planes that
+ * overlap or are out of order, wrong running sums.  SSD_E_UNSUPPORTED, nothing launched: a side outside 1..16384, a
+ * sampling other than 1x1, 2x1, 2x2, B > 65535, more than 2^31 blocks or items.  B == 0 is a no-op. */
+struct ssd_jpeg_enc_desc {
+    long long src_offset;   /* byte offset of the image's pixels in rgb_dev                                              */
+    long long coef_offset;  /* byte offset in coef_dev of its coefficient storage, a multiple of 16                      */
+    long long quant_offset; /* byte offset in tables_dev of its two quantisation tables, a multiple of 16                */
+    long long plane_offset; /* byte offset in the workspace of its component planes, a multiple of 16                    */
+    int H, W;
+    int h_samp, v_samp;     /* luma sampling: 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0)                                    */
+    int block_start, item_start;
+};
+size_t ssd_jpeg_forward_workspace_bytes(const struct ssd_jpeg_enc_desc* desc_host, int B);
+int ssd_jpeg_forward(const unsigned char* rgb_dev, size_t rgb_bytes, const unsigned char* tables_dev, size_t tables_bytes,
+                     const struct ssd_jpeg_enc_desc* desc_host, const struct ssd_jpeg_enc_desc* desc_dev, int B,
+                     short* coef_dev, size_t coef_bytes, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* HOST HALF: the header and the Huffman coding.  Plain C++ under the rules of the decoder's host half: no HIP call, no
+ * device needed, no global state, thread-safe (the error text is thread-local).
+ * ssd_jpeg_quality_tables: jpeg_set_quality(quality, force_baseline) -- quality clamped to 1..100, scale = 5000 / q below
+ *   50, else 200 - 2 q, every entry clamp((base * scale + 50) / 100, 1, 255) on the Annex K tables; out: 2 x 64 uint16,
+ *   natural order, luma then chroma.
+ * ssd_jpeg_encode_info: the ssd_jpeg_info of a width x height image with h_samp x v_samp luma sampling and these two
+ *   tables -- what ssd_jpeg_parse returns for the stream ssd_jpeg_entropy_encode then writes.  SSD_E_UNSUPPORTED: a side
+ *   outside 1..16384, another sampling; SSD_E_INVALID: a table entry outside 1..255.
+ * ssd_jpeg_encode_bound: the size no stream of this info exceeds (0: an inconsistent info).
+ * ssd_jpeg_entropy_encode: coef (the coefficient storage; only real blocks are read) -> the whole stream in out: SOI, the
+ *   18-byte JFIF 1.01 APP0 (units 0, density 1:1), two DQT segments (zigzag order), SOF0 (component ids 1, 2, 3, tables 0,
+ *   1, 1), four DHT segments (DC0, AC0, DC1, AC1: the Annex K tables), one interleaved SOS without restart markers, the
+ *   entropy-coded data (0xFF stuffed, the last byte padded with 1-bits), EOI; *written = its size.  An MCU block beyond a
+ *   component's real blocks is synthesised: all AC zero, the DC of the block emitted just before it in the same MCU.
+ *   Nothing outside [out, out + out_bytes) is written.  SSD_E_INVALID: an info that is not what ssd_jpeg_encode_info fills
+ *   in, an out that is too small for the stream (any size that holds it is enough), a DC difference beyond category 11
+ *   or an AC coefficient beyond category 10 (outside baseline range). */
+int ssd_jpeg_quality_tables(int quality, unsigned short* out);
+int ssd_jpeg_encode_info(int width, int height, int h_samp, int v_samp, const unsigned short* tables, struct ssd_jpeg_info* out);
+size_t ssd_jpeg_encode_bound(const struct ssd_jpeg_info* info);
+int ssd_jpeg_entropy_encode(const short* coef, const struct ssd_jpeg_info* info, unsigned char* out, size_t out_bytes,
+                            size_t* written);
+
 /* ---- augmentation: augmentation.py:4-183 (used at trainer.py:42), the deterministic pieces; the random draws of the
  * reference's tf.random.uniform / sample_distorted_bounding_box calls are INPUTS (host side: tf-ssd_amd/augmentation.py).
  * Images float32 [B,H,W,C] in [0,1] (the reference augments after convert + resize).

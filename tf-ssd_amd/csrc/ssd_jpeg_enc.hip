@@ -1,0 +1,522 @@
+// Baseline JPEG encoding, the mirror image of ssd_jpeg.hip, split at the same place ("JPEG encoding"):
+//   device ssd_jpeg_forward: RGB -> YCbCr + chroma downsampling (kernel 1, uint8 component planes in the workspace), then
+//          8x8 forward DCT + quantisation (kernel 2, int16 coefficients in the storage layout of struct ssd_jpeg_info).
+//          Integer arithmetic with one defined answer: [3P] libjpeg-turbo's 16-bit fixed-point colour conversion, its
+//          h2v1 / h2v2 box downsampling with alternating bias, the JDCT_ISLOW forward DCT and the baseline quantiser,
+//          restated from the published algorithms (include/ssd_hip.h spells the arithmetic out).
+//   host   ssd_jpeg_quality_tables / ssd_jpeg_encode_info / ssd_jpeg_encode_bound / ssd_jpeg_entropy_encode: the header and
+//          Huffman coding -- serial, bit-granular.  Plain C++: no HIP call, no global state, thread-safe (the data pool's
+//          threads call them in parallel).
+#include <cstring>
+
+#include "common.h"
+
+namespace ssd {
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host: tables of ITU-T T.81 Annex K
+
+static const unsigned char kEncZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+static const int kEncMaxSide = 16384;
+
+static const unsigned char kStdQuant[2][64] = {
+    {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99},
+    {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
+
+struct std_huff {
+    unsigned char cls_id;       // the DHT segment's Tc << 4 | Th
+    unsigned char bits[16];
+    int count;
+    unsigned char vals[162];
+};
+// in stream order: DC0, AC0, DC1, AC1
+static const std_huff kStdHuff[4] = {
+    {0x00, {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, 12, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}},
+    {0x10, {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d}, 162,
+     {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
+      0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
+      0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
+      0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75,
+      0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
+      0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+      0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
+      0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa}},
+    {0x01, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}, 12, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}},
+    {0x11, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}, 162,
+     {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
+      0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25,
+      0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47,
+      0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74,
+      0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
+      0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
+      0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4,
+      0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa}}};
+
+// SOI + APP0 + 2 DQT + SOF0 + 4 DHT + SOS
+static const size_t kEncHeaderBytes = 2 + 18 + 2 * 69 + 19 + 2 * (21 + 12) + 2 * (21 + 162) + 14;
+// the longest block: an 11-bit DC code + 11 bits, 63 x (a 16-bit AC code + 10 bits) = 1660 bits, every byte stuffed
+static const size_t kEncBlockBytes = 2 * ((22 + 63 * 26 + 7) / 8);
+
+struct enc_huff {
+    unsigned short code[256];
+    unsigned char len[256];     // 0: the symbol has no code
+};
+
+static void enc_build_huff(enc_huff& t, const std_huff& s) {
+    memset(&t, 0, sizeof(t));
+    unsigned code = 0;
+    int k = 0;
+    for (int len = 1; len <= 16; ++len) {
+        for (int i = 0; i < s.bits[len - 1]; ++i, ++k, ++code) {
+            t.code[s.vals[k]] = (unsigned short)code;
+            t.len[s.vals[k]] = (unsigned char)len;
+        }
+        code <<= 1;
+    }
+}
+
+// what an H x W image with h x v luma sampling looks like as a struct ssd_jpeg_info (ssd_jpeg_parse derives the same)
+static int enc_fill_info(const int width, const int height, const int hs, const int vs, ssd_jpeg_info& o) {
+    memset(&o, 0, sizeof(o));
+    SSD_UNSUPPORTED_IF(width < 1 || width > kEncMaxSide || height < 1 || height > kEncMaxSide, "ssd_jpeg_encode: %d x %d, outside 1..%d",
+                       height, width, kEncMaxSide);
+    SSD_UNSUPPORTED_IF(!((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2)),
+                       "ssd_jpeg_encode: luma sampling %dx%d (1x1, 2x1 and 2x2 only)", hs, vs);
+    o.width = width; o.height = height; o.components = 3;
+    o.mcus_x = (width + 8 * hs - 1) / (8 * hs);
+    o.mcus_y = (height + 8 * vs - 1) / (8 * vs);
+    long long bytes = 0;
+    for (int c = 0; c < 3; ++c) {
+        o.h_samp[c] = c ? 1 : hs; o.v_samp[c] = c ? 1 : vs; o.quant_index[c] = c ? 1 : 0;
+        o.blocks_w[c] = o.mcus_x * o.h_samp[c];
+        o.blocks_h[c] = o.mcus_y * o.v_samp[c];
+        o.coef_offset[c] = bytes;
+        bytes += (long long)o.blocks_w[c] * o.blocks_h[c] * 128;
+    }
+    o.coef_bytes = bytes;
+    return SSD_OK;
+}
+
+// `info` is what enc_fill_info makes of its own size and sampling, with baseline tables (1..255, chroma shared)
+static int enc_check_info(const ssd_jpeg_info* info) {
+    SSD_CHECK_ARG(info, "ssd_jpeg_encode: NULL pointer");
+    ssd_jpeg_info want;
+    const int rc = enc_fill_info(info->width, info->height, info->h_samp[0], info->v_samp[0], want);
+    if (rc != SSD_OK) return rc == SSD_E_UNSUPPORTED ? SSD_E_INVALID : rc;
+    memcpy(want.quant, info->quant, sizeof(want.quant));
+    SSD_CHECK_ARG(memcmp(&want, info, sizeof(want)) == 0, "ssd_jpeg_encode: info is inconsistent (not what ssd_jpeg_encode_info fills in)");
+    SSD_CHECK_ARG(memcmp(info->quant[1], info->quant[2], 128) == 0, "ssd_jpeg_encode: Cb and Cr do not share a quantisation table");
+    for (int c = 0; c < 2; ++c)
+        for (int i = 0; i < 64; ++i)
+            SSD_CHECK_ARG(info->quant[c][i] >= 1 && info->quant[c][i] <= 255, "ssd_jpeg_encode: quantisation value %d outside 1..255",
+                          info->quant[c][i]);
+    return SSD_OK;
+}
+
+// Bytes into [out, out + n): past the end nothing is written, the count goes on (the caller compares it with n).
+struct byte_writer {
+    unsigned char* out;
+    size_t n, at;
+    unsigned long long acc;     // the low `bits` bits are not yet written
+    int bits;
+
+    inline void byte(const unsigned b) {
+        if (at < n) out[at] = (unsigned char)b;
+        ++at;
+    }
+    inline void be16(const unsigned v) { byte(v >> 8); byte(v & 255); }
+    // len <= 16 bits of entropy-coded data, with byte stuffing
+    inline void put(const unsigned code, const int len) {
+        acc = (acc << len) | code;
+        bits += len;
+        while (bits >= 8) {
+            const unsigned b = (unsigned)(acc >> (bits - 8)) & 255;
+            byte(b);
+            if (b == 0xFF) byte(0);
+            bits -= 8;
+        }
+    }
+};
+
+static inline int enc_category(const int v) {
+    const unsigned a = (unsigned)(v < 0 ? -v : v);
+    return a ? 32 - __builtin_clz(a) : 0;
+}
+
+// one block: the DC difference against `pred`, then run-length / category coding of the AC terms in zigzag order
+static int enc_block(byte_writer& w, const enc_huff& dc, const enc_huff& ac, const short* coef, const bool dummy, int& pred) {
+    const int v0 = dummy ? pred : coef[0];
+    const int diff = v0 - pred;
+    pred = v0;
+    int s = enc_category(diff);
+    SSD_CHECK_ARG(s <= 11, "ssd_jpeg_entropy_encode: a DC difference of %d is outside the baseline range", diff);
+    w.put(dc.code[s], dc.len[s]);
+    if (s) w.put((unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << s) - 1), s);
+    if (dummy) {
+        w.put(ac.code[0], ac.len[0]);
+        return SSD_OK;
+    }
+    int run = 0;
+    for (int k = 1; k < 64; ++k) {
+        const int v = coef[kEncZigzag[k]];
+        if (v == 0) { ++run; continue; }
+        for (; run > 15; run -= 16) w.put(ac.code[0xF0], ac.len[0xF0]);
+        s = enc_category(v);
+        SSD_CHECK_ARG(s <= 10, "ssd_jpeg_entropy_encode: an AC coefficient of %d is outside the baseline range", v);
+        const int rs = (run << 4) | s;
+        w.put(ac.code[rs], ac.len[rs]);
+        w.put((unsigned)(v < 0 ? v - 1 : v) & ((1u << s) - 1), s);
+        run = 0;
+    }
+    if (run) w.put(ac.code[0], ac.len[0]);
+    return SSD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// device
+
+// what the kernels derive from a descriptor (the host check derives the same)
+struct enc_geometry {
+    int mcus_x, mcus_y;
+    int n0, n1;                 // blocks of the luma plane / of one chroma plane (padded to whole MCUs)
+    int nblocks, nitems;
+};
+__host__ __device__ __forceinline__ enc_geometry enc_geom(const ssd_jpeg_enc_desc& d) {
+    enc_geometry g;
+    g.mcus_x = (d.W + 8 * d.h_samp - 1) / (8 * d.h_samp);
+    g.mcus_y = (d.H + 8 * d.v_samp - 1) / (8 * d.v_samp);
+    g.n1 = g.mcus_x * g.mcus_y;
+    g.n0 = g.n1 * d.h_samp * d.v_samp;
+    g.nblocks = g.n0 + 2 * g.n1;
+    g.nitems = g.n1 * 16;       // four chroma samples each: 2 per MCU and row, 8 rows
+    return g;
+}
+
+// the image whose [start, next start) holds `index`: the last b with start(b) <= index
+template <typename F>
+__device__ __forceinline__ int enc_find_image(const int B, const int index, F start) {
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (start(mid) <= index) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ void enc_store(unsigned char* p, const unsigned (&w)[1]) { *reinterpret_cast<unsigned*>(p) = w[0]; }
+__device__ __forceinline__ void enc_store(unsigned char* p, const unsigned (&w)[2]) { *reinterpret_cast<uint2*>(p) = make_uint2(w[0], w[1]); }
+
+// One item of kernel 1: four chroma samples of chroma row cy (columns 4 ix ..) and the 4 HS x VS luma samples above them.
+// Edges as the library handles them: the last real column is replicated to the right; the last real row is replicated
+// only up to a whole row group, and below that the last DOWNSAMPLED row is repeated (chroma row ch - 1, luma row H - 1).
+template <int HS, int VS>
+__device__ __forceinline__ void enc_color_item(const unsigned char* __restrict__ src, const ssd_jpeg_enc_desc& d,
+                                               const enc_geometry& g, const int cy, const int ix, unsigned char* __restrict__ py) {
+    constexpr int NX = 4 * HS;
+    const int ch = (d.H + VS - 1) / VS;
+    const bool below = cy > ch - 1;
+    const int cy_eff = below ? ch - 1 : cy;
+    const int x0 = ix * NX;
+    unsigned yw[VS][HS];
+    int cb[NX], cr[NX];
+#pragma unroll
+    for (int j = 0; j < VS; ++j) {
+        const int r = min(VS * cy_eff + j, d.H - 1);
+        const unsigned char* row = src + (long)r * d.W * 3;
+#pragma unroll
+        for (int k = 0; k < HS; ++k) yw[j][k] = 0;
+#pragma unroll
+        for (int k = 0; k < NX; ++k) {
+            const unsigned char* p = row + min(x0 + k, d.W - 1) * 3;
+            const int R = p[0], G = p[1], B = p[2];
+            const int Y = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16;
+            const int Cb = (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16;
+            const int Cr = (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16;
+            yw[j][k >> 2] |= (unsigned)Y << (8 * (k & 3));
+            cb[k] = j ? cb[k] + Cb : Cb;
+            cr[k] = j ? cr[k] + Cr : Cr;
+        }
+    }
+    const int ypitch = g.mcus_x * 8 * HS, cpitch = g.mcus_x * 8;
+#pragma unroll
+    for (int j = 0; j < VS; ++j)
+        enc_store(py + (long)(VS * cy + j) * ypitch + x0, below ? yw[VS - 1] : yw[j]);
+    unsigned wb = 0, wr = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        int b, r;
+        if (HS == 1) { b = cb[i]; r = cr[i]; }
+        else if (VS == 1) { b = (cb[2 * i] + cb[2 * i + 1] + (i & 1)) >> 1; r = (cr[2 * i] + cr[2 * i + 1] + (i & 1)) >> 1; }
+        else { b = (cb[2 * i] + cb[2 * i + 1] + 1 + (i & 1)) >> 2; r = (cr[2 * i] + cr[2 * i + 1] + 1 + (i & 1)) >> 2; }
+        wb |= (unsigned)b << (8 * i);
+        wr |= (unsigned)r << (8 * i);
+    }
+    unsigned char* pcb = py + (long)g.n0 * 64 + (long)cy * cpitch + ix * 4;
+    *reinterpret_cast<unsigned*>(pcb) = wb;
+    *reinterpret_cast<unsigned*>(pcb + (long)g.n1 * 64) = wr;
+}
+
+// Kernel 1: colour conversion + downsampling into the uint8 component planes (Y, Cb, Cr one after the other at
+// desc[b].plane_offset, each padded to whole MCUs).  One index space of items over the whole batch (desc[b].item_start is
+// the prefix); every pixel is read once, every plane byte is written once, with aligned 4- and 8-byte stores.
+__global__ __launch_bounds__(256) void jpeg_enc_color_kernel(const unsigned char* __restrict__ rgb,
+                                                            const ssd_jpeg_enc_desc* __restrict__ desc, const int B,
+                                                            const int total_items, unsigned char* __restrict__ planes) {
+    const int item = blockIdx.x * 256 + threadIdx.x;
+    if (item >= total_items) return;
+    const int b = enc_find_image(B, item, [&](const int i) { return desc[i].item_start; });
+    const ssd_jpeg_enc_desc d = desc[b];
+    const enc_geometry g = enc_geom(d);
+    const int local = item - d.item_start;
+    const int per_row = g.mcus_x * 2;
+    const int cy = local / per_row, ix = local - cy * per_row;
+    const unsigned char* src = rgb + d.src_offset;
+    unsigned char* py = planes + d.plane_offset;
+    if (d.h_samp == 1) enc_color_item<1, 1>(src, d, g, cy, ix, py);
+    else if (d.v_samp == 1) enc_color_item<2, 1>(src, d, g, cy, ix, py);
+    else enc_color_item<2, 2>(src, d, g, cy, ix, py);
+}
+
+// one 8-point pass of the "islow" forward DCT: 13-bit constants, int32.  FIRST (rows): the DC terms are << 2, the others
+// descaled by 11 bits; second (columns): (v + 2) >> 2 and 15 bits; each descale is (v + 2^(n-1)) >> n.
+template <bool FIRST>
+__host__ __device__ __forceinline__ void fdct_islow_1d(const int d[8], int out[8]) {
+    int tmp0 = d[0] + d[7], tmp7 = d[0] - d[7], tmp1 = d[1] + d[6], tmp6 = d[1] - d[6];
+    int tmp2 = d[2] + d[5], tmp5 = d[2] - d[5], tmp3 = d[3] + d[4], tmp4 = d[3] - d[4];
+    const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+    constexpr int n = FIRST ? 11 : 15, half = 1 << (n - 1);
+    if (FIRST) { out[0] = (tmp10 + tmp11) << 2; out[4] = (tmp10 - tmp11) << 2; }
+    else { out[0] = (tmp10 + tmp11 + 2) >> 2; out[4] = (tmp10 - tmp11 + 2) >> 2; }
+    int z1 = (tmp12 + tmp13) * 4433;
+    out[2] = (z1 + tmp13 * 6270 + half) >> n;
+    out[6] = (z1 - tmp12 * 15137 + half) >> n;
+    z1 = tmp4 + tmp7;
+    int z2 = tmp5 + tmp6, z3 = tmp4 + tmp6, z4 = tmp5 + tmp7;
+    const int z5 = (z3 + z4) * 9633;
+    tmp4 *= 2446; tmp5 *= 16819; tmp6 *= 25172; tmp7 *= 12299;
+    z1 *= -7373; z2 *= -20995; z3 = z3 * -16069 + z5; z4 = z4 * -3196 + z5;
+    out[7] = (tmp4 + z1 + z3 + half) >> n;
+    out[5] = (tmp5 + z2 + z4 + half) >> n;
+    out[3] = (tmp6 + z2 + z3 + half) >> n;
+    out[1] = (tmp7 + z1 + z4 + half) >> n;
+}
+
+// Kernel 2: forward DCT + quantisation.  One index space of 8x8 blocks over the whole batch (desc[b].block_start is the
+// prefix; every block of the padded planes, so the storage holds no stale byte), 8 lanes per block, 32 blocks per
+// workgroup.  Lane j loads row j of the block with one aligned 8-byte load and runs the row pass; the 8x8 int32
+// intermediate is transposed through LDS (rows padded to 9 words); lane j runs column j and quantises it with a true
+// integer division; a second transpose gives lane j the eight coefficients of row j: one aligned 16-byte store.
+__global__ __launch_bounds__(256) void jpeg_enc_fdct_kernel(const unsigned char* __restrict__ planes,
+                                                           const unsigned char* __restrict__ tables,
+                                                           const ssd_jpeg_enc_desc* __restrict__ desc, const int B,
+                                                           const int total_blocks, unsigned char* __restrict__ coef) {
+    __shared__ int ws[32][8][9];
+    const int slot = threadIdx.x >> 3, j = threadIdx.x & 7;
+    const int blk = blockIdx.x * 32 + slot;
+    const bool live = blk < total_blocks;
+    ssd_jpeg_enc_desc d;
+    int local = 0, comp = 0;
+    if (live) {
+        const int b = enc_find_image(B, blk, [&](const int i) { return desc[i].block_start; });
+        d = desc[b];
+        local = blk - d.block_start;
+        const enc_geometry g = enc_geom(d);
+        comp = local < g.n0 ? 0 : (local < g.n0 + g.n1 ? 1 : 2);
+        const int inplane = local - (comp == 0 ? 0 : (comp == 1 ? g.n0 : g.n0 + g.n1));
+        const int bw = comp == 0 ? g.mcus_x * d.h_samp : g.mcus_x;
+        const int by = inplane / bw, bx = inplane - by * bw;
+        const long plane_at = d.plane_offset + (comp == 0 ? 0L : (long)g.n0 * 64 + (long)(comp - 1) * g.n1 * 64);
+        const uint2 s = *reinterpret_cast<const uint2*>(planes + plane_at + ((long)(by * 8 + j) * bw + bx) * 8);
+        int in[8], out[8];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            in[c] = (int)((s.x >> (8 * c)) & 255) - 128;
+            in[c + 4] = (int)((s.y >> (8 * c)) & 255) - 128;
+        }
+        fdct_islow_1d<true>(in, out);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) ws[slot][j][c] = out[c];
+    }
+    __syncthreads();
+    int q[8];
+    if (live) {
+        const unsigned short* qt = reinterpret_cast<const unsigned short*>(tables + d.quant_offset) + (comp ? 64 : 0);
+        int in[8], out[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) in[r] = ws[slot][r][j];
+        fdct_islow_1d<false>(in, out);
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int q8 = (int)qt[r * 8 + j] * 8;
+            const int a = (abs(out[r]) + (q8 >> 1)) / q8;
+            q[r] = out[r] < 0 ? -a : a;
+        }
+    }
+    __syncthreads();
+    if (live) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) ws[slot][r][j] = q[r];
+    }
+    __syncthreads();
+    if (live) {
+        unsigned w[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            w[c] = ((unsigned)ws[slot][j][2 * c] & 0xFFFFu) | ((unsigned)ws[slot][j][2 * c + 1] << 16);
+        *reinterpret_cast<uint4*>(coef + d.coef_offset + (long)local * 128 + j * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+}
+
+static inline size_t enc_round16(const size_t v) { return (v + 15) & ~(size_t)15; }
+static inline bool enc_desc_shape_ok(const ssd_jpeg_enc_desc& d) {
+    return d.H >= 1 && d.H <= kEncMaxSide && d.W >= 1 && d.W <= kEncMaxSide;
+}
+static inline bool enc_desc_sampling_ok(const ssd_jpeg_enc_desc& d) {
+    return (d.h_samp == 1 && d.v_samp == 1) || (d.h_samp == 2 && d.v_samp == 1) || (d.h_samp == 2 && d.v_samp == 2);
+}
+
+}  // namespace ssd
+
+using namespace ssd;
+
+extern "C" int ssd_jpeg_quality_tables(int quality, unsigned short* out) {
+    SSD_CHECK_ARG(out, "ssd_jpeg_quality_tables: NULL pointer");
+    const int q = quality < 1 ? 1 : (quality > 100 ? 100 : quality);
+    const int scale = q < 50 ? 5000 / q : 200 - 2 * q;
+    for (int t = 0; t < 2; ++t)
+        for (int i = 0; i < 64; ++i) {
+            const int v = (kStdQuant[t][i] * scale + 50) / 100;
+            out[t * 64 + i] = (unsigned short)(v < 1 ? 1 : (v > 255 ? 255 : v));
+        }
+    return SSD_OK;
+}
+
+extern "C" int ssd_jpeg_encode_info(int width, int height, int h_samp, int v_samp, const unsigned short* tables,
+                                    struct ssd_jpeg_info* out) {
+    SSD_CHECK_ARG(tables && out, "ssd_jpeg_encode_info: NULL pointer");
+    ssd_jpeg_info o;
+    const int rc = enc_fill_info(width, height, h_samp, v_samp, o);
+    if (rc != SSD_OK) return rc;
+    for (int c = 0; c < 3; ++c) memcpy(o.quant[c], tables + (c ? 64 : 0), 128);
+    memcpy(out, &o, sizeof(o));
+    return enc_check_info(out);
+}
+
+extern "C" size_t ssd_jpeg_encode_bound(const struct ssd_jpeg_info* info) {
+    if (enc_check_info(info) != SSD_OK) return 0;
+    const size_t blocks = (size_t)info->mcus_x * info->mcus_y * (size_t)(info->h_samp[0] * info->v_samp[0] + 2);
+    return kEncHeaderBytes + blocks * kEncBlockBytes + 2 + 2;                      // + the padded last byte (stuffed) + EOI
+}
+
+extern "C" int ssd_jpeg_entropy_encode(const short* coef, const struct ssd_jpeg_info* info, unsigned char* out, size_t out_bytes,
+                                       size_t* written) {
+    SSD_CHECK_ARG(coef && out && written, "ssd_jpeg_entropy_encode: NULL pointer");
+    *written = 0;
+    const int rc = enc_check_info(info);
+    if (rc != SSD_OK) return rc;
+    const ssd_jpeg_info& o = *info;
+    SSD_CHECK_ARG(out_bytes >= kEncHeaderBytes + 2, "ssd_jpeg_entropy_encode: out holds %zu bytes, fewer than the header", out_bytes);
+    byte_writer w = {out, out_bytes, 0, 0, 0};
+    w.be16(0xFFD8);
+    static const unsigned char app0[16] = {0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1};
+    for (int i = 0; i < 16; ++i) w.byte(app0[i]);
+    w.be16(0);                                                                     // no thumbnail
+    for (int t = 0; t < 2; ++t) {
+        w.be16(0xFFDB); w.be16(67); w.byte((unsigned)t);
+        for (int i = 0; i < 64; ++i) w.byte(o.quant[t][kEncZigzag[i]]);
+    }
+    w.be16(0xFFC0); w.be16(17); w.byte(8); w.be16((unsigned)o.height); w.be16((unsigned)o.width); w.byte(3);
+    for (int c = 0; c < 3; ++c) { w.byte((unsigned)c + 1); w.byte((unsigned)((o.h_samp[c] << 4) | o.v_samp[c])); w.byte((unsigned)o.quant_index[c]); }
+    enc_huff huff[4];
+    for (int t = 0; t < 4; ++t) {
+        const std_huff& s = kStdHuff[t];
+        w.be16(0xFFC4); w.be16((unsigned)(19 + s.count)); w.byte(s.cls_id);
+        for (int i = 0; i < 16; ++i) w.byte(s.bits[i]);
+        for (int i = 0; i < s.count; ++i) w.byte(s.vals[i]);
+        enc_build_huff(huff[t], s);
+    }
+    static const unsigned char sos[14] = {0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0};
+    for (int i = 0; i < 14; ++i) w.byte(sos[i]);
+    // the real blocks of each component: what the frame header's size gives; the rest of an MCU is synthesised
+    int real_w[3], real_h[3];
+    for (int c = 0; c < 3; ++c) {
+        real_w[c] = ((o.width * o.h_samp[c] + o.h_samp[0] - 1) / o.h_samp[0] + 7) / 8;
+        real_h[c] = ((o.height * o.v_samp[c] + o.v_samp[0] - 1) / o.v_samp[0] + 7) / 8;
+    }
+    int pred[3] = {0, 0, 0};
+    for (int my = 0; my < o.mcus_y; ++my)
+        for (int mx = 0; mx < o.mcus_x; ++mx) {
+            if (w.at > w.n) break;                                                 // already too small: stop early
+            for (int c = 0; c < 3; ++c)
+                for (int v = 0; v < o.v_samp[c]; ++v)
+                    for (int u = 0; u < o.h_samp[c]; ++u) {
+                        const int by = my * o.v_samp[c] + v, bx = mx * o.h_samp[c] + u;
+                        const bool dummy = by >= real_h[c] || bx >= real_w[c];     // AC zero, the DC of the block before it
+                        const short* block = coef + o.coef_offset[c] / 2 + ((long)by * o.blocks_w[c] + bx) * 64;
+                        const int r = enc_block(w, huff[c ? 2 : 0], huff[c ? 3 : 1], block, dummy, pred[c]);
+                        if (r != SSD_OK) return r;
+                    }
+        }
+    if (w.bits) w.put((1u << (8 - w.bits)) - 1, 8 - w.bits);                       // the last byte padded with 1-bits
+    w.be16(0xFFD9);
+    SSD_CHECK_ARG(w.at <= w.n, "ssd_jpeg_entropy_encode: out holds %zu bytes, the stream needs more", out_bytes);
+    *written = w.at;
+    return SSD_OK;
+}
+
+extern "C" size_t ssd_jpeg_forward_workspace_bytes(const struct ssd_jpeg_enc_desc* desc_host, int B) {
+    if (!desc_host || B <= 0) return 0;
+    size_t total = 0;
+    for (int b = 0; b < B; ++b) {
+        const ssd_jpeg_enc_desc& d = desc_host[b];
+        if (enc_desc_shape_ok(d) && enc_desc_sampling_ok(d)) total += enc_round16((size_t)enc_geom(d).nblocks * 64);
+    }
+    return total;
+}
+
+extern "C" int ssd_jpeg_forward(const unsigned char* rgb_dev, size_t rgb_bytes, const unsigned char* tables_dev, size_t tables_bytes,
+                                const struct ssd_jpeg_enc_desc* desc_host, const struct ssd_jpeg_enc_desc* desc_dev, int B,
+                                short* coef_dev, size_t coef_bytes, void* workspace_dev, size_t workspace_bytes, void* stream) {
+    SSD_CHECK_ARG(B >= 0, "ssd_jpeg_forward: bad batch");
+    SSD_UNSUPPORTED_IF(B > 65535, "ssd_jpeg_forward: B = %d (at most 65535)", B);
+    if (B == 0) return SSD_OK;
+    SSD_CHECK_ARG(rgb_dev && tables_dev && desc_host && desc_dev && coef_dev && workspace_dev, "ssd_jpeg_forward: NULL pointer");
+    SSD_CHECK_ARG((((size_t)tables_dev | (size_t)coef_dev | (size_t)workspace_dev) & 15) == 0, "ssd_jpeg_forward: a buffer is not 16-byte aligned");
+    long blocks = 0, items = 0;
+    size_t plane_end = 0, coef_end = 0;
+    for (int b = 0; b < B; ++b) {
+        const ssd_jpeg_enc_desc& d = desc_host[b];
+        SSD_UNSUPPORTED_IF(!enc_desc_shape_ok(d), "ssd_jpeg_forward: image %d is %d x %d, outside 1..%d", b, d.H, d.W, kEncMaxSide);
+        SSD_UNSUPPORTED_IF(!enc_desc_sampling_ok(d), "ssd_jpeg_forward: image %d: luma sampling %dx%d (1x1, 2x1 and 2x2 only)", b, d.h_samp, d.v_samp);
+        const enc_geometry g = enc_geom(d);
+        const size_t nb = (size_t)g.nblocks;
+        SSD_CHECK_ARG(d.src_offset >= 0 && (size_t)d.src_offset + (size_t)d.H * d.W * 3 <= rgb_bytes,
+                      "ssd_jpeg_forward: image %d lies outside rgb_dev", b);
+        SSD_CHECK_ARG(d.coef_offset >= 0 && (d.coef_offset & 15) == 0 && (size_t)d.coef_offset >= coef_end &&
+                          (size_t)d.coef_offset + nb * 128 <= coef_bytes,
+                      "ssd_jpeg_forward: image %d: coefficients outside coef_dev, misaligned or overlapping", b);
+        coef_end = (size_t)d.coef_offset + nb * 128;
+        SSD_CHECK_ARG(d.quant_offset >= 0 && (d.quant_offset & 15) == 0 && (size_t)d.quant_offset + 256 <= tables_bytes,
+                      "ssd_jpeg_forward: image %d: quantisation tables outside tables_dev or misaligned", b);
+        SSD_CHECK_ARG(d.plane_offset >= 0 && (d.plane_offset & 15) == 0 && (size_t)d.plane_offset >= plane_end &&
+                          (size_t)d.plane_offset + nb * 64 <= workspace_bytes,
+                      "ssd_jpeg_forward: image %d: planes outside the workspace, misaligned or overlapping", b);
+        plane_end = (size_t)d.plane_offset + nb * 64;
+        SSD_CHECK_ARG(d.block_start == blocks && d.item_start == items, "ssd_jpeg_forward: image %d: block_start / item_start are not the running sums", b);
+        blocks += (long)nb;
+        items += g.nitems;
+        SSD_UNSUPPORTED_IF(blocks >= (1L << 31) - 64 || items >= (1L << 31) - 512, "ssd_jpeg_forward: the batch is too large for one call (image %d)", b);
+    }
+    hipLaunchKernelGGL(jpeg_enc_color_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rgb_dev,
+                       desc_dev, B, (int)items, (unsigned char*)workspace_dev);
+    SSD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(jpeg_enc_fdct_kernel, dim3((unsigned)((blocks + 31) / 32)), dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned char*)workspace_dev, tables_dev, desc_dev, B, (int)blocks, (unsigned char*)coef_dev);
+    SSD_LAUNCH_CHECK();
+    return SSD_OK;
+}

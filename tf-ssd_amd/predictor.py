@@ -2,7 +2,8 @@
 (``-handle-gpu``, ``--backbone``), the same knobs (batch 32, ``evaluate`` switch, "bg" + VOC
 labels) and the same call order -- hyper-parameters, model, weights, priors, decoder model,
 ``predict`` over the test split, optional VOC07 mAP, optional drawing (``draw=True``: ``drawing_utils.draw_predictions``
-on the GPU, PNGs into ``draw_dir``).
+on the GPU, PNGs into ``draw_dir``, or JPEGs with ``draw_format="jpeg"``: forward DCT on the GPU, Huffman coding on the
+data pool's threads).
 
 Data: with ``SSD_VOC_DIR`` set to a directory that holds a VOCdevkit, the reference's own calls run
 (predictor.py:22-25, 40-43): ``get_dataset("voc/2007", "test")``, ``get_total_item_size``,
@@ -36,9 +37,11 @@ evaluate = False
 use_custom_images = False
 custom_image_path = "data/images/"
 # additions: the reference always draws when it does not evaluate (and blocks in plt.show()); here drawing is opt-in and
-# writes draw_dir/img_%05d.png when draw_dir is set
+# writes draw_dir/img_%05d.png when draw_dir is set (draw_format "jpeg": img_%05d.jpg at quality draw_quality)
 draw = False
 draw_dir = None
+draw_format = "png"
+draw_quality = 75
 
 
 def _model_factory(backbone):
@@ -60,7 +63,7 @@ def _load_or_synthesise_weights(model, backbone):
 
 def main(argv=None, **knobs):
     """``knobs`` override the module-level switches for one call (``evaluate``, ``use_custom_images``,
-    ``custom_image_path``, ``batch_size``, ``draw``, ``draw_dir``)."""
+    ``custom_image_path``, ``batch_size``, ``draw``, ``draw_dir``, ``draw_format``, ``draw_quality``)."""
     args = io_utils.handle_args(argv)
     if args.handle_gpu:
         io_utils.handle_gpu_compatibility()
@@ -71,6 +74,10 @@ def main(argv=None, **knobs):
     custom_path = knobs.get("custom_image_path", custom_image_path)
     do_draw = bool(knobs.get("draw", draw))
     out_dir = knobs.get("draw_dir", draw_dir)
+    out_format = knobs.get("draw_format", draw_format)
+    out_quality = int(knobs.get("draw_quality", draw_quality))
+    if out_format not in ("png", "jpeg"):
+        raise ValueError('draw_format must be "png" or "jpeg", got %r' % (out_format,))
 
     labels = ["bg"] + data_utils.get_labels()
     hyper_params = train_utils.get_hyper_params(args.backbone)
@@ -114,8 +121,9 @@ def main(argv=None, **knobs):
     if do_eval:                                           # predictor.py:54-55
         stats = eval_utils.evaluate_predictions(test_data, boxes, classes, scores, labels, bs)
         return boxes, classes, scores, stats
-    if do_draw:                                           # predictor.py:56-57, on the GPU; PNGs instead of plt.show()
-        for _ in drawing_utils.draw_predictions(test_data, boxes, classes, scores, labels, bs, out_dir=out_dir):
+    if do_draw:                                           # predictor.py:56-57, on the GPU; files instead of plt.show()
+        for _ in drawing_utils.draw_predictions(test_data, boxes, classes, scores, labels, bs, out_dir=out_dir,
+                                                out_format=out_format, out_quality=out_quality):
             pass
     return boxes, classes, scores
 

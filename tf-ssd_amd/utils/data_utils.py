@@ -588,6 +588,185 @@ def resize_lanczos_jpeg_batch(blobs, final_height, final_width, out=None, out_u8
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Baseline JPEGs encoded behind a GPU forward DCT (include/ssd_hip.h, "JPEG encoding"): the mirror
+# image of the decoder.  Colour conversion, chroma downsampling, forward DCT and quantisation run on the device
+# (``ssd_jpeg_forward``); the host writes the header and the Huffman stream (``ssd_jpeg_entropy_encode``: plain C++, the
+# GIL is released around it) on the data pool's threads.  The bytes are ``PIL.Image.fromarray(a).save(f, "JPEG",
+# quality=q, subsampling=s)``'s exactly.
+
+JPEG_SAMPLING = {"4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2)}                 # luma (h_samp, v_samp)
+# On by default since the measurement (tests/bench_jpeg_encode.py; DESIGN.md section 7, profiles/HISTORY.md): 3.3x the
+# images/s of the Pillow JPEG pool at 8 workers, spreads not overlapping, the same bytes.
+JPEG_ENCODE_GPU_DEFAULT = "1"
+_encode_pools = {}
+_encode_staging = {}
+
+
+def jpeg_encode_gpu_enabled():
+    """Whether ``encode_jpeg_batch`` runs the forward DCT on the GPU: yes unless ``SSD_JPEG_ENCODE_GPU=0``, which routes
+    to Pillow on downloaded pixels (the fallback and the A/B leg; the same bytes)."""
+    import os
+    return os.environ.get("SSD_JPEG_ENCODE_GPU", JPEG_ENCODE_GPU_DEFAULT) != "0"
+
+
+def _encode_pool(workers):
+    """The threads that write the streams: ``data_workers(workers)`` of them, kept between calls."""
+    from concurrent.futures import ThreadPoolExecutor
+    n = data_workers(workers)
+    if n not in _encode_pools:
+        _encode_pools[n] = ThreadPoolExecutor(max_workers=n, thread_name_prefix="ssd-jpeg")
+    return _encode_pools[n]
+
+
+def _per_image(value, B, name):
+    if isinstance(value, (list, tuple, np.ndarray)):
+        if len(value) != B:
+            raise ValueError("%s: %d entries for %d images" % (name, len(value), B))
+        return list(value)
+    return [value] * B
+
+
+def _jpeg_encode_layout(shapes, samplings):
+    """Where one ``ssd_jpeg_forward`` call's input and output sit: descriptors | quantisation tables in ONE upload, the
+    coefficient storage of the images one after the other (each rounded up to 16 bytes), the component planes likewise."""
+    import ssd_hip as _h
+    B = len(shapes)
+    desc = np.zeros(B, _h.JPEG_ENC_DESC_DTYPE)
+    tables_at = (desc.nbytes + 15) & ~15
+    src = coef = planes = blocks = items = 0
+    for b, ((H, W), (hs, vs)) in enumerate(zip(shapes, samplings)):
+        d = desc[b]
+        d["H"], d["W"], d["h_samp"], d["v_samp"] = H, W, hs, vs
+        d["src_offset"], d["coef_offset"], d["quant_offset"], d["plane_offset"] = src, coef, tables_at + 256 * b, planes
+        d["block_start"], d["item_start"] = blocks, items
+        n1 = -(-W // (8 * hs)) * -(-H // (8 * vs))
+        nb = n1 * (hs * vs + 2)
+        src += H * W * 3
+        coef += (nb * 128 + 15) & ~15
+        planes += (nb * 64 + 15) & ~15
+        blocks += nb
+        items += n1 * 16
+    return {"desc": desc, "tables_at": tables_at, "total": tables_at + 256 * B, "coef_bytes": coef, "plane_bytes": planes}
+
+
+def jpeg_forward_batch(rgb, shapes, samplings, tables):
+    """``ssd_jpeg_forward`` on packed device pixels: ``rgb`` a contiguous uint8 device tensor holding the images one after
+    the other, ``shapes`` [(H, W)], ``samplings`` [(h_samp, v_samp)], ``tables`` uint16 [B,2,64].  Returns ``(coef, desc)``:
+    the uint8 device buffer of the coefficient storages and the descriptors (``coef_offset`` says where each begins)."""
+    import torch
+    import ssd_hip as _h
+    dev = _h.device()
+    B = len(shapes)
+    for H, W in shapes:
+        if not (1 <= H <= 16384 and 1 <= W <= 16384):
+            raise _h.SsdHipUnsupported("encode_jpeg_batch: an image of %d x %d, outside 1..16384" % (H, W))
+    layout = _jpeg_encode_layout(shapes, samplings)
+    desc = layout["desc"]
+    tables = np.ascontiguousarray(tables, np.uint16).reshape(B, 128)
+
+    def fill(host):
+        host[:desc.nbytes] = desc.view(np.uint8)
+        host[layout["tables_at"]:layout["total"]] = tables.view(np.uint8).reshape(-1)
+
+    packed = _upload_packed(dev, layout["total"], fill)
+    assert layout["plane_bytes"] == _h.lib().ssd_jpeg_forward_workspace_bytes(desc.ctypes.data, B)
+    coef = torch.empty(max(layout["coef_bytes"], 16), dtype=torch.uint8, device=dev)
+    ws = _h.workspace(max(layout["plane_bytes"], 16))
+    base = packed.data_ptr()
+    _h.check(_h.lib().ssd_jpeg_forward(_h.ptr(rgb), rgb.numel(), base, layout["total"], desc.ctypes.data, base, B, _h.ptr(coef),
+                                       coef.numel(), _h.ptr(ws), ws.numel(), _h.stream()), "encode_jpeg_batch")
+    return coef, desc
+
+
+def jpeg_host_encode(coef, H, W, sampling, tables):
+    """The host half for one image, for a worker thread: int16 coefficient storage (a NumPy view, e.g. of the pinned
+    download) -> the JPEG stream's ``bytes``."""
+    import ctypes
+    import ssd_hip as _h
+    lib = _h.lib()
+    info = _h.JpegInfo()
+    tables = np.ascontiguousarray(tables, np.uint16)
+    _h.check(lib.ssd_jpeg_encode_info(int(W), int(H), int(sampling[0]), int(sampling[1]), tables.ctypes.data, ctypes.byref(info)),
+             "ssd_jpeg_encode_info")
+    if coef.nbytes < info.coef_bytes:
+        raise ValueError("jpeg_host_encode: %d bytes of coefficients, the image needs %d" % (coef.nbytes, info.coef_bytes))
+    out = np.empty(int(lib.ssd_jpeg_encode_bound(ctypes.byref(info))), np.uint8)
+    written = ctypes.c_size_t(0)
+    _h.check(lib.ssd_jpeg_entropy_encode(coef.ctypes.data, ctypes.byref(info), out.ctypes.data, out.nbytes, ctypes.byref(written)),
+             "ssd_jpeg_entropy_encode")
+    return out[:written.value].tobytes()
+
+
+def _pillow_jpeg(args):
+    import io
+    from PIL import Image
+    pixels, quality, subsampling = args
+    buf = io.BytesIO()
+    Image.fromarray(pixels).save(buf, "JPEG", quality=quality, subsampling=subsampling)
+    return buf.getvalue()
+
+
+def encode_jpeg_batch(images, quality=75, subsampling="4:2:0", workers=None):
+    """Device uint8 images -> their JPEG files' ``bytes``, bitwise ``PIL.Image.fromarray(a).save(f, "JPEG", quality=quality,
+    subsampling=subsampling)``'s.  ``images``: a device uint8 ``[B,H,W,3]`` tensor (what ``drawing_utils`` draws) or a list
+    of device ``[H,W,3]`` tensors of any sizes; ``quality`` and ``subsampling`` ("4:4:4", "4:2:2", "4:2:0") may be one
+    value or one per image.  Per batch: ONE descriptor upload, ONE ``ssd_jpeg_forward`` call (two launches), ONE download
+    of the int16 coefficients into pinned memory; then ``ssd_jpeg_entropy_encode`` per image on ``data_workers(workers)``
+    threads.  ``SSD_JPEG_ENCODE_GPU=0``: the pixels are downloaded and Pillow encodes them on the same threads."""
+    import torch
+    import ssd_hip as _h
+    dev = _h.device()
+    if isinstance(images, torch.Tensor):
+        if images.dim() != 4:
+            raise ValueError("images must be uint8 [B,H,W,3] or a list of [H,W,3], got %s" % (tuple(images.shape),))
+        seq = list(images)
+    else:
+        seq = list(images)
+    for t in seq:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.device != dev:
+            raise ValueError("images must be device uint8 [H,W,3] tensors")
+    B = len(seq)
+    qualities = [int(q) for q in _per_image(quality, B, "quality")]
+    subs = _per_image(subsampling, B, "subsampling")
+    for s in subs:
+        if s not in JPEG_SAMPLING:
+            raise ValueError("subsampling must be one of %s, got %r" % (sorted(JPEG_SAMPLING), s))
+    if B == 0:
+        _h.check(_h.lib().ssd_jpeg_forward(None, 0, None, 0, None, None, 0, None, 0, None, 0, _h.stream()), "encode_jpeg_batch")
+        return []
+    shapes = [(int(t.shape[0]), int(t.shape[1])) for t in seq]
+    pool = _encode_pool(workers)
+    if isinstance(images, torch.Tensor) and images.is_contiguous():
+        rgb = images.reshape(-1)
+    else:
+        rgb = torch.cat([t.reshape(-1) for t in seq])
+    if not jpeg_encode_gpu_enabled():
+        host = rgb.cpu().numpy()
+        ends = np.cumsum([h * w * 3 for h, w in shapes])
+        jobs = [(host[e - h * w * 3:e].reshape(h, w, 3), q, s) for e, (h, w), q, s in zip(ends, shapes, qualities, subs)]
+        return list(pool.map(_pillow_jpeg, jobs))
+    samplings = [JPEG_SAMPLING[s] for s in subs]
+    known = {}
+    tables = np.empty((B, 2, 64), np.uint16)
+    for b, q in enumerate(qualities):
+        if q not in known:
+            known[q] = np.empty((2, 64), np.uint16)
+            _h.check(_h.lib().ssd_jpeg_quality_tables(q, known[q].ctypes.data), "ssd_jpeg_quality_tables")
+        tables[b] = known[q]
+    coef, desc = jpeg_forward_batch(rgb, shapes, samplings, tables)
+    st = _encode_staging.get(dev.index)
+    if st is None or st.numel() < coef.numel():
+        st = _encode_staging[dev.index] = _h.pinned_empty((max(1 << (coef.numel() - 1).bit_length(), 1 << 20),), torch.uint8)
+    st[:coef.numel()].copy_(coef, non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    host = st.numpy()
+    ends = [int(d["coef_offset"]) for d in desc[1:]] + [coef.numel()]
+    jobs = [(host[int(d["coef_offset"]):e].view(np.int16), h, w, hv, t)
+            for d, e, (h, w), hv, t in zip(desc, ends, shapes, samplings, tables)]
+    return list(pool.map(lambda a: jpeg_host_encode(*a), jobs))
+
+
 def data_workers(workers=None):
     """Size of the decoding pool: ``workers``, else ``SSD_DATA_WORKERS``, else 8; always within 1..16 (never the
     machine's CPU count: the pool shares the host with the training loop and with other jobs)."""

@@ -242,7 +242,8 @@ def draw_detections_batch(imgs, boxes, label_indices, probs, labels, colors=None
     return draw_pixel_boxes(imgs, ib, li, label_texts(ib, li, pr, labels), col, out=out)
 
 
-def draw_bboxes_with_labels(img, bboxes, label_indices, probs, labels, colors=None, out=None, out_dir=None, show=False):
+def draw_bboxes_with_labels(img, bboxes, label_indices, probs, labels, colors=None, out=None, out_dir=None, show=False,
+                            out_format="png", out_quality=75):
     """drawing_utils.py:45-73: ``img`` ``[H,W,3]`` float, ``bboxes`` ``[T,4]`` DENORMALISED, ``label_indices`` / ``probs``
     ``[T]``.  The B = 1 case of the batched call; returns the uint8 device tensor ``[H,W,3]``."""
     x = img.unsqueeze(0) if isinstance(img, torch.Tensor) else np.asarray(img)[None]
@@ -253,25 +254,26 @@ def draw_bboxes_with_labels(img, bboxes, label_indices, probs, labels, colors=No
     pr = _host(probs, np.float32).reshape(1, T)
     col = _colors_u8(colors, len(labels))
     o = draw_pixel_boxes(x, ib, li, label_texts(ib, li, pr, labels), col, out=None if out is None else out.unsqueeze(0))
-    _present(o, out_dir, 0, show)
+    _present(o, out_dir, 0, show, out_format, out_quality)
     return o[0]
 
 
 def draw_predictions(dataset, pred_bboxes, pred_labels, pred_scores, labels, batch_size, colors=None, out_dir=None,
-                     show=False):
+                     show=False, out_format="png", out_quality=75):
     """drawing_utils.py:75-84 as a generator: one uint8 device tensor ``[B,H,W,3]`` per batch of ``dataset`` (items
-    ``(imgs, _, _)``), drawn with ONE colour table for the whole run.  ``out_dir``: also writes ``img_%05d.png``."""
+    ``(imgs, _, _)``), drawn with ONE colour table for the whole run.  ``out_dir``: also writes ``img_%05d.png``, or, with
+    ``out_format="jpeg"``, ``img_%05d.jpg`` at ``out_quality`` (encoded from the device tensor: ``_present``)."""
     col = _colors_u8(colors, len(labels))
     for batch_id, image_data in enumerate(dataset):
         imgs = image_data[0]
         start = batch_id * batch_size
         end = start + int(imgs.shape[0])
         o = draw_detections_batch(imgs, pred_bboxes[start:end], pred_labels[start:end], pred_scores[start:end], labels, colors=col)
-        _present(o, out_dir, start, show)
+        _present(o, out_dir, start, show, out_format, out_quality)
         yield o
 
 
-def draw_bboxes(imgs, bboxes, colors=None, out=None, out_dir=None, show=False):
+def draw_bboxes(imgs, bboxes, colors=None, out=None, out_dir=None, show=False, out_format="png", out_quality=75):
     """drawing_utils.py:31-43 -> ``tf.image.draw_bounding_boxes(imgs, bboxes, colors)``: float images ``[B,H,W,3]``,
     normalised boxes ``[B,T,4]``, ``colors`` float ``[L, 3 or 4]`` cycled by box index (default: the reference's red).
     Returns the float32 device tensor ``[B,H,W,3]``."""
@@ -289,11 +291,11 @@ def draw_bboxes(imgs, bboxes, colors=None, out=None, out_dir=None, show=False):
     _h.check(_h.lib().ssd_draw_bounding_boxes(_h.ptr(x), B, H, W, C, _h.ptr(bx), T, _h.ptr(cd), int(cd.shape[0]), _h.ptr(out),
                                               _h.stream()), "ssd_draw_bounding_boxes")
     if out_dir is not None or show:
-        _present((out.clamp(0, 1) * 255).to(torch.uint8), out_dir, 0, show)
+        _present((out.clamp(0, 1) * 255).to(torch.uint8), out_dir, 0, show, out_format, out_quality)
     return out
 
 
-def draw_grid_map(img, grid_map, stride, out=None, out_dir=None, show=False):
+def draw_grid_map(img, grid_map, stride, out=None, out_dir=None, show=False, out_format="png", out_quality=75):
     """drawing_utils.py:6-29: a filled white 5 x 5 square at ``grid + stride // 2`` for every row of ``grid_map``
     (``[N,4]``; the reference hands rows (0, 1, 2, 3) to PIL as (x0, y0, x1, y1)).  ``img`` uint8 ``[H,W,3]``.  Returns the
     uint8 device tensor ``[H,W,3]``."""
@@ -316,16 +318,30 @@ def draw_grid_map(img, grid_map, stride, out=None, out_dir=None, show=False):
         res = draw_pixel_boxes(cur.float(), part, np.zeros(part.shape[:2], np.int64), None, white,
                                out=None if (out is None or not last) else out.unsqueeze(0), scale=False, fill=True)
         cur = res
-    _present(res, out_dir, 0, show)
+    _present(res, out_dir, 0, show, out_format, out_quality)
     return res[0]
 
 
-def _present(images_u8, out_dir, start, show):
-    """``out_dir``: ``img_%05d.png`` from index ``start`` on, through PIL.  ``show``: the reference's matplotlib figures."""
+def _present(images_u8, out_dir, start, show, out_format="png", out_quality=75):
+    """``out_dir``: ``img_%05d.png`` from index ``start`` on, through PIL; with ``out_format="jpeg"``, ``img_%05d.jpg`` at
+    quality ``out_quality`` through ``data_utils.encode_jpeg_batch`` -- the drawn tensor is already on the device, so the
+    whole batch is one forward-DCT call and the files are Pillow's ``save(f, "JPEG", quality=out_quality)`` bytes.
+    ``show``: the reference's matplotlib figures."""
+    if out_format not in ("png", "jpeg"):
+        raise ValueError('out_format must be "png" or "jpeg", got %r' % (out_format,))
     if out_dir is None and not show:
         return
+    if out_dir is not None and out_format == "jpeg":
+        from utils import data_utils
+        os.makedirs(out_dir, exist_ok=True)
+        blobs = data_utils.encode_jpeg_batch(images_u8.detach().contiguous(), quality=out_quality)
+        for i, blob in enumerate(blobs):
+            with open(os.path.join(out_dir, "img_%05d.jpg" % (start + i)), "wb") as f:
+                f.write(blob)
+        if not show:
+            return
     host = images_u8.detach().cpu().numpy()
-    if out_dir is not None:
+    if out_dir is not None and out_format == "png":
         from PIL import Image
         os.makedirs(out_dir, exist_ok=True)
         for i, a in enumerate(host):
