@@ -1,4 +1,4 @@
-// Stand-alone check of the JPEG encoder's host half under a sanitizer (CPU only; never loaded into Python, needs no GPU).
+// Stand-alone check of the JPEG encoder's and decoder's host halves under a sanitizer (CPU only; never loaded into Python, needs no GPU).
 // Links csrc/ssd_jpeg_enc.hip and csrc/ssd_jpeg.hip with an error sink of its own and reads the cases
 // tests/micro/jpeg_encode_host_check.sh dumps from the fixture: per case H, W, h_samp, v_samp, quality (int32), the int16
 // coefficient storage of the NumPy restatement and the bytes Pillow wrote.  Every buffer handed to the library is a heap
@@ -58,14 +58,23 @@ int main(int argc, char** argv) {
         std::vector<short> wild(coef);                                                 // out-of-range values: an error, no UB
         wild[0] = 32767; wild[1] = -32768;
         REQUIRE(ssd_jpeg_entropy_encode(wild.data(), &info, out.data(), out.size(), &written) == SSD_E_INVALID);
-        // the decoder's host half reads the stream back into a block of exactly coef_bytes
+        // the decoder's host half on the same stream: the frame it parses is the case's, its struct ssd_jpeg_info is the
+        // encoder's byte for byte (both complete it with the same code), and it decodes into a block of exactly coef_bytes
         ssd_jpeg_info parsed;
-        REQUIRE(ssd_jpeg_parse(want.data(), want.size(), &parsed) == SSD_OK && memcmp(&parsed, &info, sizeof(info)) == 0);
+        REQUIRE(ssd_jpeg_parse(want.data(), want.size(), &parsed) == SSD_OK);
+        REQUIRE(parsed.width == W && parsed.height == H && parsed.components == 3);
+        REQUIRE(parsed.h_samp[0] == hs && parsed.v_samp[0] == vs);
+        for (int c = 1; c < 3; ++c) REQUIRE(parsed.h_samp[c] == 1 && parsed.v_samp[c] == 1);
+        REQUIRE(memcmp(&parsed, &info, sizeof(info)) == 0);
         std::vector<short> back(coef.size());
         REQUIRE(ssd_jpeg_entropy_decode(want.data(), want.size(), &parsed, back.data(), back.size() * 2) == SSD_OK);
+        REQUIRE(back[0] == coef[0]);                                                   // the first luma DC term, at least
+        std::vector<short> small(coef.size() - 64);                                    // one block short: refused, not overrun
+        REQUIRE(ssd_jpeg_entropy_decode(want.data(), want.size(), &parsed, small.data(), small.size() * 2) == SSD_E_INVALID);
+        REQUIRE(ssd_jpeg_entropy_decode(want.data(), want.size() / 2, &parsed, back.data(), back.size() * 2) == SSD_E_INVALID);
         ++n;
     }
     fclose(f);
-    printf("%d cases: bytes equal, nothing outside the buffers\n", n);
+    printf("%d cases: bytes equal, parsed back to the same frame, nothing outside the buffers\n", n);
     return n > 0 ? 0 : 3;
 }

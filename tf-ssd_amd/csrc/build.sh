@@ -11,8 +11,8 @@ need_link=0
 compile() {  # src extra-flags
   local src=$1; shift
   local obj=build/${src%.*}.o
-  if [ "$FORCE" = 1 ] || [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ common.h -nt "$obj" ] \
-     || [ ../../include/ssd_hip.h -nt "$obj" ] || [ ssd_conv.h -nt "$obj" ] || [ ssd_net.h -nt "$obj" ] || [ ssd_conv_mfma.h -nt "$obj" ] || [ ssd_bf16x3.h -nt "$obj" ] || { [ -f "${src%.*}.h" ] && [ "${src%.*}.h" -nt "$obj" ]; }; then
+  # any header newer than the object rebuilds it: no list of header names to keep in step with the sources
+  if [ "$FORCE" = 1 ] || [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ -n "$(find . ../../include -maxdepth 1 -name '*.h' -newer "$obj" -print -quit)" ]; then
     echo "hipcc $src"
     # translation units compile in parallel (ssd_conv.hip alone instantiates ~80 kernels)
     ( $HIPCC $COMMON "$@" -c "$src" -o "$obj.tmp" && mv "$obj.tmp" "$obj" ) || touch build/.failed &

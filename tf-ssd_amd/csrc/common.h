@@ -51,4 +51,20 @@ void set_error(const char* fmt, ...);
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// the image I/O paths (preprocessing, Lanczos resize, drawing, JPEG): the largest height / width they take, so that a
+// pixel's byte offset H * W * 3 stays below 2^31
+static const int kMaxImageSide = 16384;
+static inline bool image_side_ok(const int v) { return v >= 1 && v <= kMaxImageSide; }
+
+// One image's region [offset, offset + length) of a buffer of `limit` bytes, as the ragged entry points require it:
+// not negative, a multiple of `align` (a power of two; 1: any), inside the buffer and -- with `end`, the running end of
+// the regions before it, which then moves to this region's end -- not before the previous image's region ends.
+static inline bool region_ok(const long long offset, const size_t length, const size_t limit, const size_t align,
+                             size_t* end = nullptr) {
+    if (offset < 0 || ((size_t)offset & (align - 1)) != 0 || (end && (size_t)offset < *end) || (size_t)offset + length > limit)
+        return false;
+    if (end) *end = (size_t)offset + length;
+    return true;
+}
+
 }  // namespace ssd

@@ -414,26 +414,22 @@ extern "C" int ssd_preprocess(const unsigned char* image_u8_dev, int B, int H, i
     return SSD_OK;
 }
 
-static const int kResizeMaxSide = 16384;
-static inline bool resize_side_ok(const int v) { return v >= 1 && v <= kResizeMaxSide; }
-static inline size_t round16(const size_t v) { return (v + 15) & ~(size_t)15; }
-
 extern "C" int ssd_preprocess_ragged(const unsigned char* src_dev, size_t src_bytes, const struct ssd_image_desc* desc_host,
                                      const struct ssd_image_desc* desc_dev, int B, int C, int out_h, int out_w,
                                      float* out_dev, void* stream) {
     SSD_CHECK_ARG(B >= 0, "ssd_preprocess_ragged: bad batch");
     SSD_UNSUPPORTED_IF(C != 3, "ssd_preprocess_ragged: C = %d (3 only)", C);
-    SSD_UNSUPPORTED_IF(!resize_side_ok(out_h) || !resize_side_ok(out_w), "ssd_preprocess_ragged: output %d x %d outside 1..%d",
-                       out_h, out_w, kResizeMaxSide);
+    SSD_UNSUPPORTED_IF(!image_side_ok(out_h) || !image_side_ok(out_w), "ssd_preprocess_ragged: output %d x %d outside 1..%d",
+                       out_h, out_w, kMaxImageSide);
     SSD_UNSUPPORTED_IF(B > 65535, "ssd_preprocess_ragged: B = %d (at most 65535)", B);
     if (B == 0) return SSD_OK;
     SSD_CHECK_ARG(src_dev && desc_host && desc_dev && out_dev, "ssd_preprocess_ragged: NULL pointer");
     for (int b = 0; b < B; ++b) {
         const ssd_image_desc& d = desc_host[b];
-        SSD_UNSUPPORTED_IF(!resize_side_ok(d.H) || !resize_side_ok(d.W), "ssd_preprocess_ragged: image %d is %d x %d, outside 1..%d",
-                           b, d.H, d.W, kResizeMaxSide);
+        SSD_UNSUPPORTED_IF(!image_side_ok(d.H) || !image_side_ok(d.W), "ssd_preprocess_ragged: image %d is %d x %d, outside 1..%d",
+                           b, d.H, d.W, kMaxImageSide);
         SSD_CHECK_ARG(d.src_offset >= 0 && (d.src_offset & 15) == 0, "ssd_preprocess_ragged: image %d: offset not a multiple of 16", b);
-        SSD_CHECK_ARG((size_t)d.src_offset + (size_t)d.H * d.W * 3 <= src_bytes,
+        SSD_CHECK_ARG(region_ok(d.src_offset, (size_t)d.H * d.W * 3, src_bytes, 16),
                       "ssd_preprocess_ragged: image %d lies outside the source buffer", b);
     }
     const long items = ((long)out_h * out_w * 3 + 3) / 4;
@@ -444,14 +440,14 @@ extern "C" int ssd_preprocess_ragged(const unsigned char* src_dev, size_t src_by
     return SSD_OK;
 }
 
-extern "C" int ssd_resize_lanczos_pitch(int out_w) { return resize_side_ok(out_w) ? (out_w * 3 + 3) & ~3 : 0; }
+extern "C" int ssd_resize_lanczos_pitch(int out_w) { return image_side_ok(out_w) ? (out_w * 3 + 3) & ~3 : 0; }
 
 extern "C" size_t ssd_resize_lanczos_workspace_bytes(const struct ssd_resize_desc* desc_host, int B, int out_h, int out_w) {
-    if (!desc_host || B <= 0 || !resize_side_ok(out_h) || !resize_side_ok(out_w)) return 0;
+    if (!desc_host || B <= 0 || !image_side_ok(out_h) || !image_side_ok(out_w)) return 0;
     const size_t pitch = (size_t)ssd_resize_lanczos_pitch(out_w);
     size_t total = 0;
     for (int b = 0; b < B; ++b)
-        if (desc_host[b].W != out_w && resize_side_ok(desc_host[b].H)) total += round16((size_t)desc_host[b].H * pitch);
+        if (desc_host[b].W != out_w && image_side_ok(desc_host[b].H)) total += align_up((size_t)desc_host[b].H * pitch, 16);
     return total;
 }
 
@@ -461,8 +457,8 @@ extern "C" int ssd_resize_lanczos(const unsigned char* src_dev, size_t src_bytes
                                   void* workspace_dev, size_t workspace_bytes, void* stream) {
     SSD_CHECK_ARG(B >= 0, "ssd_resize_lanczos: bad batch");
     SSD_UNSUPPORTED_IF(C != 3, "ssd_resize_lanczos: C = %d (3 only)", C);
-    SSD_UNSUPPORTED_IF(!resize_side_ok(out_h) || !resize_side_ok(out_w), "ssd_resize_lanczos: output %d x %d outside 1..%d",
-                       out_h, out_w, kResizeMaxSide);
+    SSD_UNSUPPORTED_IF(!image_side_ok(out_h) || !image_side_ok(out_w), "ssd_resize_lanczos: output %d x %d outside 1..%d",
+                       out_h, out_w, kMaxImageSide);
     SSD_UNSUPPORTED_IF(B > 65535, "ssd_resize_lanczos: B = %d (at most 65535)", B);
     if (B == 0) return SSD_OK;
     SSD_CHECK_ARG(src_dev && tables_dev && desc_host && desc_dev && out_dev, "ssd_resize_lanczos: NULL pointer");
@@ -472,18 +468,16 @@ extern "C" int ssd_resize_lanczos(const unsigned char* src_dev, size_t src_bytes
     size_t tmp_end = 0;
     for (int b = 0; b < B; ++b) {
         const ssd_resize_desc& d = desc_host[b];
-        SSD_UNSUPPORTED_IF(!resize_side_ok(d.H) || !resize_side_ok(d.W), "ssd_resize_lanczos: image %d is %d x %d, outside 1..%d",
-                           b, d.H, d.W, kResizeMaxSide);
-        SSD_CHECK_ARG(d.src_offset >= 0 && (size_t)d.src_offset + (size_t)d.H * d.W * 3 <= src_bytes,
+        SSD_UNSUPPORTED_IF(!image_side_ok(d.H) || !image_side_ok(d.W), "ssd_resize_lanczos: image %d is %d x %d, outside 1..%d",
+                           b, d.H, d.W, kMaxImageSide);
+        SSD_CHECK_ARG(region_ok(d.src_offset, (size_t)d.H * d.W * 3, src_bytes, 1),
                       "ssd_resize_lanczos: image %d lies outside the source buffer", b);
         if (d.W != out_w) {
             SSD_CHECK_ARG(d.h_ksize >= 1 && d.h_bounds >= 0 && (size_t)d.h_bounds + (size_t)out_w * 2 <= tables_ints &&
                               d.h_k >= 0 && (size_t)d.h_k + (size_t)out_w * d.h_ksize <= tables_ints,
                           "ssd_resize_lanczos: image %d: horizontal tables lie outside tables_dev", b);
-            SSD_CHECK_ARG(workspace_dev && d.tmp_offset >= 0 && (d.tmp_offset & 15) == 0 && (size_t)d.tmp_offset >= tmp_end &&
-                              (size_t)d.tmp_offset + (size_t)d.H * pitch <= workspace_bytes,
+            SSD_CHECK_ARG(workspace_dev && region_ok(d.tmp_offset, (size_t)d.H * pitch, workspace_bytes, 16, &tmp_end),
                           "ssd_resize_lanczos: image %d: intermediate outside the workspace, misaligned or overlapping", b);
-            tmp_end = (size_t)d.tmp_offset + (size_t)d.H * pitch;
             h_items = std::max(h_items, (long)d.H * qpr);
         }
         if (d.H != out_h)

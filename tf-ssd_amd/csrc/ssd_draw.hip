@@ -33,7 +33,6 @@
 
 namespace ssd {
 
-static const int kDrawMaxSide = 16384;      // H, W
 static const int kDrawMaxBoxes = 4096;      // T of ssd_draw_detections (512 bytes of LDS mask)
 static const int kDrawMaxText = 64;         // maxlen
 static const int kDrawMaxOutline = 64;      // outline width
@@ -329,8 +328,6 @@ __global__ __launch_bounds__(256) void draw_bounding_boxes_kernel(const float* _
     }
 }
 
-static inline bool draw_side_ok(const int v) { return v >= 1 && v <= kDrawMaxSide; }
-
 }  // namespace ssd
 
 using namespace ssd;
@@ -343,7 +340,7 @@ extern "C" int ssd_image_minmax(const float* img_dev, int B, int H, int W, int C
                                 size_t workspace_bytes, void* stream) {
     SSD_CHECK_ARG(B >= 0, "ssd_image_minmax: bad batch");
     SSD_UNSUPPORTED_IF(C != 3, "ssd_image_minmax: C = %d (3 only)", C);
-    SSD_UNSUPPORTED_IF(!draw_side_ok(H) || !draw_side_ok(W), "ssd_image_minmax: image %d x %d outside 1..%d", H, W, kDrawMaxSide);
+    SSD_UNSUPPORTED_IF(!image_side_ok(H) || !image_side_ok(W), "ssd_image_minmax: image %d x %d outside 1..%d", H, W, kMaxImageSide);
     SSD_UNSUPPORTED_IF(B > 65535, "ssd_image_minmax: B = %d (at most 65535)", B);
     if (B == 0) return SSD_OK;
     SSD_CHECK_ARG(img_dev && minmax_out_dev && workspace_dev, "ssd_image_minmax: NULL pointer");
@@ -365,8 +362,8 @@ extern "C" int ssd_draw_detections(const float* img_dev, const float* minmax_dev
                                    void* stream) {
     SSD_CHECK_ARG(B >= 0 && T >= 0 && maxlen >= 0 && L >= 0, "ssd_draw_detections: negative size");
     SSD_UNSUPPORTED_IF(C != 3, "ssd_draw_detections: C = %d (3 only)", C);
-    SSD_UNSUPPORTED_IF(!draw_side_ok(H) || !draw_side_ok(W), "ssd_draw_detections: image %d x %d outside 1..%d", H, W,
-                       kDrawMaxSide);
+    SSD_UNSUPPORTED_IF(!image_side_ok(H) || !image_side_ok(W), "ssd_draw_detections: image %d x %d outside 1..%d", H, W,
+                       kMaxImageSide);
     SSD_UNSUPPORTED_IF(T > kDrawMaxBoxes, "ssd_draw_detections: T = %d (at most %d)", T, kDrawMaxBoxes);
     SSD_UNSUPPORTED_IF(maxlen > kDrawMaxText, "ssd_draw_detections: maxlen = %d (at most %d)", maxlen, kDrawMaxText);
     SSD_UNSUPPORTED_IF(B > 65535, "ssd_draw_detections: B = %d (at most 65535)", B);
@@ -393,8 +390,8 @@ extern "C" int ssd_draw_bounding_boxes(const float* img_dev, int B, int H, int W
                                        const float* colors_dev, int L, float* out_dev, void* stream) {
     SSD_CHECK_ARG(B >= 0 && T >= 0 && L >= 0, "ssd_draw_bounding_boxes: negative size");
     SSD_UNSUPPORTED_IF(C != 3, "ssd_draw_bounding_boxes: C = %d (3 only)", C);
-    SSD_UNSUPPORTED_IF(!draw_side_ok(H) || !draw_side_ok(W), "ssd_draw_bounding_boxes: image %d x %d outside 1..%d", H, W,
-                       kDrawMaxSide);
+    SSD_UNSUPPORTED_IF(!image_side_ok(H) || !image_side_ok(W), "ssd_draw_bounding_boxes: image %d x %d outside 1..%d", H, W,
+                       kMaxImageSide);
     SSD_UNSUPPORTED_IF(T > kBBoxMaxBoxes, "ssd_draw_bounding_boxes: T = %d (at most %d)", T, kBBoxMaxBoxes);
     SSD_UNSUPPORTED_IF(B > 65535, "ssd_draw_bounding_boxes: B = %d (at most 65535)", B);
     if (B == 0) return SSD_OK;

@@ -9,18 +9,12 @@
 // wrap int32 in the IDCT; wrapping is then the defined behaviour, as on the hardware.
 #include <cstring>
 
-#include "common.h"
+#include "ssd_jpeg_common.h"
 
 namespace ssd {
 
 // ---------------------------------------------------------------------------------------------------------------------
 // host: header
-
-static const unsigned char kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                          41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                          30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-static const int kJpegMaxSide = 16384;
 
 struct huff_table {
     bool defined;
@@ -92,7 +86,7 @@ static int parse_header(const unsigned char* data, const size_t n, jpeg_header& 
             o.height = be16(p + 1); o.width = be16(p + 3); o.components = p[5];
             SSD_CHECK_ARG(o.height >= 1 && o.width >= 1, "ssd_jpeg: empty image");
             SSD_UNSUPPORTED_IF(o.components != 1 && o.components != 3, "ssd_jpeg: %d components (CMYK / YCCK and others: grey and YCbCr only)", o.components);
-            SSD_UNSUPPORTED_IF(o.height > kJpegMaxSide || o.width > kJpegMaxSide, "ssd_jpeg: %d x %d, outside 1..%d", o.height, o.width, kJpegMaxSide);
+            SSD_UNSUPPORTED_IF(o.height > kMaxImageSide || o.width > kMaxImageSide, "ssd_jpeg: %d x %d, outside 1..%d", o.height, o.width, kMaxImageSide);
             SSD_CHECK_ARG(plen >= 6 + 3 * o.components, "ssd_jpeg: short frame header");
             for (int c = 0; c < o.components; ++c) {
                 comp_id[c] = p[6 + 3 * c];
@@ -167,25 +161,14 @@ static int parse_header(const unsigned char* data, const size_t n, jpeg_header& 
         else ycc = !(comp_id[0] == 'R' && comp_id[1] == 'G' && comp_id[2] == 'B');
         SSD_UNSUPPORTED_IF(!ycc, "ssd_jpeg: an RGB file (YCbCr and grey only)");
         const int hs = o.h_samp[0], vs = o.v_samp[0];
-        SSD_UNSUPPORTED_IF(o.h_samp[1] != 1 || o.v_samp[1] != 1 || o.h_samp[2] != 1 || o.v_samp[2] != 1 ||
-                               !((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2)),
+        SSD_UNSUPPORTED_IF(o.h_samp[1] != 1 || o.v_samp[1] != 1 || o.h_samp[2] != 1 || o.v_samp[2] != 1 || !jpeg_sampling_ok(hs, vs),
                            "ssd_jpeg: sampling %dx%d,%dx%d,%dx%d (4:4:4, 4:2:2 and 4:2:0 only)", hs, vs, o.h_samp[1], o.v_samp[1],
                            o.h_samp[2], o.v_samp[2]);
     } else {
         o.h_samp[0] = o.v_samp[0] = 1;                                            // a one-component scan is not interleaved
     }
-    const int hs = o.h_samp[0], vs = o.v_samp[0];
-    o.mcus_x = (o.width + 8 * hs - 1) / (8 * hs);
-    o.mcus_y = (o.height + 8 * vs - 1) / (8 * vs);
-    long long bytes = 0;
-    for (int c = 0; c < o.components; ++c) {
-        o.blocks_w[c] = o.mcus_x * o.h_samp[c];
-        o.blocks_h[c] = o.mcus_y * o.v_samp[c];
-        o.coef_offset[c] = bytes;
-        bytes += (long long)o.blocks_w[c] * o.blocks_h[c] * 128;
-        memcpy(o.quant[c], h.quant[o.quant_index[c]], 128);
-    }
-    o.coef_bytes = bytes;
+    jpeg_complete_info(o);
+    for (int c = 0; c < o.components; ++c) memcpy(o.quant[c], h.quant[o.quant_index[c]], 128);
     return SSD_OK;
 }
 
@@ -282,18 +265,18 @@ __host__ __device__ __forceinline__ int idct_range_limit(const int v) {
 // one 8-point pass of the "islow" inverse DCT: 13-bit constants, int32, descale by `shift` bits with rounding
 __host__ __device__ __forceinline__ void idct_islow_1d(const int in[8], int out[8], const int shift) {
     int z2 = in[2], z3 = in[6];
-    int z1 = (z2 + z3) * 4433;
-    int tmp2 = z1 + z3 * (-15137);
-    int tmp3 = z1 + z2 * 6270;
+    int z1 = (z2 + z3) * kFix0_541196100;
+    int tmp2 = z1 + z3 * (-kFix1_847759065);
+    int tmp3 = z1 + z2 * kFix0_765366865;
     int tmp0 = (in[0] + in[4]) * 8192;
     int tmp1 = (in[0] - in[4]) * 8192;
     const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
     tmp0 = in[7]; tmp1 = in[5]; tmp2 = in[3]; tmp3 = in[1];
     z1 = tmp0 + tmp3; z2 = tmp1 + tmp2; z3 = tmp0 + tmp2;
     int z4 = tmp1 + tmp3;
-    const int z5 = (z3 + z4) * 9633;
-    tmp0 *= 2446; tmp1 *= 16819; tmp2 *= 25172; tmp3 *= 12299;
-    z1 *= -7373; z2 *= -20995; z3 *= -16069; z4 *= -3196;
+    const int z5 = (z3 + z4) * kFix1_175875602;
+    tmp0 *= kFix0_298631336; tmp1 *= kFix2_053119869; tmp2 *= kFix3_072711026; tmp3 *= kFix1_501321110;
+    z1 *= -kFix0_899976223; z2 *= -kFix2_562915447; z3 *= -kFix1_961570560; z4 *= -kFix0_390180644;
     z3 += z5; z4 += z5;
     tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;
     const int half = 1 << (shift - 1);
@@ -303,31 +286,8 @@ __host__ __device__ __forceinline__ void idct_islow_1d(const int in[8], int out[
     out[3] = (tmp13 + tmp0 + half) >> shift; out[4] = (tmp13 - tmp0 + half) >> shift;
 }
 
-// what the kernels derive from a descriptor (the host check derives the same)
-struct jpeg_geometry {
-    int mcus_x, mcus_y;
-    int bw[3], bh[3];           // blocks per row / column of each component plane (padded to whole MCUs)
-    int nblocks;                // all components
-};
 __host__ __device__ __forceinline__ jpeg_geometry jpeg_geom(const ssd_jpeg_desc& d) {
-    jpeg_geometry g;
-    g.mcus_x = (d.W + 8 * d.h_samp - 1) / (8 * d.h_samp);
-    g.mcus_y = (d.H + 8 * d.v_samp - 1) / (8 * d.v_samp);
-    g.bw[0] = g.mcus_x * d.h_samp; g.bh[0] = g.mcus_y * d.v_samp;
-    g.bw[1] = g.bw[2] = g.mcus_x; g.bh[1] = g.bh[2] = g.mcus_y;
-    g.nblocks = g.bw[0] * g.bh[0] + (d.components == 3 ? 2 * g.mcus_x * g.mcus_y : 0);
-    return g;
-}
-
-// the image whose [start, next start) holds `index`: the last b with start(b) <= index (empty ranges are skipped)
-template <typename F>
-__device__ __forceinline__ int find_image(const int B, const int index, F start) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (start(mid) <= index) lo = mid; else hi = mid - 1;
-    }
-    return lo;
+    return jpeg_geom(d.H, d.W, d.h_samp, d.v_samp, d.components);
 }
 
 // Kernel 1: dequantise + inverse DCT.  One index space of 8x8 blocks over the whole batch (desc[b].block_start is the
@@ -349,9 +309,7 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const unsigned char* __r
         d = desc[b];
         local = blk - d.block_start;
         const short* coef = reinterpret_cast<const short*>(packed + d.coef_offset) + (long)local * 64;
-        const jpeg_geometry g = jpeg_geom(d);
-        const int n0 = g.bw[0] * g.bh[0], n1 = g.mcus_x * g.mcus_y;
-        const int comp = local < n0 ? 0 : (local < n0 + n1 ? 1 : 2);
+        const int comp = jpeg_block(jpeg_geom(d), local).comp;
         const unsigned short* q = reinterpret_cast<const unsigned short*>(packed + d.quant_offset) + comp * 64;
         int in[8], out[8];
 #pragma unroll
@@ -362,13 +320,7 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const unsigned char* __r
     }
     __syncthreads();
     if (live) {
-        const jpeg_geometry g = jpeg_geom(d);
-        const int n0 = g.bw[0] * g.bh[0], n1 = g.mcus_x * g.mcus_y;
-        const int comp = local < n0 ? 0 : (local < n0 + n1 ? 1 : 2);
-        const int inplane = local - (comp == 0 ? 0 : (comp == 1 ? n0 : n0 + n1));
-        const int bw = g.bw[comp];
-        const int by = inplane / bw, bx = inplane - by * bw;
-        const long plane_at = d.plane_offset + (comp == 0 ? 0L : (long)n0 * 64 + (long)(comp - 1) * n1 * 64);
+        const jpeg_block_place p = jpeg_block(jpeg_geom(d), local);
         int in[8], out[8];
 #pragma unroll
         for (int c = 0; c < 8; ++c) in[c] = ws[slot][j][c];
@@ -379,7 +331,7 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const unsigned char* __r
             lo |= (unsigned)idct_range_limit(out[c]) << (8 * c);
             hi |= (unsigned)idct_range_limit(out[c + 4]) << (8 * c);
         }
-        *reinterpret_cast<uint2*>(planes + plane_at + ((long)(by * 8 + j) * bw + bx) * 8) = make_uint2(lo, hi);
+        *reinterpret_cast<uint2*>(planes + (d.plane_offset + p.plane_at) + ((long)(p.by * 8 + j) * p.bw + p.bx) * 8) = make_uint2(lo, hi);
     }
 }
 
@@ -434,9 +386,9 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const unsigned char* __
         }
     } else {
         const jpeg_geometry g = jpeg_geom(d);
-        const int ypitch = g.bw[0] * 8, cpitch = g.mcus_x * 8;
+        const int ypitch = g.bw0 * 8, cpitch = g.mcus_x * 8;
         const unsigned char* py = planes + d.plane_offset;
-        const unsigned char* pcb = py + (long)g.bw[0] * g.bh[0] * 64;
+        const unsigned char* pcb = py + (long)g.bw0 * g.bh0 * 64;
         const unsigned char* pcr = pcb + (long)g.mcus_x * g.mcus_y * 64;
         const int cw = (d.W + d.h_samp - 1) / d.h_samp, ch = (d.H + d.v_samp - 1) / d.v_samp;
         int y = p0 / d.W, x = p0 - y * d.W;
@@ -468,13 +420,10 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const unsigned char* __
     }
 }
 
-static inline size_t jpeg_round16(const size_t v) { return (v + 15) & ~(size_t)15; }
-static inline bool jpeg_desc_shape_ok(const ssd_jpeg_desc& d) {
-    return d.H >= 1 && d.H <= kJpegMaxSide && d.W >= 1 && d.W <= kJpegMaxSide;
-}
+static inline bool jpeg_desc_shape_ok(const ssd_jpeg_desc& d) { return image_side_ok(d.H) && image_side_ok(d.W); }
 static inline bool jpeg_desc_sampling_ok(const ssd_jpeg_desc& d) {
     if (d.components == 1) return d.h_samp == 1 && d.v_samp == 1;
-    return d.components == 3 && ((d.h_samp == 1 && d.v_samp == 1) || (d.h_samp == 2 && d.v_samp == 1) || (d.h_samp == 2 && d.v_samp == 2));
+    return d.components == 3 && jpeg_sampling_ok(d.h_samp, d.v_samp);
 }
 
 }  // namespace ssd
@@ -538,7 +487,7 @@ extern "C" size_t ssd_jpeg_decode_workspace_bytes(const struct ssd_jpeg_desc* de
     for (int b = 0; b < B; ++b) {
         const ssd_jpeg_desc& d = desc_host[b];
         if (d.kind == SSD_JPEG_COEFFICIENTS && jpeg_desc_shape_ok(d) && jpeg_desc_sampling_ok(d))
-            total += jpeg_round16((size_t)jpeg_geom(d).nblocks * 64);
+            total += align_up((size_t)jpeg_geom(d).nblocks * 64, 16);
     }
     return total;
 }
@@ -558,28 +507,24 @@ extern "C" int ssd_jpeg_decode(const unsigned char* packed_dev, size_t bytes, co
         const ssd_jpeg_desc& d = desc_host[b];
         const ssd_image_desc& o = out_desc_host[b];
         SSD_CHECK_ARG(d.kind == SSD_JPEG_COEFFICIENTS || d.kind == SSD_JPEG_RAW, "ssd_jpeg_decode: image %d: kind %d", b, d.kind);
-        SSD_UNSUPPORTED_IF(!jpeg_desc_shape_ok(d), "ssd_jpeg_decode: image %d is %d x %d, outside 1..%d", b, d.H, d.W, kJpegMaxSide);
+        SSD_UNSUPPORTED_IF(!jpeg_desc_shape_ok(d), "ssd_jpeg_decode: image %d is %d x %d, outside 1..%d", b, d.H, d.W, kMaxImageSide);
         SSD_CHECK_ARG(o.H == d.H && o.W == d.W, "ssd_jpeg_decode: image %d: the output descriptor has another size", b);
         const size_t pixels = (size_t)d.H * d.W * 3;
-        SSD_CHECK_ARG(o.src_offset >= 0 && (o.src_offset & 15) == 0 && (size_t)o.src_offset >= rgb_end &&
-                          (size_t)o.src_offset + pixels <= rgb_bytes,
+        SSD_CHECK_ARG(region_ok(o.src_offset, pixels, rgb_bytes, 16, &rgb_end),
                       "ssd_jpeg_decode: image %d: output outside rgb_dev, misaligned or overlapping", b);
-        rgb_end = (size_t)o.src_offset + pixels;
         SSD_CHECK_ARG(d.coef_offset >= 0 && (d.coef_offset & 15) == 0, "ssd_jpeg_decode: image %d: offset not a multiple of 16", b);
         SSD_CHECK_ARG(d.block_start == blocks && d.item_start == items, "ssd_jpeg_decode: image %d: block_start / item_start are not the running sums", b);
         if (d.kind == SSD_JPEG_RAW) {
-            SSD_CHECK_ARG((size_t)d.coef_offset + pixels <= bytes, "ssd_jpeg_decode: image %d lies outside the packed buffer", b);
+            SSD_CHECK_ARG(region_ok(d.coef_offset, pixels, bytes, 16), "ssd_jpeg_decode: image %d lies outside the packed buffer", b);
         } else {
             SSD_UNSUPPORTED_IF(!jpeg_desc_sampling_ok(d), "ssd_jpeg_decode: image %d: %d components sampled %dx%d", b, d.components,
                                d.h_samp, d.v_samp);
             const size_t nb = (size_t)jpeg_geom(d).nblocks;
-            SSD_CHECK_ARG((size_t)d.coef_offset + nb * 128 <= bytes, "ssd_jpeg_decode: image %d lies outside the packed buffer", b);
-            SSD_CHECK_ARG(d.quant_offset >= 0 && (d.quant_offset & 15) == 0 && (size_t)d.quant_offset + 384 <= bytes,
+            SSD_CHECK_ARG(region_ok(d.coef_offset, nb * 128, bytes, 16), "ssd_jpeg_decode: image %d lies outside the packed buffer", b);
+            SSD_CHECK_ARG(region_ok(d.quant_offset, 384, bytes, 16),
                           "ssd_jpeg_decode: image %d: quantisation tables outside the packed buffer or misaligned", b);
-            SSD_CHECK_ARG(workspace_dev && d.plane_offset >= 0 && (d.plane_offset & 15) == 0 && (size_t)d.plane_offset >= plane_end &&
-                              (size_t)d.plane_offset + nb * 64 <= workspace_bytes,
+            SSD_CHECK_ARG(workspace_dev && region_ok(d.plane_offset, nb * 64, workspace_bytes, 16, &plane_end),
                           "ssd_jpeg_decode: image %d: planes outside the workspace, misaligned or overlapping", b);
-            plane_end = (size_t)d.plane_offset + nb * 64;
             blocks += (long)nb;
         }
         items += ((long)d.H * d.W + 3) / 4;

@@ -9,18 +9,12 @@
 //          threads call them in parallel).
 #include <cstring>
 
-#include "common.h"
+#include "ssd_jpeg_common.h"
 
 namespace ssd {
 
 // ---------------------------------------------------------------------------------------------------------------------
 // host: tables of ITU-T T.81 Annex K
-
-static const unsigned char kEncZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-static const int kEncMaxSide = 16384;
 
 static const unsigned char kStdQuant[2][64] = {
     {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
@@ -80,25 +74,15 @@ static void enc_build_huff(enc_huff& t, const std_huff& s) {
     }
 }
 
-// what an H x W image with h x v luma sampling looks like as a struct ssd_jpeg_info (ssd_jpeg_parse derives the same)
+// what an H x W image with h x v luma sampling looks like as a struct ssd_jpeg_info (ssd_jpeg_parse fills in the same)
 static int enc_fill_info(const int width, const int height, const int hs, const int vs, ssd_jpeg_info& o) {
     memset(&o, 0, sizeof(o));
-    SSD_UNSUPPORTED_IF(width < 1 || width > kEncMaxSide || height < 1 || height > kEncMaxSide, "ssd_jpeg_encode: %d x %d, outside 1..%d",
-                       height, width, kEncMaxSide);
-    SSD_UNSUPPORTED_IF(!((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2)),
-                       "ssd_jpeg_encode: luma sampling %dx%d (1x1, 2x1 and 2x2 only)", hs, vs);
+    SSD_UNSUPPORTED_IF(!image_side_ok(width) || !image_side_ok(height), "ssd_jpeg_encode: %d x %d, outside 1..%d", height, width,
+                       kMaxImageSide);
+    SSD_UNSUPPORTED_IF(!jpeg_sampling_ok(hs, vs), "ssd_jpeg_encode: luma sampling %dx%d (1x1, 2x1 and 2x2 only)", hs, vs);
     o.width = width; o.height = height; o.components = 3;
-    o.mcus_x = (width + 8 * hs - 1) / (8 * hs);
-    o.mcus_y = (height + 8 * vs - 1) / (8 * vs);
-    long long bytes = 0;
-    for (int c = 0; c < 3; ++c) {
-        o.h_samp[c] = c ? 1 : hs; o.v_samp[c] = c ? 1 : vs; o.quant_index[c] = c ? 1 : 0;
-        o.blocks_w[c] = o.mcus_x * o.h_samp[c];
-        o.blocks_h[c] = o.mcus_y * o.v_samp[c];
-        o.coef_offset[c] = bytes;
-        bytes += (long long)o.blocks_w[c] * o.blocks_h[c] * 128;
-    }
-    o.coef_bytes = bytes;
+    for (int c = 0; c < 3; ++c) { o.h_samp[c] = c ? 1 : hs; o.v_samp[c] = c ? 1 : vs; o.quant_index[c] = c ? 1 : 0; }
+    jpeg_complete_info(o);
     return SSD_OK;
 }
 
@@ -163,7 +147,7 @@ static int enc_block(byte_writer& w, const enc_huff& dc, const enc_huff& ac, con
     }
     int run = 0;
     for (int k = 1; k < 64; ++k) {
-        const int v = coef[kEncZigzag[k]];
+        const int v = coef[kZigzag[k]];
         if (v == 0) { ++run; continue; }
         for (; run > 15; run -= 16) w.put(ac.code[0xF0], ac.len[0xF0]);
         s = enc_category(v);
@@ -180,32 +164,8 @@ static int enc_block(byte_writer& w, const enc_huff& dc, const enc_huff& ac, con
 // ---------------------------------------------------------------------------------------------------------------------
 // device
 
-// what the kernels derive from a descriptor (the host check derives the same)
-struct enc_geometry {
-    int mcus_x, mcus_y;
-    int n0, n1;                 // blocks of the luma plane / of one chroma plane (padded to whole MCUs)
-    int nblocks, nitems;
-};
-__host__ __device__ __forceinline__ enc_geometry enc_geom(const ssd_jpeg_enc_desc& d) {
-    enc_geometry g;
-    g.mcus_x = (d.W + 8 * d.h_samp - 1) / (8 * d.h_samp);
-    g.mcus_y = (d.H + 8 * d.v_samp - 1) / (8 * d.v_samp);
-    g.n1 = g.mcus_x * g.mcus_y;
-    g.n0 = g.n1 * d.h_samp * d.v_samp;
-    g.nblocks = g.n0 + 2 * g.n1;
-    g.nitems = g.n1 * 16;       // four chroma samples each: 2 per MCU and row, 8 rows
-    return g;
-}
-
-// the image whose [start, next start) holds `index`: the last b with start(b) <= index
-template <typename F>
-__device__ __forceinline__ int enc_find_image(const int B, const int index, F start) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (start(mid) <= index) lo = mid; else hi = mid - 1;
-    }
-    return lo;
+__host__ __device__ __forceinline__ jpeg_geometry jpeg_geom(const ssd_jpeg_enc_desc& d) {
+    return jpeg_geom(d.H, d.W, d.h_samp, d.v_samp, 3);
 }
 
 __device__ __forceinline__ void enc_store(unsigned char* p, const unsigned (&w)[1]) { *reinterpret_cast<unsigned*>(p) = w[0]; }
@@ -216,7 +176,7 @@ __device__ __forceinline__ void enc_store(unsigned char* p, const unsigned (&w)[
 // only up to a whole row group, and below that the last DOWNSAMPLED row is repeated (chroma row ch - 1, luma row H - 1).
 template <int HS, int VS>
 __device__ __forceinline__ void enc_color_item(const unsigned char* __restrict__ src, const ssd_jpeg_enc_desc& d,
-                                               const enc_geometry& g, const int cy, const int ix, unsigned char* __restrict__ py) {
+                                               const jpeg_geometry& g, const int cy, const int ix, unsigned char* __restrict__ py) {
     constexpr int NX = 4 * HS;
     const int ch = (d.H + VS - 1) / VS;
     const bool below = cy > ch - 1;
@@ -269,9 +229,9 @@ __global__ __launch_bounds__(256) void jpeg_enc_color_kernel(const unsigned char
                                                             const int total_items, unsigned char* __restrict__ planes) {
     const int item = blockIdx.x * 256 + threadIdx.x;
     if (item >= total_items) return;
-    const int b = enc_find_image(B, item, [&](const int i) { return desc[i].item_start; });
+    const int b = find_image(B, item, [&](const int i) { return desc[i].item_start; });
     const ssd_jpeg_enc_desc d = desc[b];
-    const enc_geometry g = enc_geom(d);
+    const jpeg_geometry g = jpeg_geom(d);
     const int local = item - d.item_start;
     const int per_row = g.mcus_x * 2;
     const int cy = local / per_row, ix = local - cy * per_row;
@@ -292,14 +252,14 @@ __host__ __device__ __forceinline__ void fdct_islow_1d(const int d[8], int out[8
     constexpr int n = FIRST ? 11 : 15, half = 1 << (n - 1);
     if (FIRST) { out[0] = (tmp10 + tmp11) << 2; out[4] = (tmp10 - tmp11) << 2; }
     else { out[0] = (tmp10 + tmp11 + 2) >> 2; out[4] = (tmp10 - tmp11 + 2) >> 2; }
-    int z1 = (tmp12 + tmp13) * 4433;
-    out[2] = (z1 + tmp13 * 6270 + half) >> n;
-    out[6] = (z1 - tmp12 * 15137 + half) >> n;
+    int z1 = (tmp12 + tmp13) * kFix0_541196100;
+    out[2] = (z1 + tmp13 * kFix0_765366865 + half) >> n;
+    out[6] = (z1 - tmp12 * kFix1_847759065 + half) >> n;
     z1 = tmp4 + tmp7;
     int z2 = tmp5 + tmp6, z3 = tmp4 + tmp6, z4 = tmp5 + tmp7;
-    const int z5 = (z3 + z4) * 9633;
-    tmp4 *= 2446; tmp5 *= 16819; tmp6 *= 25172; tmp7 *= 12299;
-    z1 *= -7373; z2 *= -20995; z3 = z3 * -16069 + z5; z4 = z4 * -3196 + z5;
+    const int z5 = (z3 + z4) * kFix1_175875602;
+    tmp4 *= kFix0_298631336; tmp5 *= kFix2_053119869; tmp6 *= kFix3_072711026; tmp7 *= kFix1_501321110;
+    z1 *= -kFix0_899976223; z2 *= -kFix2_562915447; z3 = z3 * -kFix1_961570560 + z5; z4 = z4 * -kFix0_390180644 + z5;
     out[7] = (tmp4 + z1 + z3 + half) >> n;
     out[5] = (tmp5 + z2 + z4 + half) >> n;
     out[3] = (tmp6 + z2 + z3 + half) >> n;
@@ -322,16 +282,12 @@ __global__ __launch_bounds__(256) void jpeg_enc_fdct_kernel(const unsigned char*
     ssd_jpeg_enc_desc d;
     int local = 0, comp = 0;
     if (live) {
-        const int b = enc_find_image(B, blk, [&](const int i) { return desc[i].block_start; });
+        const int b = find_image(B, blk, [&](const int i) { return desc[i].block_start; });
         d = desc[b];
         local = blk - d.block_start;
-        const enc_geometry g = enc_geom(d);
-        comp = local < g.n0 ? 0 : (local < g.n0 + g.n1 ? 1 : 2);
-        const int inplane = local - (comp == 0 ? 0 : (comp == 1 ? g.n0 : g.n0 + g.n1));
-        const int bw = comp == 0 ? g.mcus_x * d.h_samp : g.mcus_x;
-        const int by = inplane / bw, bx = inplane - by * bw;
-        const long plane_at = d.plane_offset + (comp == 0 ? 0L : (long)g.n0 * 64 + (long)(comp - 1) * g.n1 * 64);
-        const uint2 s = *reinterpret_cast<const uint2*>(planes + plane_at + ((long)(by * 8 + j) * bw + bx) * 8);
+        const jpeg_block_place p = jpeg_block(jpeg_geom(d), local);
+        comp = p.comp;
+        const uint2 s = *reinterpret_cast<const uint2*>(planes + (d.plane_offset + p.plane_at) + ((long)(p.by * 8 + j) * p.bw + p.bx) * 8);
         int in[8], out[8];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -372,13 +328,7 @@ __global__ __launch_bounds__(256) void jpeg_enc_fdct_kernel(const unsigned char*
     }
 }
 
-static inline size_t enc_round16(const size_t v) { return (v + 15) & ~(size_t)15; }
-static inline bool enc_desc_shape_ok(const ssd_jpeg_enc_desc& d) {
-    return d.H >= 1 && d.H <= kEncMaxSide && d.W >= 1 && d.W <= kEncMaxSide;
-}
-static inline bool enc_desc_sampling_ok(const ssd_jpeg_enc_desc& d) {
-    return (d.h_samp == 1 && d.v_samp == 1) || (d.h_samp == 2 && d.v_samp == 1) || (d.h_samp == 2 && d.v_samp == 2);
-}
+static inline bool enc_desc_shape_ok(const ssd_jpeg_enc_desc& d) { return image_side_ok(d.H) && image_side_ok(d.W); }
 
 }  // namespace ssd
 
@@ -428,7 +378,7 @@ extern "C" int ssd_jpeg_entropy_encode(const short* coef, const struct ssd_jpeg_
     w.be16(0);                                                                     // no thumbnail
     for (int t = 0; t < 2; ++t) {
         w.be16(0xFFDB); w.be16(67); w.byte((unsigned)t);
-        for (int i = 0; i < 64; ++i) w.byte(o.quant[t][kEncZigzag[i]]);
+        for (int i = 0; i < 64; ++i) w.byte(o.quant[t][kZigzag[i]]);
     }
     w.be16(0xFFC0); w.be16(17); w.byte(8); w.be16((unsigned)o.height); w.be16((unsigned)o.width); w.byte(3);
     for (int c = 0; c < 3; ++c) { w.byte((unsigned)c + 1); w.byte((unsigned)((o.h_samp[c] << 4) | o.v_samp[c])); w.byte((unsigned)o.quant_index[c]); }
@@ -474,7 +424,7 @@ extern "C" size_t ssd_jpeg_forward_workspace_bytes(const struct ssd_jpeg_enc_des
     size_t total = 0;
     for (int b = 0; b < B; ++b) {
         const ssd_jpeg_enc_desc& d = desc_host[b];
-        if (enc_desc_shape_ok(d) && enc_desc_sampling_ok(d)) total += enc_round16((size_t)enc_geom(d).nblocks * 64);
+        if (enc_desc_shape_ok(d) && jpeg_sampling_ok(d.h_samp, d.v_samp)) total += align_up((size_t)jpeg_geom(d).nblocks * 64, 16);
     }
     return total;
 }
@@ -491,25 +441,20 @@ extern "C" int ssd_jpeg_forward(const unsigned char* rgb_dev, size_t rgb_bytes, 
     size_t plane_end = 0, coef_end = 0;
     for (int b = 0; b < B; ++b) {
         const ssd_jpeg_enc_desc& d = desc_host[b];
-        SSD_UNSUPPORTED_IF(!enc_desc_shape_ok(d), "ssd_jpeg_forward: image %d is %d x %d, outside 1..%d", b, d.H, d.W, kEncMaxSide);
-        SSD_UNSUPPORTED_IF(!enc_desc_sampling_ok(d), "ssd_jpeg_forward: image %d: luma sampling %dx%d (1x1, 2x1 and 2x2 only)", b, d.h_samp, d.v_samp);
-        const enc_geometry g = enc_geom(d);
+        SSD_UNSUPPORTED_IF(!enc_desc_shape_ok(d), "ssd_jpeg_forward: image %d is %d x %d, outside 1..%d", b, d.H, d.W, kMaxImageSide);
+        SSD_UNSUPPORTED_IF(!jpeg_sampling_ok(d.h_samp, d.v_samp), "ssd_jpeg_forward: image %d: luma sampling %dx%d (1x1, 2x1 and 2x2 only)", b, d.h_samp, d.v_samp);
+        const jpeg_geometry g = jpeg_geom(d);
         const size_t nb = (size_t)g.nblocks;
-        SSD_CHECK_ARG(d.src_offset >= 0 && (size_t)d.src_offset + (size_t)d.H * d.W * 3 <= rgb_bytes,
-                      "ssd_jpeg_forward: image %d lies outside rgb_dev", b);
-        SSD_CHECK_ARG(d.coef_offset >= 0 && (d.coef_offset & 15) == 0 && (size_t)d.coef_offset >= coef_end &&
-                          (size_t)d.coef_offset + nb * 128 <= coef_bytes,
+        SSD_CHECK_ARG(region_ok(d.src_offset, (size_t)d.H * d.W * 3, rgb_bytes, 1), "ssd_jpeg_forward: image %d lies outside rgb_dev", b);
+        SSD_CHECK_ARG(region_ok(d.coef_offset, nb * 128, coef_bytes, 16, &coef_end),
                       "ssd_jpeg_forward: image %d: coefficients outside coef_dev, misaligned or overlapping", b);
-        coef_end = (size_t)d.coef_offset + nb * 128;
-        SSD_CHECK_ARG(d.quant_offset >= 0 && (d.quant_offset & 15) == 0 && (size_t)d.quant_offset + 256 <= tables_bytes,
+        SSD_CHECK_ARG(region_ok(d.quant_offset, 256, tables_bytes, 16),
                       "ssd_jpeg_forward: image %d: quantisation tables outside tables_dev or misaligned", b);
-        SSD_CHECK_ARG(d.plane_offset >= 0 && (d.plane_offset & 15) == 0 && (size_t)d.plane_offset >= plane_end &&
-                          (size_t)d.plane_offset + nb * 64 <= workspace_bytes,
+        SSD_CHECK_ARG(region_ok(d.plane_offset, nb * 64, workspace_bytes, 16, &plane_end),
                       "ssd_jpeg_forward: image %d: planes outside the workspace, misaligned or overlapping", b);
-        plane_end = (size_t)d.plane_offset + nb * 64;
         SSD_CHECK_ARG(d.block_start == blocks && d.item_start == items, "ssd_jpeg_forward: image %d: block_start / item_start are not the running sums", b);
         blocks += (long)nb;
-        items += g.nitems;
+        items += g.n1 * 16;                                                   // four chroma samples each: 2 per MCU and row, 8 rows
         SSD_UNSUPPORTED_IF(blocks >= (1L << 31) - 64 || items >= (1L << 31) - 512, "ssd_jpeg_forward: the batch is too large for one call (image %d)", b);
     }
     hipLaunchKernelGGL(jpeg_enc_color_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rgb_dev,

@@ -199,6 +199,7 @@ _SIGNATURES = {
     "ssd_dwconv3x3_backward": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 8 + [vp, vp, vp, ctypes.c_size_t, vp]),
 }
 
+MAX_IMAGE_SIDE = 16384          # csrc/common.h kMaxImageSide: the largest height / width the image I/O paths take
 RESIZE_DESC_DTYPE = np.dtype([("src_offset", "<i8"), ("tmp_offset", "<i8")] + [(n, "<i4") for n in (
     "H", "W", "h_bounds", "h_k", "h_ksize", "v_bounds", "v_k", "v_ksize")])
 assert RESIZE_DESC_DTYPE.itemsize == ctypes.sizeof(ResizeDesc) == 48

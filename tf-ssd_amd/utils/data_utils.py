@@ -151,7 +151,95 @@ def lanczos_coefficients(in_size, out_size):
     return bounds, k
 
 
-_resize_staging = {}
+# ---------------------------------------------------------------------------------------------------------------------
+# What the batch functions below share.  Every call's input travels as ONE packed buffer -- descriptors | tables |
+# payload, each part at a multiple of 16 bytes -- written into pinned staging memory and uploaded with one copy.
+
+def _round16(n):
+    """THE packing rule: every part of a packed buffer, and every image inside one, begins at a multiple of 16 bytes."""
+    return (n + 15) & ~15
+
+
+def _place(sizes, at=0):
+    """Parts of ``sizes`` bytes one after the other from ``at`` on, each begun at a multiple of 16: ``(where each
+    begins, where the last one ends, rounded up)``."""
+    starts = []
+    for n in sizes:
+        starts.append(_round16(at))
+        at = starts[-1] + int(n)
+    return starts, _round16(at)
+
+
+def _put(host, at, a):
+    """``a``'s bytes (descriptor records, an int table, uint8 pixels of any strides) to ``host[at:]``."""
+    if a.dtype != np.uint8:
+        a = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    host[at:at + a.size].reshape(a.shape)[...] = a
+
+
+def _put_images(host, at, offsets, arrays):
+    for offset, a in zip(offsets, arrays):
+        _put(host, at + int(offset), a)
+
+
+def _sizes_ok(*sides):
+    import ssd_hip as _h
+    return all(1 <= v <= _h.MAX_IMAGE_SIDE for v in sides)
+
+
+def _ragged_arrays(images):
+    """The uint8 ``[H,W,C]`` NumPy arrays of a batch and their common ``C`` (3 for an empty batch)."""
+    import torch
+    arrays = []
+    for im in images:
+        a = im.detach().cpu().numpy() if isinstance(im, torch.Tensor) else np.asarray(im)
+        if a.dtype != np.uint8 or a.ndim != 3:
+            raise ValueError("images must be uint8 [H,W,3], got %s %s" % (a.dtype, tuple(a.shape)))
+        arrays.append(a)
+    C = arrays[0].shape[2] if arrays else 3
+    if any(a.shape[2] != C for a in arrays):
+        raise ValueError("images of one batch must have the same number of channels")
+    return arrays, C
+
+
+def _check_out(out, shape, dtype, dev, name="out", create=False):
+    """``out`` if it is a contiguous device tensor of that shape and type (else ``ValueError``); for None a fresh one
+    when ``create``."""
+    import torch
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=dev) if create else None
+    if tuple(out.shape) != shape or out.dtype != dtype or out.device != dev or not out.is_contiguous():
+        raise ValueError("%s must be a contiguous %s device tensor %s" % (name, dtype, shape))
+    return out
+
+
+_staging = {}
+
+
+def _pinned_staging(kind, dev, nbytes):
+    """``[buffer, event]``: the device's pinned staging buffer of this ``kind`` ("upload" / "download"), at least
+    ``nbytes`` long, grown in powers of two from 1 MiB and kept between calls."""
+    import torch
+    import ssd_hip as _h
+    st = _staging.get((kind, dev.index))
+    if st is None or st[0].numel() < nbytes:
+        st = _staging[(kind, dev.index)] = [_h.pinned_empty((max(1 << (nbytes - 1).bit_length(), 1 << 20),), torch.uint8), None]
+    return st
+
+
+def _upload_packed(dev, total, fill):
+    """``fill(host)`` writes ``total`` bytes into the device's pinned staging buffer (reused once the previous batch's
+    copy has left it); ONE asynchronous copy on the current stream makes the device buffer."""
+    import torch
+    st = _pinned_staging("upload", dev, total)
+    if st[1] is not None:
+        st[1].synchronize()                                                       # the previous batch's copy has left the buffer
+    fill(st[0].numpy())
+    packed = torch.empty(total, dtype=torch.uint8, device=dev)
+    packed.copy_(st[0][:total], non_blocking=True)
+    st[1] = torch.cuda.Event()
+    st[1].record()
+    return packed
 
 
 def resize_lanczos_batch(images, final_height, final_width, out=None, out_u8=None):
@@ -163,27 +251,11 @@ def resize_lanczos_batch(images, final_height, final_width, out=None, out_u8=Non
     import torch
     import ssd_hip as _h
     fh, fw = int(final_height), int(final_width)
-    arrays = []
-    for im in images:
-        a = im.detach().cpu().numpy() if isinstance(im, torch.Tensor) else np.asarray(im)
-        if a.dtype != np.uint8 or a.ndim != 3:
-            raise ValueError("images must be uint8 [H,W,3], got %s %s" % (a.dtype, tuple(a.shape)))
-        arrays.append(a)
-    B = len(arrays)
-    C = arrays[0].shape[2] if B else 3
-    if any(a.shape[2] != C for a in arrays):
-        raise ValueError("images of one batch must have the same number of channels")
-    dev = _h.device()
-    for name, t in (("out", out), ("out_u8", out_u8)):
-        want = torch.float32 if name == "out" else torch.uint8
-        if t is not None and (tuple(t.shape) != (B, fh, fw, C) or t.dtype != want or t.device != dev or not t.is_contiguous()):
-            raise ValueError("%s must be a contiguous %s device tensor %s" % (name, want, (B, fh, fw, C)))
-    if out is None:
-        out = torch.empty((B, fh, fw, C), dtype=torch.float32, device=dev)
-    lib = _h.lib()
-    if B == 0 or C != 3 or not (1 <= fh <= 16384 and 1 <= fw <= 16384):           # nothing to pack: the library answers
-        _h.check(lib.ssd_resize_lanczos(None, 0, None, 0, None, None, B, C, fh, fw, _h.ptr(out), _h.ptr(out_u8), None, 0,
-                                        _h.stream()), "resize_lanczos_batch")
+    arrays, C = _ragged_arrays(images)
+    B, dev = len(arrays), _h.device()
+    out = _check_out(out, (B, fh, fw, C), torch.float32, dev, create=True)
+    _check_out(out_u8, (B, fh, fw, C), torch.uint8, dev, "out_u8")
+    if _lanczos_nothing_to_pack(B, C, fh, fw, out, out_u8, "resize_lanczos_batch"):
         return out
     layout = _lanczos_layout(arrays, fh, fw)
     packed = _upload_packed(dev, layout["total"], lambda host: _lanczos_fill(host, arrays, layout))
@@ -191,30 +263,24 @@ def resize_lanczos_batch(images, final_height, final_width, out=None, out_u8=Non
     return out
 
 
-def _upload_packed(dev, total, fill):
-    """``fill(host)`` writes ``total`` bytes into the device's pinned staging buffer (grown in powers of two, reused once
-    the previous batch's copy has left it); ONE asynchronous copy on the current stream makes the device buffer."""
-    import torch
+def _lanczos_nothing_to_pack(B, C, fh, fw, out, out_u8, what):
+    """An empty batch, or one the library refuses by its sizes alone: the library answers, nothing is packed."""
     import ssd_hip as _h
-    st = _resize_staging.get(dev.index)
-    if st is None or st[0].numel() < total:
-        size = max(1 << (total - 1).bit_length(), 1 << 20)
-        st = _resize_staging[dev.index] = [_h.pinned_empty((size,), torch.uint8), None]
-    if st[1] is not None:
-        st[1].synchronize()                                                       # the previous batch's copy has left the buffer
-    fill(st[0].numpy())
-    packed = torch.empty(total, dtype=torch.uint8, device=dev)
-    packed.copy_(st[0][:total], non_blocking=True)
-    st[1] = torch.cuda.Event()
-    st[1].record()
-    return packed
+    if B > 0 and C == 3 and _sizes_ok(fh, fw):
+        return False
+    _h.check(_h.lib().ssd_resize_lanczos(None, 0, None, 0, None, None, B, C, fh, fw, _h.ptr(out), _h.ptr(out_u8), None, 0,
+                                         _h.stream()), what)
+    return True
 
 
-def _lanczos_layout(arrays, fh, fw):
+def _lanczos_layout(arrays, fh, fw, src_offsets=None):
     """Where everything one ``ssd_resize_lanczos`` call reads sits in ONE buffer: descriptors | coefficient tables (int32,
-    one per distinct (in, out) pair of the batch) | images, each part at a multiple of 16 bytes."""
+    one per distinct (in, out) pair of the batch) | images, each part at a multiple of 16 bytes.  ``arrays``: the images,
+    or only their shapes.  ``src_offsets``: the pixels are on the device already, image b at that offset of a buffer of
+    its own (``decode_jpeg_batch``'s), and this buffer ends after the tables."""
     import ssd_hip as _h
-    B = len(arrays)
+    shapes = [tuple(getattr(a, "shape", a)) for a in arrays]
+    B = len(shapes)
     desc = np.zeros(B, _h.RESIZE_DESC_DTYPE)
     tables, table_at, n_ints = [], {}, 0
 
@@ -229,61 +295,49 @@ def _lanczos_layout(arrays, fh, fw):
         return table_at[key]
     pitch = _h.lib().ssd_resize_lanczos_pitch(fw)
     tmp_bytes = 0
-    for b, a in enumerate(arrays):
-        H, W = a.shape[:2]
+    for b, (H, W) in enumerate(s[:2] for s in shapes):
         desc[b]["H"], desc[b]["W"] = H, W
-        if min(H, W) < 1 or max(H, W) > 16384:
+        if not _sizes_ok(H, W):
             continue                                                              # the library reports it (unsupported)
         if W != fw:
             desc[b]["h_bounds"], desc[b]["h_k"], desc[b]["h_ksize"] = table(W, fw)
             desc[b]["tmp_offset"] = tmp_bytes
-            tmp_bytes += (H * pitch + 15) & ~15
+            tmp_bytes += _round16(H * pitch)
         if H != fh:
             desc[b]["v_bounds"], desc[b]["v_k"], desc[b]["v_ksize"] = table(H, fh)
-    tables_at = (desc.nbytes + 15) & ~15
-    src_at = (tables_at + 4 * n_ints + 15) & ~15
+    (_, tables_at), src_at = _place([desc.nbytes, 4 * n_ints])
     total = src_at
-    for b, a in enumerate(arrays):
-        desc[b]["src_offset"] = total - src_at
-        total += (a.size + 15) & ~15
+    if src_offsets is None:
+        starts, total = _place([int(np.prod(s)) for s in shapes], src_at)
+        src_offsets = [at - src_at for at in starts]
+    desc["src_offset"] = src_offsets
     assert tmp_bytes == _h.lib().ssd_resize_lanczos_workspace_bytes(desc.ctypes.data, B, fh, fw)
     return {"desc": desc, "tables": tables, "n_ints": n_ints, "tables_at": tables_at, "src_at": src_at, "total": total,
             "tmp_bytes": tmp_bytes, "size": (fh, fw)}
 
 
 def _lanczos_fill(host, arrays, layout):
-    """Write the batch into ``host`` (uint8 NumPy view of at least ``layout["total"]`` bytes)."""
-    desc = layout["desc"]
-    host[:desc.nbytes] = desc.view(np.uint8)
+    """Write the batch into ``host`` (uint8 NumPy view of at least ``layout["total"]`` bytes); ``arrays``: the images the
+    layout was made for, or none when their pixels are on the device already."""
+    _put(host, 0, layout["desc"])
     at = layout["tables_at"]
     for tb in layout["tables"]:
-        host[at:at + tb.nbytes] = tb.reshape(-1).view(np.uint8)
+        _put(host, at, tb)
         at += tb.nbytes
-    for b, a in enumerate(arrays):
-        at = layout["src_at"] + int(desc[b]["src_offset"])
-        host[at:at + a.size].reshape(a.shape)[...] = a
+    _put_images(host, layout["src_at"], layout["desc"]["src_offset"], arrays)
 
 
-def _lanczos_launch(packed, layout, out, out_u8=None):
-    """``ssd_resize_lanczos`` on a device copy ``packed`` of the filled buffer, on the current stream."""
+def _lanczos_launch(packed, layout, out, out_u8=None, src=None, what="resize_lanczos_batch"):
+    """``ssd_resize_lanczos`` on a device copy ``packed`` of the filled buffer, on the current stream.  ``src``: the
+    device buffer that holds the pixels when ``packed`` does not."""
     import ssd_hip as _h
     desc, (fh, fw) = layout["desc"], layout["size"]
     ws = _h.workspace(max(layout["tmp_bytes"], 16))
     base, src_at = packed.data_ptr(), layout["src_at"]
-    _h.check(_h.lib().ssd_resize_lanczos(base + src_at, layout["total"] - src_at, base + layout["tables_at"], layout["n_ints"],
+    src_ptr, src_bytes = (base + src_at, layout["total"] - src_at) if src is None else (_h.ptr(src), src.numel())
+    _h.check(_h.lib().ssd_resize_lanczos(src_ptr, src_bytes, base + layout["tables_at"], layout["n_ints"],
                                          desc.ctypes.data, base, len(desc), 3, fh, fw, _h.ptr(out), _h.ptr(out_u8),
-                                         _h.ptr(ws), ws.numel(), _h.stream()), "resize_lanczos_batch")
-
-
-def _ragged_arrays(images):
-    import torch
-    arrays = []
-    for im in images:
-        a = im.detach().cpu().numpy() if isinstance(im, torch.Tensor) else np.asarray(im)
-        if a.dtype != np.uint8 or a.ndim != 3:
-            raise ValueError("images must be uint8 [H,W,3], got %s %s" % (a.dtype, tuple(a.shape)))
-        arrays.append(a)
-    return arrays
+                                         _h.ptr(ws), ws.numel(), _h.stream()), what)
 
 
 def _ragged_layout(arrays):
@@ -291,21 +345,17 @@ def _ragged_layout(arrays):
     of 16 bytes (``src_offset`` counts from the first image)."""
     import ssd_hip as _h
     desc = np.zeros(len(arrays), _h.IMAGE_DESC_DTYPE)
-    src_at = (desc.nbytes + 15) & ~15
-    total = src_at
+    src_at = _round16(desc.nbytes)
+    starts, total = _place([a.size for a in arrays], src_at)
     for b, a in enumerate(arrays):
         desc[b]["H"], desc[b]["W"] = a.shape[:2]
-        desc[b]["src_offset"] = total - src_at
-        total += (a.size + 15) & ~15
+        desc[b]["src_offset"] = starts[b] - src_at
     return {"desc": desc, "src_at": src_at, "total": total}
 
 
 def _ragged_fill(host, arrays, layout):
-    desc = layout["desc"]
-    host[:desc.nbytes] = desc.view(np.uint8)
-    for b, a in enumerate(arrays):
-        at = layout["src_at"] + int(desc[b]["src_offset"])
-        host[at:at + a.size].reshape(a.shape)[...] = a
+    _put(host, 0, layout["desc"])
+    _put_images(host, layout["src_at"], layout["desc"]["src_offset"], arrays)
 
 
 def _ragged_launch(packed, layout, fh, fw, out):
@@ -325,18 +375,10 @@ def preprocess_ragged_batch(images, final_height, final_width, out=None):
     import torch
     import ssd_hip as _h
     fh, fw = int(final_height), int(final_width)
-    arrays = _ragged_arrays(images)
-    B = len(arrays)
-    C = arrays[0].shape[2] if B else 3
-    if any(a.shape[2] != C for a in arrays):
-        raise ValueError("images of one batch must have the same number of channels")
-    dev = _h.device()
-    if out is not None and (tuple(out.shape) != (B, fh, fw, C) or out.dtype != torch.float32 or out.device != dev
-                            or not out.is_contiguous()):
-        raise ValueError("%s must be a contiguous %s device tensor %s" % ("out", torch.float32, (B, fh, fw, C)))
-    if out is None:
-        out = torch.empty((B, fh, fw, C), dtype=torch.float32, device=dev)
-    if B == 0 or C != 3 or not (1 <= fh <= 16384 and 1 <= fw <= 16384):           # nothing to pack: the library answers
+    arrays, C = _ragged_arrays(images)
+    B, dev = len(arrays), _h.device()
+    out = _check_out(out, (B, fh, fw, C), torch.float32, dev, create=True)
+    if B == 0 or C != 3 or not _sizes_ok(fh, fw):                                   # nothing to pack: the library answers
         _h.check(_h.lib().ssd_preprocess_ragged(None, 0, None, None, B, C, fh, fw, _h.ptr(out), _h.stream()),
                  "preprocess_ragged_batch")
         return out
@@ -376,10 +418,16 @@ def _pillow_rgb(blob):
     return np.asarray(Image.open(io.BytesIO(blob)).convert("RGB"), dtype=np.uint8)
 
 
+_JPEG_SOI = b"\xff\xd8"
+
+
 def _jpeg_parse(blob):
-    """``ssd_hip.JpegInfo`` of a stream the library decodes, else None (unsupported or malformed: Pillow's business)."""
+    """``ssd_hip.JpegInfo`` of a stream the library decodes, else None (no JPEG at all, unsupported or malformed:
+    Pillow's business)."""
     import ctypes
     import ssd_hip as _h
+    if blob[:2] != _JPEG_SOI:
+        return None
     info = _h.JpegInfo()
     rc = _h.lib().ssd_jpeg_parse(blob, len(blob), ctypes.byref(info))
     return info if rc == 0 else None
@@ -396,7 +444,7 @@ def jpeg_host_decode(blob, fallback=_pillow_rgb):
     memory of its own, or -- a stream the library calls unsupported or invalid, or no JPEG at all -- ``fallback(blob)``'s
     uint8 ``[H,W,3]`` pixels."""
     blob = bytes(blob)
-    info = _jpeg_parse(blob) if blob[:2] == b"\xff\xd8" else None
+    info = _jpeg_parse(blob)
     if info is None:
         return fallback(blob)
     coef = np.empty(int(info.coef_bytes) // 2, np.int16)
@@ -414,7 +462,7 @@ def _jpeg_items(blobs, fallback):
             items.append(x)
         elif isinstance(x, (bytes, bytearray, memoryview)):
             x = bytes(x)
-            info = _jpeg_parse(x) if x[:2] == b"\xff\xd8" else None
+            info = _jpeg_parse(x)
             items.append(JpegCoefficients(info, None, x) if info is not None else fallback(x))
         else:
             items.append(x)
@@ -435,26 +483,25 @@ def _jpeg_layout(items):
     B = len(items)
     desc = np.zeros(B, _h.JPEG_DESC_DTYPE)
     out_desc = np.zeros(B, _h.IMAGE_DESC_DTYPE)
-    out_at = (desc.nbytes + 15) & ~15
-    quant_at = (out_at + out_desc.nbytes + 15) & ~15
-    total = quant_at + 384 * B
+    quant_bytes = _h.JpegInfo.quant.size
+    (_, out_at, quant_at), payload_at = _place([desc.nbytes, out_desc.nbytes, quant_bytes * B])
+    coded = [isinstance(x, JpegCoefficients) for x in items]
+    starts, total = _place([int(x.info.coef_bytes) if c else x.size for x, c in zip(items, coded)], payload_at)
     blocks = n_items = rgb_bytes = plane_bytes = 0
     for b, x in enumerate(items):
         d = desc[b]
-        d["coef_offset"], d["block_start"], d["item_start"] = total, blocks, n_items
-        if isinstance(x, JpegCoefficients):
+        d["coef_offset"], d["block_start"], d["item_start"] = starts[b], blocks, n_items
+        if coded[b]:
             i = x.info
             d["kind"], d["H"], d["W"], d["components"] = _h.JPEG_COEFFICIENTS, i.height, i.width, i.components
             d["h_samp"], d["v_samp"] = i.h_samp[0], i.v_samp[0]
-            d["quant_offset"], d["plane_offset"] = quant_at + 384 * b, plane_bytes
-            total += (int(i.coef_bytes) + 15) & ~15
+            d["quant_offset"], d["plane_offset"] = quant_at + quant_bytes * b, plane_bytes
             blocks += int(i.coef_bytes) // 128
-            plane_bytes += (int(i.coef_bytes) // 2 + 15) & ~15
+            plane_bytes += _round16(int(i.coef_bytes) // 2)
         else:
             d["kind"], d["H"], d["W"], d["components"], d["h_samp"], d["v_samp"] = _h.JPEG_RAW, x.shape[0], x.shape[1], 3, 1, 1
-            total += (x.size + 15) & ~15
         out_desc[b]["H"], out_desc[b]["W"], out_desc[b]["src_offset"] = d["H"], d["W"], rgb_bytes
-        rgb_bytes += (int(d["H"]) * int(d["W"]) * 3 + 15) & ~15
+        rgb_bytes += _round16(int(d["H"]) * int(d["W"]) * 3)
         n_items += (int(d["H"]) * int(d["W"]) + 3) // 4
     assert plane_bytes == _h.lib().ssd_jpeg_decode_workspace_bytes(desc.ctypes.data, B)
     return {"desc": desc, "out_desc": out_desc, "out_at": out_at, "total": total, "rgb_bytes": rgb_bytes,
@@ -464,21 +511,21 @@ def _jpeg_layout(items):
 def _jpeg_fill(host, items, layout, failed):
     """Write the batch into ``host``; a stream still to be entropy-decoded is decoded straight into its place (the
     staging buffer is pinned memory).  Indices of streams the decoder refuses are appended to ``failed``."""
-    desc, out_desc = layout["desc"], layout["out_desc"]
-    host[:desc.nbytes] = desc.view(np.uint8)
-    host[layout["out_at"]:layout["out_at"] + out_desc.nbytes] = out_desc.view(np.uint8)
+    import ssd_hip as _h
+    desc = layout["desc"]
+    _put(host, 0, desc)
+    _put(host, layout["out_at"], layout["out_desc"])
+    quant = _h.JpegInfo.quant
     for b, x in enumerate(items):
         at = int(desc[b]["coef_offset"])
-        if isinstance(x, JpegCoefficients):
-            q = int(desc[b]["quant_offset"])
-            host[q:q + 384] = np.frombuffer(x.info, np.uint8)[120:504]          # struct ssd_jpeg_info.quant
-            n = int(x.info.coef_bytes)
-            if x.coef is not None:
-                host[at:at + n] = x.coef.view(np.uint8)
-            elif not _jpeg_entropy_into(x.blob, x.info, host.ctypes.data + at, n):
-                failed.append(b)
-        else:
-            host[at:at + x.size].reshape(x.shape)[...] = x
+        if not isinstance(x, JpegCoefficients):
+            _put(host, at, x)
+            continue
+        _put(host, int(desc[b]["quant_offset"]), np.frombuffer(x.info, np.uint8)[quant.offset:quant.offset + quant.size])
+        if x.coef is not None:
+            _put(host, at, x.coef)
+        elif not _jpeg_entropy_into(x.blob, x.info, host.ctypes.data + at, int(x.info.coef_bytes)):
+            failed.append(b)
 
 
 class JpegBatch(object):
@@ -533,11 +580,6 @@ def decode_jpeg_batch(blobs, out_u8=False, fallback=_pillow_rgb):
     return JpegBatch(images, rgb, out_desc, base + layout["out_at"], packed, [int(k) for k in desc["kind"]])
 
 
-def _check_out(out, shape, dtype, dev, name="out"):
-    if out is not None and (tuple(out.shape) != shape or out.dtype != dtype or out.device != dev or not out.is_contiguous()):
-        raise ValueError("%s must be a contiguous %s device tensor %s" % (name, dtype, shape))
-
-
 def preprocess_jpeg_batch(blobs, final_height, final_width, out=None, fallback=_pillow_rgb):
     """``preprocess_ragged_batch`` of the decoded files without the pixels ever being on the host: ``decode_jpeg_batch``,
     then ``ssd_preprocess_ragged`` on the device-resident images.  Bitwise ``preprocess_ragged_batch([Pillow's decode of
@@ -545,11 +587,8 @@ def preprocess_jpeg_batch(blobs, final_height, final_width, out=None, fallback=_
     import torch
     import ssd_hip as _h
     fh, fw = int(final_height), int(final_width)
-    dev = _h.device()
     B = len(blobs)
-    _check_out(out, (B, fh, fw, 3), torch.float32, dev)
-    if out is None:
-        out = torch.empty((B, fh, fw, 3), dtype=torch.float32, device=dev)
+    out = _check_out(out, (B, fh, fw, 3), torch.float32, _h.device(), create=True)
     jb = decode_jpeg_batch(blobs, fallback=fallback)
     _h.check(_h.lib().ssd_preprocess_ragged(_h.ptr(jb.rgb), jb.rgb.numel(), jb.desc.ctypes.data, jb.desc_ptr, B, 3, fh, fw,
                                             _h.ptr(out), _h.stream()), "preprocess_jpeg_batch")
@@ -565,26 +604,14 @@ def resize_lanczos_jpeg_batch(blobs, final_height, final_width, out=None, out_u8
     fh, fw = int(final_height), int(final_width)
     dev = _h.device()
     B = len(blobs)
-    _check_out(out, (B, fh, fw, 3), torch.float32, dev)
+    out = _check_out(out, (B, fh, fw, 3), torch.float32, dev, create=True)
     _check_out(out_u8, (B, fh, fw, 3), torch.uint8, dev, "out_u8")
-    if out is None:
-        out = torch.empty((B, fh, fw, 3), dtype=torch.float32, device=dev)
-    lib = _h.lib()
-    if B == 0 or not (1 <= fh <= 16384 and 1 <= fw <= 16384):
-        _h.check(lib.ssd_resize_lanczos(None, 0, None, 0, None, None, B, 3, fh, fw, _h.ptr(out), _h.ptr(out_u8), None, 0,
-                                        _h.stream()), "resize_lanczos_jpeg_batch")
+    if _lanczos_nothing_to_pack(B, 3, fh, fw, out, out_u8, "resize_lanczos_jpeg_batch"):
         return out
     jb = decode_jpeg_batch(blobs, fallback=fallback)
-    shapes = [np.broadcast_to(np.uint8(0), (int(o["H"]), int(o["W"]), 3)) for o in jb.desc]    # sizes only: no pixels
-    layout = _lanczos_layout(shapes, fh, fw)
-    layout["desc"]["src_offset"] = jb.desc["src_offset"]
-    layout["total"] = layout["src_at"]                                             # descriptors and tables only
+    layout = _lanczos_layout([(int(o["H"]), int(o["W"])) for o in jb.desc], fh, fw, src_offsets=jb.desc["src_offset"])
     packed = _upload_packed(dev, layout["total"], lambda host: _lanczos_fill(host, [], layout))
-    ws = _h.workspace(max(layout["tmp_bytes"], 16))
-    base = packed.data_ptr()
-    _h.check(lib.ssd_resize_lanczos(_h.ptr(jb.rgb), jb.rgb.numel(), base + layout["tables_at"], layout["n_ints"],
-                                    layout["desc"].ctypes.data, base, B, 3, fh, fw, _h.ptr(out), _h.ptr(out_u8), _h.ptr(ws),
-                                    ws.numel(), _h.stream()), "resize_lanczos_jpeg_batch")
+    _lanczos_launch(packed, layout, out, out_u8, src=jb.rgb, what="resize_lanczos_jpeg_batch")
     return out
 
 
@@ -600,7 +627,6 @@ JPEG_SAMPLING = {"4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2)}             
 # images/s of the Pillow JPEG pool at 8 workers, spreads not overlapping, the same bytes.
 JPEG_ENCODE_GPU_DEFAULT = "1"
 _encode_pools = {}
-_encode_staging = {}
 
 
 def jpeg_encode_gpu_enabled():
@@ -633,7 +659,7 @@ def _jpeg_encode_layout(shapes, samplings):
     import ssd_hip as _h
     B = len(shapes)
     desc = np.zeros(B, _h.JPEG_ENC_DESC_DTYPE)
-    tables_at = (desc.nbytes + 15) & ~15
+    (_, tables_at), total = _place([desc.nbytes, 256 * B])
     src = coef = planes = blocks = items = 0
     for b, ((H, W), (hs, vs)) in enumerate(zip(shapes, samplings)):
         d = desc[b]
@@ -643,11 +669,17 @@ def _jpeg_encode_layout(shapes, samplings):
         n1 = -(-W // (8 * hs)) * -(-H // (8 * vs))
         nb = n1 * (hs * vs + 2)
         src += H * W * 3
-        coef += (nb * 128 + 15) & ~15
-        planes += (nb * 64 + 15) & ~15
+        coef += _round16(nb * 128)
+        planes += _round16(nb * 64)
         blocks += nb
         items += n1 * 16
-    return {"desc": desc, "tables_at": tables_at, "total": tables_at + 256 * B, "coef_bytes": coef, "plane_bytes": planes}
+    return {"desc": desc, "tables_at": tables_at, "total": total, "coef_bytes": coef, "plane_bytes": planes}
+
+
+def _jpeg_encode_fill(host, layout, tables):
+    """Write the descriptors and the quantisation tables (uint16 ``[B,2,64]``) into ``host``."""
+    _put(host, 0, layout["desc"])
+    _put(host, layout["tables_at"], np.asarray(tables, np.uint16))
 
 
 def jpeg_forward_batch(rgb, shapes, samplings, tables):
@@ -659,17 +691,12 @@ def jpeg_forward_batch(rgb, shapes, samplings, tables):
     dev = _h.device()
     B = len(shapes)
     for H, W in shapes:
-        if not (1 <= H <= 16384 and 1 <= W <= 16384):
-            raise _h.SsdHipUnsupported("encode_jpeg_batch: an image of %d x %d, outside 1..16384" % (H, W))
+        if not _sizes_ok(H, W):
+            raise _h.SsdHipUnsupported("encode_jpeg_batch: an image of %d x %d, outside 1..%d" % (H, W, _h.MAX_IMAGE_SIDE))
     layout = _jpeg_encode_layout(shapes, samplings)
     desc = layout["desc"]
-    tables = np.ascontiguousarray(tables, np.uint16).reshape(B, 128)
-
-    def fill(host):
-        host[:desc.nbytes] = desc.view(np.uint8)
-        host[layout["tables_at"]:layout["total"]] = tables.view(np.uint8).reshape(-1)
-
-    packed = _upload_packed(dev, layout["total"], fill)
+    tables = np.asarray(tables, np.uint16).reshape(B, 128)
+    packed = _upload_packed(dev, layout["total"], lambda host: _jpeg_encode_fill(host, layout, tables))
     assert layout["plane_bytes"] == _h.lib().ssd_jpeg_forward_workspace_bytes(desc.ctypes.data, B)
     coef = torch.empty(max(layout["coef_bytes"], 16), dtype=torch.uint8, device=dev)
     ws = _h.workspace(max(layout["plane_bytes"], 16))
@@ -755,9 +782,7 @@ def encode_jpeg_batch(images, quality=75, subsampling="4:2:0", workers=None):
             _h.check(_h.lib().ssd_jpeg_quality_tables(q, known[q].ctypes.data), "ssd_jpeg_quality_tables")
         tables[b] = known[q]
     coef, desc = jpeg_forward_batch(rgb, shapes, samplings, tables)
-    st = _encode_staging.get(dev.index)
-    if st is None or st.numel() < coef.numel():
-        st = _encode_staging[dev.index] = _h.pinned_empty((max(1 << (coef.numel() - 1).bit_length(), 1 << 20),), torch.uint8)
+    st = _pinned_staging("download", dev, coef.numel())[0]
     st[:coef.numel()].copy_(coef, non_blocking=True)
     torch.cuda.current_stream().synchronize()
     host = st.numpy()
@@ -874,9 +899,16 @@ def _encoded_custom_image(img_path):
     if not img_path.endswith(".npy"):
         with open(img_path, "rb") as f:
             blob = f.read()
-        if blob[:2] == b"\xff\xd8":
+        if blob[:2] == _JPEG_SOI:
             return blob
     return _decode_custom_image(img_path)
+
+
+def _custom_images_resized(img_paths, final_height, final_width):
+    """The files as one resized batch: JPEG files decoded on the GPU unless ``SSD_JPEG_GPU=0``, the rest by PIL."""
+    if jpeg_gpu_enabled():
+        return resize_lanczos_jpeg_batch([_encoded_custom_image(p) for p in img_paths], final_height, final_width)
+    return resize_lanczos_batch([_decode_custom_image(p) for p in img_paths], final_height, final_width)
 
 
 def custom_data_generator(img_paths, final_height, final_width):
@@ -886,11 +918,7 @@ def custom_data_generator(img_paths, final_height, final_width):
     are accepted as well.  Yields ``(img [final_height, final_width, 3] device tensor, gt_boxes [0,4], gt_labels [0])``;
     ``custom_data_batches`` resizes a whole batch per call."""
     for img_path in img_paths:
-        if jpeg_gpu_enabled():
-            img = resize_lanczos_jpeg_batch([_encoded_custom_image(img_path)], final_height, final_width)[0]
-        else:
-            img = resize_lanczos_batch([_decode_custom_image(img_path)], final_height, final_width)[0]
-        yield img, np.zeros((0, 4), np.float32), np.zeros((0,), np.int32)
+        yield _custom_images_resized([img_path], final_height, final_width)[0], np.zeros((0, 4), np.float32), np.zeros((0,), np.int32)
 
 
 def custom_data_batches(img_paths, final_height, final_width, batch_size):
@@ -900,13 +928,8 @@ def custom_data_batches(img_paths, final_height, final_width, batch_size):
     pv = get_padding_values()
     img_paths = list(img_paths)
     for i in range(0, len(img_paths), int(batch_size)):
-        if jpeg_gpu_enabled():
-            arrays = [_encoded_custom_image(p) for p in img_paths[i:i + int(batch_size)]]
-            imgs = resize_lanczos_jpeg_batch(arrays, final_height, final_width)
-        else:
-            arrays = [_decode_custom_image(p) for p in img_paths[i:i + int(batch_size)]]
-            imgs = resize_lanczos_batch(arrays, final_height, final_width)
-        yield imgs, np.full((len(arrays), 1, 4), pv[1], np.float32), np.full((len(arrays), 1), pv[2], np.int32)
+        imgs = _custom_images_resized(img_paths[i:i + int(batch_size)], final_height, final_width)
+        yield imgs, np.full((len(imgs), 1, 4), pv[1], np.float32), np.full((len(imgs), 1), pv[2], np.int32)
 
 
 def padded_batch(items, batch_size, padding_values=None):

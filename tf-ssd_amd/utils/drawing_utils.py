@@ -202,7 +202,7 @@ def _launch(x, up, out, scale=True, fill=False, width=OUTLINE_WIDTH):
     maxlen = up["maxlen"]
     atlas = _atlas_on(x.device) if (maxlen > 0 and not fill) else None
     mm = None
-    if scale and B > 0 and C == 3 and 1 <= H <= 16384 and 1 <= W <= 16384:         # otherwise the library answers below
+    if scale and B > 0 and C == 3 and 1 <= H <= _h.MAX_IMAGE_SIDE and 1 <= W <= _h.MAX_IMAGE_SIDE:         # otherwise the library answers below
         mm = torch.empty((B, 2), dtype=torch.float32, device=x.device)
         ws = _h.workspace(lib.ssd_image_minmax_workspace_bytes(B))
         _h.check(lib.ssd_image_minmax(_h.ptr(x), B, H, W, C, _h.ptr(mm), _h.ptr(ws), ws.numel(), _h.stream()), "ssd_image_minmax")
