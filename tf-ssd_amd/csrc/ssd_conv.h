@@ -14,7 +14,7 @@ struct ConvParams {
     const float* scale;    // [Cout] or nullptr (== 1)
     const float* shift;    // [Cout] or nullptr (== 0)
     const float* residual; // dense [M][Cout] or nullptr
-    float* out;
+    float* out;            // nullptr with `op` set: a plane-only output, no fp32 store (dense [M][Cout], Cout % 4 == 0)
     int B, H, W, Cin, Ho, Wo, Cout;
     int kh, kw, stride, dil, pad_t, pad_l;
     int K, Kpad, Npad;
@@ -78,6 +78,8 @@ struct FusedBlockParams {
     short* e_planes;
     long e_plane;
     int planes_np;
+    int planes_only;            // whole-image kernel: bit 0 = y, bit 1 = the expanded map leave as planes ONLY (no fp32 store; every
+                                // consumer reads the planes).  The pointers y / e_out stay set: they also say which shapes a kernel takes
     int form2;                  // whole-image kernel: 1 = take the second form (csrc/ssd_imgblock2.hip) where it has a configuration
 };
 // Fused MobileNetV2 stem (Conv1 -> expanded_conv_depthwise -> expanded_conv_project).

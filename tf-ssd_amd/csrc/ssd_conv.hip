@@ -63,7 +63,7 @@ __global__ void splitk_reduce_kernel(const ConvParams p) {
             const long pix = m - (long)b * HoWo;
             if (p.n_split && n >= p.n_split)
                 p.out2[(long)b * p.out2_batch_stride + pix * p.out2_pixel_stride + (n - p.n_split)] = r;
-            else
+            else if (p.out)         // (nullptr: a plane-only output)
                 p.out[(long)b * p.out_batch_stride + pix * p.out_pixel_stride + n] = r;
             if (++n == p.Cout) { n = 0; ++m; }
             t[j] = r;
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(256) void conv_stem_kernel(const ConvParams p) {
                 const int b = (int)(m / HoWo);
                 const long pix = m - (long)b * HoWo;
                 const f32x4 v = *reinterpret_cast<const f32x4*>(so + pl * 36 + c4 * 4);
-                *reinterpret_cast<f32x4*>(p.out + (long)b * p.out_batch_stride + pix * p.out_pixel_stride + cg + c4 * 4) = v;
+                if (p.out) *reinterpret_cast<f32x4*>(p.out + (long)b * p.out_batch_stride + pix * p.out_pixel_stride + cg + c4 * 4) = v;
                 if (p.op) store_planes4(p.op, p.op_plane, p.op_np, m, cg + c4 * 4, p.M, v);      // (dense outputs only)
             }
         }
@@ -419,6 +419,9 @@ int conv_launch(const ConvParams& p, int cfg, hipStream_t st) {
                   p.Cin, p.kh, p.kw, p.stride);
         return SSD_E_UNSUPPORTED;
     }
+    // a plane-only output (no fp32 destination): only the families whose epilogue writes the planes, dense outputs only
+    SSD_UNSUPPORTED_IF(!p.out && !(p.op && !p.n_split && (p.Cout & 3) == 0 && conv_config_writes_planes(cfg, p)),
+                       "conv2d: config %s cannot write a plane-only output", conv_config_name(cfg));
     if (cfg >= kDma3Cfg0 && cfg < kDirectCfg) {
         const bool b1 = cfg >= kDmabCfg0;
         const int rc = dma_launch(p, cfg - (b1 ? kDmabCfg0 : kDma3Cfg0), b1 ? 1 : 3, st);
@@ -468,6 +471,7 @@ int conv_launch(const ConvParams& p, int cfg, hipStream_t st) {
 int launch_splitk_reduce(const ConvParams& p, hipStream_t st) {
     const long total = p.M * p.Cout;
     const bool vec = (total % 4 == 0) && (((uintptr_t)p.partial & 15) == 0);
+    SSD_UNSUPPORTED_IF(!vec && !p.out, "conv2d: a plane-only output needs the 4-wide split-K reduce (16-byte aligned workspace)");
     const long groups = vec ? total / 4 : total;
     const int blocks = (int)(cdiv(groups, 256) < 8192 ? cdiv(groups, 256) : 8192);
     if (vec) hipLaunchKernelGGL(splitk_reduce_kernel<4>, dim3(blocks), dim3(256), 0, st, p);
@@ -603,7 +607,7 @@ int ssd_conv2d_planes(const ssd_conv_desc* d, const void* in_planes_dev, int pla
     int rc = fill_conv_params(d, &p);
     if (rc) return rc;
     if (p.M == 0) return SSD_OK;
-    SSD_CHECK_ARG(in_planes_dev && packed_w_dev && out_dev, "conv2d_planes: NULL pointer");
+    SSD_CHECK_ARG(in_planes_dev && packed_w_dev && (out_dev || out_planes_dev), "conv2d_planes: NULL pointer");
     SSD_CHECK_ARG(planes == 1 || planes == 3, "conv2d_planes: planes must be 1 (bf16 mode) or 3 (exact split)");
     SSD_CHECK_ARG(in_plane_stride >= (long)p.B * p.H * p.W * p.Cin, "conv2d_planes: in_plane_stride shorter than the tensor");
     SSD_CHECK_ARG(!d->has_residual || residual_dev, "conv2d_planes: has_residual set but residual is NULL");
@@ -618,9 +622,11 @@ int ssd_conv2d_planes(const ssd_conv_desc* d, const void* in_planes_dev, int pla
     p.out_batch_stride = out_batch_stride > 0 ? out_batch_stride : (long)p.Ho * p.Wo * p.out_pixel_stride;
     p.vec_store = (((uintptr_t)out_dev & 15) == 0) && (p.out_pixel_stride % 4 == 0) && (p.out_batch_stride % 4 == 0);
     if (out_planes_dev) {
-        SSD_CHECK_ARG(p.out_pixel_stride == p.Cout && p.out_batch_stride == (long)p.Ho * p.Wo * p.Cout && p.Cout % 32 == 0,
-                      "conv2d_planes: plane output needs a dense [B,Ho,Wo,Cout] destination with Cout %% 32 == 0 (whole channel slices)");
-        SSD_CHECK_ARG(out_plane_stride >= p.M * p.Cout && out_plane_stride % 8 == 0, "conv2d_planes: bad out_plane_stride");
+        // (slice-major planes: the last 32-channel slice may be partly used; the epilogue stores four channels at a time)
+        SSD_CHECK_ARG(p.out_pixel_stride == p.Cout && p.out_batch_stride == (long)p.Ho * p.Wo * p.Cout && p.Cout % 4 == 0,
+                      "conv2d_planes: plane output needs a dense [B,Ho,Wo,Cout] destination with Cout %% 4 == 0");
+        SSD_CHECK_ARG(out_plane_stride >= p.M * ((p.Cout + 31) / 32 * 32) && out_plane_stride % 8 == 0 && ((uintptr_t)out_planes_dev & 7) == 0,
+                      "conv2d_planes: bad out_plane_stride (whole 32-channel slices of all %ld pixels) or unaligned planes", p.M);
         p.op = static_cast<short*>(out_planes_dev); p.op_plane = out_plane_stride; p.op_np = planes;
     }
     if (split_k > 1) {

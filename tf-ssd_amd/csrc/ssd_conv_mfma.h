@@ -99,7 +99,9 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x4 (&acc)[
                 }
                 const bool side2 = p.n_split && n >= p.n_split;
                 float* dst = (side2 ? orow2 : orow) + n;
-                if ((side2 ? p.vec_store2 : p.vec_store) && ((((uintptr_t)dst) & 15) == 0)) {
+                if (!side2 && !p.out) {
+                    // plane-only output: the planes below are the tensor
+                } else if ((side2 ? p.vec_store2 : p.vec_store) && ((((uintptr_t)dst) & 15) == 0)) {
                     *reinterpret_cast<f32x4*>(dst) = v;
                 } else {
                     dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2]; dst[3] = v[3];
@@ -114,6 +116,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x4 (&acc)[
                     t = apply_act(t, p.act);
                     if (p.residual) t += p.residual[(long)m * p.Cout + n + j];
                     float* drow = (p.n_split && n + j >= p.n_split) ? orow2 : orow;
+                    if (drow == orow && !p.out) continue;
                     drow[n + j] = t;
                 }
             }

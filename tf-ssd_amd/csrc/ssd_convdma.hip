@@ -345,6 +345,8 @@ int dma_launch(const ConvParams& p, int i, int np, hipStream_t st) {
 int launch_split_planes(const float* x, long n, int C, int np, short* planes, long plane, hipStream_t st) {
     SSD_CHECK_ARG(n % 4 == 0 && (np == 1 || np == 3), "split_planes: element count %ld must be a multiple of 4, planes 1 or 3", n);
     SSD_CHECK_ARG(C > 0 && C % 32 == 0 && n % C == 0, "split_planes: %d channels (slice-major planes need a multiple of 32 that divides the %ld elements)", C, n);
+    SSD_UNSUPPORTED_IF((((uintptr_t)x) & 15) || (((uintptr_t)planes) & 7) || (plane & 3),
+                       "split_planes: needs a 16-byte aligned source and 8-byte aligned planes (16-byte loads, 8-byte stores)");
     if (n == 0) return SSD_OK;
     const long n4 = n / 4;
     const int blocks = (int)((n4 + 255) / 256 < 16384 ? (n4 + 255) / 256 : 16384);
@@ -355,7 +357,7 @@ int launch_split_planes(const float* x, long n, int C, int np, short* planes, lo
 
 int launch_join_planes(const short* planes, long n, int C, int np, long plane, float* x, hipStream_t st) {
     if (n == 0) return SSD_OK;
-    SSD_CHECK_ARG(C > 0 && C % 32 == 0 && n % C == 0, "join_planes: %d channels do not divide the %ld elements into whole 32-channel slices", C, n);
+    SSD_CHECK_ARG(C > 0 && n % C == 0, "join_planes: %d channels do not divide the %ld elements", C, n);      // (a partly used last slice is fine)
     const int blocks = (int)((n + 255) / 256 < 16384 ? (n + 255) / 256 : 16384);
     hipLaunchKernelGGL(join_planes_kernel, dim3(blocks), dim3(256), 0, st, planes, n, C, np, plane, x);
     SSD_LAUNCH_CHECK();

@@ -221,7 +221,7 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image_block_kernel(const Fused
             if (tvalid[t]) *reinterpret_cast<f32x4*>(es + qs[t] * kILD) = v;
             if (p.e_out && real[t]) {
                 const long eo = ((long)img * H * W + opix[t]) * p.Ce + cbeg + j * kIC + g4 * 4;
-                *reinterpret_cast<f32x4*>(p.e_out + eo) = v;
+                if (!(p.planes_only & 2)) *reinterpret_cast<f32x4*>(p.e_out + eo) = v;
                 if (p.e_planes) store_planes4(p.e_planes, p.e_plane, p.planes_np, (long)img * H * W + opix[t], cbeg + j * kIC + g4 * 4, (long)B * H * W, v);
             }
         }
@@ -304,7 +304,7 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image_block_kernel(const Fused
                 f32x4 v = acc[t][ni] + *reinterpret_cast<const f32x4*>(p.ph + ni * 16 + g4 * 4);
                 if (p.residual)                                     // Cin == Cout: same layout as y
                     v = v + *reinterpret_cast<const f32x4*>(p.x + img_off + (long)opo[t] * p.Cout + ni * 16 + g4 * 4);
-                *reinterpret_cast<f32x4*>(yp + ni * 16) = v;
+                if (!(p.planes_only & 1)) *reinterpret_cast<f32x4*>(yp + ni * 16) = v;
                 if (p.y_planes) store_planes4(p.y_planes, p.y_plane, p.planes_np, (long)img * Ho * Wo + opo[t], g4 * 4 + ni * 16, (long)B * Ho * Wo, v);
             }
         }
@@ -549,7 +549,7 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image16_block_kernel(const Fus
             if (tvalid[t]) *reinterpret_cast<f32x4*>(es + qs[t] * kILD) = v;
             if (p.e_out && real[t]) {
                 const long eo = ((long)img * H * W + opix[t]) * p.Ce + cbeg + j * kIC + g4 * 4;
-                *reinterpret_cast<f32x4*>(p.e_out + eo) = v;
+                if (!(p.planes_only & 2)) *reinterpret_cast<f32x4*>(p.e_out + eo) = v;
                 if (p.e_planes) store_planes4(p.e_planes, p.e_plane, p.planes_np, (long)img * H * W + opix[t], cbeg + j * kIC + g4 * 4, (long)B * H * W, v);
             }
         }
@@ -643,7 +643,7 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image16_block_kernel(const Fus
                 f32x4 v = acc[t][ni] + *reinterpret_cast<const f32x4*>(p.ph + ni * 16 + g4 * 4);
                 if (p.residual)
                     v = v + *reinterpret_cast<const f32x4*>(p.x + img_off + (long)opo[t] * p.Cout + ni * 16 + g4 * 4);
-                *reinterpret_cast<f32x4*>(yp + ni * 16) = v;
+                if (!(p.planes_only & 1)) *reinterpret_cast<f32x4*>(yp + ni * 16) = v;
                 if (p.y_planes) store_planes4(p.y_planes, p.y_plane, p.planes_np, (long)img * Ho * Wo + opo[t], g4 * 4 + ni * 16, (long)B * Ho * Wo, v);
             }
         }
@@ -663,7 +663,7 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image16_block_kernel(const Fus
 __global__ __launch_bounds__(256) void image_combine_kernel(const float* __restrict__ slabs, const float* __restrict__ ph,
                                                             const float* __restrict__ xres, float* __restrict__ y,
                                                             long nvec, long slab_vec, int G, int c4n, short* __restrict__ yp,
-                                                            long y_plane, int np) {
+                                                            long y_plane, int np, int planes_only) {
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < nvec; e += (long)gridDim.x * 256) {
         f32x4 v = *reinterpret_cast<const f32x4*>(ph + (e % c4n) * 4);
         f32x4 s[4];
@@ -676,7 +676,7 @@ __global__ __launch_bounds__(256) void image_combine_kernel(const float* __restr
                 if (g0 + gg < G) v = v + s[gg];
         }
         if (xres) v = v + *reinterpret_cast<const f32x4*>(xres + e * 4);
-        *reinterpret_cast<f32x4*>(y + e * 4) = v;
+        if (!planes_only) *reinterpret_cast<f32x4*>(y + e * 4) = v;
         if (yp) store_planes4(yp, y_plane, np, e / c4n, (int)(e % c4n) * 4, nvec / c4n, v);
     }
 }
@@ -773,6 +773,9 @@ int launch_image_block(FusedBlockParams p, hipStream_t st) {
     }
     if (p.B == 0) return SSD_OK;
     if (p.groups < 1) p.groups = 1;
+    SSD_CHECK_ARG(!(p.planes_only & 1) || p.y_planes, "image block: plane-only y without planes");
+    SSD_CHECK_ARG(!(p.planes_only & 2) || (p.e_out && p.e_planes), "image block: plane-only expanded map without planes");
+    SSD_CHECK_ARG(!p.planes_only || !p.tickets, "image block: plane-only outputs combine by the second launch only");
     SSD_CHECK_ARG((p.Ce / kIC) % p.groups == 0, "image block: %d groups do not divide Ce/16 = %d", p.groups, p.Ce / kIC);
     SSD_CHECK_ARG(p.groups == 1 || p.slabs, "image block: %d groups need the slab workspace", p.groups);
     if (p.bf16 == 3 && image_lds_bytes(*c, p, p.groups) > 160 * 1024) p.bf16 = 0;      // split form's weight tiles do not fit: fp32 form
@@ -799,7 +802,7 @@ int launch_image_block(FusedBlockParams p, hipStream_t st) {
         const long nvec = (long)p.B * p.Ho * p.Wo * p.Cout / 4;
         const int blocks = (int)((nvec + 255) / 256 < 4096 ? (nvec + 255) / 256 : 4096);
         hipLaunchKernelGGL(image_combine_kernel, dim3(blocks), dim3(256), 0, st, p.slabs, p.ph, p.residual ? p.x : nullptr, p.y,
-                           nvec, nvec, p.groups, p.Cout / 4, p.y_planes, p.y_plane, p.planes_np);
+                           nvec, nvec, p.groups, p.Cout / 4, p.y_planes, p.y_plane, p.planes_np, p.planes_only & 1);
         SSD_LAUNCH_CHECK();
     }
     return SSD_OK;

@@ -197,7 +197,7 @@ __device__ __forceinline__ void image16v2_body(const FusedBlockParams& p, float*
             *reinterpret_cast<f32x4*>(ew + t * ROW) = v;
             if (S == 2 && p.e_out && real[t]) {       // block 13: the expanded map is SSD feature map 1 -- written once, from here
                 const int ch = cbeg + (j >> 1) * 32 + g4 * 8 + (j & 1) * 4;       // the lane's four channels of chunk j
-                *reinterpret_cast<f32x4*>(p.e_out + ((long)img * (H * W) + opix[t]) * p.Ce + ch) = v;
+                if (!(p.planes_only & 2)) *reinterpret_cast<f32x4*>(p.e_out + ((long)img * (H * W) + opix[t]) * p.Ce + ch) = v;
                 if (p.e_planes) store_planes4(p.e_planes, p.e_plane, p.planes_np, (long)img * (H * W) + opix[t], ch, (long)B * (H * W), v);
             }
         }
@@ -297,7 +297,7 @@ __device__ __forceinline__ void image16v2_body(const FusedBlockParams& p, float*
                 f32x4 v = acc[t][ni] + *reinterpret_cast<const f32x4*>(p.ph + ni * 16 + g4 * 4);
                 if (S == 1 && p.residual)
                     v = v + *reinterpret_cast<const f32x4*>(p.x + img_off + (long)opo[t] * p.Cout + ni * 16 + g4 * 4);
-                *reinterpret_cast<f32x4*>(yp + ni * 16) = v;
+                if (!(p.planes_only & 1)) *reinterpret_cast<f32x4*>(yp + ni * 16) = v;
                 if (p.y_planes) store_planes4(p.y_planes, p.y_plane, p.planes_np, (long)img * (Ho * Wo) + opo[t], g4 * 4 + ni * 16, (long)B * (Ho * Wo), v);
             }
         }

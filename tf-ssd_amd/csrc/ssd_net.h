@@ -42,6 +42,11 @@ struct Tensor {
     long plane_stride = 0;    // elements between planes
     int planes_np = 0;        // 3: exact split h, m, l (fp32 nets); 1: bf16 rounding (the bf16 mode)
     bool planes_live = false;
+    // the planes ARE the tensor: its producer skips the fp32 store into `dev` (the arena slot stays, unwritten).  Decided with
+    // the launch plan (plan_steps, ssd_net.hip): planes live, every running reader a dense conv on an LDS-DMA tile, the
+    // producer a kernel whose plane store needs no fp32 copy, option "plane_only" 1.  Inference only: the training step
+    // keeps activations of its own.  ssd_net_fetch_activation joins the planes (h + m + l is exact)
+    bool plane_only = false;
 };
 
 struct Layer {
@@ -121,6 +126,7 @@ struct ssd_net {
     bool image_split = true;        // fp32 nets: the finalize-time race also times the image kernel's split-bf16 form (img_choice 2; option "image_split" 0: leave it out)
     bool image_v2 = true;           // whole-image kernel: the second form (ssd_imgblock2.hip: compile-time geometry, adjacent pixels per lane) where it has a configuration; 0 = the first form (A/B; equal within tolerance, not bitwise: the k-slot order inside the project MFMAs differs)
     bool conv_dma = true;           // offer the LDS-DMA tiles over pre-split activation planes (ssd_convdma.hip) to the autotune / accept them from tables
+    bool plane_only = true;         // drop the fp32 copy of an activation whose readers all take its bf16 planes (Tensor::plane_only); 0: store both
     bool image_ticket = false;      // combine the channel-group slabs inside the launch (arrival ticket) instead of by a second launch
     float* img_slabs = nullptr;     // its partial-sum slabs and arrival tickets (sized for max_batch)
     unsigned* img_tickets = nullptr;

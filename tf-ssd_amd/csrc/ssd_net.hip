@@ -329,7 +329,7 @@ static ConvParams layer_conv_params(const ssd_net& net, const Layer& l, int B, c
     p.split_k = l.split_k;
     p.partial = l.splitk_part ? l.splitk_part : net.splitk_ws;
     if (l.head_kind == 0) {
-        p.out = out;
+        p.out = l.out >= 0 && net.tensors[l.out].plane_only && p.op ? nullptr : out;     // plane-only: the epilogue writes the planes alone
         p.out_pixel_stride = l.Cout;
         p.out_batch_stride = (long)l.Ho * l.Wo * l.Cout;
     } else {
@@ -373,6 +373,8 @@ static FusedBlockParams fused_shape(const ssd_net& net, const Layer& f, int B) {
         const Tensor& te = net.tensors[f.e_out];
         p.e_planes = te.planes; p.e_plane = te.plane_stride; p.planes_np = te.planes_np;
     }
+    if (f.route == RT_IMAGE || f.route == RT_IMAGE_SPLIT)     // plane-only outputs: no fp32 store (the pointers stay: they take part in the shape checks)
+        p.planes_only = (p.y_planes && net.tensors[f.out].plane_only ? 1 : 0) | (p.e_planes && net.tensors[f.e_out].plane_only ? 2 : 0);
     p.we3 = reinterpret_cast<const short*>(f.fz_we3);        // band kernel's plane layout (blocks 1-6) ...
     p.wp3 = reinterpret_cast<const short*>(f.fz_wp3);
     p.bf16 = net.precision;
@@ -455,12 +457,12 @@ static int run_layer_kernels(ssd_net& net, const Layer& l, int B, float* deltas_
                                     net.params[l.p_kernel].dev, l.scale, l.shift, l.act, out, st);
         case LK_POOL: {
             const Tensor& to = net.tensors[l.out];
-            return launch_maxpool(in, B, l.H, l.W, l.Cin, l.kh, l.stride, l.pt, l.pl, l.Ho, l.Wo, out, st,
+            return launch_maxpool(in, B, l.H, l.W, l.Cin, l.kh, l.stride, l.pt, l.pl, l.Ho, l.Wo, to.plane_only ? nullptr : out, st,
                                   to.planes_live ? to.planes : nullptr, to.plane_stride, to.planes_np);
         }
         case LK_L2NORM: {
             const Tensor& to = net.tensors[l.out];
-            return launch_l2norm(in, (long)B * l.H * l.W, l.Cin, net.params[l.p_gamma].dev, out, st,
+            return launch_l2norm(in, (long)B * l.H * l.W, l.Cin, net.params[l.p_gamma].dev, to.plane_only ? nullptr : out, st,
                                  to.planes_live ? to.planes : nullptr, to.plane_stride, to.planes_np);
         }
         case LK_SOFTMAX:
@@ -543,6 +545,38 @@ static void resolve_routes(ssd_net& net) {
     }
 }
 static bool layer_runs(const Layer& l) { return l.route != RT_OFF; }
+
+// Which activations can live as bf16 planes ALONE (Tensor::plane_only), under the current routes: `reads_planes(i)` says
+// whether conv layer i runs on an LDS-DMA tile.  A tensor qualifies when it has planes, EVERY running layer that reads it
+// (input or residual; a fused kernel reads fp32) is such a conv, and its running producer stores the planes from
+// registers -- the shared conv epilogue (fp32-MFMA, split-bf16, bf16, LDS-DMA tiles) with a dense output, the pool / L2-norm
+// writers, the whole-image block kernel with the combine as its second launch -- not by a split pass over the fp32 copy.
+// The image (tensor 0) and the head outputs are not tensors of the arena: no network output ever qualifies.
+template <typename F>
+static std::vector<char> plane_only_candidates(const ssd_net& net, F reads_planes) {
+    const int nt = (int)net.tensors.size();
+    std::vector<char> ok(nt, 0), readers(nt, 0);
+    if (!net.plane_only || net.image_ticket) return ok;
+    for (int t = 1; t < nt; ++t) ok[t] = net.tensors[t].planes != nullptr;
+    auto bar = [&](int t) { if (t >= 0) ok[t] = 0; };
+    for (int i = 0; i < (int)net.layers.size(); ++i) {
+        const Layer& l = net.layers[i];
+        if (!layer_runs(l)) continue;
+        if (l.kind == LK_CONV && l.in >= 0 && reads_planes(i)) readers[l.in] = 1;
+        else bar(l.in);
+        bar(l.res);
+        if (l.kind == LK_FUSED && l.f_project >= 0) bar(net.layers[l.f_project].res);      // (the block's residual source)
+        // the producer side
+        const bool image = l.kind == LK_FUSED && (l.route == RT_IMAGE || l.route == RT_IMAGE_SPLIT);
+        bool writes = image || l.kind == LK_POOL || l.kind == LK_L2NORM;
+        if (l.kind == LK_CONV)
+            writes = l.head_kind == 0 && (l.Cout & 3) == 0 && l.cfg >= 0 && l.cfg != conv_num_configs() - 1 &&
+                     conv_config_writes_planes(l.cfg, ConvParams{});
+        if (!writes) { bar(l.out); bar(l.e_out); }
+    }
+    for (int t = 0; t < nt; ++t) ok[t] = ok[t] && readers[t];
+    return ok;
+}
 
 static int dev_alloc(ssd_net& net, size_t floats, float** out) {
     *out = nullptr;
@@ -635,22 +669,30 @@ static int autotune(ssd_net& net, int B, hipStream_t st) {
     }
     int rc = SSD_OK;
     const bool dbg_sync = getenv("SSD_HIP_DEBUG_SYNC") != nullptr;   // name the launch a GPU fault belongs to
-    for (auto& l : net.layers) {
+    const bool dbg_tune = getenv("SSD_HIP_DEBUG_TUNE") != nullptr;
+    // the per-layer race keeps the best of BOTH families -- fam 0: tiles that read the fp32 activation, fam 1: LDS-DMA tiles
+    // over its planes -- because which of the two a layer takes is decided per TENSOR below
+    struct Best { float ms[2] = {1e30f, 1e30f}; int cfg[2] = {-1, -1}; int split[2] = {1, 1}; bool timed = false; };
+    std::vector<Best> bests(net.layers.size());
+    constexpr int kReps = 4;
+    for (size_t li = 0; li < net.layers.size(); ++li) {
+        Layer& l = net.layers[li];
+        Best& bb = bests[li];
         if (l.kind != LK_CONV) continue;
         if (l.cfg >= 0) continue;           // chosen by a valid preset line (ssd_net_set_tuning)
+        bb.timed = true;
         const float* in = net.tensors[l.in].dev;
         float* out = l.out >= 0 ? net.tensors[l.out].dev : nullptr;
         const float* res = l.res >= 0 ? net.tensors[l.res].dev : nullptr;
-        float best = 1e30f;
-        int best_cfg = -1, best_split = 1;
         for (int c = 0; c < conv_num_configs() && !rc; ++c) {
+            const int fam = conv_config_is_dma(c) ? 1 : 0;
             for (int si = 0; si < kNumSplits && !rc; ++si) {
                 const int split = kSplits[si];
                 l.split_k = split;
                 ConvParams p = layer_conv_params(net, l, B, in, out, res, d, pr);
                 if (!conv_config_valid(c, p) || !conv_config_allowed(c, net.precision)) break;
                 const bool direct = (c == conv_num_configs() - 1);
-                if (direct && (best_cfg >= 0 || split > 1)) break;     // direct only as a last resort
+                if (direct && (bb.cfg[0] >= 0 || bb.cfg[1] >= 0 || split > 1)) break;     // direct only as a last resort
                 if (split > 1) {
                     const long blocks = conv_grid_blocks(c, p);
                     const int nkt = conv_k_tiles(c, p);
@@ -658,7 +700,7 @@ static int autotune(ssd_net& net, int B, hipStream_t st) {
                     if ((size_t)split * p.M * p.Cout > net.splitk_floats) break;
                 }
                 // min over 3 trials of 4 back-to-back launches: robust against clock ramps / noise
-                const int reps = 4;
+                const int reps = kReps;
                 if (dbg_sync) fprintf(stderr, "[ssd dbg] tune %s %s split %d\n", l.name.c_str(), conv_config_name(c), split);
                 rc = conv_launch(p, c, st);     // warm-up
                 if (rc) break;
@@ -673,25 +715,76 @@ static int autotune(ssd_net& net, int B, hipStream_t st) {
                     float t = 0.f;
                     (void)hipEventElapsedTime(&t, e0, e1);
                     ms = t < ms ? t : ms;
-                    if (trial == 0 && ms > 1.5f * best) break;      // clearly slower than the incumbent
+                    if (trial == 0 && ms > 1.5f * bb.ms[fam]) break;      // clearly slower than its family's incumbent
                 }
                 if (rc) break;
-                // an LDS-DMA tile makes the producer of its input write the bf16 planes as well (6 or 2 bytes per element
-                // at the store rate the epilogues reach): charged to the candidate, the race stays a per-layer one
-                if (conv_config_is_dma(c))
-                    ms += reps * (float)((double)B * net.tensors[l.in].per_image * 2.0 * net.tensors[l.in].planes_np / 3.0e12 * 1e3);
-                if (ms < best) { best = ms; best_cfg = c; best_split = split; }
+                if (ms < bb.ms[fam]) { bb.ms[fam] = ms; bb.cfg[fam] = c; bb.split[fam] = split; }
             }
         }
         if (rc) break;
-        if (best_cfg < 0) {
+        if (bb.cfg[0] < 0 && bb.cfg[1] < 0) {
             set_error("finalize: no conv kernel can run layer %s", l.name.c_str());
             rc = SSD_E_UNSUPPORTED;
             break;
         }
-        l.cfg = best_cfg;
-        l.split_k = best_split;
+        const int f0 = bb.cfg[0] >= 0 ? 0 : 1;          // the fp32-reading family until the tensor decision below
+        l.cfg = bb.cfg[f0];
+        l.split_k = bb.split[f0];
+        if (dbg_tune)
+            fprintf(stderr, "[ssd] tune %s: %s/s%d %.4f ms | %s/s%d %.4f ms\n", l.name.c_str(), bb.cfg[0] >= 0 ? conv_config_name(bb.cfg[0]) : "-",
+                    bb.split[0], bb.cfg[0] >= 0 ? bb.ms[0] / kReps : 0.f, bb.cfg[1] >= 0 ? conv_config_name(bb.cfg[1]) : "-", bb.split[1],
+                    bb.cfg[1] >= 0 ? bb.ms[1] / kReps : 0.f);
     }
+    if (rc) return rc;
+    // The family is a property of the TENSOR: LDS-DMA readers make its producer store the bf16 planes (2 * planes_np bytes per
+    // element), and when every reader takes them the producer drops the fp32 store (4 bytes per element back: plane-only,
+    // Tensor::plane_only).  So per tensor: the sum of its timed readers' best fp32-reading tiles against the sum of their
+    // best LDS-DMA tiles plus what the producer's store changes by, at the 3 TB/s the epilogues' stores reach; all timed
+    // readers flip together.  The whole-image kernel is taken to run wherever it can (its own race comes later; it wins in
+    // every shipped table): what it fuses away reads no tensor.
+    std::vector<int> img_saved;
+    for (auto& f : net.layers) {
+        img_saved.push_back(f.img_choice);
+        if (f.img_choice < 0 && image_kernel_takes(net, f)) f.img_choice = 1;
+    }
+    resolve_routes(net);
+    for (size_t t = 1; t < net.tensors.size(); ++t) {
+        const Tensor& tt = net.tensors[t];
+        std::vector<size_t> flip;
+        bool planes_anyway = false;
+        double sum0 = 0, sum1 = 0;
+        for (size_t li = 0; li < net.layers.size(); ++li) {
+            const Layer& l = net.layers[li];
+            if (l.kind != LK_CONV || l.in != (int)t) continue;
+            const Best& bb = bests[li];
+            if (!bb.timed) { if (layer_runs(l) && conv_config_is_dma(l.cfg)) planes_anyway = true; continue; }
+            if (bb.cfg[1] < 0) continue;                 // no LDS-DMA tile takes it: stays where it is
+            if (bb.cfg[0] < 0) { planes_anyway = true; continue; }      // ... only LDS-DMA tiles do: already there
+            if (!layer_runs(l)) {       // fused away under these routes: reads nothing; on its own, with the full plane store charged
+                if (bb.ms[1] + kReps * ((double)B * tt.per_image * 2.0 * tt.planes_np / 3.0e12 * 1e3) < bb.ms[0]) {
+                    net.layers[li].cfg = bb.cfg[1];
+                    net.layers[li].split_k = bb.split[1];
+                }
+                continue;
+            }
+            flip.push_back(li);
+            sum0 += bb.ms[0];
+            sum1 += bb.ms[1];
+        }
+        if (flip.empty()) continue;
+        for (size_t li : flip) { net.layers[li].cfg = bests[li].cfg[1]; net.layers[li].split_k = bests[li].split[1]; }
+        const bool only = plane_only_candidates(net, [&](int i) { return conv_config_is_dma(net.layers[i].cfg); })[t];
+        const double bytes = only ? 2.0 * tt.planes_np - 4.0 : planes_anyway ? 0.0 : 2.0 * tt.planes_np;
+        const double store_ms = kReps * ((double)B * tt.per_image * bytes / 3.0e12 * 1e3);
+        const bool take = sum1 + store_ms < sum0;
+        if (!take)
+            for (size_t li : flip) { net.layers[li].cfg = bests[li].cfg[0]; net.layers[li].split_k = bests[li].split[0]; }
+        if (dbg_tune)
+            fprintf(stderr, "[ssd] tune tensor %s: fp32 readers %.4f ms, plane readers %.4f + store %+.4f ms (%s) -> %s\n", tt.name.c_str(),
+                    sum0 / kReps, sum1 / kReps, store_ms / kReps, only ? "plane-only" : "both copies", take ? "planes" : "fp32");
+    }
+    for (size_t i = 0; i < net.layers.size(); ++i) net.layers[i].img_choice = img_saved[i];
+    resolve_routes(net);
     return rc;
 }
 
@@ -1040,7 +1133,7 @@ static int finalize_arena(ssd_net* net, int max_batch, hipStream_t st) {
     SSD_HIP(hipMemset(net->arena, poison ? 0xFF : 0, total * sizeof(float)));
     // bf16 planes of every activation a dense conv with Cin % 32 == 0 reads (the LDS-DMA tiles' operand, ssd_convdma.hip);
     // written only while a consumer's chosen configuration asks for them (planes_live)
-    for (auto& t : net->tensors) { t.planes = nullptr; t.planes_live = false; t.planes_np = 0; t.plane_stride = 0; }
+    for (auto& t : net->tensors) { t.planes = nullptr; t.planes_live = false; t.plane_only = false; t.planes_np = 0; t.plane_stride = 0; }
     if (net->conv_dma)
         for (const auto& l : net->layers) {
             if (l.kind != LK_CONV || l.in < 0 || l.Cin % 32 != 0) continue;
@@ -1106,7 +1199,9 @@ static int finalize_apply_preset(ssd_net* net, int max_batch, bool* image_preset
 }
 
 // The planes were allocated for the race; keep them only where a CHOSEN tile reads them (6 bytes per element in fp32 nets,
-// 2 in the bf16 mode, on top of the fp32 slot: a table without LDS-DMA tiles leaves none).
+// 2 in the bf16 mode: a table without LDS-DMA tiles leaves none).  A plane-only tensor keeps its fp32 arena slot too -- the
+// layout of the arena does not depend on the routing state, and option "plane_only" 0 writes it again -- so the planes
+// always come on top of the slot in ssd_net_memory_bytes.
 static int finalize_free_unread_planes(ssd_net* net, hipStream_t st) {
     std::vector<char> read(net->tensors.size(), 0);
     for (const auto& l : net->layers)
@@ -1267,6 +1362,11 @@ static void plan_steps(ssd_net& net) {
     for (const auto& l : net.layers)
         if (l.kind == LK_CONV && l.in >= 0 && conv_config_is_dma(l.cfg) && net.tensors[l.in].planes && layer_runs(l))
             net.tensors[l.in].planes_live = true;
+    // ... and which of them exist as planes ONLY
+    {
+        const std::vector<char> only = plane_only_candidates(net, [&](int i) { return conv_config_is_dma(net.layers[i].cfg); });
+        for (size_t t = 0; t < net.tensors.size(); ++t) net.tensors[t].plane_only = only[t] && net.tensors[t].planes_live;
+    }
     const bool overlap = net.overlap_heads && !net.timing && net.side[0];
     // Stream plan (matters under hipGraph replay too: ready nodes start in capture order).  Every
     // kernel of the heavy part of the graph fills the whole GPU, so overlapping two of them only splits
@@ -1531,6 +1631,7 @@ static const OptionSpec kOptions[] = {
     // project MFMAs).  The band kernels' LDS-DMA weight staging it also selects is bitwise equal
     {"image_v2", &ssd_net::image_v2, nullptr, 0, 1, 0},
     {"conv_dma", &ssd_net::conv_dma, nullptr, 0, 1, 1},         // LDS-DMA conv tiles over pre-split activation planes (default 1)
+    {"plane_only", &ssd_net::plane_only, nullptr, 0, 1, 0},     // no fp32 copy of an activation whose readers all take its planes (default 1)
     {"use_graph", &ssd_net::use_graph, nullptr, 0, 1, 0},
 };
 
@@ -1610,7 +1711,16 @@ long ssd_net_fetch_activation(ssd_net* net, const char* layer, float* host_out, 
         set_error("ssd_net_fetch_activation: buffer holds %zu floats, need %zu", cap, n);
         return SSD_E_INVALID;
     }
-    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(host_out, t.dev, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+    ScopedDev joined;          // a plane-only tensor: the planes joined back (h + m + l is exact), its fp32 slot is not written
+    const float* src = t.dev;
+    if (t.plane_only && n) {
+        SSD_HIP(hipMalloc((void**)&joined.p, n * sizeof(float)));
+        SSD_HIP(hipDeviceSynchronize());
+        const int rc = launch_join_planes(t.planes, (long)n, t.C, t.planes_np, t.plane_stride, joined.p, nullptr);
+        if (rc) return rc;
+        src = joined.p;
+    }
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(host_out, src, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
         set_error("ssd_net_fetch_activation: copy failed");
         return SSD_E_HIP;
     }

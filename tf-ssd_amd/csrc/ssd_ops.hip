@@ -125,7 +125,7 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const float* __restrict__ 
                 m[2] = fmaxf(m[2], v[2]); m[3] = fmaxf(m[3], v[3]);
             }
         }
-        *reinterpret_cast<f32x4*>(out + e * 4) = m;
+        if (out) *reinterpret_cast<f32x4*>(out + e * 4) = m;      // (nullptr: a plane-only output)
         if (planes) store_planes4(planes, plane, np, e / C4, c, (long)B * Ho * Wo, m);      // the bf16 planes the LDS-DMA conv tiles read (ssd_convdma.hip)
     }
 }
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256) void l2norm_kernel(const float* __restrict__ i
             const f32x4 v = *reinterpret_cast<const f32x4*>(x + c);
             const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + c);
             const f32x4 y = v * inv * g;
-            *reinterpret_cast<f32x4*>(out + px * C + c) = y;
+            if (out) *reinterpret_cast<f32x4*>(out + px * C + c) = y;
             if (planes) store_planes4(planes, plane, np, px, c, pixels, y);
         }
     }
