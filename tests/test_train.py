@@ -114,11 +114,7 @@ def test_two_process_gloo_gradient_allreduce(tmp_path, bucket):
 
 def _hwc(m, name):
     n = m.train_fetch(name, 1).size
-    for t in ("Conv1_relu", ):
-        pass
     # per-image H*W*C of a named activation: recover H, W, C from the graph's tensor table
-    import ssd_hip as h
-    lib = h.lib()
     shapes = getattr(m, "_act_shapes", None)
     if shapes is None:
         from oracle import net_oracle as no

@@ -47,6 +47,10 @@ struct ConvParams {
 // bf16 nets take them instead of the split-bf16 / Winograd tiles (the fp32-MFMA and skinny tiles serve the small tail layers
 // in both modes: more accurate than asked for)
 bool conv_config_allowed(int cfg, int precision);
+// ConvParams::vec_store of these destinations: float4 stores into `out` are aligned
+inline int conv_vec_store(const ConvParams& p) {
+    return (((uintptr_t)p.out & 15) == 0) && (p.out_pixel_stride % 4 == 0) && (p.out_batch_stride % 4 == 0);
+}
 
 // One fused MobileNetV2 inverted-residual block (csrc/ssd_fused.hip).
 struct FusedBlockParams {

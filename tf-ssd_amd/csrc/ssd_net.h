@@ -89,6 +89,29 @@ struct Layer {
     hipEvent_t ev_ready = nullptr;  // recorded on the main stream when this layer's OUTPUT is complete
 };
 
+// Output routing of the fused label + box head conv of one level: columns below Cout1 go into the concatenated [B,N,L]
+// label tensor `probs`, the rest into the [B,N,4] box tensor `deltas` (inference and training forward alike)
+inline void conv_route_head(ConvParams& p, const Layer& l, float* probs, float* deltas) {
+    p.out = probs + l.head_off;
+    p.out_pixel_stride = l.head_ps;
+    p.out_batch_stride = l.head_bs;
+    p.n_split = l.Cout1;
+    p.out2 = deltas + l.head2_off;
+    p.out2_pixel_stride = l.head2_ps;
+    p.out2_batch_stride = l.head2_bs;
+    p.vec_store2 = (p.out2_pixel_stride % 4 == 0) && (p.out2_batch_stride % 4 == 0);
+}
+
+// Scope guards: the early error returns of the tuning / profiling entry points must not leak
+struct ScopedDev {
+    float* p = nullptr;
+    ~ScopedDev() { if (p) (void)hipFree(p); }
+};
+struct ScopedEvent {
+    hipEvent_t e = nullptr;
+    ~ScopedEvent() { if (e) (void)hipEventDestroy(e); }
+};
+
 // One launch of the forward's plan (plan_steps, ssd_net.hip): a pure function of the graph, the options, the
 // routes and `timing`, built at the first forward that needs it and kept until ssd_net::drop_graphs().
 struct Step {

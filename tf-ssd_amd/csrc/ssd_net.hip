@@ -333,16 +333,9 @@ static ConvParams layer_conv_params(const ssd_net& net, const Layer& l, int B, c
         p.out_pixel_stride = l.Cout;
         p.out_batch_stride = (long)l.Ho * l.Wo * l.Cout;
     } else {
-        p.out = probs_out + l.head_off;
-        p.out_pixel_stride = l.head_ps;
-        p.out_batch_stride = l.head_bs;
-        p.n_split = l.Cout1;
-        p.out2 = deltas_out + l.head2_off;
-        p.out2_pixel_stride = l.head2_ps;
-        p.out2_batch_stride = l.head2_bs;
-        p.vec_store2 = (p.out2_pixel_stride % 4 == 0) && (p.out2_batch_stride % 4 == 0);
+        conv_route_head(p, l, probs_out, deltas_out);
     }
-    p.vec_store = (((uintptr_t)p.out & 15) == 0) && (p.out_pixel_stride % 4 == 0) && (p.out_batch_stride % 4 == 0);
+    p.vec_store = conv_vec_store(p);
     return p;
 }
 
@@ -586,18 +579,6 @@ static int dev_alloc(ssd_net& net, size_t floats, float** out) {
     return SSD_OK;
 }
 
-// Time each valid (tile configuration, split-K factor) of every conv layer on the device and
-// keep the best.  Split-K is tried only where the plain grid cannot fill the 256 CUs.
-// Scope guards: the SSD_HIP early returns of the tuning / profiling entry points must not leak
-struct ScopedDev {
-    float* p = nullptr;
-    ~ScopedDev() { if (p) (void)hipFree(p); }
-};
-struct ScopedEvent {
-    hipEvent_t e = nullptr;
-    ~ScopedEvent() { if (e) (void)hipEventDestroy(e); }
-};
-
 // Whole-image block kernel vs the layer kernels (expand GEMM + depthwise/project kernel) of the
 // same block, timed on the device at batch B: at B = 64 the 4-way channel-group reduction costs
 // what the E round trip through HBM costs, at large batches (one group) the image kernel wins.
@@ -641,6 +622,8 @@ static int tune_image_blocks(ssd_net& net, int B, hipStream_t st) {
     return rc;
 }
 
+// Time each valid (tile configuration, split-K factor) of every conv layer on the device and
+// keep the best.  Split-K is tried only where the plain grid cannot fill the 256 CUs.
 static int autotune(ssd_net& net, int B, hipStream_t st) {
     ScopedEvent se0, se1;
     SSD_HIP(hipEventCreate(&se0.e));

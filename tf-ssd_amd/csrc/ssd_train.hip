@@ -917,7 +917,7 @@ struct ssd_train_state {
     std::vector<char> gwritten;
     std::vector<TrainLayer> tl;
     std::vector<float*> owned;
-    float *scratch_dy = nullptr, *scratch_dz = nullptr, *scratch_w = nullptr, *partial = nullptr;
+    float *scratch_dz = nullptr, *partial = nullptr;
     // weight gradients on a side stream beside the rest of the backward (dX chain, BatchNorm backward of the layers below):
     // dY alternates between two buffers (a buffer is rewritten only after the weight gradient that reads it is done), the
     // weight-gradient partial slab is its own
@@ -986,46 +986,35 @@ static long chunks_for(long M, long unit_blocks, long* rows_per_chunk, long min_
     return (M + rpc - 1) / rpc;
 }
 
-static int ensure_partial(ssd_train_state& s, size_t floats) {
-    if (floats <= s.partial_floats) return SSD_OK;
-    // grow-only; the old slab stays owned until the state is freed (sizes are planned once per batch)
+// a partial-sum slab (s.partial / s.partial_w) of at least `floats`: grow-only; the old slab stays owned until the state is
+// freed (sizes are planned once per batch)
+static int ensure_slab(ssd_train_state& s, size_t floats, float** slab, size_t* have) {
+    if (floats <= *have) return SSD_OK;
     float* p = nullptr;
     int rc = talloc(s, floats, &p);
     if (rc) return rc;
-    s.partial = p;
-    s.partial_floats = floats;
+    *slab = p;
+    *have = floats;
     return SSD_OK;
 }
 
 template <int OP>
 static int col_reduce(ssd_train_state& s, RedParams p, long* chunks_out, hipStream_t st) {
     const bool vec = p.C % 4 == 0 && p.lda % 4 == 0 && (((uintptr_t)p.a | (uintptr_t)p.b) & 15) == 0;
-    if (vec) {
-        // channel quads per block: a power of two <= 64 that wastes few lanes (C / 4 = 4 .. 320)
-        const int q = p.C / 4;
-        p.cw = q % 64 == 0 ? 64 : (q % 32 == 0 ? 32 : (q % 16 == 0 ? 16 : (q % 8 == 0 ? 8 : (q < 8 ? 4 : (q < 48 ? 16 : 64)))));
-        const int ctiles = (q + p.cw - 1) / p.cw;
-        long rpc = 0;
-        const long chunks = chunks_for(p.M, ctiles, &rpc, 64, 256);
-        int rc = ensure_partial(s, (size_t)chunks * 2 * p.C);
-        if (rc) return rc;
-        p.rows_per_chunk = rpc;
-        p.partial = s.partial;
-        hipLaunchKernelGGL(col_reduce4_kernel<OP>, dim3(ctiles, (unsigned)chunks), dim3(256), 0, st, p);
-        SSD_LAUNCH_CHECK();
-        *chunks_out = chunks;
-        return SSD_OK;
-    }
-    SSD_UNSUPPORTED_IF(OP == RED_STATS, "train: batch statistics need C %% 4 == 0 (C = %d)", p.C);
-    p.cw = p.C % 64 == 0 ? 64 : (p.C % 32 == 0 ? 32 : (p.C % 16 == 0 ? 16 : (p.C < 64 ? 32 : 64)));
-    const int ctiles = (p.C + p.cw - 1) / p.cw;
+    SSD_UNSUPPORTED_IF(!vec && OP == RED_STATS, "train: batch statistics need C %% 4 == 0 (C = %d)", p.C);
+    // columns of a block: channel quads (16-byte form: a power of two <= 64 that wastes few lanes, C / 4 = 4 .. 320) or channels
+    const int q = vec ? p.C / 4 : p.C;
+    if (vec) p.cw = q % 64 == 0 ? 64 : (q % 32 == 0 ? 32 : (q % 16 == 0 ? 16 : (q % 8 == 0 ? 8 : (q < 8 ? 4 : (q < 48 ? 16 : 64)))));
+    else p.cw = q % 64 == 0 ? 64 : (q % 32 == 0 ? 32 : (q % 16 == 0 ? 16 : (q < 64 ? 32 : 64)));
+    const int ctiles = (q + p.cw - 1) / p.cw;
     long rpc = 0;
     const long chunks = chunks_for(p.M, ctiles, &rpc, 64, 256);
-    int rc = ensure_partial(s, (size_t)chunks * 2 * p.C);
+    int rc = ensure_slab(s, (size_t)chunks * 2 * p.C, &s.partial, &s.partial_floats);
     if (rc) return rc;
     p.rows_per_chunk = rpc;
     p.partial = s.partial;
-    hipLaunchKernelGGL(col_reduce_kernel<OP>, dim3(ctiles, (unsigned)chunks), dim3(256), 0, st, p);
+    if (vec) hipLaunchKernelGGL(col_reduce4_kernel<OP>, dim3(ctiles, (unsigned)chunks), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(col_reduce_kernel<OP>, dim3(ctiles, (unsigned)chunks), dim3(256), 0, st, p);
     SSD_LAUNCH_CHECK();
     *chunks_out = chunks;
     return SSD_OK;
@@ -1036,6 +1025,15 @@ static int col_finalize(ssd_train_state& s, long chunks, int C, float scale, flo
                        out1, out2, mode, kBnEps);
     SSD_LAUNCH_CHECK();
     return SSD_OK;
+}
+// out[c] = scale * sum_m a[m * lda + c]
+static int col_sum(ssd_train_state& s, const float* a, long M, int C, int lda, float scale, float* out, hipStream_t st) {
+    RedParams p{};
+    p.a = a; p.M = M; p.C = C; p.lda = lda;
+    long chunks = 0;
+    int rc = col_reduce<RED_SUM>(s, p, &chunks, st);
+    if (!rc) rc = col_finalize(s, chunks, C, scale, out, nullptr, 0, st);
+    return rc;
 }
 
 // batch statistics of pre [M][C] -> mean, var (biased), istd, and the moving-average update (unbiased variance): one
@@ -1055,8 +1053,7 @@ static int bn_stats(ssd_train_state& s, TrainLayer& t, long M, int C, float* mov
         SSD_LAUNCH_CHECK();
         return SSD_OK;
     }
-    int rc = col_reduce<RED_SUM>(s, p, &chunks, st);
-    if (!rc) rc = col_finalize(s, chunks, C, 1.0f / (float)M, t.mean, nullptr, 0, st);
+    int rc = col_sum(s, t.pre, M, C, C, 1.0f / (float)M, t.mean, st);
     if (rc) return rc;
     p.mean = t.mean;
     rc = col_reduce<RED_SQDEV>(s, p, &chunks, st);
@@ -1083,9 +1080,21 @@ static ConvParams dense_conv_params(int B, int H, int W, int Cin, int Cout, int 
     return p;
 }
 
-// matrix-core FLOPs issued by the step being built, per instruction family (bench.py prices each at its own peak):
-// [0] conv forward / backward-data on fp32-MFMA tiles, [1] on split-bf16 tiles, [2] weight gradients (fp32 MFMA)
-static thread_local double g_step_flops[3] = {0, 0, 0};
+// The training step's environment switches, read once per process.
+struct TrainEnv {
+    int autotune;          // SSD_HIP_TRAIN_AUTOTUNE (default 1): 0 the cost model / heuristic tiles, 1 tiles timed on the device, 2 also prints them
+    bool wgrad_stream;     // SSD_HIP_TRAIN_WGRAD_STREAM=0 (diagnostics): weight gradients in line on the caller's stream
+    bool side_buckets;     // SSD_HIP_WGRAD_SIDE_BUCKETS=0: under gradient buckets the weight gradients run in line (StepCtx::side)
+    bool debug_buckets;    // SSD_HIP_DEBUG_BUCKETS set: print every gradient bucket as it becomes final
+};
+static const TrainEnv& train_env() {
+    static const TrainEnv env = [] {
+        auto num = [](const char* name) { const char* v = getenv(name); return v ? atoi(v) : 1; };
+        return TrainEnv{num("SSD_HIP_TRAIN_AUTOTUNE"), num("SSD_HIP_TRAIN_WGRAD_STREAM") != 0, num("SSD_HIP_WGRAD_SIDE_BUCKETS") != 0,
+                        getenv("SSD_HIP_DEBUG_BUCKETS") != nullptr};
+    }();
+    return env;
+}
 
 // Tile choice of the training convs (forward and backward-data).  Default (SSD_HIP_TRAIN_AUTOTUNE unset or 1): the first
 // time a conv shape is seen every valid tile of the net's precision is TIMED on the device (into a scratch output: a
@@ -1099,8 +1108,56 @@ struct TrainPickKey {
     long M, ops, obs; int K, Cout, kh, kw, stride, dil, H, W, Cin, flags, pad_t, pad_l;
     bool operator<(const TrainPickKey& o) const { return memcmp(this, &o, sizeof(*this)) < 0; }
 };
-static std::map<TrainPickKey, int>& train_picks() { static std::map<TrainPickKey, int> m; return m; }
-static std::mutex& train_picks_mutex() { static std::mutex m; return m; }      // nets of several host threads share the memo
+// The memo of timed picks (conv tiles and weight-gradient tiles).  Nets of several host threads share it: the map and its
+// mutex are reachable through the locked lookup and the locked store alone.
+class PickMemo {
+    std::mutex mu_;
+    std::map<TrainPickKey, int> picks_;
+
+public:
+    bool lookup(const TrainPickKey& k, int* pick) {
+        std::lock_guard<std::mutex> lock(mu_);
+        const auto it = picks_.find(k);
+        if (it != picks_.end()) *pick = it->second;
+        return it != picks_.end();
+    }
+    void store(const TrainPickKey& k, int pick) {
+        std::lock_guard<std::mutex> lock(mu_);
+        picks_[k] = pick;
+    }
+};
+static PickMemo& pick_memo() { static PickMemo m; return m; }
+
+// The one tile-timing loop: every candidate launches once untimed (a candidate whose launch fails is left out), then takes
+// the minimum over 3 trials of `reps` back-to-back launches; a candidate whose first trial takes more than twice the
+// incumbent's time stops there.  `launch(c)` must be harmless to repeat.  false: the events could not be created.
+struct TimedPick {
+    int best;                  // the fastest candidate (`model` if none ran)
+    float best_ms, model_ms;   // per `reps` launches
+};
+template <class Launch>
+static bool time_candidates(const std::vector<int>& candidates, int model, int reps, hipStream_t st, Launch launch, TimedPick* out) {
+    ScopedEvent e0, e1;
+    if (hipEventCreate(&e0.e) != hipSuccess || hipEventCreate(&e1.e) != hipSuccess) { (void)hipGetLastError(); return false; }
+    *out = TimedPick{model, 1e30f, 0.f};
+    for (const int c : candidates) {
+        if (launch(c)) { (void)hipGetLastError(); continue; }
+        float ms = 1e30f;
+        for (int trial = 0; trial < 3; ++trial) {
+            (void)hipEventRecord(e0.e, st);
+            for (int r = 0; r < reps; ++r) (void)launch(c);
+            (void)hipEventRecord(e1.e, st);
+            (void)hipEventSynchronize(e1.e);
+            float t = 0.f;
+            (void)hipEventElapsedTime(&t, e0.e, e1.e);
+            ms = t < ms ? t : ms;
+            if (trial == 0 && ms > 2.0f * out->best_ms) break;
+        }
+        if (c == model) out->model_ms = ms;
+        if (ms < out->best_ms) { out->best_ms = ms; out->best = c; }
+    }
+    return true;
+}
 
 static int pick_measured(const ConvParams& p, hipStream_t st, int model_cfg, int verbose) {
     TrainPickKey k{};
@@ -1109,66 +1166,45 @@ static int pick_measured(const ConvParams& p, hipStream_t st, int model_cfg, int
     k.Cin = p.Cin; k.pad_t = p.pad_t; k.pad_l = p.pad_l; k.ops = p.out_pixel_stride; k.obs = p.out_batch_stride;
     k.flags = (p.residual ? 1 : 0) | (p.n_split ? 2 : 0) | (p.scale ? 4 : 0) | (p.shift ? 8 : 0) | (p.act << 4) | (p.bf16 << 8) |
               (p.vec_store << 9);
-    {
-        std::lock_guard<std::mutex> lock(train_picks_mutex());
-        auto it = train_picks().find(k);
-        // (a memoised pick is re-validated against THESE parameters: alignment of the pointers is not part of the key)
-        if (it != train_picks().end()) return conv_config_valid(it->second, p) ? it->second : model_cfg;
-    }
-    float* scratch = nullptr;
+    int memo = 0;
+    // (a memoised pick is re-validated against THESE parameters: alignment of the pointers is not part of the key)
+    if (pick_memo().lookup(k, &memo)) return conv_config_valid(memo, p) ? memo : model_cfg;
+    ScopedDev scratch;
     const size_t out_floats = (size_t)p.M * (size_t)(p.out_pixel_stride > p.Cout ? p.out_pixel_stride : p.Cout) + 4096;
-    if (hipMalloc((void**)&scratch, out_floats * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return model_cfg; }
+    if (hipMalloc((void**)&scratch.p, out_floats * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return model_cfg; }
     ConvParams q = p;
-    q.out = scratch;
-    if (q.n_split) { q.out2 = scratch; q.n_split = 0; }          // (timing only: one destination)
+    q.out = scratch.p;
+    if (q.n_split) { q.out2 = scratch.p; q.n_split = 0; }          // (timing only: one destination)
     q.out_batch_stride = (long)p.Ho * p.Wo * q.out_pixel_stride;
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    int best = model_cfg;
-    float best_ms = 1e30f, model_ms = 0.f;
+    std::vector<int> candidates;
     for (int c = 0; c < conv_num_configs(); ++c) {
         if (!conv_config_valid(c, q) || !conv_config_allowed(c, q.bf16)) continue;
         const char* cn = conv_config_name(c);
         if (!strncmp(cn, "wino_", 5) || !strncmp(cn, "skinny_", 7) || (!strncmp(cn, "direct", 6) && c != model_cfg)) continue;
-        if (conv_launch(q, c, st)) { (void)hipGetLastError(); continue; }
-        float ms = 1e30f;
-        for (int trial = 0; trial < 3; ++trial) {
-            (void)hipEventRecord(e0, st);
-            for (int r = 0; r < 3; ++r) (void)conv_launch(q, c, st);
-            (void)hipEventRecord(e1, st);
-            (void)hipEventSynchronize(e1);
-            float t = 0.f;
-            (void)hipEventElapsedTime(&t, e0, e1);
-            ms = t < ms ? t : ms;
-            if (trial == 0 && ms > 2.0f * best_ms) break;
-        }
-        if (c == model_cfg) model_ms = ms;
-        if (ms < best_ms) { best_ms = ms; best = c; }
+        candidates.push_back(c);
     }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    (void)hipFree(scratch);
+    TimedPick r;
+    if (!time_candidates(candidates, model_cfg, 3, st, [&](int c) { return conv_launch(q, c, st); }, &r)) return model_cfg;
     if (verbose)
         fprintf(stderr, "[ssd train tune] M=%ld K=%d N=%d k%dx%d s%d: model %s %.1f us -> %s %.1f us\n", p.M, p.K, p.Cout, p.kh, p.kw,
-                p.stride, conv_config_name(model_cfg), model_ms * 1000.f / 3, conv_config_name(best), best_ms * 1000.f / 3);
-    {
-        std::lock_guard<std::mutex> lock(train_picks_mutex());
-        train_picks()[k] = best;
-    }
-    return best;
+                p.stride, conv_config_name(model_cfg), r.model_ms * 1000.f / 3, conv_config_name(r.best), r.best_ms * 1000.f / 3);
+    pick_memo().store(k, r.best);
+    return r.best;
 }
 
-static int launch_conv(ConvParams& p, hipStream_t st) {
-    p.vec_store = (((uintptr_t)p.out & 15) == 0) && (p.out_pixel_stride % 4 == 0) && (p.out_batch_stride % 4 == 0);
+// Launches one training conv on its tile and adds its matrix-core FLOPs to the step's counters, per instruction family
+// (bench.py prices each at its own peak): s.step_flops[0] fp32-MFMA tiles, [1] split-bf16 / bf16 tiles
+static int launch_conv(ssd_train_state& s, ConvParams& p, hipStream_t st) {
+    p.vec_store = conv_vec_store(p);
     int cfg = conv_pick_config(p);
     SSD_UNSUPPORTED_IF(cfg < 0, "train: no conv kernel for Cin=%d Cout=%d k=%dx%d", p.Cin, p.Cout, p.kh, p.kw);
-    static const int tune = getenv("SSD_HIP_TRAIN_AUTOTUNE") ? atoi(getenv("SSD_HIP_TRAIN_AUTOTUNE")) : 1;
-    if (tune) {
+    if (const int tune = train_env().autotune) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing(st, &cs);
         if (cs == hipStreamCaptureStatusNone) cfg = pick_measured(p, st, cfg, tune > 1);
     }
     const char* cn = conv_config_name(cfg);
-    g_step_flops[(strncmp(cn, "mfma3_", 6) == 0 || strncmp(cn, "bf16_", 5) == 0) ? 1 : 0] += 2.0 * (double)p.M * p.K * p.Cout;
+    s.step_flops[(strncmp(cn, "mfma3_", 6) == 0 || strncmp(cn, "bf16_", 5) == 0) ? 1 : 0] += 2.0 * (double)p.M * p.K * p.Cout;
     return conv_launch(p, cfg, st);
 }
 
@@ -1193,7 +1229,7 @@ static long wgrad_chunks(const Layer& l, int B, int N, const WgradCfg* cfg, long
     return chunks;
 }
 static int wgrad_with(const Layer& l, int B, const float* x, const float* g, int ldg, int N, float* dW, hipStream_t st,
-                      const WgradCfg* cfg, bool count, float* partial, size_t partial_floats) {
+                      const WgradCfg* cfg, float* partial, size_t partial_floats) {
     WgradParams p{};
     p.x = x; p.g = g;
     p.B = B; p.H = l.H; p.W = l.W; p.Cin = l.Cin; p.Ho = l.Ho; p.Wo = l.Wo;
@@ -1215,22 +1251,16 @@ static int wgrad_with(const Layer& l, int B, const float* x, const float* g, int
     p.partial = partial;
     hipLaunchKernelGGL(cfg->fn, dim3((unsigned)tiles, (unsigned)chunks), dim3(256), 0, st, p);
     SSD_LAUNCH_CHECK();
-    if (count) g_step_flops[2] += 2.0 * (double)p.M * p.K * N;
     return chunk_sum(partial, chunks, (long)kn, dW, st);
 }
 // the training step's slab: grow-only, its own (weight gradients may run beside the reductions of the main chain)
 static int wgrad_with(ssd_train_state& s, const Layer& l, int B, const float* x, const float* g, int ldg, int N, float* dW,
-                      hipStream_t st, const WgradCfg* cfg, bool count) {
+                      hipStream_t st, const WgradCfg* cfg) {
     long rpc = 0;
     const size_t need = (size_t)wgrad_chunks(l, B, N, cfg, &rpc, nullptr) * l.kh * l.kw * l.Cin * N;
-    if (need > s.partial_w_floats) {
-        float* np = nullptr;
-        int rca = talloc(s, need, &np);
-        if (rca) return rca;
-        s.partial_w = np;
-        s.partial_w_floats = need;
-    }
-    return wgrad_with(l, B, x, g, ldg, N, dW, st, cfg, count, s.partial_w, s.partial_w_floats);
+    const int rc = ensure_slab(s, need, &s.partial_w, &s.partial_w_floats);
+    if (rc) return rc;
+    return wgrad_with(l, B, x, g, ldg, N, dW, st, cfg, s.partial_w, s.partial_w_floats);
 }
 
 // Heuristic tile shape: least padded tile area first (MFMA work); among equals the shape that stages the fewest floats
@@ -1274,52 +1304,485 @@ static int dw_bwd_launch(const DwBwdParams& dp, long chunks, float* dw_out, hipS
 // stages the fewest floats per M row (every tile re-reads its 32-row slabs of X and G: ctiles * ntiles * (tc + tn)).
 // Measured: by staged floats alone 128 x 128 wins everywhere, +4 % on VGG16 (512-channel layers, no padding) but -3 % on
 // MobileNetV2 (96 -> 576 expands padded to 128 x 640); the lexicographic rule keeps both.  With SSD_HIP_TRAIN_AUTOTUNE
-// (default on, see launch_conv) every shape of the table is timed the first time a layer is seen (dW is written, not
-// accumulated: running it repeatedly is harmless) and the fastest kept for the process.
+// (default on, see pick_measured) every shape of the table is timed the first time a layer is seen (dW is written, not
+// accumulated: running it repeatedly is harmless) and the fastest kept for the process.  The launch that counts adds its
+// matrix-core FLOPs to s.step_flops[2].
 static int wgrad(ssd_train_state& s, const Layer& l, int B, const float* x, const float* g, int ldg, int N, float* dW,
                  hipStream_t st) {
     const WgradCfg* cfg = wgrad_heuristic(l, N);
-    static const int tune = getenv("SSD_HIP_TRAIN_AUTOTUNE") ? atoi(getenv("SSD_HIP_TRAIN_AUTOTUNE")) : 1;
+    const long M = (long)B * l.Ho * l.Wo;
+    const int K = l.kh * l.kw * l.Cin;
+    const int tune = train_env().autotune;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(st, &cs);
     if (tune && cs == hipStreamCaptureStatusNone) {
         TrainPickKey k{};
         memset(&k, 0, sizeof(k));
-        k.M = (long)B * l.Ho * l.Wo; k.K = l.kh * l.kw * l.Cin; k.Cout = N; k.kh = l.kh; k.kw = l.kw; k.stride = l.stride;
+        k.M = M; k.K = K; k.Cout = N; k.kh = l.kh; k.kw = l.kw; k.stride = l.stride;
         k.dil = l.dil; k.H = l.H; k.W = l.W; k.Cin = l.Cin; k.flags = (1 << 20) | ldg;      // bit 20: a weight gradient
-        auto it = train_picks().find(k);
-        if (it != train_picks().end()) {
-            cfg = &kWgrad[it->second];
-        } else {
-            hipEvent_t e0, e1;
-            (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-            int best = (int)(cfg - kWgrad);
-            float best_ms = 1e30f, model_ms = 0.f;
-            for (int c = 0; c < (int)(sizeof(kWgrad) / sizeof(kWgrad[0])); ++c) {
-                if (wgrad_with(s, l, B, x, g, ldg, N, dW, st, &kWgrad[c], false)) { (void)hipGetLastError(); continue; }
-                float ms = 1e30f;
-                for (int trial = 0; trial < 3; ++trial) {
-                    (void)hipEventRecord(e0, st);
-                    for (int r = 0; r < 2; ++r) (void)wgrad_with(s, l, B, x, g, ldg, N, dW, st, &kWgrad[c], false);
-                    (void)hipEventRecord(e1, st);
-                    (void)hipEventSynchronize(e1);
-                    float t = 0.f;
-                    (void)hipEventElapsedTime(&t, e0, e1);
-                    ms = t < ms ? t : ms;
-                    if (trial == 0 && ms > 2.0f * best_ms) break;
-                }
-                if (&kWgrad[c] == cfg) model_ms = ms;
-                if (ms < best_ms) { best_ms = ms; best = c; }
+        int pick = (int)(cfg - kWgrad);
+        if (!pick_memo().lookup(k, &pick)) {
+            std::vector<int> candidates;
+            for (int c = 0; c < (int)(sizeof(kWgrad) / sizeof(kWgrad[0])); ++c) candidates.push_back(c);
+            TimedPick r;
+            const auto launch = [&](int c) { return wgrad_with(s, l, B, x, g, ldg, N, dW, st, &kWgrad[c]); };
+            if (time_candidates(candidates, pick, 2, st, launch, &r)) {
+                if (tune > 1)
+                    fprintf(stderr, "[ssd train tune] wgrad M=%ld K=%d N=%d: heuristic %dx%d %.1f us -> %dx%d %.1f us\n", M, K, N, cfg->tc,
+                            cfg->tn, r.model_ms * 500.f, kWgrad[r.best].tc, kWgrad[r.best].tn, r.best_ms * 500.f);
+                pick_memo().store(k, r.best);
+                pick = r.best;
             }
-            (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-            if (tune > 1)
-                fprintf(stderr, "[ssd train tune] wgrad M=%ld K=%d N=%d: heuristic %dx%d %.1f us -> %dx%d %.1f us\n", k.M, k.K, N, cfg->tc,
-                        cfg->tn, model_ms * 500.f, kWgrad[best].tc, kWgrad[best].tn, best_ms * 500.f);
-            train_picks()[k] = best;
-            cfg = &kWgrad[best];
+        }
+        cfg = &kWgrad[pick];
+    }
+    s.step_flops[2] += 2.0 * (double)M * K * N;
+    return wgrad_with(s, l, B, x, g, ldg, N, dW, st, cfg);
+}
+
+// ------------------------------------------------------------------ the step, layer by layer
+// What one ssd_net_train_forward_backward call carries from layer to layer.
+struct StepCtx {
+    ssd_net* net;
+    ssd_train_state& s;
+    hipStream_t st;             // the caller's stream
+    int B;
+    float* grads;               // the caller's flat gradient vector
+    // The dense convs' weight gradients run on the side stream (s.wstream) beside the rest of the backward: they are needed
+    // only at the end of the step / at their gradient bucket, the data-gradient chain does not wait for them.  Under gradient
+    // buckets only with SSD_HIP_WGRAD_SIDE_BUCKETS on (the default; off: the communication stream already runs beside the
+    // backward, and a third stream measured slower at world size 1 -- 12.6 against 11.5 ms -- than the weight gradients in line)
+    bool side;
+    int dy_cur = 0;             // dY alternates between s.dy_buf[0] and [1]
+    size_t next_bucket = 0;     // gradient buckets at and above this one are published
+
+    // next dY buffer: the main stream first waits for the weight gradient still reading it
+    float* acquire_dy() {
+        dy_cur ^= 1;
+        if (s.wstream && s.wpending[dy_cur]) {
+            (void)hipStreamWaitEvent(st, s.ev_wdone[dy_cur], 0);
+            s.wpending[dy_cur] = false;
+        }
+        return s.dy_buf[dy_cur];
+    }
+    // everything issued on the side stream so far is ordered before what follows on st
+    int join_wgrads() {
+        if (!s.wstream) return SSD_OK;
+        SSD_HIP(hipEventRecord(s.ev_wall, s.wstream));
+        SSD_HIP(hipStreamWaitEvent(st, s.ev_wall, 0));
+        s.wpending[0] = s.wpending[1] = false;
+        return SSD_OK;
+    }
+    // Everything at or above `threshold` in the flat vector is final: publish those buckets.  A bucket is final when BOTH
+    // streams have passed this point: the main stream (BatchNorm / depthwise / bias gradients, the data-gradient chain) and the
+    // side stream (the dense convs' weight gradients).  The bucket's event is recorded on the SIDE stream behind a wait for the
+    // main stream's position -- the main stream itself never waits (round 4 joined the side stream INTO the main stream here and
+    // therefore ran the weight gradients in line under buckets: +0.9 ms per step).
+    int mark_ready(long threshold) {
+        bool joined = false;
+        for (; next_bucket > 0 && s.bucket_lo[next_bucket - 1] >= threshold; --next_bucket) {
+            const size_t k = next_bucket - 1;
+            if (train_env().debug_buckets) fprintf(stderr, "[ssd] bucket %zu (lo %ld) final at threshold %ld\n", k, s.bucket_lo[k], threshold);
+            if (!joined && side) {
+                SSD_HIP(hipEventRecord(s.ev_main_pos, st));
+                SSD_HIP(hipStreamWaitEvent(s.wstream, s.ev_main_pos, 0));
+            } else if (!joined) {
+                const int rj = join_wgrads();
+                if (rj) return rj;
+            }
+            joined = true;
+            SSD_HIP(hipEventRecord(s.bucket_ev[k], side ? s.wstream : st));
+        }
+        return SSD_OK;
+    }
+};
+
+static int train_forward_conv(StepCtx& c, const Layer& l, TrainLayer& t) {
+    ssd_train_state& s = c.s;
+    ConvParams p = dense_conv_params(c.B, l.H, l.W, l.Cin, l.Cout, l.kh, l.kw, l.stride, l.dil, l.pt, l.pl, l.Ho, l.Wo);
+    p.in = s.act[l.in];
+    p.w = t.wfwd;
+    p.w3 = conv_split_planes(t.wfwd, l.kh * l.kw * l.Cin, l.Cout);
+    p.bf16 = c.net->precision;          // precision 1: the cost model takes the bf16 (one-product) tiles
+    p.act = l.p_bn >= 0 ? SSD_ACT_NONE : l.act;      // BatchNorm layers: the activation follows the normalisation (bn_apply_kernel)
+    if (l.p_bn >= 0) {
+        p.out = t.pre;
+    } else if (l.head_kind == 0) {
+        p.shift = l.p_bias2 >= 0 ? nullptr : c.net->params[l.p_bias].dev;
+        p.out = s.act[l.out];
+    } else {
+        // fused label + box head conv: bias vector = [label bias | box bias]
+        SSD_HIP(hipMemcpyAsync(s.dgamma_tmp, c.net->params[l.p_bias].dev, (size_t)l.Cout1 * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+        SSD_HIP(hipMemcpyAsync(s.dgamma_tmp + l.Cout1, c.net->params[l.p_bias2].dev, (size_t)(l.Cout - l.Cout1) * sizeof(float),
+                               hipMemcpyDeviceToDevice, c.st));
+        p.shift = s.dgamma_tmp;
+        conv_route_head(p, l, s.probs, s.deltas);
+    }
+    return launch_conv(s, p, c.st);
+}
+
+// training-mode forward of layer i: BatchNorm on the batch statistics, moving averages updated
+static int train_forward_layer(StepCtx& c, size_t i) {
+    ssd_train_state& s = c.s;
+    const ssd_net* net = c.net;
+    const Layer& l = net->layers[i];
+    TrainLayer& t = s.tl[i];
+    const long M = (long)c.B * l.Ho * l.Wo;
+    const float* x = s.act[l.in];
+    if (l.kind == LK_POOL) return launch_maxpool(x, c.B, l.H, l.W, l.Cin, l.kh, l.stride, l.pt, l.pl, l.Ho, l.Wo, s.act[l.out], c.st);
+    if (l.kind == LK_L2NORM) return launch_l2norm(x, M, l.Cin, net->params[l.p_gamma].dev, s.act[l.out], c.st);
+    int rc = l.kind == LK_CONV ? train_forward_conv(c, l, t)
+                               : launch_dwconv3x3(x, c.B, l.H, l.W, l.Cin, l.stride, l.pt, l.pl, l.Ho, l.Wo, net->params[l.p_kernel].dev,
+                                                  nullptr, nullptr, SSD_ACT_NONE, t.pre, c.st);
+    if (rc || l.p_bn < 0) return rc;
+    rc = bn_stats(s, t, M, l.Cout, net->params[l.p_bn + 2].dev, net->params[l.p_bn + 3].dev, c.st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(M * l.Cout)), dim3(256), 0, c.st, t.pre, M, l.Cout, t.mean, t.istd,
+                       net->params[l.p_bn].dev, net->params[l.p_bn + 1].dev, l.act, l.res >= 0 ? s.act[l.res] : nullptr, s.act[l.out]);
+    SSD_LAUNCH_CHECK();
+    return SSD_OK;
+}
+
+static int bwd_pool(StepCtx& c, const Layer& l) {
+    ssd_train_state& s = c.s;
+    PoolBwdParams pp{};
+    pp.x = s.act[l.in]; pp.g = s.gact[l.out]; pp.dx = s.gact[l.in];
+    pp.B = c.B; pp.H = l.H; pp.W = l.W; pp.C = l.Cin; pp.Ho = l.Ho; pp.Wo = l.Wo;
+    pp.k = l.kh; pp.stride = l.stride; pp.pad_t = l.pt; pp.pad_l = l.pl;
+    pp.accumulate = s.gwritten[l.in];
+    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for((long)c.B * l.H * l.W * l.Cin)), dim3(256), 0, c.st, pp);
+    SSD_LAUNCH_CHECK();
+    s.gwritten[l.in] = 1;
+    return SSD_OK;
+}
+
+// L2 normalisation: dX, and d gamma = column sums of the per-element products the kernel leaves in `tmp`
+static int bwd_l2norm(StepCtx& c, const Layer& l, const TrainLayer& t, float* tmp) {
+    ssd_train_state& s = c.s;
+    const long M = (long)c.B * l.Ho * l.Wo, blocks = (M + 3) / 4;
+    hipLaunchKernelGGL(l2norm_bwd_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, c.st, s.act[l.in], s.gact[l.out],
+                       c.net->params[l.p_gamma].dev, M, l.Cin, s.gact[l.in], (int)s.gwritten[l.in], tmp);
+    SSD_LAUNCH_CHECK();
+    s.gwritten[l.in] = 1;
+    return col_sum(s, tmp, M, l.Cin, l.Cin, 1.0f, c.grads + t.g_gamma, c.st);
+}
+
+// The three ways to dY, the gradient w.r.t. a conv / depthwise output as a dense [M][*ldy] matrix (in `dyb` unless it is dOut
+// itself); each also writes the layer's bias or BatchNorm parameter gradients.
+// Head conv: one level gathered out of the concatenated [B,N,K] gradients of the loss; bias gradients = its column sums
+static int bwd_head_dy(StepCtx& c, const Layer& l, const TrainLayer& t, float* dyb, const float** dY, int* ldy) {
+    ssd_train_state& s = c.s;
+    const long M = (long)c.B * l.Ho * l.Wo;
+    const int ld = t.cpad, C2 = l.Cout - l.Cout1;
+    if (t.cpad != l.Cout) SSD_HIP(hipMemsetAsync(dyb, 0, (size_t)M * ld * sizeof(float), c.st));
+    hipLaunchKernelGGL(gather_head_kernel, dim3(grid_for(M * l.Cout1)), dim3(256), 0, c.st, s.glogits, l.head_bs, l.head_off, l.head_ps,
+                       c.B, l.Ho * l.Wo, l.Cout1, dyb, ld, 0);
+    hipLaunchKernelGGL(gather_head_kernel, dim3(grid_for(M * C2)), dim3(256), 0, c.st, s.gdeltas, l.head2_bs, l.head2_off, l.head2_ps,
+                       c.B, l.Ho * l.Wo, C2, dyb, ld, l.Cout1);
+    SSD_LAUNCH_CHECK();
+    const int rc = col_sum(s, dyb, M, l.Cout, ld, 1.0f, s.dbeta_tmp, c.st);
+    if (rc) return rc;
+    SSD_HIP(hipMemcpyAsync(c.grads + t.g_bias, s.dbeta_tmp, (size_t)l.Cout1 * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+    SSD_HIP(hipMemcpyAsync(c.grads + t.g_bias2, s.dbeta_tmp + l.Cout1, (size_t)C2 * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+    *dY = dyb; *ldy = ld;
+    return SSD_OK;
+}
+// out = bn(conv) + res: the residual branch receives dOut as is
+static int bwd_residual(StepCtx& c, const Layer& l) {
+    if (l.res < 0) return SSD_OK;
+    const long n = (long)c.B * l.Ho * l.Wo * l.Cout;
+    hipLaunchKernelGGL(add_kernel, dim3(grid_for(n)), dim3(256), 0, c.st, c.s.gact[l.res], c.s.gact[l.out], n, (int)c.s.gwritten[l.res]);
+    SSD_LAUNCH_CHECK();
+    c.s.gwritten[l.res] = 1;
+    return SSD_OK;
+}
+static int bwd_bn_dy(StepCtx& c, const Layer& l, const TrainLayer& t, float* dyb, const float** dY) {
+    const float* dOut = c.s.gact[l.out];
+    int rc = bwd_residual(c, l);
+    if (rc) return rc;
+    const long M = (long)c.B * l.Ho * l.Wo;
+    const float *gamma = c.net->params[l.p_bn].dev, *beta = c.net->params[l.p_bn + 1].dev;
+    float *dgamma = c.grads + t.g_gamma, *dbeta = c.grads + t.g_beta;
+    RedParams rp{};
+    rp.a = dOut; rp.b = t.pre; rp.mean = t.mean; rp.istd = t.istd; rp.gamma = gamma; rp.beta = beta;
+    rp.M = M; rp.C = l.Cout; rp.lda = l.Cout; rp.act = l.act;
+    long chunks = 0;
+    rc = col_reduce<RED_BN_BWD>(c.s, rp, &chunks, c.st);
+    if (!rc) rc = col_finalize(c.s, chunks, l.Cout, 1.0f, dbeta, dgamma, 0, c.st);      // s1 = dbeta, s2 = dgamma
+    if (rc) return rc;
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(M * l.Cout)), dim3(256), 0, c.st, dOut, t.pre, M, l.Cout, t.mean, t.istd,
+                       gamma, beta, l.act, dgamma, dbeta, dyb);
+    SSD_LAUNCH_CHECK();
+    *dY = dyb;
+    return SSD_OK;
+}
+static int bwd_bias_act_dy(StepCtx& c, const Layer& l, const TrainLayer& t, float* dyb, const float** dY) {
+    ssd_train_state& s = c.s;
+    const float* dOut = s.gact[l.out];
+    int rc = bwd_residual(c, l);
+    if (rc) return rc;
+    const long M = (long)c.B * l.Ho * l.Wo;
+    RedParams rp{};
+    rp.a = dOut; rp.b = l.act ? s.act[l.out] : nullptr;
+    rp.M = M; rp.C = l.Cout; rp.lda = l.Cout; rp.act = l.act;
+    long chunks = 0;
+    rc = col_reduce<RED_ACT_BWD>(s, rp, &chunks, c.st);
+    if (!rc) rc = col_finalize(s, chunks, l.Cout, 1.0f, c.grads + t.g_bias, nullptr, 0, c.st);
+    if (rc) return rc;
+    *dY = dOut;
+    if (!l.act) return SSD_OK;
+    hipLaunchKernelGGL(act_bwd_kernel, dim3(grid_for(M * l.Cout)), dim3(256), 0, c.st, dOut, s.act[l.out], M * l.Cout, l.act, dyb);
+    SSD_LAUNCH_CHECK();
+    *dY = dyb;
+    return SSD_OK;
+}
+
+static int bwd_depthwise(StepCtx& c, const Layer& l, const TrainLayer& t, const float* dY) {
+    ssd_train_state& s = c.s;
+    DwBwdParams dp{};
+    dp.x = s.act[l.in]; dp.g = dY; dp.w = c.net->params[l.p_kernel].dev; dp.dx = s.gact[l.in];
+    dp.B = c.B; dp.H = l.H; dp.W = l.W; dp.C = l.Cin; dp.Ho = l.Ho; dp.Wo = l.Wo;
+    dp.stride = l.stride; dp.pad_t = l.pt; dp.pad_l = l.pl;
+    dp.M = (long)c.B * l.Ho * l.Wo;
+    dp.accumulate = s.gwritten[l.in];
+    const long chunks = dw_bwd_chunks(dp);
+    int rc = ensure_slab(s, (size_t)chunks * 9 * l.Cin, &s.partial, &s.partial_floats);
+    if (rc) return rc;
+    dp.partial = s.partial;
+    s.gwritten[l.in] = 1;
+    return dw_bwd_launch(dp, chunks, c.grads + t.g_kernel, c.st);
+}
+
+// dense conv: weight gradient(s), on the side stream behind dY (StepCtx::side)
+static int bwd_dense_wgrad(StepCtx& c, const Layer& l, const TrainLayer& t, const float* dY, int ldy, const float* dyb) {
+    ssd_train_state& s = c.s;
+    const float* x = s.act[l.in];
+    hipStream_t wst = c.side ? s.wstream : c.st;
+    if (c.side) {
+        SSD_HIP(hipEventRecord(s.ev_dy, c.st));
+        SSD_HIP(hipStreamWaitEvent(s.wstream, s.ev_dy, 0));
+    }
+    int rc;
+    if (l.p_kernel2 < 0) {
+        rc = wgrad(s, l, c.B, x, dY, ldy, l.Cout, c.grads + t.g_kernel, wst);
+    } else {
+        rc = wgrad(s, l, c.B, x, dY, ldy, l.Cout1, c.grads + t.g_kernel, wst);
+        if (!rc) rc = wgrad(s, l, c.B, x, dY + l.Cout1, ldy, l.Cout - l.Cout1, c.grads + t.g_kernel2, wst);
+    }
+    if (rc) return rc;
+    // VGG16: kernel_regularizer=l2(5e-4) on every backbone / extra conv (models/ssd_vgg16.py:44-45; the head
+    // convs of models/header.py have none): d(5e-4 * sum w^2)/dw = 1e-3 * w, added right behind the layer's
+    // weight gradient so that the gradient bucket it lies in is final when the backward has passed the layer
+    if (c.net->backbone == SSD_VGG16 && !l.head_kind) {
+        const Param& w = c.net->params[l.p_kernel];
+        hipLaunchKernelGGL(axpy_kernel, dim3(grid_for((long)w.count)), dim3(256), 0, wst, c.grads + t.g_kernel, w.dev, (long)w.count,
+                           2.0f * 5e-4f);
+        SSD_LAUNCH_CHECK();
+    }
+    if (c.side && dY == dyb) {             // the buffer may be rewritten only after this weight gradient
+        SSD_HIP(hipEventRecord(s.ev_wdone[c.dy_cur], s.wstream));
+        s.wpending[c.dy_cur] = true;
+    }
+    return SSD_OK;
+}
+
+// dense conv: data gradient = conv of dY (stride 2: zero-inserted first) with the rotated / transposed weights
+static int bwd_dense_dgrad(StepCtx& c, const Layer& l, const TrainLayer& t, const float* dY, int ldy) {
+    ssd_train_state& s = c.s;
+    const int d = l.dil, kh = l.kh, kw = l.kw;
+    const float* gin = dY;
+    int Hg = l.Ho, Wg = l.Wo;
+    if (l.stride == 2) {
+        Hg = (l.Ho - 1) * 2 + 1;
+        Wg = (l.Wo - 1) * 2 + 1;
+        SSD_HIP(hipMemsetAsync(s.scratch_dz, 0, (size_t)c.B * Hg * Wg * ldy * sizeof(float), c.st));
+        hipLaunchKernelGGL(dilate2_kernel, dim3(grid_for((long)c.B * l.Ho * l.Wo * ldy)), dim3(256), 0, c.st, dY, c.B, l.Ho, l.Wo, ldy, Hg,
+                           Wg, s.scratch_dz);
+        SSD_LAUNCH_CHECK();
+        gin = s.scratch_dz;
+    }
+    const int pt = (kh - 1) * d - l.pt, pl = (kw - 1) * d - l.pl;
+    SSD_UNSUPPORTED_IF(pt < 0 || pl < 0, "train: backward-data padding of %s is negative", l.name.c_str());
+    ConvParams p = dense_conv_params(c.B, Hg, Wg, ldy, l.Cin, kh, kw, 1, d, pt, pl, l.H, l.W);
+    p.in = gin;
+    p.w = t.wbwd;
+    p.w3 = conv_split_planes(t.wbwd, p.K, p.Cout);
+    p.bf16 = c.net->precision;
+    p.out = s.gact[l.in];
+    p.act = SSD_ACT_NONE;
+    p.residual = s.gwritten[l.in] ? s.gact[l.in] : nullptr;      // accumulate in the epilogue
+    s.gwritten[l.in] = 1;
+    return launch_conv(s, p, c.st);
+}
+
+// ------------------------------------------------------------------ ssd_net_train_begin, step by step
+struct TrainSizes {             // the largest of each scratch buffer over the layers
+    size_t max_out = 0, max_dz = 0;
+    int maxC = 0;
+};
+
+// flat parameter vector (trainable parameters in table order) with the Adam moments, and every parameter's offset in it
+static int begin_flat(const ssd_net* net, ssd_train_state& s) {
+    s.P = ssd_net_trainable_floats(net);
+    int rc = talloc(s, s.P, &s.flat);
+    if (!rc) rc = talloc(s, s.P, &s.m);
+    if (!rc) rc = talloc(s, s.P, &s.v);
+    s.poff.assign(net->params.size(), -1);
+    long off = 0;
+    for (size_t i = 0; i < net->params.size(); ++i) {
+        if (!trainable(net->params[i].name)) continue;
+        s.poff[i] = off;
+        off += (long)net->params[i].count;
+    }
+    return rc;
+}
+
+// activations and their gradients, then per layer: gradient offsets, BatchNorm buffers, packed weights; the scratch sizes
+static int begin_plan_layers(const ssd_net* net, ssd_train_state& s, TrainSizes& sz) {
+    const int batch = s.batch;
+    int rc = SSD_OK;
+    s.act.assign(net->tensors.size(), nullptr);
+    s.gact.assign(net->tensors.size(), nullptr);
+    s.gwritten.assign(net->tensors.size(), 0);
+    for (size_t i = 1; i < net->tensors.size() && !rc; ++i) {
+        rc = talloc(s, net->tensors[i].per_image * batch, &s.act[i]);
+        if (!rc) rc = talloc(s, net->tensors[i].per_image * batch, &s.gact[i]);
+    }
+    s.tl.assign(net->layers.size(), TrainLayer());
+    for (size_t i = 0; i < net->layers.size() && !rc; ++i) {
+        const Layer& l = net->layers[i];
+        if (!train_runs(l)) continue;
+        TrainLayer& t = s.tl[i];
+        t.active = true;
+        const size_t mc = (size_t)batch * l.Ho * l.Wo * l.Cout;
+        sz.maxC = std::max(sz.maxC, l.Cout);
+        if (l.kind == LK_POOL) continue;
+        if (l.kind == LK_L2NORM) {
+            t.g_gamma = s.poff[l.p_gamma];
+            sz.max_out = std::max(sz.max_out, mc);
+            continue;
+        }
+        t.g_kernel = s.poff[l.p_kernel];
+        if (l.p_bias >= 0) t.g_bias = s.poff[l.p_bias];
+        if (l.p_kernel2 >= 0) { t.g_kernel2 = s.poff[l.p_kernel2]; t.g_bias2 = s.poff[l.p_bias2]; }
+        if (l.p_bn >= 0) {
+            t.g_gamma = s.poff[l.p_bn];
+            t.g_beta = s.poff[l.p_bn + 1];
+            rc = talloc(s, mc, &t.pre);
+            if (!rc) rc = talloc(s, l.Cout, &t.mean);
+            if (!rc) rc = talloc(s, l.Cout, &t.var);
+            if (!rc) rc = talloc(s, l.Cout, &t.istd);
+        }
+        if (l.kind != LK_CONV) {
+            sz.max_out = std::max(sz.max_out, mc);
+            continue;
+        }
+        SSD_UNSUPPORTED_IF(l.stride > 2 || (l.stride == 2 && l.dil != 1), "train: unsupported conv geometry in %s", l.name.c_str());
+        if (!rc) rc = talloc(s, conv_packed_floats(l.kh * l.kw * l.Cin, l.Cout), &t.wfwd);
+        t.cpad = l.head_kind ? round_up(l.Cout, 32) : l.Cout;
+        sz.max_out = std::max(sz.max_out, (size_t)batch * l.Ho * l.Wo * t.cpad);
+        if (l.in == 0) continue;        // the image needs no gradient
+        if (!rc) rc = talloc(s, conv_packed_floats(l.kh * l.kw * t.cpad, l.Cin), &t.wbwd);
+        if (l.stride == 2) sz.max_dz = std::max(sz.max_dz, (size_t)batch * ((l.Ho - 1) * 2 + 1) * ((l.Wo - 1) * 2 + 1) * l.Cout);
+    }
+    return rc;
+}
+
+// one PackJob per forward / backward-data weight matrix (the parameters will live at flat + poff)
+static int begin_pack_jobs(const ssd_net* net, ssd_train_state& s, std::vector<PackJob>& jobs) {
+    for (size_t i = 0; i < net->layers.size(); ++i) {
+        const Layer& l = net->layers[i];
+        const TrainLayer& t = s.tl[i];
+        if (!t.active || l.kind != LK_CONV) continue;
+        PackJob j{};
+        j.bf16 = net->precision;
+        j.w = s.flat + s.poff[l.p_kernel];
+        j.w2 = l.p_kernel2 >= 0 ? s.flat + s.poff[l.p_kernel2] : nullptr;
+        j.K = l.kh * l.kw * l.Cin;
+        j.Cout = l.Cout;
+        j.Cout1 = l.p_kernel2 >= 0 ? l.Cout1 : l.Cout;
+        j.kh = l.kh; j.kw = l.kw; j.Ci = l.Cin; j.CoPad = t.cpad;
+        j.mode = 0; j.dst = t.wfwd; j.Kpad = conv_kpad(j.K); j.Npad = conv_npad(l.Cout);
+        jobs.push_back(j);
+        if (t.wbwd) {
+            j.mode = 1; j.dst = t.wbwd; j.Kpad = conv_kpad(l.kh * l.kw * t.cpad); j.Npad = conv_npad(l.Cin);
+            jobs.push_back(j);
         }
     }
-    return wgrad_with(s, l, B, x, g, ldg, N, dW, st, cfg, true);
+    for (const PackJob& j : jobs)
+        SSD_UNSUPPORTED_IF((long)j.Npad * j.Kpad > 0x7fffffffL, "train: a packed weight matrix of %d x %d exceeds 32-bit indexing", j.Npad, j.Kpad);
+    s.n_pack_jobs = (int)jobs.size();
+    s.precision = net->precision;
+    return jobs.empty() ? SSD_OK : talloc(s, (jobs.size() * sizeof(PackJob) + 3) / 4, &s.pack_jobs);
+}
+
+// the dY ping-pong, the side stream of the weight gradients with its events, and the scratch of the backward and the loss
+static int begin_streams_scratch(const ssd_net* net, ssd_train_state& s, const TrainSizes& sz) {
+    int rc = talloc(s, sz.max_out, &s.dy_buf[0]);
+    if (!rc) rc = talloc(s, sz.max_out, &s.dy_buf[1]);
+    if (rc) return rc;
+    if (train_env().wgrad_stream) {
+        hipEvent_t* const evs[] = {&s.ev_dy, &s.ev_wdone[0], &s.ev_wdone[1], &s.ev_wall, &s.ev_main_pos};
+        bool ok = hipStreamCreateWithFlags(&s.wstream, hipStreamNonBlocking) == hipSuccess;
+        for (hipEvent_t* e : evs) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            set_error("ssd_net_train_begin: side stream / events for the weight gradients could not be created");
+            return SSD_E_HIP;
+        }
+    }
+    const size_t BN = (size_t)s.batch * net->num_priors;
+    rc = talloc(s, sz.max_dz, &s.scratch_dz);
+    if (!rc) rc = talloc(s, sz.maxC, &s.dgamma_tmp);
+    if (!rc) rc = talloc(s, sz.maxC, &s.dbeta_tmp);
+    if (!rc) rc = talloc(s, BN * 4, &s.deltas);
+    if (!rc) rc = talloc(s, BN * net->L, &s.probs);
+    if (!rc) rc = talloc(s, BN * 4, &s.gdeltas);
+    if (!rc) rc = talloc(s, BN * net->L, &s.glogits);
+    if (rc) return rc;
+    s.loss_ws_bytes = ssd_loss_workspace_bytes(s.batch, net->num_priors);
+    if (hipMalloc(&s.loss_ws, s.loss_ws_bytes) != hipSuccess) {
+        set_error("ssd_net_train_begin: loss workspace allocation failed");
+        return SSD_E_HIP;
+    }
+    return SSD_OK;
+}
+
+// Every allocation succeeded: adopt the optimiser state of `net`'s previous plan (a re-plan for a larger batch keeps it) and
+// move the parameters into the flat vector.  Nothing of the net is touched before the last copy has succeeded.
+static int begin_adopt(ssd_net* net, ssd_train_state* s, const std::vector<PackJob>& jobs) {
+    ssd_train_state* old = net->train;
+    bool copy_failed = false;
+    if (old) {
+        copy_failed |= hipMemcpy(s->m, old->m, s->P * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess;
+        copy_failed |= hipMemcpy(s->v, old->v, s->P * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess;
+        s->step = old->step;
+    } else {
+        copy_failed |= hipMemset(s->m, 0, s->P * sizeof(float)) != hipSuccess;
+        copy_failed |= hipMemset(s->v, 0, s->P * sizeof(float)) != hipSuccess;
+    }
+    for (size_t i = 0; i < net->params.size() && !copy_failed; ++i)
+        if (s->poff[i] >= 0)
+            copy_failed |= hipMemcpy(s->flat + s->poff[i], net->params[i].dev, net->params[i].count * sizeof(float),
+                                     hipMemcpyDeviceToDevice) != hipSuccess;
+    if (s->n_pack_jobs)
+        copy_failed |= hipMemcpy(s->pack_jobs, jobs.data(), jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice) != hipSuccess;
+    if (copy_failed) {
+        set_error("ssd_net_train_begin: device copy failed");
+        return SSD_E_HIP;
+    }
+    for (size_t i = 0; i < net->params.size(); ++i) {
+        Param& p = net->params[i];
+        if (s->poff[i] < 0) continue;
+        if (!p.in_flat) (void)hipFree(p.dev);
+        p.dev = s->flat + s->poff[i];
+        p.in_flat = true;
+    }
+    if (old) ssd_train_state_free(old);
+    net->train = s;
+    net->finalized = false;          // derived inference weights must be rebuilt from the (moved) parameters
+    net->drop_graphs();
+    return SSD_OK;
 }
 
 }  // namespace ssd
@@ -1353,185 +1816,17 @@ int ssd_net_train_begin(ssd_net* net, int batch) {
             return SSD_E_STATE;
         }
     if (net->train && net->train->batch >= batch) return SSD_OK;
-    // keep optimiser state across a re-plan for a larger batch
-    ssd_train_state* old = net->train;
     auto* s = new ssd_train_state();
     s->batch = batch;
-    int rc = SSD_OK;
-    // ---- flat parameter vector (trainable parameters in table order); params point into it
-    s->P = ssd_net_trainable_floats(net);
-    rc = talloc(*s, s->P, &s->flat);
-    if (!rc) rc = talloc(*s, s->P, &s->m);
-    if (!rc) rc = talloc(*s, s->P, &s->v);
-    if (rc) { ssd_train_state_free(s); return rc; }
-    s->poff.assign(net->params.size(), -1);
-    {
-        long off = 0;
-        for (size_t i = 0; i < net->params.size(); ++i) {
-            if (!trainable(net->params[i].name)) continue;
-            s->poff[i] = off;
-            off += (long)net->params[i].count;
-        }
-    }
-    // ---- activations, activation gradients
-    s->act.assign(net->tensors.size(), nullptr);
-    s->gact.assign(net->tensors.size(), nullptr);
-    s->gwritten.assign(net->tensors.size(), 0);
-    for (size_t i = 1; i < net->tensors.size() && !rc; ++i) {
-        rc = talloc(*s, net->tensors[i].per_image * batch, &s->act[i]);
-        if (!rc) rc = talloc(*s, net->tensors[i].per_image * batch, &s->gact[i]);
-    }
-    // ---- per-layer buffers
-    s->tl.assign(net->layers.size(), TrainLayer());
-    size_t max_out = 0, max_dz = 0, max_w = 0;
-    int maxC = 0;
-    for (size_t i = 0; i < net->layers.size() && !rc; ++i) {
-        const Layer& l = net->layers[i];
-        if (!train_runs(l)) continue;
-        TrainLayer& t = s->tl[i];
-        t.active = true;
-        const size_t mc = (size_t)batch * l.Ho * l.Wo * l.Cout;
-        maxC = std::max(maxC, l.Cout);
-        if (l.kind == LK_POOL) continue;
-        if (l.kind == LK_L2NORM) {
-            t.g_gamma = s->poff[l.p_gamma];
-            max_out = std::max(max_out, mc);
-            continue;
-        }
-        t.g_kernel = s->poff[l.p_kernel];
-        if (l.p_bias >= 0) t.g_bias = s->poff[l.p_bias];
-        if (l.p_kernel2 >= 0) { t.g_kernel2 = s->poff[l.p_kernel2]; t.g_bias2 = s->poff[l.p_bias2]; }
-        if (l.p_bn >= 0) {
-            t.g_gamma = s->poff[l.p_bn];
-            t.g_beta = s->poff[l.p_bn + 1];
-            rc = talloc(*s, mc, &t.pre);
-            if (!rc) rc = talloc(*s, l.Cout, &t.mean);
-            if (!rc) rc = talloc(*s, l.Cout, &t.var);
-            if (!rc) rc = talloc(*s, l.Cout, &t.istd);
-        }
-        if (l.kind == LK_CONV) {
-            const int K = l.kh * l.kw * l.Cin;
-            if (!rc) rc = talloc(*s, conv_packed_floats(K, l.Cout), &t.wfwd);
-            t.cpad = l.head_kind ? round_up(l.Cout, 32) : l.Cout;
-            if (l.in != 0) {        // the image needs no gradient
-                const int Kb = l.kh * l.kw * t.cpad;
-                if (!rc) rc = talloc(*s, conv_packed_floats(Kb, l.Cin), &t.wbwd);
-                max_w = std::max(max_w, (size_t)l.kh * l.kw * t.cpad * l.Cin);
-            }
-            size_t dy = (size_t)batch * l.Ho * l.Wo * t.cpad;
-            max_out = std::max(max_out, dy);
-            if (l.stride == 2 && l.in != 0) {
-                const int Hz = (l.Ho - 1) * 2 + 1, Wz = (l.Wo - 1) * 2 + 1;
-                max_dz = std::max(max_dz, (size_t)batch * Hz * Wz * l.Cout);
-            }
-            SSD_UNSUPPORTED_IF(l.stride > 2 || (l.stride == 2 && l.dil != 1), "train: unsupported conv geometry in %s",
-                               l.name.c_str());
-        } else {
-            max_out = std::max(max_out, mc);
-        }
-    }
-    // one PackJob per forward / backward-data weight matrix (the parameters will live at flat + poff)
+    TrainSizes sz;
     std::vector<PackJob> jobs;
-    for (size_t i = 0; i < net->layers.size() && !rc; ++i) {
-        const Layer& l = net->layers[i];
-        const TrainLayer& t = s->tl[i];
-        if (!t.active || l.kind != LK_CONV) continue;
-        PackJob j{};
-        j.bf16 = net->precision;
-        j.w = s->flat + s->poff[l.p_kernel];
-        j.w2 = l.p_kernel2 >= 0 ? s->flat + s->poff[l.p_kernel2] : nullptr;
-        j.K = l.kh * l.kw * l.Cin;
-        j.Cout = l.Cout;
-        j.Cout1 = l.p_kernel2 >= 0 ? l.Cout1 : l.Cout;
-        j.kh = l.kh; j.kw = l.kw; j.Ci = l.Cin; j.CoPad = t.cpad;
-        j.mode = 0; j.dst = t.wfwd; j.Kpad = conv_kpad(j.K); j.Npad = conv_npad(l.Cout);
-        jobs.push_back(j);
-        if (t.wbwd) {
-            const int Kb = l.kh * l.kw * t.cpad;
-            j.mode = 1; j.dst = t.wbwd; j.Kpad = conv_kpad(Kb); j.Npad = conv_npad(l.Cin);
-            jobs.push_back(j);
-        }
-    }
-    for (const PackJob& j : jobs)
-        SSD_UNSUPPORTED_IF((long)j.Npad * j.Kpad > 0x7fffffffL, "train: a packed weight matrix of %d x %d exceeds 32-bit indexing", j.Npad, j.Kpad);
-    s->n_pack_jobs = (int)jobs.size();
-    s->precision = net->precision;
-    if (!rc && !jobs.empty()) rc = talloc(*s, (jobs.size() * sizeof(PackJob) + 3) / 4, &s->pack_jobs);
-    if (!rc) rc = talloc(*s, max_out, &s->scratch_dy);
-    if (!rc) rc = talloc(*s, max_out, &s->dy_buf[1]);
-    s->dy_buf[0] = s->scratch_dy;
-    if (!rc && getenv("SSD_HIP_TRAIN_WGRAD_STREAM") && atoi(getenv("SSD_HIP_TRAIN_WGRAD_STREAM")) == 0) {
-        s->wstream = nullptr;                       // diagnostics: weight gradients in line on the caller's stream
-    } else if (!rc) {
-        if (hipStreamCreateWithFlags(&s->wstream, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&s->ev_dy, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&s->ev_wdone[0], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&s->ev_wdone[1], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&s->ev_wall, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&s->ev_main_pos, hipEventDisableTiming) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("ssd_net_train_begin: side stream / events for the weight gradients could not be created");
-            rc = SSD_E_HIP;
-        }
-    }
-    if (!rc) rc = talloc(*s, max_dz, &s->scratch_dz);
-    if (!rc) rc = talloc(*s, max_w, &s->scratch_w);
-    if (!rc) rc = talloc(*s, maxC, &s->dgamma_tmp);
-    if (!rc) rc = talloc(*s, maxC, &s->dbeta_tmp);
-    const size_t N = net->num_priors;
-    if (!rc) rc = talloc(*s, (size_t)batch * N * 4, &s->deltas);
-    if (!rc) rc = talloc(*s, (size_t)batch * N * net->L, &s->probs);
-    if (!rc) rc = talloc(*s, (size_t)batch * N * 4, &s->gdeltas);
-    if (!rc) rc = talloc(*s, (size_t)batch * N * net->L, &s->glogits);
-    if (!rc) {
-        s->loss_ws_bytes = ssd_loss_workspace_bytes(batch, (int)N);
-        if (hipMalloc(&s->loss_ws, s->loss_ws_bytes) != hipSuccess) {
-            set_error("ssd_net_train_begin: loss workspace allocation failed");
-            rc = SSD_E_HIP;
-        }
-    }
-    if (rc) {                           // nothing of the net was touched yet: the previous state (if any) stays valid
-        ssd_train_state_free(s);
-        return rc;
-    }
-    // ---- every allocation succeeded: adopt the optimiser state and move the parameters
-    bool copy_failed = false;
-    if (old) {
-        copy_failed |= hipMemcpy(s->m, old->m, s->P * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess;
-        copy_failed |= hipMemcpy(s->v, old->v, s->P * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess;
-        s->step = old->step;
-    } else {
-        copy_failed |= hipMemset(s->m, 0, s->P * sizeof(float)) != hipSuccess;
-        copy_failed |= hipMemset(s->v, 0, s->P * sizeof(float)) != hipSuccess;
-    }
-    {
-        long off = 0;
-        for (size_t i = 0; i < net->params.size() && !copy_failed; ++i) {
-            if (s->poff[i] < 0) continue;
-            copy_failed |= hipMemcpy(s->flat + off, net->params[i].dev, net->params[i].count * sizeof(float),
-                                     hipMemcpyDeviceToDevice) != hipSuccess;
-            off += (long)net->params[i].count;
-        }
-    }
-    if (s->n_pack_jobs)
-        copy_failed |= hipMemcpy(s->pack_jobs, jobs.data(), jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice) != hipSuccess;
-    if (copy_failed) {
-        set_error("ssd_net_train_begin: device copy failed");
-        ssd_train_state_free(s);
-        return SSD_E_HIP;
-    }
-    for (size_t i = 0; i < net->params.size(); ++i) {
-        Param& p = net->params[i];
-        if (s->poff[i] < 0) continue;
-        if (!p.in_flat) (void)hipFree(p.dev);
-        p.dev = s->flat + s->poff[i];
-        p.in_flat = true;
-    }
-    if (old) ssd_train_state_free(old);
-    net->train = s;
-    net->finalized = false;          // derived inference weights must be rebuilt from the (moved) parameters
-    net->drop_graphs();
-    return SSD_OK;
+    int rc = begin_flat(net, *s);
+    if (!rc) rc = begin_plan_layers(net, *s, sz);
+    if (!rc) rc = begin_pack_jobs(net, *s, jobs);
+    if (!rc) rc = begin_streams_scratch(net, *s, sz);
+    if (!rc) rc = begin_adopt(net, s, jobs);
+    if (rc) ssd_train_state_free(s);        // nothing of the net was touched: the previous state (if any) stays valid
+    return rc;
 }
 
 // Training-mode forward + loss + backward.  grads_flat_dev [ssd_net_trainable_floats] receives
@@ -1552,12 +1847,11 @@ int ssd_net_train_forward_backward(ssd_net* net, const float* image_dev, int B, 
     hipStream_t st = (hipStream_t)stream;
     const int N = net->num_priors, L = net->L;
     s.act[0] = const_cast<float*>(image_dev);
+    s.step_flops[0] = s.step_flops[1] = s.step_flops[2] = 0;       // whatever path returns: they hold what this call issued
+    const bool side = s.wstream && (s.bucket_lo.empty() || train_env().side_buckets);
+    StepCtx c{net, s, st, B, grads_flat_dev, side};
+    c.next_bucket = s.bucket_lo.size();
     int rc = SSD_OK;
-    g_step_flops[0] = g_step_flops[1] = g_step_flops[2] = 0;
-    struct FlopsOut {           // whatever path returns: the state holds what this call issued
-        ssd_train_state& s;
-        ~FlopsOut() { for (int i = 0; i < 3; ++i) s.step_flops[i] = g_step_flops[i]; }
-    } flops_out{s};
 
     // re-pack the (just updated) weights of every conv: forward and backward-data forms, one launch
     if (s.n_pack_jobs) {
@@ -1565,70 +1859,8 @@ int ssd_net_train_forward_backward(ssd_net* net, const float* image_dev, int B, 
                            reinterpret_cast<const PackJob*>(s.pack_jobs));
         SSD_LAUNCH_CHECK();
     }
-    // ------------------------------------------------------------ forward (training mode)
-    for (size_t i = 0; i < net->layers.size(); ++i) {
-        const Layer& l = net->layers[i];
-        TrainLayer& t = s.tl[i];
-        if (!t.active) continue;
-        const long M = (long)B * l.Ho * l.Wo;
-        const float* x = s.act[l.in];
-        if (l.kind == LK_POOL) {
-            rc = launch_maxpool(x, B, l.H, l.W, l.Cin, l.kh, l.stride, l.pt, l.pl, l.Ho, l.Wo, s.act[l.out], st);
-            if (rc) return rc;
-            continue;
-        }
-        if (l.kind == LK_L2NORM) {
-            rc = launch_l2norm(x, M, l.Cin, net->params[l.p_gamma].dev, s.act[l.out], st);
-            if (rc) return rc;
-            continue;
-        }
-        if (l.kind == LK_CONV) {
-            ConvParams p = dense_conv_params(B, l.H, l.W, l.Cin, l.Cout, l.kh, l.kw, l.stride, l.dil, l.pt, l.pl, l.Ho, l.Wo);
-            p.in = x;
-            p.w = t.wfwd;
-            p.w3 = conv_split_planes(t.wfwd, l.kh * l.kw * l.Cin, l.Cout);
-            p.bf16 = net->precision;          // precision 1: the cost model takes the bf16 (one-product) tiles
-            if (l.p_bn >= 0) {
-                p.out = t.pre;
-                p.act = SSD_ACT_NONE;
-            } else {
-                p.shift = l.p_bias2 >= 0 ? nullptr : net->params[l.p_bias].dev;
-                p.act = l.act;
-                if (l.head_kind == 0) {
-                    p.out = s.act[l.out];
-                } else {
-                    // fused label + box head conv: bias vector = [label bias | box bias]
-                    SSD_HIP(hipMemcpyAsync(s.dgamma_tmp, net->params[l.p_bias].dev, (size_t)l.Cout1 * sizeof(float),
-                                           hipMemcpyDeviceToDevice, st));
-                    SSD_HIP(hipMemcpyAsync(s.dgamma_tmp + l.Cout1, net->params[l.p_bias2].dev,
-                                           (size_t)(l.Cout - l.Cout1) * sizeof(float), hipMemcpyDeviceToDevice, st));
-                    p.shift = s.dgamma_tmp;
-                    p.out = s.probs + l.head_off;
-                    p.out_pixel_stride = l.head_ps;
-                    p.out_batch_stride = l.head_bs;
-                    p.n_split = l.Cout1;
-                    p.out2 = s.deltas + l.head2_off;
-                    p.out2_pixel_stride = l.head2_ps;
-                    p.out2_batch_stride = l.head2_bs;
-                    p.vec_store2 = (p.out2_pixel_stride % 4 == 0) && (p.out2_batch_stride % 4 == 0);
-                }
-            }
-            rc = launch_conv(p, st);
-            if (rc) return rc;
-        } else {    // depthwise
-            rc = launch_dwconv3x3(x, B, l.H, l.W, l.Cin, l.stride, l.pt, l.pl, l.Ho, l.Wo, net->params[l.p_kernel].dev,
-                                  nullptr, nullptr, SSD_ACT_NONE, t.pre, st);
-            if (rc) return rc;
-        }
-        if (l.p_bn >= 0) {
-            rc = bn_stats(s, t, M, l.Cout, net->params[l.p_bn + 2].dev, net->params[l.p_bn + 3].dev, st);
-            if (rc) return rc;
-            hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(M * l.Cout)), dim3(256), 0, st, t.pre, M, l.Cout, t.mean,
-                               t.istd, net->params[l.p_bn].dev, net->params[l.p_bn + 1].dev, l.act,
-                               l.res >= 0 ? s.act[l.res] : nullptr, s.act[l.out]);
-            SSD_LAUNCH_CHECK();
-        }
-    }
+    for (size_t i = 0; i < net->layers.size(); ++i)
+        if (s.tl[i].active && (rc = train_forward_layer(c, i))) return rc;
     rc = launch_softmax(s.probs, (long)B * N, L, s.probs, st);
     if (rc) return rc;
     rc = ssd_loss(actual_deltas_dev, s.deltas, actual_labels_dev, s.probs, B, N, L, neg_pos_ratio, loc_loss_alpha,
@@ -1636,243 +1868,42 @@ int ssd_net_train_forward_backward(ssd_net* net, const float* image_dev, int B, 
                   s.loss_ws_bytes, stream);
     if (rc) return rc;
 
-    // ------------------------------------------------------------ backward
+    // backward, last layer first
     std::fill(s.gwritten.begin(), s.gwritten.end(), 0);
-    // gradient buckets: everything at or above `threshold` in the flat vector is final -> publish those buckets
-    size_t next_bucket = s.bucket_lo.size();
-    // weight gradients run on the side stream (s.wstream) beside the rest of the backward; dY alternates between two buffers
-    int dy_cur = 0;
-    for (int k = 0; k < 2; ++k) s.wpending[k] = false;
-    auto acquire_dy = [&]() -> float* {      // next dY buffer: the main stream first waits for the weight gradient still reading it
-        dy_cur ^= 1;
-        if (s.wstream && s.wpending[dy_cur]) {
-            (void)hipStreamWaitEvent(st, s.ev_wdone[dy_cur], 0);
-            s.wpending[dy_cur] = false;
-        }
-        return s.dy_buf[dy_cur];
-    };
-    auto join_wgrads = [&]() -> int {        // everything issued on the side stream so far is ordered before what follows on st
-        if (!s.wstream) return SSD_OK;
-        SSD_HIP(hipEventRecord(s.ev_wall, s.wstream));
-        SSD_HIP(hipStreamWaitEvent(st, s.ev_wall, 0));
-        s.wpending[0] = s.wpending[1] = false;
-        return SSD_OK;
-    };
-    // A bucket is final when BOTH streams have passed this point: the main stream (BatchNorm / depthwise / bias gradients,
-    // the data-gradient chain) and the side stream (the dense convs' weight gradients).  The bucket's event is recorded on
-    // the SIDE stream behind a wait for the main stream's position -- the main stream itself never waits (round 4 joined the
-    // side stream INTO the main stream here and therefore ran the weight gradients in line under buckets: +0.9 ms per step).
-    static const bool wside_buckets = !getenv("SSD_HIP_WGRAD_SIDE_BUCKETS") || atoi(getenv("SSD_HIP_WGRAD_SIDE_BUCKETS")) != 0;
-    auto mark_ready = [&](long threshold) -> int {
-        bool joined = false;
-        while (next_bucket > 0 && s.bucket_lo[next_bucket - 1] >= threshold) {
-            if (getenv("SSD_HIP_DEBUG_BUCKETS")) fprintf(stderr, "[ssd] bucket %zu (lo %ld) final at threshold %ld\n", next_bucket - 1, s.bucket_lo[next_bucket - 1], threshold);
-            if (s.wstream && wside_buckets) {
-                if (!joined) {
-                    SSD_HIP(hipEventRecord(s.ev_main_pos, st));
-                    SSD_HIP(hipStreamWaitEvent(s.wstream, s.ev_main_pos, 0));
-                    joined = true;
-                }
-                SSD_HIP(hipEventRecord(s.bucket_ev[next_bucket - 1], s.wstream));
-            } else {
-                if (!joined) {
-                    const int rj = join_wgrads();
-                    if (rj) return rj;
-                    joined = true;
-                }
-                SSD_HIP(hipEventRecord(s.bucket_ev[next_bucket - 1], st));
-            }
-            --next_bucket;
-        }
-        return SSD_OK;
-    };
+    s.wpending[0] = s.wpending[1] = false;
     for (int i = (int)net->layers.size() - 1; i >= 0; --i) {
         const Layer& l = net->layers[i];
-        TrainLayer& t = s.tl[i];
+        const TrainLayer& t = s.tl[i];
         if (!t.active) continue;
-        if (!s.pending_hi.empty()) {        // layers > i are done: what no layer <= i owns is final
-            rc = mark_ready(s.pending_hi[i]);
-            if (rc) return rc;
+        // layers > i are done: what no layer <= i owns is final
+        if (!s.pending_hi.empty() && (rc = c.mark_ready(s.pending_hi[i]))) return rc;
+        float* const dyb = l.kind == LK_POOL ? nullptr : c.acquire_dy();      // this layer's dY / scratch buffer
+        if (!l.head_kind && !s.gwritten[l.out]) {       // (a head conv takes its gradient from the loss)
+            set_error("train: no gradient reached tensor '%s'", net->tensors[l.out].name.c_str());
+            return SSD_E_STATE;
         }
-        const long M = (long)B * l.Ho * l.Wo;
-        const float* x = s.act[l.in];
-        float* const dyb = (l.kind == LK_POOL) ? nullptr : acquire_dy();      // this layer's dY / scratch buffer
         if (l.kind == LK_POOL || l.kind == LK_L2NORM) {
-            if (!s.gwritten[l.out]) {
-                set_error("train: no gradient reached tensor '%s'", net->tensors[l.out].name.c_str());
-                return SSD_E_STATE;
-            }
-            if (l.kind == LK_POOL) {
-                PoolBwdParams pp{};
-                pp.x = x; pp.g = s.gact[l.out]; pp.dx = s.gact[l.in];
-                pp.B = B; pp.H = l.H; pp.W = l.W; pp.C = l.Cin; pp.Ho = l.Ho; pp.Wo = l.Wo;
-                pp.k = l.kh; pp.stride = l.stride; pp.pad_t = l.pt; pp.pad_l = l.pl;
-                pp.accumulate = s.gwritten[l.in];
-                hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for((long)B * l.H * l.W * l.Cin)), dim3(256), 0, st, pp);
-                SSD_LAUNCH_CHECK();
-            } else {
-                const long blocks = (M + 3) / 4;
-                hipLaunchKernelGGL(l2norm_bwd_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, st, x,
-                                   s.gact[l.out], net->params[l.p_gamma].dev, M, l.Cin, s.gact[l.in], (int)s.gwritten[l.in],
-                                   dyb);
-                SSD_LAUNCH_CHECK();
-                RedParams rp{};
-                rp.a = dyb; rp.M = M; rp.C = l.Cin; rp.lda = l.Cin;
-                long chunks = 0;
-                rc = col_reduce<RED_SUM>(s, rp, &chunks, st);
-                if (!rc) rc = col_finalize(s, chunks, l.Cin, 1.0f, grads_flat_dev + t.g_gamma, nullptr, 0, st);
-                if (rc) return rc;
-            }
-            s.gwritten[l.in] = 1;
+            rc = l.kind == LK_POOL ? bwd_pool(c, l) : bwd_l2norm(c, l, t, dyb);
+            if (rc) return rc;
             continue;
         }
         const float* dY = nullptr;       // gradient w.r.t. the conv / depthwise output, dense [M][ldy]
         int ldy = l.Cout;
-        if (l.head_kind) {
-            ldy = t.cpad;
-            if (t.cpad != l.Cout) SSD_HIP(hipMemsetAsync(dyb, 0, (size_t)M * ldy * sizeof(float), st));
-            hipLaunchKernelGGL(gather_head_kernel, dim3(grid_for(M * l.Cout1)), dim3(256), 0, st, s.glogits, l.head_bs,
-                               l.head_off, l.head_ps, B, l.Ho * l.Wo, l.Cout1, dyb, ldy, 0);
-            hipLaunchKernelGGL(gather_head_kernel, dim3(grid_for(M * (l.Cout - l.Cout1))), dim3(256), 0, st, s.gdeltas,
-                               l.head2_bs, l.head2_off, l.head2_ps, B, l.Ho * l.Wo, l.Cout - l.Cout1, dyb, ldy,
-                               l.Cout1);
-            SSD_LAUNCH_CHECK();
-            dY = dyb;
-            // bias gradients = column sums
-            RedParams rp{};
-            rp.a = dY; rp.M = M; rp.C = l.Cout; rp.lda = ldy;
-            long chunks = 0;
-            rc = col_reduce<RED_SUM>(s, rp, &chunks, st);
-            if (!rc) rc = col_finalize(s, chunks, l.Cout, 1.0f, s.dbeta_tmp, nullptr, 0, st);
-            if (rc) return rc;
-            SSD_HIP(hipMemcpyAsync(grads_flat_dev + t.g_bias, s.dbeta_tmp, (size_t)l.Cout1 * sizeof(float),
-                                   hipMemcpyDeviceToDevice, st));
-            SSD_HIP(hipMemcpyAsync(grads_flat_dev + t.g_bias2, s.dbeta_tmp + l.Cout1,
-                                   (size_t)(l.Cout - l.Cout1) * sizeof(float), hipMemcpyDeviceToDevice, st));
-        } else {
-            const float* dOut = s.gact[l.out];
-            if (!s.gwritten[l.out]) {
-                set_error("train: no gradient reached tensor '%s'", net->tensors[l.out].name.c_str());
-                return SSD_E_STATE;
-            }
-            if (l.res >= 0) {       // out = bn(conv) + res: the residual branch receives dOut as is
-                hipLaunchKernelGGL(add_kernel, dim3(grid_for(M * l.Cout)), dim3(256), 0, st, s.gact[l.res], dOut, M * l.Cout,
-                                   (int)s.gwritten[l.res]);
-                SSD_LAUNCH_CHECK();
-                s.gwritten[l.res] = 1;
-            }
-            if (l.p_bn >= 0) {
-                RedParams rp{};
-                rp.a = dOut; rp.b = t.pre; rp.mean = t.mean; rp.istd = t.istd;
-                rp.gamma = net->params[l.p_bn].dev; rp.beta = net->params[l.p_bn + 1].dev;
-                rp.M = M; rp.C = l.Cout; rp.lda = l.Cout; rp.act = l.act;
-                long chunks = 0;
-                rc = col_reduce<RED_BN_BWD>(s, rp, &chunks, st);
-                // s1 = dbeta, s2 = dgamma
-                if (!rc) rc = col_finalize(s, chunks, l.Cout, 1.0f, grads_flat_dev + t.g_beta, grads_flat_dev + t.g_gamma, 0, st);
-                if (rc) return rc;
-                hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(M * l.Cout)), dim3(256), 0, st, dOut, t.pre, M, l.Cout,
-                                   t.mean, t.istd, net->params[l.p_bn].dev, net->params[l.p_bn + 1].dev, l.act,
-                                   grads_flat_dev + t.g_gamma, grads_flat_dev + t.g_beta, dyb);
-                SSD_LAUNCH_CHECK();
-                dY = dyb;
-            } else {
-                RedParams rp{};
-                rp.a = dOut; rp.b = l.act ? s.act[l.out] : nullptr;
-                rp.M = M; rp.C = l.Cout; rp.lda = l.Cout; rp.act = l.act;
-                long chunks = 0;
-                rc = col_reduce<RED_ACT_BWD>(s, rp, &chunks, st);
-                if (!rc) rc = col_finalize(s, chunks, l.Cout, 1.0f, grads_flat_dev + t.g_bias, nullptr, 0, st);
-                if (rc) return rc;
-                if (l.act) {
-                    hipLaunchKernelGGL(act_bwd_kernel, dim3(grid_for(M * l.Cout)), dim3(256), 0, st, dOut, s.act[l.out],
-                                       M * l.Cout, l.act, dyb);
-                    SSD_LAUNCH_CHECK();
-                    dY = dyb;
-                } else {
-                    dY = dOut;
-                }
-            }
-        }
+        if (l.head_kind) rc = bwd_head_dy(c, l, t, dyb, &dY, &ldy);
+        else if (l.p_bn >= 0) rc = bwd_bn_dy(c, l, t, dyb, &dY);
+        else rc = bwd_bias_act_dy(c, l, t, dyb, &dY);
+        if (rc) return rc;
         if (l.kind == LK_DW) {
-            DwBwdParams dp{};
-            dp.x = x; dp.g = dY; dp.w = net->params[l.p_kernel].dev; dp.dx = s.gact[l.in];
-            dp.B = B; dp.H = l.H; dp.W = l.W; dp.C = l.Cin; dp.Ho = l.Ho; dp.Wo = l.Wo;
-            dp.stride = l.stride; dp.pad_t = l.pt; dp.pad_l = l.pl;
-            dp.M = M;
-            dp.accumulate = s.gwritten[l.in];
-            const long chunks = dw_bwd_chunks(dp);
-            rc = ensure_partial(s, (size_t)chunks * 9 * l.Cin);
-            if (rc) return rc;
-            dp.partial = s.partial;
-            rc = dw_bwd_launch(dp, chunks, grads_flat_dev + t.g_kernel, st);
-            if (rc) return rc;
-            s.gwritten[l.in] = 1;
-            continue;
-        }
-        // ---- dense conv: weight gradient(s), on the side stream behind dY (they are needed only at the end of the step /
-        // at their gradient bucket: the data-gradient chain below does not wait for them)
-        // (not under the bucketed data-parallel exchange: there the communication stream already runs beside the backward,
-        // and a third stream measured slower at world size 1 -- 12.6 against 11.5 ms -- than the weight gradients in line)
-        const bool side = s.wstream && (s.bucket_lo.empty() || wside_buckets);
-        hipStream_t wst = side ? s.wstream : st;
-        if (side) {
-            SSD_HIP(hipEventRecord(s.ev_dy, st));
-            SSD_HIP(hipStreamWaitEvent(s.wstream, s.ev_dy, 0));
-        }
-        if (l.p_kernel2 < 0) {
-            rc = wgrad(s, l, B, x, dY, ldy, l.Cout, grads_flat_dev + t.g_kernel, wst);
+            rc = bwd_depthwise(c, l, t, dY);
         } else {
-            rc = wgrad(s, l, B, x, dY, ldy, l.Cout1, grads_flat_dev + t.g_kernel, wst);
-            if (!rc) rc = wgrad(s, l, B, x, dY + l.Cout1, ldy, l.Cout - l.Cout1, grads_flat_dev + t.g_kernel2, wst);
+            rc = bwd_dense_wgrad(c, l, t, dY, ldy, dyb);
+            if (!rc && t.wbwd) rc = bwd_dense_dgrad(c, l, t, dY, ldy);
         }
         if (rc) return rc;
-        // VGG16: kernel_regularizer=l2(5e-4) on every backbone / extra conv (models/ssd_vgg16.py:44-45; the head
-        // convs of models/header.py have none): d(5e-4 * sum w^2)/dw = 1e-3 * w, added right behind the layer's
-        // weight gradient so that the gradient bucket it lies in is final when the backward has passed the layer
-        if (net->backbone == SSD_VGG16 && !l.head_kind) {
-            const Param& w = net->params[l.p_kernel];
-            hipLaunchKernelGGL(axpy_kernel, dim3(grid_for((long)w.count)), dim3(256), 0, wst, grads_flat_dev + t.g_kernel,
-                               w.dev, (long)w.count, 2.0f * 5e-4f);
-            SSD_LAUNCH_CHECK();
-        }
-        if (side && dY == dyb) {             // the buffer may be rewritten only after this weight gradient
-            SSD_HIP(hipEventRecord(s.ev_wdone[dy_cur], s.wstream));
-            s.wpending[dy_cur] = true;
-        }
-        // ---- data gradient: conv of dY with the rotated / transposed weights
-        if (!t.wbwd) continue;
-        const int d = l.dil, kh = l.kh, kw = l.kw;
-        const float* gin = dY;
-        int Hg = l.Ho, Wg = l.Wo;
-        if (l.stride == 2) {
-            Hg = (l.Ho - 1) * 2 + 1;
-            Wg = (l.Wo - 1) * 2 + 1;
-            SSD_HIP(hipMemsetAsync(s.scratch_dz, 0, (size_t)B * Hg * Wg * ldy * sizeof(float), st));
-            hipLaunchKernelGGL(dilate2_kernel, dim3(grid_for(M * ldy)), dim3(256), 0, st, dY, B, l.Ho, l.Wo, ldy, Hg, Wg,
-                               s.scratch_dz);
-            SSD_LAUNCH_CHECK();
-            gin = s.scratch_dz;
-        }
-        const int pt = (kh - 1) * d - l.pt, pl = (kw - 1) * d - l.pl;
-        SSD_UNSUPPORTED_IF(pt < 0 || pl < 0, "train: backward-data padding of %s is negative", l.name.c_str());
-        ConvParams p = dense_conv_params(B, Hg, Wg, ldy, l.Cin, kh, kw, 1, d, pt, pl, l.H, l.W);
-        p.in = gin;
-        p.w = t.wbwd;
-        p.w3 = conv_split_planes(t.wbwd, p.K, p.Cout);
-        p.bf16 = net->precision;
-        p.out = s.gact[l.in];
-        p.act = SSD_ACT_NONE;
-        p.residual = s.gwritten[l.in] ? s.gact[l.in] : nullptr;      // accumulate in the epilogue
-        rc = launch_conv(p, st);
-        if (rc) return rc;
-        s.gwritten[l.in] = 1;
     }
-    rc = join_wgrads();             // the caller's stream sees the complete gradient vector
+    rc = c.join_wgrads();           // the caller's stream sees the complete gradient vector
     if (rc) return rc;
-    rc = mark_ready(0);
-    if (rc) return rc;
-    return SSD_OK;
+    return c.mark_ready(0);
 }
 
 // Gradient buckets for the data-parallel exchange ("prefer ... overlapped with backward"):
@@ -2053,8 +2084,7 @@ int ssd_conv2d_wgrad_ex(const ssd_conv_desc* d, const float* x_dev, const float*
     SSD_CHECK_ARG(config >= -1 && config < ssd_conv_wgrad_num_configs(), "ssd_conv2d_wgrad_ex: config %d is outside -1..%d",
                   config, ssd_conv_wgrad_num_configs() - 1);
     const WgradCfg* cfg = config < 0 ? wgrad_heuristic(l, N) : &kWgrad[config];
-    return wgrad_with(l, d->B, x_dev, g_dev, ldg, N, dW_dev, (hipStream_t)stream, cfg, false, workspace_dev,
-                      workspace_floats);
+    return wgrad_with(l, d->B, x_dev, g_dev, ldg, N, dW_dev, (hipStream_t)stream, cfg, workspace_dev, workspace_floats);
 }
 
 int ssd_dwconv3x3_backward(const float* x_dev, const float* g_dev, const float* w_dev, int B, int H, int W, int C, int stride,
