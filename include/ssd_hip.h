@@ -363,6 +363,46 @@ int ssd_augment_geometry(const float* img_dev, int B, int H, int W, int C, int o
 int ssd_augment_color(float* img_dev, int B, int H, int W, const float* params_dev, const int* flags_dev,
                       const float* mean_dev, void* stream);
 
+/* ---- augmentation, the random plan drawn on the device (opt-in; the host draws of augmentation.py stay as they are) ----
+ * ssd_augment_plan: the decisions of augmentation.apply (:19-25: patch [expand, min overlap, window], flip, brightness,
+ *   contrast, hue, saturation) for B images of H x W in one launch, one wavefront per image, written in the layouts the
+ *   three kernels above read; the ground-truth boxes are transformed along (expand_boxes, renormalize to the window,
+ *   flip_boxes).  No atomics, no workspace, no host synchronisation, no allocation.
+ *   gt_boxes [B,G,4] (y1, x1, y2, x2 normalised); gt_labels [B,G]: a row is valid iff label > 0 (NULL: valid iff the sum
+ *   of its |coordinates| > 0).  Rows that are not valid are copied through unchanged.  An image with no valid row gets NO
+ *   patch (the host sampler raises there, like TF; a kernel cannot).  boxes_out may be gt_boxes (in place).
+ *   geom_out [B,10] = ssd_augment_geometry's params (no patch: {H, W, 0, 0, 0, 0, H, W, flip, 0}); color_out [B,4] and
+ *   flags_out [B] = ssd_augment_color's params and flags (an operation that does not run: 0 / 1 / 0 / 1); add_out [B] =
+ *   the brightness delta or 0 (ssd_image_mean's add for contrast's pivot); info_out [B,4] = {accepted sampler attempt:
+ *   -1 no patch, 0..99, 100 every attempt failed and the window is the whole canvas (the host sampler's fallback);
+ *   the min-overlap index drawn (0..4 -> 0.1, 0.3, 0.5, 0.7, 0.9; drawn whether or not a patch runs); 1 iff the patch
+ *   expands; 0}.
+ *   Random stream: Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85), key =
+ *   (seed & 0xffffffff, seed >> 32), counter = (id & 0xffffffff, id >> 32, slot, 0) with id = sample_ids[b]: the plan is
+ *   a pure function of (seed, id, H, W, the image's ground truth) -- not of B, the position in the batch or other images.
+ *   A float draw is u = (word >> 8) * 2^-24 in [0, 1); a boolean is u > 0.5f (augmentation.py:33); uniform(lo, hi) =
+ *   lo + u * (hi - lo) in fp32, each operation rounded on its own; an integer in [0, n) is (uint64(word) * n) >> 32.
+ *   Slots (fixed, never conditional: a draw's value does not depend on which branches ran):
+ *     slot 0        patch?                     expand?              flip?              brightness?
+ *     slot 1        contrast?                  hue?                 saturation?        min-overlap index (n = 5)
+ *     slot 2        expansion ratio U[1,4)     u_left               u_top              --
+ *     slot 3        brightness U[-.12,.12)     contrast U[.5,1.5)   hue U[-.08,.08)    saturation U[.5,1.5)
+ *     slot 16 + a   aspect ratio U[.5,2)       height draw          y draw             x draw          (attempt a = 0..99)
+ *   Arithmetic: fp32 throughout (the TF kernel the host sampler restates computes in float; the host sampler itself uses
+ *   float64 for its window), rintf = round half to even, pixel rectangles = the truncated fp32 product, areas in 64-bit
+ *   integers.  Attempt a: aspect; min_h / max_h = rintf(sqrtf({0.05, 1} * canvas area / aspect)); if rintf(max_h * aspect)
+ *   > canvas_w: max_h = (int)((canvas_w + 0.5f - 1e-7f) / aspect), one less if its rounded width still does not fit;
+ *   max_h = min(max_h, canvas_h); min_h = min(min_h, max_h); h = min_h + integer draw in [0, max_h - min_h + 1) when
+ *   min_h < max_h; w = rintf(h * aspect); h + 1 if w * h < min area, h - 1 if w * h > max area (w recomputed); rejected
+ *   outside the area range or the canvas; y, x = integer draws in [0, canvas_h - h), [0, canvas_w - w) (0 when the side is
+ *   full); accepted iff some valid box of >= 1 pixel has (float)intersection / (float)area >= the min overlap.  The
+ *   window is the LOWEST accepted attempt (lane l evaluates attempts l and l + 64; a wave ballot picks it): the law of
+ *   the sequential "first one that satisfies".
+ *   SSD_E_UNSUPPORTED (nothing is launched): G > 512, or a canvas side 4 * H / 4 * W beyond 16384. */
+int ssd_augment_plan(const float* gt_boxes_dev, const int* gt_labels_dev, const long long* sample_ids_dev, int B, int G, int H,
+                     int W, unsigned long long seed, int* geom_out_dev, float* color_out_dev, int* flags_out_dev,
+                     float* add_out_dev, int* info_out_dev, float* boxes_out_dev, void* stream);
+
 /* ---- drawing: utils/drawing_utils.py:6-85 (draw_grid_map, draw_bboxes, draw_bboxes_with_labels) ---------------------
  * ssd_image_minmax: minmax_out [B][2] = {min, max} over H, W, C of each image of img_dev [B,H,W,3] float32: the two numbers
  *   of [3P] Keras array_to_img(scale=True).  NaN pixels are ignored.  workspace: ssd_image_minmax_workspace_bytes(B) bytes,

@@ -9,6 +9,11 @@ through three HIP kernels (include/ssd_hip.h): ``ssd_image_mean`` (expand's fill
 -- up to 16x the pixels -- is never materialised) and ``ssd_augment_color`` (brightness -> contrast -> hue -> saturation ->
 clip in one pass).  Box arithmetic is host-side float32 NumPy (a few dozen boxes).
 
+Opt-in, the draws can be made on the device instead (``plan_batch_device`` / ``apply_batch_device`` / ``device_draws``:
+``ssd_augment_plan``, a counter-based generator, one wavefront per image): the same pixel kernels read the plan where the
+kernel wrote it, the boxes stay on the device, and an image's augmentation is a pure function of (seed, sample id).  It is
+another random stream than ``seed()``'s; everything above keeps its host draws and its bits.
+
 Images: float32 device tensors [H,W,3] in [0,1]; boxes [G,4] = (y1, x1, y2, x2) normalised.
 [3P] ``sample_distorted_bounding_box`` is restated from the TF 2.0 kernel's published algorithm (random: only its
 acceptance rule is testable); there is no TensorFlow here, parity of the TF ops themselves is unpinned."""
@@ -360,6 +365,106 @@ def apply_batch(images, gt_boxes, gt_labels=None):
         gb[b][valid] = g
         plans.append(plan)
     return run_plans(x, plans), gb
+
+
+# ---- the plan drawn on the device (opt-in) ------------------------------------------------------------------------------
+PLAN_NAMES = ("geom", "color", "flags", "add", "info", "boxes")
+_warned_host_fallback = False
+
+
+def plan_batch_device(gt_boxes, gt_labels, sample_ids, H, W, seed, out=None):
+    """``draw_plan`` for a padded batch in ONE launch (``ssd_augment_plan``, include/ssd_hip.h): returns the six device
+    tensors (geom int32 [B,10], color float32 [B,4], flags int32 [B], add float32 [B], info int32 [B,4], boxes float32
+    [B,G,4]) -- the layouts ``ssd_augment_geometry`` / ``ssd_augment_color`` / ``ssd_image_mean`` read, so nothing is
+    uploaded.  The draws come from a counter-based generator (Philox4x32-10): image ``b``'s plan is a pure function of
+    (``seed``, ``sample_ids[b]``, H, W, its ground truth), whatever the batch size, the position in the batch or the rank
+    layout -- the host generator cannot give that.  ``gt_boxes`` [B,G,4] / ``gt_labels`` [B,G] or None / ``sample_ids``
+    [B]: host or device.  ``out``: six preallocated tensors to write into (a steady-state step then allocates nothing;
+    ``out[5]`` may be the device ``gt_boxes`` itself).  An image without a valid row gets no patch (``apply_batch`` raises
+    there, like TF: a kernel cannot).  Raises ``ssd_hip.SsdHipUnsupported`` for G > 512 or H, W > 4096."""
+    g = _h.to_dev(gt_boxes)
+    if g.dim() != 3 or g.shape[2] != 4:
+        raise ValueError("gt_boxes must be [B,G,4], got %s" % (tuple(g.shape),))
+    B, G = int(g.shape[0]), int(g.shape[1])
+    gl = None if gt_labels is None else _h.to_dev(gt_labels, torch.int32)
+    ids = _h.to_dev(sample_ids, torch.int64)
+    if ids.numel() != B or (gl is not None and tuple(gl.shape) != (B, G)):
+        raise ValueError("plan_batch_device: gt_labels must be [B,G] and sample_ids [B]")
+    dev = g.device
+    if out is None:
+        out = (torch.empty((B, 10), dtype=torch.int32, device=dev), torch.empty((B, 4), dtype=torch.float32, device=dev),
+               torch.empty((B,), dtype=torch.int32, device=dev), torch.empty((B,), dtype=torch.float32, device=dev),
+               torch.empty((B, 4), dtype=torch.int32, device=dev), torch.empty((B, G, 4), dtype=torch.float32, device=dev))
+    else:
+        shapes = ((B, 10), (B, 4), (B,), (B,), (B, 4), (B, G, 4))
+        dtypes = (torch.int32, torch.float32, torch.int32, torch.float32, torch.int32, torch.float32)
+        for t, s, d, n in zip(out, shapes, dtypes, PLAN_NAMES):
+            if tuple(t.shape) != s or t.dtype != d or t.device != dev or not t.is_contiguous():
+                raise ValueError("plan_batch_device: out %s must be a contiguous %s tensor of shape %s on %s" % (n, d, s, dev))
+    geom, color, flags, add, info, boxes = out
+    _h.check(_h.lib().ssd_augment_plan(_h.ptr(g), _h.ptr(gl), _h.ptr(ids), B, G, int(H), int(W), int(seed) & (2 ** 64 - 1),
+                                       _h.ptr(geom), _h.ptr(color), _h.ptr(flags), _h.ptr(add), _h.ptr(info), _h.ptr(boxes),
+                                       _h.stream()), "ssd_augment_plan")
+    return geom, color, flags, add, info, boxes
+
+
+def run_plan_device(images, plan):
+    """``run_plans`` on a device plan (the tensors of ``plan_batch_device``): four launches, nothing uploaded, nothing read
+    back.  Both means are always computed -- cheaper than reading the expand / contrast flags back; an image that does not
+    expand never reads its fill colour, one without contrast never reads its pivot -- and an image with neither crop nor
+    flip goes through the geometry kernel's copy path: bitwise the result of ``run_plans``."""
+    x = _h.to_dev(images)
+    if x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError("images must be [B,H,W,3], got %s" % (tuple(x.shape),))
+    B, H, W, C = x.shape
+    geom, color, flags, add = plan[:4]
+    lib = _h.lib()
+    fill = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    mean = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    out = torch.empty_like(x)
+    _h.check(lib.ssd_image_mean(_h.ptr(x), B, H, W, C, None, _h.ptr(fill), _h.stream()), "ssd_image_mean")
+    _h.check(lib.ssd_augment_geometry(_h.ptr(x), B, H, W, C, H, W, _h.ptr(geom), _h.ptr(fill), _h.ptr(out), _h.stream()),
+             "ssd_augment_geometry")
+    _h.check(lib.ssd_image_mean(_h.ptr(out), B, H, W, C, _h.ptr(add), _h.ptr(mean), _h.stream()), "ssd_image_mean")
+    _h.check(lib.ssd_augment_color(_h.ptr(out), B, H, W, _h.ptr(color), _h.ptr(flags), _h.ptr(mean), _h.stream()), "ssd_augment_color")
+    return out
+
+
+def apply_batch_device(images, gt_boxes, gt_labels, sample_ids, seed=None):
+    """``apply_batch`` with the draws made on the device: five launches (the plan, the expand fill colours, the geometry
+    gather, the contrast pivots, the colour pass) and no upload of plan arrays.  Returns (images, gt_boxes) with the boxes
+    as a DEVICE tensor [B,G,4] (``ssd_match_encode``'s wrapper takes it as it is).  ``sample_ids`` [B] name the images
+    in the generator's counter (``device_draws`` hands out a running count); ``seed`` None = 0.  Not the host path's
+    stream: the same seed gives other draws than ``seed()`` + ``apply_batch``.  Shapes the plan kernel refuses (more than
+    512 ground-truth rows, sides beyond 4096) take the host draws instead, with one warning."""
+    global _warned_host_fallback
+    x = _h.to_dev(images)
+    if x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError("images must be [B,H,W,3], got %s" % (tuple(x.shape),))
+    try:
+        plan = plan_batch_device(gt_boxes, gt_labels, sample_ids, int(x.shape[1]), int(x.shape[2]), 0 if seed is None else seed)
+    except _h.SsdHipUnsupported as e:
+        if not _warned_host_fallback:
+            _warned_host_fallback = True
+            import warnings
+            warnings.warn("apply_batch_device: %s -- this shape takes the host draws (apply_batch)" % e)
+        out, gb = apply_batch(x, gt_boxes, gt_labels)
+        return out, _h.to_dev(gb)
+    return run_plan_device(x, plan), plan[5]
+
+
+def device_draws(seed, rank_offset=0):
+    """A callable with the ``augmentation_fn`` signature ``data_utils.voc_batches`` and ``augmented`` call -- ``(imgs,
+    gt_boxes, gt_labels) -> (imgs, gt_boxes)`` -- that runs ``apply_batch_device`` and numbers the images itself: a
+    running counter that starts at ``rank_offset`` (give every rank its own range, as ``trainer.py`` does)."""
+    state = {"next": int(rank_offset)}
+
+    def fn(images, gt_boxes, gt_labels=None):
+        B = int(images.shape[0])
+        ids = torch.arange(state["next"], state["next"] + B, dtype=torch.int64, device=_h.device())
+        state["next"] += B
+        return apply_batch_device(images, gt_boxes, gt_labels, ids, seed)
+    return fn
 
 
 def augmented(dataset, fn=None):

@@ -32,6 +32,8 @@ compile ssd_bbox.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
 # loss: separately rounded ops too (the hard-negative RANK depends on the per-anchor CE values)
 compile ssd_loss.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
 compile ssd_data.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
+# the augmentation plan: bit-equal to its fp32 NumPy restatement (tests/augment_plan_cases.py)
+compile ssd_augplan.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
 # JPEG: integer arithmetic only; -fwrapv makes int32 wrap-around (hostile coefficients) defined
 compile ssd_jpeg.hip -ffp-contract=off -fwrapv
 compile ssd_jpeg_enc.hip -ffp-contract=off

@@ -113,6 +113,7 @@ _SIGNATURES = {
     "ssd_image_mean": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp, vp, vp]),
     "ssd_augment_geometry": (ctypes.c_int, [vp] + [ctypes.c_int] * 6 + [vp, vp, vp, vp]),
     "ssd_augment_color": (ctypes.c_int, [vp] + [ctypes.c_int] * 3 + [vp, vp, vp, vp]),
+    "ssd_augment_plan": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 4 + [ctypes.c_ulonglong] + [vp] * 7),
     "ssd_image_minmax_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "ssd_image_minmax": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp, vp, ctypes.c_size_t, vp]),
     "ssd_draw_detections": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 4 + [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp,

@@ -113,6 +113,9 @@ def main(argv=None):
     hyper_params = train_utils.get_hyper_params(backbone)
     voc_dir = os.environ.get("SSD_VOC_DIR")
     augment = os.environ.get("SSD_TRAINER_AUGMENT", "1") != "0"
+    # SSD_TRAINER_AUGMENT=gpu: the random plan is drawn on the device (augmentation.device_draws: a counter-based
+    # generator, every rank numbers its images in a range of its own); any other value but 0 keeps the host draws
+    augment_gpu = os.environ.get("SSD_TRAINER_AUGMENT", "1") == "gpu"
     if voc_dir:
         import augmentation
         train_data, val_data, info, train_total_items, val_total_items = _voc_splits(voc_dir, batch_size, rank, world)
@@ -121,11 +124,12 @@ def main(argv=None):
         img_size = hyper_params["img_size"]
         step_size_train = int(os.environ.get("SSD_TRAINER_STEPS", "0")) or train_utils.get_step_size(train_total_items, batch_size)
         step_size_val = train_utils.get_step_size(val_total_items, batch_size)
-        if augment:
+        if augment and not augment_gpu:
             augmentation.seed(4242 + rank)
+        augmentation_fn = augmentation.device_draws(4242, rank_offset=rank << 40) if augment_gpu else augmentation.apply_batch
         # trainer.py:42-48: preprocessing (+ augmentation on the training stream), shuffle, padded batches
         train_data = data_utils.voc_batches(train_data.shuffle(batch_size * 4, seed=rank), batch_size, img_size, img_size,
-                                            augmentation_fn=augmentation.apply_batch if augment else None)
+                                            augmentation_fn=augmentation_fn if augment else None)
         val_data = data_utils.voc_batches(val_data, batch_size, img_size, img_size)
         augment = False                                   # done inside the batches
     else:
@@ -156,8 +160,11 @@ def main(argv=None):
     # SSD_TRAINER_AUGMENT=0 turns it off (deterministic smoke runs).
     if augment:
         import augmentation
-        augmentation.seed(4242 + rank)
-        train_data = augmentation.augmented(train_data)
+        if augment_gpu:
+            train_data = augmentation.augmented(train_data, augmentation.device_draws(4242, rank_offset=rank << 40))
+        else:
+            augmentation.seed(4242 + rank)
+            train_data = augmentation.augmented(train_data)
     ssd_train_feed = train_utils.generator(train_data, prior_boxes, hyper_params)
     ssd_val_feed = train_utils.generator(val_data, prior_boxes, hyper_params)
 
