@@ -345,6 +345,59 @@ int ssd_jpeg_encode_info(int width, int height, int h_samp, int v_samp, const un
 size_t ssd_jpeg_encode_bound(const struct ssd_jpeg_info* info);
 int ssd_jpeg_entropy_encode(const short* coef, const struct ssd_jpeg_info* info, unsigned char* out, size_t out_bytes,
                             size_t* written);
+/* ssd_jpeg_encode_header: everything ssd_jpeg_entropy_encode writes before the entropy-coded data (SOI through SOS, the
+ *   same bytes: it is the function the coder itself calls); *written = SSD_JPEG_HEADER_BYTES, whatever the image.
+ *   SSD_E_INVALID: NULL pointers, an inconsistent info, out_bytes below SSD_JPEG_HEADER_BYTES (nothing is written). */
+#define SSD_JPEG_HEADER_BYTES 623
+int ssd_jpeg_encode_header(const struct ssd_jpeg_info* info, unsigned char* out, size_t out_bytes, size_t* written);
+
+/* DEVICE ENTROPY CODER (ssd_jpeg_pack): the coefficient storage of a ragged batch, exactly as ssd_jpeg_forward writes it
+ * (three components, 1x1 / 2x1 / 2x2 luma sampling; only REAL blocks are read), -> the complete JPEG streams of the
+ * batch, back to back in out_dev: stream b is out_dev[offsets_dev[b] : offsets_dev[b + 1]] (int32 [B + 1], offsets[0] =
+ * 0), and its bytes are ssd_jpeg_entropy_encode's bit for bit: the header (copied from header_offset of packed_dev
+ * [packed_bytes], SSD_JPEG_HEADER_BYTES bytes that ssd_jpeg_encode_header wrote), the stuffed Huffman data of one
+ * interleaved scan with the Annex K tables, the last byte padded with 1-bits (a 0xFF made by the padding is stuffed),
+ * EOI.  Dummy blocks of the last MCU column / row are synthesised (AC zero, a DC difference of zero).  One call, a fixed
+ * number of launches (six kernels and two fills, whatever B and the sizes), asynchronous on `stream`; no workgroup waits
+ * on another, every prefix sum is reduce-then-scan in separate launches, so the bytes do not depend on scheduling.
+ *   blocks     ONE index space of emitted blocks over the batch (block_start: the running sum of mcus_x * mcus_y *
+ *              (h_samp * v_samp + 2), the same number ssd_jpeg_forward counts).  Kernel 1 gives every block its bit
+ *              length (the DC predictor is the DC of the block emitted before it in the same component, always a real
+ *              block's value; ZRL for runs above 15; EOB only when zeros trail) and every 256 blocks their sum; kernel 2
+ *              (one workgroup) scans the sums (64-bit: a batch may hold more than 2^32 bits) and finds every image's
+ *              first bit; kernel 3 re-derives the codes and ORs them, as big-endian 32-bit words with atomic ORs (blocks
+ *              share words; OR commutes), into the image's zeroed unstuffed stream.
+ *   stuffing   the unstuffed stream of image b lives at 224 * block_start of the workspace (224 bytes hold the longest
+ *              block, 1660 bits, and the padding).  Kernel 4 counts the 0xFF bytes of every 224-byte slot (the same index
+ *              space), kernel 5 (one workgroup) scans them, sizes every stream (header + data + stuffing + EOI) and scans
+ *              the sizes into offsets_dev; kernel 6 scatters every slot's bytes to their final place -- which already
+ *              includes the batch-level offsets, so the output is compact without a host round trip -- and copies the
+ *              header and the EOI.
+ * status_dev (int32 [B]): 0, or for an image with a DC difference beyond category 11 (bit 0) or an AC coefficient beyond
+ *   category 10 (bit 1) -- what ssd_jpeg_entropy_encode refuses -- nonzero; the content of that image's region is then
+ *   unspecified (its size is still within its bound), and every other image of the batch is exact.
+ * Workspace: ssd_jpeg_pack_workspace_bytes(desc_host, B) bytes (bit lengths, scan partials, the unstuffed streams at their
+ *   worst case; 0 for an unusable batch); the call itself zeroes it on `stream`.
+ * Nothing outside [out_dev, out_dev + out_bytes) is written; the bytes past offsets_dev[B] are left as they were.
+ * SSD_E_INVALID, nothing launched: NULL pointers, coef_dev / packed_dev / out_dev / workspace_dev not 16-byte aligned,
+ *   offsets_dev / status_dev not 4-byte aligned, offsets that are negative or no multiple of 16, regions outside their
+ *   buffer, coefficients that overlap or are out of order, wrong running sums, a workspace that is too small, out_bytes
+ *   below the sum of ssd_jpeg_encode_bound of the images, each rounded up to 16 (which rules out overflow by construction).
+ * SSD_E_UNSUPPORTED, nothing launched: a side outside 1..16384, a sampling other than 1x1, 2x1, 2x2, B > 65535, a bound
+ *   sum above 2^31 - 1 bytes (byte offsets are int32).  B == 0 is a no-op. */
+struct ssd_jpeg_pack_desc {
+    long long coef_offset;   /* byte offset in coef_dev of the image's coefficient storage, a multiple of 16             */
+    long long header_offset; /* byte offset in packed_dev of its SSD_JPEG_HEADER_BYTES header bytes, a multiple of 16     */
+    int H, W;
+    int h_samp, v_samp;      /* luma sampling: 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0)                                   */
+    int block_start;         /* running sum over the batch of the image's 8x8 blocks                                     */
+    int reserved;            /* 0                                                                                        */
+};
+size_t ssd_jpeg_pack_workspace_bytes(const struct ssd_jpeg_pack_desc* desc_host, int B);
+int ssd_jpeg_pack(const short* coef_dev, size_t coef_bytes, const unsigned char* packed_dev, size_t packed_bytes,
+                  const struct ssd_jpeg_pack_desc* desc_host, const struct ssd_jpeg_pack_desc* desc_dev, int B,
+                  unsigned char* out_dev, size_t out_bytes, int* offsets_dev, int* status_dev, void* workspace_dev,
+                  size_t workspace_bytes, void* stream);
 
 /* ---- augmentation: augmentation.py:4-183 (used at trainer.py:42), the deterministic pieces; the random draws of the
  * reference's tf.random.uniform / sample_distorted_bounding_box calls are INPUTS (host side: tf-ssd_amd/augmentation.py).

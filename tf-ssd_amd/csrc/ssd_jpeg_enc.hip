@@ -4,8 +4,8 @@
 //          Integer arithmetic with one defined answer: [3P] libjpeg-turbo's 16-bit fixed-point colour conversion, its
 //          h2v1 / h2v2 box downsampling with alternating bias, the JDCT_ISLOW forward DCT and the baseline quantiser,
 //          restated from the published algorithms (include/ssd_hip.h spells the arithmetic out).
-//   host   ssd_jpeg_quality_tables / ssd_jpeg_encode_info / ssd_jpeg_encode_bound / ssd_jpeg_entropy_encode: the header and
-//          Huffman coding -- serial, bit-granular.  Plain C++: no HIP call, no global state, thread-safe (the data pool's
+//   host   ssd_jpeg_quality_tables / ssd_jpeg_encode_info / ssd_jpeg_encode_bound / ssd_jpeg_encode_header /
+//          ssd_jpeg_entropy_encode: the header and Huffman coding -- serial, bit-granular.  Plain C++: no HIP call, no global state, thread-safe (the data pool's
 //          threads call them in parallel).
 #include <cstring>
 
@@ -21,40 +21,6 @@ static const unsigned char kStdQuant[2][64] = {
      18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99},
     {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
      99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
-
-struct std_huff {
-    unsigned char cls_id;       // the DHT segment's Tc << 4 | Th
-    unsigned char bits[16];
-    int count;
-    unsigned char vals[162];
-};
-// in stream order: DC0, AC0, DC1, AC1
-static const std_huff kStdHuff[4] = {
-    {0x00, {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, 12, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}},
-    {0x10, {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d}, 162,
-     {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
-      0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
-      0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
-      0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75,
-      0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
-      0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
-      0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
-      0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa}},
-    {0x01, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}, 12, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}},
-    {0x11, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}, 162,
-     {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
-      0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25,
-      0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47,
-      0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74,
-      0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
-      0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
-      0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4,
-      0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa}}};
-
-// SOI + APP0 + 2 DQT + SOF0 + 4 DHT + SOS
-static const size_t kEncHeaderBytes = 2 + 18 + 2 * 69 + 19 + 2 * (21 + 12) + 2 * (21 + 162) + 14;
-// the longest block: an 11-bit DC code + 11 bits, 63 x (a 16-bit AC code + 10 bits) = 1660 bits, every byte stuffed
-static const size_t kEncBlockBytes = 2 * ((22 + 63 * 26 + 7) / 8);
 
 struct enc_huff {
     unsigned short code[256];
@@ -360,7 +326,43 @@ extern "C" int ssd_jpeg_encode_info(int width, int height, int h_samp, int v_sam
 extern "C" size_t ssd_jpeg_encode_bound(const struct ssd_jpeg_info* info) {
     if (enc_check_info(info) != SSD_OK) return 0;
     const size_t blocks = (size_t)info->mcus_x * info->mcus_y * (size_t)(info->h_samp[0] * info->v_samp[0] + 2);
-    return kEncHeaderBytes + blocks * kEncBlockBytes + 2 + 2;                      // + the padded last byte (stuffed) + EOI
+    return jpeg_encode_bound_bytes(blocks);
+}
+
+// SOI through SOS into `w`: kEncHeaderBytes bytes, whatever the image (`o` has passed enc_check_info)
+static void enc_header(byte_writer& w, const ssd_jpeg_info& o) {
+    w.be16(0xFFD8);
+    static const unsigned char app0[16] = {0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1};
+    for (int i = 0; i < 16; ++i) w.byte(app0[i]);
+    w.be16(0);                                                                     // no thumbnail
+    for (int t = 0; t < 2; ++t) {
+        w.be16(0xFFDB); w.be16(67); w.byte((unsigned)t);
+        for (int i = 0; i < 64; ++i) w.byte(o.quant[t][kZigzag[i]]);
+    }
+    w.be16(0xFFC0); w.be16(17); w.byte(8); w.be16((unsigned)o.height); w.be16((unsigned)o.width); w.byte(3);
+    for (int c = 0; c < 3; ++c) { w.byte((unsigned)c + 1); w.byte((unsigned)((o.h_samp[c] << 4) | o.v_samp[c])); w.byte((unsigned)o.quant_index[c]); }
+    for (int t = 0; t < 4; ++t) {
+        const std_huff& s = kStdHuff[t];
+        w.be16(0xFFC4); w.be16((unsigned)(19 + s.count)); w.byte(s.cls_id);
+        for (int i = 0; i < 16; ++i) w.byte(s.bits[i]);
+        for (int i = 0; i < s.count; ++i) w.byte(s.vals[i]);
+    }
+    static const unsigned char sos[14] = {0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0};
+    for (int i = 0; i < 14; ++i) w.byte(sos[i]);
+}
+
+extern "C" int ssd_jpeg_encode_header(const struct ssd_jpeg_info* info, unsigned char* out, size_t out_bytes, size_t* written) {
+    static_assert(kEncHeaderBytes == SSD_JPEG_HEADER_BYTES, "the header's size is part of the interface");
+    SSD_CHECK_ARG(out && written, "ssd_jpeg_encode_header: NULL pointer");
+    *written = 0;
+    const int rc = enc_check_info(info);
+    if (rc != SSD_OK) return rc;
+    SSD_CHECK_ARG(out_bytes >= kEncHeaderBytes, "ssd_jpeg_encode_header: out holds %zu bytes, fewer than the header's %zu", out_bytes,
+                  kEncHeaderBytes);
+    byte_writer w = {out, out_bytes, 0, 0, 0};
+    enc_header(w, *info);
+    *written = w.at;
+    return SSD_OK;
 }
 
 extern "C" int ssd_jpeg_entropy_encode(const short* coef, const struct ssd_jpeg_info* info, unsigned char* out, size_t out_bytes,
@@ -372,26 +374,9 @@ extern "C" int ssd_jpeg_entropy_encode(const short* coef, const struct ssd_jpeg_
     const ssd_jpeg_info& o = *info;
     SSD_CHECK_ARG(out_bytes >= kEncHeaderBytes + 2, "ssd_jpeg_entropy_encode: out holds %zu bytes, fewer than the header", out_bytes);
     byte_writer w = {out, out_bytes, 0, 0, 0};
-    w.be16(0xFFD8);
-    static const unsigned char app0[16] = {0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1};
-    for (int i = 0; i < 16; ++i) w.byte(app0[i]);
-    w.be16(0);                                                                     // no thumbnail
-    for (int t = 0; t < 2; ++t) {
-        w.be16(0xFFDB); w.be16(67); w.byte((unsigned)t);
-        for (int i = 0; i < 64; ++i) w.byte(o.quant[t][kZigzag[i]]);
-    }
-    w.be16(0xFFC0); w.be16(17); w.byte(8); w.be16((unsigned)o.height); w.be16((unsigned)o.width); w.byte(3);
-    for (int c = 0; c < 3; ++c) { w.byte((unsigned)c + 1); w.byte((unsigned)((o.h_samp[c] << 4) | o.v_samp[c])); w.byte((unsigned)o.quant_index[c]); }
+    enc_header(w, o);
     enc_huff huff[4];
-    for (int t = 0; t < 4; ++t) {
-        const std_huff& s = kStdHuff[t];
-        w.be16(0xFFC4); w.be16((unsigned)(19 + s.count)); w.byte(s.cls_id);
-        for (int i = 0; i < 16; ++i) w.byte(s.bits[i]);
-        for (int i = 0; i < s.count; ++i) w.byte(s.vals[i]);
-        enc_build_huff(huff[t], s);
-    }
-    static const unsigned char sos[14] = {0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0};
-    for (int i = 0; i < 14; ++i) w.byte(sos[i]);
+    for (int t = 0; t < 4; ++t) enc_build_huff(huff[t], kStdHuff[t]);
     // the real blocks of each component: what the frame header's size gives; the rest of an MCU is synthesised
     int real_w[3], real_h[3];
     for (int c = 0; c < 3; ++c) {

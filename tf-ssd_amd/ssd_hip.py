@@ -110,6 +110,10 @@ _SIGNATURES = {
     "ssd_jpeg_encode_info": (ctypes.c_int, [ctypes.c_int] * 4 + [vp, ctypes.POINTER(JpegInfo)]),
     "ssd_jpeg_encode_bound": (ctypes.c_size_t, [ctypes.POINTER(JpegInfo)]),
     "ssd_jpeg_entropy_encode": (ctypes.c_int, [vp, ctypes.POINTER(JpegInfo), vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+    "ssd_jpeg_encode_header": (ctypes.c_int, [ctypes.POINTER(JpegInfo), vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+    "ssd_jpeg_pack_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int]),
+    "ssd_jpeg_pack": (ctypes.c_int, [vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp, ctypes.c_int, vp, ctypes.c_size_t, vp, vp, vp,
+                                      ctypes.c_size_t, vp]),
     "ssd_image_mean": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp, vp, vp]),
     "ssd_augment_geometry": (ctypes.c_int, [vp] + [ctypes.c_int] * 6 + [vp, vp, vp, vp]),
     "ssd_augment_color": (ctypes.c_int, [vp] + [ctypes.c_int] * 3 + [vp, vp, vp, vp]),
@@ -212,6 +216,10 @@ assert JPEG_DESC_DTYPE.itemsize == 56 and ctypes.sizeof(JpegInfo) == 504
 JPEG_ENC_DESC_DTYPE = np.dtype([(n, "<i8") for n in ("src_offset", "coef_offset", "quant_offset", "plane_offset")] + [
     (n, "<i4") for n in ("H", "W", "h_samp", "v_samp", "block_start", "item_start")])       # struct ssd_jpeg_enc_desc
 assert JPEG_ENC_DESC_DTYPE.itemsize == 56
+JPEG_HEADER_BYTES = 623         # SSD_JPEG_HEADER_BYTES: what ssd_jpeg_encode_header writes, whatever the image
+JPEG_PACK_DESC_DTYPE = np.dtype([("coef_offset", "<i8"), ("header_offset", "<i8")] + [
+    (n, "<i4") for n in ("H", "W", "h_samp", "v_samp", "block_start", "reserved")])         # struct ssd_jpeg_pack_desc
+assert JPEG_PACK_DESC_DTYPE.itemsize == 40
 
 _lib = None
 _inited = False

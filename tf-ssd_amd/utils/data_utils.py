@@ -725,6 +725,108 @@ def jpeg_host_encode(coef, H, W, sampling, tables):
     return out[:written.value].tobytes()
 
 
+def jpeg_entropy_gpu_enabled():
+    """Whether ``encode_jpeg_batch`` also entropy-codes on the GPU (``ssd_jpeg_pack``): only with ``SSD_JPEG_ENTROPY_GPU=1``.
+    Opt-in: the default stays the host pool (DESIGN.md section 7 has the measurement and the recommendation)."""
+    import os
+    return os.environ.get("SSD_JPEG_ENTROPY_GPU", "0") == "1"
+
+
+def _jpeg_pack_layout(desc, shapes, samplings, tables):
+    """Where one ``ssd_jpeg_pack`` call's input sits: its descriptors | every image's header in ONE upload (each part at a
+    multiple of 16), taken from ``jpeg_forward_batch``'s descriptors; and ``out_bytes``, the sum of the images'
+    ``ssd_jpeg_encode_bound``, each rounded up to 16."""
+    import ctypes
+    import ssd_hip as _h
+    lib = _h.lib()
+    B = len(shapes)
+    pd = np.zeros(B, _h.JPEG_PACK_DESC_DTYPE)
+    starts, total = _place([pd.nbytes] + [_h.JPEG_HEADER_BYTES] * B)
+    infos, bound = [], 0
+    for b, ((H, W), (hs, vs)) in enumerate(zip(shapes, samplings)):
+        d = pd[b]
+        d["H"], d["W"], d["h_samp"], d["v_samp"] = H, W, hs, vs
+        d["coef_offset"], d["block_start"], d["header_offset"] = desc[b]["coef_offset"], desc[b]["block_start"], starts[1 + b]
+        info = _h.JpegInfo()
+        t = np.ascontiguousarray(tables[b], np.uint16)
+        _h.check(lib.ssd_jpeg_encode_info(int(W), int(H), int(hs), int(vs), t.ctypes.data, ctypes.byref(info)), "ssd_jpeg_encode_info")
+        infos.append(info)
+        bound += _round16(int(lib.ssd_jpeg_encode_bound(ctypes.byref(info))))
+    return {"desc": pd, "headers_at": starts[1:], "total": total, "out_bytes": bound, "infos": infos}
+
+
+def _jpeg_pack_fill(host, layout):
+    """Write the descriptors and every image's header (``ssd_jpeg_encode_header``) into ``host``."""
+    import ctypes
+    import ssd_hip as _h
+    _put(host, 0, layout["desc"])
+    header = np.empty(_h.JPEG_HEADER_BYTES, np.uint8)
+    written = ctypes.c_size_t(0)
+    for at, info in zip(layout["headers_at"], layout["infos"]):
+        _h.check(_h.lib().ssd_jpeg_encode_header(ctypes.byref(info), header.ctypes.data, header.nbytes, ctypes.byref(written)),
+                 "ssd_jpeg_encode_header")
+        assert written.value == header.nbytes
+        _put(host, at, header)
+
+
+def _jpeg_pack(coef, desc, shapes, samplings, tables):
+    """``jpeg_pack_batch`` with ``offsets`` and ``status`` still in the ONE int32 tensor that holds both (one download)."""
+    import torch
+    import ssd_hip as _h
+    dev = _h.device()
+    lib = _h.lib()
+    B = len(shapes)
+    meta = torch.empty(2 * B + 1, dtype=torch.int32, device=dev)
+    if B == 0:
+        _h.check(lib.ssd_jpeg_pack(None, 0, None, 0, None, None, 0, None, 0, None, None, None, 0, _h.stream()), "jpeg_pack_batch")
+        return torch.empty(0, dtype=torch.uint8, device=dev), meta.zero_()
+    tables = np.asarray(tables, np.uint16).reshape(B, 2, 64)
+    layout = _jpeg_pack_layout(desc, shapes, samplings, tables)
+    pd = layout["desc"]
+    packed = _upload_packed(dev, layout["total"], lambda host: _jpeg_pack_fill(host, layout))
+    out = torch.empty(layout["out_bytes"], dtype=torch.uint8, device=dev)
+    ws = _h.workspace(max(int(lib.ssd_jpeg_pack_workspace_bytes(pd.ctypes.data, B)), 16))
+    base = packed.data_ptr()
+    _h.check(lib.ssd_jpeg_pack(_h.ptr(coef), coef.numel(), base, layout["total"], pd.ctypes.data, base, B, _h.ptr(out), out.numel(),
+                               meta.data_ptr(), meta.data_ptr() + 4 * (B + 1), _h.ptr(ws), ws.numel(), _h.stream()), "jpeg_pack_batch")
+    return out, meta
+
+
+def jpeg_pack_batch(coef, desc, shapes, samplings, tables):
+    """``ssd_jpeg_pack`` on what ``jpeg_forward_batch`` returns (``coef``, ``desc``) for the same ``shapes``, ``samplings`` and
+    ``tables``: ONE packed upload (descriptors | headers), one call, no synchronisation.  Returns device tensors ``(out,
+    offsets, status)``: stream b is ``out[offsets[b]:offsets[b + 1]]`` (int32 ``[B + 1]``), ``status`` int32 ``[B]`` is
+    nonzero for an image whose coefficients the baseline cannot code (its region's content is then unspecified)."""
+    out, meta = _jpeg_pack(coef, desc, shapes, samplings, tables)
+    B = len(shapes)
+    return out, meta[:B + 1], meta[B + 1:]
+
+
+def _jpeg_pack_streams(coef, desc, shapes, samplings, tables):
+    """The streams of a batch as ``bytes`` through the device coder: two downloads (offsets + status; the streams
+    themselves, into pinned memory), sliced on the calling thread.  An image the baseline cannot code raises what the
+    host coder raises for its coefficients."""
+    import torch
+    import ssd_hip as _h
+    B = len(shapes)
+    out, meta = _jpeg_pack(coef, desc, shapes, samplings, tables)
+    meta = meta.cpu().numpy()
+    offsets, status = meta[:B + 1], meta[B + 1:]
+    bad = np.flatnonzero(status)
+    if bad.size:
+        b = int(bad[0])
+        at = int(desc[b]["coef_offset"])
+        end = int(desc[b + 1]["coef_offset"]) if b + 1 < B else coef.numel()
+        jpeg_host_encode(coef[at:end].cpu().numpy().view(np.int16), shapes[b][0], shapes[b][1], samplings[b], tables[b])
+        raise _h.SsdHipError("jpeg_pack_batch: image %d has status %d, yet the host coder takes its coefficients" % (b, status[b]))
+    n = int(offsets[B])
+    st = _pinned_staging("download", out.device, n)[0]
+    st[:n].copy_(out[:n], non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    host = st.numpy()
+    return [host[offsets[b]:offsets[b + 1]].tobytes() for b in range(B)]
+
+
 def _pillow_jpeg(args):
     import io
     from PIL import Image
@@ -740,7 +842,10 @@ def encode_jpeg_batch(images, quality=75, subsampling="4:2:0", workers=None):
     of device ``[H,W,3]`` tensors of any sizes; ``quality`` and ``subsampling`` ("4:4:4", "4:2:2", "4:2:0") may be one
     value or one per image.  Per batch: ONE descriptor upload, ONE ``ssd_jpeg_forward`` call (two launches), ONE download
     of the int16 coefficients into pinned memory; then ``ssd_jpeg_entropy_encode`` per image on ``data_workers(workers)``
-    threads.  ``SSD_JPEG_ENCODE_GPU=0``: the pixels are downloaded and Pillow encodes them on the same threads."""
+    threads.  ``SSD_JPEG_ENCODE_GPU=0``: the pixels are downloaded and Pillow encodes them on the same threads.
+    ``SSD_JPEG_ENTROPY_GPU=1`` (opt-in): the Huffman coding, the stuffing and the header run on the GPU as well
+    (``jpeg_pack_batch``); the downloads shrink to offsets + status and the finished streams, which the calling thread
+    slices into ``bytes`` -- no thread pool is used.  A batch outside ``ssd_jpeg_pack``'s limits takes the host pool."""
     import torch
     import ssd_hip as _h
     dev = _h.device()
@@ -763,7 +868,6 @@ def encode_jpeg_batch(images, quality=75, subsampling="4:2:0", workers=None):
         _h.check(_h.lib().ssd_jpeg_forward(None, 0, None, 0, None, None, 0, None, 0, None, 0, _h.stream()), "encode_jpeg_batch")
         return []
     shapes = [(int(t.shape[0]), int(t.shape[1])) for t in seq]
-    pool = _encode_pool(workers)
     if isinstance(images, torch.Tensor) and images.is_contiguous():
         rgb = images.reshape(-1)
     else:
@@ -772,7 +876,7 @@ def encode_jpeg_batch(images, quality=75, subsampling="4:2:0", workers=None):
         host = rgb.cpu().numpy()
         ends = np.cumsum([h * w * 3 for h, w in shapes])
         jobs = [(host[e - h * w * 3:e].reshape(h, w, 3), q, s) for e, (h, w), q, s in zip(ends, shapes, qualities, subs)]
-        return list(pool.map(_pillow_jpeg, jobs))
+        return list(_encode_pool(workers).map(_pillow_jpeg, jobs))
     samplings = [JPEG_SAMPLING[s] for s in subs]
     known = {}
     tables = np.empty((B, 2, 64), np.uint16)
@@ -782,6 +886,11 @@ def encode_jpeg_batch(images, quality=75, subsampling="4:2:0", workers=None):
             _h.check(_h.lib().ssd_jpeg_quality_tables(q, known[q].ctypes.data), "ssd_jpeg_quality_tables")
         tables[b] = known[q]
     coef, desc = jpeg_forward_batch(rgb, shapes, samplings, tables)
+    if jpeg_entropy_gpu_enabled():
+        try:
+            return _jpeg_pack_streams(coef, desc, shapes, samplings, tables)
+        except _h.SsdHipUnsupported:
+            pass                                                                  # outside the device coder's limits: the host pool
     st = _pinned_staging("download", dev, coef.numel())[0]
     st[:coef.numel()].copy_(coef, non_blocking=True)
     torch.cuda.current_stream().synchronize()
@@ -789,7 +898,7 @@ def encode_jpeg_batch(images, quality=75, subsampling="4:2:0", workers=None):
     ends = [int(d["coef_offset"]) for d in desc[1:]] + [coef.numel()]
     jobs = [(host[int(d["coef_offset"]):e].view(np.int16), h, w, hv, t)
             for d, e, (h, w), hv, t in zip(desc, ends, shapes, samplings, tables)]
-    return list(pool.map(lambda a: jpeg_host_encode(*a), jobs))
+    return list(_encode_pool(workers).map(lambda a: jpeg_host_encode(*a), jobs))
 
 
 def data_workers(workers=None):
