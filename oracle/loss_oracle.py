@@ -124,17 +124,18 @@ def keras_softmax(z):
 
 
 def torch_loss_and_grads(actual_deltas, actual_labels, pred_deltas, logits, neg_pos_ratio=3.0,
-                         loc_loss_alpha=1.0):
+                         loc_loss_alpha=1.0, final_mask=None):
     """Gradient oracle: the same graph in torch-CPU fp32 ops with autograd.  The model's softmax
     is part of the graph, so the returned gradients are w.r.t. pred_deltas and the LOGITS.
     Objective: Keras batch mean of loc_loss + conf_loss (compile(loss=[loc, conf]), reduction
-    SUM_OVER_BATCH_SIZE).  Returns (loc [B], conf [B], probs, d/d pred_deltas, d/d logits)."""
+    SUM_OVER_BATCH_SIZE).  ``final_mask`` [B,N]: differentiate with this selection (the device's own) instead of
+    mining again.  Returns (loc [B], conf [B], probs, d/d pred_deltas, d/d logits)."""
     import torch
     yd = torch.from_numpy(np.asarray(actual_deltas, F32))
     yl = torch.from_numpy(np.asarray(actual_labels, F32))
     pd = torch.from_numpy(np.asarray(pred_deltas, F32)).requires_grad_(True)
     z = torch.from_numpy(np.asarray(logits, F32)).requires_grad_(True)
     probs = keras_softmax(z)
-    loc, conf = torch_loss(yd, yl, pd, probs, neg_pos_ratio, loc_loss_alpha)
+    loc, conf = torch_loss(yd, yl, pd, probs, neg_pos_ratio, loc_loss_alpha, final_mask=final_mask)
     (loc + conf).mean().backward()
     return (loc.detach().numpy(), conf.detach().numpy(), probs.detach().numpy(), pd.grad.numpy(), z.grad.numpy())
