@@ -399,6 +399,107 @@ int ssd_jpeg_pack(const short* coef_dev, size_t coef_bytes, const unsigned char*
                   unsigned char* out_dev, size_t out_bytes, int* offsets_dev, int* status_dev, void* workspace_dev,
                   size_t workspace_bytes, void* stream);
 
+/* DEVICE ENTROPY DECODER (ssd_jpeg_scan_plan, ssd_jpeg_unpack): the Huffman decoding of ssd_jpeg_entropy_decode on the
+ * device, for a ragged batch, bit for bit.  A Huffman stream is bit-granular, but JPEG's self-synchronises: a decoder
+ * started at a wrong bit falls into step with the true one after a few dozen codes.  Each SEGMENT of a scan (one restart
+ * interval, or the whole scan) is cut into subsequences of subseq_bits bits; every subsequence but the first starts from
+ * the guess "a DC code of MCU block 0 begins at my first bit", and the entry states are swept until none changes.  The
+ * first state is known, so the fixed point is the true decode: exact, not heuristic.
+ *
+ * HOST (plain C++ under the rules of the host half above: no HIP call, no global state, thread-safe, nothing read outside
+ * [data, data + n)):
+ * ssd_jpeg_scan_plan: what the device needs beyond struct ssd_jpeg_info, WITHOUT decoding a code: the byte range
+ *   [data_begin, data_end) of the entropy-coded data, each component's DC and AC table in the form the decoder indexes
+ *   (huff[2 c] DC, huff[2 c + 1] AC), and the segments: info's restart_interval ? ceil(mcus / restart_interval) : 1 of
+ *   them, each with its first byte (from data_begin), its byte length and its first MCU.  A segment ends where the host
+ *   decoder's reader stops: at the first 0xFF not followed by 0x00, or at an 0xFF that is the last byte; fill bytes 0xFF
+ *   before a marker are skipped; the k-th restart must be 0xD0 + (k & 7).  SSD_E_INVALID: what ssd_jpeg_parse refuses, an
+ *   info that does not describe the stream, a wrong or missing restart marker, fewer segments than the frame needs,
+ *   seg_capacity below the number of segments.  SSD_E_UNSUPPORTED: what ssd_jpeg_parse calls so, entropy-coded data of
+ *   SSD_JPEG_UNPACK_MAX_SCAN_BYTES or more.
+ * ssd_jpeg_entropy_decode_subseq: ssd_jpeg_entropy_decode's contract (return codes, nothing written outside coef_out)
+ *   computed by the device's algorithm: the same decode core (csrc/ssd_jpeg_huff.h) through the same phases, as loops over
+ *   "threads".  SSD_OK implies that ssd_jpeg_entropy_decode returns SSD_OK with the same coefficients; it refuses
+ *   (SSD_E_INVALID) whatever the host decoder refuses.  subseq_bits as below.
+ *
+ * DEVICE (ssd_jpeg_unpack): packed_dev [packed_bytes] holds descriptors | Huffman tables | segment tables | the stuffed
+ * scan bytes [data_begin, data_end) of every image, each part at a multiple of 16.  Image b's coefficients go to
+ * coef_offset of coef_dev [coef_bytes] in exactly the storage of struct ssd_jpeg_info -- natural order, padded planes,
+ * DC terms predicted -- so a following ssd_jpeg_decode reads that buffer as its packed_dev unchanged, and no coefficient
+ * ever exists in host memory.  One call, a fixed number of launches (four kernels and two fills), asynchronous on
+ * `stream`; no workgroup waits on another.
+ *   zero    every image's region of coef_dev (blocks the stream never reaches stay zero), nothing between the regions
+ *   sync    one workgroup per image walks its subsequences in chunks of 256 and carries the settled exit state of a chunk
+ *           into the next; the sweeps are a barrier loop ended by a workgroup-wide vote, capped at 256 (the worst case of a
+ *           chunk: each sweep settles at least one more state).  Every thread counts the blocks it completes; the running
+ *           sum of the counts gives every subsequence the ordinal of the block it starts in.
+ *   write   one thread per subsequence decodes once more from its settled state: AC values to their natural index, the DC
+ *           DIFFERENCE to index 0 (a block that straddles two subsequences is written by two threads at disjoint
+ *           indices); every store is guarded by the frame's MCU count.  Blocks beyond the frame and data after the last
+ *           MCU are ignored, as on the host.
+ *   dc      per component and segment an inclusive scan of the differences in scan order (MCU order).
+ * status_dev (int32 [B]): 0, or nonzero when the settled pass meets what the host decoder refuses: a code outside its
+ *   table or an index past 63 (bit 0), bits that run out before the segment's last MCU (bit 1), a restart interval whose
+ *   last code does not end inside its segment's last byte (bit 2: the condition under which the host decoder finds the
+ *   marker where it looks -- the device is at least as strict), tables no plan produces (bit 3).  status[b] == 0 implies
+ *   that ssd_jpeg_entropy_decode returns SSD_OK with the same coefficients.  A flagged image's region may hold anything
+ *   inside its own bounds; every other image is exact.
+ * subseq_bits: 0 = SSD_JPEG_UNPACK_SUBSEQ_BITS; else a multiple of 32, at least 128 (a step spans at most 80 stuffed
+ *   bits, so a state leaves a subsequence into the next one).
+ * block_start / seg_start / sub_start: the running sums over the batch of the images' 8x8 blocks, of segments + 1, and
+ *   of ssd_jpeg_unpack_slots(scan_bytes, segments, subseq_bits) (a multiple of 256 that bounds the image's subsequences).
+ * Workspace: ssd_jpeg_unpack_workspace_bytes(desc_host, B, subseq_bits) bytes (0 for an unusable batch).  Its first B
+ *   int32 are a debug counter: the sweeps the sync phase took for image b (the most over its chunks).
+ * SSD_E_INVALID, nothing launched: NULL pointers, packed_dev / coef_dev / workspace_dev not 16-byte aligned, status_dev
+ *   not 4-byte aligned, offsets that are negative or no multiple of 16, regions outside their buffer, coefficient regions
+ *   that overlap or are out of order, coef_dev overlapping packed_dev, a segment count that is not the frame's, wrong
+ *   running sums, a workspace that is too small.  SSD_E_UNSUPPORTED, nothing launched: a subseq_bits that is no multiple
+ *   of 32 or below 128 (and not 0) or above SSD_JPEG_UNPACK_MAX_SUBSEQ_BITS, a side outside 1..16384, components /
+ *   sampling other than the decoder's, scan_bytes of SSD_JPEG_UNPACK_MAX_SCAN_BYTES or more, B > 65535, 2^31 blocks or
+ *   subsequence slots or more.  B == 0 is a no-op. */
+#define SSD_JPEG_UNPACK_SUBSEQ_BITS 1024
+#define SSD_JPEG_UNPACK_MAX_SUBSEQ_BITS 65536
+#define SSD_JPEG_UNPACK_MAX_SCAN_BYTES (1LL << 28)
+struct ssd_jpeg_huff {              /* one Huffman table as the decoder indexes it, 912 bytes                             */
+    unsigned short look[256];       /* (length << 8) | symbol for codes of at most 8 bits, 0: longer                      */
+    int maxcode[17];                /* largest code of each length, -1: none                                              */
+    int valoff[17];                 /* index of the first symbol of that length minus its first code                      */
+    unsigned char vals[256];
+    unsigned char reserved[8];
+};
+struct ssd_jpeg_segment {
+    unsigned first_byte;            /* from data_begin                                                                    */
+    unsigned bytes;                 /* stuffed bytes, without the marker that ends it                                     */
+    int first_mcu;
+    int reserved;
+};
+struct ssd_jpeg_scan_plan {
+    long long data_begin, data_end; /* the entropy-coded data: the first segment's first byte .. the last segment's end   */
+    int segments;
+    int reserved;
+    struct ssd_jpeg_huff huff[6];   /* component c: huff[2 c] DC, huff[2 c + 1] AC (a grey image: the first two)          */
+};
+int ssd_jpeg_scan_plan(const unsigned char* data, size_t n, const struct ssd_jpeg_info* info, struct ssd_jpeg_scan_plan* plan,
+                       struct ssd_jpeg_segment* segments, size_t seg_capacity);
+int ssd_jpeg_entropy_decode_subseq(const unsigned char* data, size_t n, const struct ssd_jpeg_info* info, short* coef_out,
+                                   size_t coef_bytes, int subseq_bits);
+struct ssd_jpeg_unpack_desc {
+    long long scan_offset;  /* byte offset in packed_dev of the image's stuffed scan bytes, a multiple of 16              */
+    long long scan_bytes;   /* data_end - data_begin                                                                      */
+    long long huff_offset;  /* ... of its 6 struct ssd_jpeg_huff, a multiple of 16                                        */
+    long long seg_offset;   /* ... of its `segments` struct ssd_jpeg_segment, a multiple of 16                            */
+    long long coef_offset;  /* byte offset in coef_dev of its coefficient storage, a multiple of 16                       */
+    int H, W, components;   /* components 1 or 3                                                                          */
+    int h_samp, v_samp;     /* luma sampling: 1x1, 2x1 or 2x2 (1x1 for one component)                                     */
+    int restart_interval, segments;
+    int block_start, seg_start, sub_start;
+};
+int ssd_jpeg_unpack_slots(long long scan_bytes, int segments, int subseq_bits);
+size_t ssd_jpeg_unpack_workspace_bytes(const struct ssd_jpeg_unpack_desc* desc_host, int B, int subseq_bits);
+int ssd_jpeg_unpack(const unsigned char* packed_dev, size_t packed_bytes, const struct ssd_jpeg_unpack_desc* desc_host,
+                    const struct ssd_jpeg_unpack_desc* desc_dev, int B, int subseq_bits, unsigned char* coef_dev,
+                    size_t coef_bytes, int* status_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- augmentation: augmentation.py:4-183 (used at trainer.py:42), the deterministic pieces; the random draws of the
  * reference's tf.random.uniform / sample_distorted_bounding_box calls are INPUTS (host side: tf-ssd_amd/augmentation.py).
  * Images float32 [B,H,W,C] in [0,1] (the reference augments after convert + resize).

@@ -8,8 +8,9 @@
 // Compiled with -ffp-contract=off like ssd_data.hip (no float is involved) and -fwrapv: coefficients of a hostile file may
 // wrap int32 in the IDCT; wrapping is then the defined behaviour, as on the hardware.
 #include <cstring>
+#include <vector>
 
-#include "ssd_jpeg_common.h"
+#include "ssd_jpeg_huff.h"
 
 namespace ssd {
 
@@ -478,6 +479,148 @@ extern "C" int ssd_jpeg_entropy_decode(const unsigned char* data, size_t n, cons
                     if (r != SSD_OK) return r;
                 }
     }
+    return SSD_OK;
+}
+
+// The marker walk of the scan: a memchr over the bytes, no code is decoded.  Segment ends are where bit_reader::fill stops;
+// the markers are the ones ssd_jpeg_entropy_decode looks for.
+static int scan_plan(const unsigned char* data, const size_t n, const jpeg_header& h, struct ssd_jpeg_scan_plan* plan, ssd_jpeg_segment* segs,
+                     const size_t seg_capacity) {
+    const ssd_jpeg_info& o = h.info;
+    const long mcus = (long)o.mcus_x * o.mcus_y, ri = o.restart_interval;
+    const long nseg = ri ? (mcus + ri - 1) / ri : 1;
+    SSD_CHECK_ARG((size_t)nseg <= seg_capacity, "ssd_jpeg_scan_plan: room for %zu segments, the frame has %ld", seg_capacity, nseg);
+    memset(plan, 0, sizeof(*plan));
+    for (int c = 0; c < o.components; ++c)
+        for (int a = 0; a < 2; ++a) {
+            const huff_table& t = a ? h.ac[h.ac_sel[c]] : h.dc[h.dc_sel[c]];
+            ssd_jpeg_huff& d = plan->huff[2 * c + a];
+            memcpy(d.look, t.look, sizeof(d.look));
+            memcpy(d.maxcode, t.maxcode, sizeof(d.maxcode));
+            memcpy(d.valoff, t.valoff, sizeof(d.valoff));
+            memcpy(d.vals, t.vals, sizeof(d.vals));
+            d.maxcode[0] = -1; d.valoff[0] = 0;                                   // never indexed: a defined value
+        }
+    size_t at = h.scan_at;
+    for (long k = 0; k < nseg; ++k) {
+        const size_t first = at;
+        size_t end = first;
+        for (;;) {
+            const unsigned char* ff = end < n ? (const unsigned char*)memchr(data + end, 0xFF, n - end) : nullptr;
+            if (!ff) { end = n; break; }
+            end = (size_t)(ff - data);
+            if (end + 1 < n && data[end + 1] == 0x00) { end += 2; continue; }      // a stuffed data byte
+            break;                                                                 // a marker (or the data ends in FF)
+        }
+        SSD_UNSUPPORTED_IF((long long)(end - h.scan_at) >= SSD_JPEG_UNPACK_MAX_SCAN_BYTES,
+                           "ssd_jpeg_scan_plan: %zu bytes of entropy-coded data (below %lld only)", end - h.scan_at,
+                           (long long)SSD_JPEG_UNPACK_MAX_SCAN_BYTES);
+        segs[k].first_byte = (unsigned)(first - h.scan_at);
+        segs[k].bytes = (unsigned)(end - first);
+        segs[k].first_mcu = (int)(k * ri);
+        segs[k].reserved = 0;
+        at = end;
+        if (k + 1 < nseg) {
+            SSD_CHECK_ARG(at < n && data[at] == 0xFF, "ssd_jpeg_scan_plan: bad restart marker after segment %ld", k);
+            while (at < n && data[at] == 0xFF) ++at;                              // fill bytes
+            SSD_CHECK_ARG(at < n && data[at] == 0xD0 + (k & 7), "ssd_jpeg_scan_plan: bad restart marker after segment %ld", k);
+            ++at;
+        }
+    }
+    plan->data_begin = (long long)h.scan_at;
+    plan->data_end = (long long)at;
+    plan->segments = (int)nseg;
+    return SSD_OK;
+}
+
+extern "C" int ssd_jpeg_scan_plan(const unsigned char* data, size_t n, const struct ssd_jpeg_info* info, struct ssd_jpeg_scan_plan* plan,
+                                  struct ssd_jpeg_segment* segments, size_t seg_capacity) {
+    SSD_CHECK_ARG(info && plan && segments, "ssd_jpeg_scan_plan: NULL pointer");
+    jpeg_header h;
+    const int rc = parse_header(data, n, h);
+    if (rc != SSD_OK) return rc;
+    SSD_CHECK_ARG(memcmp(&h.info, info, sizeof(*info)) == 0, "ssd_jpeg_scan_plan: info does not describe this stream");
+    return scan_plan(data, n, h, plan, segments, seg_capacity);
+}
+
+// The host model of ssd_jpeg_unpack: the phases of ssd_jpeg_unpack.hip as loops over "threads", on the decode core both
+// include.  A sweep is two loops, as the kernel's is two barrier phases: every thread decodes from its entry state, then
+// every thread takes its left neighbour's exit state.
+extern "C" int ssd_jpeg_entropy_decode_subseq(const unsigned char* data, size_t n, const struct ssd_jpeg_info* info, short* coef_out,
+                                              size_t coef_bytes, int subseq_bits) {
+    SSD_CHECK_ARG(info && coef_out, "ssd_jpeg_entropy_decode_subseq: NULL pointer");
+    const int S = subseq_bits ? subseq_bits : kUnpackDefaultBits;
+    SSD_UNSUPPORTED_IF(S % 32 != 0 || S < 128 || S > SSD_JPEG_UNPACK_MAX_SUBSEQ_BITS,
+                       "ssd_jpeg_entropy_decode_subseq: subseq_bits = %d (0, or a multiple of 32 in 128..%d)", subseq_bits,
+                       SSD_JPEG_UNPACK_MAX_SUBSEQ_BITS);
+    jpeg_header h;
+    int rc = parse_header(data, n, h);
+    if (rc != SSD_OK) return rc;
+    SSD_CHECK_ARG(memcmp(&h.info, info, sizeof(*info)) == 0, "ssd_jpeg_entropy_decode_subseq: info does not describe this stream");
+    SSD_CHECK_ARG((long long)coef_bytes >= h.info.coef_bytes, "ssd_jpeg_entropy_decode_subseq: coef_out holds %zu bytes, the image needs %lld",
+                  coef_bytes, h.info.coef_bytes);
+    const ssd_jpeg_info& o = h.info;
+    const unpack_frame f = unpack_frame_of(o.height, o.width, o.h_samp[0], o.v_samp[0], o.components);
+    const long ri = o.restart_interval;
+    std::vector<ssd_jpeg_segment> segs((size_t)(ri ? (f.mcus + ri - 1) / ri : 1));
+    struct ssd_jpeg_scan_plan plan;
+    rc = scan_plan(data, n, h, &plan, segs.data(), segs.size());
+    if (rc != SSD_OK) return rc;
+    memset(coef_out, 0, (size_t)o.coef_bytes);
+    int flags = 0;
+    std::vector<unpack_state> entry;
+    std::vector<unsigned> before;
+    for (size_t si = 0; si < segs.size(); ++si) {
+        const unpack_seg seg = {data + plan.data_begin + segs[si].first_byte, segs[si].bytes};
+        const unsigned nsub = unpack_nsub(seg.len, S);
+        const long left = f.mcus - segs[si].first_mcu;
+        const unsigned seg_blocks = (unsigned)((ri && ri < left ? ri : left) * f.nz);
+        auto end_bit = [&](const unsigned j) { const unsigned long long e = (unsigned long long)(j + 1) * S; return e < seg.len * 8ull ? (unsigned)e : seg.len * 8u; };
+        entry.assign(nsub, unpack_state{0, 0, 0});
+        before.assign(nsub + 1, 0u);
+        unpack_state carry = {0, 0, 0}, exits[kUnpackChunk];
+        unsigned counts[kUnpackChunk], running = 0;
+        bool dirty[kUnpackChunk];
+        for (unsigned base = 0; base < nsub; base += kUnpackChunk) {
+            const unsigned cnt = nsub - base < (unsigned)kUnpackChunk ? nsub - base : (unsigned)kUnpackChunk;
+            // a. synchronise: the segment's first state is known, a chunk's first is the settled exit of the chunk before
+            for (unsigned t = 0; t < cnt; ++t) {
+                entry[base + t] = base + t == 0 ? unpack_state{0, 0, 0} : (t == 0 ? carry : unpack_guess(seg, base + t, S));
+                dirty[t] = true;
+            }
+            for (int sweep = 0; sweep < kUnpackChunk; ++sweep) {
+                for (unsigned t = 0; t < cnt; ++t)
+                    if (dirty[t]) { exits[t] = unpack_sweep(seg, plan.huff, f, entry[base + t], end_bit(base + t), counts[t]); dirty[t] = false; }
+                bool any = false;
+                for (unsigned t = 1; t < cnt; ++t)
+                    if (exits[t - 1] != entry[base + t]) { entry[base + t] = exits[t - 1]; dirty[t] = true; any = true; }
+                if (!any) break;
+            }
+            carry = exits[cnt - 1];
+            // b. place: the blocks completed before each subsequence of the segment
+            for (unsigned t = 0; t < cnt; ++t) { before[base + t] = running; running += counts[t]; }
+        }
+        // c. write
+        for (unsigned j = 0; j < nsub; ++j)
+            flags |= unpack_write(seg, plan.huff, f, kZigzag, entry[j], end_bit(j), before[j], seg_blocks, segs[si].first_mcu, j + 1 == nsub,
+                                  si + 1 == segs.size(), coef_out);
+    }
+    // d. DC prediction, per component and segment in scan order.  decode_block computes coef[0] = (short)(unsigned 32-bit
+    // running sum), so a sum that wraps at 16 bits gives the same bits.
+    for (int c = 0; c < o.components; ++c) {
+        const int per = c == 0 ? f.nl : 1;
+        const long total = (long)f.mcus * per, seglen = ri ? ri * per : total;
+        unsigned short run = 0;
+        for (long e = 0; e < total; ++e) {
+            if (e % seglen == 0) run = 0;
+            short* dcv = coef_out + unpack_dc_at(f, c, per, (int)e);
+            run = (unsigned short)(run + (unsigned short)*dcv);
+            *dcv = (short)run;
+        }
+    }
+    SSD_CHECK_ARG((flags & kUnpackBadCode) == 0, "ssd_jpeg_entropy_decode_subseq: a code that is not in its table, or a coefficient index past 63");
+    SSD_CHECK_ARG((flags & kUnpackShort) == 0, "ssd_jpeg_entropy_decode_subseq: the data ends before the last MCU");
+    SSD_CHECK_ARG(flags == 0, "ssd_jpeg_entropy_decode_subseq: a restart interval does not end in its segment's last byte");
     return SSD_OK;
 }
 

@@ -69,6 +69,18 @@ class JpegInfo(ctypes.Structure):
                 ("quant", (ctypes.c_ushort * 64) * 3)]
 
 
+class JpegHuff(ctypes.Structure):
+    """struct ssd_jpeg_huff (include/ssd_hip.h): one Huffman table as the decoders index it."""
+    _fields_ = [("look", ctypes.c_ushort * 256), ("maxcode", ctypes.c_int * 17), ("valoff", ctypes.c_int * 17),
+                ("vals", ctypes.c_ubyte * 256), ("reserved", ctypes.c_ubyte * 8)]
+
+
+class JpegScanPlan(ctypes.Structure):
+    """struct ssd_jpeg_scan_plan (include/ssd_hip.h): what ``ssd_jpeg_scan_plan`` fills in beside the segment list."""
+    _fields_ = [("data_begin", ctypes.c_longlong), ("data_end", ctypes.c_longlong), ("segments", ctypes.c_int),
+                ("reserved", ctypes.c_int), ("huff", JpegHuff * 6)]
+
+
 JPEG_COEFFICIENTS, JPEG_RAW = 0, 1
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
 MOBILENET_V2, VGG16 = 0, 1
@@ -114,6 +126,12 @@ _SIGNATURES = {
     "ssd_jpeg_pack_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int]),
     "ssd_jpeg_pack": (ctypes.c_int, [vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp, ctypes.c_int, vp, ctypes.c_size_t, vp, vp, vp,
                                       ctypes.c_size_t, vp]),
+    "ssd_jpeg_scan_plan": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(JpegInfo), ctypes.POINTER(JpegScanPlan), vp, ctypes.c_size_t]),
+    "ssd_jpeg_entropy_decode_subseq": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(JpegInfo), vp, ctypes.c_size_t, ctypes.c_int]),
+    "ssd_jpeg_unpack_slots": (ctypes.c_int, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int]),
+    "ssd_jpeg_unpack_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int, ctypes.c_int]),
+    "ssd_jpeg_unpack": (ctypes.c_int, [vp, ctypes.c_size_t, vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp, vp,
+                                        ctypes.c_size_t, vp]),
     "ssd_image_mean": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp, vp, vp]),
     "ssd_augment_geometry": (ctypes.c_int, [vp] + [ctypes.c_int] * 6 + [vp, vp, vp, vp]),
     "ssd_augment_color": (ctypes.c_int, [vp] + [ctypes.c_int] * 3 + [vp, vp, vp, vp]),
@@ -220,6 +238,13 @@ JPEG_HEADER_BYTES = 623         # SSD_JPEG_HEADER_BYTES: what ssd_jpeg_encode_he
 JPEG_PACK_DESC_DTYPE = np.dtype([("coef_offset", "<i8"), ("header_offset", "<i8")] + [
     (n, "<i4") for n in ("H", "W", "h_samp", "v_samp", "block_start", "reserved")])         # struct ssd_jpeg_pack_desc
 assert JPEG_PACK_DESC_DTYPE.itemsize == 40
+JPEG_UNPACK_SUBSEQ_BITS = 1024  # SSD_JPEG_UNPACK_SUBSEQ_BITS: what subseq_bits = 0 means
+JPEG_HUFF_BYTES = 6 * ctypes.sizeof(JpegHuff)                                              # one image's six tables
+JPEG_SEGMENT_DTYPE = np.dtype([("first_byte", "<u4"), ("bytes", "<u4"), ("first_mcu", "<i4"), ("reserved", "<i4")])   # struct ssd_jpeg_segment
+JPEG_UNPACK_DESC_DTYPE = np.dtype([(n, "<i8") for n in ("scan_offset", "scan_bytes", "huff_offset", "seg_offset", "coef_offset")] + [
+    (n, "<i4") for n in ("H", "W", "components", "h_samp", "v_samp", "restart_interval", "segments", "block_start", "seg_start",
+                         "sub_start")])                                                    # struct ssd_jpeg_unpack_desc
+assert JPEG_UNPACK_DESC_DTYPE.itemsize == 80 and JPEG_SEGMENT_DTYPE.itemsize == 16 and JPEG_HUFF_BYTES == 5472
 
 _lib = None
 _inited = False

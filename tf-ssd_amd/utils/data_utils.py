@@ -227,16 +227,17 @@ def _pinned_staging(kind, dev, nbytes):
     return st
 
 
-def _upload_packed(dev, total, fill):
+def _upload_packed(dev, total, fill, device_total=None):
     """``fill(host)`` writes ``total`` bytes into the device's pinned staging buffer (reused once the previous batch's
-    copy has left it); ONE asynchronous copy on the current stream makes the device buffer."""
+    copy has left it); ONE asynchronous copy on the current stream makes the device buffer.  ``device_total``: the device
+    buffer is that long, and what lies behind the upload is left for kernels to write."""
     import torch
     st = _pinned_staging("upload", dev, total)
     if st[1] is not None:
         st[1].synchronize()                                                       # the previous batch's copy has left the buffer
     fill(st[0].numpy())
-    packed = torch.empty(total, dtype=torch.uint8, device=dev)
-    packed.copy_(st[0][:total], non_blocking=True)
+    packed = torch.empty(total if device_total is None else device_total, dtype=torch.uint8, device=dev)
+    packed[:total].copy_(st[0][:total], non_blocking=True)
     st[1] = torch.cuda.Event()
     st[1].record()
     return packed
@@ -411,6 +412,24 @@ class JpegCoefficients(object):
         self.info, self.coef, self.blob = info, coef, blob
 
 
+class JpegScan(JpegCoefficients):
+    """One baseline JPEG whose Huffman decoding is left to the device (``ssd_jpeg_unpack``): ``info``, the file's bytes
+    (``blob``), ``plan`` (``ssd_hip.JpegScanPlan``) and ``segments`` (``JPEG_SEGMENT_DTYPE`` records); ``coef`` stays None."""
+    __slots__ = ("plan", "segments")
+
+    def __init__(self, info, blob, plan, segments):
+        JpegCoefficients.__init__(self, info, None, blob)
+        self.plan, self.segments = plan, segments
+
+
+def jpeg_entropy_decode_gpu_enabled():
+    """Whether the JPEG road also Huffman-decodes on the GPU (``ssd_jpeg_unpack``): only with
+    ``SSD_JPEG_ENTROPY_DECODE_GPU=1``.  Opt-in (DESIGN.md section 7 has the measurement); the pixels are the same either
+    way.  ``SSD_JPEG_ENTROPY_GPU`` is the encoder's switch."""
+    import os
+    return os.environ.get("SSD_JPEG_ENTROPY_DECODE_GPU", "0") == "1"
+
+
 def _pillow_rgb(blob):
     """What the loaders did before: ``Image.open(...).convert("RGB")`` (raises what it raised before)."""
     import io
@@ -437,6 +456,29 @@ def _jpeg_entropy_into(blob, info, address, nbytes):
     import ctypes
     import ssd_hip as _h
     return _h.lib().ssd_jpeg_entropy_decode(blob, len(blob), ctypes.byref(info), address, nbytes) == 0
+
+
+def _jpeg_plan(blob, info):
+    """``JpegScan`` of a parsed stream, or None where ``ssd_jpeg_scan_plan`` refuses it (a bad restart marker, a scan too
+    large for the device decoder): the host decoder's business then."""
+    import ctypes
+    import ssd_hip as _h
+    mcus = info.mcus_x * info.mcus_y
+    segments = np.zeros(-(-mcus // info.restart_interval) if info.restart_interval else 1, _h.JPEG_SEGMENT_DTYPE)
+    plan = _h.JpegScanPlan()
+    rc = _h.lib().ssd_jpeg_scan_plan(blob, len(blob), ctypes.byref(info), ctypes.byref(plan), segments.ctypes.data, len(segments))
+    return JpegScan(info, blob, plan, segments) if rc == 0 else None
+
+
+def jpeg_host_plan(blob, fallback=_pillow_rgb):
+    """``jpeg_host_decode``'s sibling for ``SSD_JPEG_ENTROPY_DECODE_GPU=1``, for a worker thread: parse the file and plan
+    its scan -- a walk over the markers, no code is decoded -- into a ``JpegScan``.  A stream the plan refuses goes the
+    way of ``jpeg_host_decode``."""
+    blob = bytes(blob)
+    info = _jpeg_parse(blob)
+    if info is None:
+        return fallback(blob)
+    return _jpeg_plan(blob, info) or jpeg_host_decode(blob, fallback)
 
 
 def jpeg_host_decode(blob, fallback=_pillow_rgb):
@@ -475,10 +517,11 @@ def _jpeg_items(blobs, fallback):
     return items
 
 
-def _jpeg_layout(items):
+def _jpeg_layout(items, subseq_bits=0):
     """Where one ``ssd_jpeg_decode`` call's input sits in ONE buffer: jpeg descriptors | output descriptors | quantisation
     tables | per image its coefficients or raw pixels, each part at a multiple of 16 bytes; and where the output images
-    and the component planes go."""
+    and the component planes go.  With ``JpegScan`` items the buffer goes on: ``ssd_jpeg_unpack``'s input
+    (``_jpeg_unpack_layout``) up to ``upload``, and behind it, never uploaded, the coefficients that call writes."""
     import ssd_hip as _h
     B = len(items)
     desc = np.zeros(B, _h.JPEG_DESC_DTYPE)
@@ -486,7 +529,26 @@ def _jpeg_layout(items):
     quant_bytes = _h.JpegInfo.quant.size
     (_, out_at, quant_at), payload_at = _place([desc.nbytes, out_desc.nbytes, quant_bytes * B])
     coded = [isinstance(x, JpegCoefficients) for x in items]
-    starts, total = _place([int(x.info.coef_bytes) if c else x.size for x, c in zip(items, coded)], payload_at)
+    sizes = [int(x.info.coef_bytes) if c else x.size for x, c in zip(items, coded)]
+    scans = [b for b, x in enumerate(items) if isinstance(x, JpegScan)]
+    unpack = None
+    if not scans:
+        starts, total = _place(sizes, payload_at)
+        upload = total
+    else:
+        # what the host fills first, then ssd_jpeg_unpack's input, and behind the upload the coefficients it writes
+        held = [b for b in range(B) if b not in set(scans)]
+        starts = [0] * B
+        at, upload = _place([sizes[b] for b in held], payload_at)
+        for b, a in zip(held, at):
+            starts[b] = a
+        unpack = _jpeg_unpack_layout([items[b] for b in scans], subseq_bits, at=upload)
+        upload = unpack["total"]
+        at, total = _place([sizes[b] for b in scans], upload)
+        for b, a in zip(scans, at):
+            starts[b] = a
+        unpack["desc"]["coef_offset"] = [a - upload for a in at]
+        unpack["coef_bytes"] = total - upload
     blocks = n_items = rgb_bytes = plane_bytes = 0
     for b, x in enumerate(items):
         d = desc[b]
@@ -505,7 +567,7 @@ def _jpeg_layout(items):
         n_items += (int(d["H"]) * int(d["W"]) + 3) // 4
     assert plane_bytes == _h.lib().ssd_jpeg_decode_workspace_bytes(desc.ctypes.data, B)
     return {"desc": desc, "out_desc": out_desc, "out_at": out_at, "total": total, "rgb_bytes": rgb_bytes,
-            "plane_bytes": plane_bytes}
+            "plane_bytes": plane_bytes, "upload": upload, "unpack": unpack, "scans": scans}
 
 
 def _jpeg_fill(host, items, layout, failed):
@@ -524,8 +586,94 @@ def _jpeg_fill(host, items, layout, failed):
         _put(host, int(desc[b]["quant_offset"]), np.frombuffer(x.info, np.uint8)[quant.offset:quant.offset + quant.size])
         if x.coef is not None:
             _put(host, at, x.coef)
+        elif isinstance(x, JpegScan):
+            continue                                                              # ssd_jpeg_unpack writes them on the device
         elif not _jpeg_entropy_into(x.blob, x.info, host.ctypes.data + at, int(x.info.coef_bytes)):
             failed.append(b)
+    if layout["unpack"] is not None:
+        _jpeg_unpack_fill(host, [items[b] for b in layout["scans"]], layout["unpack"])
+
+
+def _jpeg_unpack_layout(scans, subseq_bits=0, at=0):
+    """Where one ``ssd_jpeg_unpack`` call's input sits from ``at`` on: descriptors | per image its six Huffman tables |
+    its segment table | its stuffed scan bytes, each part at a multiple of 16.  ``coef_offset`` is laid out for a
+    coefficient buffer of its own (``coef_bytes``); a caller that places the coefficients elsewhere overwrites it."""
+    import ssd_hip as _h
+    B = len(scans)
+    desc = np.zeros(B, _h.JPEG_UNPACK_DESC_DTYPE)
+    sizes = [desc.nbytes] + [_h.JPEG_HUFF_BYTES] * B + [x.segments.nbytes for x in scans] + [
+        int(x.plan.data_end - x.plan.data_begin) for x in scans]
+    starts, total = _place(sizes, at)
+    coef_at, coef_bytes = _place([int(x.info.coef_bytes) for x in scans])
+    blocks = segs = slots = 0
+    for b, x in enumerate(scans):
+        d, i = desc[b], x.info
+        d["huff_offset"], d["seg_offset"], d["scan_offset"] = starts[1 + b], starts[1 + B + b], starts[1 + 2 * B + b]
+        d["scan_bytes"], d["coef_offset"] = sizes[1 + 2 * B + b], coef_at[b]
+        d["H"], d["W"], d["components"], d["h_samp"], d["v_samp"] = i.height, i.width, i.components, i.h_samp[0], i.v_samp[0]
+        d["restart_interval"], d["segments"] = i.restart_interval, len(x.segments)
+        d["block_start"], d["seg_start"], d["sub_start"] = blocks, segs, slots
+        blocks += int(i.coef_bytes) // 128
+        segs += len(x.segments) + 1
+        slots += _h.lib().ssd_jpeg_unpack_slots(int(d["scan_bytes"]), len(x.segments), subseq_bits)
+    return {"desc": desc, "desc_at": starts[0], "total": total, "coef_bytes": coef_bytes, "subseq_bits": int(subseq_bits)}
+
+
+def _jpeg_unpack_fill(host, scans, layout):
+    import ssd_hip as _h
+    desc = layout["desc"]
+    _put(host, layout["desc_at"], desc)
+    huff = _h.JpegScanPlan.huff
+    for d, x in zip(desc, scans):
+        _put(host, int(d["huff_offset"]), np.frombuffer(x.plan, np.uint8)[huff.offset:huff.offset + huff.size])
+        _put(host, int(d["seg_offset"]), x.segments)
+        _put(host, int(d["scan_offset"]), np.frombuffer(x.blob, np.uint8)[int(x.plan.data_begin):int(x.plan.data_end)])
+
+
+def _jpeg_unpack_launch(packed_ptr, layout, coef_ptr, ws_extra=0, what="jpeg_unpack_batch"):
+    """``ssd_jpeg_unpack`` on a device copy of the filled buffer (``packed_ptr``: its first byte), on the current stream;
+    returns the int32 device tensor ``[2, B]``: ``status`` and the debug counter ``sweeps``.  The workspace is at least
+    ``ws_extra`` bytes, for the call that follows on the same stream."""
+    import torch
+    import ssd_hip as _h
+    desc, bits = layout["desc"], layout["subseq_bits"]
+    B = len(desc)
+    need = int(_h.lib().ssd_jpeg_unpack_workspace_bytes(desc.ctypes.data, B, bits))
+    ws = _h.workspace(max(need, ws_extra, 16))
+    meta = torch.empty((2, B), dtype=torch.int32, device=_h.device())
+    _h.check(_h.lib().ssd_jpeg_unpack(packed_ptr, layout["total"], desc.ctypes.data, packed_ptr + layout["desc_at"], B, bits, coef_ptr,
+                                      layout["coef_bytes"], meta.data_ptr(), _h.ptr(ws), ws.numel(), _h.stream()), what)
+    meta[1].copy_(ws[:4 * B].view(torch.int32))                                    # the sweeps: the workspace's first B int32
+    return meta
+
+
+def jpeg_unpack_batch(blobs, subseq_bits=0):
+    """The bare ``ssd_jpeg_unpack`` call: baseline JPEG files' ``bytes`` (or ``JpegScan``) -> ``(coef, desc, status,
+    sweeps)``: a uint8 device buffer that holds image b's coefficient storage -- ``ssd_jpeg_entropy_decode``'s, bit for
+    bit -- at ``desc[b]["coef_offset"]``, the ``JPEG_UNPACK_DESC_DTYPE`` descriptors, and two int32 device tensors
+    ``[B]``: ``status`` (nonzero: the host decoder's business) and the sweeps the synchronise phase took.  ONE upload: the
+    files' scan bytes and their plans.  ``ValueError`` for a stream ``ssd_jpeg_parse`` or ``ssd_jpeg_scan_plan`` refuses."""
+    import torch
+    import ssd_hip as _h
+    dev = _h.device()
+    scans = []
+    for x in blobs:
+        if not isinstance(x, JpegScan):
+            x = bytes(x)
+            info = _jpeg_parse(x)
+            x = _jpeg_plan(x, info) if info is not None else None
+            if x is None:
+                raise ValueError("jpeg_unpack_batch: %s" % _h.lib().ssd_last_error().decode())
+        scans.append(x)
+    if not scans:
+        _h.check(_h.lib().ssd_jpeg_unpack(None, 0, None, None, 0, int(subseq_bits), None, 0, None, None, 0, _h.stream()), "jpeg_unpack_batch")
+        empty = torch.empty(0, dtype=torch.int32, device=dev)
+        return torch.empty(0, dtype=torch.uint8, device=dev), np.zeros(0, _h.JPEG_UNPACK_DESC_DTYPE), empty, empty
+    layout = _jpeg_unpack_layout(scans, subseq_bits)
+    packed = _upload_packed(dev, layout["total"], lambda host: _jpeg_unpack_fill(host, scans, layout))
+    coef = torch.empty(max(layout["coef_bytes"], 16), dtype=torch.uint8, device=dev)
+    meta = _jpeg_unpack_launch(packed.data_ptr(), layout, _h.ptr(coef))
+    return coef, layout["desc"], meta[0], meta[1]
 
 
 class JpegBatch(object):
@@ -541,7 +689,10 @@ class JpegBatch(object):
 def decode_jpeg_batch(blobs, out_u8=False, fallback=_pillow_rgb):
     """A list of JPEG files' ``bytes`` -> their pixels on the GPU, bitwise ``PIL.Image.open(...).convert("RGB")``'s, as a
     ``JpegBatch``.  Per batch: parse, lay out, entropy-decode straight into the pinned staging buffer, ONE upload, ONE
-    ``ssd_jpeg_decode`` call (two launches).  A stream the library calls unsupported (progressive, CMYK, ...) or
+    ``ssd_jpeg_decode`` call (two launches).  ``SSD_JPEG_ENTROPY_DECODE_GPU=1`` (opt-in): the host only plans each scan
+    (``ssd_jpeg_scan_plan``), the upload carries the files' scan bytes instead of their coefficients, and
+    ``ssd_jpeg_unpack`` Huffman-decodes them into the buffer ``ssd_jpeg_decode`` then reads; an image that call flags is
+    redone by the host decoder, so the pixels are the same for every input.  A stream the library calls unsupported (progressive, CMYK, ...) or
     malformed is decoded by ``fallback`` -- Pillow, exactly as before, raising what it raised before -- and travels as raw
     pixels in the same upload; entries may also be ``JpegCoefficients`` from ``jpeg_host_decode`` (the data pool's
     threads) or uint8 ``[H,W,3]`` arrays.  ``out_u8``: a contiguous 1-D uint8 device tensor, 16-byte aligned and large
@@ -554,27 +705,48 @@ def decode_jpeg_batch(blobs, out_u8=False, fallback=_pillow_rgb):
     if B == 0:
         _h.check(_h.lib().ssd_jpeg_decode(None, 0, None, None, 0, None, 0, None, None, None, 0, _h.stream()), "decode_jpeg_batch")
         return JpegBatch([], torch.empty(0, dtype=torch.uint8, device=dev), np.zeros(0, _h.IMAGE_DESC_DTYPE), 0, None, [])
+    if jpeg_entropy_decode_gpu_enabled():                                         # the files' scans go up, not their coefficients
+        for b, x in enumerate(items):
+            if isinstance(x, JpegCoefficients) and x.coef is None and not isinstance(x, JpegScan):
+                items[b] = _jpeg_plan(x.blob, x.info) or x
+    def to_host_decoder():
+        # rare: what the device decoder flags or cannot take goes the host decoder's way (and Pillow's, if that refuses
+        # too) with the whole batch, so the result is the default road's for every input whatsoever
+        for b, x in enumerate(items):
+            if isinstance(x, JpegScan):
+                items[b] = JpegCoefficients(x.info, None, x.blob)
     while True:
-        layout = _jpeg_layout(items)
-        failed = []
-        packed = _upload_packed(dev, layout["total"], lambda host: _jpeg_fill(host, items, layout, failed))
-        if not failed:
+        while True:
+            layout = _jpeg_layout(items)
+            failed = []
+            packed = _upload_packed(dev, layout["upload"], lambda host: _jpeg_fill(host, items, layout, failed), layout["total"])
+            if not failed:
+                break
+            for b in failed:                                                      # malformed past the header: Pillow's business
+                items[b] = np.asarray(fallback(items[b].blob))
+        base, meta = packed.data_ptr(), None
+        if layout["unpack"] is not None:
+            try:
+                meta = _jpeg_unpack_launch(base, layout["unpack"], base + layout["upload"], layout["plane_bytes"], "decode_jpeg_batch")
+            except _h.SsdHipUnsupported:
+                to_host_decoder()
+                continue
+        if out_u8 is None or out_u8 is False:
+            rgb = torch.empty(max(layout["rgb_bytes"], 16), dtype=torch.uint8, device=dev)
+        else:
+            rgb = out_u8
+            if (not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8 or rgb.device != dev or rgb.dim() != 1
+                    or not rgb.is_contiguous() or rgb.numel() < layout["rgb_bytes"] or rgb.data_ptr() % 16):
+                raise ValueError("out_u8 must be a contiguous 1-D uint8 device tensor of at least %d bytes, 16-byte aligned"
+                                 % layout["rgb_bytes"])
+        ws = _h.workspace(max(layout["plane_bytes"], 16))
+        desc, out_desc = layout["desc"], layout["out_desc"]
+        _h.check(_h.lib().ssd_jpeg_decode(base, layout["total"], desc.ctypes.data, base, B, _h.ptr(rgb), rgb.numel(),
+                                          out_desc.ctypes.data, base + layout["out_at"], _h.ptr(ws), ws.numel(), _h.stream()),
+                 "decode_jpeg_batch")
+        if meta is None or not meta[0].cpu().numpy().any():                       # the status: ONE small read
             break
-        for b in failed:                                                          # malformed past the header: Pillow's business
-            items[b] = np.asarray(fallback(items[b].blob))
-    if out_u8 is None or out_u8 is False:
-        rgb = torch.empty(max(layout["rgb_bytes"], 16), dtype=torch.uint8, device=dev)
-    else:
-        rgb = out_u8
-        if (not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8 or rgb.device != dev or rgb.dim() != 1
-                or not rgb.is_contiguous() or rgb.numel() < layout["rgb_bytes"] or rgb.data_ptr() % 16):
-            raise ValueError("out_u8 must be a contiguous 1-D uint8 device tensor of at least %d bytes, 16-byte aligned"
-                             % layout["rgb_bytes"])
-    ws = _h.workspace(max(layout["plane_bytes"], 16))
-    desc, out_desc, base = layout["desc"], layout["out_desc"], packed.data_ptr()
-    _h.check(_h.lib().ssd_jpeg_decode(base, layout["total"], desc.ctypes.data, base, B, _h.ptr(rgb), rgb.numel(),
-                                      out_desc.ctypes.data, base + layout["out_at"], _h.ptr(ws), ws.numel(), _h.stream()),
-             "decode_jpeg_batch")
+        to_host_decoder()
     images = [rgb[int(o["src_offset"]):int(o["src_offset"]) + int(o["H"]) * int(o["W"]) * 3].view(int(o["H"]), int(o["W"]), 3)
               for o in out_desc]
     return JpegBatch(images, rgb, out_desc, base + layout["out_at"], packed, [int(k) for k in desc["kind"]])
@@ -961,10 +1133,12 @@ class voc_batches(object):
             pool.shutdown(wait=True, cancel_futures=True)
 
     def _load_encoded(self, record):
-        """The pool's job unless ``SSD_JPEG_GPU=0``: read the file, parse it, entropy-decode it (no pixels yet)."""
+        """The pool's job unless ``SSD_JPEG_GPU=0``: read the file, parse it, entropy-decode it (no pixels yet) -- or, with
+        ``SSD_JPEG_ENTROPY_DECODE_GPU=1``, only plan its scan."""
         item = self.dataset.load_encoded(record)
         if "image" not in item:
-            item["image"] = jpeg_host_decode(item.pop("image_bytes"))
+            decode = jpeg_host_plan if jpeg_entropy_decode_gpu_enabled() else jpeg_host_decode
+            item["image"] = decode(item.pop("image_bytes"))
         return item
 
     def _batch(self, items):
