@@ -736,10 +736,11 @@ def test_image_block_kernel_vs_layer_kernels(B, ticket):
 
 @pytest.mark.parametrize("B,S", [(5, 300), (64, 300), (3, 512)])
 def test_band3_weights_through_lds_dma_bitwise(B, S):
-    """The split row-band kernel (blocks 3-6) with its weight fragments staged by LDS-DMA (two We stages + one Wp stage of 1 KB
-    blocks; option image_v2 = the "second forms", default) against the form that prefetches them into registers: the SAME
-    arithmetic in the same order -- block 6's output (stem + blocks 1-6) is bitwise equal, incl. the lone last chunk of the
-    144-channel block 3 and the 512 x 512 graph's pitches."""
+    """Option image_v2 selects the whole-image kernel's form only and does not touch blocks 1-6: the split row-band kernel
+    (blocks 3-6) has one form, with its weight fragments staged by LDS-DMA (two We stages + one Wp stage of 1 KB blocks).  With
+    image_v2 0 and 1 the outputs of blocks 3, 5 and 6 (stem + blocks 1-6) are bitwise equal, incl. the lone last chunk of the
+    144-channel block 3 and the 512 x 512 graph's pitches.  (The form that prefetched the fragments into registers, which
+    image_v2 0 used to select here and which this test held bitwise equal to the LDS-DMA form, is gone.)"""
     from models.ssd_mobilenet_v2 import get_model
     hp = helpers.hyper_params("mobilenet_v2")
     if S == 512:

@@ -71,7 +71,7 @@ struct FusedBlockParams {
     int groups;                 // G >= 1 (filled by the caller from image_block_groups)
     const short* we3;           // split-bf16 band kernel (csrc/ssd_band3.hip): bf16 planes of we [4][Ce][32] (h, m, l, r) ...
     const short* wp3;           // ... and of wp [4][npad_p][pairs][4][8]
-    int bands;                  // row-band kernel (csrc/ssd_bandblock.hip): bands per image (filled by the launcher)
+    int bands;                  // row-band kernels (csrc/ssd_band_common.h): bands per image (filled by the launcher)
     float* slabs;               // [G][B][Ho*Wo][Cout] partial sums (G > 1)
     unsigned* tickets;          // [B] arrival counters, zero between launches
     float* e_out;               // optional: the expanded map [B,H,W,Ce] is ALSO written to HBM (block 13: SSD feature map 1)
@@ -84,7 +84,7 @@ struct FusedBlockParams {
     int planes_np;
     int planes_only;            // whole-image kernel: bit 0 = y, bit 1 = the expanded map leave as planes ONLY (no fp32 store; every
                                 // consumer reads the planes).  The pointers y / e_out stay set: they also say which shapes a kernel takes
-    int form2;                  // whole-image kernel: 1 = take the second form (csrc/ssd_imgblock2.hip) where it has a configuration
+    int form2;                  // whole-image kernel only: 1 = take the second form (csrc/ssd_imgblock2.hip) where it has a configuration.  The row-band kernels have one form and ignore it
 };
 // Fused MobileNetV2 stem (Conv1 -> expanded_conv_depthwise -> expanded_conv_project).
 struct StemParams {

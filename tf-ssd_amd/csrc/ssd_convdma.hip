@@ -20,11 +20,10 @@
 //     (ssd_bf16x3.h); np = 1 (the bf16 mode): bf16 STORAGE of the activation, one MFMA per block, K = 64 per barrier.
 // Epilogue = conv_epilogue (ssd_conv_mfma.h): BN / bias, activation, residual, head routing, optional plane output.
 // config ids: behind the bf16 tiles (ssd_conv.hip): "dma3_*" (np = 3) and "dmab_*" (np = 1).
+#include "ssd_block_common.h"
 #include "ssd_conv_mfma.h"
 
 namespace ssd {
-
-typedef __attribute__((address_space(3))) void* lds_dst_t;
 
 // (the body is a __device__ function: a __global__ body that declares __amdgpu_buffer_rsrc_t objects loses its host stub)
 template <int MT, int NT, int WM, int WN, int NP, bool GEMM1X1>

@@ -22,11 +22,10 @@
 // output channels (gridDim.y): each half recomputes the (cheap, VALU) depthwise.
 
 #include "ssd_bf16x3.h"
+#include "ssd_block_common.h"
 #include "ssd_conv.h"
 
 namespace ssd {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -37,24 +36,8 @@ constexpr int kCQ = kCK / 4;      // channel quads per chunk
 // shape keeps 13 so that its double-buffered tiles still fit the 160 KB of LDS.
 constexpr int ld_for(int stride) { return stride == 2 ? kCK + 4 : kCK + 8; }
 
-__device__ __forceinline__ float relu6f(float v) { return fminf(fmaxf(v, 0.0f), 6.0f); }
-
-// LDS-only workgroup barrier and compiler-invisible prefetch loads: the same idiom as in
-// ssd_fused.hip (see the comments there) -- the next chunk's E tile / weights stay in flight
-// across the depthwise and MFMA phases; hipcc would drain them at the first barrier otherwise.
-// Every issued load IS consumed (an unconsumed asm load's destination is dead to the compiler).
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ f32x4 gload16_async(const float* ptr) {
-    f32x4 v;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(ptr) : "memory");
-    return v;
-}
-template <int N>
-__device__ __forceinline__ void wait_prefetch(f32x4 (&r)[N]) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int i = 0; i < N; ++i) asm volatile("" : "+v"(r[i]));
-}
+// lds_barrier() and the gload16_async / wait_prefetch loads (ssd_block_common.h): the next chunk's E tile /
+// weights stay in flight across the depthwise and MFMA phases.
 
 template <int S, int TH, int TW, int SL, int WM, int WN, int NTW>
 struct DwProjShape {

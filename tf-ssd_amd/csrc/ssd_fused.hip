@@ -21,40 +21,9 @@
 
 #include "ssd_conv.h"
 #include "ssd_bf16x3.h"
+#include "ssd_block_common.h"
 
 namespace ssd {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float relu6f(float v) { return fminf(fmaxf(v, 0.0f), 6.0f); }
-
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() carries a workgroup fence
-// over ALL address spaces, and since vmcnt also counts stores on gfx950 the compiler then
-// drains every outstanding global load (s_waitcnt vmcnt(0)) at the first LDS access after
-// the barrier -- which would stall on the weight / next-tile prefetch that is deliberately
-// kept in flight across the phases of this kernel.
-__device__ __forceinline__ void lds_barrier() {
-    // (an address-space-restricted __builtin_amdgcn_fence(..., "local") still drained vmcnt on
-    // ROCm 7.2, hence the explicit LDS-counter wait + raw barrier; "memory" keeps the compiler
-    // from moving LDS accesses across it)
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-// Prefetch loads the compiler must not wait for: a 16-byte global load issued through inline
-// asm is invisible to hipcc's s_waitcnt bookkeeping, so it stays in flight across the phase
-// barriers; wait_prefetch() is the matching hand-placed wait (every destination is passed
-// through an empty "+v" statement so no consumer can be scheduled above the wait).
-__device__ __forceinline__ f32x4 gload16_async(const float* ptr) {
-    f32x4 v;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(ptr) : "memory");
-    return v;
-}
-template <int N>
-__device__ __forceinline__ void wait_prefetch(f32x4 (&r)[N]) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int i = 0; i < N; ++i) asm volatile("" : "+v"(r[i]));
-}
 
 constexpr int kCK = 48;          // expanded channels per chunk
 // LDS row strides.  A b128 access of 16 rows x 4 column groups (MFMA fragments, accumulator-layout
@@ -103,7 +72,6 @@ __device__ __forceinline__ void expand_px_tiles(const float* Xs, const float* We
     if (CINP % 16 == 8) {
         // K tail of 8 (Cin = 24): lane group g reads k = 16*(CINP/16) + 2g + {0, 1} with one
         // ds_read_b64, i.e. 2 MFMA k-steps instead of the 4 a zero-padded 16-wide unit would cost
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
         constexpr int K0 = CINP / 16 * 16;
         const int fk2 = (lane >> 4) * 2;
         f32x2 xb2[NP], wa2[3];
@@ -570,7 +538,7 @@ __device__ __forceinline__ void stem_body(const StemParams& p, float* __restrict
                 const int iy = iy0 + du_row[j];
                 const bool ok = du_row[j] < kSPH && (unsigned)iy < (unsigned)p.H;
                 const int off = ok ? (iy * p.W * 3 + fs + du_q[j] * 4) * 4 : (int)0x80000000;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(patch + stage * kSPS + ii * 256), 16, off, 0, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_dst_t)(patch + stage * kSPS + ii * 256), 16, off, 0, 0, 0);
             }
         }
     };

@@ -30,11 +30,10 @@
 //   G = 1 (B >= #CUs): direct epilogue, no slabs.
 
 #include "ssd_bf16x3.h"
+#include "ssd_block_common.h"
 #include "ssd_conv.h"
 
 namespace ssd {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -42,24 +41,10 @@ constexpr int kIC = 16;           // expanded channels per chunk
 constexpr int kILD = 24;          // LDS row stride (floats) of the E / Wp chunk tiles: 6 quads, conflict-free b128 fragments
 constexpr int kIThreads = 512;
 
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// compiler-invisible prefetch loads + the matching hand-placed wait (idiom of ssd_fused.hip:
-// every issued load IS consumed)
-__device__ __forceinline__ f32x4 gload16_async(const float* ptr) {
-    f32x4 v;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(ptr) : "memory");
-    return v;
-}
 // write-through (sc1) 16-byte store: the slab lines do not stay dirty in this XCD's L2, so publishing
 // them needs no L2 write-back fence (cdna_hip_programming.md, in-launch split-K reduction)
 __device__ __forceinline__ void gstore16_sc1(float* ptr, f32x4 v) {
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(ptr), "v"(v) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_prefetch(f32x4 (&r)[N]) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int i = 0; i < N; ++i) asm volatile("" : "+v"(r[i]));
 }
 
 // S = 2 (block 13): the depthwise / project side works on the Ho x Wo output map (its own pixel space

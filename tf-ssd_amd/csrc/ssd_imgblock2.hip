@@ -25,18 +25,14 @@
 // chunk); everything else keeps the first form.
 
 #include "ssd_bf16x3.h"
+#include "ssd_block_common.h"
 #include "ssd_conv.h"
 
 namespace ssd {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_dst2_t;
-
 namespace {
 
 constexpr int kC = 16;            // expanded channels per chunk
-
-__device__ __forceinline__ void lds_barrier2() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // (a __device__ body: a __global__ function that declares __amdgpu_buffer_rsrc_t objects loses its host stub)
 // LOOP 0: one chunk per iteration (runtime buffer parity, project every second chunk); 1: unrolled by chunk pairs.
@@ -94,14 +90,14 @@ __device__ __forceinline__ void image16v2_body(const FusedBlockParams& p, float*
         const int ch0 = cbeg + (j >> 1) * 32 + (j & 1) * 4;
         for (int b = wave_s; b < NBE; b += NW) {
             const int pl = b / KS, ks = b - pl * KS;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_e, (lds_dst2_t)(Wes + (stage * NBE + b) * 512), 16, voff_e,
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_e, (lds_dst_t)(Wes + (stage * NBE + b) * 512), 16, voff_e,
                                                      (int)((pl * plane_e + (long)ch0 * p.kpad_e + ks * 32) * 2), 0, 0);
         }
     };
     auto dma_wp = [&](const int pair) {
         for (int b = wave_s; b < NBP; b += NW) {
             const int pl = b / NT, nb = b - pl * NT;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_p, (lds_dst2_t)(Wps + b * 512), 16, voff_p,
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_p, (lds_dst_t)(Wps + b * 512), 16, voff_p,
                                                      (int)((pl * plane_p + (long)nb * 16 * p.kpad_p + cbeg + pair * 32) * 2), 0, 0);
         }
     };
@@ -253,7 +249,7 @@ __device__ __forceinline__ void image16v2_body(const FusedBlockParams& p, float*
         f32x4 dprev[TO];
         for (int c = 0; c < nchunk; ++c) {
             dma_wait();              // the copies issued an iteration ago have landed ...
-            lds_barrier2();          // ... and are visible; E(c) is visible; everyone is done with E(c - 1)
+            lds_barrier();          // ... and are visible; E(c) is visible; everyone is done with E(c - 1)
             const int pb = c & 1;
             if (c + 2 < nchunk) dma_we(c + 2, pb);                  // the stage expand(c) read before this barrier
             if (!pb && c > 0) dma_wp(c >> 1);                       // everyone projected the pair before at iteration c - 1
@@ -271,13 +267,13 @@ __device__ __forceinline__ void image16v2_body(const FusedBlockParams& p, float*
         for (int i = 0; i < nchunk; i += 2) {
             f32x4 a0[TO], a1[TO];
             dma_wait();
-            lds_barrier2();          // E(i), We(i + 1) visible; everyone is done with E(i - 1) and with the pair before
+            lds_barrier();          // E(i), We(i + 1) visible; everyone is done with E(i - 1) and with the pair before
             if (i + 2 < nchunk) dma_we(i + 2, 0);
             if (i > 0) dma_wp(i >> 1);
             depthwise(i, 0, a0);
             expand(i + 1, 1);
             dma_wait();
-            lds_barrier2();          // E(i + 1), We(i + 2), Wp(pair) visible
+            lds_barrier();          // E(i + 1), We(i + 2), Wp(pair) visible
             if (i + 3 < nchunk) dma_we(i + 3, 1);
             depthwise(i + 1, 1, a1);
             project(a0, a1);

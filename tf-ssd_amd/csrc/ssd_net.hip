@@ -371,7 +371,7 @@ static FusedBlockParams fused_shape(const ssd_net& net, const Layer& f, int B) {
     p.we3 = reinterpret_cast<const short*>(f.fz_we3);        // band kernel's plane layout (blocks 1-6) ...
     p.wp3 = reinterpret_cast<const short*>(f.fz_wp3);
     p.bf16 = net.precision;
-    p.form2 = net.image_v2 ? 1 : 0;          // second forms: whole-image kernel (ssd_imgblock2.hip), LDS-DMA weight staging of the split row-band kernel
+    p.form2 = net.image_v2 ? 1 : 0;          // whole-image kernel only: its second form (ssd_imgblock2.hip); the row-band kernels do not read it
     return p;
 }
 
@@ -1611,7 +1611,7 @@ static const OptionSpec kOptions[] = {
     {"overlap_heads", &ssd_net::overlap_heads, nullptr, 0, 1, 0},
     {"use_wino", &ssd_net::use_wino, nullptr, 0, 1, 2},         // Winograd F(2x2,3x3) candidates in the autotune (default 1)
     // whole-image kernel: second form (default 1) / first form (0); equal within tolerance (another k-slot order inside the
-    // project MFMAs).  The band kernels' LDS-DMA weight staging it also selects is bitwise equal
+    // project MFMAs).  Blocks 1-6 on the row-band kernels are not touched by it
     {"image_v2", &ssd_net::image_v2, nullptr, 0, 1, 0},
     {"conv_dma", &ssd_net::conv_dma, nullptr, 0, 1, 1},         // LDS-DMA conv tiles over pre-split activation planes (default 1)
     {"plane_only", &ssd_net::plane_only, nullptr, 0, 1, 0},     // no fp32 copy of an activation whose readers all take its planes (default 1)
