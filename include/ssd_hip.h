@@ -399,6 +399,66 @@ int ssd_jpeg_pack(const short* coef_dev, size_t coef_bytes, const unsigned char*
                   unsigned char* out_dev, size_t out_bytes, int* offsets_dev, int* status_dev, void* workspace_dev,
                   size_t workspace_bytes, void* stream);
 
+/* PNG ENCODER (ssd_png_encode): uint8 RGB images of a ragged batch, on the device, -> their finished PNG files, back to
+ * back in out_dev: file b is out_dev[offsets_dev[b] : offsets_dev[b + 1]] (int32 [B + 1], offsets[0] = 0).  PNG is
+ * lossless, so the contract is not another encoder's bytes: every decoder returns the input pixels, the stream is strictly
+ * valid, and ssd_png_encode_host -- plain C++ from the same step functions (csrc/ssd_png_common.h) -- writes the same bytes.
+ * A file is the 8-byte signature, IHDR (W, H, depth 8, colour type 2, compression 0, filter 0, interlace 0), one IDAT chunk
+ * per segment, IEND; no ancillary chunks.
+ *   filtered   F is H rows of 1 + 3 W bytes: the filter type, then the filtered bytes (bpp 3, zeros above row 0).  filter
+ *              0..4 forces None / Sub / Up / Average / Paeth on every row; 5 (adaptive) takes per row the type whose
+ *              filtered bytes have the least sum of min(v, 256 - v), ties to the lowest type.  Paeth: a on pa <= pb &&
+ *              pa <= pc, else b on pb <= pc, else c.
+ *   segments   F is cut every SSD_PNG_SEGMENT_BYTES bytes, whatever the rows; seg_start is the running sum over the batch
+ *              of ssd_png_segments, row_start that of H: the kernels index ONE space of segments (and of rows).
+ *   tokens     inside a segment a maximal run of n equal bytes is one literal, then the other n - 1 bytes in pieces of
+ *              min(258, rest): a piece of 3 or more is a match of that length at distance 1, a piece of 1 or 2 that many
+ *              literals.  Runs begin anew at a segment's first byte.
+ *   block      one deflate block per segment: dynamic Huffman, or stored where that is not longer in whole bytes (ties go
+ *              to stored).  A dynamic block that is not the image's last is followed by an empty stored block (000, zeros
+ *              to the byte, 00 00 FF FF), which counts in the comparison, so every segment begins and ends on a byte; the
+ *              image's last block has BFINAL and is padded with zeros.  HLIT = 29, HDIST = 0, HCLEN = 15 always.  Literal /
+ *              length code: Huffman over the symbols that occur and 256, lengths <= 15.  Distance code: code 0 with length
+ *              1.  Code-length code: lengths <= 7 over the sequence of the 286 + 1 lengths, in which a run of z zeros is
+ *              symbol 18 (up to 138) while 11 or more are left, then 17 for 3..10, single zeros for 1..2; symbol 16 is not
+ *              used.  Huffman: the two lightest of (weight, leaves before internal nodes, sorted by (weight, symbol));
+ *              where the depth exceeds the limit, the counts per length are shortened as ITU-T T.81 K.3 does and handed
+ *              out longest first to the rarest symbols (Kraft sum exactly 1; lengths that fit are left as they are).
+ *   framing    the first segment's chunk data begins 78 9C, the last one's ends with the big-endian Adler-32 of F; every
+ *              chunk carries the CRC-32 of its type and data.
+ * One call, four launches whatever B and the sizes (filter, segment, scan, scatter), asynchronous on `stream`; no workgroup
+ * waits on another, the prefix sums are a launch of their own, bits are ORed into zeroed words and histograms are integer
+ * LDS atomics, so the bytes do not depend on scheduling.  Every RGB image is encodable: there is no per-image status.
+ * ssd_png_segments / ssd_png_encode_bound: the IDAT chunks of an H x W image, and the size no file of it exceeds: signature,
+ *   IHDR and IEND (45), per segment the chunk framing and a stored header (17), the bytes of F, and 6 (78 9C, Adler-32); 0
+ *   for a side outside 1..16384.
+ * Workspace: ssd_png_encode_workspace_bytes(desc_host, B) bytes (F, the finished chunk data per segment, sizes; 0 for an
+ *   unusable batch).
+ * Nothing outside [out_dev, out_dev + out_bytes) is written; the bytes past offsets_dev[B] are left as they were.
+ * SSD_E_INVALID, nothing launched: NULL pointers, workspace_dev not 16-byte aligned, offsets_dev not 4-byte aligned, pixels
+ *   outside rgb_dev, wrong running sums, a workspace that is too small, out_bytes below the sum of ssd_png_encode_bound.
+ * SSD_E_UNSUPPORTED, nothing launched: a side outside 1..16384, B > 65535, a filter outside 0..5, a bound sum above
+ *   2^31 - 1 bytes (byte offsets are int32).  B == 0 is a no-op.
+ * ssd_png_encode_host: one image on the host (no HIP call, no global state, thread-safe), the same bytes; *written = the
+ *   file's size.  SSD_E_INVALID: NULL pointers, out_bytes below the file's size (nothing is written; any size that holds
+ *   the file is enough); SSD_E_UNSUPPORTED as above. */
+#define SSD_PNG_SEGMENT_BYTES 16384
+struct ssd_png_desc {
+    long long src_offset;   /* byte offset of the image's pixels in rgb_dev, any alignment                                */
+    int H, W;
+    int filter;             /* 0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth, 5 adaptive                                       */
+    int seg_start;          /* running sum over the batch of ssd_png_segments                                            */
+    int row_start;          /* running sum over the batch of H                                                           */
+    int reserved;           /* 0                                                                                         */
+};
+int ssd_png_segments(int H, int W);
+size_t ssd_png_encode_bound(int H, int W);
+size_t ssd_png_encode_workspace_bytes(const struct ssd_png_desc* desc_host, int B);
+int ssd_png_encode(const unsigned char* rgb_dev, size_t rgb_bytes, const struct ssd_png_desc* desc_host,
+                   const struct ssd_png_desc* desc_dev, int B, unsigned char* out_dev, size_t out_bytes, int* offsets_dev,
+                   void* workspace_dev, size_t workspace_bytes, void* stream);
+int ssd_png_encode_host(const unsigned char* rgb, int H, int W, int filter, unsigned char* out, size_t out_bytes, size_t* written);
+
 /* DEVICE ENTROPY DECODER (ssd_jpeg_scan_plan, ssd_jpeg_unpack): the Huffman decoding of ssd_jpeg_entropy_decode on the
  * device, for a ragged batch, bit for bit.  A Huffman stream is bit-granular, but JPEG's self-synchronises: a decoder
  * started at a wrong bit falls into step with the true one after a few dozen codes.  Each SEGMENT of a scan (one restart

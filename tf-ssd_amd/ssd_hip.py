@@ -126,6 +126,12 @@ _SIGNATURES = {
     "ssd_jpeg_pack_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int]),
     "ssd_jpeg_pack": (ctypes.c_int, [vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp, ctypes.c_int, vp, ctypes.c_size_t, vp, vp, vp,
                                       ctypes.c_size_t, vp]),
+    "ssd_png_segments": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    "ssd_png_encode_bound": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "ssd_png_encode_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int]),
+    "ssd_png_encode": (ctypes.c_int, [vp, ctypes.c_size_t, vp, vp, ctypes.c_int, vp, ctypes.c_size_t, vp, vp, ctypes.c_size_t, vp]),
+    "ssd_png_encode_host": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t,
+                                            ctypes.POINTER(ctypes.c_size_t)]),
     "ssd_jpeg_scan_plan": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(JpegInfo), ctypes.POINTER(JpegScanPlan), vp, ctypes.c_size_t]),
     "ssd_jpeg_entropy_decode_subseq": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(JpegInfo), vp, ctypes.c_size_t, ctypes.c_int]),
     "ssd_jpeg_unpack_slots": (ctypes.c_int, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int]),
@@ -238,6 +244,10 @@ JPEG_HEADER_BYTES = 623         # SSD_JPEG_HEADER_BYTES: what ssd_jpeg_encode_he
 JPEG_PACK_DESC_DTYPE = np.dtype([("coef_offset", "<i8"), ("header_offset", "<i8")] + [
     (n, "<i4") for n in ("H", "W", "h_samp", "v_samp", "block_start", "reserved")])         # struct ssd_jpeg_pack_desc
 assert JPEG_PACK_DESC_DTYPE.itemsize == 40
+PNG_DESC_DTYPE = np.dtype([("src_offset", "<i8")] + [(n, "<i4") for n in ("H", "W", "filter", "seg_start", "row_start", "reserved")])
+assert PNG_DESC_DTYPE.itemsize == 32                                                        # struct ssd_png_desc
+PNG_SEGMENT_BYTES = 16384       # SSD_PNG_SEGMENT_BYTES: the filtered stream is cut into IDAT chunks of this many bytes
+PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
 JPEG_UNPACK_SUBSEQ_BITS = 1024  # SSD_JPEG_UNPACK_SUBSEQ_BITS: what subseq_bits = 0 means
 JPEG_HUFF_BYTES = 6 * ctypes.sizeof(JpegHuff)                                              # one image's six tables
 JPEG_SEGMENT_DTYPE = np.dtype([("first_byte", "<u4"), ("bytes", "<u4"), ("first_mcu", "<i4"), ("reserved", "<i4")])   # struct ssd_jpeg_segment

@@ -1073,6 +1073,127 @@ def encode_jpeg_batch(images, quality=75, subsampling="4:2:0", workers=None):
     return list(_encode_pool(workers).map(lambda a: jpeg_host_encode(*a), jobs))
 
 
+# --- PNG output: the files themselves are made on the GPU (ssd_png_encode; include/ssd_hip.h "PNG ENCODER") -----------------------------
+# PNG is lossless, so the bytes are not Pillow's (zlib's matcher is a serial heuristic): every decoder returns the input
+# pixels, and ``ssd_png_encode_host`` writes the same bytes on the host.
+
+def png_gpu_enabled():
+    """Whether ``drawing_utils`` writes ``out_format="png"`` through ``encode_png_batch``: only with ``SSD_PNG_GPU=1``.
+    Opt-in: unset or anything else is Pillow's ``save`` on downloaded pixels (DESIGN.md section 7 has the measurement)."""
+    import os
+    return os.environ.get("SSD_PNG_GPU", "0") == "1"
+
+
+def _png_filters(filter, B):
+    import ssd_hip as _h
+    out = []
+    for f in _per_image(filter, B, "filter"):
+        if f not in _h.PNG_FILTERS:
+            raise ValueError("filter must be one of %s, got %r" % (sorted(_h.PNG_FILTERS), f))
+        out.append(_h.PNG_FILTERS[f])
+    return out
+
+
+def _png_layout(shapes, filters):
+    """Where one ``ssd_png_encode`` call's input and output sit: the descriptors are the ONE upload (pixels stay where they
+    are: ``src_offset`` counts the images one after the other), ``seg_start`` / ``row_start`` the running sums of the IDAT
+    chunks (one per 16384 bytes of ``H * (1 + 3W)``) and of the rows; ``out_bytes`` the sum of the images'
+    ``ssd_png_encode_bound``."""
+    import ssd_hip as _h
+    B = len(shapes)
+    desc = np.zeros(B, _h.PNG_DESC_DTYPE)
+    src = segs = rows = bound = 0
+    for b, ((H, W), f) in enumerate(zip(shapes, filters)):
+        d = desc[b]
+        d["src_offset"], d["H"], d["W"], d["filter"], d["seg_start"], d["row_start"] = src, H, W, f, segs, rows
+        n = -(-(H * (1 + 3 * W)) // _h.PNG_SEGMENT_BYTES)
+        src += H * W * 3
+        segs += n
+        rows += H
+        bound += 45 + 17 * n + H * (1 + 3 * W) + 6
+    return {"desc": desc, "total": _round16(desc.nbytes), "out_bytes": bound, "segments": segs}
+
+
+def png_pack_batch(rgb, shapes, filter="adaptive"):
+    """``ssd_png_encode`` on packed device pixels: ``rgb`` a contiguous uint8 device tensor holding the images one after
+    the other, ``shapes`` [(H, W)], ``filter`` one of "none" | "sub" | "up" | "average" | "paeth" | "adaptive" or one per
+    image (integers 0..5 are passed through to the library).  ONE descriptor upload, one call (four launches), no
+    synchronisation.  Returns device tensors ``(out, offsets)``: file b is ``out[offsets[b]:offsets[b + 1]]`` (int32
+    ``[B + 1]``).  ``SsdHipUnsupported`` for a batch outside the kernel's limits."""
+    import torch
+    import ssd_hip as _h
+    dev = _h.device()
+    lib = _h.lib()
+    B = len(shapes)
+    offsets = torch.empty(B + 1, dtype=torch.int32, device=dev)
+    if B == 0:
+        _h.check(lib.ssd_png_encode(None, 0, None, None, 0, None, 0, None, None, 0, _h.stream()), "png_pack_batch")
+        return torch.empty(0, dtype=torch.uint8, device=dev), offsets.zero_()
+    filters = [f if isinstance(f, (int, np.integer)) else _png_filters(f, 1)[0] for f in _per_image(filter, B, "filter")]
+    layout = _png_layout(shapes, filters)
+    desc = layout["desc"]
+    packed = _upload_packed(dev, layout["total"], lambda host: _put(host, 0, desc))
+    if layout["out_bytes"] > 2 ** 31 - 1:
+        raise _h.SsdHipUnsupported("png_pack_batch: the files may need more than 2^31 - 1 bytes")
+    out = torch.empty(layout["out_bytes"], dtype=torch.uint8, device=dev)
+    ws = _h.workspace(max(int(lib.ssd_png_encode_workspace_bytes(desc.ctypes.data, B)), 16))
+    _h.check(lib.ssd_png_encode(_h.ptr(rgb), rgb.numel(), desc.ctypes.data, packed.data_ptr(), B, _h.ptr(out), out.numel(),
+                                _h.ptr(offsets), _h.ptr(ws), ws.numel(), _h.stream()), "png_pack_batch")
+    return out, offsets
+
+
+def _pillow_png(pixels):
+    import io
+    from PIL import Image
+    buf = io.BytesIO()
+    Image.fromarray(pixels).save(buf, "PNG")
+    return buf.getvalue()
+
+
+def encode_png_batch(images, filter="adaptive"):
+    """Device uint8 images -> their PNG files' ``bytes``, made on the GPU.  ``images``: a device uint8 ``[B,H,W,3]`` tensor
+    (what ``drawing_utils`` draws) or a list of device ``[H,W,3]`` tensors of any sizes; ``filter`` ("none", "sub", "up",
+    "average", "paeth", "adaptive") may be one value or one per image.  Per batch: ONE descriptor upload, ONE
+    ``ssd_png_encode`` call, the download of the offsets, then ONE download of the files into pinned memory, which the
+    calling thread slices into ``bytes``.  A batch outside the kernel's limits (``SsdHipUnsupported``) is downloaded as
+    pixels and encoded by Pillow."""
+    import torch
+    import ssd_hip as _h
+    dev = _h.device()
+    if isinstance(images, torch.Tensor):
+        if images.dim() != 4:
+            raise ValueError("images must be uint8 [B,H,W,3] or a list of [H,W,3], got %s" % (tuple(images.shape),))
+        seq = list(images)
+    else:
+        seq = list(images)
+    for t in seq:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.device != dev:
+            raise ValueError("images must be device uint8 [H,W,3] tensors")
+    B = len(seq)
+    filters = _png_filters(filter, B)
+    if B == 0:
+        png_pack_batch(None, [])
+        return []
+    shapes = [(int(t.shape[0]), int(t.shape[1])) for t in seq]
+    if isinstance(images, torch.Tensor) and images.is_contiguous():
+        rgb = images.reshape(-1)
+    else:
+        rgb = torch.cat([t.reshape(-1) for t in seq])
+    try:
+        out, offsets = png_pack_batch(rgb, shapes, filters)
+    except _h.SsdHipUnsupported:
+        host = rgb.cpu().numpy()
+        ends = np.cumsum([h * w * 3 for h, w in shapes])
+        return [_pillow_png(host[e - h * w * 3:e].reshape(h, w, 3)) for e, (h, w) in zip(ends, shapes)]
+    offsets = offsets.cpu().numpy()
+    n = int(offsets[B])
+    st = _pinned_staging("download", dev, n)[0]
+    st[:n].copy_(out[:n], non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    host = st.numpy()
+    return [host[offsets[b]:offsets[b + 1]].tobytes() for b in range(B)]
+
+
 def data_workers(workers=None):
     """Size of the decoding pool: ``workers``, else ``SSD_DATA_WORKERS``, else 8; always within 1..16 (never the
     machine's CPU count: the pool shares the host with the training loop and with other jobs)."""

@@ -323,7 +323,8 @@ def draw_grid_map(img, grid_map, stride, out=None, out_dir=None, show=False, out
 
 
 def _present(images_u8, out_dir, start, show, out_format="png", out_quality=75):
-    """``out_dir``: ``img_%05d.png`` from index ``start`` on, through PIL; with ``out_format="jpeg"``, ``img_%05d.jpg`` at
+    """``out_dir``: ``img_%05d.png`` from index ``start`` on, through PIL (with ``SSD_PNG_GPU=1``: encoded on the GPU from
+    the device tensor by ``data_utils.encode_png_batch`` -- other bytes, the same pixels); with ``out_format="jpeg"``, ``img_%05d.jpg`` at
     quality ``out_quality`` through ``data_utils.encode_jpeg_batch`` -- the drawn tensor is already on the device, so the
     whole batch is one forward-DCT call and the files are Pillow's ``save(f, "JPEG", quality=out_quality)`` bytes.
     ``show``: the reference's matplotlib figures."""
@@ -340,6 +341,16 @@ def _present(images_u8, out_dir, start, show, out_format="png", out_quality=75):
                 f.write(blob)
         if not show:
             return
+    if out_dir is not None and out_format == "png":
+        from utils import data_utils
+        if data_utils.png_gpu_enabled():                                               # opt-in (SSD_PNG_GPU=1): the files are made on the GPU
+            os.makedirs(out_dir, exist_ok=True)
+            for i, blob in enumerate(data_utils.encode_png_batch(images_u8.detach().contiguous())):
+                with open(os.path.join(out_dir, "img_%05d.png" % (start + i)), "wb") as f:
+                    f.write(blob)
+            if not show:
+                return
+            out_dir = None
     host = images_u8.detach().cpu().numpy()
     if out_dir is not None and out_format == "png":
         from PIL import Image
