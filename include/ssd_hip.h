@@ -459,6 +459,68 @@ int ssd_png_encode(const unsigned char* rgb_dev, size_t rgb_bytes, const struct 
                    void* workspace_dev, size_t workspace_bytes, void* stream);
 int ssd_png_encode_host(const unsigned char* rgb, int H, int W, int filter, unsigned char* out, size_t out_bytes, size_t* written);
 
+/* PNG DECODER (ssd_png_parse, ssd_png_idat, ssd_png_decode): PNG files -> uint8 RGB pixels on the device, behind a host
+ * inflate.  The contract is Pillow's: for every file ssd_png_parse accepts, whose zlib stream inflates to exactly
+ * H * (1 + row_bytes) bytes and whose filter bytes are 0..4, the pixels equal PIL.Image.open(f).convert("RGB") bit for bit.
+ * The format (colour type, depths -> RGB):
+ *   2 RGB           8       the samples            |  16     the HIGH byte of each sample
+ *   6 RGBA          8, 16   as RGB, alpha dropped
+ *   0 grey          8       replicated to three channels  |  1, 2, 4   sample x 255, x 85, x 17, replicated
+ *   4 grey + alpha  8, 16   (the high byte of) grey replicated, alpha dropped
+ *   3 palette       1, 2, 4, 8   PLTE[index]; an index past the end of a short PLTE gives (0, 0, 0)
+ * Ancillary chunks (tRNS, gAMA, text, ...) change nothing.  Refused, for the caller's other decoder: grey at 16 bits, Adam7
+ * interlace, a side above 16384, animated files, unknown critical chunks, PLTE in a grey image (SSD_E_UNSUPPORTED); a bad
+ * signature, chunk order, chunk length or CRC, a file that ends early, a missing PLTE for type 3, IDAT chunks that are not
+ * consecutive, a missing IEND (SSD_E_INVALID).
+ * HOST HALF.  Plain C++: no HIP call, no global state, thread-safe.
+ *   ssd_png_parse walks the chunks, verifies every CRC and fills ssd_png_info: row_bytes = ceil(W * channels * depth / 8),
+ *     filter_distance = max(1, channels * depth / 8), stream_bytes = H * (1 + row_bytes) (what inflate must return), the
+ *     palette zero-padded to 256 entries, and where the zlib stream lies: idat_count consecutive IDAT chunks from byte
+ *     first_idat of the file on, idat_bytes of payload in all.
+ *   ssd_png_idat copies that payload, joined, to `out` (out_bytes >= idat_bytes).  Inflating it is the caller's business
+ *     (zlib is no dependency of this library), and so is refusing a stream of another length or a filter byte above 4.
+ *   ssd_png_decode_host: one image's inflated stream -> H * W * 3 bytes, the same arithmetic as the device in plain loops.
+ *     SSD_E_INVALID: NULL pointers, filtered_bytes other than stream_bytes, a filter byte above 4, rgb_bytes too small.
+ * DEVICE.  ssd_png_decode: one call per ragged batch, two launches whatever the batch (un-filter: Sub / Up / Average / Paeth
+ * modulo 256, one wavefront per chain of dependent rows; convert: the table above), asynchronous on `stream`.  packed_dev
+ * holds, each part at a multiple of 16 bytes, per image its filtered scanlines (src_offset; the images in ascending order,
+ * not overlapping), for colour type 3 its 768-byte palette (palette_offset) and its chain list (chain_offset: int32 rows,
+ * ascending, at which a chain begins: row 0 and every row whose filter byte is 0 or 1; rows outside 0..H are clamped, so a
+ * wrong list gives wrong pixels, never an access outside the image).  Image b's H * W * 3 bytes go to rgb_dev + dst_offset (a
+ * multiple of 16, ascending, not overlapping: the src_offset of the ssd_image_desc that ssd_preprocess_ragged and
+ * ssd_resize_lanczos take); nothing else in rgb_dev is written.  chain_start / row_start / raw_offset: running sums over the
+ * batch of chains, H and round16(H * row_bytes).  Workspace: ssd_png_decode_workspace_bytes(desc_host, B) (the unfiltered
+ * rows; 0 for an unusable batch).
+ * SSD_E_INVALID, nothing launched: NULL pointers, packed_dev / rgb_dev / workspace_dev not 16-byte aligned, a side below 1, a
+ *   (colour type, depth) outside the table, offsets that are misaligned, outside their buffer or overlapping, chains outside
+ *   1..H, wrong running sums, a workspace that is too small.  SSD_E_UNSUPPORTED, nothing launched: a side above 16384,
+ *   B > 65535.  B == 0 is a no-op. */
+struct ssd_png_info {
+    int width, height, depth, color_type, channels, filter_distance, palette_entries, idat_count;
+    long long row_bytes, stream_bytes, idat_bytes, first_idat;
+    unsigned char palette[768];
+};
+struct ssd_png_dec_desc {
+    long long src_offset;       /* the filtered scanlines in packed_dev: H rows of 1 + row_bytes bytes                  */
+    long long palette_offset;   /* 768 bytes in packed_dev (colour type 3 only)                                          */
+    long long chain_offset;     /* int32 [chains] in packed_dev                                                          */
+    long long dst_offset;       /* the image's H * W * 3 bytes in rgb_dev                                                */
+    long long raw_offset;       /* running sum over the batch of round16(H * row_bytes): its place in the workspace      */
+    int H, W, depth, color_type;
+    int chains;                 /* 1..H                                                                                  */
+    int chain_start;            /* running sum over the batch of chains                                                  */
+    int row_start;              /* running sum over the batch of H                                                       */
+    int reserved;               /* 0                                                                                     */
+};
+int ssd_png_parse(const unsigned char* data, size_t n, struct ssd_png_info* out);
+int ssd_png_idat(const unsigned char* data, size_t n, const struct ssd_png_info* info, unsigned char* out, size_t out_bytes);
+int ssd_png_decode_host(const struct ssd_png_info* info, const unsigned char* filtered, size_t filtered_bytes, unsigned char* rgb,
+                        size_t rgb_bytes);
+size_t ssd_png_decode_workspace_bytes(const struct ssd_png_dec_desc* desc_host, int B);
+int ssd_png_decode(const unsigned char* packed_dev, size_t packed_bytes, const struct ssd_png_dec_desc* desc_host,
+                   const struct ssd_png_dec_desc* desc_dev, int B, unsigned char* rgb_dev, size_t rgb_bytes, void* workspace_dev,
+                   size_t workspace_bytes, void* stream);
+
 /* DEVICE ENTROPY DECODER (ssd_jpeg_scan_plan, ssd_jpeg_unpack): the Huffman decoding of ssd_jpeg_entropy_decode on the
  * device, for a ragged batch, bit for bit.  A Huffman stream is bit-granular, but JPEG's self-synchronises: a decoder
  * started at a wrong bit falls into step with the true one after a few dozen codes.  Each SEGMENT of a scan (one restart

@@ -538,4 +538,51 @@ SSD_PNG_HD void png_iend(unsigned char* at) {
     for (int i = 0; i < 12; ++i) at[i] = iend[i];
 }
 
+// ---- the decoder (ssd_png_dec.hip): the format contract of include/ssd_hip.h, "PNG DECODER" ----------------------------
+// the inverse of png_filter, for any filter distance: x is the filtered byte, a / b / c the raw bytes to the left, above and
+// above-left (0 outside the image)
+SSD_PNG_HD unsigned png_unfilter(const int type, const int x, const int a, const int b, const int c) {
+    const int pred = type == 0 ? 0 : (type == 1 ? a : (type == 2 ? b : (type == 3 ? (a + b) >> 1 : png_paeth(a, b, c))));
+    return (unsigned)(x + pred) & 255u;
+}
+SSD_PNG_HD int png_channels(const int color_type) { return color_type == 2 ? 3 : (color_type == 6 ? 4 : (color_type == 4 ? 2 : 1)); }
+// the (colour type, depth) pairs the decoder takes: every pair of the PNG specification but grey at 16 bits
+SSD_PNG_HD bool png_format_ok(const int color_type, const int depth) {
+    if (color_type == 0 || color_type == 3) return depth == 1 || depth == 2 || depth == 4 || depth == 8;
+    if (color_type == 2 || color_type == 4 || color_type == 6) return depth == 8 || depth == 16;
+    return false;
+}
+SSD_PNG_HD long long png_row_bytes(const int W, const int color_type, const int depth) {
+    return ((long long)W * png_channels(color_type) * depth + 7) >> 3;
+}
+SSD_PNG_HD int png_filter_distance(const int color_type, const int depth) {
+    const int v = png_channels(color_type) * depth / 8;
+    return v < 1 ? 1 : v;
+}
+// pixel x of an unfiltered row -> R, G, B: sub-byte samples unpacked (grey scaled to 0..255), the palette looked up (768
+// bytes, zeros behind the file's entries), grey replicated, alpha dropped, the high byte of a 16-bit sample
+SSD_PNG_HD void png_pixel_rgb(const unsigned char* row, const int x, const int color_type, const int depth, const unsigned char* palette,
+                              unsigned char* rgb) {
+    if (depth < 8) {
+        const int bit = x * depth;
+        const int s = (row[bit >> 3] >> (8 - depth - (bit & 7))) & ((1 << depth) - 1);
+        if (color_type == 3) {
+            rgb[0] = palette[3 * s]; rgb[1] = palette[3 * s + 1]; rgb[2] = palette[3 * s + 2];
+        } else {
+            rgb[0] = rgb[1] = rgb[2] = (unsigned char)(s * (255 / ((1 << depth) - 1)));
+        }
+        return;
+    }
+    const int step = depth >> 3;
+    const unsigned char* p = row + (long long)x * png_channels(color_type) * step;
+    if (color_type == 3) {
+        const int s = p[0];
+        rgb[0] = palette[3 * s]; rgb[1] = palette[3 * s + 1]; rgb[2] = palette[3 * s + 2];
+    } else if (color_type == 2 || color_type == 6) {
+        rgb[0] = p[0]; rgb[1] = p[step]; rgb[2] = p[2 * step];
+    } else {
+        rgb[0] = rgb[1] = rgb[2] = p[0];
+    }
+}
+
 }  // namespace ssd

@@ -81,6 +81,14 @@ class JpegScanPlan(ctypes.Structure):
                 ("reserved", ctypes.c_int), ("huff", JpegHuff * 6)]
 
 
+class PngInfo(ctypes.Structure):
+    """struct ssd_png_info (include/ssd_hip.h): what ``ssd_png_parse`` fills in for one PNG file."""
+    _fields_ = [(n, ctypes.c_int) for n in ("width", "height", "depth", "color_type", "channels", "filter_distance",
+                                            "palette_entries", "idat_count")] + [
+        (n, ctypes.c_longlong) for n in ("row_bytes", "stream_bytes", "idat_bytes", "first_idat")] + [
+        ("palette", ctypes.c_ubyte * 768)]
+
+
 JPEG_COEFFICIENTS, JPEG_RAW = 0, 1
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
 MOBILENET_V2, VGG16 = 0, 1
@@ -132,6 +140,11 @@ _SIGNATURES = {
     "ssd_png_encode": (ctypes.c_int, [vp, ctypes.c_size_t, vp, vp, ctypes.c_int, vp, ctypes.c_size_t, vp, vp, ctypes.c_size_t, vp]),
     "ssd_png_encode_host": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t,
                                             ctypes.POINTER(ctypes.c_size_t)]),
+    "ssd_png_parse": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(PngInfo)]),
+    "ssd_png_idat": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(PngInfo), vp, ctypes.c_size_t]),
+    "ssd_png_decode_host": (ctypes.c_int, [ctypes.POINTER(PngInfo), vp, ctypes.c_size_t, vp, ctypes.c_size_t]),
+    "ssd_png_decode_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int]),
+    "ssd_png_decode": (ctypes.c_int, [vp, ctypes.c_size_t, vp, vp, ctypes.c_int, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]),
     "ssd_jpeg_scan_plan": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(JpegInfo), ctypes.POINTER(JpegScanPlan), vp, ctypes.c_size_t]),
     "ssd_jpeg_entropy_decode_subseq": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(JpegInfo), vp, ctypes.c_size_t, ctypes.c_int]),
     "ssd_jpeg_unpack_slots": (ctypes.c_int, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int]),
@@ -248,6 +261,11 @@ PNG_DESC_DTYPE = np.dtype([("src_offset", "<i8")] + [(n, "<i4") for n in ("H", "
 assert PNG_DESC_DTYPE.itemsize == 32                                                        # struct ssd_png_desc
 PNG_SEGMENT_BYTES = 16384       # SSD_PNG_SEGMENT_BYTES: the filtered stream is cut into IDAT chunks of this many bytes
 PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
+PNG_DEC_DESC_DTYPE = np.dtype([(n, "<i8") for n in ("src_offset", "palette_offset", "chain_offset", "dst_offset", "raw_offset")] + [
+    (n, "<i4") for n in ("H", "W", "depth", "color_type", "chains", "chain_start", "row_start", "reserved")])   # struct ssd_png_dec_desc
+assert PNG_DEC_DESC_DTYPE.itemsize == 72 and ctypes.sizeof(PngInfo) == 832
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+PNG_SCANLINES = 2               # ``kinds`` of a decoded batch, beside JPEG_COEFFICIENTS and JPEG_RAW (raw pixels of any origin)
 JPEG_UNPACK_SUBSEQ_BITS = 1024  # SSD_JPEG_UNPACK_SUBSEQ_BITS: what subseq_bits = 0 means
 JPEG_HUFF_BYTES = 6 * ctypes.sizeof(JpegHuff)                                              # one image's six tables
 JPEG_SEGMENT_DTYPE = np.dtype([("first_byte", "<u4"), ("bytes", "<u4"), ("first_mcu", "<i4"), ("reserved", "<i4")])   # struct ssd_jpeg_segment

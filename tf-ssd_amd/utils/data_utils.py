@@ -1194,6 +1194,275 @@ def encode_png_batch(images, filter="adaptive"):
     return [host[offsets[b]:offsets[b + 1]].tobytes() for b in range(B)]
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# PNG files decoded on the GPU behind a host inflate (include/ssd_hip.h, "PNG DECODER").  The host
+# walks the chunks and verifies the CRCs (``ssd_png_parse``: plain C++, the GIL is released around it) and inflates the
+# zlib stream (Python's ``zlib``, which releases the GIL too); un-filtering the scanlines and converting the samples to
+# packed RGB run on the device (``ssd_png_decode``), Pillow's pixels exactly, and the pixels never exist in host memory.
+
+def png_decode_gpu_enabled():
+    """Whether the custom-image generators decode PNG files this way: only with ``SSD_PNG_DECODE_GPU=1``.  Opt-in
+    (DESIGN.md section 7 has the measurement); the pixels are the same either way."""
+    import os
+    return os.environ.get("SSD_PNG_DECODE_GPU", "0") == "1"
+
+
+class PngScanlines(object):
+    """One PNG file after the host half: ``info`` (``ssd_hip.PngInfo``) and ``filtered`` (uint8, what inflate returned:
+    ``height`` rows of one filter byte and ``row_bytes`` filtered bytes)."""
+    __slots__ = ("info", "filtered")
+
+    def __init__(self, info, filtered):
+        self.info, self.filtered = info, filtered
+
+
+def _png_parse(blob):
+    """``ssd_hip.PngInfo`` of a file the library decodes, else None (no PNG at all, unsupported or malformed: Pillow's
+    business)."""
+    import ctypes
+    import ssd_hip as _h
+    if blob[:8] != _h.PNG_SIGNATURE:
+        return None
+    info = _h.PngInfo()
+    rc = _h.lib().ssd_png_parse(blob, len(blob), ctypes.byref(info))
+    return info if rc == 0 else None
+
+
+def _png_inflate(blob, info):
+    """The file's filtered scanlines (uint8), or None: a zlib error, a stream that does not end where the image does
+    (never more than one byte beyond the image is decompressed), bytes behind the stream's end, a filter byte above 4,
+    or more pixels than Pillow opens without a warning."""
+    import ctypes
+    import zlib
+    import ssd_hip as _h
+    from PIL import Image
+    if Image.MAX_IMAGE_PIXELS is not None and info.width * info.height > Image.MAX_IMAGE_PIXELS:
+        return None
+    stream = np.empty(int(info.idat_bytes), np.uint8)
+    if _h.lib().ssd_png_idat(blob, len(blob), ctypes.byref(info), stream.ctypes.data, stream.nbytes) != 0:
+        return None
+    expected = int(info.stream_bytes)
+    z = zlib.decompressobj()
+    try:
+        data = z.decompress(stream, expected + 1)
+    except zlib.error:
+        return None
+    if len(data) != expected or not z.eof or z.unused_data or z.unconsumed_tail:
+        return None
+    filtered = np.frombuffer(data, np.uint8)
+    if int(filtered[::1 + int(info.row_bytes)].max()) > 4:
+        return None
+    return filtered
+
+
+def png_host_inflate(blob, fallback=_pillow_rgb):
+    """The host half for one file's bytes, for a worker thread: ``PngScanlines``, or -- a file the library calls
+    unsupported or invalid, a stream inflate refuses, or no PNG at all -- ``fallback(blob)``'s uint8 ``[H,W,3]`` pixels."""
+    blob = bytes(blob)
+    info = _png_parse(blob)
+    filtered = _png_inflate(blob, info) if info is not None else None
+    return PngScanlines(info, filtered) if filtered is not None else fallback(blob)
+
+
+def _png_items(blobs, fallback):
+    """Every entry as ``PngScanlines`` or a uint8 ``[H,W,3]`` array (raw pixels)."""
+    items = []
+    for x in blobs:
+        if isinstance(x, (bytes, bytearray, memoryview)):
+            x = png_host_inflate(x, fallback)
+        if not isinstance(x, PngScanlines):
+            x = np.asarray(x)
+            if x.dtype != np.uint8 or x.ndim != 3 or x.shape[2] != 3:
+                raise ValueError("raw images must be uint8 [H,W,3], got %s %s" % (x.dtype, tuple(x.shape)))
+        items.append(x)
+    return items
+
+
+def _png_decode_layout(items):
+    """Where one ``ssd_png_decode`` call's input sits in ONE buffer: descriptors | output descriptors | 768-byte palettes |
+    chain lists | per image its filtered scanlines, each part at a multiple of 16 bytes; and where the output images go.
+    A raw image travels as 8-bit RGB scanlines with filter byte 0: every row a chain of its own."""
+    import ssd_hip as _h
+    B = len(items)
+    desc = np.zeros(B, _h.PNG_DEC_DESC_DTYPE)
+    out_desc = np.zeros(B, _h.IMAGE_DESC_DTYPE)
+    chains, kinds, streams = [], [], []
+    for b, x in enumerate(items):
+        d = desc[b]
+        if isinstance(x, PngScanlines):
+            i = x.info
+            d["H"], d["W"], d["depth"], d["color_type"] = i.height, i.width, i.depth, i.color_type
+            types = x.filtered[::1 + int(i.row_bytes)]
+            starts = np.flatnonzero(types <= 1).astype(np.int32)
+            chains.append(starts if len(starts) and starts[0] == 0 else np.concatenate([np.zeros(1, np.int32), starts]))
+            kinds.append(_h.PNG_SCANLINES)
+            streams.append(int(i.stream_bytes))
+        else:
+            d["H"], d["W"], d["depth"], d["color_type"] = x.shape[0], x.shape[1], 8, 2
+            chains.append(np.arange(x.shape[0], dtype=np.int32))
+            kinds.append(_h.JPEG_RAW)
+            streams.append(x.shape[0] * (1 + 3 * x.shape[1]))
+    palettes = [b for b, x in enumerate(items) if isinstance(x, PngScanlines) and x.info.color_type == 3]
+    starts, total = _place([desc.nbytes, out_desc.nbytes] + [768] * len(palettes) + [4 * len(c) for c in chains] + streams)
+    out_at = starts[1]
+    for b, at in zip(palettes, starts[2:]):
+        desc[b]["palette_offset"] = at
+    desc["chain_offset"] = starts[2 + len(palettes):2 + len(palettes) + B]
+    desc["src_offset"] = starts[2 + len(palettes) + B:]
+    rgb_bytes = raw = n_chains = rows = 0
+    for b in range(B):
+        d = desc[b]
+        H, W = int(d["H"]), int(d["W"])
+        d["chains"], d["chain_start"], d["row_start"], d["raw_offset"], d["dst_offset"] = len(chains[b]), n_chains, rows, raw, rgb_bytes
+        out_desc[b]["H"], out_desc[b]["W"], out_desc[b]["src_offset"] = H, W, rgb_bytes
+        n_chains += len(chains[b])
+        rows += H
+        raw += _round16(streams[b] - H)
+        rgb_bytes += _round16(H * W * 3)
+    return {"desc": desc, "out_desc": out_desc, "out_at": out_at, "total": total, "rgb_bytes": rgb_bytes, "raw_bytes": raw,
+            "chains": chains, "kinds": kinds}
+
+
+def _png_decode_fill(host, items, layout):
+    import ssd_hip as _h
+    desc, palette = layout["desc"], _h.PngInfo.palette
+    _put(host, 0, desc)
+    _put(host, layout["out_at"], layout["out_desc"])
+    for b, x in enumerate(items):
+        d = desc[b]
+        _put(host, int(d["chain_offset"]), layout["chains"][b])
+        at = int(d["src_offset"])
+        if isinstance(x, PngScanlines):
+            if x.info.color_type == 3:
+                _put(host, int(d["palette_offset"]), np.frombuffer(x.info, np.uint8)[palette.offset:palette.offset + palette.size])
+            _put(host, at, x.filtered)
+        else:
+            H, n = x.shape[0], 3 * x.shape[1]
+            rows = host[at:at + H * (1 + n)].reshape(H, 1 + n)
+            rows[:, 0] = 0
+            rows[:, 1:] = x.reshape(H, n)
+
+
+def _check_out_u8(out_u8, nbytes, dev):
+    """``out_u8`` of the decode functions: a contiguous 1-D uint8 device tensor, 16-byte aligned and long enough."""
+    import torch
+    if (not isinstance(out_u8, torch.Tensor) or out_u8.dtype != torch.uint8 or out_u8.device != dev or out_u8.dim() != 1
+            or not out_u8.is_contiguous() or out_u8.numel() < nbytes or out_u8.data_ptr() % 16):
+        raise ValueError("out_u8 must be a contiguous 1-D uint8 device tensor of at least %d bytes, 16-byte aligned" % nbytes)
+    return out_u8
+
+
+def decode_png_batch(blobs, out_u8=None, fallback=_pillow_rgb):
+    """A list of PNG files' ``bytes`` -> their pixels on the GPU, bitwise ``PIL.Image.open(...).convert("RGB")``'s, as a
+    ``JpegBatch`` (the same object ``decode_jpeg_batch`` returns).  Per batch: parse and inflate on the host, ONE upload
+    of the filtered scanlines, ONE ``ssd_png_decode`` call (two launches).  A file the library refuses (16-bit grey,
+    interlaced, malformed, ...) is decoded by ``fallback`` -- Pillow, exactly as before, raising what it raised before --
+    and travels as raw pixels in the same upload; entries may also be ``PngScanlines`` from ``png_host_inflate`` (the
+    data pool's threads) or uint8 ``[H,W,3]`` arrays.  ``kinds``: per image ``ssd_hip.PNG_SCANLINES`` or
+    ``ssd_hip.JPEG_RAW``.  ``out_u8`` as ``decode_jpeg_batch``'s; nothing outside the images is written."""
+    import torch
+    import ssd_hip as _h
+    dev = _h.device()
+    lib = _h.lib()
+    items = _png_items(blobs, fallback)
+    B = len(items)
+    if B == 0:
+        _h.check(lib.ssd_png_decode(None, 0, None, None, 0, None, 0, None, 0, _h.stream()), "decode_png_batch")
+        return JpegBatch([], torch.empty(0, dtype=torch.uint8, device=dev), np.zeros(0, _h.IMAGE_DESC_DTYPE), 0, None, [])
+    layout = _png_decode_layout(items)
+    packed = _upload_packed(dev, layout["total"], lambda host: _png_decode_fill(host, items, layout))
+    if out_u8 is None or out_u8 is False:
+        rgb = torch.empty(max(layout["rgb_bytes"], 16), dtype=torch.uint8, device=dev)
+    else:
+        rgb = _check_out_u8(out_u8, layout["rgb_bytes"], dev)
+    desc, out_desc = layout["desc"], layout["out_desc"]
+    assert layout["raw_bytes"] == lib.ssd_png_decode_workspace_bytes(desc.ctypes.data, B)
+    ws = _h.workspace(max(layout["raw_bytes"], 16))
+    base = packed.data_ptr()
+    _h.check(lib.ssd_png_decode(base, layout["total"], desc.ctypes.data, base, B, _h.ptr(rgb), rgb.numel(), _h.ptr(ws), ws.numel(),
+                                _h.stream()), "decode_png_batch")
+    images = [rgb[int(o["src_offset"]):int(o["src_offset"]) + int(o["H"]) * int(o["W"]) * 3].view(int(o["H"]), int(o["W"]), 3)
+              for o in out_desc]
+    return JpegBatch(images, rgb, out_desc, base + layout["out_at"], packed, layout["kinds"])
+
+
+def _is_png(x):
+    import ssd_hip as _h
+    return isinstance(x, PngScanlines) or (isinstance(x, (bytes, bytearray, memoryview)) and bytes(x[:8]) == _h.PNG_SIGNATURE)
+
+
+def decode_image_batch(blobs, out_u8=None, fallback=_pillow_rgb):
+    """A mixed list -- JPEG files' bytes, PNG files' bytes, host-half items of either codec (``JpegCoefficients``,
+    ``PngScanlines``), uint8 ``[H,W,3]`` arrays -- -> ONE packed ``rgb`` buffer and ONE descriptor array in the list's
+    order, as a ``JpegBatch``.  The JPEG and raw entries go through ``decode_jpeg_batch`` into the front of the buffer, the
+    PNG entries through ``decode_png_batch`` (``ssd_png_decode``) into the rest; a list without PNG entries calls nothing
+    of the PNG road.  ``kinds``: per image ``JPEG_COEFFICIENTS``, ``JPEG_RAW`` or ``PNG_SCANLINES``."""
+    import torch
+    import ssd_hip as _h
+    dev = _h.device()
+    blobs = list(blobs)
+    png = [b for b, x in enumerate(blobs) if _is_png(x)]
+    if not png:
+        return decode_jpeg_batch(blobs, out_u8=out_u8, fallback=fallback)
+    taken = set(png)
+    rest = [b for b in range(len(blobs)) if b not in taken]
+    png_items = _png_items([blobs[b] for b in png], fallback)
+    rest_items = _jpeg_items([blobs[b] for b in rest], fallback)
+
+    def size(x):
+        H, W = (x.info.height, x.info.width) if hasattr(x, "info") else x.shape[:2]
+        return _round16(int(H) * int(W) * 3)
+    front = sum(size(x) for x in rest_items)
+    total = front + sum(size(x) for x in png_items)
+    rgb = torch.empty(max(total, 16), dtype=torch.uint8, device=dev) if out_u8 is None or out_u8 is False else _check_out_u8(out_u8, total, dev)
+    parts = [(png, decode_png_batch(png_items, out_u8=rgb[front:], fallback=fallback), front)]
+    if rest:
+        parts.append((rest, decode_jpeg_batch(rest_items, out_u8=rgb[:max(front, 16)], fallback=fallback), 0))
+    desc = np.zeros(len(blobs), _h.IMAGE_DESC_DTYPE)
+    kinds = [0] * len(blobs)
+    for where, batch, at in parts:
+        for b, o, k in zip(where, batch.desc, batch.kinds):
+            desc[b]["H"], desc[b]["W"], desc[b]["src_offset"] = o["H"], o["W"], int(o["src_offset"]) + at
+            kinds[b] = k
+    desc_dev = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
+    images = [rgb[int(o["src_offset"]):int(o["src_offset"]) + int(o["H"]) * int(o["W"]) * 3].view(int(o["H"]), int(o["W"]), 3)
+              for o in desc]
+    return JpegBatch(images, rgb, desc, desc_dev.data_ptr(), (desc_dev, [p[1].packed for p in parts]), kinds)
+
+
+def preprocess_image_batch(blobs, final_height, final_width, out=None, fallback=_pillow_rgb):
+    """``preprocess_jpeg_batch`` for a mixed list (``decode_image_batch``): bitwise ``preprocess_ragged_batch([Pillow's
+    decode of each], ...)``."""
+    import torch
+    import ssd_hip as _h
+    fh, fw = int(final_height), int(final_width)
+    B = len(blobs)
+    out = _check_out(out, (B, fh, fw, 3), torch.float32, _h.device(), create=True)
+    jb = decode_image_batch(blobs, fallback=fallback)
+    _h.check(_h.lib().ssd_preprocess_ragged(_h.ptr(jb.rgb), jb.rgb.numel(), jb.desc.ctypes.data, jb.desc_ptr, B, 3, fh, fw,
+                                            _h.ptr(out), _h.stream()), "preprocess_image_batch")
+    return out
+
+
+def resize_lanczos_image_batch(blobs, final_height, final_width, out=None, out_u8=None, fallback=_pillow_rgb):
+    """``resize_lanczos_jpeg_batch`` for a mixed list (``decode_image_batch``): bitwise ``resize_lanczos_batch([Pillow's
+    decode of each], ...)``."""
+    import torch
+    import ssd_hip as _h
+    fh, fw = int(final_height), int(final_width)
+    dev = _h.device()
+    B = len(blobs)
+    out = _check_out(out, (B, fh, fw, 3), torch.float32, dev, create=True)
+    _check_out(out_u8, (B, fh, fw, 3), torch.uint8, dev, "out_u8")
+    if _lanczos_nothing_to_pack(B, 3, fh, fw, out, out_u8, "resize_lanczos_image_batch"):
+        return out
+    jb = decode_image_batch(blobs, fallback=fallback)
+    layout = _lanczos_layout([(int(o["H"]), int(o["W"])) for o in jb.desc], fh, fw, src_offsets=jb.desc["src_offset"])
+    packed = _upload_packed(dev, layout["total"], lambda host: _lanczos_fill(host, [], layout))
+    _lanczos_launch(packed, layout, out, out_u8, src=jb.rgb, what="resize_lanczos_image_batch")
+    return out
+
+
 def data_workers(workers=None):
     """Size of the decoding pool: ``workers``, else ``SSD_DATA_WORKERS``, else 8; always within 1..16 (never the
     machine's CPU count: the pool shares the host with the training loop and with other jobs)."""
@@ -1308,8 +1577,27 @@ def _encoded_custom_image(img_path):
     return _decode_custom_image(img_path)
 
 
-def _custom_images_resized(img_paths, final_height, final_width):
-    """The files as one resized batch: JPEG files decoded on the GPU unless ``SSD_JPEG_GPU=0``, the rest by PIL."""
+def _custom_image_item(img_path):
+    """With ``SSD_PNG_DECODE_GPU=1``, for a worker thread: the file after its host half -- a PNG parsed and inflated
+    (``png_host_inflate``), a JPEG entropy-decoded or planned unless ``SSD_JPEG_GPU=0`` -- or, for ``*.npy`` and every other
+    format, its pixels as before."""
+    if not img_path.endswith(".npy"):
+        import ssd_hip as _h
+        with open(img_path, "rb") as f:
+            blob = f.read()
+        if blob[:8] == _h.PNG_SIGNATURE:
+            return png_host_inflate(blob)
+        if blob[:2] == _JPEG_SOI and jpeg_gpu_enabled():
+            return (jpeg_host_plan if jpeg_entropy_decode_gpu_enabled() else jpeg_host_decode)(blob)
+    return _decode_custom_image(img_path)
+
+
+def _custom_images_resized(img_paths, final_height, final_width, pool=None):
+    """The files as one resized batch: JPEG files decoded on the GPU unless ``SSD_JPEG_GPU=0``, PNG files only with
+    ``SSD_PNG_DECODE_GPU=1`` (their host halves on ``pool``'s threads when there is one), the rest by PIL."""
+    if png_decode_gpu_enabled():
+        items = list(pool.map(_custom_image_item, img_paths)) if pool is not None else [_custom_image_item(p) for p in img_paths]
+        return resize_lanczos_image_batch(items, final_height, final_width)
     if jpeg_gpu_enabled():
         return resize_lanczos_jpeg_batch([_encoded_custom_image(p) for p in img_paths], final_height, final_width)
     return resize_lanczos_batch([_decode_custom_image(p) for p in img_paths], final_height, final_width)
@@ -1331,9 +1619,17 @@ def custom_data_batches(img_paths, final_height, final_width, batch_size):
     ``padded_batch`` makes of the generator's items (no ground truth: one padding row)."""
     pv = get_padding_values()
     img_paths = list(img_paths)
-    for i in range(0, len(img_paths), int(batch_size)):
-        imgs = _custom_images_resized(img_paths[i:i + int(batch_size)], final_height, final_width)
-        yield imgs, np.full((len(imgs), 1, 4), pv[1], np.float32), np.full((len(imgs), 1), pv[2], np.int32)
+    pool = None
+    if png_decode_gpu_enabled():                                                  # the host halves: read, parse, inflate
+        from concurrent.futures import ThreadPoolExecutor
+        pool = ThreadPoolExecutor(max_workers=data_workers(), thread_name_prefix="ssd-data")
+    try:
+        for i in range(0, len(img_paths), int(batch_size)):
+            imgs = _custom_images_resized(img_paths[i:i + int(batch_size)], final_height, final_width, pool)
+            yield imgs, np.full((len(imgs), 1, 4), pv[1], np.float32), np.full((len(imgs), 1), pv[2], np.int32)
+    finally:
+        if pool is not None:
+            pool.shutdown(wait=True, cancel_futures=True)
 
 
 def padded_batch(items, batch_size, padding_values=None):
