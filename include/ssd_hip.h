@@ -521,6 +521,69 @@ int ssd_png_decode(const unsigned char* packed_dev, size_t packed_bytes, const s
                    const struct ssd_png_dec_desc* desc_dev, int B, unsigned char* rgb_dev, size_t rgb_bytes, void* workspace_dev,
                    size_t workspace_bytes, void* stream);
 
+/* PNG INFLATE (ssd_png_inflate, ssd_png_inflate_host): the inflate in front of ssd_png_decode, on the device, for a ragged
+ * batch.  The contract is the host inflater's: STATUS 0 IMPLIES that zlib, asked for one byte more than the image has
+ * (Python: zlib.decompressobj().decompress(s, n + 1)), returns exactly the same n = H * (1 + row_bytes) bytes with the
+ * stream at its end and no input left over, and that every filter byte is 0..4.  Any other status means "ask the host":
+ * the image's bytes are then unspecified (inside its own regions).
+ * The format: a zlib stream (RFC 1950: CM = 8, CINFO <= 7, FCHECK, no FDICT) of stored, fixed-Huffman and dynamic-Huffman
+ * blocks (RFC 1951) in any mix, and its Adler-32.
+ * ssd_png_inflate: one call per batch, two launches whatever the batch, asynchronous on `stream`, no workspace.
+ *   1 inflate  one wavefront per stream.  The decode state is wave-uniform; a dynamic block's code tables are built in LDS
+ *              by the whole wavefront; the 32 KB window is an LDS ring, so a back-reference is an LDS read (never a read of
+ *              global memory this kernel wrote); a match of length L at distance D is copied by the lanes as
+ *              out[p + l] = out[p - D + l % D]; each finished 16 KB half of the ring leaves in 16-byte stores and is folded
+ *              into the Adler-32 in parallel.  status_dev[b] is written (0 or ONE bit below: the first cause met).
+ *   2 chains   one workgroup per image reads the H filter bytes: one above 4 sets SSD_PNG_INFLATE_FILTER (only where kernel 1
+ *              left 0); the rows 0 and those of type 0 or 1 go, ascending, to the first slots of the image's chain list and H
+ *              goes to EVERY REMAINING ONE of its H slots, so an ssd_png_dec_desc with chains = H, the same chain_offset and
+ *              src_offset = dst_offset decodes the image (a padded slot is the empty chain H..H).
+ *   packed_dev holds, per image, each at a multiple of 16 bytes and none overlapping another: the joined IDAT payload
+ *   (zlib_offset, zlib_bytes; read only, and no byte outside it is read), the H * (1 + row_bytes) bytes to write (dst_offset)
+ *   and the int32[H] chain list to write (chain_offset).  Nothing else but status_dev[0..B) is written.
+ * Stricter than zlib (refused here, accepted there; the host road then decides): a distance beyond the window the header
+ *   declares (zlib checks only against the bytes produced); input left behind the Adler-32 (zlib reports it as unused data).
+ * ssd_png_inflate_host: one stream in plain C++ from the same step functions: no HIP call, no global state, thread-safe; the
+ *   same bytes in out[0..out_bytes) and the same status word as the device (filter bit included; out_bytes = H * (1 +
+ *   row_bytes)).  Nothing outside out[0..out_bytes) is written.  SSD_E_INVALID: NULL pointers, row_bytes < 1, out_bytes no
+ *   positive multiple of 1 + row_bytes.
+ * SSD_E_INVALID, nothing launched: NULL pointers, packed_dev not 16-byte aligned, desc_dev not 8-byte or status_dev not
+ *   4-byte aligned, H < 1, row_bytes < 1, zlib_bytes < 0, a region that is misaligned, outside packed_dev or overlapping
+ *   another region of the batch, reserved != 0.  SSD_E_UNSUPPORTED, nothing launched: B > 65535; H * (1 + row_bytes) above
+ *   SSD_PNG_INFLATE_MAX_STREAM.  B == 0 is a no-op.
+ * The cap: one wavefront inflates a stream alone, and it is slow: 3.0 MB of output per second, measured on an MI355X on
+ *   Pillow-written 500x375 photographs, smooth and noise alike (tests/bench_png_inflate.py leg (f): 189 ms for 562 875 bytes;
+ *   DESIGN.md section 7, "PNG inflate on the device").  SSD_PNG_INFLATE_MAX_STREAM = 1 MiB keeps a stream at that rate to
+ *   0.35 s, and leaves a stream of nothing but long codes room to be slower; a larger image is the host road's. */
+#define SSD_PNG_INFLATE_HEADER         0x0001   /* CM, CINFO, FCHECK or FDICT                                             */
+#define SSD_PNG_INFLATE_BLOCK_TYPE     0x0002   /* block type 3                                                           */
+#define SSD_PNG_INFLATE_STORED         0x0004   /* a stored block whose LEN and NLEN disagree                             */
+#define SSD_PNG_INFLATE_SYMBOLS        0x0008   /* HLIT > 286 or HDIST > 30                                               */
+#define SSD_PNG_INFLATE_REPEAT         0x0010   /* a code-length repeat with nothing before it, or running past the lengths */
+#define SSD_PNG_INFLATE_OVERSUBSCRIBED 0x0020   /* an over-subscribed code                                                */
+#define SSD_PNG_INFLATE_INCOMPLETE     0x0040   /* an incomplete code other than one 1-bit code or (distances) none       */
+#define SSD_PNG_INFLATE_NO_END         0x0080   /* no end-of-block code                                                   */
+#define SSD_PNG_INFLATE_SYMBOL         0x0100   /* length symbol 286 / 287, distance symbol 30 / 31, a code no symbol has */
+#define SSD_PNG_INFLATE_DISTANCE       0x0200   /* a distance beyond the bytes produced so far, or beyond the window      */
+#define SSD_PNG_INFLATE_INPUT          0x0400   /* input exhausted                                                        */
+#define SSD_PNG_INFLATE_OUTPUT         0x0800   /* more or fewer bytes than H * (1 + row_bytes)                           */
+#define SSD_PNG_INFLATE_ADLER          0x1000   /* Adler-32 mismatch                                                      */
+#define SSD_PNG_INFLATE_TRAILING       0x2000   /* input bytes behind the trailer                                         */
+#define SSD_PNG_INFLATE_FILTER         0x4000   /* a filter byte above 4                                                  */
+#define SSD_PNG_INFLATE_MAX_STREAM     (1ll << 20)
+struct ssd_png_inflate_desc {
+    long long zlib_offset;      /* the joined IDAT payload in packed_dev                                                 */
+    long long zlib_bytes;
+    long long dst_offset;       /* H * (1 + row_bytes) bytes in packed_dev: the src_offset of the image's ssd_png_dec_desc */
+    long long chain_offset;     /* int32 [H] in packed_dev: the chain_offset of the image's ssd_png_dec_desc (chains = H)  */
+    long long row_bytes;
+    int H;
+    int reserved;               /* 0                                                                                     */
+};
+int ssd_png_inflate(unsigned char* packed_dev, size_t packed_bytes, const struct ssd_png_inflate_desc* desc_host,
+                    const struct ssd_png_inflate_desc* desc_dev, int B, int* status_dev, void* stream);
+int ssd_png_inflate_host(const unsigned char* zlib, size_t n, unsigned char* out, size_t out_bytes, long long row_bytes, int* status);
+
 /* DEVICE ENTROPY DECODER (ssd_jpeg_scan_plan, ssd_jpeg_unpack): the Huffman decoding of ssd_jpeg_entropy_decode on the
  * device, for a ragged batch, bit for bit.  A Huffman stream is bit-granular, but JPEG's self-synchronises: a decoder
  * started at a wrong bit falls into step with the true one after a few dozen codes.  Each SEGMENT of a scan (one restart

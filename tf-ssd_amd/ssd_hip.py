@@ -145,6 +145,8 @@ _SIGNATURES = {
     "ssd_png_decode_host": (ctypes.c_int, [ctypes.POINTER(PngInfo), vp, ctypes.c_size_t, vp, ctypes.c_size_t]),
     "ssd_png_decode_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int]),
     "ssd_png_decode": (ctypes.c_int, [vp, ctypes.c_size_t, vp, vp, ctypes.c_int, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]),
+    "ssd_png_inflate": (ctypes.c_int, [vp, ctypes.c_size_t, vp, vp, ctypes.c_int, vp, vp]),
+    "ssd_png_inflate_host": (ctypes.c_int, [vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_longlong, c_int_p]),
     "ssd_jpeg_scan_plan": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(JpegInfo), ctypes.POINTER(JpegScanPlan), vp, ctypes.c_size_t]),
     "ssd_jpeg_entropy_decode_subseq": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(JpegInfo), vp, ctypes.c_size_t, ctypes.c_int]),
     "ssd_jpeg_unpack_slots": (ctypes.c_int, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int]),
@@ -265,6 +267,14 @@ PNG_DEC_DESC_DTYPE = np.dtype([(n, "<i8") for n in ("src_offset", "palette_offse
     (n, "<i4") for n in ("H", "W", "depth", "color_type", "chains", "chain_start", "row_start", "reserved")])   # struct ssd_png_dec_desc
 assert PNG_DEC_DESC_DTYPE.itemsize == 72 and ctypes.sizeof(PngInfo) == 832
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+PNG_INFLATE_DESC_DTYPE = np.dtype([(n, "<i8") for n in ("zlib_offset", "zlib_bytes", "dst_offset", "chain_offset", "row_bytes")] + [
+    ("H", "<i4"), ("reserved", "<i4")])                                                     # struct ssd_png_inflate_desc
+assert PNG_INFLATE_DESC_DTYPE.itemsize == 48
+PNG_INFLATE_MAX_STREAM = 1 << 20    # SSD_PNG_INFLATE_MAX_STREAM: the longest inflated stream ssd_png_inflate takes
+# SSD_PNG_INFLATE_*: the one bit of status_dev[b] per cause (0: the host inflater's bytes)
+PNG_INFLATE_STATUS = {"header": 0x0001, "block_type": 0x0002, "stored": 0x0004, "symbols": 0x0008, "repeat": 0x0010,
+                      "oversubscribed": 0x0020, "incomplete": 0x0040, "no_end": 0x0080, "symbol": 0x0100, "distance": 0x0200,
+                      "input": 0x0400, "output": 0x0800, "adler": 0x1000, "trailing": 0x2000, "filter": 0x4000}
 PNG_SCANLINES = 2               # ``kinds`` of a decoded batch, beside JPEG_COEFFICIENTS and JPEG_RAW (raw pixels of any origin)
 JPEG_UNPACK_SUBSEQ_BITS = 1024  # SSD_JPEG_UNPACK_SUBSEQ_BITS: what subseq_bits = 0 means
 JPEG_HUFF_BYTES = 6 * ctypes.sizeof(JpegHuff)                                              # one image's six tables

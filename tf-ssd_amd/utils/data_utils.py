@@ -1264,13 +1264,48 @@ def png_host_inflate(blob, fallback=_pillow_rgb):
     return PngScanlines(info, filtered) if filtered is not None else fallback(blob)
 
 
+def png_inflate_gpu_enabled():
+    """Whether PNG files are inflated on the device too (``ssd_png_inflate``): only with ``SSD_PNG_INFLATE_GPU=1``, and in
+    the generators only beside ``SSD_PNG_DECODE_GPU=1``.  Opt-in ("PNG inflate on the device", has
+    the measurement); the pixels are the same either way."""
+    import os
+    return os.environ.get("SSD_PNG_INFLATE_GPU", "0") == "1"
+
+
+class PngStream(object):
+    """One PNG file after parse only: ``info`` (``ssd_hip.PngInfo``) and ``blob``, the file's bytes.  Its zlib stream is
+    inflated on the device (``ssd_png_inflate``); the host never sees a pixel of it."""
+    __slots__ = ("info", "blob")
+
+    def __init__(self, info, blob):
+        self.info, self.blob = info, blob
+
+
+def png_host_parse(blob, fallback=_pillow_rgb):
+    """The host half for one file's bytes when inflate runs on the device, for a worker thread: parse and CRCs only.
+    ``PngStream``; for a file the library calls unsupported or invalid, no PNG at all, or more pixels than Pillow opens
+    without a warning, ``fallback(blob)``'s uint8 ``[H,W,3]`` pixels; for a stream longer than ``ssd_png_inflate`` takes
+    (``ssd_hip.PNG_INFLATE_MAX_STREAM``), what ``png_host_inflate`` returns."""
+    import ssd_hip as _h
+    from PIL import Image
+    blob = bytes(blob)
+    info = _png_parse(blob)
+    if info is None or (Image.MAX_IMAGE_PIXELS is not None and info.width * info.height > Image.MAX_IMAGE_PIXELS):
+        return fallback(blob)
+    if info.stream_bytes > _h.PNG_INFLATE_MAX_STREAM:
+        return png_host_inflate(blob, fallback)
+    return PngStream(info, blob)
+
+
 def _png_items(blobs, fallback):
-    """Every entry as ``PngScanlines`` or a uint8 ``[H,W,3]`` array (raw pixels)."""
+    """Every entry as ``PngScanlines``, ``PngStream`` (files' bytes only with ``SSD_PNG_INFLATE_GPU=1``) or a uint8
+    ``[H,W,3]`` array (raw pixels)."""
     items = []
+    host_half = png_host_parse if png_inflate_gpu_enabled() else png_host_inflate
     for x in blobs:
         if isinstance(x, (bytes, bytearray, memoryview)):
-            x = png_host_inflate(x, fallback)
-        if not isinstance(x, PngScanlines):
+            x = host_half(x, fallback)
+        if not isinstance(x, (PngScanlines, PngStream)):
             x = np.asarray(x)
             if x.dtype != np.uint8 or x.ndim != 3 or x.shape[2] != 3:
                 raise ValueError("raw images must be uint8 [H,W,3], got %s %s" % (x.dtype, tuple(x.shape)))
@@ -1343,6 +1378,98 @@ def _png_decode_fill(host, items, layout):
             rows[:, 1:] = x.reshape(H, n)
 
 
+def _png_stream_layout(items):
+    """``_png_decode_layout`` for a batch with at least one ``PngStream``.  The UPLOAD holds descriptors | output
+    descriptors | inflate descriptors | 768-byte palettes | the host-built chain lists and scanlines of ``PngScanlines`` and
+    raw entries | per ``PngStream`` its joined IDAT payload.  BEHIND the upload, device memory only: per ``PngStream`` the
+    scanlines ``ssd_png_inflate`` writes and its H-slot chain list.  ``ssd_png_decode`` wants its images' scanlines in
+    ascending order, so its descriptors run over the host-built entries first and the streams after them (``order``); the
+    output descriptors stay in the list's order."""
+    import ssd_hip as _h
+    B = len(items)
+    order = [b for b, x in enumerate(items) if not isinstance(x, PngStream)] + [b for b, x in enumerate(items) if isinstance(x, PngStream)]
+    n_host = sum(1 for x in items if not isinstance(x, PngStream))
+    desc = np.zeros(B, _h.PNG_DEC_DESC_DTYPE)
+    out_desc = np.zeros(B, _h.IMAGE_DESC_DTYPE)
+    inflate = np.zeros(B - n_host, _h.PNG_INFLATE_DESC_DTYPE)
+    chains, kinds, streams = {}, [0] * B, []
+    for k, b in enumerate(order):
+        x, d = items[b], desc[k]
+        if isinstance(x, np.ndarray):
+            d["H"], d["W"], d["depth"], d["color_type"] = x.shape[0], x.shape[1], 8, 2
+            chains[k] = np.arange(x.shape[0], dtype=np.int32)
+            kinds[b] = _h.JPEG_RAW
+            streams.append(x.shape[0] * (1 + 3 * x.shape[1]))
+            continue
+        i = x.info
+        d["H"], d["W"], d["depth"], d["color_type"] = i.height, i.width, i.depth, i.color_type
+        kinds[b] = _h.PNG_SCANLINES
+        streams.append(int(i.stream_bytes))
+        if isinstance(x, PngScanlines):
+            starts = np.flatnonzero(x.filtered[::1 + int(i.row_bytes)] <= 1).astype(np.int32)
+            chains[k] = starts if len(starts) and starts[0] == 0 else np.concatenate([np.zeros(1, np.int32), starts])
+    palettes = [k for k, b in enumerate(order) if not isinstance(items[b], np.ndarray) and items[b].info.color_type == 3]
+    heights = [int(desc[k]["H"]) for k in range(B)]
+    upload = ([desc.nbytes, out_desc.nbytes, inflate.nbytes] + [768] * len(palettes) + [4 * len(chains[k]) for k in range(n_host)]
+              + streams[:n_host] + [int(items[b].info.idat_bytes) for b in order[n_host:]])
+    starts, total = _place(upload)
+    behind, device_total = _place(streams[n_host:] + [4 * heights[k] for k in range(n_host, B)], total)
+    out_at, inflate_at = starts[1], starts[2]
+    at = 3
+    for k, where in zip(palettes, starts[at:]):
+        desc[k]["palette_offset"] = where
+    at += len(palettes)
+    desc["chain_offset"] = starts[at:at + n_host] + behind[B - n_host:]
+    desc["src_offset"] = starts[at + n_host:at + 2 * n_host] + behind[:B - n_host]
+    inflate["zlib_offset"] = starts[at + 2 * n_host:]
+    rgb_bytes = raw = n_chains = rows = 0
+    for k, b in enumerate(order):
+        d = desc[k]
+        H, W = int(d["H"]), int(d["W"])
+        d["chains"] = len(chains[k]) if k < n_host else H
+        d["chain_start"], d["row_start"], d["raw_offset"], d["dst_offset"] = n_chains, rows, raw, rgb_bytes
+        out_desc[b]["H"], out_desc[b]["W"], out_desc[b]["src_offset"] = H, W, rgb_bytes
+        if k >= n_host:
+            f, i = inflate[k - n_host], items[b].info
+            f["zlib_bytes"], f["dst_offset"], f["chain_offset"], f["row_bytes"], f["H"] = i.idat_bytes, d["src_offset"], d["chain_offset"], i.row_bytes, H
+        n_chains += int(d["chains"])
+        rows += H
+        raw += _round16(streams[k] - H)
+        rgb_bytes += _round16(H * W * 3)
+    return {"desc": desc, "out_desc": out_desc, "out_at": out_at, "inflate": inflate, "inflate_at": inflate_at, "total": total,
+            "device_total": device_total, "rgb_bytes": rgb_bytes, "raw_bytes": raw, "chains": chains, "kinds": kinds, "order": order,
+            "n_host": n_host}
+
+
+def _png_stream_fill(host, items, layout):
+    """The upload of ``_png_stream_layout``: ``ssd_png_idat`` writes each ``PngStream``'s payload straight into the staging
+    buffer."""
+    import ctypes
+    import ssd_hip as _h
+    desc, inflate, palette, n_host = layout["desc"], layout["inflate"], _h.PngInfo.palette, layout["n_host"]
+    _put(host, 0, desc)
+    _put(host, layout["out_at"], layout["out_desc"])
+    _put(host, layout["inflate_at"], inflate)
+    for k, b in enumerate(layout["order"]):
+        x, d = items[b], desc[k]
+        if not isinstance(x, np.ndarray) and x.info.color_type == 3:
+            _put(host, int(d["palette_offset"]), np.frombuffer(x.info, np.uint8)[palette.offset:palette.offset + palette.size])
+        if k >= n_host:
+            f = inflate[k - n_host]
+            rc = _h.lib().ssd_png_idat(x.blob, len(x.blob), ctypes.byref(x.info), host.ctypes.data + int(f["zlib_offset"]), int(f["zlib_bytes"]))
+            _h.check(rc, "ssd_png_idat")
+            continue
+        _put(host, int(d["chain_offset"]), layout["chains"][k])
+        at = int(d["src_offset"])
+        if isinstance(x, PngScanlines):
+            _put(host, at, x.filtered)
+        else:
+            H, n = x.shape[0], 3 * x.shape[1]
+            rows = host[at:at + H * (1 + n)].reshape(H, 1 + n)
+            rows[:, 0] = 0
+            rows[:, 1:] = x.reshape(H, n)
+
+
 def _check_out_u8(out_u8, nbytes, dev):
     """``out_u8`` of the decode functions: a contiguous 1-D uint8 device tensor, 16-byte aligned and long enough."""
     import torch
@@ -1359,7 +1486,12 @@ def decode_png_batch(blobs, out_u8=None, fallback=_pillow_rgb):
     interlaced, malformed, ...) is decoded by ``fallback`` -- Pillow, exactly as before, raising what it raised before --
     and travels as raw pixels in the same upload; entries may also be ``PngScanlines`` from ``png_host_inflate`` (the
     data pool's threads) or uint8 ``[H,W,3]`` arrays.  ``kinds``: per image ``ssd_hip.PNG_SCANLINES`` or
-    ``ssd_hip.JPEG_RAW``.  ``out_u8`` as ``decode_jpeg_batch``'s; nothing outside the images is written."""
+    ``ssd_hip.JPEG_RAW``.  ``out_u8`` as ``decode_jpeg_batch``'s; nothing outside the images is written.
+    With ``SSD_PNG_INFLATE_GPU=1`` the files' bytes become ``PngStream`` entries (``png_host_parse``; such entries are taken
+    either way): the upload carries their IDAT payloads instead of scanlines, ``ssd_png_inflate`` writes the scanlines and
+    the chain lists behind the upload, ``ssd_png_decode`` follows, then ONE small read of the status words.  If any is
+    nonzero, every ``PngStream`` of the batch goes through ``png_host_inflate`` (a bad stream ends at ``fallback``, raising
+    what it raised before) and the batch runs again on the host-inflate road; ``kinds`` stays ``PNG_SCANLINES``."""
     import torch
     import ssd_hip as _h
     dev = _h.device()
@@ -1369,8 +1501,13 @@ def decode_png_batch(blobs, out_u8=None, fallback=_pillow_rgb):
     if B == 0:
         _h.check(lib.ssd_png_decode(None, 0, None, None, 0, None, 0, None, 0, _h.stream()), "decode_png_batch")
         return JpegBatch([], torch.empty(0, dtype=torch.uint8, device=dev), np.zeros(0, _h.IMAGE_DESC_DTYPE), 0, None, [])
-    layout = _png_decode_layout(items)
-    packed = _upload_packed(dev, layout["total"], lambda host: _png_decode_fill(host, items, layout))
+    on_device = any(isinstance(x, PngStream) for x in items)
+    if on_device:
+        layout = _png_stream_layout(items)
+        packed = _upload_packed(dev, layout["total"], lambda host: _png_stream_fill(host, items, layout), device_total=layout["device_total"])
+    else:
+        layout = _png_decode_layout(items)
+        packed = _upload_packed(dev, layout["total"], lambda host: _png_decode_fill(host, items, layout))
     if out_u8 is None or out_u8 is False:
         rgb = torch.empty(max(layout["rgb_bytes"], 16), dtype=torch.uint8, device=dev)
     else:
@@ -1379,8 +1516,16 @@ def decode_png_batch(blobs, out_u8=None, fallback=_pillow_rgb):
     assert layout["raw_bytes"] == lib.ssd_png_decode_workspace_bytes(desc.ctypes.data, B)
     ws = _h.workspace(max(layout["raw_bytes"], 16))
     base = packed.data_ptr()
-    _h.check(lib.ssd_png_decode(base, layout["total"], desc.ctypes.data, base, B, _h.ptr(rgb), rgb.numel(), _h.ptr(ws), ws.numel(),
+    if on_device:
+        inflate = layout["inflate"]
+        status = torch.empty(len(inflate), dtype=torch.int32, device=dev)
+        _h.check(lib.ssd_png_inflate(base, packed.numel(), inflate.ctypes.data, base + layout["inflate_at"], len(inflate), _h.ptr(status),
+                                     _h.stream()), "decode_png_batch")
+    _h.check(lib.ssd_png_decode(base, packed.numel(), desc.ctypes.data, base, B, _h.ptr(rgb), rgb.numel(), _h.ptr(ws), ws.numel(),
                                 _h.stream()), "decode_png_batch")
+    if on_device and bool(status.cpu().any()):                                    # ONE small read; the host road decides, for every stream
+        redone = [png_host_inflate(x.blob, fallback) if isinstance(x, PngStream) else x for x in items]
+        return decode_png_batch(redone, out_u8=out_u8, fallback=fallback)
     images = [rgb[int(o["src_offset"]):int(o["src_offset"]) + int(o["H"]) * int(o["W"]) * 3].view(int(o["H"]), int(o["W"]), 3)
               for o in out_desc]
     return JpegBatch(images, rgb, out_desc, base + layout["out_at"], packed, layout["kinds"])
@@ -1388,7 +1533,7 @@ def decode_png_batch(blobs, out_u8=None, fallback=_pillow_rgb):
 
 def _is_png(x):
     import ssd_hip as _h
-    return isinstance(x, PngScanlines) or (isinstance(x, (bytes, bytearray, memoryview)) and bytes(x[:8]) == _h.PNG_SIGNATURE)
+    return isinstance(x, (PngScanlines, PngStream)) or (isinstance(x, (bytes, bytearray, memoryview)) and bytes(x[:8]) == _h.PNG_SIGNATURE)
 
 
 def decode_image_batch(blobs, out_u8=None, fallback=_pillow_rgb):
@@ -1579,14 +1724,14 @@ def _encoded_custom_image(img_path):
 
 def _custom_image_item(img_path):
     """With ``SSD_PNG_DECODE_GPU=1``, for a worker thread: the file after its host half -- a PNG parsed and inflated
-    (``png_host_inflate``), a JPEG entropy-decoded or planned unless ``SSD_JPEG_GPU=0`` -- or, for ``*.npy`` and every other
+    (``png_host_inflate``) or, with ``SSD_PNG_INFLATE_GPU=1`` too, parsed only (``png_host_parse``), a JPEG entropy-decoded or planned unless ``SSD_JPEG_GPU=0`` -- or, for ``*.npy`` and every other
     format, its pixels as before."""
     if not img_path.endswith(".npy"):
         import ssd_hip as _h
         with open(img_path, "rb") as f:
             blob = f.read()
         if blob[:8] == _h.PNG_SIGNATURE:
-            return png_host_inflate(blob)
+            return (png_host_parse if png_inflate_gpu_enabled() else png_host_inflate)(blob)
         if blob[:2] == _JPEG_SOI and jpeg_gpu_enabled():
             return (jpeg_host_plan if jpeg_entropy_decode_gpu_enabled() else jpeg_host_decode)(blob)
     return _decode_custom_image(img_path)
@@ -1594,7 +1739,8 @@ def _custom_image_item(img_path):
 
 def _custom_images_resized(img_paths, final_height, final_width, pool=None):
     """The files as one resized batch: JPEG files decoded on the GPU unless ``SSD_JPEG_GPU=0``, PNG files only with
-    ``SSD_PNG_DECODE_GPU=1`` (their host halves on ``pool``'s threads when there is one), the rest by PIL."""
+    ``SSD_PNG_DECODE_GPU=1`` (their host halves on ``pool``'s threads when there is one; with ``SSD_PNG_INFLATE_GPU=1`` as
+    well that half is parse and CRCs only and inflate runs on the device), the rest by PIL."""
     if png_decode_gpu_enabled():
         items = list(pool.map(_custom_image_item, img_paths)) if pool is not None else [_custom_image_item(p) for p in img_paths]
         return resize_lanczos_image_batch(items, final_height, final_width)
@@ -1616,11 +1762,12 @@ def custom_data_generator(img_paths, final_height, final_width):
 def custom_data_batches(img_paths, final_height, final_width, batch_size):
     """``custom_data_generator`` + ``padded_batch`` with one upload and one resize call per batch: yields ``(imgs
     [b,final_height,final_width,3] device tensor, gt_boxes [b,1,4] zeros, gt_labels [b,1] of -1)``, what
-    ``padded_batch`` makes of the generator's items (no ground truth: one padding row)."""
+    ``padded_batch`` makes of the generator's items (no ground truth: one padding row).  With ``SSD_PNG_DECODE_GPU=1`` the
+    files' host halves run on ``data_workers()`` threads; ``SSD_PNG_INFLATE_GPU=1`` beside it moves inflate to the device."""
     pv = get_padding_values()
     img_paths = list(img_paths)
     pool = None
-    if png_decode_gpu_enabled():                                                  # the host halves: read, parse, inflate
+    if png_decode_gpu_enabled():                                                  # the host halves: read, parse, inflate (or not)
         from concurrent.futures import ThreadPoolExecutor
         pool = ThreadPoolExecutor(max_workers=data_workers(), thread_name_prefix="ssd-data")
     try:
