@@ -1058,6 +1058,36 @@ int ssd_net_train_matrix_flops(const ssd_net* net, double* out3);
  * the `loss` and `val_loss` that fit() logs and ModelCheckpoint(save_best_only) monitors (trainer.py:56-63).
  * Synchronous (legacy stream, one float copied to the host). */
 int ssd_net_regularization_loss(ssd_net* net, float* host_out);
+/* Fine-tuning: Keras' `layer.trainable = False`, by KERAS LAYER NAME -- a parameter name up to its last '/':
+ * "Conv1", "bn_Conv1", "block_3_depthwise_BN", "extra2_1", "4_conv_boxes_output", "l2_normalization".  A conv and its
+ * BatchNorm are two Keras layers and freeze independently, as do the label and the box conv of one head level.  By
+ * default every layer is trainable and the step is the one it always was (same launches, same bits).  Both calls work
+ * before and after ssd_net_train_begin, need no device, and take effect at the next ssd_net_train_forward_backward /
+ * ssd_net_adam_step.  Unknown name: SSD_E_INVALID (get: too).
+ *   frozen kernel / bias / L2-norm scale: no gradient is computed, its range of grads_flat holds exactly 0.0f after
+ *     ssd_net_train_forward_backward (the flat vector keeps its size, order and offsets; so do the gradient buckets);
+ *   frozen BatchNorm: TF 2.0 semantics -- inference mode.  It normalises with moving_mean / moving_variance (eps 1e-3),
+ *     makes no statistics pass, leaves the moving statistics bitwise alone and produces no dgamma / dbeta;
+ *   pruning: a tensor needs a gradient only if a trainable parameter lies upstream of it; no data gradient and no
+ *     residual add go into a tensor that needs none, a layer without trainable parameters whose inputs need none is
+ *     left out of the backward altogether (ssd_net_train_plan);
+ *   ssd_net_adam_step leaves var, m and v of frozen ranges bitwise untouched (still one launch); the step counter stays
+ *     global.  Unlike Keras -- which rebuilds the optimizer at the compile() that must follow a change of `trainable` --
+ *     the moments of a layer that is unfrozen later continue from where they were.
+ * ssd_net_regularization_loss is unchanged: Keras keeps the regularisation term of frozen kernels in `loss`. */
+int ssd_net_set_trainable(ssd_net* net, const char* keras_layer, int trainable);
+int ssd_net_get_trainable(const ssd_net* net, const char* keras_layer);   /* 1 / 0, SSD_E_INVALID: unknown name */
+/* The backward plan of layer `layer` (index of ssd_net_layer_name) under the current flags, from the graph and the
+ * flags alone (no device, no ssd_net_train_begin): *flags = OR of SSD_PLAN_*.  0 for a layer the training step does not
+ * run (the fused-block and softmax entries of the layer list). */
+#define SSD_PLAN_WGRAD 1       /* gradient of the kernel (+ bias) / of the L2-norm scale                          */
+#define SSD_PLAN_WGRAD2 2      /* head conv: gradient of the box kernel (+ bias); SSD_PLAN_WGRAD is the label one   */
+#define SSD_PLAN_DGRAD 4       /* data gradient into the layer's input                                             */
+#define SSD_PLAN_RESGRAD 8     /* the output gradient is handed to the residual tensor                             */
+#define SSD_PLAN_BN_BATCH 16   /* BatchNorm on batch statistics (moving averages updated)                          */
+#define SSD_PLAN_BN_PARAMS 32  /* dgamma / dbeta                                                                   */
+#define SSD_PLAN_SKIP 64       /* nothing trainable, no input needs a gradient: not in the backward at all         */
+int ssd_net_train_plan(const ssd_net* net, int layer, int* flags);
 /* Debug / parity hook: copy a buffer of the last training forward/backward (batch B) to the host:
  * "probs", "deltas", "grad_logits", "grad_deltas", "<tensor>", "grad:<tensor>", "pre:<layer>",
  * "mean:<layer>", "var:<layer>".  Returns the element count (host_out NULL: query). */

@@ -2,6 +2,7 @@
 // parameter table, activation tensors, layer list and the net object behind `ssd_net*`.
 #pragma once
 #include <map>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -198,6 +199,10 @@ struct ssd_net {
     float* splitk_layers = nullptr;     // per-layer split-K slabs (post-autotune)
     bool timing = false;                // optional per-layer hipEvent timing of forward()/predict() (bench.py roofline leg)
     ssd_train_state* train = nullptr;    // training step state (csrc/ssd_train.hip), lazily created
+    // fine-tuning: Keras layer names (a parameter name up to its last '/') whose `trainable` is False; trainable_rev counts
+    // the changes (the training step re-plans its backward when it lags behind: ssd_net_set_trainable, csrc/ssd_train.hip)
+    std::set<std::string> frozen;
+    unsigned trainable_rev = 0;
     std::vector<std::vector<hipEvent_t>> timing_events;   // one vector of (layers + 2) events per forward
 
     ~ssd_net() {

@@ -90,6 +90,49 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ 
         dz[e] = dout[e] * act_mask(out[e], act);
 }
 
+// Backward through a FROZEN BatchNorm (Keras trainable = False: it normalises with the moving statistics, which are
+// constants of the step): bn_bwd_apply_kernel's formula without the two batch-mean terms,
+//   dy = gamma * istd_moving * dout * act'(z) = dout * act'(out) * scale[c],   scale = gamma / sqrt(moving_var + eps)
+// (the folded scale of the forward).  The pass-mask comes from the stored OUTPUT: act(z) lies strictly inside the linear
+// range exactly where z does; a layer with a residual add has no activation (the host checks), so `out` is then not read.
+// Bandwidth-bound: 16-byte accesses (C % 4 == 0, 16-byte aligned tensors), the scalar form for anything else.
+__global__ __launch_bounds__(256) void bn_frozen_bwd4_kernel(const f32x4* __restrict__ dout, const f32x4* __restrict__ out,
+                                                            const f32x4* __restrict__ scale, const long total4, const int C4,
+                                                            const int act, f32x4* __restrict__ dy) {
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total4; e += (long)gridDim.x * 256) {
+        f32x4 g = dout[e] * scale[(int)(e % C4)];
+        if (act) {
+            const f32x4 o = out[e];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) g[j] *= act_mask(o[j], act);
+        }
+        dy[e] = g;
+    }
+}
+__global__ __launch_bounds__(256) void bn_frozen_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ out,
+                                                           const float* __restrict__ scale, const long total, const int C,
+                                                           const int act, float* __restrict__ dy) {
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256)
+        dy[e] = dout[e] * scale[(int)(e % C)] * (act ? act_mask(out[e], act) : 1.f);
+}
+
+// Every frozen BatchNorm of the net folded into its per-channel scale / shift as ONE launch (blockIdx.y = job), the
+// arithmetic of fold_bn_kernel (csrc/ssd_ops.hip): the conv epilogue of the training forward then writes
+// act(scale * conv + shift) (+ residual) directly
+struct FoldJob {
+    const float *gamma, *beta, *mean, *var;
+    float *scale, *shift;
+    int C;
+};
+__global__ __launch_bounds__(256) void bn_fold_jobs_kernel(const FoldJob* __restrict__ jobs, const float eps) {
+    const FoldJob j = jobs[blockIdx.y];
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= j.C) return;
+    const float inv = j.gamma[c] / sqrtf(j.var[c] + eps);
+    j.scale[c] = inv;
+    j.shift[c] = j.beta[c] - j.mean[c] * inv;
+}
+
 // dst (+)= src
 __global__ __launch_bounds__(256) void add_kernel(float* __restrict__ dst, const float* __restrict__ src,
                                                  const long total, const int accumulate) {
@@ -870,7 +913,35 @@ __global__ void reg_finalize_kernel(const float* __restrict__ partial, const int
 
 // ------------------------------------------------------------------ Adam (TF training_ops.ApplyAdam form)
 // m += (g - m)(1 - b1); v += (g^2 - v)(1 - b2); var -= alpha * m / (sqrt(v) + eps),
-// alpha = lr * sqrt(1 - b2^t) / (1 - b1^t); g = grad * grad_scale (+ l2 * var where l2mask set)
+// alpha = lr * sqrt(1 - b2^t) / (1 - b1^t); g = grad * grad_scale (the l2 regulariser's gradient is already part of
+// grad: bwd_dense_wgrad adds it behind the layer's weight gradient)
+__device__ __forceinline__ void adam_update(float* __restrict__ var, float* __restrict__ m, float* __restrict__ v,
+                                            const float* __restrict__ grad, const long e, const float alpha, const float b1,
+                                            const float b2, const float eps, const float grad_scale) {
+    const float g = grad[e] * grad_scale;
+    const float mm = m[e] + (g - m[e]) * (1.0f - b1);
+    const float vv = v[e] + (g * g - v[e]) * (1.0f - b2);
+    m[e] = mm;
+    v[e] = vv;
+    var[e] -= alpha * mm / (sqrtf(vv) + eps);
+}
+// The same update over the TRAINABLE part of the flat vector while layers are frozen (ssd_net_set_trainable): the
+// trainable ranges, cut into segments of at most kAdamSeg elements, lie in a table in device memory; a workgroup takes
+// whole segments, so var / m / v / grad of a frozen range are not even read.  One launch however many ranges there are
+// (freezing every BatchNorm leaves ~100 disjoint ones).
+constexpr long kAdamSeg = 4096;
+struct AdamSeg {
+    long lo, n;
+};
+__global__ __launch_bounds__(256) void adam_ranges_kernel(float* __restrict__ var, float* __restrict__ m, float* __restrict__ v,
+                                                         const float* __restrict__ grad, const AdamSeg* __restrict__ segs,
+                                                         const int nseg, const float alpha, const float b1, const float b2,
+                                                         const float eps, const float grad_scale) {
+    for (int s = blockIdx.x; s < nseg; s += gridDim.x) {
+        const AdamSeg sg = segs[s];
+        for (long e = sg.lo + threadIdx.x; e < sg.lo + sg.n; e += 256) adam_update(var, m, v, grad, e, alpha, b1, b2, eps, grad_scale);
+    }
+}
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ var, float* __restrict__ m, float* __restrict__ v,
                                                   const float* __restrict__ grad, const long n, const float alpha,
                                                   const float b1, const float b2, const float eps,
@@ -898,6 +969,7 @@ struct TrainLayer {
     float* mean = nullptr;       // [C] batch statistics of the last forward
     float* var = nullptr;
     float* istd = nullptr;
+    float *fscale = nullptr, *fshift = nullptr;   // BN layers: the BatchNorm folded on its moving statistics (used while it is frozen)
     float* wfwd = nullptr;       // packed forward weights (dense convs)
     float* wbwd = nullptr;       // packed backward-data weights (rotated + transposed), nullptr: no dgrad
     int cpad = 0;                // dY channel count the backward-data conv sees (heads: padded to 32)
@@ -941,6 +1013,15 @@ struct ssd_train_state {
     std::vector<long> bucket_lo;
     std::vector<hipEvent_t> bucket_ev;
     std::vector<long> pending_hi;       // per layer i: end of the highest parameter of any ACTIVE layer j < i (0: none)
+    // fine-tuning (ssd_net_set_trainable): the backward plan of the net's current flags, one SSD_PLAN_* word per layer, made
+    // by refresh_plan when plan_rev lags behind ssd_net::trainable_rev
+    unsigned plan_rev = ~0u;
+    std::vector<int> plan;
+    bool any_frozen = false;
+    float* fold_jobs = nullptr;         // device array of FoldJob, room for every BatchNorm layer; the first n_fold_jobs are the frozen ones
+    int n_fold_jobs = 0, fold_jobs_cap = 0, fold_maxC = 0;
+    float* adam_segs = nullptr;         // device array of AdamSeg, room for adam_segs_cap; the first n_adam_segs cover the trainable ranges
+    int n_adam_segs = 0, adam_segs_cap = 0;
 };
 
 void ssd_train_state_free(ssd_train_state* s) {
@@ -973,6 +1054,44 @@ static bool trainable(const std::string& name) {
 
 // layers the training step executes: the un-fused layer list (fused kernels fold inference BatchNorm)
 static bool train_runs(const Layer& l) { return l.kind == LK_CONV || l.kind == LK_DW || l.kind == LK_POOL || l.kind == LK_L2NORM; }
+
+// ------------------------------------------------------------------ fine-tuning: trainable flags and the backward plan
+static std::string keras_layer_of(const std::string& param) { return param.substr(0, param.rfind('/')); }
+static bool param_frozen(const ssd_net* net, int p) {
+    return p >= 0 && !net->frozen.empty() && net->frozen.count(keras_layer_of(net->params[p].name)) != 0;
+}
+// a Keras layer that owns a trainable variable (one that owns only moving statistics cannot exist under this naming)
+static bool known_keras_layer(const ssd_net* net, const std::string& name) {
+    for (const auto& p : net->params)
+        if (trainable(p.name) && keras_layer_of(p.name) == name) return true;
+    return false;
+}
+
+// The backward plan: one SSD_PLAN_* word per layer, a pure function of the graph and net->frozen.  A tensor needs a gradient
+// iff a trainable parameter lies upstream of it (the image never does); a layer hands a gradient only to inputs that need
+// one, and a layer with nothing trainable whose inputs need none drops out of the backward.
+static std::vector<int> backward_plan(const ssd_net* net) {
+    std::vector<int> plan(net->layers.size(), 0);
+    std::vector<char> needs(net->tensors.size(), 0);
+    for (size_t i = 0; i < net->layers.size(); ++i) {
+        const Layer& l = net->layers[i];
+        if (!train_runs(l)) continue;
+        int f = 0;
+        if (l.kind == LK_L2NORM) {
+            if (!param_frozen(net, l.p_gamma)) f |= SSD_PLAN_WGRAD;
+        } else if (l.kind != LK_POOL) {
+            if (!param_frozen(net, l.p_kernel)) f |= SSD_PLAN_WGRAD;
+            if (l.p_kernel2 >= 0 && !param_frozen(net, l.p_kernel2)) f |= SSD_PLAN_WGRAD2;
+            if (l.p_bn >= 0 && !param_frozen(net, l.p_bn)) f |= SSD_PLAN_BN_BATCH | SSD_PLAN_BN_PARAMS;
+        }
+        if (l.in > 0 && needs[l.in]) f |= SSD_PLAN_DGRAD;
+        if (l.res >= 0 && needs[l.res]) f |= SSD_PLAN_RESGRAD;
+        if (!f) f = SSD_PLAN_SKIP;
+        else if (l.out >= 0) needs[l.out] = 1;
+        plan[i] = f;
+    }
+    return plan;
+}
 
 static long chunks_for(long M, long unit_blocks, long* rows_per_chunk, long min_rows, long max_chunks) {
     long chunks = (2048 + unit_blocks - 1) / unit_blocks;          // ~8 workgroups per CU in total
@@ -1078,6 +1197,52 @@ static ConvParams dense_conv_params(int B, int H, int W, int Cin, int Cout, int 
     p.out_pixel_stride = Cout;
     p.out_batch_stride = (long)Ho * Wo * Cout;
     return p;
+}
+
+// Brings the training state's plan up to the net's trainable flags (ssd_net_set_trainable): the per-layer backward plan, the
+// fold jobs of the frozen BatchNorms and the Adam segments of the trainable ranges.  Runs when the flags changed since the
+// last step / optimizer call, which is rare: it waits for the device (a launch in flight may still read the old tables)
+// and uploads with blocking copies.  With nothing frozen both tables are empty and the step is the all-trainable one.
+static int refresh_plan(const ssd_net* net, ssd_train_state& s) {
+    if (s.plan_rev == net->trainable_rev) return SSD_OK;
+    s.plan = backward_plan(net);
+    s.any_frozen = false;
+    std::vector<FoldJob> folds;
+    s.fold_maxC = 0;
+    for (size_t i = 0; i < net->layers.size(); ++i) {
+        const Layer& l = net->layers[i];
+        if (!s.tl[i].active) continue;
+        for (int q : {l.p_kernel, l.p_kernel2, l.p_bn, l.p_gamma}) s.any_frozen |= param_frozen(net, q);
+        if (l.p_bn < 0 || (s.plan[i] & SSD_PLAN_BN_BATCH)) continue;
+        folds.push_back(FoldJob{net->params[l.p_bn].dev, net->params[l.p_bn + 1].dev, net->params[l.p_bn + 2].dev,
+                                net->params[l.p_bn + 3].dev, s.tl[i].fscale, s.tl[i].fshift, l.Cout});
+        s.fold_maxC = std::max(s.fold_maxC, l.Cout);
+    }
+    // trainable ranges of the flat vector (neighbours merged), cut into segments
+    std::vector<AdamSeg> segs;
+    if (s.any_frozen) {
+        long lo = -1, hi = -1;
+        const auto flush = [&] {
+            for (long b = lo; b >= 0 && b < hi; b += kAdamSeg) segs.push_back(AdamSeg{b, std::min(kAdamSeg, hi - b)});
+            lo = hi = -1;
+        };
+        for (size_t q = 0; q < net->params.size(); ++q) {
+            if (s.poff[q] < 0 || param_frozen(net, (int)q)) continue;
+            if (s.poff[q] != hi) flush();
+            if (lo < 0) lo = s.poff[q];
+            hi = s.poff[q] + (long)net->params[q].count;
+        }
+        flush();
+    }
+    SSD_CHECK_ARG((int)folds.size() <= s.fold_jobs_cap && (int)segs.size() <= s.adam_segs_cap,
+                  "train: the fine-tuning tables (%zu fold jobs, %zu Adam segments) exceed their plan", folds.size(), segs.size());
+    SSD_HIP(hipDeviceSynchronize());
+    if (!folds.empty()) SSD_HIP(hipMemcpy(s.fold_jobs, folds.data(), folds.size() * sizeof(FoldJob), hipMemcpyHostToDevice));
+    if (!segs.empty()) SSD_HIP(hipMemcpy(s.adam_segs, segs.data(), segs.size() * sizeof(AdamSeg), hipMemcpyHostToDevice));
+    s.n_fold_jobs = (int)folds.size();
+    s.n_adam_segs = (int)segs.size();
+    s.plan_rev = net->trainable_rev;
+    return SSD_OK;
 }
 
 // The training step's environment switches, read once per process.
@@ -1288,10 +1453,13 @@ static long dw_bwd_chunks(DwBwdParams& dp) {
     dp.rows_per_chunk = rpc;
     return chunks;
 }
-static int dw_bwd_launch(const DwBwdParams& dp, long chunks, float* dw_out, hipStream_t st) {
-    hipLaunchKernelGGL(dw_wgrad_kernel, dim3((dp.C + 63) / 64, (unsigned)chunks), dim3(256), 0, st, dp);
-    int rc = chunk_sum(dp.partial, chunks, 9L * dp.C, dw_out, st);
-    if (rc) return rc;
+static int dw_bwd_launch(const DwBwdParams& dp, long chunks, float* dw_out, hipStream_t st, bool want_dw = true, bool want_dx = true) {
+    if (want_dw) {
+        hipLaunchKernelGGL(dw_wgrad_kernel, dim3((dp.C + 63) / 64, (unsigned)chunks), dim3(256), 0, st, dp);
+        const int rc = chunk_sum(dp.partial, chunks, 9L * dp.C, dw_out, st);
+        if (rc) return rc;
+    }
+    if (!want_dx) return SSD_OK;
     if (dp.stride == 1)
         hipLaunchKernelGGL(dw_dgrad4_kernel, dim3(grid_for((long)dp.B * dp.H * ((dp.W + 3) / 4) * (dp.C / 4))), dim3(256), 0, st, dp);
     else
@@ -1397,7 +1565,7 @@ struct StepCtx {
     }
 };
 
-static int train_forward_conv(StepCtx& c, const Layer& l, TrainLayer& t) {
+static int train_forward_conv(StepCtx& c, const Layer& l, TrainLayer& t, bool bn_frozen) {
     ssd_train_state& s = c.s;
     ConvParams p = dense_conv_params(c.B, l.H, l.W, l.Cin, l.Cout, l.kh, l.kw, l.stride, l.dil, l.pt, l.pl, l.Ho, l.Wo);
     p.in = s.act[l.in];
@@ -1405,7 +1573,15 @@ static int train_forward_conv(StepCtx& c, const Layer& l, TrainLayer& t) {
     p.w3 = conv_split_planes(t.wfwd, l.kh * l.kw * l.Cin, l.Cout);
     p.bf16 = c.net->precision;          // precision 1: the cost model takes the bf16 (one-product) tiles
     p.act = l.p_bn >= 0 ? SSD_ACT_NONE : l.act;      // BatchNorm layers: the activation follows the normalisation (bn_apply_kernel)
-    if (l.p_bn >= 0) {
+    if (bn_frozen) {
+        // frozen BatchNorm: folded on the moving statistics, the epilogue writes act(scale * conv + shift) (+ residual) --
+        // one launch, no `pre` traffic, no statistics pass, no bn_apply_kernel
+        p.scale = t.fscale;
+        p.shift = t.fshift;
+        p.act = l.act;
+        p.residual = l.res >= 0 ? s.act[l.res] : nullptr;
+        p.out = s.act[l.out];
+    } else if (l.p_bn >= 0) {
         p.out = t.pre;
     } else if (l.head_kind == 0) {
         p.shift = l.p_bias2 >= 0 ? nullptr : c.net->params[l.p_bias].dev;
@@ -1421,7 +1597,8 @@ static int train_forward_conv(StepCtx& c, const Layer& l, TrainLayer& t) {
     return launch_conv(s, p, c.st);
 }
 
-// training-mode forward of layer i: BatchNorm on the batch statistics, moving averages updated
+// training-mode forward of layer i: BatchNorm on the batch statistics, moving averages updated -- unless it is frozen
+// (Keras trainable = False, TF 2.0: inference mode), then the layer is one launch on the folded moving statistics
 static int train_forward_layer(StepCtx& c, size_t i) {
     ssd_train_state& s = c.s;
     const ssd_net* net = c.net;
@@ -1431,10 +1608,16 @@ static int train_forward_layer(StepCtx& c, size_t i) {
     const float* x = s.act[l.in];
     if (l.kind == LK_POOL) return launch_maxpool(x, c.B, l.H, l.W, l.Cin, l.kh, l.stride, l.pt, l.pl, l.Ho, l.Wo, s.act[l.out], c.st);
     if (l.kind == LK_L2NORM) return launch_l2norm(x, M, l.Cin, net->params[l.p_gamma].dev, s.act[l.out], c.st);
-    int rc = l.kind == LK_CONV ? train_forward_conv(c, l, t)
+    const bool bn_frozen = l.p_bn >= 0 && !(s.plan[i] & SSD_PLAN_BN_BATCH);
+    if (bn_frozen && l.kind == LK_DW) {
+        SSD_UNSUPPORTED_IF(l.res >= 0, "train: depthwise layer %s has a residual input", l.name.c_str());
+        return launch_dwconv3x3(x, c.B, l.H, l.W, l.Cin, l.stride, l.pt, l.pl, l.Ho, l.Wo, net->params[l.p_kernel].dev, t.fscale,
+                                t.fshift, l.act, s.act[l.out], c.st);
+    }
+    int rc = l.kind == LK_CONV ? train_forward_conv(c, l, t, bn_frozen)
                                : launch_dwconv3x3(x, c.B, l.H, l.W, l.Cin, l.stride, l.pt, l.pl, l.Ho, l.Wo, net->params[l.p_kernel].dev,
                                                   nullptr, nullptr, SSD_ACT_NONE, t.pre, c.st);
-    if (rc || l.p_bn < 0) return rc;
+    if (rc || l.p_bn < 0 || bn_frozen) return rc;
     rc = bn_stats(s, t, M, l.Cout, net->params[l.p_bn + 2].dev, net->params[l.p_bn + 3].dev, c.st);
     if (rc) return rc;
     hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(M * l.Cout)), dim3(256), 0, c.st, t.pre, M, l.Cout, t.mean, t.istd,
@@ -1457,20 +1640,24 @@ static int bwd_pool(StepCtx& c, const Layer& l) {
 }
 
 // L2 normalisation: dX, and d gamma = column sums of the per-element products the kernel leaves in `tmp`
-static int bwd_l2norm(StepCtx& c, const Layer& l, const TrainLayer& t, float* tmp) {
+// (`plan`: without SSD_PLAN_DGRAD the kernel's dX is left unused -- the input needs no gradient, nobody reads it --, without
+// SSD_PLAN_WGRAD the scale is frozen and its column sums are not taken)
+static int bwd_l2norm(StepCtx& c, const Layer& l, const TrainLayer& t, float* tmp, int plan) {
     ssd_train_state& s = c.s;
     const long M = (long)c.B * l.Ho * l.Wo, blocks = (M + 3) / 4;
+    const bool dgrad = plan & SSD_PLAN_DGRAD;
     hipLaunchKernelGGL(l2norm_bwd_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, c.st, s.act[l.in], s.gact[l.out],
-                       c.net->params[l.p_gamma].dev, M, l.Cin, s.gact[l.in], (int)s.gwritten[l.in], tmp);
+                       c.net->params[l.p_gamma].dev, M, l.Cin, s.gact[l.in], dgrad ? (int)s.gwritten[l.in] : 0, tmp);
     SSD_LAUNCH_CHECK();
-    s.gwritten[l.in] = 1;
+    if (dgrad) s.gwritten[l.in] = 1;
+    if (!(plan & SSD_PLAN_WGRAD)) return SSD_OK;
     return col_sum(s, tmp, M, l.Cin, l.Cin, 1.0f, c.grads + t.g_gamma, c.st);
 }
 
 // The three ways to dY, the gradient w.r.t. a conv / depthwise output as a dense [M][*ldy] matrix (in `dyb` unless it is dOut
 // itself); each also writes the layer's bias or BatchNorm parameter gradients.
 // Head conv: one level gathered out of the concatenated [B,N,K] gradients of the loss; bias gradients = its column sums
-static int bwd_head_dy(StepCtx& c, const Layer& l, const TrainLayer& t, float* dyb, const float** dY, int* ldy) {
+static int bwd_head_dy(StepCtx& c, const Layer& l, const TrainLayer& t, float* dyb, const float** dY, int* ldy, int plan) {
     ssd_train_state& s = c.s;
     const long M = (long)c.B * l.Ho * l.Wo;
     const int ld = t.cpad, C2 = l.Cout - l.Cout1;
@@ -1480,27 +1667,48 @@ static int bwd_head_dy(StepCtx& c, const Layer& l, const TrainLayer& t, float* d
     hipLaunchKernelGGL(gather_head_kernel, dim3(grid_for(M * C2)), dim3(256), 0, c.st, s.gdeltas, l.head2_bs, l.head2_off, l.head2_ps,
                        c.B, l.Ho * l.Wo, C2, dyb, ld, l.Cout1);
     SSD_LAUNCH_CHECK();
+    *dY = dyb; *ldy = ld;
+    if (!(plan & (SSD_PLAN_WGRAD | SSD_PLAN_WGRAD2))) return SSD_OK;        // both convs of the level frozen: no bias gradients
     const int rc = col_sum(s, dyb, M, l.Cout, ld, 1.0f, s.dbeta_tmp, c.st);
     if (rc) return rc;
-    SSD_HIP(hipMemcpyAsync(c.grads + t.g_bias, s.dbeta_tmp, (size_t)l.Cout1 * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-    SSD_HIP(hipMemcpyAsync(c.grads + t.g_bias2, s.dbeta_tmp + l.Cout1, (size_t)C2 * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-    *dY = dyb; *ldy = ld;
+    if (plan & SSD_PLAN_WGRAD)
+        SSD_HIP(hipMemcpyAsync(c.grads + t.g_bias, s.dbeta_tmp, (size_t)l.Cout1 * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+    if (plan & SSD_PLAN_WGRAD2)
+        SSD_HIP(hipMemcpyAsync(c.grads + t.g_bias2, s.dbeta_tmp + l.Cout1, (size_t)C2 * sizeof(float), hipMemcpyDeviceToDevice, c.st));
     return SSD_OK;
 }
 // out = bn(conv) + res: the residual branch receives dOut as is
-static int bwd_residual(StepCtx& c, const Layer& l) {
-    if (l.res < 0) return SSD_OK;
+static int bwd_residual(StepCtx& c, const Layer& l, int plan) {
+    if (l.res < 0 || !(plan & SSD_PLAN_RESGRAD)) return SSD_OK;
     const long n = (long)c.B * l.Ho * l.Wo * l.Cout;
     hipLaunchKernelGGL(add_kernel, dim3(grid_for(n)), dim3(256), 0, c.st, c.s.gact[l.res], c.s.gact[l.out], n, (int)c.s.gwritten[l.res]);
     SSD_LAUNCH_CHECK();
     c.s.gwritten[l.res] = 1;
     return SSD_OK;
 }
-static int bwd_bn_dy(StepCtx& c, const Layer& l, const TrainLayer& t, float* dyb, const float** dY) {
+// (`plan`: a layer whose conv is frozen and whose input needs no gradient has no use for dY -- only dgamma / dbeta are made)
+static int bwd_bn_dy(StepCtx& c, const Layer& l, const TrainLayer& t, float* dyb, const float** dY, int plan) {
     const float* dOut = c.s.gact[l.out];
-    int rc = bwd_residual(c, l);
+    int rc = bwd_residual(c, l, plan);
     if (rc) return rc;
     const long M = (long)c.B * l.Ho * l.Wo;
+    if (!(plan & SSD_PLAN_BN_BATCH)) {
+        // frozen BatchNorm: dY = dOut * act'(out) * scale (bn_frozen_bwd4_kernel), no reductions
+        *dY = dyb;
+        if (!(plan & (SSD_PLAN_WGRAD | SSD_PLAN_DGRAD))) return SSD_OK;
+        SSD_UNSUPPORTED_IF(l.res >= 0 && l.act != SSD_ACT_NONE, "train: %s has a residual add behind an activation: the stored output is no pass-mask",
+                           l.name.c_str());
+        const float* out = c.s.act[l.out];
+        const long total = M * l.Cout;
+        if (l.Cout % 4 == 0 && ((((uintptr_t)dOut | (uintptr_t)out | (uintptr_t)t.fscale | (uintptr_t)dyb) & 15) == 0))
+            hipLaunchKernelGGL(bn_frozen_bwd4_kernel, dim3(grid_for(total / 4)), dim3(256), 0, c.st, reinterpret_cast<const f32x4*>(dOut),
+                               reinterpret_cast<const f32x4*>(out), reinterpret_cast<const f32x4*>(t.fscale), total / 4, l.Cout / 4,
+                               l.act, reinterpret_cast<f32x4*>(dyb));
+        else
+            hipLaunchKernelGGL(bn_frozen_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, c.st, dOut, out, t.fscale, total, l.Cout, l.act, dyb);
+        SSD_LAUNCH_CHECK();
+        return SSD_OK;
+    }
     const float *gamma = c.net->params[l.p_bn].dev, *beta = c.net->params[l.p_bn + 1].dev;
     float *dgamma = c.grads + t.g_gamma, *dbeta = c.grads + t.g_beta;
     RedParams rp{};
@@ -1510,25 +1718,29 @@ static int bwd_bn_dy(StepCtx& c, const Layer& l, const TrainLayer& t, float* dyb
     rc = col_reduce<RED_BN_BWD>(c.s, rp, &chunks, c.st);
     if (!rc) rc = col_finalize(c.s, chunks, l.Cout, 1.0f, dbeta, dgamma, 0, c.st);      // s1 = dbeta, s2 = dgamma
     if (rc) return rc;
+    *dY = dyb;
+    if (!(plan & (SSD_PLAN_WGRAD | SSD_PLAN_DGRAD))) return SSD_OK;
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(M * l.Cout)), dim3(256), 0, c.st, dOut, t.pre, M, l.Cout, t.mean, t.istd,
                        gamma, beta, l.act, dgamma, dbeta, dyb);
     SSD_LAUNCH_CHECK();
-    *dY = dyb;
     return SSD_OK;
 }
-static int bwd_bias_act_dy(StepCtx& c, const Layer& l, const TrainLayer& t, float* dyb, const float** dY) {
+// (`plan`: a frozen conv has no bias gradient; it is in the backward only for its data gradient)
+static int bwd_bias_act_dy(StepCtx& c, const Layer& l, const TrainLayer& t, float* dyb, const float** dY, int plan) {
     ssd_train_state& s = c.s;
     const float* dOut = s.gact[l.out];
-    int rc = bwd_residual(c, l);
+    int rc = bwd_residual(c, l, plan);
     if (rc) return rc;
     const long M = (long)c.B * l.Ho * l.Wo;
-    RedParams rp{};
-    rp.a = dOut; rp.b = l.act ? s.act[l.out] : nullptr;
-    rp.M = M; rp.C = l.Cout; rp.lda = l.Cout; rp.act = l.act;
-    long chunks = 0;
-    rc = col_reduce<RED_ACT_BWD>(s, rp, &chunks, c.st);
-    if (!rc) rc = col_finalize(s, chunks, l.Cout, 1.0f, c.grads + t.g_bias, nullptr, 0, c.st);
-    if (rc) return rc;
+    if (plan & SSD_PLAN_WGRAD) {
+        RedParams rp{};
+        rp.a = dOut; rp.b = l.act ? s.act[l.out] : nullptr;
+        rp.M = M; rp.C = l.Cout; rp.lda = l.Cout; rp.act = l.act;
+        long chunks = 0;
+        rc = col_reduce<RED_ACT_BWD>(s, rp, &chunks, c.st);
+        if (!rc) rc = col_finalize(s, chunks, l.Cout, 1.0f, c.grads + t.g_bias, nullptr, 0, c.st);
+        if (rc) return rc;
+    }
     *dY = dOut;
     if (!l.act) return SSD_OK;
     hipLaunchKernelGGL(act_bwd_kernel, dim3(grid_for(M * l.Cout)), dim3(256), 0, c.st, dOut, s.act[l.out], M * l.Cout, l.act, dyb);
@@ -1537,7 +1749,7 @@ static int bwd_bias_act_dy(StepCtx& c, const Layer& l, const TrainLayer& t, floa
     return SSD_OK;
 }
 
-static int bwd_depthwise(StepCtx& c, const Layer& l, const TrainLayer& t, const float* dY) {
+static int bwd_depthwise(StepCtx& c, const Layer& l, const TrainLayer& t, const float* dY, int plan) {
     ssd_train_state& s = c.s;
     DwBwdParams dp{};
     dp.x = s.act[l.in]; dp.g = dY; dp.w = c.net->params[l.p_kernel].dev; dp.dx = s.gact[l.in];
@@ -1549,13 +1761,15 @@ static int bwd_depthwise(StepCtx& c, const Layer& l, const TrainLayer& t, const 
     int rc = ensure_slab(s, (size_t)chunks * 9 * l.Cin, &s.partial, &s.partial_floats);
     if (rc) return rc;
     dp.partial = s.partial;
-    s.gwritten[l.in] = 1;
-    return dw_bwd_launch(dp, chunks, c.grads + t.g_kernel, c.st);
+    const bool dgrad = plan & SSD_PLAN_DGRAD;
+    if (dgrad) s.gwritten[l.in] = 1;
+    return dw_bwd_launch(dp, chunks, c.grads + t.g_kernel, c.st, plan & SSD_PLAN_WGRAD, dgrad);
 }
 
 // dense conv: weight gradient(s), on the side stream behind dY (StepCtx::side)
-static int bwd_dense_wgrad(StepCtx& c, const Layer& l, const TrainLayer& t, const float* dY, int ldy, const float* dyb) {
+static int bwd_dense_wgrad(StepCtx& c, const Layer& l, const TrainLayer& t, const float* dY, int ldy, const float* dyb, int plan) {
     ssd_train_state& s = c.s;
+    if (!(plan & (SSD_PLAN_WGRAD | SSD_PLAN_WGRAD2))) return SSD_OK;       // frozen
     const float* x = s.act[l.in];
     hipStream_t wst = c.side ? s.wstream : c.st;
     if (c.side) {
@@ -1566,8 +1780,9 @@ static int bwd_dense_wgrad(StepCtx& c, const Layer& l, const TrainLayer& t, cons
     if (l.p_kernel2 < 0) {
         rc = wgrad(s, l, c.B, x, dY, ldy, l.Cout, c.grads + t.g_kernel, wst);
     } else {
-        rc = wgrad(s, l, c.B, x, dY, ldy, l.Cout1, c.grads + t.g_kernel, wst);
-        if (!rc) rc = wgrad(s, l, c.B, x, dY + l.Cout1, ldy, l.Cout - l.Cout1, c.grads + t.g_kernel2, wst);
+        // the label and the box conv of a head level freeze independently
+        rc = (plan & SSD_PLAN_WGRAD) ? wgrad(s, l, c.B, x, dY, ldy, l.Cout1, c.grads + t.g_kernel, wst) : SSD_OK;
+        if (!rc && (plan & SSD_PLAN_WGRAD2)) rc = wgrad(s, l, c.B, x, dY + l.Cout1, ldy, l.Cout - l.Cout1, c.grads + t.g_kernel2, wst);
     }
     if (rc) return rc;
     // VGG16: kernel_regularizer=l2(5e-4) on every backbone / extra conv (models/ssd_vgg16.py:44-45; the head
@@ -1672,6 +1887,9 @@ static int begin_plan_layers(const ssd_net* net, ssd_train_state& s, TrainSizes&
             if (!rc) rc = talloc(s, l.Cout, &t.mean);
             if (!rc) rc = talloc(s, l.Cout, &t.var);
             if (!rc) rc = talloc(s, l.Cout, &t.istd);
+            if (!rc) rc = talloc(s, l.Cout, &t.fscale);
+            if (!rc) rc = talloc(s, l.Cout, &t.fshift);
+            ++s.fold_jobs_cap;
         }
         if (l.kind != LK_CONV) {
             sz.max_out = std::max(sz.max_out, mc);
@@ -1739,6 +1957,11 @@ static int begin_streams_scratch(const ssd_net* net, ssd_train_state& s, const T
     if (!rc) rc = talloc(s, BN * net->L, &s.probs);
     if (!rc) rc = talloc(s, BN * 4, &s.gdeltas);
     if (!rc) rc = talloc(s, BN * net->L, &s.glogits);
+    // fine-tuning tables (refresh_plan): a fold job per BatchNorm layer, an Adam segment per kAdamSeg elements of a parameter
+    for (size_t q = 0; q < net->params.size(); ++q)
+        if (s.poff[q] >= 0) s.adam_segs_cap += (int)((net->params[q].count + kAdamSeg - 1) / kAdamSeg);
+    if (!rc) rc = talloc(s, ((size_t)s.fold_jobs_cap * sizeof(FoldJob) + 3) / 4, &s.fold_jobs);
+    if (!rc) rc = talloc(s, ((size_t)s.adam_segs_cap * sizeof(AdamSeg) + 3) / 4, &s.adam_segs);
     if (rc) return rc;
     s.loss_ws_bytes = ssd_loss_workspace_bytes(s.batch, net->num_priors);
     if (hipMalloc(&s.loss_ws, s.loss_ws_bytes) != hipSuccess) {
@@ -1851,7 +2074,18 @@ int ssd_net_train_forward_backward(ssd_net* net, const float* image_dev, int B, 
     const bool side = s.wstream && (s.bucket_lo.empty() || train_env().side_buckets);
     StepCtx c{net, s, st, B, grads_flat_dev, side};
     c.next_bucket = s.bucket_lo.size();
-    int rc = SSD_OK;
+    int rc = refresh_plan(net, s);
+    if (rc) return rc;
+    if (s.any_frozen) {
+        // frozen ranges hold exactly 0.0f for the all-reduce and every other reader: the whole vector is cleared with one
+        // memset in front of everything that writes it (the side stream's weight gradients are ordered behind it through ev_dy)
+        SSD_HIP(hipMemsetAsync(grads_flat_dev, 0, s.P * sizeof(float), st));
+        if (s.n_fold_jobs) {
+            hipLaunchKernelGGL(bn_fold_jobs_kernel, dim3((s.fold_maxC + 255) / 256, (unsigned)s.n_fold_jobs), dim3(256), 0, st,
+                               reinterpret_cast<const FoldJob*>(s.fold_jobs), kBnEps);
+            SSD_LAUNCH_CHECK();
+        }
+    }
 
     // re-pack the (just updated) weights of every conv: forward and backward-data forms, one launch
     if (s.n_pack_jobs) {
@@ -1877,27 +2111,31 @@ int ssd_net_train_forward_backward(ssd_net* net, const float* image_dev, int B, 
         if (!t.active) continue;
         // layers > i are done: what no layer <= i owns is final
         if (!s.pending_hi.empty() && (rc = c.mark_ready(s.pending_hi[i]))) return rc;
+        const int plan = s.plan[i];
+        if (plan & SSD_PLAN_SKIP) continue;             // nothing trainable here or upstream: its (zero) ranges are final already
         float* const dyb = l.kind == LK_POOL ? nullptr : c.acquire_dy();      // this layer's dY / scratch buffer
-        if (!l.head_kind && !s.gwritten[l.out]) {       // (a head conv takes its gradient from the loss)
+        // (a head conv takes its gradient from the loss; by the plan every other layer that is not skipped has a consumer
+        // that hands it one)
+        if (!l.head_kind && !s.gwritten[l.out]) {
             set_error("train: no gradient reached tensor '%s'", net->tensors[l.out].name.c_str());
             return SSD_E_STATE;
         }
         if (l.kind == LK_POOL || l.kind == LK_L2NORM) {
-            rc = l.kind == LK_POOL ? bwd_pool(c, l) : bwd_l2norm(c, l, t, dyb);
+            rc = l.kind == LK_POOL ? bwd_pool(c, l) : bwd_l2norm(c, l, t, dyb, plan);
             if (rc) return rc;
             continue;
         }
         const float* dY = nullptr;       // gradient w.r.t. the conv / depthwise output, dense [M][ldy]
         int ldy = l.Cout;
-        if (l.head_kind) rc = bwd_head_dy(c, l, t, dyb, &dY, &ldy);
-        else if (l.p_bn >= 0) rc = bwd_bn_dy(c, l, t, dyb, &dY);
-        else rc = bwd_bias_act_dy(c, l, t, dyb, &dY);
+        if (l.head_kind) rc = bwd_head_dy(c, l, t, dyb, &dY, &ldy, plan);
+        else if (l.p_bn >= 0) rc = bwd_bn_dy(c, l, t, dyb, &dY, plan);
+        else rc = bwd_bias_act_dy(c, l, t, dyb, &dY, plan);
         if (rc) return rc;
         if (l.kind == LK_DW) {
-            rc = bwd_depthwise(c, l, t, dY);
+            if (plan & (SSD_PLAN_WGRAD | SSD_PLAN_DGRAD)) rc = bwd_depthwise(c, l, t, dY, plan);
         } else {
-            rc = bwd_dense_wgrad(c, l, t, dY, ldy, dyb);
-            if (!rc && t.wbwd) rc = bwd_dense_dgrad(c, l, t, dY, ldy);
+            rc = bwd_dense_wgrad(c, l, t, dY, ldy, dyb, plan);
+            if (!rc && t.wbwd && (plan & SSD_PLAN_DGRAD)) rc = bwd_dense_dgrad(c, l, t, dY, ldy);
         }
         if (rc) return rc;
     }
@@ -1977,14 +2215,45 @@ int ssd_net_adam_step(ssd_net* net, const float* grads_flat_dev, float lr, float
     SSD_CHECK_ARG(net && grads_flat_dev, "ssd_net_adam_step: NULL argument");
     if (!net->train) { set_error("ssd_net_adam_step: call ssd_net_train_begin() first"); return SSD_E_STATE; }
     ssd_train_state& s = *net->train;
+    const int rp = refresh_plan(net, s);
+    if (rp) return rp;
     s.step += 1;
     const double t = (double)s.step;
     const float alpha = (float)((double)lr * std::sqrt(1.0 - std::pow((double)beta2, t)) / (1.0 - std::pow((double)beta1, t)));
-    hipLaunchKernelGGL(adam_kernel, dim3(grid_for((long)s.P)), dim3(256), 0, (hipStream_t)stream, s.flat, s.m, s.v,
-                       grads_flat_dev, (long)s.P, alpha, beta1, beta2, eps, grad_scale);
+    if (!s.any_frozen)
+        hipLaunchKernelGGL(adam_kernel, dim3(grid_for((long)s.P)), dim3(256), 0, (hipStream_t)stream, s.flat, s.m, s.v,
+                           grads_flat_dev, (long)s.P, alpha, beta1, beta2, eps, grad_scale);
+    else if (s.n_adam_segs)
+        // frozen ranges keep var, m and v bitwise: one launch over the table of trainable segments (adam_ranges_kernel).  The
+        // moments of a layer that is unfrozen later continue from where they were (Keras rebuilds its optimizer at the
+        // compile() that follows a change of `trainable`; here there is no such call)
+        hipLaunchKernelGGL(adam_ranges_kernel, dim3(s.n_adam_segs < 16384 ? s.n_adam_segs : 16384), dim3(256), 0, (hipStream_t)stream,
+                           s.flat, s.m, s.v, grads_flat_dev, reinterpret_cast<const AdamSeg*>(s.adam_segs), s.n_adam_segs, alpha,
+                           beta1, beta2, eps, grad_scale);
     SSD_LAUNCH_CHECK();
     net->finalized = false;
     net->drop_graphs();
+    return SSD_OK;
+}
+
+int ssd_net_set_trainable(ssd_net* net, const char* keras_layer, int trainable_flag) {
+    SSD_CHECK_ARG(net && keras_layer, "ssd_net_set_trainable: NULL argument");
+    SSD_CHECK_ARG(known_keras_layer(net, keras_layer), "ssd_net_set_trainable: '%s' is no Keras layer with trainable variables of this net", keras_layer);
+    const bool changed = trainable_flag ? net->frozen.erase(keras_layer) != 0 : net->frozen.insert(keras_layer).second;
+    if (changed) ++net->trainable_rev;
+    return SSD_OK;
+}
+
+int ssd_net_get_trainable(const ssd_net* net, const char* keras_layer) {
+    SSD_CHECK_ARG(net && keras_layer, "ssd_net_get_trainable: NULL argument");
+    SSD_CHECK_ARG(known_keras_layer(net, keras_layer), "ssd_net_get_trainable: '%s' is no Keras layer with trainable variables of this net", keras_layer);
+    return net->frozen.count(keras_layer) ? 0 : 1;
+}
+
+int ssd_net_train_plan(const ssd_net* net, int layer, int* flags) {
+    SSD_CHECK_ARG(net && flags, "ssd_net_train_plan: NULL argument");
+    SSD_CHECK_ARG(layer >= 0 && layer < (int)net->layers.size(), "ssd_net_train_plan: layer %d is outside 0..%d", layer, (int)net->layers.size() - 1);
+    *flags = backward_plan(net)[layer];
     return SSD_OK;
 }
 

@@ -4,6 +4,7 @@ stream provider only; weights live in the native net, keyed by the Keras variabl
 (``<layer>/<variable>``) in Keras layouts."""
 import ctypes
 import os
+import re
 
 import numpy as np
 import torch
@@ -15,6 +16,22 @@ _TABLE_OPTIONS = ("use_wino", "image_split", "conv_dma")
 # options that make the native net drop `finalized` (ssd_net_set_option): the Python handle must re-finalize too
 _REFINALIZE_OPTIONS = ("precision", "image_split", "use_wino", "conv_dma")
 _STALE_WARNED = set()
+
+
+class _LayerProxy(object):
+    """What ``SSDModel.get_layer`` returns: the Keras layer's ``name`` and its settable ``trainable`` flag."""
+
+    def __init__(self, model, name):
+        self._model = model
+        self.name = name
+
+    @property
+    def trainable(self):
+        return self._model._is_trainable(self.name)
+
+    @trainable.setter
+    def trainable(self, value):
+        self._model._set_trainable(self.name, bool(value))
 
 
 class SSDModel(object):
@@ -100,7 +117,93 @@ class SSDModel(object):
             m._tuning_explicit = self.get_tuning()     # the replica runs exactly the parent's kernels
         elif getattr(self, "_tuning_explicit", None) is not None:
             m._tuning_explicit = self._tuning_explicit
+        frozen = self.non_trainable_layer_names()
+        if frozen:
+            m.set_trainable(frozen, False)
         return m
+
+    # ------------------------------------------------------------------ fine-tuning (Keras layer.trainable)
+    def layer_names(self):
+        """Keras layers that own trainable variables, in parameter-table order: a parameter name up to its last ``/``
+        (``Conv1``, ``bn_Conv1``, ``block_3_depthwise_BN``, ``extra2_1``, ``4_conv_boxes_output``, ``l2_normalization``)."""
+        out = []
+        for name, _ in self.param_specs:
+            layer, var = name.rsplit("/", 1)
+            if var not in ("moving_mean", "moving_variance") and layer not in out:
+                out.append(layer)
+        return out
+
+    def batch_norm_layer_names(self):
+        return [n.rsplit("/", 1)[0] for n, _ in self.param_specs if n.endswith("/gamma")]
+
+    def _is_trainable(self, name):
+        rc = _h.lib().ssd_net_get_trainable(self._net, name.encode())
+        if rc < 0:
+            _h.check(rc, "get_layer")
+        return bool(rc)
+
+    def _set_trainable(self, name, value):
+        _h.check(_h.lib().ssd_net_set_trainable(self._net, name.encode(), 1 if value else 0), "set_trainable")
+
+    def get_layer(self, name):
+        """Keras ``model.get_layer(name)``: a proxy with ``.name`` and a settable ``.trainable``.  ``trainable = False``
+        freezes the layer in the native training step (include/ssd_hip.h, ssd_net_set_trainable): no gradient, no Adam
+        update, a BatchNorm in inference mode (TF 2.0 semantics).  Takes effect at the next step; unlike Keras no
+        ``compile()`` is needed in between -- and the Adam moments of a layer unfrozen later continue where they were."""
+        self._is_trainable(name)            # raises ValueError on an unknown name
+        return _LayerProxy(self, name)
+
+    def set_trainable(self, patterns, trainable):
+        """``fnmatch`` patterns (one string or several) over the Keras layer names -> the names matched, now all
+        ``trainable``.  Raises ValueError when nothing matches."""
+        import fnmatch
+        if isinstance(patterns, str):
+            patterns = [patterns]
+        patterns = list(patterns)
+        matched = [n for n in self.layer_names() if any(fnmatch.fnmatchcase(n, p) for p in patterns)]
+        if not matched:
+            raise ValueError("set_trainable: no layer matches %r" % (patterns,))
+        for n in matched:
+            self._set_trainable(n, trainable)
+        return matched
+
+    def trainable_layer_names(self):
+        return [n for n in self.layer_names() if self._is_trainable(n)]
+
+    def non_trainable_layer_names(self):
+        return [n for n in self.layer_names() if not self._is_trainable(n)]
+
+    def backbone_layer_names(self, batch_norm=True):
+        """The layers ``freeze_backbone`` covers.  MobileNetV2: every layer that is neither ``extra*`` nor a head (the
+        rule of ``keras_default_init``: what arrives with pretrained weights); VGG16: ``conv1_1`` .. ``conv5_3``.
+        ``batch_norm=False`` leaves the BatchNorm layers out."""
+        bn = set(self.batch_norm_layer_names())
+        if self.backbone == "mobilenet_v2":
+            names = [n for n in self.layer_names() if not (n.startswith("extra") or n[0].isdigit())]
+        else:
+            names = [n for n in self.layer_names() if re.match(r"conv[1-5]_\d$", n)]
+        return [n for n in names if batch_norm or n not in bn]
+
+    def freeze_backbone(self, batch_norm=True):
+        """Fine-tuning: ``for l in base_model.layers: l.trainable = False``.  With ``batch_norm=False`` the backbone's
+        BatchNorm layers stay trainable (batch statistics, moving averages updated).  Returns the frozen names."""
+        names = self.backbone_layer_names(batch_norm)
+        for n in names:
+            self._set_trainable(n, False)
+        return names
+
+    def train_plan(self):
+        """``ssd_net_train_plan`` of every layer the training step runs: name -> OR of ``ssd_hip.PLAN_*``.  A pure function
+        of the graph and the trainable flags: needs no device."""
+        lib = _h.lib()
+        out = {}
+        f = ctypes.c_int(0)
+        for i in range(lib.ssd_net_num_layers(self._net)):
+            if lib.ssd_net_layer_kind(self._net, i).decode() not in ("conv", "dw", "pool", "l2norm"):
+                continue
+            _h.check(lib.ssd_net_train_plan(self._net, i, ctypes.byref(f)), "ssd_net_train_plan")
+            out[lib.ssd_net_layer_name(self._net, i).decode()] = f.value
+        return out
 
     def get_weights(self):
         lib = _h.lib()

@@ -92,6 +92,8 @@ class PngInfo(ctypes.Structure):
 JPEG_COEFFICIENTS, JPEG_RAW = 0, 1
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
 MOBILENET_V2, VGG16 = 0, 1
+# SSD_PLAN_*: the bits of ssd_net_train_plan
+PLAN_WGRAD, PLAN_WGRAD2, PLAN_DGRAD, PLAN_RESGRAD, PLAN_BN_BATCH, PLAN_BN_PARAMS, PLAN_SKIP = 1, 2, 4, 8, 16, 32, 64
 
 # name -> (restype, argtypes); every symbol include/ssd_hip.h declares.
 _SIGNATURES = {
@@ -233,6 +235,9 @@ _SIGNATURES = {
                                                       vp, vp, vp, vp]),
     "ssd_net_adam_step": (ctypes.c_int, [vp, vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                          ctypes.c_float, vp]),
+    "ssd_net_set_trainable": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_int]),
+    "ssd_net_get_trainable": (ctypes.c_int, [vp, ctypes.c_char_p]),
+    "ssd_net_train_plan": (ctypes.c_int, [vp, ctypes.c_int, c_int_p]),
     "ssd_net_train_steps": (ctypes.c_long, [vp]),
     "ssd_net_train_matrix_flops": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_double)]),
     "ssd_net_train_fetch": (ctypes.c_long, [vp, ctypes.c_char_p, ctypes.c_int, c_float_p, ctypes.c_size_t]),

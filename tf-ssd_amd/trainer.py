@@ -13,7 +13,11 @@ when that year is there, ``shuffle(batch_size * 4)``, then ``data_utils.voc_batc
 decode, one upload and one resize launch per batch, batched augmentation).  Without it the splits are
 seeded synthetic padded batches (``SSD_TRAINER_ITEMS`` training images per epoch, default 512).
 ``SSD_TRAINER_ITEMS`` / ``SSD_TRAINER_EPOCHS`` / ``SSD_TRAINER_STEPS`` / ``SSD_TRAINER_BATCH`` shorten
-a run in both modes (tests, smoke)."""
+a run in both modes (tests, smoke).
+Fine-tuning: ``SSD_TRAINER_LOAD_WEIGHTS=1`` sets the reference's own ``load_weights`` switch (the checkpoint at the
+model path is loaded before training); ``SSD_TRAINER_FREEZE`` (empty by default) freezes layers first: ``backbone``
+(``model.freeze_backbone()``: the backbone with its BatchNorm layers), ``backbone-bn`` (its BatchNorm layers only) or
+comma-separated ``fnmatch`` patterns over the Keras layer names (``model.set_trainable``)."""
 import json
 import os
 import sys
@@ -95,6 +99,17 @@ def fit(model, train_feed, steps_per_epoch, val_feed, validation_steps, epochs, 
     return history
 
 
+def freeze_layers(model, spec):
+    """``SSD_TRAINER_FREEZE``: ``backbone``, ``backbone-bn`` (the backbone's BatchNorm layers only) or comma-separated
+    ``fnmatch`` patterns over the Keras layer names -> the names frozen."""
+    if spec == "backbone":
+        return model.freeze_backbone()
+    if spec == "backbone-bn":
+        bn = set(model.batch_norm_layer_names())
+        return model.set_trainable([n for n in model.backbone_layer_names() if n in bn], False)
+    return model.set_trainable([p.strip() for p in spec.split(",") if p.strip()], False)
+
+
 def main(argv=None):
     args = io_utils.handle_args(argv)
     if args.handle_gpu:
@@ -103,7 +118,7 @@ def main(argv=None):
 
     batch_size = int(os.environ.get("SSD_TRAINER_BATCH", "32"))
     epochs = int(os.environ.get("SSD_TRAINER_EPOCHS", "150"))
-    load_weights = False
+    load_weights = os.environ.get("SSD_TRAINER_LOAD_WEIGHTS", "0") == "1"
     backbone = args.backbone
     io_utils.is_valid_backbone(backbone)
     if backbone == "mobilenet_v2":
@@ -154,6 +169,11 @@ def main(argv=None):
     ssd_model_path = io_utils.get_model_path(backbone)
     if load_weights:
         ssd_model.load_weights(ssd_model_path)
+    freeze = os.environ.get("SSD_TRAINER_FREEZE", "").strip()
+    if freeze:
+        frozen = freeze_layers(ssd_model, freeze)
+        if rank == 0:
+            print("frozen: %d layers (%s)" % (len(frozen), freeze), flush=True)
     ssd_log_path = io_utils.get_log_path(backbone)
     prior_boxes = bbox_utils.generate_prior_boxes(hyper_params["feature_map_shapes"], hyper_params["aspect_ratios"])
     # reference trainer.py:42: the TRAINING stream is augmented (fresh draws every epoch), the validation stream is not.
