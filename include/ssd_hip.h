@@ -1049,6 +1049,43 @@ int ssd_net_train_wait_bucket(ssd_net* net, int k, void* stream);
 int ssd_net_adam_step(ssd_net* net, const float* grads_flat_dev, float lr, float beta1, float beta2,
                       float eps, float grad_scale, void* stream);
 long ssd_net_train_steps(const ssd_net* net);
+/* The optimizers of the reference's trainer (`from tensorflow.keras.optimizers import SGD, Adam`) with the Keras
+ * gradient-clipping arguments, TF 2.x semantics on fp32 state.  g = grads_flat * grad_scale (the averaged gradient;
+ * clipping acts on g):
+ *   SGD (training_ops ApplyKerasMomentum): accum = momentum * accum - lr * g; var += accum, with nesterov
+ *     var += momentum * accum - lr * g; momentum == 0: var -= lr * g, no accumulator is read or written.  The
+ *     accumulator is the slot "m"; "v" is left alone.
+ *   Adam: ssd_net_adam_step's arithmetic on the clipped g.
+ *   clipnorm c (tf.clip_by_norm per Keras variable = entry of the parameter table; the label and the box kernel of a
+ *     fused head conv are two): s = sum(g * g), norm = s > 0 ? sqrt(s) : s, g = (g * c) / max(norm, c).
+ *   global_clipnorm c (tf.clip_by_global_norm over all trainable variables): gn = sqrt(sum of all s),
+ *     g *= c * min(1 / gn, 1 / c).  Excludes clipnorm.
+ *   clipvalue c: g = min(max(g, -c), c), after the norm clip when both are set.
+ * Frozen variables (ssd_net_set_trainable) are not read, not written and not counted in any norm.
+ * Launches: one (the update over the table of trainable segments) without norm clipping, three with it (per-segment
+ * sums of squares in a fixed tree, per-variable sums of those in table order in double, the update); no atomics, the
+ * same inputs give the same bits in every run.  Adam with every clip off issues ssd_net_adam_step's own launch.
+ * The state remembers which kind wrote the slots: a step of another kind (ssd_net_adam_step included) while the step
+ * counter is non-zero returns SSD_E_STATE -- call ssd_net_optimizer_reset (slots = 0, step counter = 0; a no-op before
+ * ssd_net_train_begin).  SSD_E_INVALID, nothing launched: NULL pointers, an unknown kind, momentum outside [0, 1], a
+ * beta outside [0, 1), clipnorm and global_clipnorm both > 0, an unknown slot, a wrong count.
+ * The slots ("m" | "v") are flat vectors in ssd_net_trainable_offset order; get returns the count (host_out NULL:
+ * query).  ssd_net_train_set_steps sets the step counter (restoring a saved state). */
+#define SSD_OPT_ADAM 0
+#define SSD_OPT_SGD 1
+typedef struct ssd_optimizer {
+    int kind;
+    float beta1, beta2, eps;                     /* Adam */
+    float momentum;
+    int nesterov;                                /* SGD  */
+    float clipnorm, clipvalue, global_clipnorm;  /* <= 0: off */
+} ssd_optimizer;
+int ssd_net_optimizer_step(ssd_net* net, const float* grads_flat_dev, const ssd_optimizer* opt, float lr,
+                           float grad_scale, void* stream);
+int ssd_net_optimizer_reset(ssd_net* net);
+long ssd_net_optimizer_get_state(ssd_net* net, const char* slot, float* host_out, size_t cap);
+int ssd_net_optimizer_set_state(ssd_net* net, const char* slot, const float* host_in, size_t count);
+int ssd_net_train_set_steps(ssd_net* net, long steps);
 /* Measurement: matrix-core FLOPs the last ssd_net_train_forward_backward issued, per instruction family --
  * out3[0] conv forward + backward-data on fp32-MFMA tiles, out3[1] the same on split-bf16 tiles (six bf16 MFMAs per
  * fp32 product), out3[2] weight gradients (fp32 MFMA).  bench.py --train prices each family at its own peak. */

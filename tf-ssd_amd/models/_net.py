@@ -458,10 +458,18 @@ class SSDModel(object):
     def compile(self, optimizer=None, loss=None, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7,
                 neg_pos_ratio=None, loc_loss_alpha=None):
         """Keras ``Model.compile(optimizer=Adam(learning_rate=1e-3), loss=[loc, conf])`` (reference
-        trainer.py:52-53).  The optimiser is always Adam (the reference's choice) with the Keras
-        defaults; ``loss`` may be the two bound methods of a ``CustomLoss`` (its ratio / alpha are
-        then used)."""
-        self._adam = dict(lr=float(learning_rate), b1=float(beta_1), b2=float(beta_2), eps=float(epsilon))
+        trainer.py:52-53).  ``optimizer``: an ``optimizers.SGD`` / ``optimizers.Adam`` instance, ``"sgd"`` / ``"adam"``
+        (Keras defaults), or None -- Adam (the reference's choice) from ``learning_rate`` / ``beta_1`` / ``beta_2`` /
+        ``epsilon``; anything else raises TypeError.  An optimizer of another kind than the one whose slots the net
+        holds starts from fresh slots and iteration 0 (Keras' new optimizer at ``compile()``); the same kind keeps them.
+        ``loss`` may be the two bound methods of a ``CustomLoss`` (its ratio / alpha are then used)."""
+        import optimizers
+        opt = optimizers.get(optimizer, learning_rate=learning_rate, beta_1=beta_1, beta_2=beta_2, epsilon=epsilon)
+        previous = getattr(self, "_optimizer", None)
+        if previous is not None and previous.kind != opt.kind:
+            _h.check(_h.lib().ssd_net_optimizer_reset(self._net), "ssd_net_optimizer_reset")
+        self._optimizer = opt
+        self._native_optimizer = opt.to_native()
         owner = getattr(loss[0], "__self__", None) if loss else None
         self._neg_pos_ratio = float(neg_pos_ratio if neg_pos_ratio is not None else
                                     getattr(owner, "neg_pos_ratio", self.hyper_params.get("neg_pos_ratio", 3)))
@@ -481,7 +489,7 @@ class SSDModel(object):
     def forward_backward(self, images, actual_deltas, actual_labels):
         """Training-mode forward + loss + backward.  Returns (loc_loss [B], conf_loss [B],
         grads_flat) as device tensors; ``grads_flat`` is what data-parallel ranks all-reduce."""
-        if not hasattr(self, "_adam"):
+        if not hasattr(self, "_optimizer"):
             self.compile()
         if not self._weights_set:
             raise RuntimeError("model has no weights: call set_weights()/load_weights() first")
@@ -508,12 +516,91 @@ class SSDModel(object):
         return loc, conf, self._grads
 
     def apply_gradients(self, grads_flat, learning_rate=None, grad_scale=1.0):
-        a = self._adam
-        lr = a["lr"] if learning_rate is None else float(learning_rate)
-        _h.check(_h.lib().ssd_net_adam_step(self._net, _h.ptr(grads_flat), lr, a["b1"], a["b2"], a["eps"],
-                                            float(grad_scale), _h.stream()), "ssd_net_adam_step")
+        """One step of the compiled optimizer (``ssd_net_optimizer_step``) from the flat gradient; ``learning_rate``
+        overrides the optimizer's own for this step (the trainer's LearningRateScheduler)."""
+        lr = self._optimizer.learning_rate if learning_rate is None else float(learning_rate)
+        _h.check(_h.lib().ssd_net_optimizer_step(self._net, _h.ptr(grads_flat), ctypes.byref(self._native_optimizer), lr,
+                                                 float(grad_scale), _h.stream()), "ssd_net_optimizer_step")
         self._finalized_for = 0          # inference weights (folded BN, packed) are stale now
         self._weights_version += 1
+
+    # ------------------------------------------------------------------ optimizer state (resuming a run)
+    def _optimizer_slot(self, slot):
+        lib = _h.lib()
+        a = np.empty((lib.ssd_net_trainable_floats(self._net),), np.float32)
+        n = lib.ssd_net_optimizer_get_state(self._net, slot.encode(), a.ctypes.data_as(_h.c_float_p), a.size)
+        if n < 0:
+            _h.check(int(n), "ssd_net_optimizer_get_state")
+        return a
+
+    def get_optimizer_state(self):
+        """``{"kind": "sgd" | "adam", "iterations": steps so far, "slots": {parameter name: {slot: array}}}`` with the slots
+        of the compiled optimizer in the parameter's shape: Adam ``m`` and ``v``, SGD ``momentum`` (its accumulator)."""
+        if not hasattr(self, "_optimizer"):
+            self.compile()
+        opt = self._optimizer
+        flat = {s: self._optimizer_slot("m" if s == "momentum" else s) for s in opt.slots}
+        slots = {}
+        for name, (off, shape) in self.trainable_offsets().items():
+            n = int(np.prod(shape))
+            slots[name] = {s: flat[s][off:off + n].reshape(shape).copy() for s in opt.slots}
+        return {"kind": opt.name, "iterations": int(_h.lib().ssd_net_train_steps(self._net)), "slots": slots}
+
+    def set_optimizer_state(self, state):
+        """Restores what ``get_optimizer_state`` returned, for the compiled optimizer's kind (ValueError for another, for
+        unknown or missing parameters and for wrong shapes).  Slots the kind does not use are cleared."""
+        if not hasattr(self, "_optimizer"):
+            self.compile()
+        opt = self._optimizer
+        if state.get("kind") != opt.name:
+            raise ValueError("the state is %r's, the model is compiled with %r" % (state.get("kind"), opt.name))
+        offs = self.trainable_offsets()
+        if set(state["slots"]) != set(offs):
+            odd = sorted(set(state["slots"]) ^ set(offs))
+            raise ValueError("the state's parameters do not match the model's trainable ones (e.g. %s)" % odd[:2])
+        lib = _h.lib()
+        flat = {s: np.zeros((lib.ssd_net_trainable_floats(self._net),), np.float32) for s in opt.slots}
+        for name, (off, shape) in offs.items():
+            for s in opt.slots:
+                a = np.asarray(state["slots"][name][s], np.float32)
+                if tuple(a.shape) != tuple(shape):
+                    raise ValueError("slot %r of %r has shape %s, expected %s" % (s, name, a.shape, shape))
+                flat[s][off:off + a.size] = a.ravel()
+        iterations = int(state["iterations"])
+        if iterations < 0:
+            raise ValueError("iterations must be >= 0, got %d" % iterations)
+        if getattr(self, "_train_batch", 0) < 1:
+            if not self._weights_set:
+                raise RuntimeError("model has no weights: call set_weights()/load_weights() first")
+            _h.device()
+            _h.check(lib.ssd_net_train_begin(self._net, 1), "ssd_net_train_begin")
+            self._train_batch = 1
+            self._finalized_for = 0
+            self._bucket_starts = None
+        _h.check(lib.ssd_net_optimizer_reset(self._net), "ssd_net_optimizer_reset")
+        for s, a in flat.items():
+            _h.check(lib.ssd_net_optimizer_set_state(self._net, ("m" if s == "momentum" else s).encode(),
+                                                     a.ctypes.data_as(_h.c_float_p), a.size), "ssd_net_optimizer_set_state")
+        _h.check(lib.ssd_net_train_set_steps(self._net, iterations), "ssd_net_train_set_steps")
+
+    def save_optimizer_state(self, path):
+        """The optimizer state as a NumPy ``.npz``: ``kind``, ``iterations`` and one array per ``<parameter>:<slot>``."""
+        st = self.get_optimizer_state()
+        arrays = {"kind": np.array(st["kind"]), "iterations": np.array(st["iterations"], np.int64)}
+        for name, slots in st["slots"].items():
+            for s, a in slots.items():
+                arrays["%s:%s" % (name, s)] = a
+        with open(path, "wb") as f:
+            np.savez(f, **arrays)
+
+    def load_optimizer_state(self, path):
+        with np.load(path) as z:
+            st = {"kind": str(z["kind"]), "iterations": int(z["iterations"]), "slots": {}}
+            for key in z.files:
+                if ":" in key:
+                    name, s = key.rsplit(":", 1)
+                    st["slots"].setdefault(name, {})[s] = z[key]
+        self.set_optimizer_state(st)
 
     def train_on_batch(self, images, targets, learning_rate=None):
         """Keras ``Model.train_on_batch``: one optimisation step; with torch.distributed

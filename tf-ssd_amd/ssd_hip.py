@@ -89,9 +89,17 @@ class PngInfo(ctypes.Structure):
         ("palette", ctypes.c_ubyte * 768)]
 
 
+class Optimizer(ctypes.Structure):
+    """struct ssd_optimizer (include/ssd_hip.h): what ``ssd_net_optimizer_step`` applies."""
+    _fields_ = [("kind", ctypes.c_int), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
+                ("momentum", ctypes.c_float), ("nesterov", ctypes.c_int), ("clipnorm", ctypes.c_float),
+                ("clipvalue", ctypes.c_float), ("global_clipnorm", ctypes.c_float)]
+
+
 JPEG_COEFFICIENTS, JPEG_RAW = 0, 1
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
 MOBILENET_V2, VGG16 = 0, 1
+OPT_ADAM, OPT_SGD = 0, 1
 # SSD_PLAN_*: the bits of ssd_net_train_plan
 PLAN_WGRAD, PLAN_WGRAD2, PLAN_DGRAD, PLAN_RESGRAD, PLAN_BN_BATCH, PLAN_BN_PARAMS, PLAN_SKIP = 1, 2, 4, 8, 16, 32, 64
 
@@ -235,6 +243,11 @@ _SIGNATURES = {
                                                       vp, vp, vp, vp]),
     "ssd_net_adam_step": (ctypes.c_int, [vp, vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                          ctypes.c_float, vp]),
+    "ssd_net_optimizer_step": (ctypes.c_int, [vp, vp, ctypes.POINTER(Optimizer), ctypes.c_float, ctypes.c_float, vp]),
+    "ssd_net_optimizer_reset": (ctypes.c_int, [vp]),
+    "ssd_net_optimizer_get_state": (ctypes.c_long, [vp, ctypes.c_char_p, c_float_p, ctypes.c_size_t]),
+    "ssd_net_optimizer_set_state": (ctypes.c_int, [vp, ctypes.c_char_p, c_float_p, ctypes.c_size_t]),
+    "ssd_net_train_set_steps": (ctypes.c_int, [vp, ctypes.c_long]),
     "ssd_net_set_trainable": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_int]),
     "ssd_net_get_trainable": (ctypes.c_int, [vp, ctypes.c_char_p]),
     "ssd_net_train_plan": (ctypes.c_int, [vp, ctypes.c_int, c_int_p]),

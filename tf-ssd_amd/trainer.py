@@ -17,7 +17,10 @@ a run in both modes (tests, smoke).
 Fine-tuning: ``SSD_TRAINER_LOAD_WEIGHTS=1`` sets the reference's own ``load_weights`` switch (the checkpoint at the
 model path is loaded before training); ``SSD_TRAINER_FREEZE`` (empty by default) freezes layers first: ``backbone``
 (``model.freeze_backbone()``: the backbone with its BatchNorm layers), ``backbone-bn`` (its BatchNorm layers only) or
-comma-separated ``fnmatch`` patterns over the Keras layer names (``model.set_trainable``)."""
+comma-separated ``fnmatch`` patterns over the Keras layer names (``model.set_trainable``).
+Optimizer: ``SSD_TRAINER_OPTIMIZER`` (``adam`` | ``sgd``), ``SSD_TRAINER_MOMENTUM``, ``SSD_TRAINER_NESTEROV``,
+``SSD_TRAINER_CLIPNORM``, ``SSD_TRAINER_CLIPVALUE``, ``SSD_TRAINER_GLOBAL_CLIPNORM`` (``optimizer_from_env``); with none
+of them set the run is the reference's ``Adam(1e-3)``."""
 import json
 import os
 import sys
@@ -110,6 +113,27 @@ def freeze_layers(model, spec):
     return model.set_trainable([p.strip() for p in spec.split(",") if p.strip()], False)
 
 
+def optimizer_from_env():
+    """``SSD_TRAINER_OPTIMIZER`` = ``adam`` (default) | ``sgd``, ``SSD_TRAINER_MOMENTUM`` (sgd: default 0.9, SSD's classic
+    setting), ``SSD_TRAINER_NESTEROV=1``, ``SSD_TRAINER_CLIPNORM`` / ``SSD_TRAINER_CLIPVALUE`` /
+    ``SSD_TRAINER_GLOBAL_CLIPNORM`` -> an ``optimizers`` instance at the reference's rate 1e-3 (the LearningRateScheduler
+    sets the rate of every epoch anyway), or None when none of them is set: the run is then the reference's Adam."""
+    import optimizers
+    env = os.environ
+    names = ("OPTIMIZER", "MOMENTUM", "NESTEROV", "CLIPNORM", "CLIPVALUE", "GLOBAL_CLIPNORM")
+    if not any(env.get("SSD_TRAINER_" + n, "").strip() for n in names):
+        return None
+    kind = env.get("SSD_TRAINER_OPTIMIZER", "adam").strip().lower() or "adam"
+    clips = {k.lower(): float(env["SSD_TRAINER_" + k]) for k in ("CLIPNORM", "CLIPVALUE", "GLOBAL_CLIPNORM")
+             if env.get("SSD_TRAINER_" + k, "").strip()}
+    if kind == "adam":
+        return optimizers.Adam(learning_rate=1e-3, **clips)
+    if kind == "sgd":
+        return optimizers.SGD(learning_rate=1e-3, momentum=float(env.get("SSD_TRAINER_MOMENTUM", "").strip() or 0.9),
+                              nesterov=env.get("SSD_TRAINER_NESTEROV", "0").strip() == "1", **clips)
+    raise ValueError("SSD_TRAINER_OPTIMIZER must be 'adam' or 'sgd', got %r" % kind)
+
+
 def main(argv=None):
     args = io_utils.handle_args(argv)
     if args.handle_gpu:
@@ -164,7 +188,10 @@ def main(argv=None):
 
     ssd_model = get_model(hyper_params, max_batch=batch_size)
     ssd_custom_losses = CustomLoss(hyper_params["neg_pos_ratio"], hyper_params["loc_loss_alpha"])
-    ssd_model.compile(learning_rate=1e-3, loss=[ssd_custom_losses.loc_loss_fn, ssd_custom_losses.conf_loss_fn])
+    optimizer = optimizer_from_env()
+    ssd_model.compile(optimizer=optimizer, learning_rate=1e-3, loss=[ssd_custom_losses.loc_loss_fn, ssd_custom_losses.conf_loss_fn])
+    if optimizer is not None and rank == 0:
+        print("optimizer: %r" % (optimizer,), flush=True)
     init_model(ssd_model)
     ssd_model_path = io_utils.get_model_path(backbone)
     if load_weights:
