@@ -1045,7 +1045,14 @@ int ssd_net_train_forward_backward(ssd_net* net, const float* image_dev, int B,
 int ssd_net_train_set_buckets(ssd_net* net, int n, const long* lo);
 int ssd_net_train_wait_bucket(ssd_net* net, int k, void* stream);
 /* Adam (Keras defaults beta1 0.9, beta2 0.999, eps 1e-7; TF ApplyAdam form) on every trainable
- * parameter; grads are multiplied by grad_scale first (1/world_size after a SUM all-reduce). */
+ * parameter; grads are multiplied by grad_scale first (1/world_size after a SUM all-reduce).
+ * This is ssd_net_optimizer_step (below) with kind = SSD_OPT_ADAM and every clip off, under an older signature: the
+ * same launch, the same checks in the same order, the same return codes.  So a beta1 or beta2 outside [0, 1) is
+ * refused with SSD_E_INVALID (it used to go through and give a NaN step length).
+ * The update's roundings are fixed in the source: g = grad * grad_scale is rounded before g - m, and
+ * m + (g - m)(1 - beta1) takes three roundings.  With grad_scale == 1 and nothing frozen or clipped these are the bits
+ * this call always gave; with grad_scale != 1 (the data-parallel step), frozen layers or a clip, m and var can differ
+ * in the last bit from what earlier builds gave, which fused some of these operations depending on the kernel. */
 int ssd_net_adam_step(ssd_net* net, const float* grads_flat_dev, float lr, float beta1, float beta2,
                       float eps, float grad_scale, void* stream);
 long ssd_net_train_steps(const ssd_net* net);
@@ -1055,7 +1062,8 @@ long ssd_net_train_steps(const ssd_net* net);
  *   SGD (training_ops ApplyKerasMomentum): accum = momentum * accum - lr * g; var += accum, with nesterov
  *     var += momentum * accum - lr * g; momentum == 0: var -= lr * g, no accumulator is read or written.  The
  *     accumulator is the slot "m"; "v" is left alone.
- *   Adam: ssd_net_adam_step's arithmetic on the clipped g.
+ *   Adam (training_ops ApplyAdam): m += (g - m)(1 - beta1); v += (g * g - v)(1 - beta2);
+ *     var -= lr * sqrt(1 - beta2^t) / (1 - beta1^t) * m / (sqrt(v) + eps), t the step counter after this step.
  *   clipnorm c (tf.clip_by_norm per Keras variable = entry of the parameter table; the label and the box kernel of a
  *     fused head conv are two): s = sum(g * g), norm = s > 0 ? sqrt(s) : s, g = (g * c) / max(norm, c).
  *   global_clipnorm c (tf.clip_by_global_norm over all trainable variables): gn = sqrt(sum of all s),
@@ -1064,7 +1072,9 @@ long ssd_net_train_steps(const ssd_net* net);
  * Frozen variables (ssd_net_set_trainable) are not read, not written and not counted in any norm.
  * Launches: one (the update over the table of trainable segments) without norm clipping, three with it (per-segment
  * sums of squares in a fixed tree, per-variable sums of those in table order in double, the update); no atomics, the
- * same inputs give the same bits in every run.  Adam with every clip off issues ssd_net_adam_step's own launch.
+ * same inputs give the same bits in every run.  Every setting is an instantiation of the one update kernel over the one
+ * table, Adam with every clip off (ssd_net_adam_step) included: what a step does to an element does not depend on what
+ * else is trainable.
  * The state remembers which kind wrote the slots: a step of another kind (ssd_net_adam_step included) while the step
  * counter is non-zero returns SSD_E_STATE -- call ssd_net_optimizer_reset (slots = 0, step counter = 0; a no-op before
  * ssd_net_train_begin).  SSD_E_INVALID, nothing launched: NULL pointers, an unknown kind, momentum outside [0, 1], a
@@ -1098,7 +1108,7 @@ int ssd_net_regularization_loss(ssd_net* net, float* host_out);
 /* Fine-tuning: Keras' `layer.trainable = False`, by KERAS LAYER NAME -- a parameter name up to its last '/':
  * "Conv1", "bn_Conv1", "block_3_depthwise_BN", "extra2_1", "4_conv_boxes_output", "l2_normalization".  A conv and its
  * BatchNorm are two Keras layers and freeze independently, as do the label and the box conv of one head level.  By
- * default every layer is trainable and the step is the one it always was (same launches, same bits).  Both calls work
+ * default every layer is trainable and the step is the one it always was (same bits).  Both calls work
  * before and after ssd_net_train_begin, need no device, and take effect at the next ssd_net_train_forward_backward /
  * ssd_net_adam_step.  Unknown name: SSD_E_INVALID (get: too).
  *   frozen kernel / bias / L2-norm scale: no gradient is computed, its range of grads_flat holds exactly 0.0f after
@@ -1108,9 +1118,10 @@ int ssd_net_regularization_loss(ssd_net* net, float* host_out);
  *   pruning: a tensor needs a gradient only if a trainable parameter lies upstream of it; no data gradient and no
  *     residual add go into a tensor that needs none, a layer without trainable parameters whose inputs need none is
  *     left out of the backward altogether (ssd_net_train_plan);
- *   ssd_net_adam_step leaves var, m and v of frozen ranges bitwise untouched (still one launch); the step counter stays
- *     global.  Unlike Keras -- which rebuilds the optimizer at the compile() that must follow a change of `trainable` --
- *     the moments of a layer that is unfrozen later continue from where they were.
+ *   the optimizer step leaves var, m and v of frozen ranges bitwise untouched (they are in no segment of its table: the
+ *     same launches, the same bits for every element that stays trainable); the step counter stays global.  Unlike
+ *     Keras -- which rebuilds the optimizer at the compile() that must follow a change of `trainable` -- the moments
+ *     of a layer that is unfrozen later continue from where they were.
  * ssd_net_regularization_loss is unchanged: Keras keeps the regularisation term of frozen kernels in `loss`. */
 int ssd_net_set_trainable(ssd_net* net, const char* keras_layer, int trainable);
 int ssd_net_get_trainable(const ssd_net* net, const char* keras_layer);   /* 1 / 0, SSD_E_INVALID: unknown name */

@@ -1,7 +1,7 @@
 """Diagnostics script (not a test): the time of the optimizer step alone (``ssd_net_optimizer_step``) on the flat trainable
 vector of SSD300-MobileNetV2 and SSD300-VGG16 (21 labels), one GPU, a resident synthetic gradient, no forward pass.
 
-Settings: Adam (``ssd_net_adam_step``'s launch), SGD plain, SGD with momentum, SGD with momentum + ``clipnorm``, SGD with
+Settings: Adam (no clip: what ``ssd_net_adam_step`` and ``compile()``'s default run), SGD plain, SGD with momentum, SGD with momentum + ``clipnorm``, SGD with
 momentum + ``global_clipnorm``, SGD with momentum under ``freeze_backbone()``.  The settings alternate inside one process,
 round after round; after every change three untimed steps run; every timed window is >= --seconds of back-to-back steps
 closed by ONE synchronise.  Reported: median of --rounds windows with min .. max, and the achieved bytes per second against

@@ -125,6 +125,26 @@ def test_abi_refuses_bad_arguments_before_any_launch(model):
     assert lib.ssd_net_train_set_steps(net, 3) == -4 and lib.ssd_net_train_steps(net) == 0
 
 
+def test_adam_step_is_the_optimizer_step_under_another_signature(model):
+    """``ssd_net_adam_step`` fills an ``ssd_optimizer`` and calls ``ssd_net_optimizer_step``, so its checks are that function's,
+    in that function's order: NULL arguments, then the betas, then the training state.  A net that has its training state
+    and a bad beta needs a device; what is reachable here is the order: a NULL net or gradient returns -1, a beta outside
+    [0, 1) returns -1 although this net has no training state (the beta check does not sit behind the state check, it comes
+    first), and good arguments get as far as the state check (-4)."""
+    import ssd_hip as h
+    lib, net = h.lib(), model._net
+    buf = (ctypes.c_float * 4)()
+    g = ctypes.cast(buf, ctypes.c_void_p)
+
+    def step(net=net, g=g, b1=0.9, b2=0.999):
+        return lib.ssd_net_adam_step(net, g, 1e-3, b1, b2, 1e-7, 1.0, None)
+    assert step(net=None) == -1 and step(g=None) == -1 and step(net=None, g=None) == -1
+    for bad in (dict(b1=1.0), dict(b1=-0.1), dict(b2=1.0), dict(b2=-0.1), dict(b1=float("nan"))):
+        assert step(**bad) == -1, bad
+        assert b"[0, 1)" in lib.ssd_last_error()
+    assert step() == -4 and step(b1=0.0, b2=0.0) == -4
+
+
 # ---------------------------------------------------------------------------------------------- the trainer's switches
 def test_trainer_reads_the_environment(monkeypatch):
     import optimizers

@@ -1,4 +1,4 @@
-"""Keras SGD / Adam with gradient clipping on the device (csrc/ssd_train.hip, ssd_net_optimizer_step) against the float64
+"""Keras SGD / Adam with gradient clipping on the device (csrc/ssd_optim.hip, ssd_net_optimizer_step) against the float64
 restatement of tests/optimizer_cases.py.  Shaped like tests/test_finetune_gpu.py::test_adam_leaves_frozen_parameters_alone:
 the full 300 x 300 MobileNetV2 net, ``ssd_net_train_begin(net, 1)``, synthetic gradients handed to ``apply_gradients``, no
 forward pass (but for the public-path and the trainer test).  ONE model instance serves every case: each case puts the
@@ -229,6 +229,62 @@ def test_unclipped_adam_is_ssd_net_adam_step_bit_for_bit(ctx, freeze):
         if _layer(n) in frozen:
             np.testing.assert_array_equal(new_w[n].view(np.uint32), ctx["w0"][n].view(np.uint32), err_msg=n)
     assert changed > 10 and (not freeze or changed < len(ctx["offs"]) - 100)
+
+
+def test_a_trainable_elements_update_does_not_depend_on_the_table(ctx):
+    """Two unclipped Adam steps with everything trainable, then from the same start under ``freeze_backbone()``: the table
+    of segments differs (the frozen variables have none), what happens to an element that is in both does not.  Every
+    variable trainable in both runs has the same bits in var, m and v; a frozen one keeps its initial bits and zero slots."""
+    import optimizers as o
+    runs = []
+    for freeze in (False, True):
+        m, frozen = _fresh(ctx, o.Adam(LR), freeze)
+        for gd in ctx["gd"]:
+            m.apply_gradients(gd)
+        st = m.get_optimizer_state()
+        assert st["iterations"] == 2
+        runs.append((m.get_weights(), st["slots"]))
+    m.set_trainable("*", True)
+    (all_w, all_s), (fr_w, fr_s) = runs
+    live = [n for n in ctx["offs"] if _layer(n) not in frozen]
+    assert len(frozen) == 104 and 0 < len(live) < len(ctx["offs"])
+    for n in ctx["offs"]:
+        if n in live:
+            np.testing.assert_array_equal(fr_w[n].view(np.uint32), all_w[n].view(np.uint32), err_msg=n)
+            for s in ("m", "v"):
+                np.testing.assert_array_equal(fr_s[n][s].view(np.uint32), all_s[n][s].view(np.uint32), err_msg="%s:%s" % (n, s))
+        else:
+            np.testing.assert_array_equal(fr_w[n].view(np.uint32), ctx["w0"][n].view(np.uint32), err_msg=n)
+            assert not fr_s[n]["m"].any() and not fr_s[n]["v"].any(), n
+    assert sum(int((all_w[n] != ctx["w0"][n]).any()) for n in live) > 10
+
+
+def test_the_scalar_and_the_16_byte_path_give_the_same_bits(ctx):
+    """Two unclipped Adam steps at grad_scale 0.5 from a gradient buffer that is 16-byte aligned (head, 16-byte body and tail
+    loops) and from the same values 4 bytes further on (every element through the scalar loop): the same bits in var, m and v.
+    Adam's roundings are spelled out in the source, so they do not depend on the loop an element goes through."""
+    import optimizers as o
+    P = ctx["P"]
+    runs = []
+    for shift in (0, 1):
+        m, _ = _fresh(ctx, o.Adam(LR))
+        for gd in ctx["gd"]:
+            buf = torch.empty(P + 4, dtype=torch.float32, device=gd.device)
+            base = (-(buf.data_ptr() // 4)) % 4                  # first element of buf on a 16-byte boundary
+            g = buf[base + shift:base + shift + P]
+            g.copy_(gd)
+            assert g.data_ptr() % 16 == 4 * shift
+            m.apply_gradients(g, grad_scale=0.5)
+        torch.cuda.synchronize()
+        st = m.get_optimizer_state()
+        assert st["iterations"] == 2
+        runs.append((m.get_weights(), st["slots"]))
+    (a_w, a_s), (u_w, u_s) = runs
+    for n in ctx["offs"]:
+        np.testing.assert_array_equal(u_w[n].view(np.uint32), a_w[n].view(np.uint32), err_msg=n)
+        for s in ("m", "v"):
+            np.testing.assert_array_equal(u_s[n][s].view(np.uint32), a_s[n][s].view(np.uint32), err_msg="%s:%s" % (n, s))
+    assert sum(int((a_w[n] != ctx["w0"][n]).any()) for n in ctx["offs"]) > 100
 
 
 # ---------------------------------------------------------------------------------------------- frozen ranges

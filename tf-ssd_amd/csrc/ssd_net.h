@@ -8,7 +8,7 @@
 
 #include "ssd_conv.h"
 
-struct ssd_train_state;      // csrc/ssd_train.hip
+struct ssd_train_state;      // csrc/ssd_train.h
 void ssd_train_state_free(ssd_train_state*);
 
 namespace ssd {
@@ -198,7 +198,7 @@ struct ssd_net {
     std::vector<ssd::Step> steps;       // the forward's launch plan (empty: not built for the current state)
     float* splitk_layers = nullptr;     // per-layer split-K slabs (post-autotune)
     bool timing = false;                // optional per-layer hipEvent timing of forward()/predict() (bench.py roofline leg)
-    ssd_train_state* train = nullptr;    // training step state (csrc/ssd_train.hip), lazily created
+    ssd_train_state* train = nullptr;    // training step state (csrc/ssd_train.h), lazily created
     // fine-tuning: Keras layer names (a parameter name up to its last '/') whose `trainable` is False; trainable_rev counts
     // the changes (the training step re-plans its backward when it lags behind: ssd_net_set_trainable, csrc/ssd_train.hip)
     std::set<std::string> frozen;

@@ -1,6 +1,7 @@
 // Training step of the SSD graphs (reference trainer.py:50-76):
 // training-mode forward (BatchNorm on batch statistics, moving averages updated with Keras'
-// momentum 0.999), the HIP loss (csrc/ssd_loss.hip), backward of every layer and Adam.
+// momentum 0.999), the HIP loss (csrc/ssd_loss.hip) and backward of every layer; the optimizer
+// that follows is csrc/ssd_optim.hip.
 //
 //   conv backward-data   = the forward MFMA implicit-GEMM kernel (conv_mfma_kernel) on dY with the
 //                          180-degree-rotated, in/out-transposed weights; stride-2 3x3 convs go
@@ -9,10 +10,9 @@
 //                          v_mfma_f32_16x16x4_f32, M split over the grid, deterministic two-stage sum;
 //   depthwise backward   = gather kernels (HBM-bound);
 //   BatchNorm            = two-pass batch statistics and the usual two-reduction backward, all
-//                          reductions deterministic (fixed chunking, fixed order);
-//   Adam                 = one fused kernel over the flat parameter / moment / gradient buffers.
+//                          reductions deterministic (fixed chunking, fixed order).
 // Gradients leave through a caller-owned flat buffer (parameter-table order), which is what the
-// host all-reduces over RCCL between backward and the Adam step.
+// host all-reduces over RCCL between backward and the optimizer step.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -20,7 +20,7 @@
 #include <mutex>
 
 #include "ssd_bf16x3.h"
-#include "ssd_net.h"
+#include "ssd_train.h"
 
 using namespace ssd;
 
@@ -891,302 +891,14 @@ __global__ __launch_bounds__(256) void axpy_kernel(float* __restrict__ g, const 
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) g[e] += coef * w[e];
 }
 
-// partial[blockIdx.x] = sum of w^2 over this block's grid-stride slice (fixed slices, fixed in-block tree:
-// deterministic); reg_finalize sums the partials in order and applies the l2 factor
-__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ w, const long n, float* __restrict__ partial) {
-    __shared__ float sh[256];
-    float s = 0.f;
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) s += w[e] * w[e];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
-}
-__global__ void reg_finalize_kernel(const float* __restrict__ partial, const int n, const float l2, float* out) {
-    double s = 0.0;
-    for (int i = 0; i < n; ++i) s += (double)partial[i];
-    *out = (float)(s * (double)l2);
-}
-
-// ------------------------------------------------------------------ Adam (TF training_ops.ApplyAdam form)
-// m += (g - m)(1 - b1); v += (g^2 - v)(1 - b2); var -= alpha * m / (sqrt(v) + eps),
-// alpha = lr * sqrt(1 - b2^t) / (1 - b1^t); g = grad * grad_scale (the l2 regulariser's gradient is already part of
-// grad: bwd_dense_wgrad adds it behind the layer's weight gradient)
-__device__ __forceinline__ void adam_update(float* __restrict__ var, float* __restrict__ m, float* __restrict__ v,
-                                            const float* __restrict__ grad, const long e, const float alpha, const float b1,
-                                            const float b2, const float eps, const float grad_scale) {
-    const float g = grad[e] * grad_scale;
-    const float mm = m[e] + (g - m[e]) * (1.0f - b1);
-    const float vv = v[e] + (g * g - v[e]) * (1.0f - b2);
-    m[e] = mm;
-    v[e] = vv;
-    var[e] -= alpha * mm / (sqrtf(vv) + eps);
-}
-// The same update over the TRAINABLE part of the flat vector while layers are frozen (ssd_net_set_trainable): the
-// trainable ranges, cut into segments of at most kAdamSeg elements, lie in a table in device memory; a workgroup takes
-// whole segments, so var / m / v / grad of a frozen range are not even read.  One launch however many ranges there are
-// (freezing every BatchNorm leaves ~100 disjoint ones).
-constexpr long kAdamSeg = 4096;
-struct AdamSeg {
-    long lo, n;
-};
-__global__ __launch_bounds__(256) void adam_ranges_kernel(float* __restrict__ var, float* __restrict__ m, float* __restrict__ v,
-                                                         const float* __restrict__ grad, const AdamSeg* __restrict__ segs,
-                                                         const int nseg, const float alpha, const float b1, const float b2,
-                                                         const float eps, const float grad_scale) {
-    for (int s = blockIdx.x; s < nseg; s += gridDim.x) {
-        const AdamSeg sg = segs[s];
-        for (long e = sg.lo + threadIdx.x; e < sg.lo + sg.n; e += 256) adam_update(var, m, v, grad, e, alpha, b1, b2, eps, grad_scale);
-    }
-}
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ var, float* __restrict__ m, float* __restrict__ v,
-                                                  const float* __restrict__ grad, const long n, const float alpha,
-                                                  const float b1, const float b2, const float eps,
-                                                  const float grad_scale) {
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
-        const float g = grad[e] * grad_scale;
-        const float mm = m[e] + (g - m[e]) * (1.0f - b1);
-        const float vv = v[e] + (g * g - v[e]) * (1.0f - b2);
-        m[e] = mm;
-        v[e] = vv;
-        var[e] -= alpha * mm / (sqrtf(vv) + eps);
-    }
-}
-
 static inline int grid_for(long total) {
     const long b = (total + 255) / 256;
     return (int)(b < 1 ? 1 : (b > 16384 ? 16384 : b));
 }
 
-// ------------------------------------------------------------------ SGD and the Keras gradient clips (ssd_net_optimizer_step)
-// These walk a second table over the same trainable ranges: a segment never crosses a Keras variable (an entry of the
-// parameter table) and names it, so tf.clip_by_norm has its per-variable sum and the update its per-variable scale.
-// Streaming kernels: per element SGD without momentum moves 12 B (grad in, var in and out), with momentum 20 B, Adam
-// 28 B; the norm pass reads grad once more (4 B).  A segment starts at its variable's offset, which is not always a
-// multiple of 4 floats (the 126 label biases of a 21-label head push what follows 8 bytes off): the head of a segment
-// up to the next 16-byte boundary and its tail go element by element, the body in 16-byte accesses.
-struct OptSeg {
-    long lo;
-    int n, var;      // var: the variable's index among the trainable parameters (table order)
-};
-struct OptVar {
-    int seg0, nseg;  // the variable's segments in the table (nseg 0: frozen)
-};
-enum { kClipNorm = 1, kClipGlobal = 2, kClipValue = 4 };
-constexpr int kOptMaxVars = 2048;
-struct OptArgs {
-    float lr;        // Adam: alpha = lr * sqrt(1 - b2^t) / (1 - b1^t)
-    float b1, b2, eps, momentum, grad_scale, clipnorm, clipvalue;
-};
-
-// cs: clipnorm max(norm, c) of the element's variable; global_clipnorm the one scale c * min(1 / gn, 1 / c)
-template <int CLIP>
-__device__ __forceinline__ float opt_clip(const float graw, const OptArgs& a, const float cs) {
-    float g = graw * a.grad_scale;
-    if (CLIP & kClipNorm) g = (g * a.clipnorm) / cs;
-    if (CLIP & kClipGlobal) g *= cs;
-    if (CLIP & kClipValue) g = fminf(fmaxf(g, -a.clipvalue), a.clipvalue);
-    return g;
-}
-template <int OPT, bool NESTEROV, bool ACC>
-__device__ __forceinline__ void opt_apply(float& var, float& m, float& v, const float g, const OptArgs& a) {
-    if (OPT == SSD_OPT_ADAM) {
-        const float mm = m + (g - m) * (1.0f - a.b1);
-        const float vv = v + (g * g - v) * (1.0f - a.b2);
-        m = mm;
-        v = vv;
-        var -= a.lr * mm / (sqrtf(vv) + a.eps);
-    } else if (ACC) {
-        const float acc = a.momentum * m - a.lr * g;
-        m = acc;
-        var += NESTEROV ? a.momentum * acc - a.lr * g : acc;
-    } else {
-        var -= a.lr * g;
-    }
-}
-// the three pieces of a segment: [0, head) and [head + 4 * nv, n) scalar, nv float4 between them (vec == 0: all scalar)
-__device__ __forceinline__ void opt_split(const OptSeg& sg, const int vec, int& head, int& nv) {
-    head = vec ? min(sg.n, (int)((4 - (sg.lo & 3)) & 3)) : sg.n;
-    nv = (sg.n - head) >> 2;
-}
-
-template <int OPT, bool NESTEROV, bool ACC, int CLIP>
-__global__ __launch_bounds__(256) void opt_update_kernel(float* __restrict__ var, float* __restrict__ m, float* __restrict__ v,
-                                                        const float* __restrict__ grad, const OptSeg* __restrict__ segs,
-                                                        const int nseg, const float* __restrict__ cscale, const OptArgs a,
-                                                        const int vec) {
-    constexpr bool kM = OPT == SSD_OPT_ADAM || ACC, kV = OPT == SSD_OPT_ADAM;
-    for (int s = blockIdx.x; s < nseg; s += gridDim.x) {
-        const OptSeg sg = segs[s];
-        const float cs = (CLIP & (kClipNorm | kClipGlobal)) ? cscale[sg.var] : 1.0f;
-        int head, nv;
-        opt_split(sg, vec, head, nv);
-        const auto one = [&](const long e) {
-            float w = var[e], mm = kM ? m[e] : 0.f, vv = kV ? v[e] : 0.f;
-            opt_apply<OPT, NESTEROV, ACC>(w, mm, vv, opt_clip<CLIP>(grad[e], a, cs), a);
-            var[e] = w;
-            if (kM) m[e] = mm;
-            if (kV) v[e] = vv;
-        };
-        for (int i = threadIdx.x; i < head; i += 256) one(sg.lo + i);
-        const long body = sg.lo + head;
-        for (int i = threadIdx.x; i < nv; i += 256) {
-            const long e = body + 4L * i;
-            const float4 g4 = *reinterpret_cast<const float4*>(grad + e);
-            float4 w4 = *reinterpret_cast<const float4*>(var + e);
-            float4 m4 = make_float4(0.f, 0.f, 0.f, 0.f), v4 = m4;
-            if (kM) m4 = *reinterpret_cast<const float4*>(m + e);
-            if (kV) v4 = *reinterpret_cast<const float4*>(v + e);
-            opt_apply<OPT, NESTEROV, ACC>(w4.x, m4.x, v4.x, opt_clip<CLIP>(g4.x, a, cs), a);
-            opt_apply<OPT, NESTEROV, ACC>(w4.y, m4.y, v4.y, opt_clip<CLIP>(g4.y, a, cs), a);
-            opt_apply<OPT, NESTEROV, ACC>(w4.z, m4.z, v4.z, opt_clip<CLIP>(g4.z, a, cs), a);
-            opt_apply<OPT, NESTEROV, ACC>(w4.w, m4.w, v4.w, opt_clip<CLIP>(g4.w, a, cs), a);
-            *reinterpret_cast<float4*>(var + e) = w4;
-            if (kM) *reinterpret_cast<float4*>(m + e) = m4;
-            if (kV) *reinterpret_cast<float4*>(v + e) = v4;
-        }
-        for (int i = head + 4 * nv + threadIdx.x; i < sg.n; i += 256) one(sg.lo + i);
-    }
-}
-
-// Norm pass, launch 1: partial[s] = sum of (grad * grad_scale)^2 over segment s.  A thread adds its elements in index
-// order, the 256 sums go through a fixed tree; which workgroup takes a segment changes nothing: no atomics, the same
-// bits at every grid size.
-__global__ __launch_bounds__(256) void opt_sumsq_kernel(const float* __restrict__ grad, const OptSeg* __restrict__ segs, const int nseg,
-                                                       const float grad_scale, float* __restrict__ partial, const int vec) {
-    __shared__ float sh[256];
-    for (int s = blockIdx.x; s < nseg; s += gridDim.x) {
-        const OptSeg sg = segs[s];
-        int head, nv;
-        opt_split(sg, vec, head, nv);
-        float acc = 0.f;
-        const auto sq = [&](const float x) { const float g = x * grad_scale; acc += g * g; };
-        for (int i = threadIdx.x; i < head; i += 256) sq(grad[sg.lo + i]);
-        const long body = sg.lo + head;
-        for (int i = threadIdx.x; i < nv; i += 256) {
-            const float4 g4 = *reinterpret_cast<const float4*>(grad + body + 4L * i);
-            sq(g4.x); sq(g4.y); sq(g4.z); sq(g4.w);
-        }
-        for (int i = head + 4 * nv + threadIdx.x; i < sg.n; i += 256) sq(grad[sg.lo + i]);
-        sh[threadIdx.x] = acc;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) partial[s] = sh[0];
-        __syncthreads();
-    }
-}
-// Norm pass, launch 2 (one workgroup): every variable's partials, which lie in table order, summed in double -- lane l of
-// a wavefront takes partials l, l + 64, ... in that order, the 64 sums go through a fixed butterfly -- then what the update
-// reads per variable: clipnorm max(norm, c) with norm = s > 0 ? sqrt(s) : s (tf.clip_by_norm: an all-zero gradient
-// divides by c and stays zero), global_clipnorm the one scale c * min(1 / gn, 1 / c) over the sum of every s.
-__global__ __launch_bounds__(1024) void opt_norm_finish_kernel(const float* __restrict__ partial, const OptVar* __restrict__ vars,
-                                                              const int nvars, float* __restrict__ cscale, const float clipnorm,
-                                                              const float global_clipnorm) {
-    __shared__ double ssum[kOptMaxVars];
-    __shared__ double total;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int q = wave; q < nvars; q += 16) {
-        const OptVar r = vars[q];
-        double s = 0.0;
-        for (int i = lane; i < r.nseg; i += 64) s += (double)partial[r.seg0 + i];
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-        if (lane == 0) ssum[q] = s;
-    }
-    __syncthreads();
-    if (global_clipnorm > 0.f) {
-        if (wave == 0) {
-            double t = 0.0;
-            for (int q = lane; q < nvars; q += 64) t += ssum[q];
-            for (int o = 32; o > 0; o >>= 1) t += __shfl_down(t, o, 64);
-            if (lane == 0) total = t;
-        }
-        __syncthreads();
-        const float gn = (float)sqrt(total);
-        const float sc = global_clipnorm * fminf(1.0f / gn, 1.0f / global_clipnorm);
-        for (int q = threadIdx.x; q < nvars; q += 1024) cscale[q] = sc;
-    } else {
-        for (int q = threadIdx.x; q < nvars; q += 1024) {
-            const double s = ssum[q];
-            cscale[q] = fmaxf(s > 0.0 ? (float)sqrt(s) : 0.f, clipnorm);
-        }
-    }
-}
-
 }  // namespace ssd
 
-// ====================================================================== training state
-struct TrainLayer {
-    float* pre = nullptr;        // BN layers: conv / depthwise output before BatchNorm [M][C]
-    float* mean = nullptr;       // [C] batch statistics of the last forward
-    float* var = nullptr;
-    float* istd = nullptr;
-    float *fscale = nullptr, *fshift = nullptr;   // BN layers: the BatchNorm folded on its moving statistics (used while it is frozen)
-    float* wfwd = nullptr;       // packed forward weights (dense convs)
-    float* wbwd = nullptr;       // packed backward-data weights (rotated + transposed), nullptr: no dgrad
-    int cpad = 0;                // dY channel count the backward-data conv sees (heads: padded to 32)
-    long g_kernel = -1, g_bias = -1, g_gamma = -1, g_beta = -1, g_kernel2 = -1, g_bias2 = -1;
-    bool active = false;
-};
-
-struct ssd_train_state {
-    int batch = 0;
-    size_t P = 0;
-    int precision = 0;                  // the net's precision the weight re-pack jobs were planned for
-    double step_flops[3] = {0, 0, 0};   // matrix-core FLOPs of the last forward_backward: fp32-MFMA convs, split-bf16 convs, weight gradients
-    float *flat = nullptr, *m = nullptr, *v = nullptr;
-    std::vector<long> poff;             // parameter -> offset in the flat trainable vector (-1: not trainable)
-    std::vector<float*> act;            // training activations per tensor (own arena: no finalize needed)
-    std::vector<float*> gact;           // gradient w.r.t. each activation tensor
-    std::vector<char> gwritten;
-    std::vector<TrainLayer> tl;
-    std::vector<float*> owned;
-    float *scratch_dz = nullptr, *partial = nullptr;
-    // weight gradients on a side stream beside the rest of the backward (dX chain, BatchNorm backward of the layers below):
-    // dY alternates between two buffers (a buffer is rewritten only after the weight gradient that reads it is done), the
-    // weight-gradient partial slab is its own
-    float* dy_buf[2] = {nullptr, nullptr};
-    float* partial_w = nullptr;
-    size_t partial_w_floats = 0;
-    hipStream_t wstream = nullptr;
-    hipEvent_t ev_dy = nullptr, ev_wdone[2] = {nullptr, nullptr}, ev_wall = nullptr, ev_main_pos = nullptr;
-    bool wpending[2] = {false, false};
-    float* pack_jobs = nullptr;  // device array of PackJob (one launch re-packs every conv weight)
-    int n_pack_jobs = 0;
-    size_t partial_floats = 0;
-    float *dgamma_tmp = nullptr, *dbeta_tmp = nullptr;
-    float *deltas = nullptr, *probs = nullptr, *gdeltas = nullptr, *glogits = nullptr;
-    void* loss_ws = nullptr;
-    size_t loss_ws_bytes = 0;
-    long step = 0;
-    // gradient buckets for the data-parallel exchange (ssd_net_train_set_buckets): bucket k = flat offsets
-    // [bucket_lo[k], bucket_lo[k + 1]) and is FINAL once the backward has passed every layer that owns a
-    // parameter at or above bucket_lo[k]; bucket_ev[k] is recorded on the backward's stream right there
-    std::vector<long> bucket_lo;
-    std::vector<hipEvent_t> bucket_ev;
-    std::vector<long> pending_hi;       // per layer i: end of the highest parameter of any ACTIVE layer j < i (0: none)
-    // fine-tuning (ssd_net_set_trainable): the backward plan of the net's current flags, one SSD_PLAN_* word per layer, made
-    // by refresh_plan when plan_rev lags behind ssd_net::trainable_rev
-    unsigned plan_rev = ~0u;
-    std::vector<int> plan;
-    bool any_frozen = false;
-    float* fold_jobs = nullptr;         // device array of FoldJob, room for every BatchNorm layer; the first n_fold_jobs are the frozen ones
-    int n_fold_jobs = 0, fold_jobs_cap = 0, fold_maxC = 0;
-    float* adam_segs = nullptr;         // device array of AdamSeg, room for adam_segs_cap; the first n_adam_segs cover the trainable ranges
-    int n_adam_segs = 0, adam_segs_cap = 0;
-    // ssd_net_optimizer_step: the per-variable table of the trainable ranges (always made, frozen or not: clipped and
-    // frozen runs share one reduction order), room for adam_segs_cap segments and n_opt_vars variables, and the norm
-    // pass's scratch: a sum of squares per segment, a clip scale per variable
-    float *opt_segs = nullptr, *opt_vars = nullptr, *opt_partial = nullptr, *opt_norm = nullptr;
-    int n_opt_segs = 0, n_opt_vars = 0;
-    int opt_kind = -1;                  // SSD_OPT_* of the steps that wrote m / v (-1: none since the last reset)
-};
-
+// ====================================================================== training state (ssd_train.h)
 void ssd_train_state_free(ssd_train_state* s) {
     if (!s) return;
     for (auto e : s->bucket_ev)
@@ -1202,7 +914,7 @@ void ssd_train_state_free(ssd_train_state* s) {
 
 namespace ssd {
 
-static int talloc(ssd_train_state& s, size_t floats, float** out) {
+int talloc(ssd_train_state& s, size_t floats, float** out) {
     *out = nullptr;
     if (!floats) return SSD_OK;
     SSD_HIP(hipMalloc((void**)out, floats * sizeof(float)));
@@ -1220,7 +932,7 @@ static bool train_runs(const Layer& l) { return l.kind == LK_CONV || l.kind == L
 
 // ------------------------------------------------------------------ fine-tuning: trainable flags and the backward plan
 static std::string keras_layer_of(const std::string& param) { return param.substr(0, param.rfind('/')); }
-static bool param_frozen(const ssd_net* net, int p) {
+bool param_frozen(const ssd_net* net, int p) {
     return p >= 0 && !net->frozen.empty() && net->frozen.count(keras_layer_of(net->params[p].name)) != 0;
 }
 // a Keras layer that owns a trainable variable (one that owns only moving statistics cannot exist under this naming)
@@ -1363,10 +1075,10 @@ static ConvParams dense_conv_params(int B, int H, int W, int Cin, int Cout, int 
 }
 
 // Brings the training state's plan up to the net's trainable flags (ssd_net_set_trainable): the per-layer backward plan, the
-// fold jobs of the frozen BatchNorms and the Adam segments of the trainable ranges.  Runs when the flags changed since the
-// last step / optimizer call, which is rare: it waits for the device (a launch in flight may still read the old tables)
-// and uploads with blocking copies.  With nothing frozen both tables are empty and the step is the all-trainable one.
-static int refresh_plan(const ssd_net* net, ssd_train_state& s) {
+// fold jobs of the frozen BatchNorms and the optimizer's table of the trainable ranges.  Runs when the flags changed since
+// the last step / optimizer call, which is rare: it waits for the device (a launch in flight may still read the old tables)
+// and uploads with blocking copies.  With nothing frozen there are no fold jobs and the step is the all-trainable one.
+int refresh_plan(const ssd_net* net, ssd_train_state& s) {
     if (s.plan_rev == net->trainable_rev) return SSD_OK;
     s.plan = backward_plan(net);
     s.any_frozen = false;
@@ -1381,44 +1093,12 @@ static int refresh_plan(const ssd_net* net, ssd_train_state& s) {
                                 net->params[l.p_bn + 3].dev, s.tl[i].fscale, s.tl[i].fshift, l.Cout});
         s.fold_maxC = std::max(s.fold_maxC, l.Cout);
     }
-    // trainable ranges of the flat vector (neighbours merged), cut into segments
-    std::vector<AdamSeg> segs;
-    if (s.any_frozen) {
-        long lo = -1, hi = -1;
-        const auto flush = [&] {
-            for (long b = lo; b >= 0 && b < hi; b += kAdamSeg) segs.push_back(AdamSeg{b, std::min(kAdamSeg, hi - b)});
-            lo = hi = -1;
-        };
-        for (size_t q = 0; q < net->params.size(); ++q) {
-            if (s.poff[q] < 0 || param_frozen(net, (int)q)) continue;
-            if (s.poff[q] != hi) flush();
-            if (lo < 0) lo = s.poff[q];
-            hi = s.poff[q] + (long)net->params[q].count;
-        }
-        flush();
-    }
-    // the same ranges per Keras variable (ssd_net_optimizer_step), whether anything is frozen or not
-    std::vector<OptSeg> osegs;
-    std::vector<OptVar> ovars;
-    for (size_t q = 0; q < net->params.size(); ++q) {
-        if (s.poff[q] < 0) continue;
-        OptVar ov{(int)osegs.size(), 0};
-        if (!param_frozen(net, (int)q))
-            for (long b = 0; b < (long)net->params[q].count; b += kAdamSeg, ++ov.nseg)
-                osegs.push_back(OptSeg{s.poff[q] + b, (int)std::min(kAdamSeg, (long)net->params[q].count - b), (int)ovars.size()});
-        ovars.push_back(ov);
-    }
-    SSD_CHECK_ARG((int)folds.size() <= s.fold_jobs_cap && (int)segs.size() <= s.adam_segs_cap &&
-                      (int)osegs.size() <= s.adam_segs_cap && (int)ovars.size() == s.n_opt_vars,
-                  "train: the fine-tuning tables (%zu fold jobs, %zu Adam segments) exceed their plan", folds.size(), segs.size());
+    SSD_CHECK_ARG((int)folds.size() <= s.fold_jobs_cap, "train: %zu BatchNorm fold jobs exceed their plan (%d)", folds.size(), s.fold_jobs_cap);
     SSD_HIP(hipDeviceSynchronize());
+    const int rc = opt_refresh_tables(net, s);
+    if (rc) return rc;
     if (!folds.empty()) SSD_HIP(hipMemcpy(s.fold_jobs, folds.data(), folds.size() * sizeof(FoldJob), hipMemcpyHostToDevice));
-    if (!segs.empty()) SSD_HIP(hipMemcpy(s.adam_segs, segs.data(), segs.size() * sizeof(AdamSeg), hipMemcpyHostToDevice));
-    if (!osegs.empty()) SSD_HIP(hipMemcpy(s.opt_segs, osegs.data(), osegs.size() * sizeof(OptSeg), hipMemcpyHostToDevice));
-    if (!ovars.empty()) SSD_HIP(hipMemcpy(s.opt_vars, ovars.data(), ovars.size() * sizeof(OptVar), hipMemcpyHostToDevice));
-    s.n_opt_segs = (int)osegs.size();
     s.n_fold_jobs = (int)folds.size();
-    s.n_adam_segs = (int)segs.size();
     s.plan_rev = net->trainable_rev;
     return SSD_OK;
 }
@@ -2014,7 +1694,7 @@ struct TrainSizes {             // the largest of each scratch buffer over the l
     int maxC = 0;
 };
 
-// flat parameter vector (trainable parameters in table order) with the Adam moments, and every parameter's offset in it
+// flat parameter vector (trainable parameters in table order) with the optimizer's two slots, and every parameter's offset in it
 static int begin_flat(const ssd_net* net, ssd_train_state& s) {
     s.P = ssd_net_trainable_floats(net);
     int rc = talloc(s, s.P, &s.flat);
@@ -2135,19 +1815,9 @@ static int begin_streams_scratch(const ssd_net* net, ssd_train_state& s, const T
     if (!rc) rc = talloc(s, BN * net->L, &s.probs);
     if (!rc) rc = talloc(s, BN * 4, &s.gdeltas);
     if (!rc) rc = talloc(s, BN * net->L, &s.glogits);
-    // fine-tuning tables (refresh_plan): a fold job per BatchNorm layer, an Adam segment per kAdamSeg elements of a parameter
-    for (size_t q = 0; q < net->params.size(); ++q)
-        if (s.poff[q] >= 0) {
-            s.adam_segs_cap += (int)((net->params[q].count + kAdamSeg - 1) / kAdamSeg);
-            ++s.n_opt_vars;
-        }
+    // refresh_plan's tables: a fold job per BatchNorm layer, and the optimizer's
     if (!rc) rc = talloc(s, ((size_t)s.fold_jobs_cap * sizeof(FoldJob) + 3) / 4, &s.fold_jobs);
-    if (!rc) rc = talloc(s, ((size_t)s.adam_segs_cap * sizeof(AdamSeg) + 3) / 4, &s.adam_segs);
-    // the optimizer's per-variable table and the scratch of its norm pass (ssd_net_optimizer_step)
-    if (!rc) rc = talloc(s, ((size_t)s.adam_segs_cap * sizeof(OptSeg) + 3) / 4, &s.opt_segs);
-    if (!rc) rc = talloc(s, ((size_t)s.n_opt_vars * sizeof(OptVar) + 3) / 4, &s.opt_vars);
-    if (!rc) rc = talloc(s, (size_t)s.adam_segs_cap, &s.opt_partial);
-    if (!rc) rc = talloc(s, (size_t)s.n_opt_vars, &s.opt_norm);
+    if (!rc) rc = opt_alloc_tables(net, s);
     if (rc) return rc;
     s.loss_ws_bytes = ssd_loss_workspace_bytes(s.batch, net->num_priors);
     if (hipMalloc(&s.loss_ws, s.loss_ws_bytes) != hipSuccess) {
@@ -2193,27 +1863,6 @@ static int begin_adopt(ssd_net* net, ssd_train_state* s, const std::vector<PackJ
     net->finalized = false;          // derived inference weights must be rebuilt from the (moved) parameters
     net->drop_graphs();
     return SSD_OK;
-}
-
-// opt_update_kernel's instantiation for an optimizer and a clip mask (norm and global norm exclude each other)
-template <int OPT, bool NESTEROV, bool ACC>
-static void launch_opt_update(const int clip, ssd_train_state& s, const float* grad, const OptArgs& a, const int vec, hipStream_t st) {
-    const dim3 grid(s.n_opt_segs < 16384 ? s.n_opt_segs : 16384);
-    const OptSeg* segs = reinterpret_cast<const OptSeg*>(s.opt_segs);
-#define SSD_OPT_CASE(C)                                                                                                    \
-    case C:                                                                                                                \
-        hipLaunchKernelGGL((opt_update_kernel<OPT, NESTEROV, ACC, C>), grid, dim3(256), 0, st, s.flat, s.m, s.v, grad, segs, \
-                           s.n_opt_segs, s.opt_norm, a, vec);                                                              \
-        break;
-    switch (clip) {
-        SSD_OPT_CASE(0)
-        SSD_OPT_CASE(kClipNorm)
-        SSD_OPT_CASE(kClipGlobal)
-        SSD_OPT_CASE(kClipValue)
-        SSD_OPT_CASE(kClipNorm | kClipValue)
-        SSD_OPT_CASE(kClipGlobal | kClipValue)
-    }
-#undef SSD_OPT_CASE
 }
 
 }  // namespace ssd
@@ -2392,176 +2041,6 @@ int ssd_net_train_wait_bucket(ssd_net* net, int k, void* stream) {
     return SSD_OK;
 }
 
-// Sum of the layers' regularisation losses, the term Keras adds to `loss` / `val_loss` beside the compiled
-// losses: VGG16's kernel_regularizer=l2(5e-4) on every backbone / extra conv (models/ssd_vgg16.py:44-45),
-// nothing for MobileNetV2 (keras-applications builds it without regularisers; models/header.py:60-61 has none).
-int ssd_net_regularization_loss(ssd_net* net, float* host_out) {
-    SSD_CHECK_ARG(net && host_out, "ssd_net_regularization_loss: NULL argument");
-    *host_out = 0.f;
-    if (net->backbone != SSD_VGG16) return SSD_OK;
-    std::vector<const Param*> ws;
-    for (const auto& l : net->layers)
-        if (l.kind == LK_CONV && !l.head_kind && l.p_kernel >= 0 && net->params[l.p_kernel].dev) ws.push_back(&net->params[l.p_kernel]);
-    if (ws.empty()) return SSD_OK;
-    constexpr int kBlocks = 64;
-    float* scratch = nullptr;
-    SSD_HIP(hipMalloc((void**)&scratch, (ws.size() * kBlocks + 1) * sizeof(float)));
-    for (size_t i = 0; i < ws.size(); ++i)
-        hipLaunchKernelGGL(sumsq_kernel, dim3(kBlocks), dim3(256), 0, nullptr, ws[i]->dev, (long)ws[i]->count, scratch + i * kBlocks);
-    hipLaunchKernelGGL(reg_finalize_kernel, dim3(1), dim3(1), 0, nullptr, scratch, (int)(ws.size() * kBlocks), 5e-4f,
-                       scratch + ws.size() * kBlocks);
-    const hipError_t e = hipMemcpy(host_out, scratch + ws.size() * kBlocks, sizeof(float), hipMemcpyDeviceToHost);
-    (void)hipFree(scratch);
-    SSD_HIP(e);
-    return SSD_OK;
-}
-
-// One Adam update of every trainable parameter from grads_flat_dev (e.g. after the host's RCCL
-// all-reduce; grad_scale = 1 / world_size turns the reduced SUM into the global-batch mean).
-int ssd_net_adam_step(ssd_net* net, const float* grads_flat_dev, float lr, float beta1, float beta2, float eps,
-                      float grad_scale, void* stream) {
-    SSD_CHECK_ARG(net && grads_flat_dev, "ssd_net_adam_step: NULL argument");
-    if (!net->train) { set_error("ssd_net_adam_step: call ssd_net_train_begin() first"); return SSD_E_STATE; }
-    ssd_train_state& s = *net->train;
-    const int rp = refresh_plan(net, s);
-    if (rp) return rp;
-    if (s.step > 0 && s.opt_kind == SSD_OPT_SGD) {
-        set_error("ssd_net_adam_step: the optimizer slots hold SGD's momentum after %ld steps: call ssd_net_optimizer_reset first", s.step);
-        return SSD_E_STATE;
-    }
-    s.opt_kind = SSD_OPT_ADAM;
-    s.step += 1;
-    const double t = (double)s.step;
-    const float alpha = (float)((double)lr * std::sqrt(1.0 - std::pow((double)beta2, t)) / (1.0 - std::pow((double)beta1, t)));
-    if (!s.any_frozen)
-        hipLaunchKernelGGL(adam_kernel, dim3(grid_for((long)s.P)), dim3(256), 0, (hipStream_t)stream, s.flat, s.m, s.v,
-                           grads_flat_dev, (long)s.P, alpha, beta1, beta2, eps, grad_scale);
-    else if (s.n_adam_segs)
-        // frozen ranges keep var, m and v bitwise: one launch over the table of trainable segments (adam_ranges_kernel).  The
-        // moments of a layer that is unfrozen later continue from where they were (Keras rebuilds its optimizer at the
-        // compile() that follows a change of `trainable`; here there is no such call)
-        hipLaunchKernelGGL(adam_ranges_kernel, dim3(s.n_adam_segs < 16384 ? s.n_adam_segs : 16384), dim3(256), 0, (hipStream_t)stream,
-                           s.flat, s.m, s.v, grads_flat_dev, reinterpret_cast<const AdamSeg*>(s.adam_segs), s.n_adam_segs, alpha,
-                           beta1, beta2, eps, grad_scale);
-    SSD_LAUNCH_CHECK();
-    net->finalized = false;
-    net->drop_graphs();
-    return SSD_OK;
-}
-
-// Keras SGD / Adam with clipnorm, clipvalue, global_clipnorm (include/ssd_hip.h has the arithmetic).  One launch over the
-// per-variable table; with a norm clip two launches in front of it fill one scale per variable.
-int ssd_net_optimizer_step(ssd_net* net, const float* grads_flat_dev, const ssd_optimizer* opt, float lr, float grad_scale,
-                           void* stream) {
-    SSD_CHECK_ARG(net && grads_flat_dev && opt, "ssd_net_optimizer_step: NULL argument");
-    SSD_CHECK_ARG(opt->kind == SSD_OPT_ADAM || opt->kind == SSD_OPT_SGD, "ssd_net_optimizer_step: unknown optimizer kind %d", opt->kind);
-    if (opt->kind == SSD_OPT_ADAM)
-        SSD_CHECK_ARG(opt->beta1 >= 0.f && opt->beta1 < 1.f && opt->beta2 >= 0.f && opt->beta2 < 1.f,
-                      "ssd_net_optimizer_step: Adam's beta1 %g / beta2 %g must lie in [0, 1)", opt->beta1, opt->beta2);
-    else
-        SSD_CHECK_ARG(opt->momentum >= 0.f && opt->momentum <= 1.f, "ssd_net_optimizer_step: momentum %g must lie in [0, 1]", opt->momentum);
-    SSD_CHECK_ARG(!(opt->clipnorm > 0.f && opt->global_clipnorm > 0.f),
-                  "ssd_net_optimizer_step: clipnorm and global_clipnorm exclude each other");
-    if (!net->train) { set_error("ssd_net_optimizer_step: call ssd_net_train_begin() first"); return SSD_E_STATE; }
-    const int clip = (opt->clipnorm > 0.f ? kClipNorm : 0) | (opt->global_clipnorm > 0.f ? kClipGlobal : 0) |
-                     (opt->clipvalue > 0.f ? kClipValue : 0);
-    // Adam without a clip is ssd_net_adam_step: its launches, its bits
-    if (opt->kind == SSD_OPT_ADAM && !clip)
-        return ssd_net_adam_step(net, grads_flat_dev, lr, opt->beta1, opt->beta2, opt->eps, grad_scale, stream);
-    ssd_train_state& s = *net->train;
-    const int rp = refresh_plan(net, s);
-    if (rp) return rp;
-    if (s.step > 0 && s.opt_kind >= 0 && s.opt_kind != opt->kind) {
-        set_error("ssd_net_optimizer_step: the optimizer slots were written by %s steps (%ld so far): call ssd_net_optimizer_reset before a step of another kind",
-                  s.opt_kind == SSD_OPT_SGD ? "SGD" : "Adam", s.step);
-        return SSD_E_STATE;
-    }
-    const bool norms = clip & (kClipNorm | kClipGlobal);
-    SSD_UNSUPPORTED_IF(norms && s.n_opt_vars > kOptMaxVars, "ssd_net_optimizer_step: norm clipping over %d variables (limit %d)", s.n_opt_vars, kOptMaxVars);
-    s.opt_kind = opt->kind;
-    s.step += 1;
-    OptArgs a{};
-    a.lr = lr;
-    if (opt->kind == SSD_OPT_ADAM) {
-        const double t = (double)s.step;
-        a.lr = (float)((double)lr * std::sqrt(1.0 - std::pow((double)opt->beta2, t)) / (1.0 - std::pow((double)opt->beta1, t)));
-        a.b1 = opt->beta1; a.b2 = opt->beta2; a.eps = opt->eps;
-    }
-    a.momentum = opt->momentum;
-    a.grad_scale = grad_scale;
-    a.clipnorm = opt->clipnorm;
-    a.clipvalue = opt->clipvalue;
-    hipStream_t st = (hipStream_t)stream;
-    const int vec = ((uintptr_t)grads_flat_dev & 15) == 0;     // (var, m and v are allocations of their own)
-    if (s.n_opt_segs) {
-        const OptSeg* segs = reinterpret_cast<const OptSeg*>(s.opt_segs);
-        if (norms) {
-            hipLaunchKernelGGL(opt_sumsq_kernel, dim3(s.n_opt_segs < 16384 ? s.n_opt_segs : 16384), dim3(256), 0, st, grads_flat_dev,
-                               segs, s.n_opt_segs, grad_scale, s.opt_partial, vec);
-            hipLaunchKernelGGL(opt_norm_finish_kernel, dim3(1), dim3(1024), 0, st, s.opt_partial,
-                               reinterpret_cast<const OptVar*>(s.opt_vars), s.n_opt_vars, s.opt_norm, opt->clipnorm,
-                               opt->global_clipnorm);
-        }
-        if (opt->kind == SSD_OPT_ADAM) launch_opt_update<SSD_OPT_ADAM, false, true>(clip, s, grads_flat_dev, a, vec, st);
-        else if (opt->momentum == 0.f) launch_opt_update<SSD_OPT_SGD, false, false>(clip, s, grads_flat_dev, a, vec, st);
-        else if (opt->nesterov) launch_opt_update<SSD_OPT_SGD, true, true>(clip, s, grads_flat_dev, a, vec, st);
-        else launch_opt_update<SSD_OPT_SGD, false, true>(clip, s, grads_flat_dev, a, vec, st);
-    }
-    SSD_LAUNCH_CHECK();
-    net->finalized = false;
-    net->drop_graphs();
-    return SSD_OK;
-}
-
-int ssd_net_optimizer_reset(ssd_net* net) {
-    SSD_CHECK_ARG(net, "ssd_net_optimizer_reset: NULL argument");
-    if (!net->train) return SSD_OK;
-    ssd_train_state& s = *net->train;
-    SSD_HIP(hipDeviceSynchronize());
-    SSD_HIP(hipMemset(s.m, 0, s.P * sizeof(float)));
-    SSD_HIP(hipMemset(s.v, 0, s.P * sizeof(float)));
-    SSD_HIP(hipDeviceSynchronize());
-    s.step = 0;
-    s.opt_kind = -1;
-    return SSD_OK;
-}
-
-static float* optimizer_slot(ssd_net* net, const char* slot) {
-    const std::string w(slot);
-    return w == "m" ? net->train->m : w == "v" ? net->train->v : nullptr;
-}
-static bool optimizer_slot_known(const char* slot) { return std::string(slot) == "m" || std::string(slot) == "v"; }
-
-long ssd_net_optimizer_get_state(ssd_net* net, const char* slot, float* host_out, size_t cap) {
-    SSD_CHECK_ARG(net && slot, "ssd_net_optimizer_get_state: NULL argument");
-    SSD_CHECK_ARG(optimizer_slot_known(slot), "ssd_net_optimizer_get_state: unknown slot '%s' (\"m\" | \"v\")", slot);
-    const size_t n = ssd_net_trainable_floats(net);
-    if (!host_out) return (long)n;
-    SSD_CHECK_ARG(cap >= n, "ssd_net_optimizer_get_state: room for %zu floats, the slot has %zu", cap, n);
-    if (!net->train) { set_error("ssd_net_optimizer_get_state: call ssd_net_train_begin() first"); return SSD_E_STATE; }
-    SSD_HIP(hipDeviceSynchronize());
-    SSD_HIP(hipMemcpy(host_out, optimizer_slot(net, slot), n * sizeof(float), hipMemcpyDeviceToHost));
-    return (long)n;
-}
-
-int ssd_net_optimizer_set_state(ssd_net* net, const char* slot, const float* host_in, size_t count) {
-    SSD_CHECK_ARG(net && slot && host_in, "ssd_net_optimizer_set_state: NULL argument");
-    SSD_CHECK_ARG(optimizer_slot_known(slot), "ssd_net_optimizer_set_state: unknown slot '%s' (\"m\" | \"v\")", slot);
-    SSD_CHECK_ARG(count == ssd_net_trainable_floats(net), "ssd_net_optimizer_set_state: %zu floats given, the slot has %zu", count,
-                  ssd_net_trainable_floats(net));
-    if (!net->train) { set_error("ssd_net_optimizer_set_state: call ssd_net_train_begin() first"); return SSD_E_STATE; }
-    SSD_HIP(hipDeviceSynchronize());
-    SSD_HIP(hipMemcpy(optimizer_slot(net, slot), host_in, count * sizeof(float), hipMemcpyHostToDevice));
-    return SSD_OK;
-}
-
-int ssd_net_train_set_steps(ssd_net* net, long steps) {
-    SSD_CHECK_ARG(net && steps >= 0, "ssd_net_train_set_steps: bad arguments");
-    if (!net->train) { set_error("ssd_net_train_set_steps: call ssd_net_train_begin() first"); return SSD_E_STATE; }
-    net->train->step = steps;
-    return SSD_OK;
-}
-
 int ssd_net_set_trainable(ssd_net* net, const char* keras_layer, int trainable_flag) {
     SSD_CHECK_ARG(net && keras_layer, "ssd_net_set_trainable: NULL argument");
     SSD_CHECK_ARG(known_keras_layer(net, keras_layer), "ssd_net_set_trainable: '%s' is no Keras layer with trainable variables of this net", keras_layer);
@@ -2582,8 +2061,6 @@ int ssd_net_train_plan(const ssd_net* net, int layer, int* flags) {
     *flags = backward_plan(net)[layer];
     return SSD_OK;
 }
-
-long ssd_net_train_steps(const ssd_net* net) { return (net && net->train) ? net->train->step : 0; }
 
 int ssd_net_train_matrix_flops(const ssd_net* net, double* out3) {
     SSD_CHECK_ARG(net && out3, "ssd_net_train_matrix_flops: NULL argument");

@@ -11,10 +11,10 @@ python - "$f" <<'PY'
 import csv, sys, re, collections
 rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-# steady region: the last 6 steps = after the last-but-6th adam_kernel
-adam = [i for i, r in enumerate(rows) if "adam_kernel" in r["Kernel_Name"]]
-print("adam launches", len(adam), "kernels", len(rows))
-lo, hi = adam[-7] + 1, adam[-1] + 1
+# steady region: the last 6 steps = after the last-but-6th opt_update_kernel
+steps = [i for i, r in enumerate(rows) if "opt_update_kernel" in r["Kernel_Name"]]
+print("optimizer launches", len(steps), "kernels", len(rows))
+lo, hi = steps[-7] + 1, steps[-1] + 1
 seg = rows[lo:hi]
 t0, t1 = int(seg[0]["Start_Timestamp"]), int(seg[-1]["End_Timestamp"])
 busy = 0; cur_s, cur_e = None, None

@@ -4,8 +4,8 @@ import csv, sys, re, glob
 f = glob.glob(sys.argv[1] + "/*/*kernel_trace.csv")[0]
 rows = list(csv.DictReader(open(f)))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-adam = [i for i, r in enumerate(rows) if "adam_kernel" in r["Kernel_Name"]]
-seg = rows[adam[-2] + 1: adam[-1] + 1]
+steps = [i for i, r in enumerate(rows) if "opt_update_kernel" in r["Kernel_Name"]]
+seg = rows[steps[-2] + 1: steps[-1] + 1]
 t0 = int(seg[0]["Start_Timestamp"])
 for r in seg:
     n = re.sub(r"void ssd::|\(anonymous namespace\)::|ssd::", "", r["Kernel_Name"])
