@@ -131,6 +131,39 @@ int ssd_eval_match(const float* det_boxes_dev, const float* det_labels_dev,
                    int* rec_class_out, float* rec_score_out, int* rec_tp_out, int* rec_det_out,
                    int* rec_count_out, void* stream);
 
+/* ---- detection scoring by the standard protocols: the per-image matching of VOCdevkit's
+ * VOCevaldet.m (SSD_EVAL_RULE_VOC) and of pycocotools' cocoeval.evaluateImg without crowd boxes
+ * and area ranges (SSD_EVAL_RULE_COCO).  Inputs as ssd_eval_match, plus gt_ignore [B,G] uint8
+ * (nullable = nothing ignored; VOC "difficult") and NT IoU thresholds iou_thrs_host (HOST).
+ * The IoU is taken on the normalised corner boxes the decoder emits, WITHOUT the devkit's
+ * "+1 pixel" on widths and heights; its bits are ssd_iou_map's.  A NaN IoU never matches and
+ * never wins a maximum.
+ * Per image the records are the rows with a non-zero label in DESCENDING SCORE, equal scores by
+ * ascending detection index (-0 == +0; NaN scores last).  They are walked in that order,
+ * separately for every class c and every threshold t; taken[t][g] is private to the threshold.
+ *   VOC:  ovmax = -inf; over the image's class-c boxes in index order, ignored and taken ones
+ *         included: if iou > ovmax: ovmax = iou, jmax = g (first maximum).  No class-c box or
+ *         ovmax < t: FP.  Else ignore[jmax]: ignored.  Else not taken[t][jmax]: TP, take it.
+ *         Else FP (duplicate).
+ *   COCO: candidates = the class-c boxes, non-ignored first, then ignored, index order within.
+ *         best = t, m = -1; per candidate g: skip if taken[t][g]; stop if m >= 0, m not ignored
+ *         and g ignored; skip if !(iou >= best); else best = iou, m = g (a later tie wins).
+ *         m < 0: FP.  Else take m; ignored if ignore[m] (an ignored box absorbs one detection
+ *         per threshold), else TP.
+ * Outputs (device, fully overwritten, zeros at and after the count): rec_class_out [B,T] int32,
+ * rec_score_out [B,T], rec_det_out (nullable) [B,T] int32, rec_state_out [B,NT,T] int8 (1 TP,
+ * 0 FP, -1 ignored), rec_count_out [B] int32.  Deterministic: the same bits on every run.
+ * Supported: 0 <= T <= 1024, 1 <= G <= 256, 1 <= NT <= 10 (one workgroup per image, everything
+ * in LDS); anything else returns SSD_E_UNSUPPORTED before any launch.  B == 0 is a no-op. */
+#define SSD_EVAL_RULE_VOC 0
+#define SSD_EVAL_RULE_COCO 1
+int ssd_eval_match_protocol(const float* det_boxes_dev, const float* det_labels_dev,
+                            const float* det_scores_dev, const float* gt_boxes_dev,
+                            const int* gt_labels_dev, const unsigned char* gt_ignore_dev,
+                            int B, int T, int G, int rule, const float* iou_thrs_host, int NT,
+                            int* rec_class_out, float* rec_score_out, int* rec_det_out,
+                            signed char* rec_state_out, int* rec_count_out, void* stream);
+
 /* ---- input pipeline: utils/data_utils.py:22-23 (N4) ---------------------------------------
  * tf.image.convert_image_dtype(uint8 -> float32, x 1/255) + tf.image.resize(bilinear, TF2
  * half-pixel centres, no antialias) in one kernel.  image_u8 [B,H,W,C] uint8 (device) ->

@@ -427,12 +427,16 @@ class DecoderModel(object):
         return tuple(np.concatenate(a, 0) for a in outs)
 
     @staticmethod
-    def _upload_ground_truth(gt_boxes, gt_labels):
+    def _upload_ground_truth(gt_boxes, gt_labels, gt_ignore=None):
         """Ground truth of one batch as device tensors, the upload queued on the current stream: host arrays go through
         page-locked staging blocks (torch's caching host allocator recycles a block once its copy ran), so the host
-        does not wait for the stream; device tensors are used where they are."""
+        does not wait for the stream; device tensors are used where they are.  ``gt_ignore`` (uint8 flags), when given,
+        is the third tensor."""
         out = []
-        for a, dt in ((gt_boxes, torch.float32), (gt_labels, torch.int32)):
+        parts = [(gt_boxes, torch.float32), (gt_labels, torch.int32)]
+        if gt_ignore is not None:
+            parts.append((gt_ignore, torch.uint8))
+        for a, dt in parts:
             if isinstance(a, torch.Tensor) and a.is_cuda:
                 a = a.to(dtype=dt).contiguous()
             else:
@@ -444,14 +448,18 @@ class DecoderModel(object):
             out.append(a)
         return out
 
-    def evaluate(self, dataset, labels, steps=None, verbose=0):
+    def evaluate(self, dataset, labels, steps=None, verbose=0, protocol=None):
         """Streaming VOC07 mAP over ``dataset``, an iterable of ``(images, gt_boxes, gt_labels)`` padded batches
         (reference predictor.py:43-55 in one pass); ``labels`` is the class-name list, background first.  Every step
         goes the way ``predict`` sends it (lanes when they are in use, else one step at a time); the batch's ground
         truth is uploaded and ``ssd_eval_match`` enqueued on the stream that produced the detections, on the device
         tensors of that step.  Detections and IoUs never reach the host: the record arrays are copied out after the
         last batch, appended with ``eval_utils.stats_from_records`` and scored by ``calculate_mAP``.
-        Returns ``(stats, mAP)``."""
+        Returns ``(stats, mAP)``.
+        ``protocol`` (``"voc07"`` / ``"voc10"`` / ``"coco"``; ``None``: the reference's scoring, above): the same
+        streaming pass with ``ssd_eval_match_protocol`` and ``eval_utils.DetectionEvaluator``; batches may carry a fourth
+        item, the ignore (VOC "difficult") flags uint8 [B,G] (``data_utils.voc_batches(keep_difficult=True)``).  Returns
+        ``(result, mAP)``, ``result`` being ``DetectionEvaluator.result()``."""
         from utils import eval_utils
         try:
             n_batches = len(dataset)
@@ -460,6 +468,8 @@ class DecoderModel(object):
         if steps is not None:
             n_batches = steps if n_batches is None else min(n_batches, steps)
         use_lanes = self.lanes > 1 and not (self.auto_lanes and n_batches is not None and n_batches < 2 * self.lanes)
+        if protocol is not None:
+            return self._evaluate_protocol(dataset, eval_utils.DetectionEvaluator(labels, protocol), steps, verbose, use_lanes)
         stats = eval_utils.init_stats(labels)
         pending, gt_seen = [], []
         done = 0
@@ -491,6 +501,39 @@ class DecoderModel(object):
             eval_utils.stats_from_records(host[0], host[1], host[2], host[3], gt_seen, stats)
         return eval_utils.calculate_mAP(stats)
 
+    def _evaluate_protocol(self, dataset, evaluator, steps, verbose, use_lanes):
+        """``evaluate`` with a protocol: per batch the ground truth (and its flags) is uploaded and
+        ``evaluator.update`` enqueues the matching on the stream that produced the detections; the evaluator reads its
+        record tensors back in ``result()``, after the last batch."""
+        done = 0
+        cur = torch.cuda.current_stream()
+        for batch in dataset:
+            if steps is not None and done >= steps:
+                break
+            if len(batch) not in (3, 4):
+                raise ValueError("batches are (images, gt_boxes, gt_labels[, gt_ignore]), got %d items" % len(batch))
+            images, gt_boxes, gt_labels = batch[:3]
+            gt_ignore = batch[3] if len(batch) == 4 else None
+            b, l, s, st = self._submit(images) if use_lanes else (tuple(self(images)) + (None,))
+            if st is None:
+                st = cur
+            elif any(isinstance(a, torch.Tensor) and a.is_cuda for a in (gt_boxes, gt_labels, gt_ignore)):
+                st.wait_stream(cur)                    # resident ground truth was produced on the caller's stream
+            with torch.cuda.stream(st):
+                truth = self._upload_ground_truth(gt_boxes, gt_labels, gt_ignore)
+                rec = evaluator.update(b, l, s, *truth)
+            for t in tuple(truth) + tuple(rec or ()):
+                t.record_stream(st)
+            done += 1
+            if verbose:
+                print("\r%d/%s" % (done, steps if steps is not None else "?"), end="", flush=True)
+        if verbose:
+            print()
+        self.wait()
+        cur.synchronize()
+        result = evaluator.result()
+        return result, result["mAP"]
+
 
 def default_lanes():
     """Batches ``predict`` keeps in flight when the caller does not say: as many as the HIP runtime has hardware
@@ -502,13 +545,20 @@ def default_lanes():
     return int(q) if q.isdigit() and 1 < int(q) < 4 else 1
 
 
-def get_decoder_model(base_model, prior_boxes, hyper_params, lanes=None):
+def get_decoder_model(base_model, prior_boxes, hyper_params, lanes=None, score_threshold=None, max_total_size=None):
     """reference models/decoder.py:57-69.  ``lanes``: batches in flight for ``predict`` / ``submit`` (see
     DecoderModel).  Default: env SSD_HIP_LANES, else ``default_lanes()`` in AUTO mode -- ``predict`` uses the lanes
     when it has at least two batches per lane (a short check on the first such call falls back to one lane where
-    lanes do not pay), everything else stays on the one-step-at-a-time path."""
+    lanes do not pay), everything else stays on the one-step-at-a-time path.  ``score_threshold`` / ``max_total_size``
+    go to ``SSDDecoder`` (``None``: its defaults, 0.5 and 200): the devkit / COCO protocols of ``evaluate`` are meant
+    to be run at a low score threshold, the 0.5 default cuts the precision-recall curve short."""
     import os
-    decoder = SSDDecoder(prior_boxes, hyper_params["variances"])
+    extra = {}
+    if score_threshold is not None:
+        extra["score_threshold"] = float(score_threshold)
+    if max_total_size is not None:
+        extra["max_total_size"] = int(max_total_size)
+    decoder = SSDDecoder(prior_boxes, hyper_params["variances"], **extra)
     auto = False
     if lanes is None:
         env = os.environ.get("SSD_HIP_LANES")

@@ -42,6 +42,11 @@ draw = False
 draw_dir = None
 draw_format = "png"
 draw_quality = 75
+# additions: eval_protocol "voc07" / "voc10" / "coco" scores by the devkit's / pycocotools' rules (DecoderModel.evaluate on the
+# split built with keep_difficult=True) instead of the reference's; eval_score_threshold replaces the decoder's 0.5 (the
+# protocols are meant to be run at a low threshold, e.g. 0.01: 0.5 cuts the precision-recall curve short)
+eval_protocol = None
+eval_score_threshold = None
 
 
 def _model_factory(backbone):
@@ -63,7 +68,9 @@ def _load_or_synthesise_weights(model, backbone):
 
 def main(argv=None, **knobs):
     """``knobs`` override the module-level switches for one call (``evaluate``, ``use_custom_images``,
-    ``custom_image_path``, ``batch_size``, ``draw``, ``draw_dir``, ``draw_format``, ``draw_quality``)."""
+    ``custom_image_path``, ``batch_size``, ``draw``, ``draw_dir``, ``draw_format``, ``draw_quality``, ``eval_protocol``,
+    ``eval_score_threshold``).  With ``evaluate`` and an ``eval_protocol`` the fourth return value is
+    ``DetectionEvaluator.result()``."""
     args = io_utils.handle_args(argv)
     if args.handle_gpu:
         io_utils.handle_gpu_compatibility()
@@ -76,6 +83,11 @@ def main(argv=None, **knobs):
     out_dir = knobs.get("draw_dir", draw_dir)
     out_format = knobs.get("draw_format", draw_format)
     out_quality = int(knobs.get("draw_quality", draw_quality))
+    protocol = knobs.get("eval_protocol", eval_protocol) if do_eval else None
+    score_thr = knobs.get("eval_score_threshold", eval_score_threshold)
+    if protocol is not None:
+        eval_utils.protocol_spec(protocol)                # an unknown name fails before anything is built
+    keep = protocol is not None
     if out_format not in ("png", "jpeg"):
         raise ValueError('draw_format must be "png" or "jpeg", got %r' % (out_format,))
 
@@ -98,18 +110,18 @@ def main(argv=None, **knobs):
             test_data = test_data.take(total_items)
         # materialised like the synthetic split below: predict() and evaluate_predictions() / draw_predictions() both
         # walk it (1.08 MB of device memory per 300x300 image: 5.3 GB for all of VOC2007 test)
-        test_data = list(data_utils.voc_batches(test_data, bs, img_size, img_size, evaluate=do_eval))
+        test_data = list(data_utils.voc_batches(test_data, bs, img_size, img_size, evaluate=do_eval, keep_difficult=keep))
     else:                                                 # no devkit: a synthetic stand-in for voc/2007 test
         total_items = int(os.environ.get("SSD_SYNTHETIC_ITEMS", "128"))
         raw = data_utils.synthetic_voc_items(total_items, len(labels))
-        items = (data_utils.preprocessing(x, img_size, img_size, evaluate=do_eval) for x in raw)
+        items = (data_utils.preprocessing(x, img_size, img_size, evaluate=do_eval, keep_difficult=keep) for x in raw)
         # predictor.py:43 -- materialised: predict() and evaluate_predictions() both walk it
         test_data = list(data_utils.padded_batch(items, bs, padding_values))
 
     ssd_model = _model_factory(args.backbone)(hyper_params, max_batch=bs)
     _load_or_synthesise_weights(ssd_model, args.backbone)
     prior_boxes = bbox_utils.generate_prior_boxes(hyper_params["feature_map_shapes"], hyper_params["aspect_ratios"])
-    ssd_decoder_model = get_decoder_model(ssd_model, prior_boxes, hyper_params)
+    ssd_decoder_model = get_decoder_model(ssd_model, prior_boxes, hyper_params, score_threshold=score_thr)
 
     t0 = time.perf_counter()
     boxes, classes, scores = ssd_decoder_model.predict(
@@ -118,6 +130,14 @@ def main(argv=None, **knobs):
     print("predicted %d images in %.3f s (%.1f images/sec incl. host transfers); mean detections/image %.1f" % (
         boxes.shape[0], dt, boxes.shape[0] / max(dt, 1e-9), float((classes > 0).sum(-1).mean()) if boxes.shape[0] else 0.0))
 
+    if protocol is not None:
+        result, mean_ap = ssd_decoder_model.evaluate(test_data, labels, steps=train_utils.get_step_size(total_items, bs),
+                                                     protocol=protocol)
+        print("mAP ({}): {}".format(protocol, float(mean_ap)))
+        if protocol == "coco":
+            print("AP50: {}".format(result["AP50"]))
+            print("AP75: {}".format(result["AP75"]))
+        return boxes, classes, scores, result
     if do_eval:                                           # predictor.py:54-55
         stats = eval_utils.evaluate_predictions(test_data, boxes, classes, scores, labels, bs)
         return boxes, classes, scores, stats

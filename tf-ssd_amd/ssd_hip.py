@@ -100,6 +100,7 @@ JPEG_COEFFICIENTS, JPEG_RAW = 0, 1
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
 MOBILENET_V2, VGG16 = 0, 1
 OPT_ADAM, OPT_SGD = 0, 1
+EVAL_RULE_VOC, EVAL_RULE_COCO = 0, 1        # SSD_EVAL_RULE_*
 # SSD_PLAN_*: the bits of ssd_net_train_plan
 PLAN_WGRAD, PLAN_WGRAD2, PLAN_DGRAD, PLAN_RESGRAD, PLAN_BN_BATCH, PLAN_BN_PARAMS, PLAN_SKIP = 1, 2, 4, 8, 16, 32, 64
 
@@ -122,6 +123,7 @@ _SIGNATURES = {
     "ssd_match_encode": (ctypes.c_int, [vp, vp, vp, c_float_p, ctypes.c_float] + [ctypes.c_int] * 4 +
                          [vp, vp, vp, vp, vp]),
     "ssd_eval_match": (ctypes.c_int, [vp] * 5 + [ctypes.c_int] * 3 + [ctypes.c_float] + [vp] * 6),
+    "ssd_eval_match_protocol": (ctypes.c_int, [vp] * 6 + [ctypes.c_int] * 4 + [c_float_p, ctypes.c_int] + [vp] * 6),
     "ssd_preprocess": (ctypes.c_int, [vp] + [ctypes.c_int] * 6 + [vp, vp]),
     "ssd_preprocess_ragged": (ctypes.c_int, [vp, ctypes.c_size_t, vp, vp] + [ctypes.c_int] * 4 + [vp, vp]),
     "ssd_resize_lanczos_pitch": (ctypes.c_int, [ctypes.c_int]),

@@ -17,13 +17,15 @@ from . import voc_utils
 from .voc_utils import VOC_LABELS  # noqa: F401  (the 20 class names, alphabetical)
 
 
-def preprocessing(image_data, final_height, final_width, augmentation_fn=None, evaluate=False):
+def preprocessing(image_data, final_height, final_width, augmentation_fn=None, evaluate=False, keep_difficult=False):
     """reference utils/data_utils.py:7-30: uint8 image -> float32 [0,1] resized (bilinear) to
     ``(final_height, final_width)`` ON THE GPU (``ssd_preprocess``: one kernel, no float copy of
     the original image), labels shifted by +1 (0 is the background), difficult objects dropped when
     ``evaluate``.  ``image_data`` is the tfds-style dict ``{"image": uint8 [H,W,3], "objects":
     {"bbox": [G,4], "label": [G], "is_difficult": [G]}}``.  Returns (img device tensor, gt_boxes,
-    gt_labels)."""
+    gt_labels).  ``keep_difficult`` (not in the reference; for the devkit / COCO protocols of
+    ``eval_utils.DetectionEvaluator``): no object is dropped, whatever ``evaluate`` says, and a fourth item
+    ``gt_difficult`` (uint8 [G]) is returned."""
     import torch
     import ssd_hip as _h
     img = image_data["image"]
@@ -35,9 +37,11 @@ def preprocessing(image_data, final_height, final_width, augmentation_fn=None, e
     out = torch.empty((int(final_height), int(final_width), C), dtype=torch.float32, device=src.device)
     _h.check(_h.lib().ssd_preprocess(_h.ptr(src), 1, H, W, C, int(final_height), int(final_width), _h.ptr(out),
                                      _h.stream()), "preprocessing")
-    gt_boxes, gt_labels = _ground_truth(image_data, evaluate)
+    gt_boxes, gt_labels = _ground_truth(image_data, evaluate and not keep_difficult)
     if augmentation_fn:
         out, gt_boxes = augmentation_fn(out, gt_boxes)
+    if keep_difficult:
+        return out, gt_boxes, gt_labels, _difficult(image_data)
     return out, gt_boxes, gt_labels
 
 
@@ -50,6 +54,19 @@ def _ground_truth(image_data, evaluate):
         not_diff = np.logical_not(np.asarray(image_data["objects"]["is_difficult"], bool))
         gt_boxes, gt_labels = gt_boxes[not_diff], gt_labels[not_diff]
     return gt_boxes, gt_labels
+
+
+def _difficult(image_data):
+    """The difficult flags of one item's objects as uint8 [G], in the order of its boxes."""
+    return np.asarray(image_data["objects"]["is_difficult"], bool).astype(np.uint8).reshape(-1)
+
+
+def _pad_flags(flags, width):
+    """``padded_batch``'s fourth item: uint8 flag vectors padded with 0 to ``width``."""
+    out = np.zeros((len(flags), width), np.uint8)
+    for i, f in enumerate(flags):
+        out[i, :len(f)] = np.asarray(f, np.uint8)
+    return out
 
 
 def preprocess_batch(images_u8, final_height, final_width):
@@ -1627,15 +1644,17 @@ class voc_batches(object):
     when the generator is closed or collected: decodes not yet started are cancelled, the few in flight are waited
     for.  The order is the dataset's whatever the worker count.  ``augmentation_fn``: the batched
     ``augmentation.apply_batch``, applied after the resize as the reference does.  Every ``iter()`` is a fresh pass (a
-    shuffled dataset draws a new order), so ``train_utils.generator`` can cycle it."""
+    shuffled dataset draws a new order), so ``train_utils.generator`` can cycle it.  ``keep_difficult``: as in
+    ``preprocessing`` -- no object is dropped and a fourth item ``gt_difficult`` (uint8 [b,G], padding 0) is yielded."""
 
     def __init__(self, dataset, batch_size, final_height, final_width, evaluate=False, augmentation_fn=None, workers=None,
-                 prefetch=2):
+                 prefetch=2, keep_difficult=False):
         if int(batch_size) < 1:
             raise ValueError("batch_size must be positive, got %r" % (batch_size,))
         self.dataset, self.batch_size = dataset, int(batch_size)
         self.size = (int(final_height), int(final_width))
         self.evaluate, self.augmentation_fn = bool(evaluate), augmentation_fn
+        self.keep_difficult = bool(keep_difficult)
         self.workers, self.prefetch = data_workers(workers), max(int(prefetch), 0)
 
     def _decode_jobs(self):
@@ -1682,9 +1701,12 @@ class voc_batches(object):
             imgs = preprocess_jpeg_batch(images, self.size[0], self.size[1])
         else:
             imgs = preprocess_ragged_batch(images, self.size[0], self.size[1])
-        gt_boxes, gt_labels = _pad_ground_truth([_ground_truth(it, self.evaluate) for it in items], get_padding_values())
+        drop = self.evaluate and not self.keep_difficult
+        gt_boxes, gt_labels = _pad_ground_truth([_ground_truth(it, drop) for it in items], get_padding_values())
         if self.augmentation_fn:
             imgs, gt_boxes = self.augmentation_fn(imgs, gt_boxes, gt_labels)
+        if self.keep_difficult:
+            return imgs, gt_boxes, gt_labels, _pad_flags([_difficult(it) for it in items], gt_labels.shape[1])
         return imgs, gt_boxes, gt_labels
 
 
@@ -1783,15 +1805,18 @@ def padded_batch(items, batch_size, padding_values=None):
     """``Dataset.padded_batch(batch_size, padded_shapes=data_shapes, padding_values=...)`` of the reference
     scripts (predictor.py:43, trainer.py:33-34): consecutive ``(img, gt_boxes, gt_labels)`` items are stacked,
     ground truth padded to the longest of the batch with 0 / -1.  Images stay where they are (device tensors
-    are stacked on the device)."""
+    are stacked on the device).  Items with a fourth element (``preprocessing(keep_difficult=True)``) give batches
+    with a fourth element: the flags as uint8 [b,G], padded with 0."""
     import torch
     pv = padding_values or get_padding_values()
     batch = []
 
     def flush():
-        gt, gl = _pad_ground_truth([(bb, ll) for _, bb, ll in batch], pv)
+        gt, gl = _pad_ground_truth([(b[1], b[2]) for b in batch], pv)
         imgs = [b[0] for b in batch]
         x = torch.stack(imgs) if isinstance(imgs[0], torch.Tensor) else np.stack(imgs)
+        if len(batch[0]) > 3:
+            return x, gt, gl, _pad_flags([b[3] for b in batch], gl.shape[1])
         return x, gt, gl
 
     for it in items:
