@@ -839,6 +839,44 @@ int ssd_loss(const float* actual_deltas_dev, const float* pred_deltas_dev,
              float* ce_out_dev, float* mask_out_dev, float* grad_deltas_dev, float* grad_logits_dev,
              float grad_scale, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- focal confidence loss: Keras CategoricalFocalCrossentropy(alpha, gamma) ---------------------
+ * The same tensors as ssd_loss; the localisation term is ssd_loss's, the confidence term replaces the hard-negative
+ * mining: every anchor counts.  Per anchor, with q the predicted probabilities and y the target row, in fp32, every
+ * operation rounded on its own (no contraction), sums in class order:
+ *   s   = sum_c q_c
+ *   r_c = clip(q_c / s, 1e-7, 1 - 1e-7)                                 (ssd_loss's renormalise-and-clip)
+ *   f   = sum_c (alpha * (1 - r_c)^gamma) * -(y_c * log r_c)            (a class with y_c == 0 adds exactly 0)
+ * Per image: pos = #{anchors with any y[1:] != 0};  conf_loss[b] = (sum over ALL anchors of f) / (pos == 0 ? 1 : pos),
+ * the sum taken per tile of ssd_focal_loss_tile(L) anchors by a fixed tree, then over the tiles in order by a fixed tree.
+ * ce_out [B,N] <- f; mask_out [B,N] <- 1 (no mining: the final mask is all ones).
+ * Gradients of grad_scale * (loc_loss[b] + conf_loss[b]) w.r.t. pred_deltas and the LOGITS behind pred_labels:
+ *   df/dr_c = (y_c * alpha) * (gamma * ((1 - r)^gamma / (1 - r)) * log r - (1 - r)^gamma / r),  r = q_c / s,
+ *             where r lies in [1e-7, 1 - 1e-7] (bounds included), 0 elsewhere (ssd_loss's rule);
+ *   then through r = q / s and the softmax backward exactly as ssd_loss does with g_c = df/dr_c and
+ *   gce = grad_scale / (pos == 0 ? 1 : pos).
+ *   gamma == 0: the modulating factor is exactly 1 and the first term exactly 0 (no powf is evaluated).
+ * An anchor's bits depend on its own rows and the image's two positive counts, not on the grid; no atomics.
+ * Rows of L <= 119 floats are staged through LDS (coalesced 16-byte accesses); longer rows are read directly.
+ * SSD_E_INVALID, nothing launched: bad sizes, alpha <= 0, gamma < 0, either not finite, neither term given, a gradient
+ * without its target, a workspace below ssd_focal_loss_workspace_bytes(B, N, L), delta tensors not 16-byte aligned.
+ * ssd_focal_loss_tile: anchors per workgroup for this L (*staged_out, nullable: 1 when the rows go through LDS). */
+int ssd_focal_loss_tile(int L, int* staged_out);
+size_t ssd_focal_loss_workspace_bytes(int B, int N, int L);
+int ssd_focal_loss(const float* actual_deltas_dev, const float* pred_deltas_dev,
+                   const float* actual_labels_dev, const float* pred_labels_dev, int B, int N, int L,
+                   float loc_loss_alpha, float focal_alpha, float focal_gamma, float* loc_loss_dev,
+                   float* conf_loss_dev, float* ce_out_dev, float* mask_out_dev, float* grad_deltas_dev,
+                   float* grad_logits_dev, float grad_scale, void* workspace_dev, size_t workspace_bytes,
+                   void* stream);
+
+/* The loss of a training step (ssd_net_train_forward_backward_cfg). */
+#define SSD_LOSS_HARD_NEGATIVE 0   /* ssd_loss: the reference's mining; neg_pos_ratio, loc_loss_alpha          */
+#define SSD_LOSS_FOCAL 1           /* ssd_focal_loss: loc_loss_alpha, focal_alpha (> 0), focal_gamma (>= 0)   */
+typedef struct ssd_loss_config {
+    int kind;
+    float neg_pos_ratio, loc_loss_alpha, focal_alpha, focal_gamma;
+} ssd_loss_config;
+
 /* =====================================================================================
  * Conv family (the TF/Keras ops the models dispatch: SURVEY.md 2.3 K1-K7).
  * All tensors NHWC fp32 on the device.
@@ -1070,6 +1108,14 @@ int ssd_net_train_forward_backward(ssd_net* net, const float* image_dev, int B,
                                    const float* actual_deltas_dev, const float* actual_labels_dev,
                                    float neg_pos_ratio, float loc_loss_alpha, float* grads_flat_dev,
                                    float* loc_loss_dev, float* conf_loss_dev, void* stream);
+/* The same step with the loss chosen by `loss` (SSD_LOSS_*): ssd_net_train_forward_backward is this call with kind
+ * SSD_LOSS_HARD_NEGATIVE and its two numbers, and issues exactly the same launches.  The training state's loss workspace
+ * is planned for the larger of the two losses.  SSD_E_INVALID before any launch: a NULL `loss`, an unknown kind, a focal
+ * alpha <= 0 or gamma < 0. */
+int ssd_net_train_forward_backward_cfg(ssd_net* net, const float* image_dev, int B,
+                                       const float* actual_deltas_dev, const float* actual_labels_dev,
+                                       const ssd_loss_config* loss, float* grads_flat_dev,
+                                       float* loc_loss_dev, float* conf_loss_dev, void* stream);
 /* Gradient buckets for the batch data-parallel step (the reference trains on one device, trainer.py:50-76; the
  * RCCL exchange is this build's SURVEY.md 8e row 2): bucket k = flat offsets [lo[k], lo[k + 1]), lo ascending
  * from 0.  The backward finishes the flat gradient vector from its end (heads first, stem last) and records an

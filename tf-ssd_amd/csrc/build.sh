@@ -31,6 +31,8 @@ compile ssd_core.hip
 compile ssd_bbox.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
 # loss: separately rounded ops too (the hard-negative RANK depends on the per-anchor CE values)
 compile ssd_loss.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
+# focal loss: its stated arithmetic is one rounding per operation (include/ssd_hip.h)
+compile ssd_focal.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
 compile ssd_data.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
 # the augmentation plan: bit-equal to its fp32 NumPy restatement (tests/augment_plan_cases.py)
 compile ssd_augplan.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt

@@ -11,6 +11,7 @@
 // hard negatives, ties AT T are broken by ascending anchor index (tf.argsort DESCENDING orders
 // equal keys by index: top_k semantics) through an ordered ballot/popcount prefix count.
 #include "common.h"
+#include "loss_reduce.h"
 
 namespace ssd {
 
@@ -36,36 +37,9 @@ struct LossParams {
     unsigned char* flags; // workspace [B,N]: bit0 conf-positive, bit1 loc-positive
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// deterministic block sums: per-thread partials (index order), wave butterfly, waves in order
-__device__ float block_sum(float v, float* sh) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = 0.f;
-    for (int w = 0; w < kLossWaves; ++w) t += sh[w];
-    return t;
-}
-__device__ int block_sum_i(int v, int* sh) {
-    v = wave_sum_i(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int t = 0;
-    for (int w = 0; w < kLossWaves; ++w) t += sh[w];
-    return t;
-}
+// wave_sum / block_sum: loss_reduce.h (shared with csrc/ssd_focal.hip), here over the workgroup's kLossWaves waves
+__device__ __forceinline__ float block_sum(float v, float* sh) { return block_sum<kLossWaves>(v, sh); }
+__device__ __forceinline__ int block_sum_i(int v, int* sh) { return block_sum_i<kLossWaves>(v, sh); }
 
 __global__ __launch_bounds__(kLossThreads) void ssd_loss_kernel(const LossParams p) {
     __shared__ float shf[kLossWaves];

@@ -1819,7 +1819,9 @@ static int begin_streams_scratch(const ssd_net* net, ssd_train_state& s, const T
     if (!rc) rc = talloc(s, ((size_t)s.fold_jobs_cap * sizeof(FoldJob) + 3) / 4, &s.fold_jobs);
     if (!rc) rc = opt_alloc_tables(net, s);
     if (rc) return rc;
-    s.loss_ws_bytes = ssd_loss_workspace_bytes(s.batch, net->num_priors);
+    // either loss may be chosen per step: the larger of the two workspaces
+    s.loss_ws_bytes = std::max(ssd_loss_workspace_bytes(s.batch, net->num_priors),
+                               ssd_focal_loss_workspace_bytes(s.batch, net->num_priors, net->L));
     if (hipMalloc(&s.loss_ws, s.loss_ws_bytes) != hipSuccess) {
         set_error("ssd_net_train_begin: loss workspace allocation failed");
         return SSD_E_HIP;
@@ -1915,8 +1917,24 @@ int ssd_net_train_begin(ssd_net* net, int batch) {
 int ssd_net_train_forward_backward(ssd_net* net, const float* image_dev, int B, const float* actual_deltas_dev,
                                    const float* actual_labels_dev, float neg_pos_ratio, float loc_loss_alpha,
                                    float* grads_flat_dev, float* loc_loss_dev, float* conf_loss_dev, void* stream) {
+    const ssd_loss_config loss = {SSD_LOSS_HARD_NEGATIVE, neg_pos_ratio, loc_loss_alpha, 0.25f, 2.0f};
+    return ssd_net_train_forward_backward_cfg(net, image_dev, B, actual_deltas_dev, actual_labels_dev, &loss, grads_flat_dev,
+                                              loc_loss_dev, conf_loss_dev, stream);
+}
+
+// The step with the loss chosen by `loss`: ssd_loss (the reference's mining) or ssd_focal_loss, on the same buffers.
+int ssd_net_train_forward_backward_cfg(ssd_net* net, const float* image_dev, int B, const float* actual_deltas_dev,
+                                       const float* actual_labels_dev, const ssd_loss_config* loss, float* grads_flat_dev,
+                                       float* loc_loss_dev, float* conf_loss_dev, void* stream) {
     SSD_CHECK_ARG(net && image_dev && actual_deltas_dev && actual_labels_dev && grads_flat_dev,
                   "ssd_net_train_forward_backward: NULL argument");
+    SSD_CHECK_ARG(loss, "ssd_net_train_forward_backward_cfg: NULL loss");
+    SSD_CHECK_ARG(loss->kind == SSD_LOSS_HARD_NEGATIVE || loss->kind == SSD_LOSS_FOCAL,
+                  "ssd_net_train_forward_backward_cfg: unknown loss kind %d", loss->kind);
+    SSD_CHECK_ARG(loss->kind != SSD_LOSS_FOCAL || (loss->focal_alpha > 0.f && loss->focal_alpha < INFINITY &&
+                                                   loss->focal_gamma >= 0.f && loss->focal_gamma < INFINITY),
+                  "ssd_net_train_forward_backward_cfg: focal alpha must be > 0 and gamma >= 0 (finite), got alpha=%g gamma=%g",
+                  (double)loss->focal_alpha, (double)loss->focal_gamma);
     if (!net->train) { set_error("ssd_net_train_forward_backward: call ssd_net_train_begin() first"); return SSD_E_STATE; }
     ssd_train_state& s = *net->train;
     SSD_CHECK_ARG(B >= 1 && B <= s.batch, "ssd_net_train_forward_backward: batch %d exceeds the planned %d", B, s.batch);
@@ -1954,9 +1972,14 @@ int ssd_net_train_forward_backward(ssd_net* net, const float* image_dev, int B, 
         if (s.tl[i].active && (rc = train_forward_layer(c, i))) return rc;
     rc = launch_softmax(s.probs, (long)B * N, L, s.probs, st);
     if (rc) return rc;
-    rc = ssd_loss(actual_deltas_dev, s.deltas, actual_labels_dev, s.probs, B, N, L, neg_pos_ratio, loc_loss_alpha,
-                  loc_loss_dev, conf_loss_dev, nullptr, nullptr, s.gdeltas, s.glogits, 1.0f / (float)B, s.loss_ws,
-                  s.loss_ws_bytes, stream);
+    if (loss->kind == SSD_LOSS_FOCAL)
+        rc = ssd_focal_loss(actual_deltas_dev, s.deltas, actual_labels_dev, s.probs, B, N, L, loss->loc_loss_alpha,
+                            loss->focal_alpha, loss->focal_gamma, loc_loss_dev, conf_loss_dev, nullptr, nullptr, s.gdeltas,
+                            s.glogits, 1.0f / (float)B, s.loss_ws, s.loss_ws_bytes, stream);
+    else
+        rc = ssd_loss(actual_deltas_dev, s.deltas, actual_labels_dev, s.probs, B, N, L, loss->neg_pos_ratio,
+                      loss->loc_loss_alpha, loc_loss_dev, conf_loss_dev, nullptr, nullptr, s.gdeltas, s.glogits,
+                      1.0f / (float)B, s.loss_ws, s.loss_ws_bytes, stream);
     if (rc) return rc;
 
     // backward, last layer first

@@ -205,6 +205,23 @@ class SSDModel(object):
             out[lib.ssd_net_layer_name(self._net, i).decode()] = f.value
         return out
 
+    def conf_head_names(self):
+        """The label head convs, ``{i}_conv_label_output``, by level."""
+        return sorted((n for n in self.layer_names() if n.endswith("_conv_label_output")), key=lambda n: int(n.split("_")[0]))
+
+    def set_conf_prior(self, pi):
+        """Writes ``models.header.conf_prior_bias(pi, ...)`` into every label head's bias (through ``set_weights``): each
+        anchor starts at probability ``pi`` of being an object, the initialisation focal loss is normally trained with.
+        Kernels and every other parameter stay as they are.  Returns the names written."""
+        from models.header import conf_prior_bias
+        shapes = dict(self.param_specs)
+        new = {}
+        for layer in self.conf_head_names():
+            name = layer + "/bias"
+            new[name] = conf_prior_bias(pi, self.total_labels, shapes[name][0] // self.total_labels)
+        self.set_weights(new)
+        return sorted(new)
+
     def get_weights(self):
         lib = _h.lib()
         out = {}
@@ -462,7 +479,8 @@ class SSDModel(object):
         (Keras defaults), or None -- Adam (the reference's choice) from ``learning_rate`` / ``beta_1`` / ``beta_2`` /
         ``epsilon``; anything else raises TypeError.  An optimizer of another kind than the one whose slots the net
         holds starts from fresh slots and iteration 0 (Keras' new optimizer at ``compile()``); the same kind keeps them.
-        ``loss`` may be the two bound methods of a ``CustomLoss`` (its ratio / alpha are then used)."""
+        ``loss`` may be the two bound methods of a ``CustomLoss`` (its ratio / alpha are then used) or of a ``FocalLoss``:
+        the object is kept, the training step evaluates its ``ssd_loss_config`` and ``evaluate_on_batch`` calls it."""
         import optimizers
         opt = optimizers.get(optimizer, learning_rate=learning_rate, beta_1=beta_1, beta_2=beta_2, epsilon=epsilon)
         previous = getattr(self, "_optimizer", None)
@@ -475,6 +493,16 @@ class SSDModel(object):
                                     getattr(owner, "neg_pos_ratio", self.hyper_params.get("neg_pos_ratio", 3)))
         self._loc_alpha = float(loc_loss_alpha if loc_loss_alpha is not None else
                                 getattr(owner, "loc_loss_alpha", self.hyper_params.get("loc_loss_alpha", 1)))
+        from ssd_loss import CustomLoss, FocalLoss
+        if isinstance(owner, FocalLoss):
+            if neg_pos_ratio is not None or loc_loss_alpha is not None:
+                raise ValueError("compile: neg_pos_ratio / loc_loss_alpha belong to the mining loss; a FocalLoss brings its own")
+            self._loss = owner
+        else:
+            # the mining loss from the two numbers, as before (whatever object carried them)
+            self._loss = owner if type(owner) is CustomLoss and (owner.neg_pos_ratio, owner.loc_loss_alpha) == (
+                self._neg_pos_ratio, self._loc_alpha) else CustomLoss(self._neg_pos_ratio, self._loc_alpha)
+        self._native_loss = self._loss.to_native()
 
     def trainable_offsets(self):
         """name -> (offset, shape) inside the flat gradient / parameter vector."""
@@ -509,9 +537,9 @@ class SSDModel(object):
             self._grads = torch.empty((P,), dtype=torch.float32, device=x.device)
         loc = torch.empty((B,), dtype=torch.float32, device=x.device)
         conf = torch.empty((B,), dtype=torch.float32, device=x.device)
-        _h.check(lib.ssd_net_train_forward_backward(self._net, _h.ptr(x), B, _h.ptr(yd), _h.ptr(yl),
-                                                    self._neg_pos_ratio, self._loc_alpha, _h.ptr(self._grads),
-                                                    _h.ptr(loc), _h.ptr(conf), _h.stream()), "train_forward_backward")
+        _h.check(lib.ssd_net_train_forward_backward_cfg(self._net, _h.ptr(x), B, _h.ptr(yd), _h.ptr(yl),
+                                                        ctypes.byref(self._native_loss), _h.ptr(self._grads),
+                                                        _h.ptr(loc), _h.ptr(conf), _h.stream()), "train_forward_backward")
         self._last_input = x
         return loc, conf, self._grads
 
@@ -682,10 +710,11 @@ class SSDModel(object):
         return a
 
     def evaluate_on_batch(self, images, targets):
-        """Validation loss of one batch (inference-mode forward + the HIP loss)."""
+        """Validation loss of one batch (inference-mode forward + the compiled HIP loss; nothing compiled: the
+        reference's mining loss at ratio 3, alpha 1)."""
         from ssd_loss import CustomLoss
         d, p = self(images)
-        cl = CustomLoss(getattr(self, "_neg_pos_ratio", 3.0), getattr(self, "_loc_alpha", 1.0))
+        cl = getattr(self, "_loss", None) or CustomLoss(3.0, 1.0)
         lm = float(cl.loc_loss_fn(targets[0], d).mean().item())
         cm = float(cl.conf_loss_fn(targets[1], p).mean().item())
         return lm + cm + self.regularization_loss(), lm, cm

@@ -41,6 +41,23 @@ def head_layout(hyper_params):
     return out, off
 
 
+def conf_prior_bias(pi, total_labels, anchors):
+    """The label head's bias that makes every anchor start at probability ``pi`` of being an object (the prior-probability
+    initialisation focal loss is trained with, RetinaNet section 4.1, for a softmax with a background class): background
+    ``log((1 - pi) * (L - 1) / pi)``, every other class 0, so that with a zero kernel softmax gives the background
+    ``1 - pi`` and each of the ``L - 1`` classes ``pi / (L - 1)``.  Layout of a level's ``{i}_conv_label_output/bias``:
+    ``[anchors * L]``, anchor-major, class 0 the background."""
+    import numpy as np
+    pi, L = float(pi), int(total_labels)
+    if not 0.0 < pi < 1.0:
+        raise ValueError("pi must lie in (0, 1), got %r" % (pi,))
+    if L < 2 or int(anchors) < 1:
+        raise ValueError("need at least 2 labels and 1 anchor, got %r / %r" % (total_labels, anchors))
+    bias = np.zeros((int(anchors), L), np.float32)
+    bias[:, 0] = np.float32(np.log((1.0 - pi) * (L - 1) / pi))
+    return bias.reshape(-1)
+
+
 def get_head_from_outputs(hyper_params, outputs, weights=None, seed=0):
     """reference models/header.py:43-67: per level ``Conv2D(A*L, 3x3, same)`` (labels) and
     ``Conv2D(A*4, 3x3, same)`` (boxes) on the feature map, HeadWrapper merge, softmax on the

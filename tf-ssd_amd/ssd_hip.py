@@ -96,10 +96,17 @@ class Optimizer(ctypes.Structure):
                 ("clipvalue", ctypes.c_float), ("global_clipnorm", ctypes.c_float)]
 
 
+class LossConfig(ctypes.Structure):
+    """struct ssd_loss_config (include/ssd_hip.h): the loss ``ssd_net_train_forward_backward_cfg`` evaluates."""
+    _fields_ = [("kind", ctypes.c_int), ("neg_pos_ratio", ctypes.c_float), ("loc_loss_alpha", ctypes.c_float),
+                ("focal_alpha", ctypes.c_float), ("focal_gamma", ctypes.c_float)]
+
+
 JPEG_COEFFICIENTS, JPEG_RAW = 0, 1
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
 MOBILENET_V2, VGG16 = 0, 1
 OPT_ADAM, OPT_SGD = 0, 1
+LOSS_HARD_NEGATIVE, LOSS_FOCAL = 0, 1       # SSD_LOSS_*
 EVAL_RULE_VOC, EVAL_RULE_COCO = 0, 1        # SSD_EVAL_RULE_*
 # SSD_PLAN_*: the bits of ssd_net_train_plan
 PLAN_WGRAD, PLAN_WGRAD2, PLAN_DGRAD, PLAN_RESGRAD, PLAN_BN_BATCH, PLAN_BN_PARAMS, PLAN_SKIP = 1, 2, 4, 8, 16, 32, 64
@@ -177,6 +184,11 @@ _SIGNATURES = {
     "ssd_loss_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "ssd_loss": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                 ctypes.c_float, vp, vp, vp, vp, vp, vp, ctypes.c_float, vp, ctypes.c_size_t, vp]),
+    "ssd_focal_loss_tile": (ctypes.c_int, [ctypes.c_int, c_int_p]),
+    "ssd_focal_loss_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "ssd_focal_loss": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                                      ctypes.c_float, ctypes.c_float, vp, vp, vp, vp, vp, vp, ctypes.c_float, vp,
+                                      ctypes.c_size_t, vp]),
     "ssd_same_pads": (ctypes.c_int, [ctypes.c_int] * 4 + [c_int_p, c_int_p]),
     "ssd_conv_out_size": (ctypes.c_int, [ctypes.c_int] * 6),
     "ssd_conv_packed_weight_floats": (ctypes.c_size_t, [ctypes.c_int] * 4),
@@ -243,6 +255,7 @@ _SIGNATURES = {
     "ssd_net_trainable_offset": (ctypes.c_long, [vp, ctypes.c_char_p]),
     "ssd_net_train_forward_backward": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp, ctypes.c_float, ctypes.c_float,
                                                       vp, vp, vp, vp]),
+    "ssd_net_train_forward_backward_cfg": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp, ctypes.POINTER(LossConfig), vp, vp, vp, vp]),
     "ssd_net_adam_step": (ctypes.c_int, [vp, vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                          ctypes.c_float, vp]),
     "ssd_net_optimizer_step": (ctypes.c_int, [vp, vp, ctypes.POINTER(Optimizer), ctypes.c_float, ctypes.c_float, vp]),

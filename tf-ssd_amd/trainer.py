@@ -20,7 +20,10 @@ model path is loaded before training); ``SSD_TRAINER_FREEZE`` (empty by default)
 comma-separated ``fnmatch`` patterns over the Keras layer names (``model.set_trainable``).
 Optimizer: ``SSD_TRAINER_OPTIMIZER`` (``adam`` | ``sgd``), ``SSD_TRAINER_MOMENTUM``, ``SSD_TRAINER_NESTEROV``,
 ``SSD_TRAINER_CLIPNORM``, ``SSD_TRAINER_CLIPVALUE``, ``SSD_TRAINER_GLOBAL_CLIPNORM`` (``optimizer_from_env``); with none
-of them set the run is the reference's ``Adam(1e-3)``."""
+of them set the run is the reference's ``Adam(1e-3)``.
+Loss: ``SSD_TRAINER_LOSS`` (``hard`` | ``focal``), ``SSD_TRAINER_FOCAL_ALPHA`` (0.25), ``SSD_TRAINER_FOCAL_GAMMA`` (2.0)
+(``loss_from_env``); unset: the reference's hard-negative mining.  ``SSD_TRAINER_FOCAL_PRIOR`` (off by default) = pi
+writes the prior-probability bias into the label heads after ``init_model`` (``model.set_conf_prior``)."""
 import json
 import os
 import sys
@@ -31,7 +34,7 @@ if _HERE not in sys.path:
     sys.path.insert(0, _HERE)
 
 import parallel  # noqa: E402
-from ssd_loss import CustomLoss  # noqa: E402
+from ssd_loss import CustomLoss, FocalLoss  # noqa: E402
 from utils import bbox_utils, data_utils, io_utils, train_utils, voc_utils  # noqa: E402
 
 with_voc_2012 = True
@@ -134,6 +137,23 @@ def optimizer_from_env():
     raise ValueError("SSD_TRAINER_OPTIMIZER must be 'adam' or 'sgd', got %r" % kind)
 
 
+def loss_from_env(hyper_params):
+    """``SSD_TRAINER_LOSS`` = ``hard`` (default: the reference's ``CustomLoss(neg_pos_ratio, loc_loss_alpha)``) | ``focal``
+    (``FocalLoss(loc_loss_alpha, SSD_TRAINER_FOCAL_ALPHA or 0.25, SSD_TRAINER_FOCAL_GAMMA or 2.0)``).  ValueError for another
+    kind, for a number that does not parse or lies outside its range, and for a focal knob set beside the mining loss."""
+    env = os.environ
+    kind = env.get("SSD_TRAINER_LOSS", "").strip().lower() or "hard"
+    knobs = {k: env.get("SSD_TRAINER_FOCAL_" + k, "").strip() for k in ("ALPHA", "GAMMA")}
+    if kind == "hard":
+        used = sorted("SSD_TRAINER_FOCAL_" + k for k, v in knobs.items() if v)
+        if used:
+            raise ValueError("%s set, but SSD_TRAINER_LOSS is not 'focal'" % ", ".join(used))
+        return CustomLoss(hyper_params["neg_pos_ratio"], hyper_params["loc_loss_alpha"])
+    if kind == "focal":
+        return FocalLoss(hyper_params["loc_loss_alpha"], alpha=knobs["ALPHA"] or 0.25, gamma=knobs["GAMMA"] or 2.0)
+    raise ValueError("SSD_TRAINER_LOSS must be 'hard' or 'focal', got %r" % kind)
+
+
 def main(argv=None):
     args = io_utils.handle_args(argv)
     if args.handle_gpu:
@@ -187,12 +207,23 @@ def main(argv=None):
                                                      seed=777 + 1000 * rank))
 
     ssd_model = get_model(hyper_params, max_batch=batch_size)
-    ssd_custom_losses = CustomLoss(hyper_params["neg_pos_ratio"], hyper_params["loc_loss_alpha"])
+    ssd_custom_losses = loss_from_env(hyper_params)
     optimizer = optimizer_from_env()
     ssd_model.compile(optimizer=optimizer, learning_rate=1e-3, loss=[ssd_custom_losses.loc_loss_fn, ssd_custom_losses.conf_loss_fn])
     if optimizer is not None and rank == 0:
         print("optimizer: %r" % (optimizer,), flush=True)
+    if isinstance(ssd_custom_losses, FocalLoss) and rank == 0:
+        print("loss: %r" % (ssd_custom_losses,), flush=True)
     init_model(ssd_model)
+    focal_prior = os.environ.get("SSD_TRAINER_FOCAL_PRIOR", "").strip()
+    if focal_prior:
+        try:
+            pi = float(focal_prior)
+        except ValueError:
+            raise ValueError("SSD_TRAINER_FOCAL_PRIOR must be a number in (0, 1), got %r" % focal_prior)
+        ssd_model.set_conf_prior(pi)
+        if rank == 0:
+            print("label heads: prior probability %g" % pi, flush=True)
     ssd_model_path = io_utils.get_model_path(backbone)
     if load_weights:
         ssd_model.load_weights(ssd_model_path)
