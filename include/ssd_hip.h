@@ -869,13 +869,61 @@ int ssd_focal_loss(const float* actual_deltas_dev, const float* pred_deltas_dev,
                    float* grad_logits_dev, float grad_scale, void* workspace_dev, size_t workspace_bytes,
                    void* stream);
 
+/* ---- IoU-family localisation losses: IoU / GIoU / DIoU / CIoU on the decoded boxes ----------------
+ * The delta tensors of ssd_loss, plus priors [N,4] (y1,x1,y2,x2) on the device and variances[4] on the host; replaces
+ * only the localisation term.  Per anchor, t is the box decoded from actual_deltas and b the box decoded from
+ * pred_deltas, both by ssd_decode_boxes' arithmetic with `var` (utils/bbox_utils.py:61-85 on deltas * variances):
+ *   h = exp(dh*vh)*ph,  cy = dy*vy*ph + pcy,  y1 = cy - 0.5h,  y2 = h + y1,  likewise for x; nothing is clamped.
+ * In fp32, every operation rounded on its own (no contraction), eps = 1e-7:
+ *   inter = max(min(y2,ty2) - max(y1,ty1), 0) * max(min(x2,tx2) - max(x1,tx1), 0)
+ *   union = ((y2-y1)(x2-x1) + (ty2-ty1)(tx2-tx1)) - inter;           iou = inter / (union + eps)
+ *   ch = max(y2,ty2) - min(y1,ty1), cw likewise, ac = ch*cw          (the enclosing box)
+ *   rho2 = ((y1+y2)/2 - (ty1+ty2)/2)^2 + ((x1+x2)/2 - (tx1+tx2)/2)^2;   c2 = (ch*ch + cw*cw) + eps
+ *   v = (4/pi^2) * (atan(tw/th) - atan(w/h))^2  with w = x2-x1, h = y2-y1;   a = v / (((1 - iou) + v) + eps)
+ *   SSD_LOC_IOU   l = 1 - iou
+ *   SSD_LOC_GIOU  l = 1 - (iou - (ac - union) / (ac + eps))
+ *   SSD_LOC_DIOU  l = (1 - iou) + rho2/c2
+ *   SSD_LOC_CIOU  l = ((1 - iou) + rho2/c2) + a*v
+ * (torchvision.ops' generalized_ / distance_ / complete_box_iou_loss with the boxes in (y1,x1,y2,x2) order.)
+ * Per image: positives are the anchors with any non-zero actual delta (ssd_loss's rule);
+ *   loc_loss[b] = (sum over the positives of l) / (pos == 0 ? 1 : pos) * loc_loss_alpha,
+ * the sum taken per tile of ssd_iou_loc_loss_tile() anchors by a fixed tree, then over the tiles in order by a fixed tree.
+ * per_anchor_out [B,N] (nullable) <- l for a positive, 0 for every other anchor.
+ * grad_deltas [B,N,4] (nullable) <- the analytic gradient of grad_scale * loc_loss[b] w.r.t. pred_deltas, through the box
+ * terms and the decode (exp and the variances included); exactly 0.0f for every anchor that is not positive.
+ * Subgradients: min(p, q) / max(p, q) with p the prediction's coordinate pass the gradient to p at a tie (p == q), so a
+ * prediction equal to its target gets a finite one-sided gradient; max(x, 0) passes it where x > 0; CIoU's `a` is a
+ * constant in the backward (the usual stop-gradient).
+ * An anchor's bits depend on its own rows and the image's positive count, not on the grid; no atomics.
+ * SSD_E_INVALID, nothing launched: bad sizes, a mode outside SSD_LOC_IOU .. SSD_LOC_CIOU, variances NULL, not finite or
+ * <= 0, priors NULL, a gradient without the target, actual_deltas or pred_deltas NULL, a workspace below
+ * ssd_iou_loc_loss_workspace_bytes(B, N), priors or delta tensors not 16-byte aligned.  B == 0: SSD_OK, nothing written. */
+#define SSD_LOC_HUBER 0            /* the reference's Huber loss on the encoded deltas (ssd_loss / ssd_focal_loss) */
+#define SSD_LOC_IOU 1
+#define SSD_LOC_GIOU 2
+#define SSD_LOC_DIOU 3
+#define SSD_LOC_CIOU 4
+int ssd_iou_loc_loss_tile(void);
+size_t ssd_iou_loc_loss_workspace_bytes(int B, int N);
+int ssd_iou_loc_loss(const float* priors_dev, const float* variances, const float* actual_deltas_dev,
+                     const float* pred_deltas_dev, int B, int N, int mode, float loc_loss_alpha,
+                     float* loc_loss_dev, float* per_anchor_out_dev, float* grad_deltas_dev, float grad_scale,
+                     void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* The loss of a training step (ssd_net_train_forward_backward_cfg). */
 #define SSD_LOSS_HARD_NEGATIVE 0   /* ssd_loss: the reference's mining; neg_pos_ratio, loc_loss_alpha          */
 #define SSD_LOSS_FOCAL 1           /* ssd_focal_loss: loc_loss_alpha, focal_alpha (> 0), focal_gamma (>= 0)   */
 typedef struct ssd_loss_config {
     int kind;
     float neg_pos_ratio, loc_loss_alpha, focal_alpha, focal_gamma;
+    /* the localisation term (SSD_LOC_*); a zero-filled tail is SSD_LOC_HUBER, the term of `kind`'s own kernel.  Another
+     * value: the confidence term alone comes from `kind`'s kernel and ssd_iou_loc_loss(priors_dev [num_priors,4],
+     * variances, mode = loc_kind) writes the localisation loss and its gradient. */
+    int loc_kind;
+    const float* priors_dev;
+    float variances[4];
 } ssd_loss_config;
+size_t ssd_loss_config_bytes(void);      /* sizeof(ssd_loss_config) of this library (for mirrors of the struct) */
 
 /* =====================================================================================
  * Conv family (the TF/Keras ops the models dispatch: SURVEY.md 2.3 K1-K7).
@@ -1110,8 +1158,10 @@ int ssd_net_train_forward_backward(ssd_net* net, const float* image_dev, int B,
                                    float* loc_loss_dev, float* conf_loss_dev, void* stream);
 /* The same step with the loss chosen by `loss` (SSD_LOSS_*): ssd_net_train_forward_backward is this call with kind
  * SSD_LOSS_HARD_NEGATIVE and its two numbers, and issues exactly the same launches.  The training state's loss workspace
- * is planned for the larger of the two losses.  SSD_E_INVALID before any launch: a NULL `loss`, an unknown kind, a focal
- * alpha <= 0 or gamma < 0. */
+ * is planned for the largest of the losses.  SSD_E_INVALID before any launch: a NULL `loss`, an unknown kind, a focal
+ * alpha <= 0 or gamma < 0, a loc_kind outside SSD_LOC_HUBER .. SSD_LOC_CIOU, and beside a loc_kind other than
+ * SSD_LOC_HUBER NULL or misaligned priors or variances that are not finite and > 0.  With loc_kind == SSD_LOC_HUBER the
+ * launches are exactly those of the struct's first five fields. */
 int ssd_net_train_forward_backward_cfg(ssd_net* net, const float* image_dev, int B,
                                        const float* actual_deltas_dev, const float* actual_labels_dev,
                                        const ssd_loss_config* loss, float* grads_flat_dev,

@@ -33,6 +33,8 @@ compile ssd_bbox.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
 compile ssd_loss.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
 # focal loss: its stated arithmetic is one rounding per operation (include/ssd_hip.h)
 compile ssd_focal.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
+# IoU-family localisation losses: one rounding per operation as well
+compile ssd_iouloss.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
 compile ssd_data.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
 # the augmentation plan: bit-equal to its fp32 NumPy restatement (tests/augment_plan_cases.py)
 compile ssd_augplan.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt

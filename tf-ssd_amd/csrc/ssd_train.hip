@@ -1819,9 +1819,11 @@ static int begin_streams_scratch(const ssd_net* net, ssd_train_state& s, const T
     if (!rc) rc = talloc(s, ((size_t)s.fold_jobs_cap * sizeof(FoldJob) + 3) / 4, &s.fold_jobs);
     if (!rc) rc = opt_alloc_tables(net, s);
     if (rc) return rc;
-    // either loss may be chosen per step: the larger of the two workspaces
-    s.loss_ws_bytes = std::max(ssd_loss_workspace_bytes(s.batch, net->num_priors),
-                               ssd_focal_loss_workspace_bytes(s.batch, net->num_priors, net->L));
+    // any loss may be chosen per step: the largest of the workspaces (the IoU localisation term runs behind the
+    // confidence term on the same stream and takes the workspace over)
+    s.loss_ws_bytes = std::max({ssd_loss_workspace_bytes(s.batch, net->num_priors),
+                                ssd_focal_loss_workspace_bytes(s.batch, net->num_priors, net->L),
+                                ssd_iou_loc_loss_workspace_bytes(s.batch, net->num_priors)});
     if (hipMalloc(&s.loss_ws, s.loss_ws_bytes) != hipSuccess) {
         set_error("ssd_net_train_begin: loss workspace allocation failed");
         return SSD_E_HIP;
@@ -1917,12 +1919,20 @@ int ssd_net_train_begin(ssd_net* net, int batch) {
 int ssd_net_train_forward_backward(ssd_net* net, const float* image_dev, int B, const float* actual_deltas_dev,
                                    const float* actual_labels_dev, float neg_pos_ratio, float loc_loss_alpha,
                                    float* grads_flat_dev, float* loc_loss_dev, float* conf_loss_dev, void* stream) {
-    const ssd_loss_config loss = {SSD_LOSS_HARD_NEGATIVE, neg_pos_ratio, loc_loss_alpha, 0.25f, 2.0f};
+    ssd_loss_config loss = {};               // the zero-filled tail: SSD_LOC_HUBER, this kernel's own localisation term
+    loss.kind = SSD_LOSS_HARD_NEGATIVE;
+    loss.neg_pos_ratio = neg_pos_ratio;
+    loss.loc_loss_alpha = loc_loss_alpha;
+    loss.focal_alpha = 0.25f;
+    loss.focal_gamma = 2.0f;
     return ssd_net_train_forward_backward_cfg(net, image_dev, B, actual_deltas_dev, actual_labels_dev, &loss, grads_flat_dev,
                                               loc_loss_dev, conf_loss_dev, stream);
 }
 
-// The step with the loss chosen by `loss`: ssd_loss (the reference's mining) or ssd_focal_loss, on the same buffers.
+size_t ssd_loss_config_bytes(void) { return sizeof(ssd_loss_config); }
+
+// The step with the loss chosen by `loss`: ssd_loss (the reference's mining) or ssd_focal_loss, on the same buffers; with
+// a loc_kind other than SSD_LOC_HUBER that kernel evaluates the confidence term alone and ssd_iou_loc_loss the other.
 int ssd_net_train_forward_backward_cfg(ssd_net* net, const float* image_dev, int B, const float* actual_deltas_dev,
                                        const float* actual_labels_dev, const ssd_loss_config* loss, float* grads_flat_dev,
                                        float* loc_loss_dev, float* conf_loss_dev, void* stream) {
@@ -1935,6 +1945,17 @@ int ssd_net_train_forward_backward_cfg(ssd_net* net, const float* image_dev, int
                                                    loss->focal_gamma >= 0.f && loss->focal_gamma < INFINITY),
                   "ssd_net_train_forward_backward_cfg: focal alpha must be > 0 and gamma >= 0 (finite), got alpha=%g gamma=%g",
                   (double)loss->focal_alpha, (double)loss->focal_gamma);
+    SSD_CHECK_ARG(loss->loc_kind >= SSD_LOC_HUBER && loss->loc_kind <= SSD_LOC_CIOU,
+                  "ssd_net_train_forward_backward_cfg: unknown loc_kind %d", loss->loc_kind);
+    const bool iou_loc = loss->loc_kind != SSD_LOC_HUBER;
+    if (iou_loc) {
+        SSD_CHECK_ARG(loss->priors_dev && ((uintptr_t)loss->priors_dev & 15) == 0,
+                      "ssd_net_train_forward_backward_cfg: loc_kind %d needs priors (16-byte aligned)", loss->loc_kind);
+        for (int k = 0; k < 4; ++k)
+            SSD_CHECK_ARG(loss->variances[k] > 0.f && loss->variances[k] < INFINITY,
+                          "ssd_net_train_forward_backward_cfg: variances must be > 0 and finite, got variances[%d]=%g", k,
+                          (double)loss->variances[k]);
+    }
     if (!net->train) { set_error("ssd_net_train_forward_backward: call ssd_net_train_begin() first"); return SSD_E_STATE; }
     ssd_train_state& s = *net->train;
     SSD_CHECK_ARG(B >= 1 && B <= s.batch, "ssd_net_train_forward_backward: batch %d exceeds the planned %d", B, s.batch);
@@ -1972,7 +1993,20 @@ int ssd_net_train_forward_backward_cfg(ssd_net* net, const float* image_dev, int
         if (s.tl[i].active && (rc = train_forward_layer(c, i))) return rc;
     rc = launch_softmax(s.probs, (long)B * N, L, s.probs, st);
     if (rc) return rc;
-    if (loss->kind == SSD_LOSS_FOCAL)
+    if (iou_loc) {
+        if (loss->kind == SSD_LOSS_FOCAL)
+            rc = ssd_focal_loss(nullptr, nullptr, actual_labels_dev, s.probs, B, N, L, loss->loc_loss_alpha, loss->focal_alpha,
+                                loss->focal_gamma, nullptr, conf_loss_dev, nullptr, nullptr, nullptr, s.glogits,
+                                1.0f / (float)B, s.loss_ws, s.loss_ws_bytes, stream);
+        else
+            rc = ssd_loss(nullptr, nullptr, actual_labels_dev, s.probs, B, N, L, loss->neg_pos_ratio, loss->loc_loss_alpha,
+                          nullptr, conf_loss_dev, nullptr, nullptr, nullptr, s.glogits, 1.0f / (float)B, s.loss_ws,
+                          s.loss_ws_bytes, stream);
+        if (rc) return rc;
+        rc = ssd_iou_loc_loss(loss->priors_dev, loss->variances, actual_deltas_dev, s.deltas, B, N, loss->loc_kind,
+                              loss->loc_loss_alpha, loc_loss_dev, nullptr, s.gdeltas, 1.0f / (float)B, s.loss_ws,
+                              s.loss_ws_bytes, stream);
+    } else if (loss->kind == SSD_LOSS_FOCAL)
         rc = ssd_focal_loss(actual_deltas_dev, s.deltas, actual_labels_dev, s.probs, B, N, L, loss->loc_loss_alpha,
                             loss->focal_alpha, loss->focal_gamma, loc_loss_dev, conf_loss_dev, nullptr, nullptr, s.gdeltas,
                             s.glogits, 1.0f / (float)B, s.loss_ws, s.loss_ws_bytes, stream);

@@ -480,7 +480,8 @@ class SSDModel(object):
         ``epsilon``; anything else raises TypeError.  An optimizer of another kind than the one whose slots the net
         holds starts from fresh slots and iteration 0 (Keras' new optimizer at ``compile()``); the same kind keeps them.
         ``loss`` may be the two bound methods of a ``CustomLoss`` (its ratio / alpha are then used) or of a ``FocalLoss``:
-        the object is kept, the training step evaluates its ``ssd_loss_config`` and ``evaluate_on_batch`` calls it."""
+        the object is kept, the training step evaluates its ``ssd_loss_config`` and ``evaluate_on_batch`` calls it.  An
+        ``IoULocLoss`` (an IoU-family localisation term over either of the two) is kept the same way."""
         import optimizers
         opt = optimizers.get(optimizer, learning_rate=learning_rate, beta_1=beta_1, beta_2=beta_2, epsilon=epsilon)
         previous = getattr(self, "_optimizer", None)
@@ -493,10 +494,15 @@ class SSDModel(object):
                                     getattr(owner, "neg_pos_ratio", self.hyper_params.get("neg_pos_ratio", 3)))
         self._loc_alpha = float(loc_loss_alpha if loc_loss_alpha is not None else
                                 getattr(owner, "loc_loss_alpha", self.hyper_params.get("loc_loss_alpha", 1)))
-        from ssd_loss import CustomLoss, FocalLoss
-        if isinstance(owner, FocalLoss):
+        from ssd_loss import CustomLoss, FocalLoss, IoULocLoss
+        if isinstance(owner, (FocalLoss, IoULocLoss)):
             if neg_pos_ratio is not None or loc_loss_alpha is not None:
-                raise ValueError("compile: neg_pos_ratio / loc_loss_alpha belong to the mining loss; a FocalLoss brings its own")
+                raise ValueError("compile: neg_pos_ratio / loc_loss_alpha belong to the mining loss; a %s brings its own" %
+                                 type(owner).__name__)
+            if isinstance(owner, IoULocLoss) and owner.num_priors != self.num_priors:
+                # the training step reads one prior row per anchor of THIS model through a bare pointer
+                raise ValueError("compile: the IoULocLoss holds %d prior boxes, the model has %d anchors" % (
+                    owner.num_priors, self.num_priors))
             self._loss = owner
         else:
             # the mining loss from the two numbers, as before (whatever object carried them)

@@ -99,7 +99,9 @@ class Optimizer(ctypes.Structure):
 class LossConfig(ctypes.Structure):
     """struct ssd_loss_config (include/ssd_hip.h): the loss ``ssd_net_train_forward_backward_cfg`` evaluates."""
     _fields_ = [("kind", ctypes.c_int), ("neg_pos_ratio", ctypes.c_float), ("loc_loss_alpha", ctypes.c_float),
-                ("focal_alpha", ctypes.c_float), ("focal_gamma", ctypes.c_float)]
+                ("focal_alpha", ctypes.c_float), ("focal_gamma", ctypes.c_float),
+                # the localisation term: zero-filled (five positional values) is LOC_HUBER, the term of ``kind``'s own kernel
+                ("loc_kind", ctypes.c_int), ("priors_dev", ctypes.c_void_p), ("variances", ctypes.c_float * 4)]
 
 
 JPEG_COEFFICIENTS, JPEG_RAW = 0, 1
@@ -107,6 +109,7 @@ ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
 MOBILENET_V2, VGG16 = 0, 1
 OPT_ADAM, OPT_SGD = 0, 1
 LOSS_HARD_NEGATIVE, LOSS_FOCAL = 0, 1       # SSD_LOSS_*
+LOC_HUBER, LOC_IOU, LOC_GIOU, LOC_DIOU, LOC_CIOU = 0, 1, 2, 3, 4        # SSD_LOC_*
 EVAL_RULE_VOC, EVAL_RULE_COCO = 0, 1        # SSD_EVAL_RULE_*
 # SSD_PLAN_*: the bits of ssd_net_train_plan
 PLAN_WGRAD, PLAN_WGRAD2, PLAN_DGRAD, PLAN_RESGRAD, PLAN_BN_BATCH, PLAN_BN_PARAMS, PLAN_SKIP = 1, 2, 4, 8, 16, 32, 64
@@ -189,6 +192,11 @@ _SIGNATURES = {
     "ssd_focal_loss": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                       ctypes.c_float, ctypes.c_float, vp, vp, vp, vp, vp, vp, ctypes.c_float, vp,
                                       ctypes.c_size_t, vp]),
+    "ssd_iou_loc_loss_tile": (ctypes.c_int, []),
+    "ssd_iou_loc_loss_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "ssd_iou_loc_loss": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float), vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_float, vp, vp, vp, ctypes.c_float, vp, ctypes.c_size_t, vp]),
+    "ssd_loss_config_bytes": (ctypes.c_size_t, []),
     "ssd_same_pads": (ctypes.c_int, [ctypes.c_int] * 4 + [c_int_p, c_int_p]),
     "ssd_conv_out_size": (ctypes.c_int, [ctypes.c_int] * 6),
     "ssd_conv_packed_weight_floats": (ctypes.c_size_t, [ctypes.c_int] * 4),

@@ -23,7 +23,9 @@ Optimizer: ``SSD_TRAINER_OPTIMIZER`` (``adam`` | ``sgd``), ``SSD_TRAINER_MOMENTU
 of them set the run is the reference's ``Adam(1e-3)``.
 Loss: ``SSD_TRAINER_LOSS`` (``hard`` | ``focal``), ``SSD_TRAINER_FOCAL_ALPHA`` (0.25), ``SSD_TRAINER_FOCAL_GAMMA`` (2.0)
 (``loss_from_env``); unset: the reference's hard-negative mining.  ``SSD_TRAINER_FOCAL_PRIOR`` (off by default) = pi
-writes the prior-probability bias into the label heads after ``init_model`` (``model.set_conf_prior``)."""
+writes the prior-probability bias into the label heads after ``init_model`` (``model.set_conf_prior``).
+``SSD_TRAINER_LOC_LOSS`` (``huber`` | ``iou`` | ``giou`` | ``diou`` | ``ciou``, ``loc_loss_from_env``) puts an IoU-family loss on
+the decoded boxes in place of the Huber localisation term of either; unset: the reference's Huber term."""
 import json
 import os
 import sys
@@ -34,7 +36,7 @@ if _HERE not in sys.path:
     sys.path.insert(0, _HERE)
 
 import parallel  # noqa: E402
-from ssd_loss import CustomLoss, FocalLoss  # noqa: E402
+from ssd_loss import CustomLoss, FocalLoss, IoULocLoss  # noqa: E402
 from utils import bbox_utils, data_utils, io_utils, train_utils, voc_utils  # noqa: E402
 
 with_voc_2012 = True
@@ -154,6 +156,18 @@ def loss_from_env(hyper_params):
     raise ValueError("SSD_TRAINER_LOSS must be 'hard' or 'focal', got %r" % kind)
 
 
+def loc_loss_from_env(base, prior_boxes, hyper_params):
+    """``SSD_TRAINER_LOC_LOSS`` = ``huber`` (default: ``base`` itself, the Huber term of the reference) | ``iou`` | ``giou`` |
+    ``diou`` | ``ciou`` (``IoULocLoss(base, prior_boxes, hyper_params["variances"], mode)``: that loss on the decoded boxes,
+    ``base``'s confidence term).  ValueError for anything else."""
+    mode = os.environ.get("SSD_TRAINER_LOC_LOSS", "").strip().lower() or "huber"
+    if mode == "huber":
+        return base
+    if mode in ("iou", "giou", "diou", "ciou"):
+        return IoULocLoss(base, prior_boxes, hyper_params["variances"], mode=mode)
+    raise ValueError("SSD_TRAINER_LOC_LOSS must be 'huber', 'iou', 'giou', 'diou' or 'ciou', got %r" % mode)
+
+
 def main(argv=None):
     args = io_utils.handle_args(argv)
     if args.handle_gpu:
@@ -207,12 +221,13 @@ def main(argv=None):
                                                      seed=777 + 1000 * rank))
 
     ssd_model = get_model(hyper_params, max_batch=batch_size)
-    ssd_custom_losses = loss_from_env(hyper_params)
+    prior_boxes = bbox_utils.generate_prior_boxes(hyper_params["feature_map_shapes"], hyper_params["aspect_ratios"])
+    ssd_custom_losses = loc_loss_from_env(loss_from_env(hyper_params), prior_boxes, hyper_params)
     optimizer = optimizer_from_env()
     ssd_model.compile(optimizer=optimizer, learning_rate=1e-3, loss=[ssd_custom_losses.loc_loss_fn, ssd_custom_losses.conf_loss_fn])
     if optimizer is not None and rank == 0:
         print("optimizer: %r" % (optimizer,), flush=True)
-    if isinstance(ssd_custom_losses, FocalLoss) and rank == 0:
+    if isinstance(ssd_custom_losses, (FocalLoss, IoULocLoss)) and rank == 0:
         print("loss: %r" % (ssd_custom_losses,), flush=True)
     init_model(ssd_model)
     focal_prior = os.environ.get("SSD_TRAINER_FOCAL_PRIOR", "").strip()
@@ -233,7 +248,6 @@ def main(argv=None):
         if rank == 0:
             print("frozen: %d layers (%s)" % (len(frozen), freeze), flush=True)
     ssd_log_path = io_utils.get_log_path(backbone)
-    prior_boxes = bbox_utils.generate_prior_boxes(hyper_params["feature_map_shapes"], hyper_params["aspect_ratios"])
     # reference trainer.py:42: the TRAINING stream is augmented (fresh draws every epoch), the validation stream is not.
     # SSD_TRAINER_AUGMENT=0 turns it off (deterministic smoke runs).
     if augment:
