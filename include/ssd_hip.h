@@ -92,6 +92,61 @@ int ssd_combined_nms(const float* boxes_dev, const float* scores_dev, int B, int
                      float* classes_out_dev, int* valid_dev, int* kept_idx_dev,
                      void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- Soft-NMS and class-agnostic suppression: the same two post-processors behind one config -------------------------
+ * Soft-NMS (Bodla et al. 2017) in the form of tf.image.non_max_suppression_with_scores (its V5 kernel: the Gaussian weight
+ * exp(-0.5 / soft_nms_sigma * iou^2), strict '>' everywhere); class_agnostic pools the classes of an image into ONE list,
+ * so an anchor's box suppresses (or decays) its own other classes and an overlapping box of any class.
+ *
+ * Candidates: (anchor i, class c, score s) with s > score_threshold (strict: a NaN score is never a candidate); in the decoder
+ * form after the "argmax == 0 zeroes the row" mask, class 0 of an unmasked row being an ordinary class -- exactly the
+ * candidates of ssd_decode_nms / ssd_combined_nms.  One list per (image, class), or one per image when class_agnostic.
+ *
+ *   limit = per class: min(max_per_class, N)      class-agnostic: min(max_per_class, max_total, candidates)
+ *   while selected < limit and a candidate is alive:
+ *       w = the alive candidate with the largest CURRENT score (ties: lower anchor index, then lower class index)
+ *       emit (w, current score of w); w leaves the list
+ *       for every alive j:                            o = IoU(box[j], box[w]), the helper of the hard NMS, boxes unclipped
+ *           SSD_NMS_HARD:      if o > iou_threshold: j leaves
+ *           SSD_NMS_LINEAR:    if o > iou_threshold: s[j] = s[j] * (1.0f - o)
+ *           SSD_NMS_GAUSSIAN:  s[j] = s[j] * expf((scale * o) * o)          scale = -0.5f / sigma, one float division (host)
+ *           LINEAR / GAUSSIAN: if !(s[j] > score_threshold): j leaves
+ *
+ * Every operation is fp32 and rounded on its own (no contraction, correctly rounded division, expf and not the fast
+ * intrinsic); a candidate receives its decays in selection order, oldest first -- that order defines the bits.  The emitted
+ * scores are the decayed ones, non-increasing within a list.  The per-image merge is ssd_decode_nms's: the emitted rows sorted
+ * by (score desc, anchor asc, class asc), the first max_total kept, zero padding, valid and kept_idx as there (a class-agnostic
+ * list already is in that order).  The decoder forms clip the boxes to [0,1] whatever clip_boxes says (SSDDecoder always
+ * does); ssd_combined_nms_cfg honours it.
+ *
+ * SSD_NMS_HARD with class_agnostic == 0 IS ssd_decode_nms / ssd_combined_nms: the same launches, the same bits.  Everything
+ * else runs the selection kernel (csrc/ssd_bbox.hip soft_nms_kernel): lists of up to ssd_nms_lds_candidates() candidates are
+ * held in LDS, longer ones in the workspace.  SSD_E_INVALID: an unknown method, SSD_NMS_GAUSSIAN with sigma not finite or
+ * <= 0, iou_threshold NaN or outside [0,1], and the size checks of ssd_decode_nms; its LDS limit on max_per_class still
+ * answers SSD_E_UNSUPPORTED. */
+#define SSD_NMS_HARD 0
+#define SSD_NMS_GAUSSIAN 1
+#define SSD_NMS_LINEAR 2
+typedef struct ssd_nms_config {
+    int method;             /* SSD_NMS_* */
+    int class_agnostic;     /* 0: one list per (image, class); otherwise one list per image */
+    int max_per_class;
+    int max_total;
+    int clip_boxes;         /* ssd_combined_nms_cfg only */
+    float iou_threshold;
+    float score_threshold;
+    float sigma;            /* SSD_NMS_GAUSSIAN: TF's soft_nms_sigma */
+} ssd_nms_config;
+size_t ssd_nms_config_bytes(void);          /* sizeof(ssd_nms_config) of this library (for mirrors of the struct) */
+int ssd_nms_lds_candidates(void);           /* the longest list the selection kernel keeps wholly in LDS */
+size_t ssd_decode_nms_cfg_workspace_bytes(int B, int N, int L, const ssd_nms_config* cfg);
+int ssd_decode_nms_cfg(const float* deltas_dev, const float* probs_dev, const float* priors_dev, const float* var,
+                       int B, int N, int L, const ssd_nms_config* cfg, float* boxes_dev, float* labels_dev,
+                       float* scores_dev, int* valid_dev, int* kept_idx_dev, void* workspace_dev, size_t workspace_bytes,
+                       void* stream);
+int ssd_combined_nms_cfg(const float* boxes_dev, const float* scores_dev, int B, int N, int C, const ssd_nms_config* cfg,
+                         float* boxes_out_dev, float* scores_out_dev, float* classes_out_dev, int* valid_dev,
+                         int* kept_idx_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- pairwise IoU: utils/bbox_utils.py:27-59 (M1) -----------------------------------
  * boxes [N,4] (boxes_batched == 0, shared across the batch) or [B,N,4]; gt [B,G,4];
  * out [B,N,G].  No epsilon: 0/0 -> NaN exactly like the reference. */
@@ -1082,6 +1137,11 @@ int ssd_net_predict(ssd_net* net, const float* image_dev, int B, const float* pr
                     const float* var, int max_total, float iou_thr, float score_thr,
                     float* boxes_dev, float* labels_dev, float* scores_dev, int* valid_dev,
                     void* stream);
+/* ... with the decoder of ssd_decode_nms_cfg (cfg->max_per_class and cfg->max_total are both honoured; ssd_net_predict is
+ * max_per_class == max_total == max_total, SSD_NMS_HARD, per class).  Calls with different configs may alternate on one net. */
+int ssd_net_predict_cfg(ssd_net* net, const float* image_dev, int B, const float* priors_dev, const float* var,
+                        const ssd_nms_config* cfg, float* boxes_dev, float* labels_dev, float* scores_dev,
+                        int* valid_dev, void* stream);
 
 /* Debug/test hook: copy the activation of a named layer of the LAST forward to the host.
  * Returns the element count (or negative error); host_out may be NULL to query size. */

@@ -8,6 +8,9 @@
 // indices kept by NMS and match indices are bit-exact against the oracle.
 #include "common.h"
 
+#include <algorithm>
+#include <cmath>
+
 namespace ssd {
 
 // ------------------------------------------------------------------ shared device math
@@ -166,7 +169,9 @@ __global__ __launch_bounds__(256) void softmax_kernel(const float* __restrict__ 
 
 // LOGITS (ssd_net_predict): `probs` holds the head convs' LOGITS; the softmax runs on the LDS-staged slab right here
 // (no separate softmax pass over the [B, N, L] buffer, no launch); needs use_lds.
-template <bool DECODE, bool LOGITS>
+// AGN (class-agnostic suppression): one list per image, `cap` = N * L, the key already in the selection kernel's form
+// [score desc : 32][anchor : 22][class : 10]; the image's counter is cand_count[b].
+template <bool DECODE, bool LOGITS, bool AGN = false>
 __global__ __launch_bounds__(256) void compact_kernel(
     const float4* __restrict__ deltas, const float* __restrict__ probs,
     const float4* __restrict__ priors, const float4 var, const int N, const int L,
@@ -202,10 +207,17 @@ __global__ __launch_bounds__(256) void compact_kernel(
     for (int c = 0; c < L; ++c) {
         const float s = masked ? 0.0f : row[c];
         if (s > score_thr) {
-            const int slot = atomicAdd(&cand_count[b * L + c], 1);
-            if (slot < cap)
-                cand_keys[((size_t)b * L + c) * cap + slot] =
-                    ((unsigned long long)score_desc_key(s) << 32) | (unsigned)i;
+            if (AGN) {
+                const int slot = atomicAdd(&cand_count[b], 1);
+                if (slot < cap)
+                    cand_keys[(size_t)b * cap + slot] = ((unsigned long long)score_desc_key(s) << 32) |
+                                                        ((unsigned)i << kClsBits) | (unsigned)c;
+            } else {
+                const int slot = atomicAdd(&cand_count[b * L + c], 1);
+                if (slot < cap)
+                    cand_keys[((size_t)b * L + c) * cap + slot] =
+                        ((unsigned long long)score_desc_key(s) << 32) | (unsigned)i;
+            }
             any = true;
         }
     }
@@ -356,6 +368,157 @@ __global__ __launch_bounds__(256) void nms_class_kernel(
         __syncthreads();
     }
     if (tid == 0) kept_count[bc] = kept;
+}
+
+// ------------------------------------------------------------------ Soft-NMS / class-agnostic selection
+// include/ssd_hip.h states the arithmetic.  The order of a list is not fixed in advance (every selection changes the
+// scores that are left), so nothing is sorted: one 256-thread block per list keeps the candidates as u64 keys
+// [score_desc_key(CURRENT score) : 32][anchor : 22][class : 10] -- the minimum key IS the winner under the tie rule, and
+// (anchor, class) makes every key of a list unique -- and thread t owns the slots t, t + 256, ..., of which the first
+// `cnt` are alive.  One selection = one pass of every thread over its own live slots (drop the last winner, decay the
+// others by it, drop what left the list, move the survivors down to the front of the thread's stripe, keep the running
+// minimum and ITS box in registers) + a minimum over the block: DPP and readlane within the wave (wave_min_u64), then
+// one (key, box) pair per wave through a double-buffered LDS slot, so a selection costs ONE barrier (the pairs of
+// selection k + 1 go to the other buffer while late threads still read those of k).  The winner's box travels with its
+// key, so no thread reads another thread's slots and the per-stripe compaction needs no synchronisation; a pass costs what
+// is still alive, not what the list started with.  Lists of up to `lds_cap` (<= kSoftLds) candidates hold keys and boxes
+// in LDS (24 B a candidate, 96 KiB at kSoftLds); longer ones keep the keys where the compaction left them in the workspace
+// (rewritten in place) and gather the boxes by anchor -- the same loop, two pointers.
+// Cost: selections x (live candidates / 256 box tests per thread + the wave minimum + one barrier), nothing but the list's
+// own latency; B * L (or B) blocks, occupancy is not the concern.
+constexpr int kSoftLds = 4096;
+constexpr unsigned long long kDeadKey = ~0ull;    // no candidate has it: score_desc_key is 0xffffffff for a NaN only
+enum { kNmsHard = 0, kNmsGaussian = 1, kNmsLinear = 2 };     // SSD_NMS_*
+
+// minimum over the wave, the same value in every lane.  Within a row of 16 lanes by DPP (quad_perm [1,0,3,2], [2,3,0,1],
+// row_half_mirror, row_mirror: every lane ends with its row's minimum), then the four rows by readlane + scalar compares:
+// no LDS crossbar (ds_bpermute) on the loop's critical path -- six dependent __shfl_xor pairs cost ~1500 of the ~2500
+// cycles a selection took with them
+template <int CTRL>
+__device__ __forceinline__ unsigned long long dpp_min_u64(unsigned long long v) {
+    const int lo = (int)(unsigned)(v & 0xffffffffull), hi = (int)(unsigned)(v >> 32);
+    const unsigned olo = (unsigned)__builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false);
+    const unsigned ohi = (unsigned)__builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false);
+    const unsigned long long o = ((unsigned long long)ohi << 32) | olo;
+    return o < v ? o : v;
+}
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+    v = dpp_min_u64<0xb1>(v);
+    v = dpp_min_u64<0x4e>(v);
+    v = dpp_min_u64<0x141>(v);
+    v = dpp_min_u64<0x140>(v);
+    const int lo = (int)(unsigned)(v & 0xffffffffull), hi = (int)(unsigned)(v >> 32);
+    unsigned long long r = ~0ull;
+#pragma unroll
+    for (int row = 0; row < 64; row += 16) {
+        const unsigned long long o = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(hi, row) << 32) |
+                                     (unsigned)__builtin_amdgcn_readlane(lo, row);
+        r = o < r ? o : r;
+    }
+    return r;
+}
+
+__device__ __forceinline__ float4 readlane_box(const float4 v, const int src) {
+    float4 r;
+    r.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.x), src));
+    r.y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.y), src));
+    r.z = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.z), src));
+    r.w = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.w), src));
+    return r;
+}
+
+template <int METHOD>
+__global__ __launch_bounds__(256) void soft_nms_kernel(
+    unsigned long long* __restrict__ cand_keys, int* __restrict__ cand_count, const float4* __restrict__ boxes,
+    const int N, const int L, const int agnostic, const int cap, const int lds_cap, const int limit,
+    const int kept_stride, const float iou_thr, const float score_thr, const float scale,
+    unsigned long long* __restrict__ kept_keys, int* __restrict__ kept_count) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float4* sbox = reinterpret_cast<float4*>(smem);                                         // [lds_cap]
+    unsigned long long* skeys = reinterpret_cast<unsigned long long*>(sbox + lds_cap);      // [lds_cap]
+    __shared__ __attribute__((aligned(16))) float4 x_box[2][4];
+    __shared__ unsigned long long x_key[2][4];
+
+    const int list = blockIdx.x;        // b * L + c, or b
+    const int b = agnostic ? list : list / L;
+    const unsigned c = agnostic ? 0u : (unsigned)(list - b * L);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = min(cand_count[list], cap);
+    // as nms_class_kernel: the list's owner leaves its counter at zero for the next call on this workspace
+    __syncthreads();
+    if (tid == 0) cand_count[list] = 0;
+    if (n == 0) {
+        if (tid == 0) kept_count[list] = 0;
+        return;
+    }
+    unsigned long long* gkeys = cand_keys + (size_t)list * cap;
+    const bool in_lds = n <= lds_cap;
+    unsigned long long* keys = in_lds ? skeys : gkeys;
+    const float4* img_boxes = boxes + (size_t)b * N;
+    unsigned long long local = kDeadKey;        // this thread's best live key and that candidate's box
+    float4 lbox = make_float4(0.f, 0.f, 0.f, 0.f);
+    int cnt = 0;                                // live slots of this thread: tid + 256 * i, i < cnt
+    for (int j = tid; j < n; j += 256, ++cnt) {
+        unsigned long long k = gkeys[j];
+        if (!agnostic) k = (k & 0xffffffff00000000ull) | ((k & 0xffffffffull) << kClsBits) | c;
+        keys[j] = k;
+        if (in_lds) {
+            const float4 box = img_boxes[(unsigned)(k & 0xffffffffull) >> kClsBits];
+            sbox[j] = box;
+            if (k < local) lbox = box;
+        }
+        if (k < local) local = k;
+    }
+    if (!in_lds && local != kDeadKey) lbox = img_boxes[(unsigned)(local & 0xffffffffull) >> kClsBits];
+    unsigned long long* out_keys = kept_keys + (size_t)list * kept_stride;
+    const int lim = min(min(limit, n), kept_stride);
+    int sel = 0, buf = 0;
+    for (; sel < lim; ++sel) {
+        const unsigned long long wm = wave_min_u64(local);
+        // the first lane that holds the wave's minimum hands over its box (all lanes hold the dead key: any box, never used)
+        const float4 wave_box = readlane_box(lbox, __ffsll((long long)__ballot(local == wm)) - 1);
+        if (lane == 0) { x_key[buf][wave] = wm; x_box[buf][wave] = wave_box; }
+        __syncthreads();
+        unsigned long long wk = x_key[buf][0];
+        int ww = 0;
+        for (int w = 1; w < 4; ++w) {
+            const unsigned long long k = x_key[buf][w];
+            if (k < wk) { wk = k; ww = w; }
+        }
+        if (wk == kDeadKey) break;          // nothing alive (the same value in every thread)
+        if (tid == 0) out_keys[sel] = wk;
+        const float4 wbox = x_box[buf][ww];
+        local = kDeadKey;
+        int live = 0;
+        for (int i = 0; i < cnt; ++i) {
+            const int j = tid + 256 * i;
+            unsigned long long k = keys[j];
+            if (k == wk) continue;          // the winner leaves (keys are unique)
+            const float4 box = in_lds ? sbox[j] : img_boxes[(unsigned)(k & 0xffffffffull) >> kClsBits];
+            const float o = nms_iou(box, wbox);
+            if (METHOD == kNmsHard) {
+                if (o > iou_thr) continue;
+            } else {
+                float s = score_from_key((unsigned)(k >> 32));
+                if (METHOD == kNmsLinear) {
+                    if (o > iou_thr) s = s * (1.0f - o);
+                } else {
+                    s = s * expf((scale * o) * o);
+                }
+                if (!(s > score_thr)) continue;
+                k = ((unsigned long long)score_desc_key(s) << 32) | (k & 0xffffffffull);
+            }
+            // survivor: down to the front of this thread's stripe
+            const int jd = tid + 256 * live;
+            if (METHOD != kNmsHard || live != i) keys[jd] = k;
+            if (in_lds && live != i) sbox[jd] = box;
+            if (k < local) { local = k; lbox = box; }
+            ++live;
+        }
+        cnt = live;
+        buf ^= 1;
+    }
+    if (tid == 0) kept_count[list] = sel;
 }
 
 // ------------------------------------------------------------------ per-image top-K merge
@@ -820,14 +983,19 @@ static int check_nms_args(int B, int N, int L, int max_per_class, int max_total)
 // flags (the net's own predict path): kNmsLogits -- `scores` holds logits, softmax fused into the compaction;
 // kNmsCountsClean -- the workspace's candidate counters are known to be zero (zeroed at allocation, re-zeroed by
 // nms_class_kernel of the previous call): no memset launch
+// mode (NULL: the reference's hard per-class NMS, the launches below as they always were): Soft-NMS and / or one pooled
+// list per image -- the compaction's AGN form, soft_nms_kernel in place of nms_class_kernel, the same merge
 enum { kNmsLogits = 1, kNmsCountsClean = 2 };
+struct NmsMode { int method; int agnostic; float scale; };
 static int run_nms(bool decode, const float* deltas, const float* scores, const float* priors_or_boxes,
                    const float* var, int B, int N, int L, int max_per_class, int max_total,
                    float iou_thr, float score_thr, int clip, float* boxes_out, float* labels_out,
                    float* scores_out, int* valid_out, int* kept_idx, void* ws, size_t ws_bytes,
-                   hipStream_t st, int flags = 0, int ws_batch = 0) {
+                   hipStream_t st, int flags = 0, int ws_batch = 0, const NmsMode* mode = nullptr) {
     int rc = check_nms_args(B, N, L, max_per_class, max_total);
     if (rc) return rc;
+    const bool agn = mode && mode->agnostic;
+    SSD_UNSUPPORTED_IF(agn && (long)N * L > 0x7fffffffL, "decode_nms: N=%d x L=%d candidates in one class-agnostic list", N, L);
     if (B == 0) return SSD_OK;
     if (N == 0) {   // nothing to select: all-zero outputs
         SSD_HIP(hipMemsetAsync(boxes_out, 0, (size_t)B * max_total * 16, st));
@@ -859,9 +1027,26 @@ static int run_nms(bool decode, const float* deltas, const float* scores, const 
         SSD_HIP(hipFuncSetAttribute((const void*)compact_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_bytes));
         SSD_HIP(hipFuncSetAttribute((const void*)compact_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_bytes));
         SSD_HIP(hipFuncSetAttribute((const void*)compact_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_bytes));
+        SSD_HIP(hipFuncSetAttribute((const void*)compact_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_bytes));
+        SSD_HIP(hipFuncSetAttribute((const void*)compact_kernel<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_bytes));
+        SSD_HIP(hipFuncSetAttribute((const void*)compact_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_bytes));
     }
     dim3 grid(cdiv(N, 256), B);
-    if (decode && (flags & kNmsLogits)) {
+    if (agn) {
+        // one list per image: N * L keys, the image's slice of the cand_keys carve
+        const float4* d4 = decode ? (const float4*)deltas : nullptr;
+        const float4* p4 = decode ? (const float4*)priors_or_boxes : nullptr;
+        float4* bo = decode ? w.boxes : nullptr;
+        if (decode && (flags & kNmsLogits))
+            hipLaunchKernelGGL((compact_kernel<true, true, true>), grid, dim3(256), tile_bytes, st, d4, scores, p4, v4, N, L,
+                               score_thr, use_lds, bo, w.cand_keys, w.cand_count, N * L);
+        else if (decode)
+            hipLaunchKernelGGL((compact_kernel<true, false, true>), grid, dim3(256), use_lds ? tile_bytes : 0, st, d4, scores,
+                               p4, v4, N, L, score_thr, use_lds, bo, w.cand_keys, w.cand_count, N * L);
+        else
+            hipLaunchKernelGGL((compact_kernel<false, false, true>), grid, dim3(256), use_lds ? tile_bytes : 0, st, d4, scores,
+                               p4, v4, N, L, score_thr, use_lds, bo, w.cand_keys, w.cand_count, N * L);
+    } else if (decode && (flags & kNmsLogits)) {
         hipLaunchKernelGGL((compact_kernel<true, true>), grid, dim3(256), tile_bytes, st,
                            (const float4*)deltas, scores, (const float4*)priors_or_boxes, v4, N, L,
                            score_thr, use_lds, w.boxes, w.cand_keys, w.cand_count, N);
@@ -876,6 +1061,37 @@ static int run_nms(bool decode, const float* deltas, const float* scores, const 
     }
     SSD_LAUNCH_CHECK();
     const float4* nms_boxes = decode ? w.boxes : (const float4*)priors_or_boxes;
+    if (mode) {
+        const int lists = agn ? B : B * L;
+        const int cap = agn ? N * L : N;
+        const int kept_stride = agn ? L * maxk : maxk;      // an image's (class's) slice of the kept_keys carve
+        const int limit = agn ? std::min(std::min(max_per_class, max_total), kept_stride) : maxk;
+        const int lds_cap = std::min(cap, kSoftLds);
+        const size_t lds = (size_t)lds_cap * 24;
+        const void* fn = mode->method == kNmsHard ? (const void*)soft_nms_kernel<kNmsHard>
+                         : mode->method == kNmsLinear ? (const void*)soft_nms_kernel<kNmsLinear>
+                                                      : (const void*)soft_nms_kernel<kNmsGaussian>;
+        if (lds > 64 * 1024) SSD_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(lists), dim3(256), lds, st, w.cand_keys, w.cand_count, nms_boxes, N, L,
+                               agn ? 1 : 0, cap, lds_cap, limit, kept_stride, iou_thr, score_thr, mode->scale, w.kept_keys,
+                               w.kept_count);
+        };
+        if (mode->method == kNmsHard) launch(soft_nms_kernel<kNmsHard>);
+        else if (mode->method == kNmsLinear) launch(soft_nms_kernel<kNmsLinear>);
+        else launch(soft_nms_kernel<kNmsGaussian>);
+        SSD_LAUNCH_CHECK();
+        // the merge of an agnostic image: ONE list of up to kept_stride rows, already in order
+        const int mL = agn ? 1 : L;
+        const size_t mkeys = (size_t)mL * kept_stride * 8;
+        const size_t mhdr = align_up((size_t)(mL + 1) * 4, 16);
+        const int mlds_ok = mhdr + mkeys <= 64 * 1024;
+        hipLaunchKernelGGL(merge_topk_kernel, dim3(B), dim3(256), mhdr + (mlds_ok ? mkeys : 0), st, w.kept_keys, w.kept_count,
+                           nms_boxes, N, mL, kept_stride, max_total, clip, mlds_ok, w.merge_ws, (float4*)boxes_out, labels_out,
+                           scores_out, valid_out, kept_idx);
+        SSD_LAUNCH_CHECK();
+        return SSD_OK;
+    }
     if (nms_lds > 64 * 1024)
         SSD_HIP(hipFuncSetAttribute((const void*)nms_class_kernel,
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)nms_lds));
@@ -893,6 +1109,23 @@ static int run_nms(bool decode, const float* deltas, const float* scores, const 
     return SSD_OK;
 }
 
+// ssd_nms_config -> what run_nms takes: *use stays NULL for the reference's post-processor (HARD, per class), which then
+// runs on its own kernels; SSD_E_INVALID for the arguments include/ssd_hip.h rejects
+int nms_mode_of(const ssd_nms_config* cfg, NmsMode* mode, const NmsMode** use) {
+    SSD_CHECK_ARG(cfg != nullptr, "nms config is NULL");
+    SSD_CHECK_ARG(cfg->method == SSD_NMS_HARD || cfg->method == SSD_NMS_GAUSSIAN || cfg->method == SSD_NMS_LINEAR,
+                  "nms config: unknown method %d", cfg->method);
+    SSD_CHECK_ARG(cfg->method != SSD_NMS_GAUSSIAN || (std::isfinite(cfg->sigma) && cfg->sigma > 0.0f),
+                  "nms config: sigma=%g (SSD_NMS_GAUSSIAN needs a finite sigma > 0)", (double)cfg->sigma);
+    SSD_CHECK_ARG(cfg->iou_threshold >= 0.0f && cfg->iou_threshold <= 1.0f, "nms config: iou_threshold=%g outside [0, 1]",
+                  (double)cfg->iou_threshold);
+    mode->method = cfg->method;
+    mode->agnostic = cfg->class_agnostic != 0;
+    mode->scale = cfg->method == SSD_NMS_GAUSSIAN ? -0.5f / cfg->sigma : 0.0f;
+    *use = (cfg->method == SSD_NMS_HARD && !mode->agnostic) ? nullptr : mode;
+    return SSD_OK;
+}
+
 // The net's own predict path (csrc/ssd_net.hip): head LOGITS in, softmax fused into the compaction, no counter memset.
 // `ws` is the net's workspace, zeroed at allocation.  Returns SSD_E_UNSUPPORTED when the fused form cannot run (L too
 // large for the LDS-staged slab): the caller then runs the softmax layer + ssd_decode_nms.
@@ -902,6 +1135,16 @@ int decode_nms_fused(const float* deltas, const float* logits, const float* prio
                      float* scores, int* valid, void* ws, size_t ws_bytes, int ws_batch, hipStream_t st) {
     return run_nms(true, deltas, logits, priors, var, B, N, L, max_per_class, max_total, iou_thr, score_thr, 1, boxes,
                    labels, scores, valid, nullptr, ws, ws_bytes, st, kNmsLogits | kNmsCountsClean, ws_batch);
+}
+int decode_nms_fused_cfg(const float* deltas, const float* logits, const float* priors, const float* var, int B, int N, int L,
+                         const ssd_nms_config* cfg, float* boxes, float* labels, float* scores, int* valid, void* ws,
+                         size_t ws_bytes, int ws_batch, hipStream_t st) {
+    NmsMode mode;
+    const NmsMode* m = nullptr;
+    if (const int rc = nms_mode_of(cfg, &mode, &m)) return rc;
+    return run_nms(true, deltas, logits, priors, var, B, N, L, cfg->max_per_class, cfg->max_total, cfg->iou_threshold,
+                   cfg->score_threshold, 1, boxes, labels, scores, valid, nullptr, ws, ws_bytes, st,
+                   kNmsLogits | kNmsCountsClean, ws_batch, m);
 }
 int launch_softmax_lds(const float* in, long rows, int L, float* out, hipStream_t st) {
     hipLaunchKernelGGL(softmax_kernel, dim3(cdiv(rows, 256)), dim3(256), (size_t)256 * L * 4, st, in, rows, L, out);
@@ -997,6 +1240,42 @@ int ssd_combined_nms(const float* boxes_dev, const float* scores_dev, int B, int
     return run_nms(false, nullptr, scores_dev, boxes_dev, nullptr, B, N, C, max_per_class, max_total,
                    iou_thr, score_thr, clip_boxes, boxes_out_dev, classes_out_dev, scores_out_dev,
                    valid_dev, kept_idx_dev, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+
+size_t ssd_nms_config_bytes(void) { return sizeof(ssd_nms_config); }
+int ssd_nms_lds_candidates(void) { return kSoftLds; }
+
+size_t ssd_decode_nms_cfg_workspace_bytes(int B, int N, int L, const ssd_nms_config* cfg) {
+    return ssd_decode_nms_workspace_bytes(B, N, L, cfg ? cfg->max_per_class : 0);
+}
+
+int ssd_decode_nms_cfg(const float* deltas_dev, const float* probs_dev, const float* priors_dev, const float* var,
+                       int B, int N, int L, const ssd_nms_config* cfg, float* boxes_dev, float* labels_dev,
+                       float* scores_dev, int* valid_dev, int* kept_idx_dev, void* workspace_dev, size_t workspace_bytes,
+                       void* stream) {
+    NmsMode mode;
+    const NmsMode* m = nullptr;
+    if (const int rc = nms_mode_of(cfg, &mode, &m)) return rc;
+    SSD_CHECK_ARG(var != nullptr, "ssd_decode_nms_cfg: variances pointer is NULL");
+    SSD_CHECK_ARG(B == 0 || (boxes_dev && labels_dev && scores_dev && valid_dev), "ssd_decode_nms_cfg: NULL output pointer");
+    SSD_CHECK_ARG(B == 0 || N == 0 || (deltas_dev && probs_dev && priors_dev), "ssd_decode_nms_cfg: NULL input pointer");
+    return run_nms(true, deltas_dev, probs_dev, priors_dev, var, B, N, L, cfg->max_per_class, cfg->max_total,
+                   cfg->iou_threshold, cfg->score_threshold, 1, boxes_dev, labels_dev, scores_dev, valid_dev, kept_idx_dev,
+                   workspace_dev, workspace_bytes, (hipStream_t)stream, 0, 0, m);
+}
+
+int ssd_combined_nms_cfg(const float* boxes_dev, const float* scores_dev, int B, int N, int C, const ssd_nms_config* cfg,
+                         float* boxes_out_dev, float* scores_out_dev, float* classes_out_dev, int* valid_dev,
+                         int* kept_idx_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+    NmsMode mode;
+    const NmsMode* m = nullptr;
+    if (const int rc = nms_mode_of(cfg, &mode, &m)) return rc;
+    SSD_CHECK_ARG(B == 0 || (boxes_out_dev && scores_out_dev && classes_out_dev && valid_dev),
+                  "ssd_combined_nms_cfg: NULL output pointer");
+    SSD_CHECK_ARG(B == 0 || N == 0 || (boxes_dev && scores_dev), "ssd_combined_nms_cfg: NULL input pointer");
+    return run_nms(false, nullptr, scores_dev, boxes_dev, nullptr, B, N, C, cfg->max_per_class, cfg->max_total,
+                   cfg->iou_threshold, cfg->score_threshold, cfg->clip_boxes, boxes_out_dev, classes_out_dev, scores_out_dev,
+                   valid_dev, kept_idx_dev, workspace_dev, workspace_bytes, (hipStream_t)stream, 0, 0, m);
 }
 
 int ssd_iou_map(const float* boxes_dev, int boxes_batched, const float* gt_dev, int B, int N, int G,

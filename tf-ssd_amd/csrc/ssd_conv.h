@@ -213,6 +213,11 @@ bool decode_nms_fused_ok(int L);
 int decode_nms_fused(const float* deltas, const float* logits, const float* priors, const float* var, int B, int N, int L,
                      int max_per_class, int max_total, float iou_thr, float score_thr, float* boxes, float* labels,
                      float* scores, int* valid, void* ws, size_t ws_bytes, int ws_batch, hipStream_t st);
+// ... behind an ssd_nms_config (Soft-NMS / class-agnostic lists; hard per class is decode_nms_fused's launches): the same
+// workspace, the same invariant -- every counter a call used is zero again when it ends
+int decode_nms_fused_cfg(const float* deltas, const float* logits, const float* priors, const float* var, int B, int N, int L,
+                         const ssd_nms_config* cfg, float* boxes, float* labels, float* scores, int* valid, void* ws,
+                         size_t ws_bytes, int ws_batch, hipStream_t st);
 int launch_pack_weights(const float* hwio, int K, int Cout, int Kpad, int Npad, float* packed, hipStream_t st);
 // packed fp32 weights + room for their four bf16 planes (conv_split_planes points at them)
 inline size_t conv_packed_floats(int K, int Cout) {

@@ -1515,9 +1515,13 @@ int ssd_net_forward(ssd_net* net, const float* image_dev, int B, float* deltas_o
                        [&]() { return forward_impl(net, image_dev, B, deltas_out_dev, probs_out_dev, st); });
 }
 
-int ssd_net_predict(ssd_net* net, const float* image_dev, int B, const float* priors_dev, const float* var,
-                    int max_total, float iou_thr, float score_thr, float* boxes_dev, float* labels_dev,
-                    float* scores_dev, int* valid_dev, void* stream) {
+// ssd_net_predict (cfg == NULL: hard per-class NMS, max_per_class = max_total) and ssd_net_predict_cfg behind one body.
+// Whatever the config, a call leaves every candidate counter it used at zero (nms_class_kernel / soft_nms_kernel reset
+// their own list's), so calls of different configs may alternate on one workspace; the carve depends on max_per_class
+// alone.
+static int predict_impl(ssd_net* net, const float* image_dev, int B, const float* priors_dev, const float* var,
+                        int max_total, float iou_thr, float score_thr, const ssd_nms_config* cfg, float* boxes_dev,
+                        float* labels_dev, float* scores_dev, int* valid_dev, void* stream) {
     SSD_CHECK_ARG(net != nullptr, "ssd_net_predict: net is NULL");
     if (!net->finalized) {
         set_error("ssd_net_predict: call ssd_net_finalize() first");
@@ -1526,6 +1530,8 @@ int ssd_net_predict(ssd_net* net, const float* image_dev, int B, const float* pr
     const int N = net->num_priors, L = net->L;
     SSD_CHECK_ARG(B >= 0 && B <= net->max_batch, "ssd_net_predict: batch %d exceeds max_batch %d", B, net->max_batch);
     SSD_CHECK_ARG(max_total >= 1, "ssd_net_predict: max_total must be >= 1");
+    const int max_per_class = cfg ? cfg->max_per_class : max_total;
+    SSD_CHECK_ARG(max_per_class >= 1, "ssd_net_predict: max_per_class must be >= 1");
     // head-output scratch follows max_batch (a re-finalize with a larger batch regrows it); every
     // reallocation invalidates the captured graphs, which have the old pointers baked in
     if (net->scratch_batch < net->max_batch) {
@@ -1540,11 +1546,11 @@ int ssd_net_predict(ssd_net* net, const float* image_dev, int B, const float* pr
         net->scratch_batch = net->max_batch;
     }
     // the fused decoder carves the workspace for nms_ws_batch images whatever B a call runs: a re-finalize with another
-    // max_batch, or a call with a larger max_total, re-carves -- and re-zeroes -- it (never a layout for one batch over
+    // max_batch, or a call with another max_per_class (ssd_net_predict: its max_total), re-carves -- and re-zeroes -- it (never a layout for one batch over
     // counters left by another)
     const int ws_batch = std::max(net->max_batch, net->nms_ws_batch);
-    const size_t need = ssd_decode_nms_workspace_bytes(ws_batch, N, L, max_total);
-    if (need > net->nms_ws_bytes || ws_batch != net->nms_ws_batch || max_total != net->nms_ws_total) {
+    const size_t need = ssd_decode_nms_workspace_bytes(ws_batch, N, L, max_per_class);
+    if (need > net->nms_ws_bytes || ws_batch != net->nms_ws_batch || max_per_class != net->nms_ws_total) {
         (void)hipDeviceSynchronize();
         net->drop_graphs();
         if (net->nms_ws) (void)hipFree(net->nms_ws);
@@ -1554,7 +1560,7 @@ int ssd_net_predict(ssd_net* net, const float* image_dev, int B, const float* pr
         SSD_HIP(hipMemset(net->nms_ws, 0, need));      // candidate counters start at zero and are re-zeroed by every call (nms_class_kernel)
         net->nms_ws_bytes = need;
         net->nms_ws_batch = ws_batch;
-        net->nms_ws_total = max_total;
+        net->nms_ws_total = max_per_class;
     }
     hipStream_t st = (hipStream_t)stream;
     SSD_CHECK_ARG(var != nullptr, "ssd_net_predict: variances pointer is NULL");
@@ -1563,14 +1569,27 @@ int ssd_net_predict(ssd_net* net, const float* image_dev, int B, const float* pr
     k1.f = iou_thr; k2.f = score_thr;
     std::vector<const void*> key = {image_dev, priors_dev, boxes_dev, labels_dev, scores_dev, valid_dev,
                                     (const void*)(intptr_t)B, (const void*)(intptr_t)max_total,
-                                    (const void*)k1.i, (const void*)k2.i, (const void*)2};
+                                    (const void*)k1.i, (const void*)k2.i, (const void*)(intptr_t)(cfg ? 3 : 2)};
     for (int i = 0; i < 4; ++i) { union { float f; intptr_t i; } k{}; k.f = v4[i]; key.push_back((const void*)k.i); }
+    if (cfg) {      // every field of the config (max_total, the two thresholds: above)
+        union { float f; intptr_t i; } ks{};
+        ks.f = cfg->sigma;
+        for (const int v : {cfg->method, cfg->class_agnostic != 0 ? 1 : 0, cfg->max_per_class, cfg->clip_boxes})
+            key.push_back((const void*)(intptr_t)v);
+        key.push_back((const void*)ks.i);
+    }
     // softmax folded into the decoder's compaction (one pass over the [B, N, L] buffer and two launches -- softmax, counter
     // memset -- less); option "fuse_softmax" 0 keeps the layer-by-layer form
     const bool fused_sm = net->fuse_softmax && decode_nms_fused_ok(L) && N >= 1 && net->nms_ws_batch >= B;
     int rc = run_graphed(net, key, st, [&]() {
         int r = forward_impl(net, image_dev, B, net->deltas, net->probs, st, fused_sm);
         if (r) return r;
+        if (cfg && fused_sm)
+            return decode_nms_fused_cfg(net->deltas, net->probs, priors_dev, v4, B, N, L, cfg, boxes_dev, labels_dev, scores_dev,
+                                        valid_dev, net->nms_ws, net->nms_ws_bytes, net->nms_ws_batch, st);
+        if (cfg)
+            return ssd_decode_nms_cfg(net->deltas, net->probs, priors_dev, v4, B, N, L, cfg, boxes_dev, labels_dev, scores_dev,
+                                      valid_dev, nullptr, net->nms_ws, net->nms_ws_bytes, (void*)st);
         if (fused_sm)
             return decode_nms_fused(net->deltas, net->probs, priors_dev, v4, B, N, L, max_total, max_total, iou_thr, score_thr,
                                     boxes_dev, labels_dev, scores_dev, valid_dev, net->nms_ws, net->nms_ws_bytes, net->nms_ws_batch, st);
@@ -1587,6 +1606,21 @@ int ssd_net_predict(ssd_net* net, const float* image_dev, int B, const float* pr
     if (!rc && net->timing && !net->timing_events.empty())
         (void)hipEventRecord(net->timing_events.back().back(), st);
     return rc;
+}
+
+int ssd_net_predict(ssd_net* net, const float* image_dev, int B, const float* priors_dev, const float* var,
+                    int max_total, float iou_thr, float score_thr, float* boxes_dev, float* labels_dev,
+                    float* scores_dev, int* valid_dev, void* stream) {
+    return predict_impl(net, image_dev, B, priors_dev, var, max_total, iou_thr, score_thr, nullptr, boxes_dev, labels_dev,
+                        scores_dev, valid_dev, stream);
+}
+
+int ssd_net_predict_cfg(ssd_net* net, const float* image_dev, int B, const float* priors_dev, const float* var,
+                        const ssd_nms_config* cfg, float* boxes_dev, float* labels_dev, float* scores_dev,
+                        int* valid_dev, void* stream) {
+    SSD_CHECK_ARG(cfg != nullptr, "ssd_net_predict_cfg: config is NULL");
+    return predict_impl(net, image_dev, B, priors_dev, var, cfg->max_total, cfg->iou_threshold, cfg->score_threshold, cfg,
+                        boxes_dev, labels_dev, scores_dev, valid_dev, stream);
 }
 
 // The integer options: a bool field (any non-zero value is 1) or an int field clamped to [lo, hi].  `refinalize`: the

@@ -450,10 +450,12 @@ class SSDModel(object):
         return out
 
     def predict_on_device(self, images, priors, variances, max_total=200, iou_threshold=0.5,
-                          score_threshold=0.5):
+                          score_threshold=0.5, nms_config=None):
         """Forward + SSDDecoder in ONE native call (``ssd_net_predict``): what
         ``get_decoder_model(...).predict`` runs per batch.  Returns device tensors
-        (boxes, labels, scores, valid)."""
+        (boxes, labels, scores, valid).  ``nms_config`` (an ``ssd_hip.NmsConfig``, ``SSDDecoder.nms_config()``): the
+        decoder is ``ssd_net_predict_cfg``'s -- Soft-NMS / class-agnostic lists; its ``max_total`` and thresholds are the
+        ones that count."""
         x = _h.to_dev(images)
         B = x.shape[0]
         self._ensure(max(B, 1))
@@ -464,6 +466,14 @@ class SSDModel(object):
         scores = torch.empty((B, max_total), dtype=torch.float32, device=dev)
         valid = torch.empty((B,), dtype=torch.int32, device=dev)
         var_p, _keep = _h.host4(variances)
+        if nms_config is not None:
+            if int(nms_config.max_total) != int(max_total):
+                raise ValueError("nms_config.max_total %d != max_total %d" % (nms_config.max_total, max_total))
+            _h.check(_h.lib().ssd_net_predict_cfg(self._net, _h.ptr(x), B, _h.ptr(pri), var_p, nms_config, _h.ptr(boxes),
+                                                  _h.ptr(labels), _h.ptr(scores), _h.ptr(valid), _h.stream()),
+                     "ssd_net_predict_cfg")
+            self._last_input = x
+            return boxes, labels, scores, valid
         _h.check(_h.lib().ssd_net_predict(self._net, _h.ptr(x), B, _h.ptr(pri), var_p, int(max_total),
                                           float(iou_threshold), float(score_threshold), _h.ptr(boxes),
                                           _h.ptr(labels), _h.ptr(scores), _h.ptr(valid), _h.stream()),

@@ -13,15 +13,27 @@ class SSDDecoder(object):
 
     inputs:  [pred_deltas (B,N,4), pred_label_probs (B,N,L)]
     outputs: pred_bboxes (B,top_n,4), pred_labels (B,top_n), pred_scores (B,top_n)
+
+    Beyond the reference: ``iou_threshold`` (TF's default 0.5), ``nms_method`` "hard" | "gaussian" | "linear" (Soft-NMS;
+    ``soft_nms_sigma`` is ``tf.image.non_max_suppression_with_scores``' for "gaussian"; the scores that come out are the
+    decayed ones) and ``class_agnostic`` (one list per image over all classes: a box comes out under one class only).
+    With the defaults ``call`` is ``ssd_decode_nms``, the reference's post-processor; everything else goes through
+    ``ssd_decode_nms_cfg`` (include/ssd_hip.h states the arithmetic).
     """
 
-    def __init__(self, prior_boxes, variances, max_total_size=200, score_threshold=0.5, **kwargs):
+    def __init__(self, prior_boxes, variances, max_total_size=200, score_threshold=0.5, iou_threshold=0.5,
+                 nms_method="hard", soft_nms_sigma=0.5, class_agnostic=False, **kwargs):
         self.name = kwargs.pop("name", "ssd_decoder")
+        _h.nms_config(nms_method, class_agnostic, max_total_size, max_total_size, iou_threshold, score_threshold,
+                      soft_nms_sigma)                              # ValueError on a bad argument
         self.prior_boxes = prior_boxes
         self.variances = variances
         self.max_total_size = max_total_size
         self.score_threshold = score_threshold
-        self.iou_threshold = 0.5           # TF default of combined_non_max_suppression
+        self.iou_threshold = float(iou_threshold)     # 0.5: TF default of combined_non_max_suppression
+        self.nms_method = nms_method
+        self.soft_nms_sigma = float(soft_nms_sigma)
+        self.class_agnostic = bool(class_agnostic)
         self._priors_dev = None
         self.last_valid_detections = None  # TF's 4th output, discarded by the reference (:49)
         self.last_kept_indices = None
@@ -36,7 +48,28 @@ class SSDDecoder(object):
             "variances": self.variances,
             "max_total_size": self.max_total_size,
             "score_threshold": self.score_threshold,
+            "iou_threshold": self.iou_threshold,
+            "nms_method": self.nms_method,
+            "soft_nms_sigma": self.soft_nms_sigma,
+            "class_agnostic": self.class_agnostic,
         }
+
+    def nms_config(self):
+        """The ``ssd_hip.NmsConfig`` of this decoder, or None with the reference's post-processor (hard, per class): the
+        entry points without a config then run, exactly as before."""
+        if _h.nms_is_default(self.nms_method, self.class_agnostic):
+            return None
+        T = int(self.max_total_size)
+        return _h.nms_config(self.nms_method, self.class_agnostic, T, T, self.iou_threshold, self.score_threshold,
+                             self.soft_nms_sigma)
+
+    def predict_kwargs(self):
+        """What ``predict_on_device`` (models/_net.py) takes beside the images, the priors and the variances."""
+        kw = {"max_total": self.max_total_size, "iou_threshold": self.iou_threshold, "score_threshold": self.score_threshold}
+        cfg = self.nms_config()
+        if cfg is not None:
+            kw["nms_config"] = cfg
+        return kw
 
     def call(self, inputs, return_indices=False):
         """reference models/decoder.py:36-55."""
@@ -60,6 +93,14 @@ class SSDDecoder(object):
         var_p, _keep = _h.host4(self.variances)
         lib = _h.lib()
         ws = _h.workspace(lib.ssd_decode_nms_workspace_bytes(B, N, L, T))
+        cfg = self.nms_config()
+        if cfg is not None:
+            _h.check(lib.ssd_decode_nms_cfg(_h.ptr(pred_deltas), _h.ptr(pred_label_probs), _h.ptr(pri), var_p, B, N, L, cfg,
+                                            _h.ptr(boxes), _h.ptr(labels), _h.ptr(scores), _h.ptr(valid), _h.ptr(kept),
+                                            _h.ptr(ws), ws.numel(), _h.stream()), "SSDDecoder.call")
+            self.last_valid_detections = valid
+            self.last_kept_indices = kept
+            return boxes, labels, scores
         _h.check(lib.ssd_decode_nms(_h.ptr(pred_deltas), _h.ptr(pred_label_probs), _h.ptr(pri), var_p,
                                     B, N, L, T, T, float(self.iou_threshold), float(self.score_threshold),
                                     _h.ptr(boxes), _h.ptr(labels), _h.ptr(scores), _h.ptr(valid),
@@ -171,8 +212,7 @@ class DecoderModel(object):
             t0 = time.perf_counter()
             for i in range(n):
                 with torch.cuda.stream((sa, sb)[i % 2]):
-                    models[i % 2].predict_on_device(x, d.prior_boxes, d.variances, max_total=d.max_total_size,
-                                                    iou_threshold=d.iou_threshold, score_threshold=d.score_threshold)
+                    models[i % 2].predict_on_device(x, d.prior_boxes, d.variances, **d.predict_kwargs())
             torch.cuda.synchronize()
             return (time.perf_counter() - t0) / n
 
@@ -196,8 +236,7 @@ class DecoderModel(object):
         t0 = time.perf_counter()
         for _ in range(12):
             with torch.cuda.stream(cands[best[0]]):
-                models[0].predict_on_device(x, d.prior_boxes, d.variances, max_total=d.max_total_size,
-                                            iou_threshold=d.iou_threshold, score_threshold=d.score_threshold)
+                models[0].predict_on_device(x, d.prior_boxes, d.variances, **d.predict_kwargs())
         torch.cuda.synchronize()
         single = (time.perf_counter() - t0) / 12
         self._lanes_active = sustained < 0.985 * single
@@ -237,8 +276,7 @@ class DecoderModel(object):
             t0 = time.perf_counter()
             for i in range(n):
                 with torch.cuda.stream(streams[i % lanes]):
-                    models[i % lanes].predict_on_device(x, d.prior_boxes, d.variances, max_total=d.max_total_size,
-                                                        iou_threshold=d.iou_threshold, score_threshold=d.score_threshold)
+                    models[i % lanes].predict_on_device(x, d.prior_boxes, d.variances, **d.predict_kwargs())
             torch.cuda.synchronize()
             return (time.perf_counter() - t0) / n
 
@@ -323,8 +361,7 @@ class DecoderModel(object):
         elif sync_input:
             st.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(st):
-            b, l, s, v = m.predict_on_device(x, d.prior_boxes, d.variances, max_total=d.max_total_size,
-                                             iou_threshold=d.iou_threshold, score_threshold=d.score_threshold)
+            b, l, s, v = m.predict_on_device(x, d.prior_boxes, d.variances, **d.predict_kwargs())
         for t in (x, b, l, s, v):
             t.record_stream(st)
         d.last_valid_detections = v
@@ -367,9 +404,7 @@ class DecoderModel(object):
         if getattr(images, "dtype", None) in (np.uint8, torch.uint8) and hasattr(self.base_model, "img_size"):
             images = self._resident_float(images)       # uint8 [B,H,W,3]: convert + resize on the GPU (ssd_preprocess)
         if hasattr(self.base_model, "predict_on_device"):
-            b, l, s, v = self.base_model.predict_on_device(
-                images, d.prior_boxes, d.variances, max_total=d.max_total_size,
-                iou_threshold=d.iou_threshold, score_threshold=d.score_threshold)
+            b, l, s, v = self.base_model.predict_on_device(images, d.prior_boxes, d.variances, **d.predict_kwargs())
             d.last_valid_detections = v
             return b, l, s
         deltas, probs = self.base_model(images)
@@ -545,19 +580,27 @@ def default_lanes():
     return int(q) if q.isdigit() and 1 < int(q) < 4 else 1
 
 
-def get_decoder_model(base_model, prior_boxes, hyper_params, lanes=None, score_threshold=None, max_total_size=None):
+def get_decoder_model(base_model, prior_boxes, hyper_params, lanes=None, score_threshold=None, max_total_size=None,
+                      iou_threshold=None, nms_method=None, soft_nms_sigma=None, class_agnostic=None):
     """reference models/decoder.py:57-69.  ``lanes``: batches in flight for ``predict`` / ``submit`` (see
     DecoderModel).  Default: env SSD_HIP_LANES, else ``default_lanes()`` in AUTO mode -- ``predict`` uses the lanes
     when it has at least two batches per lane (a short check on the first such call falls back to one lane where
     lanes do not pay), everything else stays on the one-step-at-a-time path.  ``score_threshold`` / ``max_total_size``
     go to ``SSDDecoder`` (``None``: its defaults, 0.5 and 200): the devkit / COCO protocols of ``evaluate`` are meant
-    to be run at a low score threshold, the 0.5 default cuts the precision-recall curve short."""
+    to be run at a low score threshold, the 0.5 default cuts the precision-recall curve short.  ``iou_threshold`` /
+    ``nms_method`` / ``soft_nms_sigma`` / ``class_agnostic`` go there as well (``None``: 0.5, "hard", 0.5, False -- the
+    reference's post-processor): Soft-NMS keeps the recall hard NMS costs at such a threshold, class-agnostic suppression
+    removes the cross-class duplicates that show up there."""
     import os
     extra = {}
     if score_threshold is not None:
         extra["score_threshold"] = float(score_threshold)
     if max_total_size is not None:
         extra["max_total_size"] = int(max_total_size)
+    for k, v in (("iou_threshold", iou_threshold), ("nms_method", nms_method), ("soft_nms_sigma", soft_nms_sigma),
+                 ("class_agnostic", class_agnostic)):
+        if v is not None:
+            extra[k] = v
     decoder = SSDDecoder(prior_boxes, hyper_params["variances"], **extra)
     auto = False
     if lanes is None:

@@ -47,6 +47,13 @@ draw_quality = 75
 # protocols are meant to be run at a low threshold, e.g. 0.01: 0.5 cuts the precision-recall curve short)
 eval_protocol = None
 eval_score_threshold = None
+# additions: the decoder's suppression (models/decoder.py SSDDecoder), with and without evaluate; None keeps the reference's
+# (hard, per class, IoU 0.5).  nms_method "hard" / "gaussian" / "linear" (Soft-NMS; nms_sigma is TF's soft_nms_sigma),
+# nms_class_agnostic True: one list per image, a box comes out under one class only
+nms_method = None
+nms_sigma = None
+nms_iou_threshold = None
+nms_class_agnostic = None
 
 
 def _model_factory(backbone):
@@ -69,7 +76,7 @@ def _load_or_synthesise_weights(model, backbone):
 def main(argv=None, **knobs):
     """``knobs`` override the module-level switches for one call (``evaluate``, ``use_custom_images``,
     ``custom_image_path``, ``batch_size``, ``draw``, ``draw_dir``, ``draw_format``, ``draw_quality``, ``eval_protocol``,
-    ``eval_score_threshold``).  With ``evaluate`` and an ``eval_protocol`` the fourth return value is
+    ``eval_score_threshold``, ``nms_method``, ``nms_sigma``, ``nms_iou_threshold``, ``nms_class_agnostic``).  With ``evaluate`` and an ``eval_protocol`` the fourth return value is
     ``DetectionEvaluator.result()``."""
     args = io_utils.handle_args(argv)
     if args.handle_gpu:
@@ -121,7 +128,11 @@ def main(argv=None, **knobs):
     ssd_model = _model_factory(args.backbone)(hyper_params, max_batch=bs)
     _load_or_synthesise_weights(ssd_model, args.backbone)
     prior_boxes = bbox_utils.generate_prior_boxes(hyper_params["feature_map_shapes"], hyper_params["aspect_ratios"])
-    ssd_decoder_model = get_decoder_model(ssd_model, prior_boxes, hyper_params, score_threshold=score_thr)
+    ssd_decoder_model = get_decoder_model(ssd_model, prior_boxes, hyper_params, score_threshold=score_thr,
+                                          iou_threshold=knobs.get("nms_iou_threshold", nms_iou_threshold),
+                                          nms_method=knobs.get("nms_method", nms_method),
+                                          soft_nms_sigma=knobs.get("nms_sigma", nms_sigma),
+                                          class_agnostic=knobs.get("nms_class_agnostic", nms_class_agnostic))
 
     t0 = time.perf_counter()
     boxes, classes, scores = ssd_decoder_model.predict(

@@ -104,6 +104,13 @@ class LossConfig(ctypes.Structure):
                 ("loc_kind", ctypes.c_int), ("priors_dev", ctypes.c_void_p), ("variances", ctypes.c_float * 4)]
 
 
+class NmsConfig(ctypes.Structure):
+    """struct ssd_nms_config (include/ssd_hip.h): the post-processor of ``ssd_decode_nms_cfg`` / ``ssd_combined_nms_cfg`` /
+    ``ssd_net_predict_cfg``."""
+    _fields_ = [(n, ctypes.c_int) for n in ("method", "class_agnostic", "max_per_class", "max_total", "clip_boxes")] + [
+        (n, ctypes.c_float) for n in ("iou_threshold", "score_threshold", "sigma")]
+
+
 JPEG_COEFFICIENTS, JPEG_RAW = 0, 1
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
 MOBILENET_V2, VGG16 = 0, 1
@@ -111,6 +118,8 @@ OPT_ADAM, OPT_SGD = 0, 1
 LOSS_HARD_NEGATIVE, LOSS_FOCAL = 0, 1       # SSD_LOSS_*
 LOC_HUBER, LOC_IOU, LOC_GIOU, LOC_DIOU, LOC_CIOU = 0, 1, 2, 3, 4        # SSD_LOC_*
 EVAL_RULE_VOC, EVAL_RULE_COCO = 0, 1        # SSD_EVAL_RULE_*
+NMS_HARD, NMS_GAUSSIAN, NMS_LINEAR = 0, 1, 2        # SSD_NMS_*
+NMS_METHODS = {"hard": NMS_HARD, "gaussian": NMS_GAUSSIAN, "linear": NMS_LINEAR}
 # SSD_PLAN_*: the bits of ssd_net_train_plan
 PLAN_WGRAD, PLAN_WGRAD2, PLAN_DGRAD, PLAN_RESGRAD, PLAN_BN_BATCH, PLAN_BN_PARAMS, PLAN_SKIP = 1, 2, 4, 8, 16, 32, 64
 
@@ -128,6 +137,13 @@ _SIGNATURES = {
     "ssd_combined_nms": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 5 +
                          [ctypes.c_float, ctypes.c_float, ctypes.c_int, vp, vp, vp, vp, vp, vp,
                           ctypes.c_size_t, vp]),
+    "ssd_nms_config_bytes": (ctypes.c_size_t, []),
+    "ssd_nms_lds_candidates": (ctypes.c_int, []),
+    "ssd_decode_nms_cfg_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3 + [ctypes.POINTER(NmsConfig)]),
+    "ssd_decode_nms_cfg": (ctypes.c_int, [vp, vp, vp, c_float_p] + [ctypes.c_int] * 3 + [ctypes.POINTER(NmsConfig)] +
+                           [vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]),
+    "ssd_combined_nms_cfg": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 3 + [ctypes.POINTER(NmsConfig)] +
+                             [vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]),
     "ssd_iou_map": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
     "ssd_encode_deltas": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]),
     "ssd_match_encode": (ctypes.c_int, [vp, vp, vp, c_float_p, ctypes.c_float] + [ctypes.c_int] * 4 +
@@ -245,6 +261,7 @@ _SIGNATURES = {
     "ssd_net_forward": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp, vp]),
     "ssd_net_predict": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, c_float_p, ctypes.c_int,
                                        ctypes.c_float, ctypes.c_float, vp, vp, vp, vp, vp]),
+    "ssd_net_predict_cfg": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, c_float_p, ctypes.POINTER(NmsConfig), vp, vp, vp, vp, vp]),
     "ssd_net_fetch_activation": (ctypes.c_long, [vp, ctypes.c_char_p, c_float_p, ctypes.c_size_t]),
     "ssd_net_fetch_planes": (ctypes.c_long, [vp, ctypes.c_char_p, c_float_p, ctypes.c_size_t, c_int_p]),
     "ssd_net_num_layers": (ctypes.c_int, [vp]),
@@ -351,8 +368,34 @@ def lib():
             fn = getattr(l, name)    # AttributeError here == the .so is stale: rebuild it
             fn.restype = res
             fn.argtypes = args
+        if l.ssd_nms_config_bytes() != ctypes.sizeof(NmsConfig):     # the mirror and the library disagree: a stale .so
+            raise SsdHipError("ssd_nms_config is %d bytes in %s, %d in ssd_hip.NmsConfig: rebuild the library" % (
+                l.ssd_nms_config_bytes(), LIB_PATH, ctypes.sizeof(NmsConfig)))
         _lib = l
     return _lib
+
+
+def nms_config(method="hard", class_agnostic=False, max_per_class=200, max_total=200, iou_threshold=0.5, score_threshold=0.5,
+               sigma=0.5, clip_boxes=True):
+    """A validated ``NmsConfig``: ``method`` "hard" | "gaussian" | "linear" (``sigma``: TF's ``soft_nms_sigma``, finite and
+    > 0 for "gaussian"), ``iou_threshold`` in [0, 1].  ValueError otherwise -- the checks the library repeats."""
+    import math
+    if method not in NMS_METHODS:
+        raise ValueError('nms_method must be "hard", "gaussian" or "linear", got %r' % (method,))
+    iou_threshold, sigma = float(iou_threshold), float(sigma)
+    if not 0.0 <= iou_threshold <= 1.0:
+        raise ValueError("iou_threshold must lie in [0, 1], got %r" % (iou_threshold,))
+    if method == "gaussian" and not (math.isfinite(sigma) and sigma > 0.0):
+        raise ValueError("soft_nms_sigma must be finite and > 0, got %r" % (sigma,))
+    if not math.isfinite(sigma):
+        sigma = 0.0             # unused by this method: keep the graph key (which holds every field) comparable
+    return NmsConfig(NMS_METHODS[method], int(bool(class_agnostic)), int(max_per_class), int(max_total), int(bool(clip_boxes)),
+                     iou_threshold, float(score_threshold), sigma)
+
+
+def nms_is_default(method, class_agnostic):
+    """The reference's post-processor (hard, per class): the one the entry points without a config run."""
+    return method == "hard" and not class_agnostic
 
 
 def check(rc, what=""):

@@ -18,6 +18,11 @@ def non_max_suppression(pred_bboxes, pred_labels, **kwargs):
     pred_bboxes [B,N,1,4], pred_labels [B,N,C]; kwargs as TF's: max_output_size_per_class,
     max_total_size, iou_threshold=0.5, score_threshold=-inf, pad_per_class=False,
     clip_boxes=True.  Returns (nmsed_boxes, nmsed_scores, nmsed_classes, valid_detections).
+
+    Beyond TF's: ``nms_method`` "hard" (default) | "gaussian" | "linear" -- Soft-NMS, ``soft_nms_sigma`` (0.5) being
+    ``tf.image.non_max_suppression_with_scores``' for "gaussian", the returned scores the decayed ones -- and
+    ``class_agnostic`` (False): one list per image over all classes (include/ssd_hip.h ``ssd_nms_config``).  The defaults
+    run ``ssd_combined_nms`` as ever.
     """
     try:
         max_per_class = int(kwargs.pop("max_output_size_per_class"))
@@ -28,11 +33,17 @@ def non_max_suppression(pred_bboxes, pred_labels, **kwargs):
     score_thr = float(kwargs.pop("score_threshold", float("-inf")))
     pad_per_class = bool(kwargs.pop("pad_per_class", False))
     clip_boxes = bool(kwargs.pop("clip_boxes", True))
+    nms_method = kwargs.pop("nms_method", "hard")
+    soft_nms_sigma = kwargs.pop("soft_nms_sigma", 0.5)
+    class_agnostic = bool(kwargs.pop("class_agnostic", False))
     kwargs.pop("name", None)
     if kwargs:
         raise TypeError("unexpected keyword arguments: %s" % sorted(kwargs))
     if pad_per_class:
         raise NotImplementedError("pad_per_class=True is never used by the reference")
+    cfg = _h.nms_config(nms_method, class_agnostic, max_per_class, max_total, iou_thr, score_thr, soft_nms_sigma, clip_boxes)
+    if _h.nms_is_default(nms_method, class_agnostic):
+        cfg = None                                        # validated; the reference's post-processor runs as ever
     boxes = _h.to_dev(pred_bboxes)
     scores = _h.to_dev(pred_labels)
     if boxes.dim() != 4 or scores.dim() != 3:
@@ -50,6 +61,11 @@ def non_max_suppression(pred_bboxes, pred_labels, **kwargs):
     valid = torch.empty((B,), dtype=torch.int32, device=dev)
     nbytes = _h.lib().ssd_decode_nms_workspace_bytes(B, N, C, max_per_class)
     ws = _h.workspace(nbytes)
+    if cfg is not None:
+        _h.check(_h.lib().ssd_combined_nms_cfg(
+            _h.ptr(boxes), _h.ptr(scores), B, N, C, cfg, _h.ptr(ob), _h.ptr(osc), _h.ptr(oc), _h.ptr(valid), _h.vp(0),
+            _h.ptr(ws), ws.numel(), _h.stream()), "non_max_suppression")
+        return ob, osc, oc, valid
     _h.check(_h.lib().ssd_combined_nms(
         _h.ptr(boxes), _h.ptr(scores), B, N, C, max_per_class, max_total, iou_thr, score_thr,
         int(clip_boxes), _h.ptr(ob), _h.ptr(osc), _h.ptr(oc), _h.ptr(valid), _h.vp(0),
