@@ -1050,6 +1050,30 @@ int ssd_conv2d_planes(const ssd_conv_desc* d, const void* in_planes_dev, int pla
                       void* out_planes_dev, long out_plane_stride, int config, int split_k,
                       float* splitk_ws_dev, void* stream);
 
+/* The two-plane fp16 form of the LDS-DMA tiles ("dmah_*" configs; "dmah_*_ks2": two 32-wide k-steps per barrier).
+ * planes = 2 in ssd_split_planes / ssd_join_planes: the activation x as the fp16 pair h = fp16(256 x),
+ * l = fp16(256 x - h), both rounded to nearest even, in the slice-major layout above (2 bytes per element).
+ * RANGE CONTRACT: the form is made for ReLU6 outputs.  |x| <= 255 is represented within
+ *     |join(split(x)) - x| <= 2^-22 |x| + 2^-33;
+ * |x| above ~255.9 becomes inf and joins to a non-finite value -- nothing is silently made finite.  The weights are
+ * two fp16 planes of 2^k w, [2][Kpad / 32][Npad][32] (ssd_conv_f16x2_weight_bytes of device memory, 16-byte aligned),
+ * written by ssd_conv_pack_weights_f16x2 from the packed fp32 weights of ssd_conv_pack_weights (whose buffer keeps its
+ * size and layout); it chooses k so that max |w| 2^k lies in [2^13, 2^14) (all-zero weights: k = 0), returns it in
+ * *k_out, synchronises the stream, and answers SSD_E_UNSUPPORTED for a non-finite weight.  Each fp32 product is three
+ * v_mfma_f32_16x16x32_f16 (wl xh, wh xl, wh xh; the dropped wl xl is ~2^-22 relative) into one fp32 accumulator,
+ * multiplied by the exact 2^-(8 + k) before the epilogue and before split-K partials are written.  An output requested
+ * as planes is written in the same two-plane form (so it obeys the same range contract).
+ * ssd_conv2d_planes_f16x2 takes only "dmah_*" configs and these take only this entry point: bf16 planes, the fp32
+ * entry points and Cin % 32 != 0 answer SSD_E_UNSUPPORTED. */
+size_t ssd_conv_f16x2_weight_bytes(int kh, int kw, int Cin, int Cout);
+int ssd_conv_pack_weights_f16x2(const float* packed_w_dev, int kh, int kw, int Cin, int Cout, void* w_planes_dev,
+                                int* k_out, void* stream);
+int ssd_conv2d_planes_f16x2(const ssd_conv_desc* d, const void* in_planes_dev, long in_plane_stride,
+                            const float* packed_w_dev, const void* w_planes_dev, int w_exp, const float* scale_dev,
+                            const float* shift_dev, const float* residual_dev, float* out_dev,
+                            long out_batch_stride, long out_pixel_stride, void* out_planes_dev,
+                            long out_plane_stride, int config, int split_k, float* splitk_ws_dev, void* stream);
+
 /* Winograd F(2x2,3x3) variant of the same op for 3x3 stride-1 dilation-1 convs with Cin % 16 == 0
  * (the SSD head convs, models/header.py:60-61, and VGG16's 3x3 backbone, models/ssd_vgg16.py:52-72):
  * 2.25x fewer multiplications on the same fp32 MFMA, fused input / output transforms.  Weights are

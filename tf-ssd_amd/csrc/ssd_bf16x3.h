@@ -84,9 +84,45 @@ __device__ __forceinline__ unsigned rne2(float a, float b) {          // two fp3
 __device__ __forceinline__ short rne1(float a) { return (short)(rne2(a, 0.f) & 0xffffu); }
 __device__ __forceinline__ uint2 rne4(const b3_f32x4 v) { return make_uint2(rne2(v[0], v[1]), rne2(v[2], v[3])); }
 
+// ------------------------------------------------------------------------------------------------------------------
+// NP = 2, the two-plane fp16 split ("f16x2"): fp16 carries 11 significand bits, so x = h + l with h = fp16_rn(x),
+// l = fp16_rn(x - h) keeps 22 - 23 bits and an fp32-grade product is THREE v_mfma_f32_16x16x32_f16,
+//
+//     x * y = hl + lh + hh  (+ ll, dropped: ~2^-22 |x y|),
+//
+// half the matrix instructions and two thirds of the plane bytes of the bf16 three-way split.  fp16's range is what
+// the form costs: it is offered only where the range is known.  ACTIVATIONS are scaled by the fixed 2^8 (exact) before
+// the split -- made for ReLU6 outputs, [0, 6] -> [0, 1536]; |x| <= 255 splits within
+//
+//     |join(split(x)) - x| <= 2^-22 |x| + 2^-33        (h: 11 bits; l: 11 more, or fp16's subnormal grid 2^-24 / 2^8)
+//
+// and a larger |x| becomes inf (the join returns a non-finite value: nothing is silently made finite).  WEIGHTS are
+// scaled by a per-layer 2^k chosen on the host from max |w| (conv_f16x2_weight_exp, ssd_conv.h).  The tile multiplies its accumulators
+// by the exact 2^-(8 + k) (ConvParams::acc_scale) before the epilogue.  Both roundings are to nearest even.
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+constexpr float kF16x2ActScale = 256.f;
+
+__device__ __forceinline__ void split_h2(const float a, const float b, unsigned& h, unsigned& l) {      // two values -> packed fp16 pairs (a low)
+    const f16x2_t hh = __builtin_convertvector(b3_f32x2{a, b}, f16x2_t);
+    const b3_f32x2 back = __builtin_convertvector(hh, b3_f32x2);
+    const f16x2_t ll = __builtin_convertvector(b3_f32x2{a - back[0], b - back[1]}, f16x2_t);         // (a - h is exact)
+    h = __builtin_bit_cast(unsigned, hh);
+    l = __builtin_bit_cast(unsigned, ll);
+}
+// four k-values of an activation -> 4 fp16 (8 bytes) per plane, scaled by 2^8
+__device__ __forceinline__ void split4_h(const b3_f32x4 v, uint2& h, uint2& l) {
+    split_h2(v[0] * kF16x2ActScale, v[1] * kF16x2ActScale, h.x, l.x);
+    split_h2(v[2] * kF16x2ActScale, v[3] * kF16x2ActScale, h.y, l.y);
+}
+__device__ __forceinline__ float join_h(const short h, const short l) {
+    const float fh = (float)__builtin_bit_cast(_Float16, h), fl = (float)__builtin_bit_cast(_Float16, l);
+    return (fh + fl) * (1.f / kF16x2ActScale);
+}
+
 template <int NP>
 struct BP {
-    bf16x8 p[NP];          // NP = 3: h, m, l;  NP = 1: the bf16 rounding
+    bf16x8 p[NP];          // NP = 3: h, m, l;  NP = 1: the bf16 rounding;  NP = 2: fp16 h, l (read from planes only)
 };
 template <int NP>
 __device__ __forceinline__ BP<NP> splitN(const b3_f32x4 a, const b3_f32x4 b) {
@@ -102,6 +138,13 @@ __device__ __forceinline__ BP<NP> splitN(const b3_f32x4 a, const b3_f32x4 b) {
 }
 template <int NP>
 __device__ __forceinline__ b3_f32x4 mmaN(const BP<NP>& w, const BP<NP>& x, b3_f32x4 acc) {
+    if constexpr (NP == 2) {          // f16x2: wl xh, wh xl, wh xh -- small terms first
+        const f16x8 wh = __builtin_bit_cast(f16x8, w.p[0]), wl = __builtin_bit_cast(f16x8, w.p[1]);
+        const f16x8 xh = __builtin_bit_cast(f16x8, x.p[0]), xl = __builtin_bit_cast(f16x8, x.p[1]);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl, acc, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xh, acc, 0, 0, 0);
+    }
     if constexpr (NP == 3) {
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.p[1], x.p[1], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.p[0], x.p[2], acc, 0, 0, 0);
@@ -118,7 +161,8 @@ __device__ __forceinline__ void pack_planes(float x, int bf16_mode, short& h, sh
 }
 
 // The activation as bf16 PLANES for the LDS-DMA tiles of its consumers (ssd_convdma.hip): np = 3 the exact split
-// x = h + m + l (planes h, m, l), np = 1 the bf16 rounding; `plane` elements between planes.  Inside a plane the layout is
+// x = h + m + l (planes h, m, l), np = 1 the bf16 rounding, np = 2 the fp16 pair h, l of 2^8 x (same layout, 2 bytes per
+// element); `plane` elements between planes.  Inside a plane the layout is
 // SLICE-MAJOR, [C / 32][P pixels][32 channels]: the 16 tile rows x 64 bytes one LDS-DMA wave-instruction copies are 1 KB of
 // CONTIGUOUS memory for consecutive pixels (a [pixel][C] plane makes them 16 half-used 128-byte lines C * 2 bytes apart:
 // tests/micro/lds_dma_rate.hip measures 35 - 48 GB/s per workgroup for that against 50 - 67 contiguous, and the conv tiles
@@ -132,6 +176,11 @@ __device__ __forceinline__ void store_planes4(short* __restrict__ op, const long
     const long e = plane_elem(pix, c, P);
     if (np == 1) {
         *reinterpret_cast<uint2*>(op + e) = rne4(v);
+    } else if (np == 2) {
+        uint2 h, l;
+        split4_h(v, h, l);
+        *reinterpret_cast<uint2*>(op + e) = h;
+        *reinterpret_cast<uint2*>(op + plane + e) = l;
     } else {
         uint2 h, m, l;
         split4(v, h, m, l);

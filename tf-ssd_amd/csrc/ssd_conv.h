@@ -1,6 +1,9 @@
 // Internal interface between the conv kernels (ssd_conv.hip / ssd_ops.hip) and the graph
 // runner (ssd_net.hip).
 #pragma once
+#include <cmath>
+#include <cstring>
+
 #include "common.h"
 
 namespace ssd {
@@ -33,7 +36,7 @@ struct ConvParams {
     const float* wino_w;   // Winograd F(2x2,3x3) weights U [16][Npad][Cin] (ssd_wino.hip) or nullptr
     int bf16;              // the net's precision-1 mode: the cost model (conv_pick_config) may take the bf16 tiles
     // LDS-DMA tiles (csrc/ssd_convdma.hip): the INPUT as bf16 planes [np][B*H*W*Cin] (np = 3: exact split h, m, l of the
-    // fp32 activation; np = 1: its bf16 rounding), `xp_plane` elements between planes; nullptr = not available
+    // fp32 activation; np = 1: its bf16 rounding; np = 2: the fp16 pair of 2^8 x), `xp_plane` elements between planes; nullptr = not available
     const short* xp;
     long xp_plane;
     int xp_np;
@@ -42,6 +45,11 @@ struct ConvParams {
     short* op;
     long op_plane;
     int op_np;
+    // the two-plane fp16 tiles ("dmah_*", ssd_bf16x3.h): the weights as fp16 planes [2][Kpad / 32][Npad][32] of 2^k w
+    // (launch_pack_f16x2) or nullptr, and the exact power of two 2^-(8 + k) the tile multiplies its accumulators by
+    // before anything else (split-K partials included); the input planes are then xp_np = 2
+    const short* wh;
+    float acc_scale;
 };
 // may a net of this precision (0 fp32, 1 bf16) choose config `cfg`?  fp32 nets never take the bf16 (one-product) tiles;
 // bf16 nets take them instead of the split-bf16 / Winograd tiles (the fp32-MFMA and skinny tiles serve the small tail layers
@@ -82,6 +90,7 @@ struct FusedBlockParams {
     short* e_planes;
     long e_plane;
     int planes_np;
+    int e_planes_np;            // ... of the expanded map's planes (its consumers may take another family than y's: 2 = the fp16 pair)
     int planes_only;            // whole-image kernel: bit 0 = y, bit 1 = the expanded map leave as planes ONLY (no fp32 store; every
                                 // consumer reads the planes).  The pointers y / e_out stay set: they also say which shapes a kernel takes
     int form2;                  // whole-image kernel only: 1 = take the second form (csrc/ssd_imgblock2.hip) where it has a configuration.  The row-band kernels have one form and ignore it
@@ -193,9 +202,35 @@ long dma_grid_blocks(int i, const ConvParams& p);
 int dma_k_tiles(int np, const ConvParams& p);
 void dma_tile(int i, int* BM, int* BN);
 int dma_launch(const ConvParams& p, int i, int np, hipStream_t st);
+// ... then "dmah_*" (np = 2, fp32 nets, ReLU6-bounded inputs): the same tiles on the two-plane fp16 split, index j in
+// [0, dmah_num_configs()): every tile with one 32-wide k-step per barrier, then ("..._ks2") the tiles whose two stages
+// fit the LDS with two
+int dmah_num_configs();
+const char* dmah_config_name(int j);
+int dmah_tile_index(int j);                // the dma_* tile (and "dma3_*" twin) of dmah config j
+bool dmah_config_valid(int j, const ConvParams& p);
+int dmah_k_tiles(int j, const ConvParams& p);
+int dmah_launch(const ConvParams& p, int j, hipStream_t st);
+// fp16 weight planes of a packed [Npad][Kpad] matrix: *absmax_bits_dev receives max |w| as fp32 bits (a non-finite weight:
+// >= 0x7f800000), zeroed by the caller; then the planes of 2^k w
+int launch_absmax_bits(const float* packed, int K, int Cout, unsigned* absmax_bits_dev, hipStream_t st);
+int launch_pack_f16x2(const float* packed, int K, int Cout, int k, short* planes, hipStream_t st);
+// the exponent k of a layer's weight scale from max |w| (as fp32 bits, finite): max |w| 2^k in [2^13, 2^14) -- headroom
+// below fp16's 65504, the low plane's subnormal grid 2^-24 far below the high plane's ulp; all-zero weights: 0
+inline int conv_f16x2_weight_exp(unsigned absmax_bits) {
+    float wmax;
+    std::memcpy(&wmax, &absmax_bits, sizeof(float));
+    if (!(wmax > 0.f)) return 0;
+    int e = 0;
+    (void)std::frexp(wmax, &e);          // wmax = f 2^e, f in [0.5, 1)
+    return 14 - e;
+}
+inline size_t conv_f16x2_plane_shorts(int K, int Cout) { return (size_t)2 * conv_kpad(K) * conv_npad(Cout); }
+bool conv_config_is_dmah(int cfg);
+int conv_dmah_twin(int cfg);               // the "dma3_*" config of the same tile
 int launch_split_planes(const float* x, long n, int C, int np, short* planes, long plane, hipStream_t st);
 int launch_join_planes(const short* planes, long n, int C, int np, long plane, float* x, hipStream_t st);
-bool conv_config_is_dma(int cfg);          // either family
+bool conv_config_is_dma(int cfg);          // any of the three families
 bool conv_config_writes_planes(int cfg, const ConvParams& p);   // the family's epilogue (conv_epilogue / splitk_reduce_kernel) honours ConvParams::op
 
 int launch_dwconv3x3(const float* in, int B, int H, int W, int C, int stride, int pad_t, int pad_l,

@@ -292,14 +292,19 @@ static int bf16_cfg0() { return kNumMfmaCfgs + wino_num_configs() + skinny_num_c
 // then the LDS-DMA tiles over pre-split activation planes (csrc/ssd_convdma.hip): "dma3_*" (fp32 nets), "dmab_*" (bf16 mode)
 static int dma3_cfg0() { return kNumMfmaCfgs + wino_num_configs() + skinny_num_configs() + 2 * mfma3_num_configs(); }
 static int dmab_cfg0() { return dma3_cfg0() + dma_num_configs(); }
-static int direct_cfg() { return dma3_cfg0() + 2 * dma_num_configs(); }
+// then the same tiles on the two-plane fp16 split, "dmah_*" (fp32 nets, ReLU6-bounded inputs: ssd_bf16x3.h)
+static int dmah_cfg0() { return dma3_cfg0() + 2 * dma_num_configs(); }
+static int direct_cfg() { return dmah_cfg0() + dmah_num_configs(); }
 #define kSkinnyCfg0 skinny_cfg0()
 #define kMfma3Cfg0 mfma3_cfg0()
 #define kBf16Cfg0 bf16_cfg0()
 #define kDma3Cfg0 dma3_cfg0()
 #define kDmabCfg0 dmab_cfg0()
+#define kDmahCfg0 dmah_cfg0()
 #define kDirectCfg direct_cfg()
 bool conv_config_is_dma(int cfg) { return cfg >= kDma3Cfg0 && cfg < kDirectCfg; }
+bool conv_config_is_dmah(int cfg) { return cfg >= kDmahCfg0 && cfg < kDirectCfg; }
+int conv_dmah_twin(int cfg) { return conv_config_is_dmah(cfg) ? kDma3Cfg0 + dmah_tile_index(cfg - kDmahCfg0) : cfg; }
 bool conv_config_writes_planes(int cfg, const ConvParams& p) {
     if (cfg == kDirectCfg) return stem_ok(p);              // the RGB stem kernel does, the generic VALU kernel does not
     return (cfg >= 0 && cfg < kNumMfmaCfgs) || (cfg >= kMfma3Cfg0 && cfg < kDirectCfg);      // fp32-MFMA, split-bf16, bf16 and LDS-DMA tiles
@@ -309,7 +314,8 @@ int conv_num_mfma_configs() { return kNumMfmaCfgs; }
 int conv_num_configs() { return kDirectCfg + 1; }
 const char* conv_config_name(int cfg) {
     if (cfg == kDirectCfg) return "direct_valu";
-    if (cfg >= kDmabCfg0 && cfg < kDirectCfg) return dma_config_name(cfg - kDmabCfg0, 1);
+    if (cfg >= kDmahCfg0 && cfg < kDirectCfg) return dmah_config_name(cfg - kDmahCfg0);
+    if (cfg >= kDmabCfg0 && cfg < kDmahCfg0) return dma_config_name(cfg - kDmabCfg0, 1);
     if (cfg >= kDma3Cfg0 && cfg < kDmabCfg0) return dma_config_name(cfg - kDma3Cfg0, 3);
     if (cfg >= kBf16Cfg0 && cfg < kDma3Cfg0) return bf16_config_name(cfg - kBf16Cfg0);
     if (cfg >= kMfma3Cfg0 && cfg < kBf16Cfg0) return mfma3_config_name(cfg - kMfma3Cfg0);
@@ -320,9 +326,9 @@ const char* conv_config_name(int cfg) {
 }
 
 bool conv_config_allowed(int cfg, int precision) {
-    const bool bf16 = (cfg >= kBf16Cfg0 && cfg < kDma3Cfg0) || (cfg >= kDmabCfg0 && cfg < kDirectCfg);
+    const bool bf16 = (cfg >= kBf16Cfg0 && cfg < kDma3Cfg0) || (cfg >= kDmabCfg0 && cfg < kDmahCfg0);
     if (!precision) return !bf16;
-    const bool split = (cfg >= kMfma3Cfg0 && cfg < kBf16Cfg0) || (cfg >= kDma3Cfg0 && cfg < kDmabCfg0);
+    const bool split = (cfg >= kMfma3Cfg0 && cfg < kBf16Cfg0) || (cfg >= kDma3Cfg0 && cfg < kDmabCfg0) || conv_config_is_dmah(cfg);
     const bool wino = cfg >= kNumMfmaCfgs && cfg < kSkinnyCfg0;
     return !split && !wino;
 }
@@ -333,7 +339,8 @@ static bool is_gemm1x1(const ConvParams& p) {
 
 bool conv_config_valid(int cfg, const ConvParams& p) {
     if (cfg == kDirectCfg) return (size_t)p.K * ((p.Cout + 3) & ~3) * 4 <= 64 * 1024;
-    if (cfg >= kDmabCfg0 && cfg < kDirectCfg) return dma_config_valid(cfg - kDmabCfg0, 1, p);
+    if (cfg >= kDmahCfg0 && cfg < kDirectCfg) return dmah_config_valid(cfg - kDmahCfg0, p);
+    if (cfg >= kDmabCfg0 && cfg < kDmahCfg0) return dma_config_valid(cfg - kDmabCfg0, 1, p);
     if (cfg >= kDma3Cfg0 && cfg < kDmabCfg0) return dma_config_valid(cfg - kDma3Cfg0, 3, p);
     if (cfg >= kBf16Cfg0 && cfg < kDma3Cfg0) return mfma3_config_valid(cfg - kBf16Cfg0, p);
     if (cfg >= kMfma3Cfg0 && cfg < kBf16Cfg0) return mfma3_config_valid(cfg - kMfma3Cfg0, p);
@@ -389,7 +396,8 @@ int conv_pick_config(const ConvParams& p) {
 }
 
 long conv_grid_blocks(int cfg, const ConvParams& p) {
-    if (cfg >= kDmabCfg0 && cfg < kDirectCfg) return dma_grid_blocks(cfg - kDmabCfg0, p);
+    if (cfg >= kDmahCfg0 && cfg < kDirectCfg) return dma_grid_blocks(dmah_tile_index(cfg - kDmahCfg0), p);
+    if (cfg >= kDmabCfg0 && cfg < kDmahCfg0) return dma_grid_blocks(cfg - kDmabCfg0, p);
     if (cfg >= kDma3Cfg0 && cfg < kDmabCfg0) return dma_grid_blocks(cfg - kDma3Cfg0, p);
     if (cfg >= kBf16Cfg0 && cfg < kDma3Cfg0) return mfma3_grid_blocks(cfg - kBf16Cfg0, p);
     if (cfg >= kMfma3Cfg0 && cfg < kBf16Cfg0) return mfma3_grid_blocks(cfg - kMfma3Cfg0, p);
@@ -400,7 +408,8 @@ long conv_grid_blocks(int cfg, const ConvParams& p) {
     return ((p.M + g.BM - 1) / g.BM) * ((p.Cout + g.BN - 1) / g.BN);
 }
 int conv_k_tiles(int cfg, const ConvParams& p) {
-    if (cfg >= kDma3Cfg0 && cfg < kDirectCfg) return dma_k_tiles(cfg >= kDmabCfg0 ? 1 : 3, p);
+    if (cfg >= kDmahCfg0 && cfg < kDirectCfg) return dmah_k_tiles(cfg - kDmahCfg0, p);
+    if (cfg >= kDma3Cfg0 && cfg < kDmahCfg0) return dma_k_tiles(cfg >= kDmabCfg0 ? 1 : 3, p);
     if (cfg >= kMfma3Cfg0 && cfg < kDma3Cfg0) return mfma3_k_tiles(p);      // (split-bf16 and bf16 tiles)
     if (cfg >= kSkinnyCfg0 && cfg < kMfma3Cfg0) return p.K / 16;
     if (cfg >= kNumMfmaCfgs && cfg < kSkinnyCfg0) return wino_k_tiles(p);
@@ -422,7 +431,12 @@ int conv_launch(const ConvParams& p, int cfg, hipStream_t st) {
     // a plane-only output (no fp32 destination): only the families whose epilogue writes the planes, dense outputs only
     SSD_UNSUPPORTED_IF(!p.out && !(p.op && !p.n_split && (p.Cout & 3) == 0 && conv_config_writes_planes(cfg, p)),
                        "conv2d: config %s cannot write a plane-only output", conv_config_name(cfg));
-    if (cfg >= kDma3Cfg0 && cfg < kDirectCfg) {
+    if (cfg >= kDmahCfg0 && cfg < kDirectCfg) {
+        const int rc = dmah_launch(p, cfg - kDmahCfg0, st);
+        if (rc || p.split_k <= 1) return rc;
+        return launch_splitk_reduce(p, st);
+    }
+    if (cfg >= kDma3Cfg0 && cfg < kDmahCfg0) {
         const bool b1 = cfg >= kDmabCfg0;
         const int rc = dma_launch(p, cfg - (b1 ? kDmabCfg0 : kDma3Cfg0), b1 ? 1 : 3, st);
         if (rc || p.split_k <= 1) return rc;
@@ -595,20 +609,78 @@ int ssd_split_planes(const float* x_dev, long n, int channels, int planes, void*
 }
 
 int ssd_join_planes(const void* planes_dev, long n, int channels, int planes, long plane_stride, float* x_dev, void* stream) {
-    SSD_CHECK_ARG(x_dev && planes_dev && n >= 0 && (planes == 1 || planes == 3) && plane_stride >= n, "ssd_join_planes: bad arguments");
+    SSD_CHECK_ARG(x_dev && planes_dev && n >= 0 && planes >= 1 && planes <= 3 && plane_stride >= n, "ssd_join_planes: bad arguments");
     return launch_join_planes(static_cast<const short*>(planes_dev), n, channels, planes, plane_stride, x_dev, (hipStream_t)stream);
 }
+
+size_t ssd_conv_f16x2_weight_bytes(int kh, int kw, int Cin, int Cout) {
+    if (kh < 1 || kw < 1 || Cin < 1 || Cout < 1) return 0;
+    return conv_f16x2_plane_shorts(kh * kw * Cin, Cout) * sizeof(short);
+}
+
+int ssd_conv_pack_weights_f16x2(const float* packed_w_dev, int kh, int kw, int Cin, int Cout, void* w_planes_dev, int* k_out,
+                                void* stream) {
+    SSD_CHECK_ARG(packed_w_dev && w_planes_dev && k_out, "ssd_conv_pack_weights_f16x2: NULL pointer");
+    SSD_CHECK_ARG(kh >= 1 && kw >= 1 && Cin >= 1 && Cout >= 1, "ssd_conv_pack_weights_f16x2: bad shape");
+    SSD_CHECK_ARG(((uintptr_t)w_planes_dev & 15) == 0, "ssd_conv_pack_weights_f16x2: the planes must be 16-byte aligned");
+    const int K = kh * kw * Cin;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned* bits_dev = nullptr;
+    unsigned bits = 0;
+    SSD_HIP(hipMalloc((void**)&bits_dev, sizeof(unsigned)));
+    int rc = hipMemsetAsync(bits_dev, 0, sizeof(unsigned), st) == hipSuccess ? SSD_OK : SSD_E_HIP;
+    if (!rc) rc = launch_absmax_bits(packed_w_dev, K, Cout, bits_dev, st);
+    if (!rc && (hipMemcpyAsync(&bits, bits_dev, sizeof(unsigned), hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipStreamSynchronize(st) != hipSuccess)) rc = SSD_E_HIP;
+    (void)hipFree(bits_dev);
+    if (rc) return rc;
+    SSD_UNSUPPORTED_IF(bits >= 0x7f800000u, "ssd_conv_pack_weights_f16x2: a non-finite weight: the layer cannot take the two-plane fp16 tiles");
+    *k_out = conv_f16x2_weight_exp(bits);
+    return launch_pack_f16x2(packed_w_dev, K, Cout, *k_out, static_cast<short*>(w_planes_dev), st);
+}
+
+static int conv2d_planes_impl(const ssd_conv_desc* d, const void* in_planes_dev, int planes, long in_plane_stride,
+                              const float* packed_w_dev, const void* w_planes_dev, int w_exp, const float* scale_dev,
+                              const float* shift_dev, const float* residual_dev, float* out_dev, long out_batch_stride,
+                              long out_pixel_stride, void* out_planes_dev, long out_plane_stride, int config, int split_k,
+                              float* splitk_ws_dev, void* stream);
 
 int ssd_conv2d_planes(const ssd_conv_desc* d, const void* in_planes_dev, int planes, long in_plane_stride,
                       const float* packed_w_dev, const float* scale_dev, const float* shift_dev, const float* residual_dev,
                       float* out_dev, long out_batch_stride, long out_pixel_stride, void* out_planes_dev,
                       long out_plane_stride, int config, int split_k, float* splitk_ws_dev, void* stream) {
+    return conv2d_planes_impl(d, in_planes_dev, planes, in_plane_stride, packed_w_dev, nullptr, 0, scale_dev, shift_dev, residual_dev,
+                              out_dev, out_batch_stride, out_pixel_stride, out_planes_dev, out_plane_stride, config, split_k,
+                              splitk_ws_dev, stream);
+}
+
+int ssd_conv2d_planes_f16x2(const ssd_conv_desc* d, const void* in_planes_dev, long in_plane_stride, const float* packed_w_dev,
+                            const void* w_planes_dev, int w_exp, const float* scale_dev, const float* shift_dev,
+                            const float* residual_dev, float* out_dev, long out_batch_stride, long out_pixel_stride,
+                            void* out_planes_dev, long out_plane_stride, int config, int split_k, float* splitk_ws_dev,
+                            void* stream) {
+    SSD_CHECK_ARG(w_planes_dev != nullptr, "conv2d_planes_f16x2: the fp16 weight planes are NULL");
+    SSD_CHECK_ARG(w_exp >= -100 && w_exp <= 100, "conv2d_planes_f16x2: weight exponent %d out of range", w_exp);
+    return conv2d_planes_impl(d, in_planes_dev, 2, in_plane_stride, packed_w_dev, w_planes_dev, w_exp, scale_dev, shift_dev,
+                              residual_dev, out_dev, out_batch_stride, out_pixel_stride, out_planes_dev, out_plane_stride, config,
+                              split_k, splitk_ws_dev, stream);
+}
+
+static int conv2d_planes_impl(const ssd_conv_desc* d, const void* in_planes_dev, int planes, long in_plane_stride,
+                              const float* packed_w_dev, const void* w_planes_dev, int w_exp, const float* scale_dev,
+                              const float* shift_dev, const float* residual_dev, float* out_dev, long out_batch_stride,
+                              long out_pixel_stride, void* out_planes_dev, long out_plane_stride, int config, int split_k,
+                              float* splitk_ws_dev, void* stream) {
     ConvParams p;
     int rc = fill_conv_params(d, &p);
     if (rc) return rc;
     if (p.M == 0) return SSD_OK;
     SSD_CHECK_ARG(in_planes_dev && packed_w_dev && (out_dev || out_planes_dev), "conv2d_planes: NULL pointer");
-    SSD_CHECK_ARG(planes == 1 || planes == 3, "conv2d_planes: planes must be 1 (bf16 mode) or 3 (exact split)");
+    SSD_CHECK_ARG(planes >= 1 && planes <= 3, "conv2d_planes: planes must be 1 (bf16 mode), 2 (fp16 pair) or 3 (exact split)");
+    if (w_planes_dev) {
+        p.wh = static_cast<const short*>(w_planes_dev);
+        p.acc_scale = ldexpf(1.f, -(8 + w_exp));
+    }
     SSD_CHECK_ARG(in_plane_stride >= (long)p.B * p.H * p.W * p.Cin, "conv2d_planes: in_plane_stride shorter than the tensor");
     SSD_CHECK_ARG(!d->has_residual || residual_dev, "conv2d_planes: has_residual set but residual is NULL");
     SSD_CHECK_ARG(config >= 0 && config < conv_num_configs() && conv_config_is_dma(config), "conv2d_planes: config %d is not an LDS-DMA tile", config);

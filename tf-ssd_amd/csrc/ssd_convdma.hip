@@ -17,19 +17,23 @@
 //     tap-validity mask); two LDS stages, the next tile's DMA is issued before the current tile's MFMAs and waited for
 //     (vmcnt(0)) at the one barrier per tile;
 //   * np = 3 (fp32 nets): six v_mfma_f32_16x16x32_bf16 per 16 x 16 x 32 block on the exact three-way split, fp32 results
-//     (ssd_bf16x3.h); np = 1 (the bf16 mode): bf16 STORAGE of the activation, one MFMA per block, K = 64 per barrier.
+//     (ssd_bf16x3.h); np = 1 (the bf16 mode): bf16 STORAGE of the activation, one MFMA per block, K = 64 per barrier;
+//   * np = 2 (fp32 nets, ReLU6-bounded inputs): the two-plane fp16 split of 2^8 x and 2^k w, three
+//     v_mfma_f32_16x16x32_f16 per block (ssd_bf16x3.h) -- half the matrix instructions and two thirds of the plane bytes
+//     of np = 3 -- with K = 32 or (tiles whose two stages fit 160 KB) K = 64 per barrier; the accumulators are multiplied
+//     by the exact 2^-(8 + k) before the epilogue.
 // Epilogue = conv_epilogue (ssd_conv_mfma.h): BN / bias, activation, residual, head routing, optional plane output.
-// config ids: behind the bf16 tiles (ssd_conv.hip): "dma3_*" (np = 3) and "dmab_*" (np = 1).
+// config ids: behind the bf16 tiles (ssd_conv.hip): "dma3_*" (np = 3), "dmab_*" (np = 1), "dmah_*" / "dmah_*_ks2" (np = 2).
 #include "ssd_block_common.h"
 #include "ssd_conv_mfma.h"
 
 namespace ssd {
 
 // (the body is a __device__ function: a __global__ body that declares __amdgpu_buffer_rsrc_t objects loses its host stub)
-template <int MT, int NT, int WM, int WN, int NP, bool GEMM1X1>
+template <int MT, int NT, int WM, int WN, int NP, bool GEMM1X1, int KSH = 1>
 __device__ __forceinline__ void conv_dma_body(const ConvParams& p, char* __restrict__ dsm) {
-    constexpr int KS = NP == 1 ? 2 : 1;          // 32-wide k-steps per LDS stage
-    constexpr int WPL = NP == 1 ? 3 : 0;         // first weight plane: [h, m, l, r]
+    constexpr int KS = NP == 1 ? 2 : NP == 2 ? KSH : 1;      // 32-wide k-steps per LDS stage (np = 2: either, by configuration)
+    constexpr int WPL = NP == 1 ? 3 : 0;         // first weight plane: [h, m, l, r] (np = 2: the fp16 planes [h, l] of ConvParams::wh)
     constexpr int BM = 16 * MT * WM, BN = 16 * NT * WN, NW = WM * WN;
     constexpr int RBX = BM / 16, RBW = BN / 16;                          // 16-row blocks of the two operands
     constexpr int RPX = (RBX + NW - 1) / NW, RPW = (RBW + NW - 1) / NW;   // ... per wave
@@ -60,7 +64,7 @@ __device__ __forceinline__ void conv_dma_body(const ConvParams& p, char* __restr
     for (int pl = 0; pl < NP; ++pl)
         xrs[pl] = __builtin_amdgcn_make_buffer_rsrc(const_cast<short*>(p.xp + pl * p.xp_plane + xbase_e), 0, (int)xrange, 0x00020000);
     const long wplane_b = (long)p.Npad * p.Kpad * 2;
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<short*>(p.w3), 0, (int)(4 * wplane_b), 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<short*>(NP == 2 ? p.wh : p.w3), 0, (int)((NP == 2 ? 2 : 4) * wplane_b), 0x00020000);
 
     int xoff[RPX];
     unsigned xvalid[RPX];
@@ -98,7 +102,9 @@ __device__ __forceinline__ void conv_dma_body(const ConvParams& p, char* __restr
 
     // ---- K walk: tiles of KS k-steps; general path channel-slice-major with the taps innermost (ssd_conv_mfma.h)
     const int nks = p.K / 32;                                       // K % 32 == 0 (host check)
-    const int ntiles = GEMM1X1 ? (nks + KS - 1) / KS : ntaps * (p.Cin / (32 * KS));
+    // (np = 2 with two k-steps per stage: the last channel tile of a tap may hold one slice -- Cin % 64 == 32)
+    const int nsl = p.Cin / 32;
+    const int ntiles = GEMM1X1 ? (nks + KS - 1) / KS : ntaps * (NP == 2 ? (nsl + KS - 1) / KS : p.Cin / (32 * KS));
     int kt_begin = 0, kt_end = ntiles;
     if (p.split_k > 1) {
         const int per = (ntiles + p.split_k - 1) / p.split_k;
@@ -136,7 +142,11 @@ __device__ __forceinline__ void conv_dma_body(const ConvParams& p, char* __restr
         }
     };
     // k-steps of the tile at l_k0 that exist (1x1 path with KS = 2: the last tile may hold one)
-    auto steps_here = [&]() -> int { return KS == 1 ? 1 : min(KS, nks - l_k0 / 32); };
+    auto steps_here = [&]() -> int {
+        if (KS == 1) return 1;
+        if (NP == 2 && !GEMM1X1) return min(KS, nsl - (l_ci >> 5));
+        return min(KS, nks - l_k0 / 32);
+    };
 
     auto issue = [&](int stage) {              // DMA of the tile described by the l_* state into `stage`
         char* sb = dsm + stage * STAGE;
@@ -227,13 +237,19 @@ __device__ __forceinline__ void conv_dma_body(const ConvParams& p, char* __restr
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the next tile's copies, before the barrier that publishes them
         __syncthreads();
     }
+    if constexpr (NP == 2) {         // back from the operands' scales 2^8 (activation) and 2^k (weights): exact, before anything else
+#pragma unroll
+        for (int mi = 0; mi < MT; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < NT; ++ni) acc[mi][ni] *= p.acc_scale;
+    }
     conv_epilogue<MT, NT>(p, acc, m0, n0, wm, wn, lane, HoWo);
 }
 
-template <int MT, int NT, int WM, int WN, int NP, bool GEMM1X1>
+template <int MT, int NT, int WM, int WN, int NP, bool GEMM1X1, int KSH = 1>
 __global__ __launch_bounds__(64 * WM * WN) void conv_dma_kernel(const ConvParams p) {
     extern __shared__ __attribute__((aligned(1024))) char dsm_dma[];
-    conv_dma_body<MT, NT, WM, WN, NP, GEMM1X1>(p, dsm_dma);
+    conv_dma_body<MT, NT, WM, WN, NP, GEMM1X1, KSH>(p, dsm_dma);
 }
 
 namespace {
@@ -242,13 +258,24 @@ typedef void (*convd_kernel_t)(const ConvParams);
 struct ConvDCfg {
     const char* name3;
     const char* name1;
+    const char* nameh;       // the two-plane fp16 form, one k-step per barrier ...
+    const char* nameh2;      // ... and two ("_ks2"): only the tiles whose two stages fit 160 KB, BM + BN <= 320
     int BM, BN, threads;
-    convd_kernel_t gemm3, general3, gemm1, general1;
+    convd_kernel_t gemm3, general3, gemm1, general1, gemmh, generalh, gemmh2, generalh2;
 };
+// (the k64 kernels of a tile that does not fit are never instantiated)
+template <int MT, int NT, int WM, int WN, bool GEMM1X1>
+constexpr convd_kernel_t dmah_ks2_kernel() {
+    if constexpr (16 * MT * WM + 16 * NT * WN <= 320) return conv_dma_kernel<MT, NT, WM, WN, 2, GEMM1X1, 2>;
+    else return nullptr;
+}
 #define DCFG(MT, NT, WM, WN)                                                                                  \
-    {"dma3_" #MT "x" #NT "_" #WM "x" #WN, "dmab_" #MT "x" #NT "_" #WM "x" #WN, 16 * MT * WM, 16 * NT * WN, 64 * WM * WN, \
+    {"dma3_" #MT "x" #NT "_" #WM "x" #WN, "dmab_" #MT "x" #NT "_" #WM "x" #WN, "dmah_" #MT "x" #NT "_" #WM "x" #WN,          \
+     "dmah_" #MT "x" #NT "_" #WM "x" #WN "_ks2", 16 * MT * WM, 16 * NT * WN, 64 * WM * WN,                       \
      conv_dma_kernel<MT, NT, WM, WN, 3, true>, conv_dma_kernel<MT, NT, WM, WN, 3, false>,                       \
-     conv_dma_kernel<MT, NT, WM, WN, 1, true>, conv_dma_kernel<MT, NT, WM, WN, 1, false>}
+     conv_dma_kernel<MT, NT, WM, WN, 1, true>, conv_dma_kernel<MT, NT, WM, WN, 1, false>,                       \
+     conv_dma_kernel<MT, NT, WM, WN, 2, true>, conv_dma_kernel<MT, NT, WM, WN, 2, false>,                       \
+     dmah_ks2_kernel<MT, NT, WM, WN, true>(), dmah_ks2_kernel<MT, NT, WM, WN, false>()}
 const ConvDCfg kCfgD[] = {
     DCFG(4, 4, 4, 2),    // 256 x 128, 8 waves
     DCFG(2, 4, 4, 2),    // 128 x 128, 8 waves
@@ -266,6 +293,19 @@ const ConvDCfg kCfgD[] = {
     DCFG(2, 5, 6, 2),    // 192 x 160, 12 waves (round 6: the 150-column heads on one tile column)
 };
 constexpr int kNumCfgD = sizeof(kCfgD) / sizeof(kCfgD[0]);
+// dmah config j: j < kNumCfgD the tile j with one k-step per barrier, then the k64 forms in table order
+struct DmahList {
+    int n = 0, tile[2 * kNumCfgD], ks[2 * kNumCfgD];
+    DmahList() {
+        for (int i = 0; i < kNumCfgD; ++i) { tile[n] = i; ks[n++] = 1; }
+        for (int i = 0; i < kNumCfgD; ++i)
+            if (kCfgD[i].gemmh2) { tile[n] = i; ks[n++] = 2; }
+    }
+};
+const DmahList& dmah_list() {
+    static const DmahList l;
+    return l;
+}
 
 bool cd_gemm1x1(const ConvParams& p) {
     return p.kh == 1 && p.kw == 1 && p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 && p.Ho == p.H && p.Wo == p.W;
@@ -280,13 +320,17 @@ __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restri
         store_planes4_lin(planes, plane, np, e * 4, C, P, *reinterpret_cast<const f32x4*>(x + e * 4));
 }
 
-// bf16 planes -> fp32 (h + m + l is exact; np = 1: the rounded value): debug fetches / tests
+// bf16 planes -> fp32 (h + m + l is exact; np = 1: the rounded value; np = 2: within 2^-22 |x| + 2^-33): debug fetches / tests
 __global__ __launch_bounds__(256) void join_planes_kernel(const short* __restrict__ planes, const long n, const int C, const int np,
                                                           const long plane, float* __restrict__ x) {
     const long P = n / C;
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
         const long pix = e / C;
         const long s = plane_elem(pix, (int)(e - pix * C), P);
+        if (np == 2) {          // the fp16 pair of 2^8 x (ssd_bf16x3.h)
+            x[e] = join_h(planes[s], planes[plane + s]);
+            continue;
+        }
         float v = __uint_as_float((unsigned)(unsigned short)planes[s] << 16);
         if (np == 3) {
             v += __uint_as_float((unsigned)(unsigned short)planes[plane + s] << 16);
@@ -296,14 +340,34 @@ __global__ __launch_bounds__(256) void join_planes_kernel(const short* __restric
     }
 }
 
+// max |w| of the packed matrix as fp32 bits (non-negative floats order like their bits; NaN / inf land at >= 0x7f800000)
+__global__ __launch_bounds__(256) void absmax_bits_kernel(const float* __restrict__ w, const long total, unsigned* __restrict__ out) {
+    unsigned m = 0;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) m = max(m, __float_as_uint(w[e]) & 0x7fffffffu);
+    atomicMax(out, m);
+}
+// fp16 planes h, l of 2^k w, slice-major [Kpad / 32][Npad][32] like the bf16 planes
+__global__ __launch_bounds__(256) void pack_f16x2_kernel(const float* __restrict__ w, const long total, const int Kpad, const int Npad,
+                                                         const float scale, short* __restrict__ out) {
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+        const long n = e / Kpad;
+        const long d = plane_elem(n, (int)(e - n * Kpad), Npad);
+        unsigned h, l;
+        split_h2(w[e] * scale, 0.f, h, l);
+        out[d] = (short)(h & 0xffffu);
+        out[total + d] = (short)(l & 0xffffu);
+    }
+}
+
 }  // namespace
 
 int dma_num_configs() { return kNumCfgD; }
 const char* dma_config_name(int i, int np) { return (i >= 0 && i < kNumCfgD) ? (np == 1 ? kCfgD[i].name1 : kCfgD[i].name3) : "?"; }
 bool dma_config_valid(int i, int np, const ConvParams& p) {
     if (i < 0 || i >= kNumCfgD) return false;
-    if (!p.xp || !p.w3 || p.xp_np != np) return false;
-    if (((uintptr_t)p.xp & 15) || ((uintptr_t)p.w3 & 15) || (p.xp_plane & 7)) return false;
+    const short* wpl = np == 2 ? p.wh : p.w3;        // (np = 2: the fp16 weight planes; every family refuses planes of another)
+    if (!p.xp || !wpl || p.xp_np != np) return false;
+    if (((uintptr_t)p.xp & 15) || ((uintptr_t)wpl & 15) || (p.xp_plane & 7)) return false;
     if (p.M > 0x7fffffffL - 1024) return false;
     if (4 * (long)p.Npad * p.Kpad * 2 > 0x7fffffffL) return false;
     // slice-major planes: a K tile's channel slice is a scalar offset of up to the whole plane (31 bits)
@@ -341,8 +405,60 @@ int dma_launch(const ConvParams& p, int i, int np, hipStream_t st) {
     return SSD_OK;
 }
 
+int dmah_num_configs() { return dmah_list().n; }
+const char* dmah_config_name(int j) {
+    const DmahList& l = dmah_list();
+    return (j >= 0 && j < l.n) ? (l.ks[j] == 2 ? kCfgD[l.tile[j]].nameh2 : kCfgD[l.tile[j]].nameh) : "?";
+}
+int dmah_tile_index(int j) { return (j >= 0 && j < dmah_list().n) ? dmah_list().tile[j] : -1; }
+bool dmah_config_valid(int j, const ConvParams& p) {
+    if (j < 0 || j >= dmah_list().n) return false;
+    if (!(p.acc_scale > 0.f)) return false;
+    return dma_config_valid(dmah_list().tile[j], 2, p);
+}
+int dmah_k_tiles(int j, const ConvParams& p) {
+    const int ks = (j >= 0 && j < dmah_list().n) ? dmah_list().ks[j] : 1;
+    if (cd_gemm1x1(p)) return ((p.K + 31) / 32 + ks - 1) / ks;
+    return p.kh * p.kw * ((p.Cin / 32 + ks - 1) / ks);
+}
+int dmah_launch(const ConvParams& p, int j, hipStream_t st) {
+    if (!dmah_config_valid(j, p)) {
+        set_error("conv2d: two-plane fp16 LDS-DMA config %d cannot run Cin=%d k=%dx%d (input planes %s, %d of them; fp16 weight planes %s)", j,
+                  p.Cin, p.kh, p.kw, p.xp ? "present" : "missing", p.xp_np, p.wh ? "present" : "missing");
+        return SSD_E_UNSUPPORTED;
+    }
+    const int i = dmah_list().tile[j], ks = dmah_list().ks[j];
+    const long blocks = dma_grid_blocks(i, p);
+    SSD_UNSUPPORTED_IF(blocks > 0x7fffffffL, "conv2d: grid too large");
+    const ConvDCfg& g = kCfgD[i];
+    const convd_kernel_t fn = ks == 2 ? (cd_gemm1x1(p) ? g.gemmh2 : g.generalh2) : (cd_gemm1x1(p) ? g.gemmh : g.generalh);
+    const int lds = 2 * ks * 2 * (g.BM + g.BN) * 64;
+    if (lds > 64 * 1024) SSD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    dim3 grid((unsigned)blocks, p.split_k > 1 ? p.split_k : 1);
+    hipLaunchKernelGGL(fn, grid, dim3(g.threads), lds, st, p);
+    SSD_LAUNCH_CHECK();
+    return SSD_OK;
+}
+
+int launch_absmax_bits(const float* packed, int K, int Cout, unsigned* absmax_bits_dev, hipStream_t st) {
+    const long total = (long)conv_kpad(K) * conv_npad(Cout);
+    if (total == 0) return SSD_OK;
+    const int blocks = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
+    hipLaunchKernelGGL(absmax_bits_kernel, dim3(blocks), dim3(256), 0, st, packed, total, absmax_bits_dev);
+    SSD_LAUNCH_CHECK();
+    return SSD_OK;
+}
+int launch_pack_f16x2(const float* packed, int K, int Cout, int k, short* planes, hipStream_t st) {
+    const long total = (long)conv_kpad(K) * conv_npad(Cout);
+    if (total == 0) return SSD_OK;
+    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    hipLaunchKernelGGL(pack_f16x2_kernel, dim3(blocks), dim3(256), 0, st, packed, total, conv_kpad(K), conv_npad(Cout), ldexpf(1.f, k), planes);
+    SSD_LAUNCH_CHECK();
+    return SSD_OK;
+}
+
 int launch_split_planes(const float* x, long n, int C, int np, short* planes, long plane, hipStream_t st) {
-    SSD_CHECK_ARG(n % 4 == 0 && (np == 1 || np == 3), "split_planes: element count %ld must be a multiple of 4, planes 1 or 3", n);
+    SSD_CHECK_ARG(n % 4 == 0 && np >= 1 && np <= 3, "split_planes: element count %ld must be a multiple of 4, planes 1, 2 or 3", n);
     SSD_CHECK_ARG(C > 0 && C % 32 == 0 && n % C == 0, "split_planes: %d channels (slice-major planes need a multiple of 32 that divides the %ld elements)", C, n);
     SSD_UNSUPPORTED_IF((((uintptr_t)x) & 15) || (((uintptr_t)planes) & 7) || (plane & 3),
                        "split_planes: needs a 16-byte aligned source and 8-byte aligned planes (16-byte loads, 8-byte stores)");

@@ -207,7 +207,7 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image_block_kernel(const Fused
             if (p.e_out && real[t]) {
                 const long eo = ((long)img * H * W + opix[t]) * p.Ce + cbeg + j * kIC + g4 * 4;
                 if (!(p.planes_only & 2)) *reinterpret_cast<f32x4*>(p.e_out + eo) = v;
-                if (p.e_planes) store_planes4(p.e_planes, p.e_plane, p.planes_np, (long)img * H * W + opix[t], cbeg + j * kIC + g4 * 4, (long)B * H * W, v);
+                if (p.e_planes) store_planes4(p.e_planes, p.e_plane, p.e_planes_np, (long)img * H * W + opix[t], cbeg + j * kIC + g4 * 4, (long)B * H * W, v);
             }
         }
     };
@@ -535,7 +535,7 @@ __global__ __launch_bounds__(kIThreads) void mbv2_image16_block_kernel(const Fus
             if (p.e_out && real[t]) {
                 const long eo = ((long)img * H * W + opix[t]) * p.Ce + cbeg + j * kIC + g4 * 4;
                 if (!(p.planes_only & 2)) *reinterpret_cast<f32x4*>(p.e_out + eo) = v;
-                if (p.e_planes) store_planes4(p.e_planes, p.e_plane, p.planes_np, (long)img * H * W + opix[t], cbeg + j * kIC + g4 * 4, (long)B * H * W, v);
+                if (p.e_planes) store_planes4(p.e_planes, p.e_plane, p.e_planes_np, (long)img * H * W + opix[t], cbeg + j * kIC + g4 * 4, (long)B * H * W, v);
             }
         }
     };

@@ -194,7 +194,7 @@ __device__ __forceinline__ void image16v2_body(const FusedBlockParams& p, float*
             if (S == 2 && p.e_out && real[t]) {       // block 13: the expanded map is SSD feature map 1 -- written once, from here
                 const int ch = cbeg + (j >> 1) * 32 + g4 * 8 + (j & 1) * 4;       // the lane's four channels of chunk j
                 if (!(p.planes_only & 2)) *reinterpret_cast<f32x4*>(p.e_out + ((long)img * (H * W) + opix[t]) * p.Ce + ch) = v;
-                if (p.e_planes) store_planes4(p.e_planes, p.e_plane, p.planes_np, (long)img * (H * W) + opix[t], ch, (long)B * (H * W), v);
+                if (p.e_planes) store_planes4(p.e_planes, p.e_plane, p.e_planes_np, (long)img * (H * W) + opix[t], ch, (long)B * (H * W), v);
             }
         }
     };

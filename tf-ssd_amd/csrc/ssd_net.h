@@ -41,7 +41,9 @@ struct Tensor {
     // chosen configuration is an LDS-DMA tile (planes_live, recomputed with the launch plan)
     short* planes = nullptr;
     long plane_stride = 0;    // elements between planes
-    int planes_np = 0;        // 3: exact split h, m, l (fp32 nets); 1: bf16 rounding (the bf16 mode)
+    int planes_np = 0;        // 3: exact split h, m, l (fp32 nets); 1: bf16 rounding (the bf16 mode); 2: the fp16 pair of 2^8 x (fp32 nets, a
+                              // ReLU6-bounded tensor whose plane readers all chose "dmah_*" tiles: finalize_resolve_f16x2, ssd_net.hip)
+    int planes_cap = 0;       // planes the allocation holds (planes_np <= planes_cap)
     bool planes_live = false;
     // the planes ARE the tensor: its producer skips the fp32 store into `dev` (the arena slot stays, unwritten).  Decided with
     // the launch plan (plan_steps, ssd_net.hip): planes live, every running reader a dense conv on an LDS-DMA tile, the
@@ -71,6 +73,8 @@ struct Layer {
     float* shift = nullptr;
     int cfg = -1;
     int split_k = 1;
+    float* wh = nullptr;            // fp16 planes [2][Kpad / 32][Npad][32] of 2^wh_k w for the "dmah_*" tiles: conv layers of fp32 nets whose
+    int wh_k = 0;                   // input is ReLU6-bounded and whose weights are finite (ssd_bf16x3.h); kept while the chosen tile reads them
     // fused inverted-residual block: LK_FUSED layer points at its three member layers;
     // members carry the index of their LK_FUSED layer in `fused_by`
     int f_expand = -1, f_dw = -1, f_project = -1;
@@ -150,6 +154,7 @@ struct ssd_net {
     bool image_split = true;        // fp32 nets: the finalize-time race also times the image kernel's split-bf16 form (img_choice 2; option "image_split" 0: leave it out)
     bool image_v2 = true;           // whole-image kernel only (the row-band kernels of blocks 1-6 have one form): the second form (ssd_imgblock2.hip: compile-time geometry, adjacent pixels per lane) where it has a configuration; 0 = the first form (A/B; equal within tolerance, not bitwise: the k-slot order inside the project MFMAs differs)
     bool conv_dma = true;           // offer the LDS-DMA tiles over pre-split activation planes (ssd_convdma.hip) to the autotune / accept them from tables
+    bool conv_f16x2 = true;         // accept the two-plane fp16 tiles ("dmah_*") from tables / offer them to the autotune; 0: a "dmah_*" line runs its "dma3_*" twin (the same tile and split-K)
     bool plane_only = true;         // drop the fp32 copy of an activation whose readers all take its bf16 planes (Tensor::plane_only); 0: store both
     bool image_ticket = false;      // combine the channel-group slabs inside the launch (arrival ticket) instead of by a second launch
     float* img_slabs = nullptr;     // its partial-sum slabs and arrival tickets (sized for max_batch)
@@ -159,6 +164,7 @@ struct ssd_net {
     std::vector<float*> owned;      // device allocations to free
     float* arena = nullptr;
     size_t arena_bytes = 0, plane_bytes = 0, slab_bytes = 0;    // ssd_net_memory_bytes
+    size_t wplane_bytes = 0;        // the fp16 weight planes of the layers on "dmah_*" tiles (counted with the planes)
     float* splitk_ws = nullptr;
     size_t splitk_floats = 0;
     // predict() scratch

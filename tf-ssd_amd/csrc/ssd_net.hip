@@ -307,6 +307,10 @@ static ConvParams layer_conv_params(const ssd_net& net, const Layer& l, int B, c
     p.w = l.packed;
     p.w3 = conv_split_planes(l.packed, l.kh * l.kw * l.Cin, l.Cout);
     p.bf16 = net.precision;
+    if (l.wh) {                                        // the two-plane fp16 tiles' weights and the way back from both scales
+        p.wh = reinterpret_cast<const short*>(l.wh);
+        p.acc_scale = ldexpf(1.f, -(8 + l.wh_k));
+    }
     if (l.in >= 0 && net.tensors[l.in].planes) {       // the LDS-DMA tiles read the input's bf16 planes
         const Tensor& ti = net.tensors[l.in];
         p.xp = ti.planes; p.xp_plane = ti.plane_stride; p.xp_np = ti.planes_np;
@@ -364,7 +368,7 @@ static FusedBlockParams fused_shape(const ssd_net& net, const Layer& f, int B) {
     }
     if (f.e_out >= 0 && net.tensors[f.e_out].planes_live) {
         const Tensor& te = net.tensors[f.e_out];
-        p.e_planes = te.planes; p.e_plane = te.plane_stride; p.planes_np = te.planes_np;
+        p.e_planes = te.planes; p.e_plane = te.plane_stride; p.e_planes_np = te.planes_np;
     }
     if (f.route == RT_IMAGE || f.route == RT_IMAGE_SPLIT)     // plane-only outputs: no fp32 store (the pointers stay: they take part in the shape checks)
         p.planes_only = (p.y_planes && net.tensors[f.out].plane_only ? 1 : 0) | (p.e_planes && net.tensors[f.e_out].plane_only ? 2 : 0);
@@ -571,6 +575,27 @@ static std::vector<char> plane_only_candidates(const ssd_net& net, F reads_plane
     return ok;
 }
 
+// May tensor t live as the two-plane fp16 split (Tensor::planes_np 2, ssd_bf16x3.h)?  Its values must lie in [0, 6] by
+// construction: an fp32 net, and EVERY layer that can write it -- whatever the routes -- ends with ReLU6 over the whole
+// tensor: a conv with SSD_ACT_RELU6 and no residual, or a whole-block layer's expanded map (the expand conv's output).
+// In MobileNetV2-SSD: block 13's expanded map and Conv_1's output; nothing in VGG16 (ReLU / linear tensors).
+static bool tensor_relu6_bounded(const ssd_net& net, int t) {
+    if (net.precision != 0 || t < 1) return false;
+    bool any = false;
+    for (const Layer& l : net.layers) {
+        if (l.kind == LK_FUSED && l.e_out == t) {
+            const Layer& le = net.layers[l.f_expand];
+            if (le.act != SSD_ACT_RELU6 || le.res >= 0) return false;
+            any = true;
+            continue;
+        }
+        if (l.out != t) continue;
+        if (l.kind != LK_CONV || l.act != SSD_ACT_RELU6 || l.res >= 0 || l.head_kind != 0) return false;
+        any = true;
+    }
+    return any;
+}
+
 static int dev_alloc(ssd_net& net, size_t floats, float** out) {
     *out = nullptr;
     if (floats == 0) return SSD_OK;
@@ -653,9 +678,13 @@ static int autotune(ssd_net& net, int B, hipStream_t st) {
     int rc = SSD_OK;
     const bool dbg_sync = getenv("SSD_HIP_DEBUG_SYNC") != nullptr;   // name the launch a GPU fault belongs to
     const bool dbg_tune = getenv("SSD_HIP_DEBUG_TUNE") != nullptr;
-    // the per-layer race keeps the best of BOTH families -- fam 0: tiles that read the fp32 activation, fam 1: LDS-DMA tiles
-    // over its planes -- because which of the two a layer takes is decided per TENSOR below
-    struct Best { float ms[2] = {1e30f, 1e30f}; int cfg[2] = {-1, -1}; int split[2] = {1, 1}; bool timed = false; };
+    // the per-layer race keeps the best of EACH family -- fam 0: tiles that read the fp32 activation, fam 1: LDS-DMA tiles
+    // over its three bf16 planes ("dma3_*" / "dmab_*"), fam 2: LDS-DMA tiles over its fp16 pair ("dmah_*", layers with fp16
+    // weight planes only) -- because which of them a layer takes is decided per TENSOR below
+    struct Best {
+        float ms[3] = {1e30f, 1e30f, 1e30f}; int cfg[3] = {-1, -1, -1}; int split[3] = {1, 1, 1}; bool timed = false;
+        float ms_k64 = 1e30f, ms_k32 = 1e30f;        // (SSD_HIP_DEBUG_TUNE: fam 2's best with two / one k-step per barrier)
+    };
     std::vector<Best> bests(net.layers.size());
     constexpr int kReps = 4;
     for (size_t li = 0; li < net.layers.size(); ++li) {
@@ -668,11 +697,13 @@ static int autotune(ssd_net& net, int B, hipStream_t st) {
         float* out = l.out >= 0 ? net.tensors[l.out].dev : nullptr;
         const float* res = l.res >= 0 ? net.tensors[l.res].dev : nullptr;
         for (int c = 0; c < conv_num_configs() && !rc; ++c) {
-            const int fam = conv_config_is_dma(c) ? 1 : 0;
+            const int fam = conv_config_is_dmah(c) ? 2 : conv_config_is_dma(c) ? 1 : 0;
+            if (fam == 2 && (!net.conv_f16x2 || !l.wh)) continue;
             for (int si = 0; si < kNumSplits && !rc; ++si) {
                 const int split = kSplits[si];
                 l.split_k = split;
                 ConvParams p = layer_conv_params(net, l, B, in, out, res, d, pr);
+                if (fam == 2) p.xp_np = 2;       // (timed on whatever the planes hold: the matrix unit's time does not depend on the data)
                 if (!conv_config_valid(c, p) || !conv_config_allowed(c, net.precision)) break;
                 const bool direct = (c == conv_num_configs() - 1);
                 if (direct && (bb.cfg[0] >= 0 || bb.cfg[1] >= 0 || split > 1)) break;     // direct only as a last resort
@@ -702,6 +733,10 @@ static int autotune(ssd_net& net, int B, hipStream_t st) {
                 }
                 if (rc) break;
                 if (ms < bb.ms[fam]) { bb.ms[fam] = ms; bb.cfg[fam] = c; bb.split[fam] = split; }
+                if (fam == 2) {
+                    float& m2 = strstr(conv_config_name(c), "_ks2") ? bb.ms_k64 : bb.ms_k32;
+                    m2 = ms < m2 ? ms : m2;
+                }
             }
         }
         if (rc) break;
@@ -714,9 +749,13 @@ static int autotune(ssd_net& net, int B, hipStream_t st) {
         l.cfg = bb.cfg[f0];
         l.split_k = bb.split[f0];
         if (dbg_tune)
-            fprintf(stderr, "[ssd] tune %s: %s/s%d %.4f ms | %s/s%d %.4f ms\n", l.name.c_str(), bb.cfg[0] >= 0 ? conv_config_name(bb.cfg[0]) : "-",
-                    bb.split[0], bb.cfg[0] >= 0 ? bb.ms[0] / kReps : 0.f, bb.cfg[1] >= 0 ? conv_config_name(bb.cfg[1]) : "-", bb.split[1],
-                    bb.cfg[1] >= 0 ? bb.ms[1] / kReps : 0.f);
+            fprintf(stderr, "[ssd] tune %s: %s/s%d %.4f ms | %s/s%d %.4f ms | %s/s%d %.4f ms\n", l.name.c_str(),
+                    bb.cfg[0] >= 0 ? conv_config_name(bb.cfg[0]) : "-", bb.split[0], bb.cfg[0] >= 0 ? bb.ms[0] / kReps : 0.f,
+                    bb.cfg[1] >= 0 ? conv_config_name(bb.cfg[1]) : "-", bb.split[1], bb.cfg[1] >= 0 ? bb.ms[1] / kReps : 0.f,
+                    bb.cfg[2] >= 0 ? conv_config_name(bb.cfg[2]) : "-", bb.split[2], bb.cfg[2] >= 0 ? bb.ms[2] / kReps : 0.f);
+        if (dbg_tune && bb.cfg[2] >= 0)
+            fprintf(stderr, "[ssd] tune %s: dmah best with one k-step per barrier %.4f ms, with two %.4f ms\n", l.name.c_str(),
+                    bb.ms_k32 / kReps, bb.ms_k64 < 1e29f ? bb.ms_k64 / kReps : 0.f);
     }
     if (rc) return rc;
     // The family is a property of the TENSOR: LDS-DMA readers make its producer store the bf16 planes (2 * planes_np bytes per
@@ -735,36 +774,51 @@ static int autotune(ssd_net& net, int B, hipStream_t st) {
         const Tensor& tt = net.tensors[t];
         std::vector<size_t> flip;
         bool planes_anyway = false;
-        double sum0 = 0, sum1 = 0;
+        // the fp16 pair (fam 2) is open to the tensor only when every reader of its planes can take it: all the timed ones
+        // have a "dmah_*" best, and no other conv layer reads the planes through another family
+        bool pair_ok = net.conv_f16x2;
+        double sum0 = 0, sum1 = 0, sum2 = 0;
         for (size_t li = 0; li < net.layers.size(); ++li) {
             const Layer& l = net.layers[li];
             if (l.kind != LK_CONV || l.in != (int)t) continue;
             const Best& bb = bests[li];
-            if (!bb.timed) { if (layer_runs(l) && conv_config_is_dma(l.cfg)) planes_anyway = true; continue; }
+            if (!bb.timed) {
+                if (layer_runs(l) && conv_config_is_dma(l.cfg)) planes_anyway = true;
+                if (conv_config_is_dma(l.cfg) && !conv_config_is_dmah(l.cfg)) pair_ok = false;
+                continue;
+            }
             if (bb.cfg[1] < 0) continue;                 // no LDS-DMA tile takes it: stays where it is
-            if (bb.cfg[0] < 0) { planes_anyway = true; continue; }      // ... only LDS-DMA tiles do: already there
+            if (bb.cfg[0] < 0) { planes_anyway = true; pair_ok = false; continue; }      // ... only LDS-DMA tiles do: already there (three planes)
             if (!layer_runs(l)) {       // fused away under these routes: reads nothing; on its own, with the full plane store charged
                 if (bb.ms[1] + kReps * ((double)B * tt.per_image * 2.0 * tt.planes_np / 3.0e12 * 1e3) < bb.ms[0]) {
                     net.layers[li].cfg = bb.cfg[1];
                     net.layers[li].split_k = bb.split[1];
+                    pair_ok = false;
                 }
                 continue;
             }
             flip.push_back(li);
             sum0 += bb.ms[0];
             sum1 += bb.ms[1];
+            sum2 += bb.ms[2];
+            if (bb.cfg[2] < 0) pair_ok = false;
         }
         if (flip.empty()) continue;
         for (size_t li : flip) { net.layers[li].cfg = bests[li].cfg[1]; net.layers[li].split_k = bests[li].split[1]; }
         const bool only = plane_only_candidates(net, [&](int i) { return conv_config_is_dma(net.layers[i].cfg); })[t];
-        const double bytes = only ? 2.0 * tt.planes_np - 4.0 : planes_anyway ? 0.0 : 2.0 * tt.planes_np;
-        const double store_ms = kReps * ((double)B * tt.per_image * bytes / 3.0e12 * 1e3);
-        const bool take = sum1 + store_ms < sum0;
-        if (!take)
-            for (size_t li : flip) { net.layers[li].cfg = bests[li].cfg[0]; net.layers[li].split_k = bests[li].split[0]; }
+        // what the producer's store changes by, per element: np planes of 2 bytes more, 4 bytes less where the fp32 copy goes
+        auto store_ms_of = [&](int np) {
+            const double bytes = only ? 2.0 * np - 4.0 : planes_anyway ? 0.0 : 2.0 * np;
+            return kReps * ((double)B * tt.per_image * bytes / 3.0e12 * 1e3);
+        };
+        const double store_ms = store_ms_of(tt.planes_np), store2_ms = store_ms_of(2);
+        int take = sum1 + store_ms < sum0 ? 1 : 0;
+        if (pair_ok && sum2 + store2_ms < (take ? sum1 + store_ms : sum0)) take = 2;
+        for (size_t li : flip) { net.layers[li].cfg = bests[li].cfg[take]; net.layers[li].split_k = bests[li].split[take]; }
         if (dbg_tune)
-            fprintf(stderr, "[ssd] tune tensor %s: fp32 readers %.4f ms, plane readers %.4f + store %+.4f ms (%s) -> %s\n", tt.name.c_str(),
-                    sum0 / kReps, sum1 / kReps, store_ms / kReps, only ? "plane-only" : "both copies", take ? "planes" : "fp32");
+            fprintf(stderr, "[ssd] tune tensor %s: fp32 readers %.4f ms, plane readers %.4f + store %+.4f ms, fp16-pair readers %.4f + store %+.4f ms%s (%s) -> %s\n",
+                    tt.name.c_str(), sum0 / kReps, sum1 / kReps, store_ms / kReps, sum2 / kReps, store2_ms / kReps, pair_ok ? "" : " [not open]",
+                    only ? "plane-only" : "both copies", take == 2 ? "fp16 pair" : take ? "planes" : "fp32");
     }
     for (size_t i = 0; i < net.layers.size(); ++i) net.layers[i].img_choice = img_saved[i];
     resolve_routes(net);
@@ -987,6 +1041,26 @@ static int finalize_pack_conv(ssd_net* net, Layer& l, hipStream_t st) {
     }
     if (!rc) rc = launch_pack_split(l.packed, K, l.Cout, st);
     if (rc) return rc;
+    // fp16 planes of 2^k w for the two-plane fp16 tiles, where the layer's input is ReLU6-bounded: one k per layer from
+    // max |w| (read back once); a non-finite weight leaves the layer without them, i.e. on the other families
+    l.wh = nullptr;
+    l.wh_k = 0;
+    if (net->conv_dma && l.in >= 0 && l.Cin % 32 == 0 && tensor_relu6_bounded(*net, l.in)) {
+        ScopedDev bits_dev;
+        unsigned bits = 0;
+        SSD_HIP(hipMalloc((void**)&bits_dev.p, sizeof(unsigned)));
+        SSD_HIP(hipMemsetAsync(bits_dev.p, 0, sizeof(unsigned), st));
+        rc = launch_absmax_bits(l.packed, K, l.Cout, reinterpret_cast<unsigned*>(bits_dev.p), st);
+        if (rc) return rc;
+        SSD_HIP(hipMemcpyAsync(&bits, bits_dev.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        SSD_HIP(hipStreamSynchronize(st));
+        if (bits < 0x7f800000u) {
+            l.wh_k = conv_f16x2_weight_exp(bits);
+            rc = dev_alloc(*net, (conv_f16x2_plane_shorts(K, l.Cout) + 1) / 2, &l.wh);
+            if (!rc) rc = launch_pack_f16x2(l.packed, K, l.Cout, l.wh_k, reinterpret_cast<short*>(l.wh), st);
+            if (rc) return rc;
+        }
+    }
     // Winograd form of the 3x3 stride-1 convs (heads, VGG16 backbone): the autotune decides
     if (l.kh == 3 && l.kw == 3 && l.stride == 1 && l.dil == 1 && l.Cin % 16 == 0 && l.res < 0 && net->use_wino) {
         const int np = conv_npad(l.Cout);
@@ -1116,13 +1190,13 @@ static int finalize_arena(ssd_net* net, int max_batch, hipStream_t st) {
     SSD_HIP(hipMemset(net->arena, poison ? 0xFF : 0, total * sizeof(float)));
     // bf16 planes of every activation a dense conv with Cin % 32 == 0 reads (the LDS-DMA tiles' operand, ssd_convdma.hip);
     // written only while a consumer's chosen configuration asks for them (planes_live)
-    for (auto& t : net->tensors) { t.planes = nullptr; t.planes_live = false; t.plane_only = false; t.planes_np = 0; t.plane_stride = 0; }
+    for (auto& t : net->tensors) { t.planes = nullptr; t.planes_live = false; t.plane_only = false; t.planes_np = t.planes_cap = 0; t.plane_stride = 0; }
     if (net->conv_dma)
         for (const auto& l : net->layers) {
             if (l.kind != LK_CONV || l.in < 0 || l.Cin % 32 != 0) continue;
             Tensor& t = net->tensors[l.in];
             if (t.planes) continue;
-            t.planes_np = net->precision ? 1 : 3;
+            t.planes_np = t.planes_cap = net->precision ? 1 : 3;
             t.plane_stride = (long)align_up(t.per_image * max_batch, 64);
             float* pl = nullptr;
             const int rcp = dev_alloc(*net, (size_t)t.planes_np * t.plane_stride / 2 + 64, &pl);
@@ -1149,12 +1223,19 @@ static int finalize_apply_preset(ssd_net* net, int max_batch, bool* image_preset
         int cfg = -1;
         for (int c = 0; c < conv_num_configs(); ++c)
             if (it->second.first == conv_config_name(c)) cfg = c;
+        SSD_UNSUPPORTED_IF(cfg >= 0 && conv_config_is_dmah(cfg) && net->precision != 0,
+                           "finalize: the table puts layer %s on %s: the two-plane fp16 tiles are admitted in fp32 nets (precision 0) only",
+                           l.name.c_str(), conv_config_name(cfg));
+        // a "dmah_*" line where the form may not run -- option conv_f16x2 0, an input that is not ReLU6-bounded, non-finite
+        // weights -- runs its "dma3_*" twin: the same tile, the same split-K
+        if (cfg >= 0 && conv_config_is_dmah(cfg) && (!net->conv_f16x2 || !l.wh)) cfg = conv_dmah_twin(cfg);
         if (cfg < 0 || !conv_config_allowed(cfg, net->precision)) { ++n_tuned; continue; }
         l.cfg = cfg;
         l.split_k = it->second.second;
         ConvParams p = layer_conv_params(*net, l, max_batch, net->tensors[l.in].dev,
                                          l.out >= 0 ? net->tensors[l.out].dev : nullptr, nullptr,
                                          net->arena, net->arena);
+        if (conv_config_is_dmah(cfg)) p.xp_np = 2;         // (which form the tensor's planes take is settled below: finalize_resolve_f16x2)
         const bool split_ok = l.split_k == 1 || conv_k_tiles(cfg, p) >= l.split_k;
         if (l.split_k < 1 || !split_ok || !conv_config_valid(cfg, p)) { l.cfg = -1; l.split_k = 1; ++n_tuned; continue; }
         ++n_preset;
@@ -1190,18 +1271,46 @@ static int finalize_free_unread_planes(ssd_net* net, hipStream_t st) {
     for (const auto& l : net->layers)
         if (l.kind == LK_CONV && l.in >= 0 && conv_config_is_dma(l.cfg)) read[l.in] = 1;
     SSD_HIP(hipStreamSynchronize(st));
-    net->plane_bytes = 0;
+    net->plane_bytes = net->wplane_bytes;
     for (size_t i = 0; i < net->tensors.size(); ++i) {
         Tensor& t = net->tensors[i];
         if (!t.planes) continue;
-        const size_t bytes = ((size_t)t.planes_np * t.plane_stride / 2 + 64) * sizeof(float);
+        const size_t bytes = ((size_t)t.planes_cap * t.plane_stride / 2 + 64) * sizeof(float);
         if (read[i]) { net->plane_bytes += bytes; continue; }
         float* pl = reinterpret_cast<float*>(t.planes);
         net->owned.erase(std::remove(net->owned.begin(), net->owned.end(), pl), net->owned.end());
         (void)hipFree(pl);
-        t.planes = nullptr; t.planes_np = 0; t.plane_stride = 0;
+        t.planes = nullptr; t.planes_np = t.planes_cap = 0; t.plane_stride = 0;
     }
     return SSD_OK;
+}
+
+// The two-plane fp16 form is a property of the TENSOR too: its planes are written once, in one form.  A tensor takes
+// planes_np 2 iff option conv_f16x2 is on and EVERY conv layer reading its planes (running or fused away: the routes may
+// change without a finalize) chose a "dmah_*" tile -- which only layers with fp16 weight planes, i.e. with a
+// ReLU6-bounded input, can.  Otherwise the tensor keeps the exact three-way split and a "dmah_*" reader runs its
+// "dma3_*" twin (same tile, same split-K).  fp16 weight planes no chosen tile reads are freed.
+static void finalize_resolve_f16x2(ssd_net* net) {
+    const int nt = (int)net->tensors.size();
+    std::vector<char> any(nt, 0), all(nt, 1);
+    for (const auto& l : net->layers) {
+        if (l.kind != LK_CONV || l.in < 0 || !conv_config_is_dma(l.cfg)) continue;
+        any[l.in] = 1;
+        if (!conv_config_is_dmah(l.cfg) || !l.wh || !net->conv_f16x2) all[l.in] = 0;
+    }
+    net->wplane_bytes = 0;
+    for (auto& l : net->layers) {
+        if (l.kind != LK_CONV) continue;
+        if (conv_config_is_dmah(l.cfg) && !(any[l.in] && all[l.in])) l.cfg = conv_dmah_twin(l.cfg);
+        if (conv_config_is_dmah(l.cfg)) {
+            net->tensors[l.in].planes_np = 2;
+            net->wplane_bytes += (conv_f16x2_plane_shorts(l.kh * l.kw * l.Cin, l.Cout) + 1) / 2 * sizeof(float);
+        } else if (l.wh) {
+            net->owned.erase(std::remove(net->owned.begin(), net->owned.end(), l.wh), net->owned.end());
+            (void)hipFree(l.wh);
+            l.wh = nullptr;
+        }
+    }
 }
 
 // Every split-K layer gets its own slab (layers on different streams may overlap); the side streams and the events.
@@ -1245,6 +1354,7 @@ int ssd_net_finalize(ssd_net* net, int max_batch) {
     for (auto& l : net->layers) {
         l.packed = l.scale = l.shift = nullptr;
         l.wino = nullptr;
+        l.wh = nullptr;
         l.splitk_part = nullptr;        // autotune runs on the shared slab; per-layer slabs are re-planned below
         if (l.kind == LK_CONV) rc = finalize_pack_conv(net, l, st);
         if (!rc && (l.kind == LK_CONV || l.kind == LK_DW)) rc = finalize_fold_bn(net, l, st);
@@ -1256,6 +1366,10 @@ int ssd_net_finalize(ssd_net* net, int max_batch) {
     bool image_preset_ok = true;
     if (!rc) rc = finalize_apply_preset(net, max_batch, &image_preset_ok);       // tile configurations: from the table ...
     if (!rc && net->n_autotuned) rc = autotune(*net, max_batch, st);             // ... or timed on the device
+    if (!rc) {
+        SSD_HIP(hipStreamSynchronize(st));
+        finalize_resolve_f16x2(net);
+    }
     if (!rc) rc = finalize_free_unread_planes(net, st);
     if (!rc) rc = finalize_streams(net, max_batch);
     if (rc) return rc;
@@ -1648,6 +1762,7 @@ static const OptionSpec kOptions[] = {
     // project MFMAs).  Blocks 1-6 on the row-band kernels are not touched by it
     {"image_v2", &ssd_net::image_v2, nullptr, 0, 1, 0},
     {"conv_dma", &ssd_net::conv_dma, nullptr, 0, 1, 1},         // LDS-DMA conv tiles over pre-split activation planes (default 1)
+    {"conv_f16x2", &ssd_net::conv_f16x2, nullptr, 0, 1, 1},     // two-plane fp16 tiles "dmah_*" on ReLU6-bounded inputs (default 1); 0: such a table line runs its "dma3_*" twin
     {"plane_only", &ssd_net::plane_only, nullptr, 0, 1, 0},     // no fp32 copy of an activation whose readers all take its planes (default 1)
     {"use_graph", &ssd_net::use_graph, nullptr, 0, 1, 0},
 };
@@ -1728,7 +1843,10 @@ long ssd_net_fetch_activation(ssd_net* net, const char* layer, float* host_out, 
         set_error("ssd_net_fetch_activation: buffer holds %zu floats, need %zu", cap, n);
         return SSD_E_INVALID;
     }
-    ScopedDev joined;          // a plane-only tensor: the planes joined back (h + m + l is exact), its fp32 slot is not written
+    // a plane-only tensor: the planes joined back, its fp32 slot is not written.  Three planes: h + m + l is exact.  Two
+    // (the fp16 pair of a ReLU6-bounded tensor): the value the conv tiles read, within 2^-22 |x| + 2^-33 of what an fp32
+    // store would have held (ssd_bf16x3.h)
+    ScopedDev joined;
     const float* src = t.dev;
     if (t.plane_only && n) {
         SSD_HIP(hipMalloc((void**)&joined.p, n * sizeof(float)));
@@ -1745,7 +1863,7 @@ long ssd_net_fetch_activation(ssd_net* net, const char* layer, float* host_out, 
 }
 
 // ... and its bf16 planes (the LDS-DMA conv tiles' operand) joined back to fp32: 0 when no running consumer asked for
-// them in the last forward; *planes_out = 3 (exact split) or 1 (bf16 rounding)
+// them in the last forward; *planes_out = 3 (exact split), 2 (the fp16 pair, within 2^-22 |x| + 2^-33) or 1 (bf16 rounding)
 long ssd_net_fetch_planes(ssd_net* net, const char* layer, float* host_out, size_t cap, int* planes_out) {
     if (!net || !layer) return SSD_E_INVALID;
     auto it = net->tensor_index.find(layer);

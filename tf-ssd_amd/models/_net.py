@@ -14,7 +14,7 @@ import ssd_hip as _h
 # options that change which kernel configurations finalize may choose (the memo is per option set)
 _TABLE_OPTIONS = ("use_wino", "image_split", "conv_dma")
 # options that make the native net drop `finalized` (ssd_net_set_option): the Python handle must re-finalize too
-_REFINALIZE_OPTIONS = ("precision", "image_split", "use_wino", "conv_dma")
+_REFINALIZE_OPTIONS = ("precision", "image_split", "use_wino", "conv_dma", "conv_f16x2")
 _STALE_WARNED = set()
 
 
@@ -422,8 +422,9 @@ class SSDModel(object):
 
     def fetch_planes(self, name):
         """The bf16 planes of a named activation of the last forward (what the LDS-DMA conv tiles of its consumers read),
-        joined back to fp32: ``(array, planes)`` with planes 3 (exact split) or 1 (bf16 rounding); ``(None, planes)`` when
-        no running layer asked for them."""
+        joined back to fp32: ``(array, planes)`` with planes 3 (exact split), 2 (the fp16 pair of a ReLU6-bounded tensor
+        whose readers run ``dmah_*`` tiles: within 2^-22 |x| + 2^-33 of the fp32 value) or 1 (bf16 rounding); ``(None, planes)``
+        when no running layer asked for them.  ``fetch_activation`` of a plane-only tensor returns the same joined value."""
         lib = _h.lib()
         npl = ctypes.c_int(0)
         n = lib.ssd_net_fetch_planes(self._net, name.encode(), None, 0, ctypes.byref(npl))

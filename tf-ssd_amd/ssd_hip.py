@@ -227,6 +227,10 @@ _SIGNATURES = {
     "ssd_join_planes": (ctypes.c_int, [vp, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_long, vp, vp]),
     "ssd_conv2d_planes": (ctypes.c_int, [ctypes.POINTER(ConvDesc), vp, ctypes.c_int, ctypes.c_long, vp, vp, vp, vp, vp,
                                          ctypes.c_long, ctypes.c_long, vp, ctypes.c_long, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "ssd_conv_f16x2_weight_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "ssd_conv_pack_weights_f16x2": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp, c_int_p, vp]),
+    "ssd_conv2d_planes_f16x2": (ctypes.c_int, [ctypes.POINTER(ConvDesc), vp, ctypes.c_long, vp, vp, ctypes.c_int, vp, vp, vp, vp,
+                                               ctypes.c_long, ctypes.c_long, vp, ctypes.c_long, ctypes.c_int, ctypes.c_int, vp, vp]),
     "ssd_conv_wino_weight_floats": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "ssd_conv_wino_pack_weights": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp]),
     "ssd_conv_wino_num_configs": (ctypes.c_int, []),

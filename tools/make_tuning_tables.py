@@ -11,6 +11,12 @@ provenance header.  Copy the files into tf-ssd_amd/tables/ and commit them: from
 nothing for these shapes and every process runs the same kernels (bit-identical results).
 
     python tools/make_tuning_tables.py --adopt DIR     # CPU: copy SSD_HIP_TUNE_CACHE-style files from DIR
+
+`--retime LAYER ...` re-measures only the named conv layers: every other line of the shipped table (the `__launch` line
+included) is handed to finalize as it stands, so only those layers are raced -- for a change that adds candidates to a
+few layers and leaves every other kernel as it was.  `--restamp` (CPU) writes the current build id into the shipped
+tables WITHOUT measuring; re-measured tables are copied over them afterwards.  Only for a change that leaves every kernel
+the remaining tables can name as it was.
 """
 import argparse
 import collections
@@ -69,17 +75,24 @@ def generate(args):
             hp["feature_map_shapes"] = [32, 16, 8, 4, 2, 1]
         w = helpers.synthetic_weights(bb, hp)
         tabs = []
+        key = tuning.table_key(bb, S, hp["total_labels"], hp["aspect_ratios"], B) + ("" if prec == "fp32" else "_" + prec)
+        preset = ""                            # nothing preset: time everything
+        if args.retime:
+            shipped = tuning.load_shipped(key)
+            if shipped is None:
+                print("%-40s no shipped table to start from: skipped" % key, flush=True)
+                continue
+            preset = "".join(l + "\n" for l in tuning.body(shipped).splitlines() if l.split(" ")[0] not in args.retime)
         for r in range(args.repeats):
             m = SSDModel(bb, hp, max_batch=B, precision=prec)
             m.set_weights(w)
-            m.set_tuning("")                   # nothing preset: time everything
+            m.set_tuning(preset)
             m._ensure(B)
             tabs.append(m.get_tuning())
             del m
             torch.cuda.empty_cache()
         table = majority(tabs)
         agree = sum(t == tabs[0] for t in tabs)
-        key = tuning.table_key(bb, S, hp["total_labels"], hp["aspect_ratios"], B) + ("" if prec == "fp32" else "_" + prec)
         with open(os.path.join(args.out, key + ".tune"), "w") as f:
             f.write(tuning.with_header(table, key=key, build=build, device=dev, repeats=args.repeats,
                                        version=ssd_hip.lib().ssd_version().decode().replace(" ", "_")))
@@ -105,11 +118,31 @@ def adopt(args):
     print("adopted %d tables into %s" % (n, tuning.SHIPPED_DIR))
 
 
+def restamp(args):
+    import bench
+    import tuning
+    build = bench.build_id_from_sources()
+    n = 0
+    for f in sorted(os.listdir(tuning.SHIPPED_DIR)):
+        if not f.endswith(".tune"):
+            continue
+        p = os.path.join(tuning.SHIPPED_DIR, f)
+        text = open(p).read()
+        hdr = tuning.header(text)
+        hdr["build"] = build
+        with open(p, "w") as g:
+            g.write(tuning.with_header(text, **hdr))
+        n += 1
+    print("restamped %d tables to build %s" % (n, build))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "gpurun_out", "tables"))
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--shapes", nargs="*", help="backbone:size:batch[:bf16] ...")
     ap.add_argument("--adopt")
+    ap.add_argument("--retime", nargs="*", help="conv layer names: race only these, keep the shipped table's other lines")
+    ap.add_argument("--restamp", action="store_true")
     a = ap.parse_args()
-    adopt(a) if a.adopt else generate(a)
+    restamp(a) if a.restamp else adopt(a) if a.adopt else generate(a)
