@@ -1077,7 +1077,10 @@ int ssd_conv2d_planes_f16x2(const ssd_conv_desc* d, const void* in_planes_dev, l
 /* Winograd F(2x2,3x3) variant of the same op for 3x3 stride-1 dilation-1 convs with Cin % 16 == 0
  * (the SSD head convs, models/header.py:60-61, and VGG16's 3x3 backbone, models/ssd_vgg16.py:52-72):
  * 2.25x fewer multiplications on the same fp32 MFMA, fused input / output transforms.  Weights are
- * transformed once ([16][Npad][Cin] floats).  The graph runner's autotune picks it per layer. */
+ * transformed once ([16][Npad][Cin] floats).  The graph runner's autotune picks it per layer.
+ * Any other convolution answers SSD_E_UNSUPPORTED with "cannot run" in ssd_last_error(), as every tile family of
+ * ssd_conv2d_ex / ssd_conv2d_planes does for a shape outside its constraints (the refusal contract on non-square
+ * geometry: tests/conv_geometry_cases.py REFUSALS). */
 size_t ssd_conv_wino_weight_floats(int Cin, int Cout);
 int ssd_conv_wino_pack_weights(const float* hwio_dev, int Cin, int Cout, float* wino_w_dev, void* stream);
 int ssd_conv_wino_num_configs(void);

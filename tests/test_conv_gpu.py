@@ -61,7 +61,9 @@ def guarded(a, pad=4096):
 
 
 def run_conv(x, w, scale=None, shift=None, res=None, stride=1, dil=1, pads=(0, 0, 0, 0), act=0, cfg=-1,
-             split_k=1, out_strides=None):
+             split_k=1, out_strides=None, canvas=None):
+    """``out_strides`` = (batch stride, pixel stride, offset, total floats): the destination lies inside a flat buffer,
+    NaN-filled here or handed in as ``canvas`` (a float32 device tensor of ``total`` floats) -- which is what comes back."""
     import ssd_hip as h
     lib = h.lib()
     B, H, W, Cin = x.shape
@@ -86,7 +88,8 @@ def run_conv(x, w, scale=None, shift=None, res=None, stride=1, dil=1, pads=(0, 0
         optr = h.ptr(out)
     else:
         bs, ps, off, total = out_strides
-        out = torch.full((total,), float("nan"), dtype=torch.float32, device=xd.device)
+        out = canvas if canvas is not None else torch.full((total,), float("nan"), dtype=torch.float32, device=xd.device)
+        assert out.numel() == total
         optr = h.vp(out.data_ptr() + 4 * off)
     ws = torch.empty(max(1, split_k * B * Ho * Wo * Cout), dtype=torch.float32, device=xd.device) if split_k > 1 else None
     rc = lib.ssd_conv2d_ex(ctypes.byref(d), h.ptr(xd), h.ptr(packed), h.ptr(sd), h.ptr(hd), h.ptr(rd), optr,
@@ -294,6 +297,50 @@ def test_dwconv3x3(H, C, stride):
     h.check(h.lib().ssd_dwconv3x3(h.ptr(xd), B, H, H, C, stride, pads[0], pads[2], pads[1], pads[3], h.ptr(wd),
                                   h.ptr(sd), h.ptr(hd), 2, h.ptr(out), h.stream()), "dw")
     _close(_np(out), ref, 1e-5)
+
+
+@pytest.mark.parametrize("H,W,C,stride,pads", [(7, 12, 36, 1, (1, 1, 1, 1)), (13, 6, 8, 2, (1, 1, 0, 1)), (2, 9, 64, 2, (0, 1, 1, 1))])
+def test_dwconv3x3_non_square(H, W, C, stride, pads):
+    """H != W and pads that differ between the axes (pads = (top, bottom, left, right)): a kernel that decodes the pixel
+    with the wrong extent, addresses rows with H, or swaps pad_t and pad_l cannot pass.  Reference: float64."""
+    import ssd_hip as h
+    rng = np.random.default_rng(1000 * H + W)
+    B = 3
+    x = rng.standard_normal((B, H, W, C)).astype(np.float32)
+    w = rng.standard_normal((3, 3, C, 1)).astype(np.float32)
+    scale = rng.uniform(0.5, 1.5, C).astype(np.float32)
+    shift = rng.uniform(-0.5, 0.5, C).astype(np.float32)
+    xp = np.pad(x.astype(np.float64), ((0, 0), (pads[0], pads[1]), (pads[2], pads[3]), (0, 0)))
+    Ho, Wo = (xp.shape[1] - 3) // stride + 1, (xp.shape[2] - 3) // stride + 1
+    assert Ho != Wo
+    ref = np.zeros((B, Ho, Wo, C))
+    for ky in range(3):
+        for kx in range(3):
+            ref += xp[:, ky:ky + (Ho - 1) * stride + 1:stride, kx:kx + (Wo - 1) * stride + 1:stride, :] * w[ky, kx, :, 0].astype(np.float64)
+    ref = np.minimum(np.maximum(ref * scale + shift, 0.0), 6.0)
+    xd, wd, sd, hd = guarded(x), guarded(w[..., 0]), guarded(scale), guarded(shift)
+    out = torch.full(ref.shape, float("nan"), dtype=torch.float32, device=xd.device)
+    h.check(h.lib().ssd_dwconv3x3(h.ptr(xd), B, H, W, C, stride, pads[0], pads[2], pads[1], pads[3], h.ptr(wd),
+                                  h.ptr(sd), h.ptr(hd), 2, h.ptr(out), h.stream()), "dw")
+    _close(_np(out), ref, 1e-5)
+
+
+@pytest.mark.parametrize("H,W,C,k,stride", [(7, 12, 36, 3, 1), (13, 6, 8, 2, 2), (2, 9, 64, 3, 2)])
+def test_maxpool_non_square(H, W, C, k, stride):
+    """H != W; the SAME pads then differ between the axes ((13, 6) at 2x2 stride 2: (0, 1) on y, none on x;
+    (2, 9) at 3x3 stride 2: (0, 1) on y, (1, 1) on x)."""
+    import ssd_hip as h
+    rng = np.random.default_rng(1000 * H + W)
+    B = 3
+    x = rng.standard_normal((B, H, W, C)).astype(np.float32)
+    ref = no.max_pool(x, k, stride)
+    pt, pb = same(H, k, stride)
+    pl, pr = same(W, k, stride)
+    assert ref.shape[1] != ref.shape[2] and (stride == 1 or (pt, pb) != (pl, pr))
+    xd = guarded(x)
+    out = torch.full(ref.shape, float("nan"), dtype=torch.float32, device=xd.device)
+    h.check(h.lib().ssd_maxpool2d(h.ptr(xd), B, H, W, C, k, stride, pt, pl, pb, pr, h.ptr(out), h.stream()), "pool")
+    np.testing.assert_array_equal(_np(out), ref)
 
 
 @pytest.mark.parametrize("H,C,k,stride", [(300, 64, 2, 2), (75, 256, 2, 2), (19, 512, 3, 1), (5, 8, 3, 2)])

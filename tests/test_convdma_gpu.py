@@ -53,7 +53,8 @@ def join_planes(p0, n, channels, np_, stride):
 
 
 def run_conv_planes(x, w, np_, cfg, scale=None, shift=None, res=None, stride=1, dil=1, pads=(0, 0, 0, 0), act=0, split_k=1,
-                    want_planes=True):
+                    want_planes=True, out_strides=None, canvas=None):
+    """``out_strides`` / ``canvas``: a strided destination inside a flat buffer, as in ``run_conv``."""
     import ssd_hip as h
     lib = h.lib()
     B, H, W, Cin = x.shape
@@ -70,7 +71,15 @@ def run_conv_planes(x, w, np_, cfg, scale=None, shift=None, res=None, stride=1, 
     sd = guarded(scale) if scale is not None else None
     hd = guarded(shift) if shift is not None else None
     rd = guarded(res) if res is not None else None
-    out = torch.full((B, Ho, Wo, Cout), float("nan"), dtype=torch.float32, device=wd.device)
+    bs = ps = 0
+    if out_strides is None:
+        out = torch.full((B, Ho, Wo, Cout), float("nan"), dtype=torch.float32, device=wd.device)
+        optr = h.ptr(out)
+    else:
+        bs, ps, off, total = out_strides
+        out = canvas if canvas is not None else torch.full((total,), float("nan"), dtype=torch.float32, device=wd.device)
+        assert out.numel() == total
+        optr = h.vp(out.data_ptr() + 4 * off)
     n_out = B * Ho * Wo * Cout
     op = None
     ostride = 0
@@ -79,7 +88,7 @@ def run_conv_planes(x, w, np_, cfg, scale=None, shift=None, res=None, stride=1, 
         op = torch.full((np_ * ostride + 64,), 0x7fc0, dtype=torch.int16, device=wd.device)
     ws = torch.empty(max(1, split_k * n_out), dtype=torch.float32, device=wd.device) if split_k > 1 else None
     rc = lib.ssd_conv2d_planes(ctypes.byref(d), h.vp(p0), np_, pstride, h.ptr(packed), h.ptr(sd), h.ptr(hd), h.ptr(rd),
-                               h.ptr(out), 0, 0, h.ptr(op), ostride, cfg, split_k, h.ptr(ws), h.stream())
+                               optr, bs, ps, h.ptr(op), ostride, cfg, split_k, h.ptr(ws), h.stream())
     joined = None
     if rc == 0 and op is not None:
         joined = join_planes(op.data_ptr(), n_out, Cout, np_, ostride).reshape(B, Ho, Wo, Cout)

@@ -37,8 +37,9 @@ def pack_weights(w):
 
 
 def run_conv_h(x, w, cfg, scale=None, shift=None, res=None, stride=1, dil=1, pads=(0, 0, 0, 0), act=0, split_k=1, in_planes=2,
-               packed_w=None):
-    """``ssd_conv2d_planes_f16x2`` on the planes of x; returns (rc, out, joined plane output or None)."""
+               packed_w=None, want_planes=True, out_strides=None, canvas=None):
+    """``ssd_conv2d_planes_f16x2`` on the planes of x; returns (rc, out, joined plane output or None).  ``out_strides`` /
+    ``canvas``: a strided destination inside a flat buffer, as in ``run_conv``."""
     import ssd_hip as h
     lib = h.lib()
     B, H, W, Cin = x.shape
@@ -56,15 +57,23 @@ def run_conv_h(x, w, cfg, scale=None, shift=None, res=None, stride=1, dil=1, pad
     sd = guarded(scale) if scale is not None else None
     hd = guarded(shift) if shift is not None else None
     rd = guarded(res) if res is not None else None
-    out = torch.full((B, Ho, Wo, Cout), float("nan"), dtype=torch.float32, device=packed.device)
+    bs = ps = 0
+    if out_strides is None:
+        out = torch.full((B, Ho, Wo, Cout), float("nan"), dtype=torch.float32, device=packed.device)
+        optr = h.ptr(out)
+    else:
+        bs, ps, off, total = out_strides
+        out = canvas if canvas is not None else torch.full((total,), float("nan"), dtype=torch.float32, device=packed.device)
+        assert out.numel() == total
+        optr = h.vp(out.data_ptr() + 4 * off)
     n_out = B * Ho * Wo * Cout
     op, ostride = None, 0
-    if Cout % 32 == 0:
+    if want_planes and Cout % 32 == 0:
         ostride = (n_out + 63) // 64 * 64
         op = torch.full((2 * ostride + 64,), 0x7fc0, dtype=torch.int16, device=packed.device)
     ws = torch.empty(max(1, split_k * n_out), dtype=torch.float32, device=packed.device) if split_k > 1 else None
     rc = lib.ssd_conv2d_planes_f16x2(ctypes.byref(d), h.vp(p0), pstride, h.ptr(packed), h.vp(wpl.data_ptr()), k, h.ptr(sd), h.ptr(hd),
-                                     h.ptr(rd), h.ptr(out), 0, 0, h.ptr(op), ostride, cfg, split_k, h.ptr(ws), h.stream())
+                                     h.ptr(rd), optr, bs, ps, h.ptr(op), ostride, cfg, split_k, h.ptr(ws), h.stream())
     joined = None
     if rc == 0 and op is not None:
         joined = join_planes(op.data_ptr(), n_out, Cout, 2, ostride).reshape(B, Ho, Wo, Cout)

@@ -742,7 +742,9 @@ int ssd_conv2d_wino(const ssd_conv_desc* d, const float* in_dev, const float* wi
         p.split_k = split_k;
         p.partial = splitk_ws_dev;
     }
-    SSD_UNSUPPORTED_IF(!wino_applicable(p), "conv2d_wino: needs a 3x3 stride-1 dilation-1 conv with Cin %% 16 == 0");
+    // (worded like every other family's refusal: "cannot run" is what callers and tests look for in ssd_last_error())
+    SSD_UNSUPPORTED_IF(!wino_applicable(p), "conv2d_wino: the Winograd tiles cannot run Cin=%d k=%dx%d stride=%d dilation=%d (they need a 3x3 "
+                       "stride-1 dilation-1 conv with Cin %% 16 == 0 and no residual)", p.Cin, p.kh, p.kw, p.stride, p.dil);
     const int cfg = conv_num_mfma_configs() + (wino_config >= 0 ? wino_config : 0);
     return conv_launch(p, cfg, (hipStream_t)stream);
 }
