@@ -55,6 +55,27 @@ def test_pure_host_entry_points():
     assert not l.ssd_net_create(7, 300, 6, na, 21) and b"bad arguments" in l.ssd_last_error()
 
 
+def test_conv_config_ids_and_names_are_pinned():
+    """Tuning tables name conv tiles by name, the autotune walks and breaks ties in id order, and tests take the last id as
+    the direct kernel: the id -> name list is the recorded one, names are unique, and every family's prefix is one
+    contiguous id range, the families in the recorded order."""
+    import ssd_hip
+    l = ssd_hip.lib()
+    names = [l.ssd_conv_config_name(c).decode() for c in range(l.ssd_conv_num_configs())]
+    golden = open(os.path.join(REPO, "tests", "golden", "conv_config_names.txt")).read().split()
+    assert names == golden
+    assert len(set(names)) == len(names)
+    order = ["mfma_", "wino_", "skinny_", "mfma3_", "bf16_", "dma3_", "dmab_", "dmah_", "direct_valu"]
+    seen = []          # the prefix of each run of ids
+    for n in names:
+        prefix = [p for p in order if n.startswith(p)]
+        assert len(prefix) == 1, n
+        if not seen or seen[-1] != prefix[0]:
+            seen.append(prefix[0])
+    assert seen == order and names[-1] == "direct_valu"
+    assert l.ssd_conv_config_name(-1) == b"?" and l.ssd_conv_config_name(len(names)) == b"?"
+
+
 def test_no_cpu_fallback():
     """Without a GPU every compute entry point of the Python surface must raise."""
     import torch

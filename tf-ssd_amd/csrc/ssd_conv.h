@@ -51,10 +51,6 @@ struct ConvParams {
     const short* wh;
     float acc_scale;
 };
-// may a net of this precision (0 fp32, 1 bf16) choose config `cfg`?  fp32 nets never take the bf16 (one-product) tiles;
-// bf16 nets take them instead of the split-bf16 / Winograd tiles (the fp32-MFMA and skinny tiles serve the small tail layers
-// in both modes: more accurate than asked for)
-bool conv_config_allowed(int cfg, int precision);
 // ConvParams::vec_store of these destinations: float4 stores into `out` are aligned
 inline int conv_vec_store(const ConvParams& p) {
     return (((uintptr_t)p.out & 15) == 0) && (p.out_pixel_stride % 4 == 0) && (p.out_batch_stride % 4 == 0);
@@ -150,67 +146,73 @@ inline int round_up(int v, int a) { return (v + a - 1) / a * a; }
 inline int conv_kpad(int K) { return round_up(K, 32); }
 inline int conv_npad(int Cout) { return round_up(Cout, 16); }
 
+// ---- dense-conv tile families ----------------------------------------------------------------------------------------
+// A config id names one tile of one FAMILY.  Each family lives in its own file and exports one `extern const ConvFamily`;
+// ssd_conv.hip lists them in kFamilies[] (in ConvFamilyId order = config id order: a family's ids are one contiguous range,
+// direct_valu is the last id) and every conv_* function below resolves `cfg` to (family, index in the family) through that
+// list.  Adding a family = define its ConvFamily in its file + one ConvFamilyId + one kFamilies[] line.
+enum ConvFamilyId { CF_NONE = -1, CF_MFMA, CF_WINO, CF_SKINNY, CF_MFMA3, CF_BF16, CF_DMA3, CF_DMAB, CF_DMAH, CF_DIRECT };
+// ConvFamily::traits
+enum : unsigned {
+    // what the tiles read (conv_config_reads): the fp32 activation `in`, or the planes `xp` -- bf16 planes (xp_np = 3 / 1)
+    // or the fp16 pair (xp_np = 2, weights `wh`)
+    CONV_READS_FP32 = 0, CONV_READS_PLANES = 1, CONV_READS_F16X2 = 2, CONV_READS_MASK = 3,
+    // which nets may choose the family (conv_config_allowed): fp32 nets never take the bf16 (one-product) tiles; bf16 nets take
+    // them instead of the split-bf16 / Winograd tiles (the fp32-MFMA and skinny tiles serve the small tail layers in both
+    // modes: more accurate than asked for)
+    CONV_NET_FP32 = 4, CONV_NET_BF16 = 8,
+    CONV_WRITES_PLANES = 16,     // the epilogue (conv_epilogue / splitk_reduce_kernel) honours ConvParams::op
+    CONV_SPLITK_REDUCE = 32,     // split_k > 1: the tiles leave partial sums, launch_splitk_reduce follows
+};
+struct ConvFamily {
+    ConvFamilyId id;
+    int (*count)();
+    const char* (*name)(int i);
+    bool (*valid)(int i, const ConvParams& p);        // alignment / shape constraints
+    long (*grid_blocks)(int i, const ConvParams& p);  // blocks of the un-split grid
+    int (*k_tiles)(int i, const ConvParams& p);       // K tiles per block without split
+    int (*launch)(const ConvParams& p, int i, hipStream_t st);   // the kernel only, of a config conv_launch found valid
+    unsigned traits;
+};
+// (host data: a definition sits under #ifndef __HIP_DEVICE_COMPILE__, or the device pass would emit the constant with its
+// pointers to host functions)
+extern const ConvFamily kConvMfma, kConvDirect;              // ssd_conv.hip
+extern const ConvFamily kConvWino;                           // ssd_wino.hip: Winograd F(2x2, 3x3)
+extern const ConvFamily kConvSkinny;                         // ssd_skinny.hip: small-M / long-K convs, the K split inside the workgroup
+extern const ConvFamily kConvMfma3, kConvBf16;               // ssd_conv3.hip: split-bf16 tiles and their bf16 (one-product) forms
+extern const ConvFamily kConvDma3, kConvDmab, kConvDmah;     // ssd_convdma.hip: LDS-DMA tiles over activation planes (np = 3, 1, 2)
+
 int conv_num_configs();
 const char* conv_config_name(int cfg);
-// true if config `cfg` can run these parameters (alignment / shape constraints).
+ConvFamilyId conv_config_family(int cfg);                  // (CF_NONE: no config id)
+// true if config `cfg` can run these parameters
 bool conv_config_valid(int cfg, const ConvParams& p);
+bool conv_config_allowed(int cfg, int precision);          // may a net of this precision (0 fp32, 1 bf16) choose it?
+int conv_config_reads(int cfg);                            // CONV_READS_*
+bool conv_config_is_dma(int cfg);                          // reads planes: any of the three LDS-DMA families
+bool conv_config_is_dmah(int cfg);                         // ... the fp16 pair
+int conv_dmah_twin(int cfg);                               // the "dma3_*" config of a "dmah_*" config's tile
+bool conv_config_writes_planes(int cfg, const ConvParams& p);
 int conv_pick_config(const ConvParams& p);                 // heuristic
-long conv_grid_blocks(int cfg, const ConvParams& p);       // blocks of the un-split grid
-int conv_k_tiles(int cfg, const ConvParams& p);            // K tiles per block without split
+long conv_grid_blocks(int cfg, const ConvParams& p);
+int conv_k_tiles(int cfg, const ConvParams& p);
 int conv_launch(const ConvParams& p, int cfg, hipStream_t st);
-size_t conv_splitk_workspace_floats(const ConvParams& p, int cfg);
 
 int fill_conv_params(const ssd_conv_desc* d, ConvParams* p);   // geometry + validation
 int launch_splitk_reduce(const ConvParams& p, hipStream_t st);
+// 1x1 stride-1 unpadded: the implicit GEMM is a plain one (the GEMM1X1 kernel forms)
+inline bool conv_is_gemm1x1(const ConvParams& p) {
+    return p.kh == 1 && p.kw == 1 && p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 && p.Ho == p.H && p.Wo == p.W;
+}
 
-// Winograd F(2x2, 3x3) path (csrc/ssd_wino.hip): config ids [conv_num_mfma_configs(), +wino_num_configs())
-int conv_num_mfma_configs();
-int wino_num_configs();
-const char* wino_config_name(int i);
+// what other files need of a family beyond its ConvFamily
 bool wino_applicable(const ConvParams& p);
-bool wino_config_valid(int i, const ConvParams& p);
-long wino_grid_blocks(int i, const ConvParams& p);
-int wino_k_tiles(const ConvParams& p);
-int wino_launch(const ConvParams& p, int i, hipStream_t st);
 size_t wino_weight_floats(int Cin, int Cout);
 int launch_wino_pack(const float* hwio, int Cin, int Cout, int Npad, int row_off, float* U, hipStream_t st);
-
-// Skinny path (csrc/ssd_skinny.hip): small-M / long-K convs with the K split inside the workgroup;
-// config ids [conv_num_mfma_configs() + wino_num_configs(), + skinny_num_configs())
-int skinny_num_configs();
-const char* skinny_config_name(int i);
-bool skinny_config_valid(int i, const ConvParams& p);
-long skinny_grid_blocks(int i, const ConvParams& p);
-int skinny_launch(const ConvParams& p, int i, hipStream_t st);
-
-// Split-bf16 implicit-GEMM tiles (csrc/ssd_conv3.hip); config ids behind the skinny ones
-int mfma3_num_configs();
-const char* mfma3_config_name(int i);
-bool mfma3_config_valid(int i, const ConvParams& p);
-long mfma3_grid_blocks(int i, const ConvParams& p);
-int mfma3_k_tiles(const ConvParams& p);
-void mfma3_tile(int i, int* BM, int* BN);
-int mfma3_launch(const ConvParams& p, int i, hipStream_t st, bool bf16 = false);
-const char* bf16_config_name(int i);     // bf16 (one-product) form of split-bf16 tile i; config ids behind the mfma3 ones
-
-// LDS-DMA tiles over pre-split bf16 activation planes (csrc/ssd_convdma.hip); config ids behind the bf16 ones:
-// "dma3_*" (np = 3, fp32 nets) then "dmab_*" (np = 1, the bf16 mode)
-int dma_num_configs();
-const char* dma_config_name(int i, int np);
-bool dma_config_valid(int i, int np, const ConvParams& p);
-long dma_grid_blocks(int i, const ConvParams& p);
-int dma_k_tiles(int np, const ConvParams& p);
-void dma_tile(int i, int* BM, int* BN);
-int dma_launch(const ConvParams& p, int i, int np, hipStream_t st);
-// ... then "dmah_*" (np = 2, fp32 nets, ReLU6-bounded inputs): the same tiles on the two-plane fp16 split, index j in
-// [0, dmah_num_configs()): every tile with one 32-wide k-step per barrier, then ("..._ks2") the tiles whose two stages
-// fit the LDS with two
-int dmah_num_configs();
-const char* dmah_config_name(int j);
-int dmah_tile_index(int j);                // the dma_* tile (and "dma3_*" twin) of dmah config j
-bool dmah_config_valid(int j, const ConvParams& p);
-int dmah_k_tiles(int j, const ConvParams& p);
-int dmah_launch(const ConvParams& p, int j, hipStream_t st);
+void mfma3_tile(int i, int* BM, int* BN);      // the cost model (conv_pick_config)
+// "dmah_*" config j: every dma_* tile with one 32-wide k-step per barrier, then ("..._ks2") the tiles whose two stages fit
+// the LDS with two; the tile's index in the "dma3_*" family
+int dmah_tile_index(int j);
 // fp16 weight planes of a packed [Npad][Kpad] matrix: *absmax_bits_dev receives max |w| as fp32 bits (a non-finite weight:
 // >= 0x7f800000), zeroed by the caller; then the planes of 2^k w
 int launch_absmax_bits(const float* packed, int K, int Cout, unsigned* absmax_bits_dev, hipStream_t st);
@@ -226,12 +228,8 @@ inline int conv_f16x2_weight_exp(unsigned absmax_bits) {
     return 14 - e;
 }
 inline size_t conv_f16x2_plane_shorts(int K, int Cout) { return (size_t)2 * conv_kpad(K) * conv_npad(Cout); }
-bool conv_config_is_dmah(int cfg);
-int conv_dmah_twin(int cfg);               // the "dma3_*" config of the same tile
 int launch_split_planes(const float* x, long n, int C, int np, short* planes, long plane, hipStream_t st);
 int launch_join_planes(const short* planes, long n, int C, int np, long plane, float* x, hipStream_t st);
-bool conv_config_is_dma(int cfg);          // any of the three families
-bool conv_config_writes_planes(int cfg, const ConvParams& p);   // the family's epilogue (conv_epilogue / splitk_reduce_kernel) honours ConvParams::op
 
 int launch_dwconv3x3(const float* in, int B, int H, int W, int C, int stride, int pad_t, int pad_l,
                      int Ho, int Wo, const float* w, const float* scale, const float* shift, int act,

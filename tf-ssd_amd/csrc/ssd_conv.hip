@@ -281,78 +281,127 @@ static const ConvCfg kCfgs[] = {
     CFG(2, 10, 2, 2, 32),  // 64 x 320
 };
 constexpr int kNumMfmaCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
-// config ids: [0, kNumMfmaCfgs) implicit-GEMM tiles, then the Winograd F(2x2,3x3) tiles
-// (csrc/ssd_wino.hip), last = VALU direct kernel
-// then the skinny (in-workgroup K split) tiles (csrc/ssd_skinny.hip)
-// then the split-bf16 implicit-GEMM tiles (csrc/ssd_conv3.hip)
-static int skinny_cfg0() { return kNumMfmaCfgs + wino_num_configs(); }
-static int mfma3_cfg0() { return kNumMfmaCfgs + wino_num_configs() + skinny_num_configs(); }
-// then the same tiles as bf16 (one-product) kernels: only chosen when asked for by name / by the net's precision-1 mode
-static int bf16_cfg0() { return kNumMfmaCfgs + wino_num_configs() + skinny_num_configs() + mfma3_num_configs(); }
-// then the LDS-DMA tiles over pre-split activation planes (csrc/ssd_convdma.hip): "dma3_*" (fp32 nets), "dmab_*" (bf16 mode)
-static int dma3_cfg0() { return kNumMfmaCfgs + wino_num_configs() + skinny_num_configs() + 2 * mfma3_num_configs(); }
-static int dmab_cfg0() { return dma3_cfg0() + dma_num_configs(); }
-// then the same tiles on the two-plane fp16 split, "dmah_*" (fp32 nets, ReLU6-bounded inputs: ssd_bf16x3.h)
-static int dmah_cfg0() { return dma3_cfg0() + 2 * dma_num_configs(); }
-static int direct_cfg() { return dmah_cfg0() + dmah_num_configs(); }
-#define kSkinnyCfg0 skinny_cfg0()
-#define kMfma3Cfg0 mfma3_cfg0()
-#define kBf16Cfg0 bf16_cfg0()
-#define kDma3Cfg0 dma3_cfg0()
-#define kDmabCfg0 dmab_cfg0()
-#define kDmahCfg0 dmah_cfg0()
-#define kDirectCfg direct_cfg()
-bool conv_config_is_dma(int cfg) { return cfg >= kDma3Cfg0 && cfg < kDirectCfg; }
-bool conv_config_is_dmah(int cfg) { return cfg >= kDmahCfg0 && cfg < kDirectCfg; }
-int conv_dmah_twin(int cfg) { return conv_config_is_dmah(cfg) ? kDma3Cfg0 + dmah_tile_index(cfg - kDmahCfg0) : cfg; }
-bool conv_config_writes_planes(int cfg, const ConvParams& p) {
-    if (cfg == kDirectCfg) return stem_ok(p);              // the RGB stem kernel does, the generic VALU kernel does not
-    return (cfg >= 0 && cfg < kNumMfmaCfgs) || (cfg >= kMfma3Cfg0 && cfg < kDirectCfg);      // fp32-MFMA, split-bf16, bf16 and LDS-DMA tiles
-}
 
-int conv_num_mfma_configs() { return kNumMfmaCfgs; }
-int conv_num_configs() { return kDirectCfg + 1; }
-const char* conv_config_name(int cfg) {
-    if (cfg == kDirectCfg) return "direct_valu";
-    if (cfg >= kDmahCfg0 && cfg < kDirectCfg) return dmah_config_name(cfg - kDmahCfg0);
-    if (cfg >= kDmabCfg0 && cfg < kDmahCfg0) return dma_config_name(cfg - kDmabCfg0, 1);
-    if (cfg >= kDma3Cfg0 && cfg < kDmabCfg0) return dma_config_name(cfg - kDma3Cfg0, 3);
-    if (cfg >= kBf16Cfg0 && cfg < kDma3Cfg0) return bf16_config_name(cfg - kBf16Cfg0);
-    if (cfg >= kMfma3Cfg0 && cfg < kBf16Cfg0) return mfma3_config_name(cfg - kMfma3Cfg0);
-    if (cfg >= kSkinnyCfg0 && cfg < kMfma3Cfg0) return skinny_config_name(cfg - kSkinnyCfg0);
-    if (cfg >= kNumMfmaCfgs && cfg < kSkinnyCfg0) return wino_config_name(cfg - kNumMfmaCfgs);
-    if (cfg < 0 || cfg >= kNumMfmaCfgs) return "?";
-    return kCfgs[cfg].name;
-}
-
-bool conv_config_allowed(int cfg, int precision) {
-    const bool bf16 = (cfg >= kBf16Cfg0 && cfg < kDma3Cfg0) || (cfg >= kDmabCfg0 && cfg < kDmahCfg0);
-    if (!precision) return !bf16;
-    const bool split = (cfg >= kMfma3Cfg0 && cfg < kBf16Cfg0) || (cfg >= kDma3Cfg0 && cfg < kDmabCfg0) || conv_config_is_dmah(cfg);
-    const bool wino = cfg >= kNumMfmaCfgs && cfg < kSkinnyCfg0;
-    return !split && !wino;
-}
-
-static bool is_gemm1x1(const ConvParams& p) {
-    return p.kh == 1 && p.kw == 1 && p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 && p.Ho == p.H && p.Wo == p.W;
-}
-
-bool conv_config_valid(int cfg, const ConvParams& p) {
-    if (cfg == kDirectCfg) return (size_t)p.K * ((p.Cout + 3) & ~3) * 4 <= 64 * 1024;
-    if (cfg >= kDmahCfg0 && cfg < kDirectCfg) return dmah_config_valid(cfg - kDmahCfg0, p);
-    if (cfg >= kDmabCfg0 && cfg < kDmahCfg0) return dma_config_valid(cfg - kDmabCfg0, 1, p);
-    if (cfg >= kDma3Cfg0 && cfg < kDmabCfg0) return dma_config_valid(cfg - kDma3Cfg0, 3, p);
-    if (cfg >= kBf16Cfg0 && cfg < kDma3Cfg0) return mfma3_config_valid(cfg - kBf16Cfg0, p);
-    if (cfg >= kMfma3Cfg0 && cfg < kBf16Cfg0) return mfma3_config_valid(cfg - kMfma3Cfg0, p);
-    if (cfg >= kSkinnyCfg0 && cfg < kMfma3Cfg0) return skinny_config_valid(cfg - kSkinnyCfg0, p);
-    if (cfg >= kNumMfmaCfgs && cfg < kSkinnyCfg0) return wino_config_valid(cfg - kNumMfmaCfgs, p);
-    if (cfg < 0 || cfg >= kNumMfmaCfgs) return false;
+static int mfma_num_configs() { return kNumMfmaCfgs; }
+static const char* mfma_config_name(int i) { return kCfgs[i].name; }
+static bool mfma_config_valid(int i, const ConvParams& p) {
     if (((uintptr_t)p.in & 15) || ((uintptr_t)p.w & 15)) return false;
     if (p.Cin % 4) return false;
     if (p.M > 0x7fffffffL - 1024) return false;   // 32-bit pixel indices in the kernel
-    if (is_gemm1x1(p)) return true;
+    if (conv_is_gemm1x1(p)) return true;
     if (p.kh * p.kw > 32) return false;          // per-row tap validity is a 32-bit mask
-    return p.Cin % kCfgs[cfg].BK == 0;
+    return p.Cin % kCfgs[i].BK == 0;
+}
+static long mfma_grid_blocks(int i, const ConvParams& p) {
+    const ConvCfg& g = kCfgs[i];
+    return ((p.M + g.BM - 1) / g.BM) * ((p.Cout + g.BN - 1) / g.BN);
+}
+static int mfma_k_tiles(int i, const ConvParams& p) { return (p.K + kCfgs[i].BK - 1) / kCfgs[i].BK; }
+static int mfma_launch(const ConvParams& p, int i, hipStream_t st) {
+    const long blocks = mfma_grid_blocks(i, p);
+    SSD_UNSUPPORTED_IF(blocks > 0x7fffffffL, "conv2d: grid too large");
+    dim3 grid((unsigned)blocks, p.split_k > 1 ? p.split_k : 1);
+    hipLaunchKernelGGL(conv_is_gemm1x1(p) ? kCfgs[i].gemm : kCfgs[i].general, grid, dim3(256), 0, st, p);
+    SSD_LAUNCH_CHECK();
+    return SSD_OK;
+}
+#ifndef __HIP_DEVICE_COMPILE__      // (host data)
+const ConvFamily kConvMfma = {CF_MFMA, mfma_num_configs, mfma_config_name, mfma_config_valid, mfma_grid_blocks, mfma_k_tiles, mfma_launch,
+                              CONV_READS_FP32 | CONV_NET_FP32 | CONV_NET_BF16 | CONV_WRITES_PLANES | CONV_SPLITK_REDUCE};
+#endif
+
+// the one VALU config: the RGB stem kernel where it applies (stem_ok), the generic direct kernel otherwise.  Neither splits K.
+static int direct_num_configs() { return 1; }
+static const char* direct_config_name(int) { return "direct_valu"; }
+static bool direct_config_valid(int, const ConvParams& p) { return (size_t)p.K * ((p.Cout + 3) & ~3) * 4 <= 64 * 1024; }
+static long direct_grid_blocks(int, const ConvParams&) { return 0; }      // (grid-stride kernels: no tile grid to fill the CUs with)
+static int direct_k_tiles(int, const ConvParams&) { return 0; }
+static int direct_launch(const ConvParams& p, int, hipStream_t st) {
+    if (stem_ok(p)) {
+        constexpr int PX = 2;
+        const long blocks = cdiv(p.M, 256 * PX);
+        dim3 grid((unsigned)(blocks < 65535 ? blocks : 65535), p.Cout / 32);
+        hipLaunchKernelGGL(conv_stem_kernel<PX>, grid, dim3(256), 0, st, p);
+    } else {
+        const long total = p.M * ((p.Cout + 3) / 4);
+        const int blocks = (int)(cdiv(total, 256) < 8192 ? cdiv(total, 256) : 8192);
+        const size_t lds = (size_t)p.K * ((p.Cout + 3) & ~3) * 4;
+        hipLaunchKernelGGL(conv_direct_kernel, dim3(blocks), dim3(256), lds, st, p);
+    }
+    SSD_LAUNCH_CHECK();
+    return SSD_OK;
+}
+#ifndef __HIP_DEVICE_COMPILE__      // (host data)
+const ConvFamily kConvDirect = {CF_DIRECT, direct_num_configs, direct_config_name, direct_config_valid, direct_grid_blocks, direct_k_tiles,
+                                direct_launch, CONV_READS_FP32 | CONV_NET_FP32 | CONV_NET_BF16};
+#endif
+
+// ------------------------------------------------------------------ the registry
+// Indexed by ConvFamilyId; config ids run through the families in this order.  The tuning tables name configs by name, the
+// autotune walks and breaks ties in id order, and the direct kernel is the last id: append tiles to a family's table, new
+// families before kConvDirect -- both shift ids but no name.
+static const ConvFamily* const kFamilies[] = {&kConvMfma, &kConvWino, &kConvSkinny, &kConvMfma3, &kConvBf16,
+                                              &kConvDma3, &kConvDmab, &kConvDmah,   &kConvDirect};
+constexpr int kNumFamilies = sizeof(kFamilies) / sizeof(kFamilies[0]);
+// first[f] = the first config id of family f; first[kNumFamilies] = the number of configs
+static const int* family_first() {
+    static const struct First {
+        int v[kNumFamilies + 1];
+        First() {
+            v[0] = 0;
+            for (int f = 0; f < kNumFamilies; ++f) v[f + 1] = v[f] + kFamilies[f]->count();
+        }
+    } first;
+    return first.v;
+}
+struct ConvRef {
+    const ConvFamily* fam;       // nullptr: cfg is no config id
+    int i;                       // index in the family
+};
+static ConvRef conv_resolve(int cfg) {
+    const int* first = family_first();
+    for (int f = 0; f < kNumFamilies && cfg >= 0; ++f)
+        if (cfg < first[f + 1]) return {kFamilies[f], cfg - first[f]};
+    return {nullptr, 0};
+}
+
+int conv_num_configs() { return family_first()[kNumFamilies]; }
+const char* conv_config_name(int cfg) {
+    const ConvRef r = conv_resolve(cfg);
+    return r.fam ? r.fam->name(r.i) : "?";
+}
+ConvFamilyId conv_config_family(int cfg) {
+    const ConvRef r = conv_resolve(cfg);
+    return r.fam ? r.fam->id : CF_NONE;
+}
+static unsigned conv_config_traits(int cfg) {
+    const ConvRef r = conv_resolve(cfg);
+    return r.fam ? r.fam->traits : 0;
+}
+bool conv_config_allowed(int cfg, int precision) { return conv_config_traits(cfg) & (precision ? CONV_NET_BF16 : CONV_NET_FP32); }
+int conv_config_reads(int cfg) { return conv_config_traits(cfg) & CONV_READS_MASK; }
+bool conv_config_is_dma(int cfg) { return conv_config_reads(cfg) != CONV_READS_FP32; }
+bool conv_config_is_dmah(int cfg) { return conv_config_reads(cfg) == CONV_READS_F16X2; }
+int conv_dmah_twin(int cfg) {
+    const ConvRef r = conv_resolve(cfg);
+    return r.fam == &kConvDmah ? family_first()[CF_DMA3] + dmah_tile_index(r.i) : cfg;
+}
+bool conv_config_writes_planes(int cfg, const ConvParams& p) {
+    const ConvRef r = conv_resolve(cfg);
+    if (r.fam == &kConvDirect) return stem_ok(p);          // the RGB stem kernel does, the generic VALU kernel does not
+    return r.fam && (r.fam->traits & CONV_WRITES_PLANES);
+}
+bool conv_config_valid(int cfg, const ConvParams& p) {
+    const ConvRef r = conv_resolve(cfg);
+    return r.fam && r.fam->valid(r.i, p);
+}
+long conv_grid_blocks(int cfg, const ConvParams& p) {
+    const ConvRef r = conv_resolve(cfg);
+    return r.fam ? r.fam->grid_blocks(r.i, p) : 0;
+}
+int conv_k_tiles(int cfg, const ConvParams& p) {
+    const ConvRef r = conv_resolve(cfg);
+    return r.fam ? r.fam->k_tiles(r.i, p) : 0;
 }
 
 // Cost model used when no autotuned choice is supplied: MFMA time of the padded tiles on
@@ -361,7 +410,7 @@ int conv_pick_config(const ConvParams& p) {
     int best = -1;
     double best_cost = 1e300;
     for (int c = 0; c < kNumMfmaCfgs; ++c) {
-        if (!conv_config_valid(c, p)) continue;
+        if (!mfma_config_valid(c, p)) continue;
         const ConvCfg& g = kCfgs[c];
         const double mb = (double)((p.M + g.BM - 1) / g.BM), nb = (double)((p.Cout + g.BN - 1) / g.BN);
         const double kk = (double)round_up(p.K, g.BK);
@@ -371,14 +420,14 @@ int conv_pick_config(const ConvParams& p) {
         const double bytes = (mb * g.BM * kk * nb + nb * g.BN * kk * mb) * 4.0 + (double)p.M * p.Cout * 4.0;
         const double t_mem = bytes / 6.0e12;
         const double cost = (t_mfma > t_mem ? t_mfma : t_mem) + 0.25 * (t_mfma < t_mem ? t_mfma : t_mem);
-        if (cost < best_cost) { best_cost = cost; best = c; }
+        if (cost < best_cost) { best_cost = cost; best = family_first()[CF_MFMA] + c; }
     }
     // split-bf16 tiles (need the weights' planes): matrix rate derated to what the kernels measured (the staging of
     // the split operands shares the loop), 6 bytes per weight element; not for the smallest problems
     // (bf16 mode: the same tiles with one product instead of six -- matrix rate x 4 in the model, 2 bytes per weight element)
     if (p.w3 && p.M >= 2048 && p.K >= 64) {
-        for (int c = 0; c < mfma3_num_configs(); ++c) {
-            if (!mfma3_config_valid(c, p)) continue;
+        for (int c = 0; c < kConvMfma3.count(); ++c) {
+            if (!kConvMfma3.valid(c, p)) continue;
             int BM, BN;
             mfma3_tile(c, &BM, &BN);
             const double mb = (double)((p.M + BM - 1) / BM), nb = (double)((p.Cout + BN - 1) / BN);
@@ -388,37 +437,11 @@ int conv_pick_config(const ConvParams& p) {
             const double bytes = mb * BM * kk * nb * 4.0 + nb * BN * kk * mb * (p.bf16 ? 2.0 : 6.0) + (double)p.M * p.Cout * 4.0;
             const double t_mem = bytes / 6.0e12;
             const double cost = (t_mfma > t_mem ? t_mfma : t_mem) + 0.25 * (t_mfma < t_mem ? t_mfma : t_mem);
-            if (cost < best_cost) { best_cost = cost; best = (p.bf16 ? kBf16Cfg0 : kMfma3Cfg0) + c; }
+            if (cost < best_cost) { best_cost = cost; best = family_first()[p.bf16 ? CF_BF16 : CF_MFMA3] + c; }
         }
     }
-    if (best < 0 && conv_config_valid(kDirectCfg, p)) best = kDirectCfg;
+    if (best < 0 && direct_config_valid(0, p)) best = family_first()[CF_DIRECT];
     return best;
-}
-
-long conv_grid_blocks(int cfg, const ConvParams& p) {
-    if (cfg >= kDmahCfg0 && cfg < kDirectCfg) return dma_grid_blocks(dmah_tile_index(cfg - kDmahCfg0), p);
-    if (cfg >= kDmabCfg0 && cfg < kDmahCfg0) return dma_grid_blocks(cfg - kDmabCfg0, p);
-    if (cfg >= kDma3Cfg0 && cfg < kDmabCfg0) return dma_grid_blocks(cfg - kDma3Cfg0, p);
-    if (cfg >= kBf16Cfg0 && cfg < kDma3Cfg0) return mfma3_grid_blocks(cfg - kBf16Cfg0, p);
-    if (cfg >= kMfma3Cfg0 && cfg < kBf16Cfg0) return mfma3_grid_blocks(cfg - kMfma3Cfg0, p);
-    if (cfg >= kSkinnyCfg0 && cfg < kMfma3Cfg0) return skinny_grid_blocks(cfg - kSkinnyCfg0, p);
-    if (cfg >= kNumMfmaCfgs && cfg < kSkinnyCfg0) return wino_grid_blocks(cfg - kNumMfmaCfgs, p);
-    if (cfg < 0 || cfg >= kNumMfmaCfgs) return 0;
-    const ConvCfg& g = kCfgs[cfg];
-    return ((p.M + g.BM - 1) / g.BM) * ((p.Cout + g.BN - 1) / g.BN);
-}
-int conv_k_tiles(int cfg, const ConvParams& p) {
-    if (cfg >= kDmahCfg0 && cfg < kDirectCfg) return dmah_k_tiles(cfg - kDmahCfg0, p);
-    if (cfg >= kDma3Cfg0 && cfg < kDmahCfg0) return dma_k_tiles(cfg >= kDmabCfg0 ? 1 : 3, p);
-    if (cfg >= kMfma3Cfg0 && cfg < kDma3Cfg0) return mfma3_k_tiles(p);      // (split-bf16 and bf16 tiles)
-    if (cfg >= kSkinnyCfg0 && cfg < kMfma3Cfg0) return p.K / 16;
-    if (cfg >= kNumMfmaCfgs && cfg < kSkinnyCfg0) return wino_k_tiles(p);
-    if (cfg < 0 || cfg >= kNumMfmaCfgs) return 0;
-    return (p.K + kCfgs[cfg].BK - 1) / kCfgs[cfg].BK;
-}
-
-size_t conv_splitk_workspace_floats(const ConvParams& p, int) {
-    return p.split_k > 1 ? (size_t)p.split_k * p.M * p.Cout : 0;
 }
 
 int conv_launch(const ConvParams& p, int cfg, hipStream_t st) {
@@ -431,55 +454,10 @@ int conv_launch(const ConvParams& p, int cfg, hipStream_t st) {
     // a plane-only output (no fp32 destination): only the families whose epilogue writes the planes, dense outputs only
     SSD_UNSUPPORTED_IF(!p.out && !(p.op && !p.n_split && (p.Cout & 3) == 0 && conv_config_writes_planes(cfg, p)),
                        "conv2d: config %s cannot write a plane-only output", conv_config_name(cfg));
-    if (cfg >= kDmahCfg0 && cfg < kDirectCfg) {
-        const int rc = dmah_launch(p, cfg - kDmahCfg0, st);
-        if (rc || p.split_k <= 1) return rc;
-        return launch_splitk_reduce(p, st);
-    }
-    if (cfg >= kDma3Cfg0 && cfg < kDmahCfg0) {
-        const bool b1 = cfg >= kDmabCfg0;
-        const int rc = dma_launch(p, cfg - (b1 ? kDmabCfg0 : kDma3Cfg0), b1 ? 1 : 3, st);
-        if (rc || p.split_k <= 1) return rc;
-        return launch_splitk_reduce(p, st);
-    }
-    if (cfg >= kMfma3Cfg0 && cfg < kDma3Cfg0) {
-        const bool bf16 = cfg >= kBf16Cfg0;
-        const int rc = mfma3_launch(p, cfg - (bf16 ? kBf16Cfg0 : kMfma3Cfg0), st, bf16);
-        if (rc || p.split_k <= 1) return rc;
-        return launch_splitk_reduce(p, st);
-    }
-    if (cfg >= kSkinnyCfg0 && cfg < kMfma3Cfg0) return skinny_launch(p, cfg - kSkinnyCfg0, st);
-    if (cfg >= kNumMfmaCfgs && cfg < kSkinnyCfg0) {
-        const int rc = wino_launch(p, cfg - kNumMfmaCfgs, st);
-        if (rc || p.split_k <= 1) return rc;
-        return launch_splitk_reduce(p, st);
-    }
-    if (cfg == kDirectCfg && stem_ok(p)) {
-        constexpr int PX = 2;
-        const long blocks = cdiv(p.M, 256 * PX);
-        dim3 grid((unsigned)(blocks < 65535 ? blocks : 65535), p.Cout / 32);
-        hipLaunchKernelGGL(conv_stem_kernel<PX>, grid, dim3(256), 0, st, p);
-        SSD_LAUNCH_CHECK();
-        return SSD_OK;
-    }
-    if (cfg == kDirectCfg) {
-        const long total = p.M * ((p.Cout + 3) / 4);
-        const int blocks = (int)(cdiv(total, 256) < 8192 ? cdiv(total, 256) : 8192);
-        const size_t lds = (size_t)p.K * ((p.Cout + 3) & ~3) * 4;
-        hipLaunchKernelGGL(conv_direct_kernel, dim3(blocks), dim3(256), lds, st, p);
-        SSD_LAUNCH_CHECK();
-        return SSD_OK;
-    }
-    const ConvCfg& g = kCfgs[cfg];
-    const long mb = (p.M + g.BM - 1) / g.BM;
-    const int nb = (p.Cout + g.BN - 1) / g.BN;
-    SSD_UNSUPPORTED_IF(mb * nb > 0x7fffffffL, "conv2d: grid too large");
-    dim3 grid((unsigned)(mb * nb), p.split_k > 1 ? p.split_k : 1);
-    conv_kernel_t k = is_gemm1x1(p) ? g.gemm : g.general;
-    hipLaunchKernelGGL(k, grid, dim3(256), 0, st, p);
-    SSD_LAUNCH_CHECK();
-    if (p.split_k > 1) return launch_splitk_reduce(p, st);
-    return SSD_OK;
+    const ConvRef r = conv_resolve(cfg);
+    const int rc = r.fam->launch(p, r.i, st);
+    if (rc || p.split_k <= 1 || !(r.fam->traits & CONV_SPLITK_REDUCE)) return rc;
+    return launch_splitk_reduce(p, st);
 }
 
 int launch_splitk_reduce(const ConvParams& p, hipStream_t st) {
@@ -534,6 +512,24 @@ int fill_conv_params(const ssd_conv_desc* d, ConvParams* p) {
 
 using namespace ssd;
 
+// What the three conv entry points share (`who` = the entry point's message prefix): the residual, the fp32 destination
+// with its default strides, the split-K workspace.
+static int bind_conv_io(ConvParams& p, const ssd_conv_desc* d, const char* who, const float* residual_dev, float* out_dev,
+                        long out_batch_stride, long out_pixel_stride, int split_k, float* splitk_ws_dev) {
+    SSD_CHECK_ARG(!d->has_residual || residual_dev, "%s: has_residual set but residual is NULL", who);
+    p.residual = d->has_residual ? residual_dev : nullptr;
+    p.out = out_dev;
+    p.out_pixel_stride = out_pixel_stride > 0 ? out_pixel_stride : p.Cout;
+    p.out_batch_stride = out_batch_stride > 0 ? out_batch_stride : (long)p.Ho * p.Wo * p.out_pixel_stride;
+    p.vec_store = conv_vec_store(p);
+    if (split_k > 1) {
+        SSD_CHECK_ARG(splitk_ws_dev != nullptr, "%s: split_k > 1 needs a workspace", who);
+        p.split_k = split_k;
+        p.partial = splitk_ws_dev;
+    }
+    return SSD_OK;
+}
+
 extern "C" {
 
 int ssd_same_pads(int in, int k, int stride, int dilation, int* before, int* after) {
@@ -582,22 +578,13 @@ int ssd_conv2d_ex(const ssd_conv_desc* d, const float* in_dev, const float* pack
     if (rc) return rc;
     if (p.M == 0) return SSD_OK;
     SSD_CHECK_ARG(in_dev && packed_w_dev && out_dev, "conv2d: NULL pointer");
-    SSD_CHECK_ARG(!d->has_residual || residual_dev, "conv2d: has_residual set but residual is NULL");
+    rc = bind_conv_io(p, d, "conv2d", residual_dev, out_dev, out_batch_stride, out_pixel_stride, split_k, splitk_ws_dev);
+    if (rc) return rc;
     p.in = in_dev; p.w = packed_w_dev; p.scale = scale_dev; p.shift = shift_dev;
     p.w3 = conv_split_planes(packed_w_dev, p.K, p.Cout);
-    p.residual = d->has_residual ? residual_dev : nullptr;
-    p.out = out_dev;
-    p.out_pixel_stride = out_pixel_stride > 0 ? out_pixel_stride : p.Cout;
-    p.out_batch_stride = out_batch_stride > 0 ? out_batch_stride : (long)p.Ho * p.Wo * p.out_pixel_stride;
-    p.vec_store = (((uintptr_t)out_dev & 15) == 0) && (p.out_pixel_stride % 4 == 0) && (p.out_batch_stride % 4 == 0);
-    if (split_k > 1) {
-        SSD_CHECK_ARG(splitk_ws_dev != nullptr, "conv2d: split_k > 1 needs a workspace");
-        p.split_k = split_k;
-        p.partial = splitk_ws_dev;
-    }
     const int cfg = config >= 0 ? config : conv_pick_config(p);
     SSD_UNSUPPORTED_IF(cfg < 0, "conv2d: no kernel for Cin=%d Cout=%d k=%dx%d", p.Cin, p.Cout, p.kh, p.kw);
-    if (cfg == conv_num_configs() - 1) p.split_k = 1;
+    if (conv_config_family(cfg) == CF_DIRECT) p.split_k = 1;
     return conv_launch(p, cfg, (hipStream_t)stream);
 }
 
@@ -682,17 +669,13 @@ static int conv2d_planes_impl(const ssd_conv_desc* d, const void* in_planes_dev,
         p.acc_scale = ldexpf(1.f, -(8 + w_exp));
     }
     SSD_CHECK_ARG(in_plane_stride >= (long)p.B * p.H * p.W * p.Cin, "conv2d_planes: in_plane_stride shorter than the tensor");
-    SSD_CHECK_ARG(!d->has_residual || residual_dev, "conv2d_planes: has_residual set but residual is NULL");
+    rc = bind_conv_io(p, d, "conv2d_planes", residual_dev, out_dev, out_batch_stride, out_pixel_stride, split_k, splitk_ws_dev);
+    if (rc) return rc;
     SSD_CHECK_ARG(config >= 0 && config < conv_num_configs() && conv_config_is_dma(config), "conv2d_planes: config %d is not an LDS-DMA tile", config);
     p.xp = static_cast<const short*>(in_planes_dev); p.xp_plane = in_plane_stride; p.xp_np = planes;
     p.bf16 = planes == 1;
     p.w = packed_w_dev; p.scale = scale_dev; p.shift = shift_dev;
     p.w3 = conv_split_planes(packed_w_dev, p.K, p.Cout);
-    p.residual = d->has_residual ? residual_dev : nullptr;
-    p.out = out_dev;
-    p.out_pixel_stride = out_pixel_stride > 0 ? out_pixel_stride : p.Cout;
-    p.out_batch_stride = out_batch_stride > 0 ? out_batch_stride : (long)p.Ho * p.Wo * p.out_pixel_stride;
-    p.vec_store = (((uintptr_t)out_dev & 15) == 0) && (p.out_pixel_stride % 4 == 0) && (p.out_batch_stride % 4 == 0);
     if (out_planes_dev) {
         // (slice-major planes: the last 32-channel slice may be partly used; the epilogue stores four channels at a time)
         SSD_CHECK_ARG(p.out_pixel_stride == p.Cout && p.out_batch_stride == (long)p.Ho * p.Wo * p.Cout && p.Cout % 4 == 0,
@@ -700,11 +683,6 @@ static int conv2d_planes_impl(const ssd_conv_desc* d, const void* in_planes_dev,
         SSD_CHECK_ARG(out_plane_stride >= p.M * ((p.Cout + 31) / 32 * 32) && out_plane_stride % 8 == 0 && ((uintptr_t)out_planes_dev & 7) == 0,
                       "conv2d_planes: bad out_plane_stride (whole 32-channel slices of all %ld pixels) or unaligned planes", p.M);
         p.op = static_cast<short*>(out_planes_dev); p.op_plane = out_plane_stride; p.op_np = planes;
-    }
-    if (split_k > 1) {
-        SSD_CHECK_ARG(splitk_ws_dev != nullptr, "conv2d_planes: split_k > 1 needs a workspace");
-        p.split_k = split_k;
-        p.partial = splitk_ws_dev;
     }
     return conv_launch(p, config, (hipStream_t)stream);
 }
@@ -720,7 +698,7 @@ int ssd_conv_wino_pack_weights(const float* hwio_dev, int Cin, int Cout, float* 
     return launch_wino_pack(hwio_dev, Cin, Cout, conv_npad(Cout), 0, wino_w_dev, (hipStream_t)stream);
 }
 
-int ssd_conv_wino_num_configs(void) { return wino_num_configs(); }
+int ssd_conv_wino_num_configs(void) { return kConvWino.count(); }
 
 int ssd_conv2d_wino(const ssd_conv_desc* d, const float* in_dev, const float* wino_w_dev, const float* scale_dev,
                     const float* shift_dev, float* out_dev, long out_batch_stride, long out_pixel_stride,
@@ -732,21 +710,13 @@ int ssd_conv2d_wino(const ssd_conv_desc* d, const float* in_dev, const float* wi
     SSD_CHECK_ARG(in_dev && wino_w_dev && out_dev, "conv2d_wino: NULL pointer");
     SSD_CHECK_ARG(!d->has_residual, "conv2d_wino: residual is not supported");
     p.in = in_dev; p.wino_w = wino_w_dev; p.scale = scale_dev; p.shift = shift_dev;
-    p.out = out_dev;
-    p.out_pixel_stride = out_pixel_stride > 0 ? out_pixel_stride : p.Cout;
-    p.out_batch_stride = out_batch_stride > 0 ? out_batch_stride : (long)p.Ho * p.Wo * p.out_pixel_stride;
-    p.vec_store = (((uintptr_t)out_dev & 15) == 0) && (p.out_pixel_stride % 4 == 0) && (p.out_batch_stride % 4 == 0);
-    if (split_k > 1) {
-        SSD_CHECK_ARG(splitk_ws_dev != nullptr, "conv2d_wino: split_k > 1 needs a workspace");
-        SSD_CHECK_ARG(split_k <= p.Cin / 16, "conv2d_wino: split_k %d exceeds the %d channel slabs", split_k, p.Cin / 16);
-        p.split_k = split_k;
-        p.partial = splitk_ws_dev;
-    }
+    rc = bind_conv_io(p, d, "conv2d_wino", nullptr, out_dev, out_batch_stride, out_pixel_stride, split_k, splitk_ws_dev);
+    if (rc) return rc;
+    SSD_CHECK_ARG(split_k <= 1 || split_k <= p.Cin / 16, "conv2d_wino: split_k %d exceeds the %d channel slabs", split_k, p.Cin / 16);
     // (worded like every other family's refusal: "cannot run" is what callers and tests look for in ssd_last_error())
     SSD_UNSUPPORTED_IF(!wino_applicable(p), "conv2d_wino: the Winograd tiles cannot run Cin=%d k=%dx%d stride=%d dilation=%d (they need a 3x3 "
                        "stride-1 dilation-1 conv with Cin %% 16 == 0 and no residual)", p.Cin, p.kh, p.kw, p.stride, p.dil);
-    const int cfg = conv_num_mfma_configs() + (wino_config >= 0 ? wino_config : 0);
-    return conv_launch(p, cfg, (hipStream_t)stream);
+    return conv_launch(p, family_first()[CF_WINO] + (wino_config >= 0 ? wino_config : 0), (hipStream_t)stream);
 }
 
 int ssd_conv2d(const ssd_conv_desc* d, const float* in_dev, const float* packed_w_dev, const float* scale_dev,

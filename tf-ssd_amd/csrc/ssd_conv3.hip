@@ -4,7 +4,7 @@
 // v_mfma_f32_16x16x4_f32 and, unlike it, overlapping with the vector ALU.  The wave tiles are 2x..4x wide in BOTH
 // dimensions: a split fragment is 48 bytes per lane for 96 matrix cycles, so it has to be reused from registers
 // (3 (1/MT + 1/NT) LDS reads per six-pack; at MT = 1 -- or under Winograd's 8 accumulator banks -- LDS binds instead).
-// config ids: behind the skinny tiles (ssd_conv.hip).
+// Two tile families, "mfma3_*" and "bf16_*" (kConvMfma3 / kConvBf16 below).
 #include "ssd_conv_mfma.h"
 
 namespace ssd {
@@ -76,51 +76,51 @@ __global__ __launch_bounds__(256) void pack_split_kernel(const float* __restrict
     }
 }
 
-bool c3_gemm1x1(const ConvParams& p) {
-    return p.kh == 1 && p.kw == 1 && p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 && p.Ho == p.H && p.Wo == p.W;
-}
-
-}  // namespace
-
 int mfma3_num_configs() { return kNumCfg3; }
-const char* mfma3_config_name(int i) { return (i >= 0 && i < kNumCfg3) ? kCfg3[i].name : "?"; }
-bool mfma3_config_valid(int i, const ConvParams& p) {
-    if (i < 0 || i >= kNumCfg3) return false;
+const char* mfma3_config_name(int i) { return kCfg3[i].name; }
+const char* bf16_config_name(int i) { return kCfg3[i].name1; }
+bool mfma3_config_valid(int, const ConvParams& p) {
     if (((uintptr_t)p.in & 15) || ((uintptr_t)p.w3 & 15) || !p.w3) return false;
     if (p.Cin % 4) return false;
     if (p.M > 0x7fffffffL - 1024) return false;
-    if (c3_gemm1x1(p)) return true;
+    if (conv_is_gemm1x1(p)) return true;
     if (p.kh * p.kw > 32) return false;
     return p.Cin % 32 == 0;
 }
 long mfma3_grid_blocks(int i, const ConvParams& p) {
-    if (i < 0 || i >= kNumCfg3) return 0;
     return ((p.M + kCfg3[i].BM - 1) / kCfg3[i].BM) * ((p.Cout + kCfg3[i].BN - 1) / kCfg3[i].BN);
 }
-int mfma3_k_tiles(const ConvParams& p) { return (p.K + 31) / 32; }
-void mfma3_tile(int i, int* BM, int* BN) {
-    *BM = (i >= 0 && i < kNumCfg3) ? kCfg3[i].BM : 0;
-    *BN = (i >= 0 && i < kNumCfg3) ? kCfg3[i].BN : 0;
-}
+int mfma3_k_tiles(int, const ConvParams& p) { return (p.K + 31) / 32; }
 
-const char* bf16_config_name(int i) { return (i >= 0 && i < kNumCfg3) ? kCfg3[i].name1 : "?"; }
-
-// the kernel only (the caller adds the split-K reduction); bf16: the one-product form of the same tile
-int mfma3_launch(const ConvParams& p, int i, hipStream_t st, bool bf16) {
-    if (!mfma3_config_valid(i, p)) {
-        set_error("conv2d: split-bf16 / bf16 config %d cannot run Cin=%d k=%dx%d", i, p.Cin, p.kh, p.kw);
-        return SSD_E_UNSUPPORTED;
-    }
+// bf16: the one-product form of the same tile
+int c3_launch(const ConvParams& p, int i, hipStream_t st, bool bf16) {
     const long blocks = mfma3_grid_blocks(i, p);
     SSD_UNSUPPORTED_IF(blocks > 0x7fffffffL, "conv2d: grid too large");
-    const conv3_kernel_t fn = bf16 ? (c3_gemm1x1(p) ? kCfg3[i].gemm1 : kCfg3[i].general1)
-                                   : (c3_gemm1x1(p) ? kCfg3[i].gemm : kCfg3[i].general);
+    const conv3_kernel_t fn = bf16 ? (conv_is_gemm1x1(p) ? kCfg3[i].gemm1 : kCfg3[i].general1)
+                                   : (conv_is_gemm1x1(p) ? kCfg3[i].gemm : kCfg3[i].general);
     const int lds = c3_lds_bytes(kCfg3[i], bf16 ? 1 : 3);
     if (lds > 64 * 1024) SSD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     dim3 grid((unsigned)blocks, p.split_k > 1 ? p.split_k : 1);
     hipLaunchKernelGGL(fn, grid, dim3(kCfg3[i].threads), lds, st, p);
     SSD_LAUNCH_CHECK();
     return SSD_OK;
+}
+int mfma3_launch(const ConvParams& p, int i, hipStream_t st) { return c3_launch(p, i, st, false); }
+int bf16_launch(const ConvParams& p, int i, hipStream_t st) { return c3_launch(p, i, st, true); }
+
+}  // namespace
+
+#ifndef __HIP_DEVICE_COMPILE__      // (host data)
+// two families over the one tile table: the split-bf16 tiles (fp32 nets) and their bf16 forms (the precision-1 mode)
+const ConvFamily kConvMfma3 = {CF_MFMA3, mfma3_num_configs, mfma3_config_name, mfma3_config_valid, mfma3_grid_blocks, mfma3_k_tiles,
+                               mfma3_launch, CONV_READS_FP32 | CONV_NET_FP32 | CONV_WRITES_PLANES | CONV_SPLITK_REDUCE};
+const ConvFamily kConvBf16 = {CF_BF16, mfma3_num_configs, bf16_config_name, mfma3_config_valid, mfma3_grid_blocks, mfma3_k_tiles,
+                              bf16_launch, CONV_READS_FP32 | CONV_NET_BF16 | CONV_WRITES_PLANES | CONV_SPLITK_REDUCE};
+#endif
+
+void mfma3_tile(int i, int* BM, int* BN) {
+    *BM = kCfg3[i].BM;
+    *BN = kCfg3[i].BN;
 }
 
 int launch_pack_split(float* packed, int K, int Cout, hipStream_t st, bool row_major) {

@@ -23,7 +23,7 @@
 //     of np = 3 -- with K = 32 or (tiles whose two stages fit 160 KB) K = 64 per barrier; the accumulators are multiplied
 //     by the exact 2^-(8 + k) before the epilogue.
 // Epilogue = conv_epilogue (ssd_conv_mfma.h): BN / bias, activation, residual, head routing, optional plane output.
-// config ids: behind the bf16 tiles (ssd_conv.hip): "dma3_*" (np = 3), "dmab_*" (np = 1), "dmah_*" / "dmah_*_ks2" (np = 2).
+// Three tile families (kConvDma3 / kConvDmab / kConvDmah below): "dma3_*" (np = 3), "dmab_*" (np = 1), "dmah_*" / "dmah_*_ks2" (np = 2).
 #include "ssd_block_common.h"
 #include "ssd_conv_mfma.h"
 
@@ -307,10 +307,6 @@ const DmahList& dmah_list() {
     return l;
 }
 
-bool cd_gemm1x1(const ConvParams& p) {
-    return p.kh == 1 && p.kw == 1 && p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 && p.Ho == p.H && p.Wo == p.W;
-}
-
 // fp32 activation -> bf16 planes (np = 3: exact split; np = 1: bf16 rounding); the fallback producer of a tensor whose
 // own producing kernel has no plane epilogue
 __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restrict__ x, const long n4, const int C, const int np,
@@ -359,12 +355,10 @@ __global__ __launch_bounds__(256) void pack_f16x2_kernel(const float* __restrict
     }
 }
 
-}  // namespace
-
 int dma_num_configs() { return kNumCfgD; }
-const char* dma_config_name(int i, int np) { return (i >= 0 && i < kNumCfgD) ? (np == 1 ? kCfgD[i].name1 : kCfgD[i].name3) : "?"; }
+const char* dma3_config_name(int i) { return kCfgD[i].name3; }
+const char* dmab_config_name(int i) { return kCfgD[i].name1; }
 bool dma_config_valid(int i, int np, const ConvParams& p) {
-    if (i < 0 || i >= kNumCfgD) return false;
     const short* wpl = np == 2 ? p.wh : p.w3;        // (np = 2: the fp16 weight planes; every family refuses planes of another)
     if (!p.xp || !wpl || p.xp_np != np) return false;
     if (((uintptr_t)p.xp & 15) || ((uintptr_t)wpl & 15) || (p.xp_plane & 7)) return false;
@@ -372,73 +366,70 @@ bool dma_config_valid(int i, int np, const ConvParams& p) {
     if (4 * (long)p.Npad * p.Kpad * 2 > 0x7fffffffL) return false;
     // slice-major planes: a K tile's channel slice is a scalar offset of up to the whole plane (31 bits)
     if ((long)p.B * p.H * p.W * p.Cin * 2 > 0x7fffffffL) return false;
-    if (cd_gemm1x1(p)) return p.Cin % 32 == 0;
+    if (conv_is_gemm1x1(p)) return p.Cin % 32 == 0;
     if (p.kh * p.kw > 32) return false;
     // a tile's rows span at most BM / (Ho Wo) + 2 images: their per-lane offsets (64 bytes per pixel) must fit 31 bits
     if (((long)kCfgD[i].BM / (p.Ho * p.Wo) + 3) * p.H * p.W * 64 > 0x3fffffffL) return false;
     return p.Cin % (np == 1 ? 64 : 32) == 0;
 }
+bool dma3_config_valid(int i, const ConvParams& p) { return dma_config_valid(i, 3, p); }
+bool dmab_config_valid(int i, const ConvParams& p) { return dma_config_valid(i, 1, p); }
 long dma_grid_blocks(int i, const ConvParams& p) {
-    if (i < 0 || i >= kNumCfgD) return 0;
     return ((p.M + kCfgD[i].BM - 1) / kCfgD[i].BM) * ((p.Cout + kCfgD[i].BN - 1) / kCfgD[i].BN);
 }
-int dma_k_tiles(int np, const ConvParams& p) { return (p.K + 31) / 32 / (np == 1 ? 2 : 1); }
-void dma_tile(int i, int* BM, int* BN) {
-    *BM = (i >= 0 && i < kNumCfgD) ? kCfgD[i].BM : 0;
-    *BN = (i >= 0 && i < kNumCfgD) ? kCfgD[i].BN : 0;
-}
+int dma3_k_tiles(int, const ConvParams& p) { return (p.K + 31) / 32; }
+int dmab_k_tiles(int, const ConvParams& p) { return (p.K + 31) / 32 / 2; }
 
-int dma_launch(const ConvParams& p, int i, int np, hipStream_t st) {
-    if (!dma_config_valid(i, np, p)) {
-        set_error("conv2d: LDS-DMA config %d cannot run Cin=%d k=%dx%d (input planes %s)", i, p.Cin, p.kh, p.kw, p.xp ? "present" : "missing");
-        return SSD_E_UNSUPPORTED;
-    }
+// tile i as kernel `gemm` (a 1x1 GEMM) or `general`, `stage_planes` LDS planes of (BM + BN) x 32 per stage, two stages
+int dma_launch(const ConvParams& p, int i, convd_kernel_t gemm, convd_kernel_t general, int stage_planes, hipStream_t st) {
     const long blocks = dma_grid_blocks(i, p);
     SSD_UNSUPPORTED_IF(blocks > 0x7fffffffL, "conv2d: grid too large");
     const ConvDCfg& g = kCfgD[i];
-    const convd_kernel_t fn = np == 1 ? (cd_gemm1x1(p) ? g.gemm1 : g.general1) : (cd_gemm1x1(p) ? g.gemm3 : g.general3);
-    const int lds = 2 * (np == 1 ? 2 : 3) * (g.BM + g.BN) * 64;
+    const convd_kernel_t fn = conv_is_gemm1x1(p) ? gemm : general;
+    const int lds = 2 * stage_planes * (g.BM + g.BN) * 64;
     if (lds > 64 * 1024) SSD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     dim3 grid((unsigned)blocks, p.split_k > 1 ? p.split_k : 1);
     hipLaunchKernelGGL(fn, grid, dim3(g.threads), lds, st, p);
     SSD_LAUNCH_CHECK();
     return SSD_OK;
 }
+int dma3_launch(const ConvParams& p, int i, hipStream_t st) { return dma_launch(p, i, kCfgD[i].gemm3, kCfgD[i].general3, 3, st); }
+int dmab_launch(const ConvParams& p, int i, hipStream_t st) { return dma_launch(p, i, kCfgD[i].gemm1, kCfgD[i].general1, 2, st); }
 
 int dmah_num_configs() { return dmah_list().n; }
 const char* dmah_config_name(int j) {
     const DmahList& l = dmah_list();
-    return (j >= 0 && j < l.n) ? (l.ks[j] == 2 ? kCfgD[l.tile[j]].nameh2 : kCfgD[l.tile[j]].nameh) : "?";
+    return l.ks[j] == 2 ? kCfgD[l.tile[j]].nameh2 : kCfgD[l.tile[j]].nameh;
 }
-int dmah_tile_index(int j) { return (j >= 0 && j < dmah_list().n) ? dmah_list().tile[j] : -1; }
 bool dmah_config_valid(int j, const ConvParams& p) {
-    if (j < 0 || j >= dmah_list().n) return false;
     if (!(p.acc_scale > 0.f)) return false;
     return dma_config_valid(dmah_list().tile[j], 2, p);
 }
+long dmah_grid_blocks(int j, const ConvParams& p) { return dma_grid_blocks(dmah_list().tile[j], p); }
 int dmah_k_tiles(int j, const ConvParams& p) {
-    const int ks = (j >= 0 && j < dmah_list().n) ? dmah_list().ks[j] : 1;
-    if (cd_gemm1x1(p)) return ((p.K + 31) / 32 + ks - 1) / ks;
+    const int ks = dmah_list().ks[j];
+    if (conv_is_gemm1x1(p)) return ((p.K + 31) / 32 + ks - 1) / ks;
     return p.kh * p.kw * ((p.Cin / 32 + ks - 1) / ks);
 }
 int dmah_launch(const ConvParams& p, int j, hipStream_t st) {
-    if (!dmah_config_valid(j, p)) {
-        set_error("conv2d: two-plane fp16 LDS-DMA config %d cannot run Cin=%d k=%dx%d (input planes %s, %d of them; fp16 weight planes %s)", j,
-                  p.Cin, p.kh, p.kw, p.xp ? "present" : "missing", p.xp_np, p.wh ? "present" : "missing");
-        return SSD_E_UNSUPPORTED;
-    }
-    const int i = dmah_list().tile[j], ks = dmah_list().ks[j];
-    const long blocks = dma_grid_blocks(i, p);
-    SSD_UNSUPPORTED_IF(blocks > 0x7fffffffL, "conv2d: grid too large");
-    const ConvDCfg& g = kCfgD[i];
-    const convd_kernel_t fn = ks == 2 ? (cd_gemm1x1(p) ? g.gemmh2 : g.generalh2) : (cd_gemm1x1(p) ? g.gemmh : g.generalh);
-    const int lds = 2 * ks * 2 * (g.BM + g.BN) * 64;
-    if (lds > 64 * 1024) SSD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    dim3 grid((unsigned)blocks, p.split_k > 1 ? p.split_k : 1);
-    hipLaunchKernelGGL(fn, grid, dim3(g.threads), lds, st, p);
-    SSD_LAUNCH_CHECK();
-    return SSD_OK;
+    const ConvDCfg& g = kCfgD[dmah_list().tile[j]];
+    if (dmah_list().ks[j] == 2) return dma_launch(p, dmah_list().tile[j], g.gemmh2, g.generalh2, 4, st);
+    return dma_launch(p, dmah_list().tile[j], g.gemmh, g.generalh, 2, st);
 }
+
+}  // namespace
+
+#ifndef __HIP_DEVICE_COMPILE__      // (host data)
+// three families over the one tile table: the exact bf16 split (np = 3, fp32 nets), the bf16 rounding (np = 1, the
+// precision-1 mode) and the fp16 pair (np = 2, fp32 nets, ReLU6-bounded inputs: ssd_bf16x3.h)
+const ConvFamily kConvDma3 = {CF_DMA3, dma_num_configs, dma3_config_name, dma3_config_valid, dma_grid_blocks, dma3_k_tiles, dma3_launch,
+                              CONV_READS_PLANES | CONV_NET_FP32 | CONV_WRITES_PLANES | CONV_SPLITK_REDUCE};
+const ConvFamily kConvDmab = {CF_DMAB, dma_num_configs, dmab_config_name, dmab_config_valid, dma_grid_blocks, dmab_k_tiles, dmab_launch,
+                              CONV_READS_PLANES | CONV_NET_BF16 | CONV_WRITES_PLANES | CONV_SPLITK_REDUCE};
+const ConvFamily kConvDmah = {CF_DMAH, dmah_num_configs, dmah_config_name, dmah_config_valid, dmah_grid_blocks, dmah_k_tiles, dmah_launch,
+                              CONV_READS_F16X2 | CONV_NET_FP32 | CONV_WRITES_PLANES | CONV_SPLITK_REDUCE};
+#endif
+int dmah_tile_index(int j) { return dmah_list().tile[j]; }
 
 int launch_absmax_bits(const float* packed, int K, int Cout, unsigned* absmax_bits_dev, hipStream_t st) {
     const long total = (long)conv_kpad(K) * conv_npad(Cout);

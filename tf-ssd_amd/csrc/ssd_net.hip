@@ -567,8 +567,7 @@ static std::vector<char> plane_only_candidates(const ssd_net& net, F reads_plane
         const bool image = l.kind == LK_FUSED && (l.route == RT_IMAGE || l.route == RT_IMAGE_SPLIT);
         bool writes = image || l.kind == LK_POOL || l.kind == LK_L2NORM;
         if (l.kind == LK_CONV)
-            writes = l.head_kind == 0 && (l.Cout & 3) == 0 && l.cfg >= 0 && l.cfg != conv_num_configs() - 1 &&
-                     conv_config_writes_planes(l.cfg, ConvParams{});
+            writes = l.head_kind == 0 && (l.Cout & 3) == 0 && l.cfg >= 0 && conv_config_writes_planes(l.cfg, ConvParams{});
         if (!writes) { bar(l.out); bar(l.e_out); }
     }
     for (int t = 0; t < nt; ++t) ok[t] = ok[t] && readers[t];
@@ -697,15 +696,15 @@ static int autotune(ssd_net& net, int B, hipStream_t st) {
         float* out = l.out >= 0 ? net.tensors[l.out].dev : nullptr;
         const float* res = l.res >= 0 ? net.tensors[l.res].dev : nullptr;
         for (int c = 0; c < conv_num_configs() && !rc; ++c) {
-            const int fam = conv_config_is_dmah(c) ? 2 : conv_config_is_dma(c) ? 1 : 0;
-            if (fam == 2 && (!net.conv_f16x2 || !l.wh)) continue;
+            const int fam = conv_config_reads(c);      // the best tile is kept per storage it reads: fp32, bf16 planes, fp16 pair
+            if (fam == CONV_READS_F16X2 && (!net.conv_f16x2 || !l.wh)) continue;
             for (int si = 0; si < kNumSplits && !rc; ++si) {
                 const int split = kSplits[si];
                 l.split_k = split;
                 ConvParams p = layer_conv_params(net, l, B, in, out, res, d, pr);
-                if (fam == 2) p.xp_np = 2;       // (timed on whatever the planes hold: the matrix unit's time does not depend on the data)
+                if (fam == CONV_READS_F16X2) p.xp_np = 2;       // (timed on whatever the planes hold: the matrix unit's time does not depend on the data)
                 if (!conv_config_valid(c, p) || !conv_config_allowed(c, net.precision)) break;
-                const bool direct = (c == conv_num_configs() - 1);
+                const bool direct = conv_config_family(c) == CF_DIRECT;
                 if (direct && (bb.cfg[0] >= 0 || bb.cfg[1] >= 0 || split > 1)) break;     // direct only as a last resort
                 if (split > 1) {
                     const long blocks = conv_grid_blocks(c, p);
@@ -733,7 +732,7 @@ static int autotune(ssd_net& net, int B, hipStream_t st) {
                 }
                 if (rc) break;
                 if (ms < bb.ms[fam]) { bb.ms[fam] = ms; bb.cfg[fam] = c; bb.split[fam] = split; }
-                if (fam == 2) {
+                if (fam == CONV_READS_F16X2) {
                     float& m2 = strstr(conv_config_name(c), "_ks2") ? bb.ms_k64 : bb.ms_k32;
                     m2 = ms < m2 ? ms : m2;
                 }
@@ -1935,7 +1934,7 @@ double ssd_net_layer_executed_flops(const ssd_net* net, int i, int B) {
     if (!net || i < 0 || i >= (int)net->layers.size()) return 0;
     const Layer& l = net->layers[i];
     if (!layer_runs(l)) return 0;
-    if (l.kind == LK_CONV && l.cfg >= conv_num_mfma_configs() && l.cfg < conv_num_mfma_configs() + wino_num_configs())
+    if (l.kind == LK_CONV && conv_config_family(l.cfg) == CF_WINO)
         return 2.0 * B * ((l.Ho + 1) / 2) * ((l.Wo + 1) / 2) * 16.0 * l.Cin * l.Cout;
     return ssd_net_layer_flops(net, i, B);
 }

@@ -195,15 +195,12 @@ const SkinnyCfg kSkinny[] = {
 };
 constexpr int kNumSkinny = sizeof(kSkinny) / sizeof(kSkinny[0]);
 
-}  // namespace
-
 int skinny_num_configs() { return kNumSkinny; }
-const char* skinny_config_name(int i) { return (i >= 0 && i < kNumSkinny) ? kSkinny[i].name : "?"; }
+const char* skinny_config_name(int i) { return kSkinny[i].name; }
 
 // Small-M, long-K dense convs only (the candidates are timed by the finalize-time autotune: keep the list
 // to the shapes the kernel is for); K in whole 16-wide groups inside one tap.
-bool skinny_config_valid(int i, const ConvParams& p) {
-    if (i < 0 || i >= kNumSkinny) return false;
+bool skinny_config_valid(int, const ConvParams& p) {
     if (p.split_k > 1 || p.Cin % 16 != 0 || p.kh * p.kw > 32 || p.K != p.kh * p.kw * p.Cin) return false;
     if (((uintptr_t)p.in & 15) || ((uintptr_t)p.w & 15) || (p.Kpad & 3)) return false;
     if (p.M > 8192 || p.K < 256) return false;
@@ -211,17 +208,21 @@ bool skinny_config_valid(int i, const ConvParams& p) {
     return true;
 }
 long skinny_grid_blocks(int i, const ConvParams& p) {
-    if (i < 0 || i >= kNumSkinny) return 0;
     return ((p.M + kSkinny[i].tm - 1) / kSkinny[i].tm) * ((p.Cout + kSkinny[i].tn - 1) / kSkinny[i].tn);
 }
+int skinny_k_tiles(int, const ConvParams& p) { return p.K / 16; }
 int skinny_launch(const ConvParams& p, int i, hipStream_t st) {
-    if (!skinny_config_valid(i, p)) {
-        set_error("conv2d: skinny config %d cannot run this convolution", i);
-        return SSD_E_UNSUPPORTED;
-    }
     hipLaunchKernelGGL(kSkinny[i].fn, dim3((unsigned)skinny_grid_blocks(i, p)), dim3(kSkWaves * 64), 0, st, p);
     SSD_LAUNCH_CHECK();
     return SSD_OK;
 }
+
+}  // namespace
+
+#ifndef __HIP_DEVICE_COMPILE__      // (host data)
+// the K split never leaves the workgroup: no split-K slab, no reduce launch
+const ConvFamily kConvSkinny = {CF_SKINNY, skinny_num_configs, skinny_config_name, skinny_config_valid, skinny_grid_blocks,
+                                skinny_k_tiles, skinny_launch, CONV_READS_FP32 | CONV_NET_FP32 | CONV_NET_BF16};
+#endif
 
 }  // namespace ssd

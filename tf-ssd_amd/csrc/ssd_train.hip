@@ -1202,8 +1202,8 @@ static int pick_measured(const ConvParams& p, hipStream_t st, int model_cfg, int
     std::vector<int> candidates;
     for (int c = 0; c < conv_num_configs(); ++c) {
         if (!conv_config_valid(c, q) || !conv_config_allowed(c, q.bf16)) continue;
-        const char* cn = conv_config_name(c);
-        if (!strncmp(cn, "wino_", 5) || !strncmp(cn, "skinny_", 7) || (!strncmp(cn, "direct", 6) && c != model_cfg)) continue;
+        const ConvFamilyId f = conv_config_family(c);
+        if (f == CF_WINO || f == CF_SKINNY || (f == CF_DIRECT && c != model_cfg)) continue;
         candidates.push_back(c);
     }
     TimedPick r;
@@ -1226,8 +1226,8 @@ static int launch_conv(ssd_train_state& s, ConvParams& p, hipStream_t st) {
         (void)hipStreamIsCapturing(st, &cs);
         if (cs == hipStreamCaptureStatusNone) cfg = pick_measured(p, st, cfg, tune > 1);
     }
-    const char* cn = conv_config_name(cfg);
-    s.step_flops[(strncmp(cn, "mfma3_", 6) == 0 || strncmp(cn, "bf16_", 5) == 0) ? 1 : 0] += 2.0 * (double)p.M * p.K * p.Cout;
+    const ConvFamilyId f = conv_config_family(cfg);
+    s.step_flops[(f == CF_MFMA3 || f == CF_BF16) ? 1 : 0] += 2.0 * (double)p.M * p.K * p.Cout;
     return conv_launch(p, cfg, st);
 }
 

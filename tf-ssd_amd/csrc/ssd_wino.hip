@@ -313,29 +313,24 @@ static const WinoCfg kWino[] = {
 };
 constexpr int kNumWino = sizeof(kWino) / sizeof(kWino[0]);
 
-int wino_num_configs() { return kNumWino; }
-const char* wino_config_name(int i) { return (i >= 0 && i < kNumWino) ? kWino[i].name : "?"; }
+static int wino_num_configs() { return kNumWino; }
+static const char* wino_config_name(int i) { return kWino[i].name; }
 
 bool wino_applicable(const ConvParams& p) {
     return p.kh == 3 && p.kw == 3 && p.stride == 1 && p.dil == 1 && p.Cin % 16 == 0 && !p.residual &&
            (((uintptr_t)p.in & 15) == 0) && p.Ho >= 1 && p.Wo >= 1 && p.pad_t >= 0 && p.pad_t <= 2 && p.pad_l >= 0 &&
            p.pad_l <= 2 && p.M < 0x7fffffffL - 1024;
 }
-bool wino_config_valid(int i, const ConvParams& p) {
-    return i >= 0 && i < kNumWino && p.wino_w != nullptr && (((uintptr_t)p.wino_w & 15) == 0) && wino_applicable(p);
+static bool wino_config_valid(int, const ConvParams& p) {
+    return p.wino_w != nullptr && (((uintptr_t)p.wino_w & 15) == 0) && wino_applicable(p);
 }
-long wino_grid_blocks(int i, const ConvParams& p) {
-    if (i < 0 || i >= kNumWino) return 0;
+static long wino_grid_blocks(int i, const ConvParams& p) {
     const long T = (long)p.B * ((p.Ho + 1) / 2) * ((p.Wo + 1) / 2);
     return ((T + kWino[i].TT - 1) / kWino[i].TT) * ((p.Cout + kWino[i].TN - 1) / kWino[i].TN);
 }
-int wino_k_tiles(const ConvParams& p) { return p.Cin / 16; }
+static int wino_k_tiles(int, const ConvParams& p) { return p.Cin / 16; }
 
-int wino_launch(const ConvParams& p, int i, hipStream_t st) {
-    if (!wino_config_valid(i, p)) {
-        set_error("conv2d: Winograd config %d cannot run this convolution", i);
-        return SSD_E_UNSUPPORTED;
-    }
+static int wino_launch(const ConvParams& p, int i, hipStream_t st) {
     const long blocks = wino_grid_blocks(i, p);
     SSD_UNSUPPORTED_IF(blocks > 0x7fffffffL, "conv2d: grid too large");
     dim3 grid((unsigned)blocks, p.split_k > 1 ? p.split_k : 1);
@@ -343,6 +338,11 @@ int wino_launch(const ConvParams& p, int i, hipStream_t st) {
     SSD_LAUNCH_CHECK();
     return SSD_OK;
 }
+#ifndef __HIP_DEVICE_COMPILE__      // (host data)
+// fp32 nets only; the output transform has no plane epilogue
+const ConvFamily kConvWino = {CF_WINO, wino_num_configs, wino_config_name, wino_config_valid, wino_grid_blocks, wino_k_tiles,
+                              wino_launch, CONV_READS_FP32 | CONV_NET_FP32 | CONV_SPLITK_REDUCE};
+#endif
 
 size_t wino_weight_floats(int Cin, int Cout) { return (size_t)16 * conv_npad(Cout) * Cin; }
 
