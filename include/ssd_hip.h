@@ -167,6 +167,53 @@ int ssd_match_encode(const float* priors_dev, const float* gt_boxes_dev,
                      int* label_idx_out_dev, int* match_idx_out_dev, float* onehot_out_dev,
                      void* stream);
 
+/* ---- target assignment behind a strategy (csrc/ssd_match.hip) ------------------------
+ * Inputs and the four outputs are ssd_match_encode's.  A ground-truth row is VALID iff its label is > 0 (padding rows:
+ * box 0, label -1, anywhere among the rows).  IoU bits are ssd_iou_map's; a NaN IoU never wins a maximum and never passes
+ * a comparison.  A background prior holds label_idx 0, the one-hot of class 0 and the encoding of the all-zero box divided
+ * by the variances; a positive prior of box g holds label[g], match_idx g and the deltas of box g.
+ *
+ * SSD_MATCH_MAX_IOU: ssd_match_encode itself -- the same launch, the same bits (iou_threshold is its iou_thr).
+ *
+ * SSD_MATCH_BIPARTITE (SSD paper section 2.2, Caffe MultiBoxLoss), per image: U = the valid boxes, T = {} taken priors.
+ *   repeat: among the pairs (i, g), g in U, i not in T, IoU(i, g) > 0, take the one with the largest IoU (ties: the
+ *   smaller g, then the smaller i); forced[i] = g, g leaves U, i joins T; stop when no such pair is left.
+ *   A forced prior is positive for its box whatever its IoU.  Every other prior follows ssd_match_encode's rule over all G
+ *   columns: first maximum, positive iff strictly > iou_threshold, match_idx = that arg-max.
+ *
+ * SSD_MATCH_ATSS (Zhang et al., CVPR 2020), per image: priors [level_start[l], level_start[l+1]) are level l,
+ *   level_start[0] == 0, level_start[n_levels] == N, non-decreasing.  Centres, priors and boxes alike, in fp32:
+ *   cy = (y1 + y2) * 0.5f, cx = (x1 + x2) * 0.5f; d2 = fl(fl(dy * dy) + fl(dx * dx)), nothing fused.  For each valid box g:
+ *   per level the candidates are the min(topk, level size) priors with the smallest (d2, i), lexicographic, a NaN d2 last;
+ *   the list is ordered by level, then rank, n entries; with v_k the candidates' IoUs widened to double,
+ *   mean = (sum v_k) / n, var = (sum (v_k - mean)^2) / (n - 1) (0 when n == 1), both sums in list order, in double, nothing
+ *   fused; thr = mean + sqrt(var); candidate k is positive for g iff v_k >= thr and y1 < cy < y2 and x1 < cx < x2 (its own
+ *   centre, the box's corners).  A prior positive for several boxes takes the one with the largest IoU (ties: the smaller g).
+ *   Everything else is background with match_idx -1.  iou_threshold is unused; topk in 1..SSD_MATCH_MAX_TOPK.
+ *
+ * workspace_dev: ssd_match_encode_cfg_workspace_bytes(B, N, G, cfg) bytes, 16-byte aligned (0 bytes: may be NULL); the
+ * query answers 0 for a config the entry would refuse.  SSD_E_INVALID, nothing launched: a NULL or unknown config, ATSS
+ * with topk or level_start out of range, NULL pointers, a workspace that is too small.  SSD_E_UNSUPPORTED: G beyond
+ * ssd_match_encode's LDS limit, B > 65535.  B == 0 or N == 0 launches nothing.  Results do not depend on scheduling: ownership is
+ * resolved by integer maxima only. */
+#define SSD_MATCH_MAX_IOU 0   /* the reference rule; what ssd_match_encode does */
+#define SSD_MATCH_BIPARTITE 1 /* SSD paper: bipartite stage, then the reference rule */
+#define SSD_MATCH_ATSS 2      /* adaptive training sample selection */
+#define SSD_MATCH_MAX_LEVELS 8
+#define SSD_MATCH_MAX_TOPK 64
+typedef struct ssd_match_config {
+    int strategy;           /* SSD_MATCH_* */
+    float iou_threshold;    /* MAX_IOU, BIPARTITE */
+    int topk;               /* ATSS */
+    int n_levels;           /* ATSS: 1..SSD_MATCH_MAX_LEVELS */
+    int level_start[SSD_MATCH_MAX_LEVELS + 1];
+} ssd_match_config;
+size_t ssd_match_encode_cfg_workspace_bytes(int B, int N, int G, const ssd_match_config* cfg);
+int ssd_match_encode_cfg(const float* priors_dev, const float* gt_boxes_dev, const int* gt_labels_dev, const float* var,
+                         const ssd_match_config* cfg, int B, int N, int G, int L, float* deltas_out_dev,
+                         int* label_idx_out_dev, int* match_idx_out_dev, float* onehot_out_dev, void* workspace_dev,
+                         size_t workspace_bytes, void* stream);
+
 /* ---- detection scoring: utils/eval_utils.py:20-50 (N2), the per-image part of update_stats ----
  * det_boxes [B,T,4], det_labels [B,T] (float class id, 0 = padding row), det_scores [B,T],
  * gt_boxes [B,G,4], gt_labels [B,G] int32 (-1 = padding), all device.  Per image: best IoU and

@@ -6,6 +6,7 @@
 // Built with -ffp-contract=off: every product and sum is rounded separately, exactly as
 // the reference's chain of elementwise TF ops does (utils/bbox_utils.py), so that anchor
 // indices kept by NMS and match indices are bit-exact against the oracle.
+#include "box_math.h"
 #include "common.h"
 
 #include <algorithm>
@@ -44,17 +45,6 @@ __device__ __forceinline__ float nms_iou(const float4 a, const float4 b) {
     const float ix = fmaxf(fminf(xmax_i, xmax_j) - fmaxf(xmin_i, xmin_j), 0.0f);
     const float inter = iy * ix;
     return ((inter) / (area_i + area_j - inter));
-}
-
-// utils/bbox_utils.py:44-59 for one (box, gt) pair.
-__device__ __forceinline__ float pair_iou(const float4 p, const float4 g) {
-    const float garea = (g.z - g.x) * (g.w - g.y);
-    const float parea = (p.z - p.x) * (p.w - p.y);
-    const float x_top = fmaxf(p.y, g.y), y_top = fmaxf(p.x, g.x);
-    const float x_bot = fminf(p.w, g.w), y_bot = fminf(p.z, g.z);
-    const float inter = fmaxf(x_bot - x_top, 0.0f) * fmaxf(y_bot - y_top, 0.0f);
-    const float uni = parea + garea - inter;
-    return ((inter) / (uni));
 }
 
 // Sort keys: ascending u64 order == (score desc, anchor asc[, class asc]).
@@ -593,22 +583,7 @@ __global__ void iou_map_kernel(const float4* __restrict__ boxes, const int boxes
     }
 }
 
-// ------------------------------------------------------------------ encode (M3)
-__device__ __forceinline__ float4 encode_box(const float4 p, const float4 g) {
-    // utils/bbox_utils.py:96-113
-    float bw = p.w - p.y, bh = p.z - p.x;
-    const float bcx = p.y + 0.5f * bw, bcy = p.x + 0.5f * bh;
-    const float gw = g.w - g.y, gh = g.z - g.x;
-    const float gcx = g.y + 0.5f * gw, gcy = g.x + 0.5f * gh;
-    if (bw == 0.0f) bw = 1e-3f;
-    if (bh == 0.0f) bh = 1e-3f;
-    const float dx = gw == 0.0f ? 0.0f : ((gcx - bcx) / (bw));
-    const float dy = gh == 0.0f ? 0.0f : ((gcy - bcy) / (bh));
-    const float dw = gw == 0.0f ? 0.0f : logf(((gw) / (bw)));
-    const float dh = gh == 0.0f ? 0.0f : logf(((gh) / (bh)));
-    return make_float4(dy, dx, dh, dw);
-}
-
+// ------------------------------------------------------------------ encode (M3): encode_box, box_math.h
 __global__ void encode_kernel(const float4* __restrict__ bboxes, const float4* __restrict__ gt,
                               const int N, const long total, float4* __restrict__ out) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total;

@@ -111,6 +111,17 @@ class NmsConfig(ctypes.Structure):
         (n, ctypes.c_float) for n in ("iou_threshold", "score_threshold", "sigma")]
 
 
+MATCH_MAX_LEVELS, MATCH_MAX_TOPK = 8, 64        # SSD_MATCH_MAX_*
+
+
+class MatchConfig(ctypes.Structure):
+    """struct ssd_match_config (include/ssd_hip.h): the target-assignment strategy of ``ssd_match_encode_cfg``."""
+    _fields_ = [("strategy", ctypes.c_int), ("iou_threshold", ctypes.c_float), ("topk", ctypes.c_int), ("n_levels", ctypes.c_int),
+                ("level_start", ctypes.c_int * (MATCH_MAX_LEVELS + 1))]
+
+
+MATCH_MAX_IOU, MATCH_BIPARTITE, MATCH_ATSS = 0, 1, 2        # SSD_MATCH_*
+MATCH_STRATEGIES = {"max_iou": MATCH_MAX_IOU, "bipartite": MATCH_BIPARTITE, "atss": MATCH_ATSS}
 JPEG_COEFFICIENTS, JPEG_RAW = 0, 1
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
 MOBILENET_V2, VGG16 = 0, 1
@@ -148,6 +159,9 @@ _SIGNATURES = {
     "ssd_encode_deltas": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]),
     "ssd_match_encode": (ctypes.c_int, [vp, vp, vp, c_float_p, ctypes.c_float] + [ctypes.c_int] * 4 +
                          [vp, vp, vp, vp, vp]),
+    "ssd_match_encode_cfg_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3 + [ctypes.POINTER(MatchConfig)]),
+    "ssd_match_encode_cfg": (ctypes.c_int, [vp, vp, vp, c_float_p, ctypes.POINTER(MatchConfig)] + [ctypes.c_int] * 4 +
+                             [vp, vp, vp, vp, vp, ctypes.c_size_t, vp]),
     "ssd_eval_match": (ctypes.c_int, [vp] * 5 + [ctypes.c_int] * 3 + [ctypes.c_float] + [vp] * 6),
     "ssd_eval_match_protocol": (ctypes.c_int, [vp] * 6 + [ctypes.c_int] * 4 + [c_float_p, ctypes.c_int] + [vp] * 6),
     "ssd_preprocess": (ctypes.c_int, [vp] + [ctypes.c_int] * 6 + [vp, vp]),
@@ -395,6 +409,29 @@ def nms_config(method="hard", class_agnostic=False, max_per_class=200, max_total
         sigma = 0.0             # unused by this method: keep the graph key (which holds every field) comparable
     return NmsConfig(NMS_METHODS[method], int(bool(class_agnostic)), int(max_per_class), int(max_total), int(bool(clip_boxes)),
                      iou_threshold, float(score_threshold), sigma)
+
+
+def match_config(strategy="max_iou", iou_threshold=0.5, topk=9, level_start=None):
+    """A validated ``MatchConfig``: ``strategy`` "max_iou" | "bipartite" | "atss"; for "atss" ``topk`` in 1..64 and
+    ``level_start`` = the first prior of each pyramid level and, last, the number of priors (2..9 non-decreasing ints from 0).
+    ValueError otherwise -- the checks the library repeats (it also holds ``level_start[-1]`` against its N)."""
+    if strategy not in MATCH_STRATEGIES:
+        raise ValueError('match_strategy must be "max_iou", "bipartite" or "atss", got %r' % (strategy,))
+    cfg = MatchConfig(MATCH_STRATEGIES[strategy], float(iou_threshold), int(topk), 0)
+    if strategy != "atss":
+        return cfg
+    if not 1 <= int(topk) <= MATCH_MAX_TOPK:
+        raise ValueError("match_topk must lie in 1..%d, got %r" % (MATCH_MAX_TOPK, topk))
+    starts = [int(s) for s in (level_start if level_start is not None else ())]
+    if not 2 <= len(starts) <= MATCH_MAX_LEVELS + 1:
+        raise ValueError("level_start must hold 2..%d entries (1..%d levels), got %r" % (MATCH_MAX_LEVELS + 1, MATCH_MAX_LEVELS,
+                                                                                         level_start))
+    if starts[0] != 0 or any(b < a for a, b in zip(starts, starts[1:])):
+        raise ValueError("level_start must begin at 0 and never decrease, got %r" % (starts,))
+    cfg.n_levels = len(starts) - 1
+    for l, s in enumerate(starts):
+        cfg.level_start[l] = s
+    return cfg
 
 
 def nms_is_default(method, class_agnostic):

@@ -25,7 +25,9 @@ Loss: ``SSD_TRAINER_LOSS`` (``hard`` | ``focal``), ``SSD_TRAINER_FOCAL_ALPHA`` (
 (``loss_from_env``); unset: the reference's hard-negative mining.  ``SSD_TRAINER_FOCAL_PRIOR`` (off by default) = pi
 writes the prior-probability bias into the label heads after ``init_model`` (``model.set_conf_prior``).
 ``SSD_TRAINER_LOC_LOSS`` (``huber`` | ``iou`` | ``giou`` | ``diou`` | ``ciou``, ``loc_loss_from_env``) puts an IoU-family loss on
-the decoded boxes in place of the Huber localisation term of either; unset: the reference's Huber term."""
+the decoded boxes in place of the Huber localisation term of either; unset: the reference's Huber term.
+Target assignment: ``SSD_TRAINER_MATCH`` (``max_iou`` | ``bipartite`` | ``atss``) and ``SSD_TRAINER_MATCH_TOPK`` (atss, default 9)
+(``match_from_env``); unset: the reference's threshold rule."""
 import json
 import os
 import sys
@@ -36,6 +38,7 @@ if _HERE not in sys.path:
     sys.path.insert(0, _HERE)
 
 import parallel  # noqa: E402
+import ssd_hip  # noqa: E402
 from ssd_loss import CustomLoss, FocalLoss, IoULocLoss  # noqa: E402
 from utils import bbox_utils, data_utils, io_utils, train_utils, voc_utils  # noqa: E402
 
@@ -168,6 +171,31 @@ def loc_loss_from_env(base, prior_boxes, hyper_params):
     raise ValueError("SSD_TRAINER_LOC_LOSS must be 'huber', 'iou', 'giou', 'diou' or 'ciou', got %r" % mode)
 
 
+def match_from_env(hyper_params):
+    """``SSD_TRAINER_MATCH`` = ``max_iou`` (default: the reference's rule, ``hyper_params`` untouched) | ``bipartite`` |
+    ``atss`` (``match_strategy``); ``SSD_TRAINER_MATCH_TOPK`` (atss only, 1..64, default 9: ``match_topk``).  Returns the
+    hyper-parameters ``train_utils.calculate_actual_outputs`` is to read: a COPY with those keys for another strategy than the
+    default (``hyper_params`` is the module-level table of ``train_utils``, which must not gain keys), ``hyper_params`` itself
+    otherwise.  ValueError for another strategy, for a top-k that does not parse or lies outside its range, and for a top-k
+    set beside a strategy that ignores it."""
+    env = os.environ
+    kind = env.get("SSD_TRAINER_MATCH", "").strip().lower() or "max_iou"
+    topk = env.get("SSD_TRAINER_MATCH_TOPK", "").strip()
+    if kind not in ssd_hip.MATCH_STRATEGIES:
+        raise ValueError("SSD_TRAINER_MATCH must be 'max_iou', 'bipartite' or 'atss', got %r" % kind)
+    if kind != "atss":
+        if topk:
+            raise ValueError("SSD_TRAINER_MATCH_TOPK set, but SSD_TRAINER_MATCH is not 'atss'")
+        return hyper_params if kind == "max_iou" else dict(hyper_params, match_strategy=kind)
+    try:
+        k = int(topk or 9)
+    except ValueError:
+        k = 0
+    if not 1 <= k <= ssd_hip.MATCH_MAX_TOPK:
+        raise ValueError("SSD_TRAINER_MATCH_TOPK must be an integer in 1..%d, got %r" % (ssd_hip.MATCH_MAX_TOPK, topk))
+    return dict(hyper_params, match_strategy=kind, match_topk=k)
+
+
 def main(argv=None):
     args = io_utils.handle_args(argv)
     if args.handle_gpu:
@@ -220,6 +248,11 @@ def main(argv=None):
         val_data = list(data_utils.synthetic_dataset(step_size_val * batch_size, batch_size, img_size, len(labels),
                                                      seed=777 + 1000 * rank))
 
+    target_params = match_from_env(hyper_params)
+    if target_params is not hyper_params and rank == 0:
+        print("target assignment: %s%s" % (target_params["match_strategy"],
+                                           " (top-k %d)" % target_params["match_topk"] if "match_topk" in target_params else ""),
+              flush=True)
     ssd_model = get_model(hyper_params, max_batch=batch_size)
     prior_boxes = bbox_utils.generate_prior_boxes(hyper_params["feature_map_shapes"], hyper_params["aspect_ratios"])
     ssd_custom_losses = loc_loss_from_env(loss_from_env(hyper_params), prior_boxes, hyper_params)
@@ -257,8 +290,8 @@ def main(argv=None):
         else:
             augmentation.seed(4242 + rank)
             train_data = augmentation.augmented(train_data)
-    ssd_train_feed = train_utils.generator(train_data, prior_boxes, hyper_params)
-    ssd_val_feed = train_utils.generator(val_data, prior_boxes, hyper_params)
+    ssd_train_feed = train_utils.generator(train_data, prior_boxes, target_params)
+    ssd_val_feed = train_utils.generator(val_data, prior_boxes, target_params)
 
     return fit(ssd_model, ssd_train_feed, step_size_train, ssd_val_feed, step_size_val, epochs, ssd_model_path,
                ssd_log_path, rank)

@@ -53,8 +53,31 @@ def generator(dataset, prior_boxes, hyper_params):
             yield img, calculate_actual_outputs(prior_boxes, gt_boxes, gt_labels, hyper_params)
 
 
+def match_config_from(hyper_params, total_priors):
+    """The ``MatchConfig`` of ``hyper_params``' optional keys ``match_strategy`` ("max_iou" | "bipartite" | "atss") and
+    ``match_topk`` (ATSS, default 9), or None when neither is there: the reference's rule through ``ssd_match_encode``.
+    ATSS's pyramid levels are the feature maps': ``fm * fm * (len(ratios) + 1)`` priors each, which must add up to
+    ``total_priors`` (ValueError otherwise)."""
+    if "match_strategy" not in hyper_params and "match_topk" not in hyper_params:
+        return None
+    strategy = hyper_params.get("match_strategy", "max_iou")
+    level_start = None
+    if strategy == "atss":
+        level_start = [0]
+        for fm, ratios in zip(hyper_params["feature_map_shapes"], hyper_params["aspect_ratios"]):
+            level_start.append(level_start[-1] + int(fm) * int(fm) * (len(ratios) + 1))
+        if level_start[-1] != total_priors:
+            raise ValueError("feature_map_shapes and aspect_ratios describe %d priors, prior_boxes holds %d" % (
+                level_start[-1], total_priors))
+    return _h.match_config(strategy, float(hyper_params["iou_threshold"]), hyper_params.get("match_topk", 9), level_start)
+
+
 def calculate_actual_outputs(prior_boxes, gt_boxes, gt_labels, hyper_params, return_indices=False):
     """reference utils/train_utils.py:90-127 -> (bbox_deltas [B,N,4], bbox_labels [B,N,L]).
+
+    ``hyper_params["match_strategy"]`` = "bipartite" (the SSD paper's best-prior-per-box stage in front of the reference's
+    rule) or "atss" (with ``hyper_params["match_topk"]``, default 9) selects another assignment (``ssd_match_encode_cfg``);
+    without these keys the reference's rule runs as before.
 
     With ``return_indices`` also returns the int32 label index and matched-GT index per
     prior (bit-exact quantities of the parity contract)."""
@@ -73,10 +96,19 @@ def calculate_actual_outputs(prior_boxes, gt_boxes, gt_labels, hyper_params, ret
     labels = torch.empty((B, N, total_labels), dtype=torch.float32, device=dev)
     lab_idx = torch.empty((B, N), dtype=torch.int32, device=dev)
     match_idx = torch.empty((B, N), dtype=torch.int32, device=dev)
-    _h.check(_h.lib().ssd_match_encode(_h.ptr(p), _h.ptr(g), _h.ptr(gl), var_p, iou_threshold,
-                                       B, N, G, total_labels, _h.ptr(deltas), _h.ptr(lab_idx),
-                                       _h.ptr(match_idx), _h.ptr(labels), _h.stream()),
-             "calculate_actual_outputs")
+    cfg = match_config_from(hyper_params, N)
+    if cfg is None:
+        _h.check(_h.lib().ssd_match_encode(_h.ptr(p), _h.ptr(g), _h.ptr(gl), var_p, iou_threshold,
+                                           B, N, G, total_labels, _h.ptr(deltas), _h.ptr(lab_idx),
+                                           _h.ptr(match_idx), _h.ptr(labels), _h.stream()),
+                 "calculate_actual_outputs")
+    else:
+        nbytes = _h.lib().ssd_match_encode_cfg_workspace_bytes(B, N, G, cfg)
+        ws = _h.workspace(nbytes) if nbytes else None
+        _h.check(_h.lib().ssd_match_encode_cfg(_h.ptr(p), _h.ptr(g), _h.ptr(gl), var_p, cfg, B, N, G, total_labels,
+                                               _h.ptr(deltas), _h.ptr(lab_idx), _h.ptr(match_idx), _h.ptr(labels),
+                                               _h.ptr(ws), nbytes, _h.stream()),
+                 "calculate_actual_outputs")
     if return_indices:
         return deltas, labels, lab_idx, match_idx
     return deltas, labels
