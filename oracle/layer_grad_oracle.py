@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE ONLY -- teacher-forced float64 backward of ONE layer at a time.
+"""TEST INFRASTRUCTURE ONLY -- teacher-forced float64 backward (and forward) of ONE layer at a time.
 
 The end-to-end gradient checks (tests/test_train.py) let ~50 layers of fp32 error accumulate and can
 only bound a tensor's error against its largest entry.  Here every layer's backward is recomputed in
@@ -31,6 +31,20 @@ order and move by a few tenths from host to host):
     dense 3x3 s1 2.4   dense 3x3 s2 2.7   dense 3x3 dilated 3.0   1x1 1.4   depthwise s1 1.2
     depthwise s2 correct_pad 2.0   BN + ReLU6 1.1   BN + residual 1.2   bias + ReLU 2.0
     max-pool 2/2 0.0   max-pool 3/1 SAME 1.7   L2-norm 3.8
+
+The FORWARD of the same layers is held the same way (``layer_forward`` / ``check_forward_graph``: each output from the
+other implementation's own input tensor; a BatchNorm layer's ``out`` from its own ``pre`` / ``mean`` / ``var``, so that
+neither the conv's nor the statistics' error reaches it).  The fp32 restatement's worst E there
+(tests/test_layer_forward_cpu.py, same conditions), ``pre`` / ``out``:
+
+    dense 3x3 s1 - / 2.1   dense 3x3 s2 - / 1.7   dense 3x3 dilated - / 1.6   1x1 + BN 2.3 / 2.3
+    depthwise s1 + BN + ReLU6 2.3 / 1.6   depthwise s2 correct_pad 2.0 / 2.2   1x1 + BN + ReLU6 2.5 / 2.4
+    1x1 + BN + residual 2.8 / 1.9   1x1 bias + ReLU - / 2.1   frozen BN + ReLU6 + residual - / 1.6
+    max-pools 0.0 (bit for bit)   L2-norm 3.3   head deltas 1.1, probs 0.6
+and of six subtly wrong forwards built from the reference formulas alone (each has to exceed 4 x E_BAR = 64):
+    tap skipped at the last output column: pre 4.5e6      both operands cut to 16 significand bits: pre 291 (K = 144),
+    deltas 282, probs 101 (K = 288)      istd without eps: out 1.4e4      residual added before the activation: out 1.4e7
+    ReLU in place of ReLU6: out 8.3e6      head halves swapped at the split column: probs 3.6e9, deltas 2.9e7
 
 Layouts: activations NHWC, kernels HWIO, depthwise kernels [3,3,C,1] (Keras).  Only tests/ imports
 this module."""
@@ -311,6 +325,121 @@ def layer_backward(spec, t, dtype=torch.float64, absolute=False, round_dx=None):
     return r
 
 
+# ------------------------------------------------------------------ one layer, forward
+def conv_forward(x, w, stride, dil, pads, round_ops=None):
+    """conv2d(x NHWC, w HWIO): per tap one GEMM.  round_ops (e.g. ``bf16_rne``) rounds BOTH operands once before they
+    are multiplied (the bf16 mode's rule, as conv_backward(round_dx=...) states it for the data gradient)."""
+    B, H, W, Cin = x.shape
+    kh, kw, _, Cout = w.shape
+    pt, pb, pl, pr = pads
+    if round_ops:
+        x, w = round_ops(x).to(x.dtype), round_ops(w).to(w.dtype)
+    xp = torch.nn.functional.pad(x, (0, 0, pl, pr, pt, pb))
+    Ho = (H + pt + pb - ((kh - 1) * dil + 1)) // stride + 1
+    Wo = (W + pl + pr - ((kw - 1) * dil + 1)) // stride + 1
+    out = torch.zeros((B * Ho * Wo, Cout), dtype=x.dtype)
+    for ky in range(kh):
+        for kx in range(kw):
+            ys, xs = ky * dil, kx * dil
+            sl = (slice(None), slice(ys, ys + (Ho - 1) * stride + 1, stride), slice(xs, xs + (Wo - 1) * stride + 1, stride))
+            out += xp[sl].reshape(-1, Cin) @ w[ky, kx]
+    return out.reshape(B, Ho, Wo, Cout)
+
+
+def depthwise_forward(x, w, stride, pads):
+    """The 3x3 depthwise conv (w [3,3,C,1])."""
+    B, H, W, C = x.shape
+    pt, pb, pl, pr = pads
+    xp = torch.nn.functional.pad(x, (0, 0, pl, pr, pt, pb))
+    Ho, Wo = (H + pt + pb - 3) // stride + 1, (W + pl + pr - 3) // stride + 1
+    out = torch.zeros((B, Ho, Wo, C), dtype=x.dtype)
+    for ky in range(3):
+        for kx in range(3):
+            out += xp[:, ky:ky + (Ho - 1) * stride + 1:stride, kx:kx + (Wo - 1) * stride + 1:stride] * w[ky, kx, :, 0]
+    return out
+
+
+def _act(z, act):
+    return z.clamp(0.0, 6.0) if act == "relu6" else (z.clamp(min=0.0) if act == "relu" else z)
+
+
+def softmax_forward(z, a_z, absolute=False):
+    """softmax over the last axis of the logits z and, with ``absolute``, its A to first order in the logits' own A:
+    p_i = e_i / S with e_j = exp(z_j - m), m = max_j z_j.  dp_i = p_i (dz_i - sum_j p_j dz_j); besides the logit's A_z the
+    exponent z_j - m is evaluated with a relative error on d_j = |z_j - m| (the subtraction and the exp's argument
+    reduction), and the exp, the sum and the division add a unit each of the result:
+        A_p,i = p_i (A_z,i + sum_j p_j A_z,j + d_i + sum_j p_j d_j + 1)."""
+    m = z.max(-1, keepdim=True).values
+    e = torch.exp(z - m)
+    p = e / e.sum(-1, keepdim=True)
+    if not absolute:
+        return p
+    d = (z - m).abs()
+    return p * (a_z + (p * a_z).sum(-1, keepdim=True) + d + (p * d).sum(-1, keepdim=True) + 1.0)
+
+
+def layer_forward(spec, t, dtype=torch.float64, absolute=False, round_ops=None):
+    """Forward of one layer from the other implementation's own tensors.  ``t``: x (input activation) and, by kind, w,
+    gamma, beta, bias, res (the residual tensor); BatchNorm on batch statistics: pre / mean / var AS THE DEVICE HOLDS THEM
+    (``out`` is evaluated from those, so that no error of the conv or of the statistics reaches it); a frozen BatchNorm:
+    moving_mean / moving_var instead (no pre: the conv epilogue applies the folded scale / shift); head: w_label / b_label /
+    w_box / b_box.  Returns {key: tensor}:
+      "pre"             BatchNorm layers on batch statistics: conv(x, w);                A = conv(|x|, |w|)
+      "out"             ... act(gamma (pre - mean) istd + beta) + res, istd = rsqrt(var + eps);
+                                                    A = |gamma| (|pre| + |mean|) istd + |beta| + |res|
+                        (covers the subtract-first form and the folded scale / shift form alike)
+                        frozen: act(fscale conv + fshift) + res, fscale = gamma rsqrt(moving_var + eps),
+                        fshift = beta - moving_mean fscale;  A = |fscale| conv(|x|, |w|) + |beta| + |moving_mean fscale| + |res|
+                        bias layers: act(conv + bias);       A = conv(|x|, |w|) + |bias|
+                        pool: the window maximum, A = 0 (bit for bit);  L2 norm: gamma x rsqrt(max(sum x^2, 1e-12)),
+                        A = |gamma x| rs
+      "deltas", "probs" heads: conv(x, w_box) + b_box [B,H,W,a*4]; softmax over L of conv(x, w_label) + b_label
+                        [B,H,W,a*L] (A: softmax_forward)
+    absolute=True returns A.  round_ops: see conv_forward (dense convs only; the depthwise conv is fp32 in both modes)."""
+    ab = (lambda v: v.abs()) if absolute else (lambda v: v)
+    kind = spec["kind"]
+    xs = _t(t["x"], dtype)
+    if kind == "pool":
+        cells, _, _ = pool_windows(xs, spec)
+        mx = cells.max(0).values
+        return {"out": torch.zeros_like(mx) if absolute else mx}
+    if kind == "l2norm":
+        rs = torch.rsqrt(torch.clamp((xs * xs).sum(-1, keepdim=True), min=1e-12))
+        return {"out": ab(_t(t["gamma"], dtype) * xs) * rs}
+    pads = _pads(spec, xs.shape[1], xs.shape[2])
+    if kind == "head":
+        L = spec["labels"]
+        lin = lambda x, w, b: conv_forward(x, w, 1, 1, pads, round_ops) + b
+        r = {"deltas": lin(ab(xs), ab(_t(t["w_box"], dtype)), ab(_t(t["b_box"], dtype)))}
+        z = lin(xs, _t(t["w_label"], dtype), _t(t["b_label"], dtype))
+        a_z = lin(xs.abs(), _t(t["w_label"], dtype).abs(), _t(t["b_label"], dtype).abs()) if absolute else z
+        sh = z.shape
+        r["probs"] = softmax_forward(z.reshape(sh[:3] + (-1, L)), a_z.reshape(sh[:3] + (-1, L)), absolute).reshape(sh)
+        return r
+    x, w = ab(xs), ab(_t(t["w"], dtype))
+    conv = depthwise_forward(x, w, spec["stride"], pads) if kind == "dw" else \
+        conv_forward(x, w, spec["stride"], spec["dil"], pads, round_ops)
+    r = {}
+    if spec["bn"] and "moving_var" not in t:
+        r["pre"] = conv
+        gamma, beta = ab(_t(t["gamma"], dtype)), ab(_t(t["beta"], dtype))
+        istd = torch.rsqrt(_t(t["var"], dtype) + BN_EPS)
+        pre, mean = ab(_t(t["pre"], dtype)), ab(_t(t["mean"], dtype))
+        z = gamma * ((pre + mean) if absolute else (pre - mean)) * istd + beta
+    elif spec["bn"]:
+        fscale = _t(t["gamma"], dtype) * torch.rsqrt(_t(t["moving_var"], dtype) + BN_EPS)
+        shift_mean = _t(t["moving_mean"], dtype) * fscale
+        z = fscale.abs() * conv + _t(t["beta"], dtype).abs() + shift_mean.abs() if absolute else \
+            fscale * conv + (_t(t["beta"], dtype) - shift_mean)
+    else:
+        z = conv + ab(_t(t["bias"], dtype)) if spec["bias"] else conv
+    out = z if absolute else _act(z, spec["act"])
+    if spec["res"]:
+        out = out + ab(_t(t["res"], dtype))
+    r["out"] = out
+    return r
+
+
 def batch_stats(pre, dtype=torch.float64):
     """mean, biased variance over (B,H,W) and their A: the two-pass formulas mean = sum x / M, var = sum (x - mean)^2 / M
     with absolute values and the subtraction as an addition -- A_mean = sum |x| / M, A_var = sum (|x| + |mean|)^2 / M."""
@@ -484,3 +613,67 @@ def check_graph(specs, fetch, weights, grads, hyper_params, B, report, moving_af
             progress(s["name"])
     assert only is not None or not contrib, "tensors with consumers that never ran: %s" % sorted(contrib)
     return {"layers": n_layers, "pool_excluded": pool_tied / pool_cells if pool_cells else 0.0}
+
+
+def check_forward_graph(specs, fetch, weights, hyper_params, B, report, only=None, frozen=(), round_ops=None):
+    """Hold the training FORWARD of another implementation to the float64 layer oracle: every layer's outputs
+    (layer_forward) recomputed from the implementation's own input tensor ``fetch(s["tin"])`` and compared through
+    ``report.add``.  ``fetch`` as in check_graph, plus "probs" [B,N,L] and "deltas" [B,N,4] (a head's slices are taken at
+    the level's anchor offset, as check_graph slices the head gradients).  frozen: names of the layers whose BatchNorm is
+    frozen -- folded on the moving statistics of ``weights``; their "pre:" / "mean:" / "var:" are NOT fetched (a frozen
+    layer never writes them).  round_ops: the bf16 mode -- a dense conv's outputs are admitted in two forms, both operands
+    rounded once or neither (the same conv on an fp32 tile); one launch writes all outputs of a layer, so ONE form must
+    meet the bar for all of them (the form with the smaller worst E is the one reported).
+    Returns {"layers": n, "clamps": {ReLU6 layer: (share of sixes, share of zeros) of the ORACLE's out}}."""
+    fm = hyper_params["feature_map_shapes"]
+    lvl_off = np.cumsum([0] + [f * f * (len(a) + 1) for f, a in zip(fm, hyper_params["aspect_ratios"])])
+    n_layers, clamps = 0, {}
+    for s in specs:
+        if only is not None and s["name"] not in only:
+            continue
+        kind = layer_kind(s)
+        t = {"x": fetch(s["tin"])}
+        got = {}
+        if s["kind"] == "head":
+            i, L = s["level"], s["labels"]
+            H, W = t["x"].shape[1], t["x"].shape[2]
+            lo, hi = int(lvl_off[i]), int(lvl_off[i + 1])
+            got["probs"] = fetch("probs")[:, lo:hi].reshape(B, H, W, s["anchors"] * L)
+            got["deltas"] = fetch("deltas")[:, lo:hi].reshape(B, H, W, s["anchors"] * 4)
+            for part, key in (("label", "label"), ("boxes", "box")):
+                t["w_" + key] = weights["%d_conv_%s_output/kernel" % (i + 1, part)]
+                t["b_" + key] = weights["%d_conv_%s_output/bias" % (i + 1, part)]
+        elif s["kind"] == "l2norm":
+            t["gamma"] = weights["l2_normalization/scale"]
+            got["out"] = fetch(s["tout"])
+        elif s["kind"] == "pool":
+            got["out"] = fetch(s["tout"])
+        else:
+            t["w"] = weights[s["name"] + ("/depthwise_kernel" if s["kind"] == "dw" else "/kernel")]
+            got["out"] = fetch(s["tout"])
+            if s["res"]:
+                t["res"] = fetch(s["res"])
+            if s["bias"]:
+                t["bias"] = weights[s["name"] + "/bias"]
+            if s["bn"]:
+                t["gamma"], t["beta"] = weights[s["bn"] + "/gamma"], weights[s["bn"] + "/beta"]
+                if s["name"] in frozen:
+                    t["moving_mean"], t["moving_var"] = weights[s["bn"] + "/moving_mean"], weights[s["bn"] + "/moving_variance"]
+                else:
+                    for k in ("pre", "mean", "var"):
+                        t[k] = fetch(k + ":" + s["name"])
+                    got["pre"] = t["pre"]
+        forms = [(layer_forward(s, t, round_ops=round_ops), layer_forward(s, t, absolute=True, round_ops=round_ops))]
+        if round_ops and s["kind"] in ("conv", "head"):
+            forms.append((layer_forward(s, t), layer_forward(s, t, absolute=True)))
+            worst = [max(e_metric(got[k], ref[k], A[k])[0] for k in got) for ref, A in forms]
+            forms = [forms[int(np.argmin(worst))]]
+        ref, A = forms[0]
+        assert set(ref) == set(got), (s["name"], sorted(ref), sorted(got))
+        for k in sorted(got):
+            report.add(kind, s["name"], k + ":" + (s["tout"] or s["name"]), got[k], ref[k], A[k])
+        if s.get("act") == "relu6":
+            o = ref["out"]
+            clamps[s["name"]] = (float((o == 6).double().mean()), float((o == 0).double().mean()))
+        n_layers += 1
+    return {"layers": n_layers, "clamps": clamps}

@@ -95,6 +95,22 @@ def synthetic_weights(backbone, hp=None, seed=1, target_frac=0.05):
     return w
 
 
+def clamp_weights(backbone, hp=None):
+    """A copy of ``synthetic_weights`` with, for every BatchNorm that feeds a ReLU6, gamma x 3 and beta + 1.5.  Under BATCH
+    statistics z = gamma x^ + beta has the scale of gamma whatever the input is (a gain on the images is normalised
+    away), so with gamma 1 +- 0.1 a training forward almost never reaches 6: the upper clamp and the ``z < 6`` side of the
+    backward's pass-mask stay unreached.  With these every ReLU6 map of the training forward holds sixes AND zeros
+    (MobileNetV2, B = 2, images(seed=41): at least 6.4 % sixes and 30.8 % zeros per map)."""
+    from oracle import layer_grad_oracle as lg
+    hp = hp or hyper_params(backbone)
+    w = {k: v.copy() for k, v in synthetic_weights(backbone, hp).items()}
+    for spec in lg.layers(backbone, hp):
+        if spec.get("bn") and spec.get("act") == "relu6":
+            w[spec["bn"] + "/gamma"] *= np.float32(3.0)
+            w[spec["bn"] + "/beta"] += np.float32(1.5)
+    return w
+
+
 RESIDUAL_BLOCKS = (2, 4, 5, 7, 8, 9, 11, 12, 14, 15)       # MobileNetV2 blocks with `x + project(...)` (stride 1, Cin == Cout)
 
 

@@ -8,6 +8,8 @@ E = |got - ref64| / (u A): no GPU.
 * three subtly wrong fp32 restatements -- one tap skipped at the last output column, one 32-row slab of M
   left out of a weight gradient, a residual gradient overwritten instead of accumulated -- each score
   E > 100 on at least one element: the bar of 16 separates right from subtly wrong."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -115,9 +117,9 @@ def _make(case, seed=0):
     dout = rn(*out.shape)
     grads = dict(zip(leaves, torch.autograd.grad(out, list(leaves.values()), dout)))
     t = {"x": x.detach(), "dout": dout, "out": out.detach()}
-    for k in ("w", "gamma"):
+    for k, key in (("w", "w"), ("gamma", "gamma"), ("beta", "beta"), ("bias", "bias"), ("skip", "res")):   # (the last three: the forward's)
         if k in P:
-            t[k] = P[k].detach()
+            t[key] = P[k].detach()
     for k, v in inter.items():
         t[k] = v.detach()
     return spec, t, grads
@@ -227,9 +229,13 @@ def test_mutant_residual_overwritten():
 
 
 def test_graph_descriptions_cover_every_parameter():
-    """Every trainable parameter of both graphs belongs to exactly one layer of the description."""
+    """Every trainable parameter of both graphs belongs to exactly one layer of the description, and (the forward side)
+    every training activation the graph records -- what the step's fetch hook serves by name -- is the ``tout`` of exactly
+    one layer, read only after it was written."""
     import helpers
     from oracle import net_oracle as no
+    from oracle import torch_cpu_graph as tg
+    torch.set_num_threads(min(8, os.cpu_count() or 1))       # one full-size forward per graph, on zeros (_one_thread restores it)
     for backbone, n_layers in (("mobilenet_v2", 66), ("vgg16", 35)):
         hp = helpers.hyper_params(backbone)
         specs = lg.layers(backbone, hp)
@@ -249,3 +255,18 @@ def test_graph_descriptions_cover_every_parameter():
                     names |= {s["bn"] + "/gamma", s["bn"] + "/beta"}
         want = {n for n, _ in no.param_specs(backbone, hp) if not n.endswith(("moving_mean", "moving_variance"))}
         assert names == want
+        zeros = {n: torch.zeros(shape) for n, shape in no.param_specs(backbone, hp)}
+        acts = {}
+        with torch.no_grad():
+            no.forward(backbone, hp, zeros, np.zeros((1, 300, 300, 3), np.float32), acts, ops=tg.TorchOps)
+        recorded = {n for n, v in acts.items() if getattr(v, "ndim", 0) == 4}
+        touts = [s["tout"] for s in specs if s["tout"]]
+        assert len(touts) == len(set(touts)) and set(touts) == recorded, set(touts) ^ recorded
+        written = {"input"}
+        for s in specs:
+            assert s["tin"] in written and (not s.get("res") or s["res"] in written), s["name"]
+            written.add(s["tout"])
+        shapes = lg.tensor_shapes(specs, zeros)
+        for n in recorded:
+            v = acts[n]
+            assert tuple(v.shape[1:]) in (shapes[n], (shapes[n][2],) + shapes[n][:2]), n      # NHWC, or the torch graph's NCHW
