@@ -49,20 +49,35 @@ def expand_geometry(height, width, expansion_ratio, u_left, u_top):
     return int(final_h), int(final_w), int(pad_top), int(pad_left)
 
 
-def expand_image(img, gt_boxes, expansion_ratio, u_left, u_top):
-    """augmentation.py:123-151: the image on a larger canvas filled with its per-channel mean (``tf.nn.moments(img,
-    [0, 1])``; float64 mean here -- TF's fp32 reduction order is not reproducible), boxes renormalised to the canvas
-    (min_max = [-pad_top, -pad_left, pad_bottom + h, pad_right + w] / [h, w, h, w])."""
+def channel_mean(img):
+    """Per-channel mean over H, W (``tf.nn.moments(img, [0, 1])``): float64 sum, rounded ONCE to float32 -- TF's fp32
+    reduction order is not reproducible."""
+    return np.asarray(img, F32).astype(np.float64).mean((0, 1)).astype(F32)
+
+
+def expand_canvas(img, gt_boxes, final_h, final_w, pad_top, pad_left, fill=None):
+    """augmentation.py:141-151 with the integers of ``expand_geometry`` given: the image at (pad_top, pad_left) of a
+    final_h x final_w canvas filled with ``fill`` (None: its per-channel mean, ``channel_mean``; a caller that holds
+    another evaluation of that mean -- the device's -- passes it, so that the pixels can be compared bit for bit), boxes
+    renormalised to the canvas (min_max = [-pad_top, -pad_left, pad_bottom + h, pad_right + w] / [h, w, h, w])."""
     x = np.asarray(img, F32)
     h, w, _ = x.shape
-    fh, fw, pt, pl = expand_geometry(h, w, expansion_ratio, u_left, u_top)
-    mean = x.astype(np.float64).mean((0, 1)).astype(F32)
+    fh, fw, pt, pl = int(final_h), int(final_w), int(pad_top), int(pad_left)
+    mean = channel_mean(x) if fill is None else np.asarray(fill, F32).reshape(x.shape[2])
     canvas = np.empty((fh, fw, x.shape[2]), F32)
     canvas[...] = mean
     canvas[pt:pt + h, pl:pl + w] = x
     pad_bottom, pad_right = F32(fh) - (F32(h) + F32(pt)), F32(fw) - (F32(w) + F32(pl))
     min_max = np.array([-F32(pt), -F32(pl), pad_bottom + F32(h), pad_right + F32(w)], F32) / np.array([h, w, h, w], F32)
     return canvas, renormalize_bboxes_with_min_max(gt_boxes, min_max), mean
+
+
+def expand_image(img, gt_boxes, expansion_ratio, u_left, u_top, fill=None):
+    """augmentation.py:123-151: the image on a larger canvas filled with its per-channel mean (``tf.nn.moments(img,
+    [0, 1])``; float64 mean here, or the caller's ``fill``), boxes renormalised to the canvas."""
+    x = np.asarray(img, F32)
+    fh, fw, pt, pl = expand_geometry(x.shape[0], x.shape[1], expansion_ratio, u_left, u_top)
+    return expand_canvas(x, gt_boxes, fh, fw, pt, pl, fill)
 
 
 def resize_bilinear(img, out_h, out_w):
@@ -129,7 +144,7 @@ def adjust_brightness(img, delta):
 def adjust_contrast(img, factor, mean=None):
     """tf.image.random_contrast -> adjust_contrast: (x - mean_c) * factor + mean_c, mean per channel over H, W."""
     x = np.asarray(img, F32)
-    m = x.astype(np.float64).mean((0, 1)).astype(F32) if mean is None else np.asarray(mean, F32)
+    m = channel_mean(x) if mean is None else np.asarray(mean, F32)
     return ((x - m) * F32(factor) + m).astype(F32)
 
 
@@ -186,19 +201,52 @@ def adjust_saturation(img, factor):
     return hsv_to_rgb(np.stack([hsv[..., 0], s, hsv[..., 2]], -1))
 
 
-def color(img, brightness=None, contrast=None, hue=None, saturation=None):
+def color(img, brightness=None, contrast=None, hue=None, saturation=None, pivot=None):
     """The photometric half of ``apply`` in the reference's order (augmentation.py:17, 22-25): brightness, contrast, hue,
-    saturation, each applied when its draw is not None, then ``clip_by_value(img, 0, 1)``."""
+    saturation, each applied when its draw is not None, then ``clip_by_value(img, 0, 1)``.  ``pivot``: the per-channel
+    mean contrast turns on (None: ``channel_mean`` of the brightness-adjusted image)."""
     x = np.asarray(img, F32)
     if brightness is not None:
         x = adjust_brightness(x, brightness)
     if contrast is not None:
-        x = adjust_contrast(x, contrast)
+        x = adjust_contrast(x, contrast, pivot)
     if hue is not None:
         x = adjust_hue(x, hue)
     if saturation is not None:
         x = adjust_saturation(x, saturation)
     return np.clip(x, F32(0), F32(1)).astype(F32)
+
+
+def apply_plan(img, gt_boxes, plan, fill=None, pivot=None):
+    """``apply`` (augmentation.py:4-27) for ONE image with every decision given as the plan dict tf-ssd_amd/augmentation.py's
+    ``run_plans`` takes: ``canvas`` (final_h, final_w, pad_top, pad_left) integers, ``crop`` None or (begin_y, begin_x,
+    size_h, size_w) on the canvas, ``flip``, ``expand``, and the four colour draws or None.  The pieces above in the
+    reference's order -- mean-filled canvas, ``crop_and_resize`` back to H x W, ``flip_horizontally``, ``color`` with its
+    final clip -- and no arithmetic of its own.  ``fill`` / ``pivot``: expand's fill colour and contrast's pivot from the
+    caller (teacher forcing: a float64 sum in another order can round to the neighbouring float32, and the pixels are
+    bit-equal only from the same two means); None = ``channel_mean`` of the image / of the brightness-adjusted geometry
+    output.  Returns (pixels, boxes, fill_used, pivot_used); fill_used is None when the plan never reads a fill colour
+    (no expand), pivot_used None when it never reads a pivot (no contrast)."""
+    x = np.asarray(img, F32)
+    g = np.asarray(gt_boxes, F32)
+    H, W, _ = x.shape
+    fill_used = pivot_used = None
+    if plan["crop"] is not None:
+        if plan["expand"]:
+            x, g, fill_used = expand_canvas(x, g, *plan["canvas"], fill=fill)
+        elif tuple(int(v) for v in plan["canvas"]) != (H, W, 0, 0):
+            raise ValueError("a plan that does not expand keeps the image as its canvas")
+        crop = [int(v) for v in plan["crop"]]
+        x, g, _ = crop_and_resize(x, g, crop[:2], crop[2:], H, W)
+    elif plan["expand"]:
+        raise ValueError("expand without a crop is not a reference path (patch always crops)")
+    if plan["flip"]:
+        x, g = flip_horizontally(x, g)
+    if plan["contrast"] is not None:
+        lit = x if plan["brightness"] is None else adjust_brightness(x, plan["brightness"])
+        pivot_used = channel_mean(lit) if pivot is None else np.asarray(pivot, F32).reshape(3)
+    x = color(x, plan["brightness"], plan["contrast"], plan["hue"], plan["saturation"], pivot=pivot_used)
+    return x, g, fill_used, pivot_used
 
 
 def satisfies_overlap(window, gt_boxes, min_object_covered, height, width):

@@ -3,7 +3,8 @@ pieces: given the random draws, the HIP kernels behind ``tf-ssd_amd/augmentation
 ``ssd_augment_geometry``, ``ssd_augment_color``) against the NumPy restatement oracle/augment_oracle.py -- geometry BIT-EXACT
 (same per-op fp32 rounding: gather + bilinear interpolation + box arithmetic), colour within 1 ulp-scale tolerance (2e-6:
 the per-channel mean is a float64 reduction in another order), boxes bit-exact.  The sampler itself is random: its
-acceptance rule and its invariants are tested.  CPU tests pin the oracle to hand-computed known answers."""
+acceptance rule and its invariants are tested.  CPU tests pin the oracle to hand-computed known answers.
+The kernels run at B = 1 here; for B > 1 (per-image rows, fills, pivots, the grid-stride trip) see test_augment_batch_gpu.py."""
 import numpy as np
 import pytest
 

@@ -151,7 +151,8 @@ __global__ __launch_bounds__(256) void augment_geometry_kernel(const float* __re
         const int sx = q[8] ? Wo - 1 - ox : ox;
         const float* xb = img + (long)b * H * W * C;
         float* o = out + e * C;
-        if (!q[9]) {        // flip only (Ho == H, Wo == W: host check)
+        if (!q[9]) {        // flip only: Ho == H, Wo == W is the caller's contract (include/ssd_hip.h) -- the params are on
+                            // the device, the C entry cannot check it
             for (int c = 0; c < C; ++c) o[c] = xb[((long)oy * W + sx) * C + c];
             continue;
         }
