@@ -877,6 +877,58 @@ int ssd_augment_plan(const float* gt_boxes_dev, const int* gt_labels_dev, const 
                      int W, unsigned long long seed, int* geom_out_dev, float* color_out_dev, int* flags_out_dev,
                      float* add_out_dev, int* info_out_dev, float* boxes_out_dev, void* stream);
 
+/* ---- augmentation, mosaic (opt-in; not in the reference): four images of the batch tiled around a random centre ----------
+ * ssd_augment_mosaic_plan draws the plan of every output image and merges the ground truth; ssd_augment_mosaic_pixels
+ * writes the images.  No atomics, no workspace, no host synchronisation, no allocation.  Both read other images of the
+ * batch: no output may overlap an input (SSD_E_INVALID).
+ *   Inputs: images [B,H,W,3] float32 (already resized); gt_boxes [B,G,4] (y1, x1, y2, x2 normalised), 16-byte aligned;
+ *   gt_labels [B,G] int32, REQUIRED (they are merged): a row is valid iff its label > 0; sample_ids [B]; seed; p = the
+ *   probability that an output image is a mosaic; (s_min, s_max) = the scale range; G_out = rows of the output ground
+ *   truth; pad_label = the label of a padding row (data_utils.get_padding_values()[2] = -1).
+ *   Random stream: ssd_augment_plan's Philox4x32-10 with its key, counter layout and draw conventions (u, uniform(lo, hi),
+ *   integer below n: above), on slots that kernel does not touch (it uses 0..3 and 16..115), so the same (seed, id) may feed
+ *   both and the draws are independent:
+ *     slot 128      mosaic?                    partner 1            partner 2          partner 3
+ *     slot 129      centre y draw              centre x draw        --                 --
+ *     slot 130      scale of tile 0            tile 1               tile 2             tile 3
+ *   The plan of output image b (every value is computed and written whether or not b is a mosaic):
+ *     mosaic iff u < p (p = 0: never, p = 1: always).
+ *     tile 0 (top-left) shows image b itself; tiles 1, 2, 3 (top-right, bottom-left, bottom-right) show the images
+ *       integer(word_t) below B of THIS batch, drawn with replacement (a partner may be b, partners may repeat).
+ *     centre: yc = clamp((int)(H * (0.25f + 0.5f * u)), 1, H - 1), xc the same with W and its own draw.
+ *     tile t: s_t = uniform(s_min, s_max); hs_t = max(1, rintf(H * s_t)), ws_t = max(1, rintf(W * s_t)).  The source image
+ *       is resized as a whole to hs_t x ws_t (bilinear, half-pixel centres: ssd_augment_geometry's arithmetic with the
+ *       whole image as the window and hs_t x ws_t as the output size) and placed with one corner on the centre:
+ *         tile 0 rows [yc - hs, yc) columns [xc - ws, xc);    tile 1 rows [yc - hs, yc) columns [xc, xc + ws);
+ *         tile 2 rows [yc, yc + hs) columns [xc - ws, xc);    tile 3 rows [yc, yc + hs) columns [xc, xc + ws).
+ *     plan_out [B,16] int32 = {mosaic, yc, xc, 0, then for t = 0..3 {source, hs_t, ws_t}}.
+ *   Pixels: output pixel (oy, ox) belongs to the tile (oy < yc ? top : bottom, ox < xc ? left : right); inside that tile's
+ *     placed image it is the resized image's pixel, outside it fill[c] (fill: 3 floats on the HOST).  An image that is not
+ *     a mosaic is copied through.  The plan is device data: a tile whose row names no image of the batch, a centre outside
+ *     [0, H] x [0, W] or a size outside 1..8192 (what the plan kernel can write) shows the fill colour.
+ *   Ground truth of a mosaic image: for t = 0..3 in this order and the VALID rows of tile t's source in row order, in fp32
+ *   with every operation rounded on its own (top / left = the first row / column of the placed image, as floats):
+ *     Y1 = top + y1 * hs, Y2 = top + y2 * hs, X1 = left + x1 * ws, X2 = left + x2 * ws                       (pixels)
+ *     (cy1, cy2) = Y1, Y2 clipped to the tile's rows [0, yc] or [yc, H]; (cx1, cx2) = X1, X2 clipped to its columns [0, xc]
+ *       or [xc, W]   (v < lo ? lo : v > hi ? hi : v)
+ *     h = cy2 - cy1, w = cx2 - cx1, h0 = Y2 - Y1, w0 = X2 - X1; the row is KEPT iff
+ *       h >= 2 && w >= 2 && w * h >= 0.1f * (w0 * h0) && w < 100 * h && h < 100 * w
+ *     a kept row is written as (cy1 / H, cx1 / W, cy2 / H, cx2 / W) with its source's label at the next free output row;
+ *     kept rows beyond G_out are dropped; the remaining rows are padding: all-zero box, pad_label.
+ *   Ground truth of an image that is not a mosaic: its G rows copied to rows 0..G-1 as they are, valid or not; the rest
+ *     is padding.
+ *   info_out [B,4] = {mosaic, rows kept by the rule, rows written, valid source rows seen}; not a mosaic: {0, 0, G, 0}.
+ *   The plan kernel runs one wavefront per output image: lanes take a source's rows 64 at a time, a wave ballot and a
+ *   prefix popcount give every kept row its output index -- the law of the sequential order above.
+ *   SSD_E_UNSUPPORTED (nothing is launched) outside 2 <= H, W <= 4096, 1 <= G <= 512, G <= G_out <= 2048, B <= 65535.
+ *   SSD_E_INVALID (nothing is launched): p outside [0, 1]; a scale range outside 0.1 <= s_min <= s_max <= 2; a NULL
+ *   pointer; an output that overlaps an input or another output.  B == 0 is a no-op. */
+int ssd_augment_mosaic_plan(const float* gt_boxes_dev, const int* gt_labels_dev, const long long* sample_ids_dev, int B, int G,
+                            int H, int W, unsigned long long seed, float p, float s_min, float s_max, int G_out, int pad_label,
+                            int* plan_out_dev, float* boxes_out_dev, int* labels_out_dev, int* info_out_dev, void* stream);
+int ssd_augment_mosaic_pixels(const float* img_dev, int B, int H, int W, const int* plan_dev, const float* fill /* host, 3 */,
+                              float* out_dev, void* stream);
+
 /* ---- drawing: utils/drawing_utils.py:6-85 (draw_grid_map, draw_bboxes, draw_bboxes_with_labels) ---------------------
  * ssd_image_minmax: minmax_out [B][2] = {min, max} over H, W, C of each image of img_dev [B,H,W,3] float32: the two numbers
  *   of [3P] Keras array_to_img(scale=True).  NaN pixels are ignored.  workspace: ssd_image_minmax_workspace_bytes(B) bytes,

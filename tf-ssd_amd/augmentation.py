@@ -14,6 +14,10 @@ Opt-in, the draws can be made on the device instead (``plan_batch_device`` / ``a
 kernel wrote it, the boxes stay on the device, and an image's augmentation is a pure function of (seed, sample id).  It is
 another random stream than ``seed()``'s; everything above keeps its host draws and its bits.
 
+Opt-in as well, and not in the reference: mosaic (``mosaic_batch_device`` / ``mosaicked``: ``ssd_augment_mosaic_plan`` and
+``ssd_augment_mosaic_pixels``) tiles four images of a padded batch around a random centre and merges their boxes AND labels,
+in front of the device draws (a mosaic may keep no box: the device plan gives such an image no patch, the host draws raise).
+
 Images: float32 device tensors [H,W,3] in [0,1]; boxes [G,4] = (y1, x1, y2, x2) normalised.
 [3P] ``sample_distorted_bounding_box`` is restated from the TF 2.0 kernel's published algorithm (random: only its
 acceptance rule is testable); there is no TensorFlow here, parity of the TF ops themselves is unpinned."""
@@ -478,3 +482,113 @@ def augmented(dataset, fn=None):
                 im, gb = fn(img, gt_boxes, gt_labels)
                 yield im, gb, gt_labels
     return _Aug()
+
+
+# ---- mosaic (opt-in; not in the reference) ------------------------------------------------------------------------------
+MOSAIC_NAMES = ("plan", "boxes", "labels", "info")
+MOSAIC_MAX_BOXES = 512          # max_boxes=None never asks for more rows: the result still fits ``ssd_augment_plan``
+MOSAIC_SCALE = (0.5, 1.0)
+
+
+def _mosaic_args(p, scale):
+    """(p, s_min, s_max) as floats, or ValueError: the checks the library repeats."""
+    try:
+        p = float(p)
+        lo, hi = (float(v) for v in scale)
+    except (TypeError, ValueError):
+        raise ValueError("mosaic: p must be a number and scale a pair of numbers, got %r and %r" % (p, scale))
+    if not 0.0 <= p <= 1.0:
+        raise ValueError("mosaic: p must lie in [0, 1], got %r" % (p,))
+    if not 0.1 <= lo <= hi <= 2.0:
+        raise ValueError("mosaic: scale must satisfy 0.1 <= lo <= hi <= 2, got %r" % (tuple(scale),))
+    return p, lo, hi
+
+
+def mosaic_plan_device(gt_boxes, gt_labels, sample_ids, H, W, seed, p=1.0, scale=MOSAIC_SCALE, max_boxes=None, out=None):
+    """The mosaic plan and the merged ground truth of a padded batch in ONE launch (``ssd_augment_mosaic_plan``,
+    include/ssd_hip.h): returns the four device tensors (plan int32 [B,16], boxes float32 [B,G_out,4], labels int32
+    [B,G_out], info int32 [B,4]).  Output image ``b`` is a mosaic with probability ``p``: itself top-left and three images
+    of THIS batch, each resized by its own draw from ``scale``, around a random centre; their valid rows (label > 0) are
+    moved, clipped to the tile, filtered (2 px, 10 % of the area, aspect below 100) and merged with their labels, padding
+    rows get an all-zero box and ``data_utils.get_padding_values()[2]``.  ``max_boxes`` = G_out (None: ``min(4 * G, 512)``);
+    kept rows beyond it are dropped (``info[:, 1]`` counts them all, ``info[:, 2]`` the written ones).  The draws come from
+    ``ssd_augment_plan``'s generator on slots of their own: the same (``seed``, ``sample_ids``) may feed both.  ``out``: four
+    preallocated tensors to write into; none may be an input.  Raises ``ssd_hip.SsdHipUnsupported`` outside 2 <= H, W <=
+    4096, 1 <= G <= 512, G <= G_out <= 2048, B <= 65535."""
+    from utils import data_utils
+    p, lo, hi = _mosaic_args(p, scale)
+    g = _h.to_dev(gt_boxes)
+    if g.dim() != 3 or g.shape[2] != 4:
+        raise ValueError("gt_boxes must be [B,G,4], got %s" % (tuple(g.shape),))
+    B, G = int(g.shape[0]), int(g.shape[1])
+    if gt_labels is None:
+        raise ValueError("mosaic_plan_device: gt_labels are required (they are merged)")
+    gl = _h.to_dev(gt_labels, torch.int32)
+    ids = _h.to_dev(sample_ids, torch.int64)
+    if ids.numel() != B or tuple(gl.shape) != (B, G):
+        raise ValueError("mosaic_plan_device: gt_labels must be [B,G] and sample_ids [B]")
+    G_out = min(4 * G, MOSAIC_MAX_BOXES) if max_boxes is None else int(max_boxes)
+    dev = g.device
+    shapes = ((B, 16), (B, max(G_out, 0), 4), (B, max(G_out, 0)), (B, 4))
+    dtypes = (torch.int32, torch.float32, torch.int32, torch.int32)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes))
+    else:
+        for t, s, d, n in zip(out, shapes, dtypes, MOSAIC_NAMES):
+            if tuple(t.shape) != s or t.dtype != d or t.device != dev or not t.is_contiguous():
+                raise ValueError("mosaic_plan_device: out %s must be a contiguous %s tensor of shape %s on %s" % (n, d, s, dev))
+    plan, boxes, labels, info = out
+    _h.check(_h.lib().ssd_augment_mosaic_plan(_h.ptr(g), _h.ptr(gl), _h.ptr(ids), B, G, int(H), int(W), int(seed) & (2 ** 64 - 1),
+                                              p, lo, hi, G_out, int(data_utils.get_padding_values()[2]), _h.ptr(plan),
+                                              _h.ptr(boxes), _h.ptr(labels), _h.ptr(info), _h.stream()), "ssd_augment_mosaic_plan")
+    return plan, boxes, labels, info
+
+
+def run_mosaic_device(images, plan, fill=(0.5, 0.5, 0.5)):
+    """The images of a mosaic plan (``mosaic_plan_device``'s first tensor) in ONE launch (``ssd_augment_mosaic_pixels``):
+    every output pixel is its tile's source image resized as a whole (the four taps of ``ssd_augment_geometry``) or, outside
+    the placed image, ``fill``; an image that is not a mosaic is copied through.  Returns a new [B,H,W,3] tensor."""
+    import ctypes
+    x = _h.to_dev(images)
+    if x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError("images must be [B,H,W,3], got %s" % (tuple(x.shape),))
+    B, H, W, _ = x.shape
+    if tuple(plan.shape) != (B, 16) or plan.dtype != torch.int32 or plan.device != x.device or not plan.is_contiguous():
+        raise ValueError("run_mosaic_device: plan must be a contiguous int32 [B,16] tensor on %s" % (x.device,))
+    f = (ctypes.c_float * 3)(*[float(v) for v in fill])
+    out = torch.empty_like(x)
+    _h.check(_h.lib().ssd_augment_mosaic_pixels(_h.ptr(x), B, H, W, _h.ptr(plan), f, _h.ptr(out), _h.stream()),
+             "ssd_augment_mosaic_pixels")
+    return out
+
+
+def mosaic_batch_device(images, gt_boxes, gt_labels, sample_ids, seed=None, p=1.0, scale=MOSAIC_SCALE, max_boxes=None):
+    """Mosaic on a padded batch: two launches (the plan with the merged ground truth, the pixels), nothing uploaded but what
+    the caller passed on the host.  Returns (images [B,H,W,3], gt_boxes [B,G_out,4], gt_labels [B,G_out] int32) on the
+    device; ``seed`` None = 0.  Unlike every ``augmentation_fn`` it returns labels: the row count and the labels change."""
+    x = _h.to_dev(images)
+    if x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError("images must be [B,H,W,3], got %s" % (tuple(x.shape),))
+    plan, boxes, labels, _ = mosaic_plan_device(gt_boxes, gt_labels, sample_ids, int(x.shape[1]), int(x.shape[2]),
+                                                0 if seed is None else seed, p, scale, max_boxes)
+    return run_mosaic_device(x, plan), boxes, labels
+
+
+def mosaicked(dataset, p, seed, rank_offset=0, scale=MOSAIC_SCALE, max_boxes=None):
+    """A dataset of padded batches (img, gt_boxes, gt_labels) with every image a mosaic of its batch with probability ``p``
+    (``mosaic_batch_device``), fresh draws on every pass: the images are numbered by a running counter that starts at
+    ``rank_offset`` (give every rank its own range).  Goes IN FRONT of ``augmented``, which then treats a mosaic like any
+    image.  A mosaic may keep NO row: the function behind it must take an image without a valid row -- ``device_draws`` does
+    (no patch), ``apply_batch`` raises there like TF's sampler, so use the device draws behind a mosaic.  ValueError for ``p``
+    outside [0, 1] or a bad ``scale``, here and not at the first batch."""
+    p, lo, hi = _mosaic_args(p, scale)
+    state = {"next": int(rank_offset)}
+
+    class _Mosaic(object):
+        def __iter__(self_inner):
+            for img, gt_boxes, gt_labels in dataset:
+                B = int(img.shape[0])
+                ids = torch.arange(state["next"], state["next"] + B, dtype=torch.int64, device=_h.device())
+                state["next"] += B
+                yield mosaic_batch_device(img, gt_boxes, gt_labels, ids, seed, p, (lo, hi), max_boxes)
+    return _Mosaic()

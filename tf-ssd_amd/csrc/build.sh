@@ -40,6 +40,8 @@ compile ssd_iouloss.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sq
 compile ssd_data.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
 # the augmentation plan: bit-equal to its fp32 NumPy restatement (tests/augment_plan_cases.py)
 compile ssd_augplan.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
+# mosaic: the plan bit-equal to tests/mosaic_cases.py, the pixels ssd_data.hip's four taps (bilinear_taps.h) under its flags
+compile ssd_mosaic.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
 # JPEG: integer arithmetic only; -fwrapv makes int32 wrap-around (hostile coefficients) defined
 compile ssd_jpeg.hip -ffp-contract=off -fwrapv
 compile ssd_jpeg_enc.hip -ffp-contract=off

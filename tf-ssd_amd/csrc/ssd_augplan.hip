@@ -8,39 +8,13 @@
 // rounded division / sqrt: every fp32 operation rounds on its own, as in the NumPy restatement the tests compare with
 // (tests/augment_plan_cases.py).
 #include "common.h"
+#include "philox.h"
 
 namespace ssd {
 
 static const int kPlanMaxBoxes = 512;
 static const int kPlanAttempts = 100;
 
-struct philox4 {
-    unsigned int w[4];
-};
-
-__device__ __forceinline__ philox4 philox4x32_10(const unsigned int c0, const unsigned int c1, const unsigned int c2,
-                                                 const unsigned int c3, unsigned int k0, unsigned int k1) {
-    philox4 c = {{c0, c1, c2, c3}};
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = 0xD2511F53ull * c.w[0], p1 = 0xCD9E8D57ull * c.w[2];
-        const philox4 n = {{(unsigned int)(p1 >> 32) ^ c.w[1] ^ k0, (unsigned int)p1, (unsigned int)(p0 >> 32) ^ c.w[3] ^ k1,
-                            (unsigned int)p0}};
-        c = n;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
-
-__device__ __forceinline__ float draw_unit(const unsigned int word) { return (float)(word >> 8) * 0x1p-24f; }
-__device__ __forceinline__ bool draw_bool(const unsigned int word) { return draw_unit(word) > 0.5f; }
-__device__ __forceinline__ float draw_uniform(const unsigned int word, const float lo, const float hi) {
-    return lo + draw_unit(word) * (hi - lo);
-}
-__device__ __forceinline__ int draw_below(const unsigned int word, const int n) {
-    return (int)(((unsigned long long)word * (unsigned long long)(unsigned int)n) >> 32);
-}
 // np.clip(v, 0, 1): a NaN stays a NaN
 __device__ __forceinline__ float clip01(const float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
 

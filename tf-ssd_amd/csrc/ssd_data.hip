@@ -9,6 +9,7 @@
 // Compiled with -ffp-contract=off: every multiply/add rounds separately like the reference's ops.
 #include <algorithm>
 
+#include "bilinear_taps.h"
 #include "common.h"
 
 namespace ssd {
@@ -156,12 +157,10 @@ __global__ __launch_bounds__(256) void augment_geometry_kernel(const float* __re
             for (int c = 0; c < C; ++c) o[c] = xb[((long)oy * W + sx) * C + c];
             continue;
         }
-        const float sy = (float)ch / (float)Ho, sxs = (float)cw / (float)Wo;
-        const float fy = ((float)oy + 0.5f) * sy - 0.5f, fx = ((float)sx + 0.5f) * sxs - 0.5f;
-        const float fyf = floorf(fy), fxf = floorf(fx);
-        const int y0 = max((int)fyf, 0), y1 = min((int)ceilf(fy), ch - 1);
-        const int x0 = max((int)fxf, 0), x1 = min((int)ceilf(fx), cw - 1);
-        const float ly = fy - fyf, lx = fx - fxf;
+        int y0, y1, x0, x1;
+        float ly, lx;
+        bilinear_axis(oy, ch, Ho, y0, y1, ly);      // bilinear_taps.h: shared with the mosaic pixels
+        bilinear_axis(sx, cw, Wo, x0, x1, lx);
         // canvas -> image coordinates; outside the image the canvas holds the fill colour
         const int iy0 = cy + y0 - pad_top, iy1 = cy + y1 - pad_top, ix0 = cx + x0 - pad_left, ix1 = cx + x1 - pad_left;
         const bool vy0 = (unsigned)iy0 < (unsigned)H, vy1 = (unsigned)iy1 < (unsigned)H;
@@ -172,9 +171,7 @@ __global__ __launch_bounds__(256) void augment_geometry_kernel(const float* __re
             const float tr = (vy0 && vx1) ? xb[((long)iy0 * W + ix1) * C + c] : f;
             const float bl = (vy1 && vx0) ? xb[((long)iy1 * W + ix0) * C + c] : f;
             const float br = (vy1 && vx1) ? xb[((long)iy1 * W + ix1) * C + c] : f;
-            const float top = tl + (tr - tl) * lx;
-            const float bot = bl + (br - bl) * lx;
-            o[c] = top + (bot - top) * ly;
+            o[c] = bilinear_blend(tl, tr, bl, br, lx, ly);
         }
     }
 }

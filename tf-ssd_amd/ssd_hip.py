@@ -209,6 +209,9 @@ _SIGNATURES = {
     "ssd_augment_geometry": (ctypes.c_int, [vp] + [ctypes.c_int] * 6 + [vp, vp, vp, vp]),
     "ssd_augment_color": (ctypes.c_int, [vp] + [ctypes.c_int] * 3 + [vp, vp, vp, vp]),
     "ssd_augment_plan": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 4 + [ctypes.c_ulonglong] + [vp] * 7),
+    "ssd_augment_mosaic_plan": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 4 + [ctypes.c_ulonglong] + [ctypes.c_float] * 3 +
+                                [ctypes.c_int] * 2 + [vp] * 5),
+    "ssd_augment_mosaic_pixels": (ctypes.c_int, [vp] + [ctypes.c_int] * 3 + [vp, c_float_p, vp, vp]),
     "ssd_image_minmax_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "ssd_image_minmax": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp, vp, ctypes.c_size_t, vp]),
     "ssd_draw_detections": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 4 + [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp,

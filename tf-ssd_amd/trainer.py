@@ -27,7 +27,11 @@ writes the prior-probability bias into the label heads after ``init_model`` (``m
 ``SSD_TRAINER_LOC_LOSS`` (``huber`` | ``iou`` | ``giou`` | ``diou`` | ``ciou``, ``loc_loss_from_env``) puts an IoU-family loss on
 the decoded boxes in place of the Huber localisation term of either; unset: the reference's Huber term.
 Target assignment: ``SSD_TRAINER_MATCH`` (``max_iou`` | ``bipartite`` | ``atss``) and ``SSD_TRAINER_MATCH_TOPK`` (atss, default 9)
-(``match_from_env``); unset: the reference's threshold rule."""
+(``match_from_env``); unset: the reference's threshold rule.
+Mosaic: ``SSD_TRAINER_MOSAIC`` = the probability that a training image becomes a mosaic of four images of its batch, in front
+of the reference's augmentation, and ``SSD_TRAINER_MOSAIC_SCALE`` = ``lo,hi`` (default ``0.5,1.0``) (``mosaic_from_env``); unset,
+empty or 0: no mosaic, the feed is unchanged.  Mosaic needs ``SSD_TRAINER_AUGMENT=gpu`` (or ``0``): a mosaic may keep no box, and the
+host draws' window sampler raises on an image without one.  """
 import json
 import os
 import sys
@@ -196,6 +200,54 @@ def match_from_env(hyper_params):
     return dict(hyper_params, match_strategy=kind, match_topk=k)
 
 
+def mosaic_from_env():
+    """``SSD_TRAINER_MOSAIC`` = the probability that a training image is a mosaic of its batch (``augmentation.mosaicked``);
+    ``SSD_TRAINER_MOSAIC_SCALE`` = ``"lo,hi"``, the tiles' scale range (default ``0.5,1.0``).  Returns None when the
+    probability is unset, empty or 0 -- no wrapper, no launch: the feed is the one without the knob -- and ``(p, (lo, hi))``
+    otherwise.  ValueError for a probability that does not parse or lies outside [0, 1], for a scale that is not two numbers
+    with 0.1 <= lo <= hi <= 2, for a scale set without mosaic, and for mosaic beside the host draws of the augmentation
+    (``SSD_TRAINER_AUGMENT`` anything but ``gpu`` or ``0``): a mosaic may keep no ground-truth row, and ``apply_batch``'s sampler
+    raises on such an image, like TF's; the device plan gives it no patch instead."""
+    env = os.environ
+    raw, raw_scale = env.get("SSD_TRAINER_MOSAIC", "").strip(), env.get("SSD_TRAINER_MOSAIC_SCALE", "").strip()
+    try:
+        p = float(raw or 0)
+    except ValueError:
+        p = -1.0
+    if not 0.0 <= p <= 1.0:
+        raise ValueError("SSD_TRAINER_MOSAIC must be a probability in [0, 1], got %r" % raw)
+    if p == 0.0:
+        if raw_scale:
+            raise ValueError("SSD_TRAINER_MOSAIC_SCALE set, but SSD_TRAINER_MOSAIC is not")
+        return None
+    try:
+        lo, hi = (float(v) for v in (raw_scale or "0.5,1.0").split(","))
+    except ValueError:
+        lo, hi = 0.0, 0.0
+    if not 0.1 <= lo <= hi <= 2.0:
+        raise ValueError("SSD_TRAINER_MOSAIC_SCALE must be 'lo,hi' with 0.1 <= lo <= hi <= 2, got %r" % raw_scale)
+    if env.get("SSD_TRAINER_AUGMENT", "1") not in ("gpu", "0"):
+        raise ValueError("SSD_TRAINER_MOSAIC needs SSD_TRAINER_AUGMENT=gpu (or 0): a mosaic may keep no ground-truth row, which "
+                         "the host draws' window sampler refuses; got SSD_TRAINER_AUGMENT=%r" % env.get("SSD_TRAINER_AUGMENT", "1"))
+    return p, (lo, hi)
+
+
+def voc_training_batches(train_data, batch_size, img_size, rank, augment, augment_gpu, mosaic):
+    """The training stream of the VOC road (reference trainer.py:42-48: preprocessing + augmentation, shuffle, padded batches).
+    Without mosaic the augmentation runs inside ``voc_batches``; with it ``voc_batches`` only resizes, ``mosaicked`` wraps it
+    and ``augmented`` wraps that, so the reference's augmentation treats a mosaic like any image."""
+    import augmentation
+    if augment and not augment_gpu:
+        augmentation.seed(4242 + rank)
+    augmentation_fn = augmentation.device_draws(4242, rank_offset=rank << 40) if augment_gpu else augmentation.apply_batch
+    shuffled = train_data.shuffle(batch_size * 4, seed=rank)
+    if mosaic is None:
+        return data_utils.voc_batches(shuffled, batch_size, img_size, img_size, augmentation_fn=augmentation_fn if augment else None)
+    batches = data_utils.voc_batches(shuffled, batch_size, img_size, img_size, augmentation_fn=None)
+    batches = augmentation.mosaicked(batches, mosaic[0], 4242, rank_offset=rank << 40, scale=mosaic[1])
+    return augmentation.augmented(batches, augmentation_fn) if augment else batches
+
+
 def main(argv=None):
     args = io_utils.handle_args(argv)
     if args.handle_gpu:
@@ -213,24 +265,21 @@ def main(argv=None):
         from models.ssd_vgg16 import get_model, init_model
     hyper_params = train_utils.get_hyper_params(backbone)
     voc_dir = os.environ.get("SSD_VOC_DIR")
+    mosaic = mosaic_from_env()
+    if mosaic is not None and rank == 0:
+        print("mosaic: p %g, scale %g..%g" % (mosaic[0], mosaic[1][0], mosaic[1][1]), flush=True)
     augment = os.environ.get("SSD_TRAINER_AUGMENT", "1") != "0"
     # SSD_TRAINER_AUGMENT=gpu: the random plan is drawn on the device (augmentation.device_draws: a counter-based
     # generator, every rank numbers its images in a range of its own); any other value but 0 keeps the host draws
     augment_gpu = os.environ.get("SSD_TRAINER_AUGMENT", "1") == "gpu"
     if voc_dir:
-        import augmentation
         train_data, val_data, info, train_total_items, val_total_items = _voc_splits(voc_dir, batch_size, rank, world)
         labels = ["bg"] + data_utils.get_labels(info)
         hyper_params["total_labels"] = len(labels)
         img_size = hyper_params["img_size"]
         step_size_train = int(os.environ.get("SSD_TRAINER_STEPS", "0")) or train_utils.get_step_size(train_total_items, batch_size)
         step_size_val = train_utils.get_step_size(val_total_items, batch_size)
-        if augment and not augment_gpu:
-            augmentation.seed(4242 + rank)
-        augmentation_fn = augmentation.device_draws(4242, rank_offset=rank << 40) if augment_gpu else augmentation.apply_batch
-        # trainer.py:42-48: preprocessing (+ augmentation on the training stream), shuffle, padded batches
-        train_data = data_utils.voc_batches(train_data.shuffle(batch_size * 4, seed=rank), batch_size, img_size, img_size,
-                                            augmentation_fn=augmentation_fn if augment else None)
+        train_data = voc_training_batches(train_data, batch_size, img_size, rank, augment, augment_gpu, mosaic)
         val_data = data_utils.voc_batches(val_data, batch_size, img_size, img_size)
         augment = False                                   # done inside the batches
     else:
@@ -283,6 +332,9 @@ def main(argv=None):
     ssd_log_path = io_utils.get_log_path(backbone)
     # reference trainer.py:42: the TRAINING stream is augmented (fresh draws every epoch), the validation stream is not.
     # SSD_TRAINER_AUGMENT=0 turns it off (deterministic smoke runs).
+    if mosaic is not None and not voc_dir:          # SSD_TRAINER_MOSAIC: in front of the augmentation (the VOC road did it above)
+        import augmentation
+        train_data = augmentation.mosaicked(train_data, mosaic[0], 4242, rank_offset=rank << 40, scale=mosaic[1])
     if augment:
         import augmentation
         if augment_gpu:
