@@ -1247,6 +1247,21 @@ int ssd_net_tuning_stats(const ssd_net* net, int* from_table, int* timed);
  * no chosen tile reads them), out[2] partial-sum slabs of the whole-image block kernel, out[3] split-K slabs.  A lane
  * replica (models/decoder.py) holds the same again. */
 int ssd_net_memory_bytes(const ssd_net* net, size_t out[4]);
+/* ... and, on top of those, the fp16 weight planes of the whole-image blocks (option "image_f16x2"; 0 with the option off). */
+size_t ssd_net_image_f16x2_bytes(const ssd_net* net);
+/* Static bound of a named tensor of a finalized net: max |x| over EVERY input, computed at finalize from the weights alone
+ * for the tensors a project conv behind a ReLU6 depthwise writes (alone or inside a fused block), a residual adding its
+ * source's interval; < 0: no bound is known (other tensors, non-finite weights).  Recomputed by every finalize. */
+float ssd_net_tensor_bound(const ssd_net* net, const char* tensor);
+/* The interval arithmetic behind it, on the host (no device): output channel r of y = W' d + shift (+ residual) with d in
+ * [0, 6]^k lies in [6 sum min(w', 0) + shift + res_lo, 6 sum max(w', 0) + shift + res_hi], w' = w[r * ld + c] * scale[r]
+ * (scale / shift / res_lo + res_hi may be NULL: 1 / 0 / no residual).  Returns 1, or 0 if anything is not finite (no bound),
+ * or a negative SSD_E_* code. */
+int ssd_block_output_interval(const float* w, int n, int k, int ld, const float* scale, const float* shift, const double* res_lo,
+                              const double* res_hi, double* lo, double* hi);
+/* Exponent s = floor(log2(2^15 / bound)) of the input scale 2^s of the two-plane fp16 form of the whole-image blocks:
+ * |2^s x| <= 2^15 for |x| <= bound.  Returns 1, or 0 (no fp16 form) for an unknown (< 0), zero or non-finite bound or |s| > 12. */
+int ssd_f16x2_input_exp(float bound, int* s);
 /* sha256 (first 16 hex digits) of the kernel sources this library was built from (csrc/build.sh);
  * shipped tuning tables record the build they were measured on. */
 const char* ssd_build_id(void);
@@ -1282,6 +1297,9 @@ int ssd_net_num_layers(const ssd_net* net);
 const char* ssd_net_layer_name(const ssd_net* net, int i);
 const char* ssd_net_layer_kind(const ssd_net* net, int i);   /* "conv","dw","pool",... */
 const char* ssd_net_layer_config(const ssd_net* net, int i); /* autotuned conv tile config */
+/* Which form of the whole-image block kernel runs layer i at batch B: -1 the layer is not routed to it, 0 fp32 MFMA,
+ * 1 the bf16 mode, 3 the split-bf16 form, 2 the two-plane fp16 form (option "image_f16x2", a statically bounded input). */
+int ssd_net_layer_image_form(const ssd_net* net, int i, int B);
 double ssd_net_layer_flops(const ssd_net* net, int i, int B); /* 2*MACs                  */
 double ssd_net_layer_bytes(const ssd_net* net, int i, int B); /* in + out + weights      */
 /* FLOPs the chosen kernel issues: = layer_flops except Winograd layers (x 16/36, whole border tiles) */

@@ -99,6 +99,9 @@ __device__ __forceinline__ uint2 rne4(const b3_f32x4 v) { return make_uint2(rne2
 // and a larger |x| becomes inf (the join returns a non-finite value: nothing is silently made finite).  WEIGHTS are
 // scaled by a per-layer 2^k chosen on the host from max |w| (conv_f16x2_weight_exp, ssd_conv.h).  The tile multiplies its accumulators
 // by the exact 2^-(8 + k) (ConvParams::acc_scale) before the epilogue.  Both roundings are to nearest even.
+// The whole-image block kernel (ssd_imgblock2.hip, NP = 2) also takes a tensor WITHOUT a ReLU6 in front, a linear
+// bottleneck output, scaled by 2^s with s from a static bound of the tensor (|2^s x| <= 2^15): values far below the bound
+// lose the low plane to fp16's subnormal grid -- an absolute error of 2^-25 / 2^s, <= 2^-39 of the bound.
 typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 constexpr float kF16x2ActScale = 256.f;
@@ -122,7 +125,7 @@ __device__ __forceinline__ float join_h(const short h, const short l) {
 
 template <int NP>
 struct BP {
-    bf16x8 p[NP];          // NP = 3: h, m, l;  NP = 1: the bf16 rounding;  NP = 2: fp16 h, l (read from planes only)
+    bf16x8 p[NP];          // NP = 3: h, m, l;  NP = 1: the bf16 rounding;  NP = 2: fp16 h, l (read from planes, or splitN_scaled)
 };
 template <int NP>
 __device__ __forceinline__ BP<NP> splitN(const b3_f32x4 a, const b3_f32x4 b) {
@@ -135,6 +138,24 @@ __device__ __forceinline__ BP<NP> splitN(const b3_f32x4 a, const b3_f32x4 b) {
         r.p[0] = __builtin_bit_cast(bf16x8, u);
     }
     return r;
+}
+// ... of `scale` x: NP = 2 the fp16 pair h, l of scale * x (an exact power of two the caller knows keeps |scale x| inside
+// fp16's range: 2^8 for ReLU6 outputs, 2^s from a static bound of the tensor); the bf16 forms ignore the scale
+template <int NP>
+__device__ __forceinline__ BP<NP> splitN_scaled(const b3_f32x4 a, const b3_f32x4 b, const float scale) {
+    if constexpr (NP == 2) {
+        uint4 h, l;
+        split_h2(a[0] * scale, a[1] * scale, h.x, l.x);
+        split_h2(a[2] * scale, a[3] * scale, h.y, l.y);
+        split_h2(b[0] * scale, b[1] * scale, h.z, l.z);
+        split_h2(b[2] * scale, b[3] * scale, h.w, l.w);
+        BP<NP> r;
+        r.p[0] = __builtin_bit_cast(bf16x8, h);
+        r.p[1] = __builtin_bit_cast(bf16x8, l);
+        return r;
+    } else {
+        return splitN<NP>(a, b);
+    }
 }
 template <int NP>
 __device__ __forceinline__ b3_f32x4 mmaN(const BP<NP>& w, const BP<NP>& x, b3_f32x4 acc) {

@@ -90,6 +90,12 @@ struct FusedBlockParams {
     int planes_only;            // whole-image kernel: bit 0 = y, bit 1 = the expanded map leave as planes ONLY (no fp32 store; every
                                 // consumer reads the planes).  The pointers y / e_out stay set: they also say which shapes a kernel takes
     int form2;                  // whole-image kernel only: 1 = take the second form (csrc/ssd_imgblock2.hip) where it has a configuration.  The row-band kernels have one form and ignore it
+    // whole-image kernel, second form, bf16 == 2 -- the two-plane fp16 form (fp32 results, three fp16 MFMAs per product in
+    // BOTH 1x1 GEMMs; ssd_bf16x3.h): we3 / wp3 are then the fp16 pairs [2][Ce][kpad_e] of 2^ke we and [2][npad_p][kpad_p] of
+    // 2^kp wp, and these three exact powers of two: x is split as the pair of f16_xs x = 2^s x (s from the static bound of
+    // the block's input: ssd_f16x2_input_exp), the expand accumulators are multiplied by f16_es = 2^-(s + ke), the depthwise
+    // output is split as the pair of 2^8 d and the project accumulators are multiplied by f16_ps = 2^-(8 + kp)
+    float f16_xs, f16_es, f16_ps;
 };
 // Fused MobileNetV2 stem (Conv1 -> expanded_conv_depthwise -> expanded_conv_project).
 struct StemParams {
@@ -216,7 +222,7 @@ int dmah_tile_index(int j);
 // fp16 weight planes of a packed [Npad][Kpad] matrix: *absmax_bits_dev receives max |w| as fp32 bits (a non-finite weight:
 // >= 0x7f800000), zeroed by the caller; then the planes of 2^k w
 int launch_absmax_bits(const float* packed, int K, int Cout, unsigned* absmax_bits_dev, hipStream_t st);
-int launch_pack_f16x2(const float* packed, int K, int Cout, int k, short* planes, hipStream_t st);
+int launch_pack_f16x2(const float* packed, int K, int Cout, int k, short* planes, hipStream_t st, bool row_major = false);
 // the exponent k of a layer's weight scale from max |w| (as fp32 bits, finite): max |w| 2^k in [2^13, 2^14) -- headroom
 // below fp16's 65504, the low plane's subnormal grid 2^-24 far below the high plane's ulp; all-zero weights: 0
 inline int conv_f16x2_weight_exp(unsigned absmax_bits) {

@@ -342,12 +342,13 @@ __global__ __launch_bounds__(256) void absmax_bits_kernel(const float* __restric
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) m = max(m, __float_as_uint(w[e]) & 0x7fffffffu);
     atomicMax(out, m);
 }
-// fp16 planes h, l of 2^k w, slice-major [Kpad / 32][Npad][32] like the bf16 planes
+// fp16 planes h, l of 2^k w, slice-major [Kpad / 32][Npad][32] like the bf16 planes (Npad 0: plain row-major [N][Kpad], the
+// whole-image block kernel's expand / project matrices)
 __global__ __launch_bounds__(256) void pack_f16x2_kernel(const float* __restrict__ w, const long total, const int Kpad, const int Npad,
                                                          const float scale, short* __restrict__ out) {
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
         const long n = e / Kpad;
-        const long d = plane_elem(n, (int)(e - n * Kpad), Npad);
+        const long d = Npad ? plane_elem(n, (int)(e - n * Kpad), Npad) : e;
         unsigned h, l;
         split_h2(w[e] * scale, 0.f, h, l);
         out[d] = (short)(h & 0xffffu);
@@ -439,11 +440,11 @@ int launch_absmax_bits(const float* packed, int K, int Cout, unsigned* absmax_bi
     SSD_LAUNCH_CHECK();
     return SSD_OK;
 }
-int launch_pack_f16x2(const float* packed, int K, int Cout, int k, short* planes, hipStream_t st) {
+int launch_pack_f16x2(const float* packed, int K, int Cout, int k, short* planes, hipStream_t st, bool row_major) {
     const long total = (long)conv_kpad(K) * conv_npad(Cout);
     if (total == 0) return SSD_OK;
     const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    hipLaunchKernelGGL(pack_f16x2_kernel, dim3(blocks), dim3(256), 0, st, packed, total, conv_kpad(K), conv_npad(Cout), ldexpf(1.f, k), planes);
+    hipLaunchKernelGGL(pack_f16x2_kernel, dim3(blocks), dim3(256), 0, st, packed, total, conv_kpad(K), row_major ? 0 : conv_npad(Cout), ldexpf(1.f, k), planes);
     SSD_LAUNCH_CHECK();
     return SSD_OK;
 }

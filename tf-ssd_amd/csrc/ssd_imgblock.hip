@@ -763,6 +763,9 @@ int launch_image_block(FusedBlockParams p, hipStream_t st) {
     SSD_CHECK_ARG(!p.planes_only || !p.tickets, "image block: plane-only outputs combine by the second launch only");
     SSD_CHECK_ARG((p.Ce / kIC) % p.groups == 0, "image block: %d groups do not divide Ce/16 = %d", p.groups, p.Ce / kIC);
     SSD_CHECK_ARG(p.groups == 1 || p.slabs, "image block: %d groups need the slab workspace", p.groups);
+    // the two-plane fp16 form exists in the second form only: the caller asks for it where that form takes the block
+    SSD_UNSUPPORTED_IF(p.bf16 == 2 && !(p.form2 && !p.tickets && image_block2_supported(p)),
+                       "image block: the two-plane fp16 form has no kernel for Cin=%d Ce=%d Cout=%d %dx%d at %d groups", p.Cin, p.Ce, p.Cout, p.H, p.W, p.groups);
     if (p.bf16 == 3 && image_lds_bytes(*c, p, p.groups) > 160 * 1024) p.bf16 = 0;      // split form's weight tiles do not fit: fp32 form
     const size_t lds = image_lds_bytes(*c, p, p.groups);
     SSD_UNSUPPORTED_IF(lds > 160 * 1024, "image block: needs %zu B of LDS", lds);

@@ -23,6 +23,15 @@
 // Stride 1, and stride 2 for block 13 (one output pixel per lane, its expanded map -- SSD feature map 1 -- written to HBM from
 // the expand's epilogue); a group takes whole chunk PAIRS (the Ce / 32 pairs dealt as evenly as they go over the groups: no lone last
 // chunk); everything else keeps the first form.
+//
+// NP = 2, the two-plane fp16 form (fp32 results; option image_f16x2, ssd_bf16x3.h): BOTH 1x1 GEMMs on three fp16 MFMAs per
+// product instead of six bf16 ones.  The project's B operand is the depthwise output, [0, 6] by construction: the pair of
+// 2^8 d.  The expand's B operand is the block's input, a linear bottleneck output -- bounded all the same, statically, from
+// the weights (finalize_tensor_bounds, ssd_net.hip): the pair of 2^s x, s from that bound (FusedBlockParams::f16_xs), split
+// once in the prologue.  The weights are the pairs of 2^ke we / 2^kp wp (two planes in place of the three: two thirds of
+// the weight stream and of the weight LDS); the expand accumulators are multiplied by the exact 2^-(s + ke) before shift
+// and ReLU6, the project accumulators by 2^-(8 + kp) before the epilogue (slab store included: the combine adds the
+// shift).  E in LDS, the depthwise, the parameters, the dealing of the chunk pairs, the groups and the slabs are NP = 3's.
 
 #include "ssd_bf16x3.h"
 #include "ssd_block_common.h"
@@ -129,7 +138,7 @@ __device__ __forceinline__ void image16v2_body(const FusedBlockParams& p, float*
         for (int ks = 0; ks < KS; ++ks) {
             const f32x4 lo = real[t] ? *reinterpret_cast<const f32x4*>(xp + ks * 32) : f32x4{0.f, 0.f, 0.f, 0.f};
             const f32x4 hi = real[t] ? *reinterpret_cast<const f32x4*>(xp + ks * 32 + 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-            xs[t][ks] = splitN<NP>(lo, hi);
+            xs[t][ks] = splitN_scaled<NP>(lo, hi, p.f16_xs);
         }
     }
     // per-channel parameters, chunk-major: Ps[(j * 11 + row) * 16 + r], r = the chunk's MFMA row; channel of (j, r) =
@@ -174,7 +183,7 @@ __device__ __forceinline__ void image16v2_body(const FusedBlockParams& p, float*
         f32x4 ea[T];
         const f32x4 sh = *reinterpret_cast<const f32x4*>(ps_l + j * PCH);
 #pragma unroll
-        for (int t = 0; t < T; ++t) ea[t] = sh;
+        for (int t = 0; t < T; ++t) ea[t] = NP == 2 ? f32x4{0.f, 0.f, 0.f, 0.f} : sh;       // (the fp16 pair: the scaled sums first)
         const short* wl = we_l + pb * NBE * 512;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
@@ -188,6 +197,7 @@ __device__ __forceinline__ void image16v2_body(const FusedBlockParams& p, float*
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             f32x4 v = ea[t];
+            if constexpr (NP == 2) v = v * p.f16_es + sh;        // the exact 2^-(s + ke), then the shift
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = __builtin_amdgcn_fmed3f(v[e], 0.0f, relu_hi[t]);
             *reinterpret_cast<f32x4*>(ew + t * ROW) = v;
@@ -232,7 +242,7 @@ __device__ __forceinline__ void image16v2_body(const FusedBlockParams& p, float*
     auto project = [&](const f32x4 (&a0)[TO], const f32x4 (&a1)[TO]) {
         BP<NP> d[TO];
 #pragma unroll
-        for (int t = 0; t < TO; ++t) d[t] = splitN<NP>(a0[t], a1[t]);
+        for (int t = 0; t < TO; ++t) d[t] = splitN_scaled<NP>(a0[t], a1[t], kF16x2ActScale);
 #pragma unroll
         for (int ni = 0; ni < NT; ++ni) {
             BP<NP> wa;
@@ -281,6 +291,12 @@ __device__ __forceinline__ void image16v2_body(const FusedBlockParams& p, float*
         }
     }
 
+    if constexpr (NP == 2) {         // the fp16 pair: back from both scales by the exact 2^-(8 + kp), before anything else
+#pragma unroll
+        for (int t = 0; t < TO; ++t)
+#pragma unroll
+            for (int ni = 0; ni < NT; ++ni) acc[t][ni] = acc[t][ni] * p.f16_ps;
+    }
     // ---- epilogue (fp32): G = 1 direct; G > 1 partial-sum slab, combined by image_combine_kernel
     const long img_off = (long)img * (Ho * Wo) * p.Cout;
     if (G == 1) {
@@ -318,10 +334,12 @@ __global__ __launch_bounds__(NW * 64) void mbv2_image16v2_kernel(const FusedBloc
 typedef void (*image2_kernel_t)(const FusedBlockParams);
 struct Image2Cfg {
     int cin, nt, nw, t, h, w, stride;
-    image2_kernel_t fn1, fn3;       // bf16 mode (NP = 1), split-bf16 form (NP = 3)
+    image2_kernel_t fn1, fn3, fn2;  // bf16 mode (NP = 1), split-bf16 form (NP = 3), two-plane fp16 form (NP = 2; fp32 results)
 };
-#define I2CFG(CIN, NT, NW, T, H, W, LOOP) {CIN, NT, NW, T, H, W, 1, mbv2_image16v2_kernel<CIN, NT, NW, T, H, W, 1, LOOP>, mbv2_image16v2_kernel<CIN, NT, NW, T, H, W, 3, LOOP>}
-#define I2CFG2(CIN, NT, NW, T, H, W, LOOP) {CIN, NT, NW, T, H, W, 2, mbv2_image16v2_kernel<CIN, NT, NW, T, H, W, 1, LOOP, 2>, mbv2_image16v2_kernel<CIN, NT, NW, T, H, W, 3, LOOP, 2>}
+#define I2CFG(CIN, NT, NW, T, H, W, LOOP) {CIN, NT, NW, T, H, W, 1, mbv2_image16v2_kernel<CIN, NT, NW, T, H, W, 1, LOOP>, mbv2_image16v2_kernel<CIN, NT, NW, T, H, W, 3, LOOP>, \
+                                           mbv2_image16v2_kernel<CIN, NT, NW, T, H, W, 2, LOOP>}
+#define I2CFG2(CIN, NT, NW, T, H, W, LOOP) {CIN, NT, NW, T, H, W, 2, mbv2_image16v2_kernel<CIN, NT, NW, T, H, W, 1, LOOP, 2>, mbv2_image16v2_kernel<CIN, NT, NW, T, H, W, 3, LOOP, 2>, \
+                                            mbv2_image16v2_kernel<CIN, NT, NW, T, H, W, 2, LOOP, 2>}
 const Image2Cfg kImage2[] = {       // (one loop form per shape)
     I2CFG(64, 4, 8, 3, 19, 19, 1),     // blocks 7-9:   64 -> 384 -> 64 at 19x19
     I2CFG(64, 6, 8, 3, 19, 19, 1),     // block 10:     64 -> 384 -> 96
@@ -334,7 +352,7 @@ const Image2Cfg kImage2[] = {       // (one loop form per shape)
 
 size_t image2_lds_bytes(const Image2Cfg& c, const FusedBlockParams& p, int G) {
     const int P = c.w + 1, npix = c.nw * 16 * c.t, NE = npix + 2 * P + 2, row = c.stride == 2 ? 20 : (c.t & 1) ? 24 : 20;
-    const int np = p.bf16 == 3 ? 3 : 1, ks = c.cin / 32;
+    const int np = p.bf16 == 3 ? 3 : p.bf16 == 2 ? 2 : 1, ks = c.cin / 32;
     const size_t w = (size_t)(2 * np * ks + np * c.nt) * 1024;      // Wes (two stages) + Wps
     const int pairs = p.Ce / (2 * kC), cmax = ((pairs + G - 1) / G) * 2 * kC;      // channels of the largest group
     return ((size_t)2 * NE * row + (size_t)11 * cmax) * sizeof(float) + w;
@@ -372,7 +390,7 @@ int launch_image_block2(FusedBlockParams p, hipStream_t st) {
     SSD_CHECK_ARG(p.we3 && p.wp3, "image block: the bf16 forms need the weights' bf16 planes");
     const size_t lds = image2_lds_bytes(*c, p, p.groups);
     SSD_UNSUPPORTED_IF(lds > 160 * 1024, "image block (second form): needs %zu B of LDS", lds);
-    const image2_kernel_t fn = p.bf16 == 3 ? c->fn3 : c->fn1;
+    const image2_kernel_t fn = p.bf16 == 3 ? c->fn3 : p.bf16 == 2 ? c->fn2 : c->fn1;
     if (lds > 64 * 1024)
         SSD_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(fn, dim3((unsigned)((long)p.B * p.groups)), dim3(c->nw * 64), lds, st, p);

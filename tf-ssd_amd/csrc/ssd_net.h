@@ -50,6 +50,10 @@ struct Tensor {
     // producer a kernel whose plane store needs no fp32 copy, option "plane_only" 1.  Inference only: the training step
     // keeps activations of its own.  ssd_net_fetch_activation joins the planes (h + m + l is exact)
     bool plane_only = false;
+    // static bound of the tensor, from the weights alone (finalize_tensor_bounds, ssd_net.hip): every value any input can
+    // produce lies in [blo[c], bhi[c]] for channel c; bound = max |.| over the channels, < 0: no bound is known
+    std::vector<double> blo, bhi;
+    float bound = -1.f;
 };
 
 struct Layer {
@@ -83,13 +87,18 @@ struct Layer {
     int fused_by = -1;
     int e_out = -1;                 // whole-block LK_FUSED layer that must ALSO materialise its expanded map: that tensor
                                     // (block 13, whose expanded map is SSD feature map #1)
-    int img_choice = -1;            // whole-block LK_FUSED layers the image kernel can run: 1 / 2 = its fp32-MFMA / split-bf16 form won the finalize-time race against the layer kernels, 0 = it lost, -1 = not timed
+    int img_choice = -1;            // whole-block LK_FUSED layers the image kernel can run: 1 / 2 = its fp32-MFMA / split-bf16 form (with option image_f16x2 and a statically bounded input: the two-plane fp16 form in its place, same table line) won the finalize-time race against the layer kernels, 0 = it lost, -1 = not timed
     int fused_by2 = -1;             // depthwise / project members: their type-2 LK_FUSED layer
     Route route = RT_OFF;           // what runs this layer under the current options and tuning choices (resolve_routes, ssd_net.hip)
     float* splitk_part = nullptr;   // this layer's own split-K slab (layers may run concurrently)
     // LK_FUSED: weight copies with the folded BatchNorm scale multiplied in (per output channel)
     float *fz_we = nullptr, *fz_wd = nullptr, *fz_wp = nullptr;
     float *fz_we3 = nullptr, *fz_wp3 = nullptr;      // bf16 planes of fz_we / fz_wp for the split-bf16 band kernel (ssd_band3.hip)
+    // whole-block LK_FUSED layers the image kernel's second form takes, fp32 nets, option image_f16x2: the fp16 pairs
+    // [2][Ce][kpad_e] of 2^f16_ke fz_we and [2][npad_p][kpad_p] of 2^f16_kp fz_wp, and the exponent f16_s of the input's
+    // scale from its static bound; nullptr: the block has no bounded input (or non-finite weights) and keeps the bf16 split
+    float *fz_weh = nullptr, *fz_wph = nullptr;
+    int f16_ke = 0, f16_kp = 0, f16_s = 0;
     int side = 0;                   // 1, 2: runs on that side stream (SSD head convs)
     hipEvent_t ev_ready = nullptr;  // recorded on the main stream when this layer's OUTPUT is complete
 };
@@ -155,6 +164,7 @@ struct ssd_net {
     bool image_v2 = true;           // whole-image kernel only (the row-band kernels of blocks 1-6 have one form): the second form (ssd_imgblock2.hip: compile-time geometry, adjacent pixels per lane) where it has a configuration; 0 = the first form (A/B; equal within tolerance, not bitwise: the k-slot order inside the project MFMAs differs)
     bool conv_dma = true;           // offer the LDS-DMA tiles over pre-split activation planes (ssd_convdma.hip) to the autotune / accept them from tables
     bool conv_f16x2 = true;         // accept the two-plane fp16 tiles ("dmah_*") from tables / offer them to the autotune; 0: a "dmah_*" line runs its "dma3_*" twin (the same tile and split-K)
+    bool image_f16x2 = true;        // whole-image blocks of fp32 nets on the split route (img_choice 2): the two-plane fp16 form (three fp16 MFMAs per product in both 1x1 GEMMs) where the block's input has a static bound (Tensor::bound); 0: the split-bf16 form everywhere
     bool plane_only = true;         // drop the fp32 copy of an activation whose readers all take its bf16 planes (Tensor::plane_only); 0: store both
     bool image_ticket = false;      // combine the channel-group slabs inside the launch (arrival ticket) instead of by a second launch
     float* img_slabs = nullptr;     // its partial-sum slabs and arrival tickets (sized for max_batch)
@@ -165,6 +175,7 @@ struct ssd_net {
     float* arena = nullptr;
     size_t arena_bytes = 0, plane_bytes = 0, slab_bytes = 0;    // ssd_net_memory_bytes
     size_t wplane_bytes = 0;        // the fp16 weight planes of the layers on "dmah_*" tiles (counted with the planes)
+    size_t iplane_bytes = 0;        // the fp16 weight planes of the whole-image blocks (option image_f16x2; counted with the planes)
     float* splitk_ws = nullptr;
     size_t splitk_floats = 0;
     // predict() scratch

@@ -391,6 +391,18 @@ static FusedBlockParams fused_params(const ssd_net& net, const Layer& f, int B) 
         // (the in-launch ticketed combine exists for the fp32-MFMA form only: a no-op for the bf16 / split-bf16 forms)
         p.tickets = net.image_ticket && !p.bf16 ? net.img_tickets : nullptr;
         if (f.route == RT_IMAGE_SPLIT) { p.bf16 = 3; p.tickets = nullptr; }    // the split-bf16 form of the image kernel (fp32 results)
+        // ... or, with a statically bounded input (finalize_image_f16x2), its two-plane fp16 form where the second form
+        // takes the block at this group count
+        if (f.route == RT_IMAGE_SPLIT && net.image_f16x2 && net.image_v2 && f.fz_weh && f.fz_wph) {
+            FusedBlockParams q = p;
+            q.bf16 = 2;
+            q.we3 = reinterpret_cast<const short*>(f.fz_weh);
+            q.wp3 = reinterpret_cast<const short*>(f.fz_wph);
+            q.f16_xs = ldexpf(1.f, f.f16_s);
+            q.f16_es = ldexpf(1.f, -(f.f16_s + f.f16_ke));
+            q.f16_ps = ldexpf(1.f, -(8 + f.f16_kp));
+            if (image_block2_supported(q)) return q;
+        }
     }
     return p;
 }
@@ -627,7 +639,10 @@ static int tune_image_blocks(ssd_net& net, int B, hipStream_t st) {
         for (int choice = 0; choice < nchoice && !rc; ++choice) {
             f.img_choice = choice;
             resolve_routes(net);
-            if (choice == 2 && !image_block_split_fits(fused_params(net, f, B))) continue;
+            if (choice == 2) {          // (the form that will run: the fp16 pair where fused_params chose it, which then fits by construction)
+                const FusedBlockParams fp = fused_params(net, f, B);
+                if (fp.bf16 != 2 && !image_block_split_fits(fp)) continue;
+            }
             for (int trial = 0; trial < 4 && !rc; ++trial) {        // trial 0 warms up
                 (void)hipEventRecord(se0.e, st);
                 for (int r = 0; r < 4 && !rc; ++r)
@@ -1145,6 +1160,133 @@ static int finalize_fused_weights(ssd_net* net, hipStream_t st) {
     return SSD_OK;
 }
 
+// ---- static tensor bounds (host arithmetic, no device work: callable without a GPU)
+//
+// A 1x1 conv with BatchNorm folded in, y[n] = sum_c w'[n][c] d[c] + shift[n] (+ r[n]), whose input d lies in [0, 6] (a
+// ReLU6 map) and whose residual source r[n] lies in [res_lo[n], res_hi[n]], has its output channel n in
+//
+//     [ 6 sum_c min(w'[n][c], 0) + shift[n] + res_lo[n] ,  6 sum_c max(w'[n][c], 0) + shift[n] + res_hi[n] ]
+//
+// whatever the images are.  w' = fl32(w[n][c] * scale[n]) as launch_scale_rows folds it (scale nullptr: 1; shift nullptr:
+// 0; res_lo / res_hi nullptr: no residual); sums in double.  Returns 1 and fills lo / hi [n], or 0 when a weight, scale,
+// shift or residual bound is not finite: the tensor then has no bound.
+int ssd_block_output_interval(const float* w, int n, int k, int ld, const float* scale, const float* shift, const double* res_lo,
+                              const double* res_hi, double* lo, double* hi) {
+    SSD_CHECK_ARG(w && lo && hi && n >= 0 && k >= 0 && ld >= k && (res_lo == nullptr) == (res_hi == nullptr), "ssd_block_output_interval: bad arguments");
+    bool finite = true;
+    for (int r = 0; r < n; ++r) {
+        double neg = 0.0, pos = 0.0;
+        const float s = scale ? scale[r] : 1.f;
+        for (int c = 0; c < k; ++c) {
+            const float v = w[(size_t)r * ld + c] * s;
+            finite = finite && std::isfinite(v);
+            if (v < 0.f) neg += v; else pos += v;
+        }
+        const double h = shift ? (double)shift[r] : 0.0;
+        lo[r] = 6.0 * neg + h + (res_lo ? res_lo[r] : 0.0);
+        hi[r] = 6.0 * pos + h + (res_hi ? res_hi[r] : 0.0);
+        finite = finite && std::isfinite(lo[r]) && std::isfinite(hi[r]);
+    }
+    return finite ? 1 : 0;
+}
+// The exponent s of the input scale of the two-plane fp16 form from a tensor's bound: s = floor(log2(2^15 / bound)), so
+// that |2^s x| <= 2^15 < 65504 for every |x| <= bound.  Returns 1 and *s, or 0 when the bound is negative (unknown), not
+// finite, or s leaves [-12, 12] (a tensor that is all but zero, or astronomically large: its reader keeps the bf16 split).
+int ssd_f16x2_input_exp(float bound, int* s) {
+    if (s) *s = 0;
+    if (!(bound >= 0.f) || !std::isfinite(bound)) return 0;
+    if (bound == 0.f) return 0;
+    int e = 0;
+    const float f = std::frexp(bound, &e);            // bound = f 2^e, f in [0.5, 1)
+    const int v = f == 0.5f ? 16 - e : 15 - e;
+    if (v < -12 || v > 12) return 0;
+    if (s) *s = v;
+    return 1;
+}
+
+// Static bounds of every tensor a project conv behind a ReLU6 depthwise writes (alone or inside a fused block: the bound
+// is a property of the graph, like tensor_relu6_bounded, not of the routes): the interval above from the BN-folded weights
+// and shift, plus the residual source's interval.  Layers come in graph order, so a residual source is bounded first.
+static int finalize_tensor_bounds(ssd_net* net, hipStream_t st) {
+    for (auto& t : net->tensors) { t.blo.clear(); t.bhi.clear(); t.bound = -1.f; }
+    SSD_HIP(hipStreamSynchronize(st));
+    std::vector<float> w, sc, sh;
+    for (const Layer& l : net->layers) {
+        if (l.kind != LK_CONV || l.kh != 1 || l.kw != 1 || l.head_kind != 0 || l.out < 0 || l.in < 0 || l.act != SSD_ACT_NONE || !l.packed) continue;
+        bool relu6_dw = false, other = false;
+        for (const Layer& d : net->layers) {
+            if (d.kind == LK_FUSED || d.out != l.in) continue;
+            if (d.kind == LK_DW && d.act == SSD_ACT_RELU6) relu6_dw = true; else other = true;
+        }
+        if (!relu6_dw || other) continue;
+        Tensor& to = net->tensors[l.out];
+        const Tensor* tr = l.res >= 0 ? &net->tensors[l.res] : nullptr;
+        if (tr && (tr->bound < 0.f || (int)tr->blo.size() != l.Cout)) continue;       // an unbounded residual source
+        const int kpad = conv_kpad(l.Cin);
+        w.resize((size_t)l.Cout * kpad);
+        SSD_HIP(hipMemcpy(w.data(), l.packed, w.size() * sizeof(float), hipMemcpyDeviceToHost));
+        sc.assign(l.Cout, 1.f);
+        sh.assign(l.Cout, 0.f);
+        if (l.scale) SSD_HIP(hipMemcpy(sc.data(), l.scale, l.Cout * sizeof(float), hipMemcpyDeviceToHost));
+        if (l.shift) SSD_HIP(hipMemcpy(sh.data(), l.shift, l.Cout * sizeof(float), hipMemcpyDeviceToHost));
+        std::vector<double> lo(l.Cout), hi(l.Cout);
+        const int ok = ssd_block_output_interval(w.data(), l.Cout, l.Cin, kpad, sc.data(), sh.data(), tr ? tr->blo.data() : nullptr,
+                                                 tr ? tr->bhi.data() : nullptr, lo.data(), hi.data());
+        if (ok < 0) return ok;
+        if (!ok) continue;
+        double m = 0.0;
+        for (int c = 0; c < l.Cout; ++c) m = std::max(m, std::max(std::fabs(lo[c]), std::fabs(hi[c])));
+        float b = (float)m;
+        if ((double)b < m) b = std::nextafter(b, INFINITY);
+        if (!std::isfinite(b)) continue;
+        to.blo = std::move(lo);
+        to.bhi = std::move(hi);
+        to.bound = b;
+    }
+    return SSD_OK;
+}
+
+// Whole-image blocks on the two-plane fp16 form (option image_f16x2, fp32 nets): fp16 pairs of 2^ke fz_we and 2^kp fz_wp,
+// plain row-major like the bf16 planes the second form's LDS-DMA reads, for every block the image kernel can take whose
+// input has a static bound with a sane scale exponent and whose folded weights are finite.  Others keep the bf16 split.
+static int finalize_image_f16x2(ssd_net* net, hipStream_t st) {
+    net->iplane_bytes = 0;
+    for (auto& f : net->layers) { f.fz_weh = f.fz_wph = nullptr; f.f16_ke = f.f16_kp = f.f16_s = 0; }
+    if (!net->image_f16x2 || net->precision != 0 || !net->image_split) return SSD_OK;
+    ScopedDev bits_dev;
+    SSD_HIP(hipMalloc((void**)&bits_dev.p, 2 * sizeof(unsigned)));
+    for (auto& f : net->layers) {
+        if (f.kind != LK_FUSED || f.f_type != 0 || f.in < 0 || !image_kernel_takes(*net, f)) continue;
+        int s = 0;
+        if (!ssd_f16x2_input_exp(net->tensors[f.in].bound, &s)) continue;
+        FusedBlockParams q = fused_shape(*net, f, 1);
+        q.bf16 = 2; q.groups = q.Ce / 32;      // (the form's smallest LDS footprint: does the second form have the shape at all?)
+        q.we3 = q.wp3 = reinterpret_cast<const short*>(f.fz_we);
+        if (!image_block2_supported(q)) continue;
+        const Layer& le = net->layers[f.f_expand];
+        const Layer& lp = net->layers[f.f_project];
+        unsigned bits[2] = {0, 0};
+        SSD_HIP(hipMemsetAsync(bits_dev.p, 0, 2 * sizeof(unsigned), st));
+        int rc = launch_absmax_bits(f.fz_we, le.Cin, le.Cout, reinterpret_cast<unsigned*>(bits_dev.p), st);
+        if (!rc) rc = launch_absmax_bits(f.fz_wp, lp.Cin, lp.Cout, reinterpret_cast<unsigned*>(bits_dev.p) + 1, st);
+        if (rc) return rc;
+        SSD_HIP(hipMemcpyAsync(bits, bits_dev.p, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        SSD_HIP(hipStreamSynchronize(st));
+        if (bits[0] >= 0x7f800000u || bits[1] >= 0x7f800000u) continue;       // a non-finite weight
+        const int ke = conv_f16x2_weight_exp(bits[0]), kp = conv_f16x2_weight_exp(bits[1]);
+        if (std::abs(s + ke) > 100 || std::abs(8 + kp) > 100) continue;       // (2^-(s + ke), 2^-(8 + kp) must be normal floats)
+        f.f16_s = s; f.f16_ke = ke; f.f16_kp = kp;
+        const size_t fe = (conv_f16x2_plane_shorts(le.Cin, le.Cout) + 1) / 2, fp = (conv_f16x2_plane_shorts(lp.Cin, lp.Cout) + 1) / 2;
+        rc = dev_alloc(*net, fe, &f.fz_weh);
+        if (!rc) rc = dev_alloc(*net, fp, &f.fz_wph);
+        if (!rc) rc = launch_pack_f16x2(f.fz_we, le.Cin, le.Cout, f.f16_ke, reinterpret_cast<short*>(f.fz_weh), st, true);
+        if (!rc) rc = launch_pack_f16x2(f.fz_wp, lp.Cin, lp.Cout, f.f16_kp, reinterpret_cast<short*>(f.fz_wph), st, true);
+        if (rc) return rc;
+        net->iplane_bytes += (fe + fp) * sizeof(float);
+    }
+    return SSD_OK;
+}
+
 // Whole-image block kernel: slab workspace for the largest (groups x batch) product any batch
 // up to max_batch can ask for, and the arrival tickets (zero between launches).
 static int finalize_image_slabs(ssd_net* net, int max_batch, hipStream_t st) {
@@ -1360,6 +1502,8 @@ int ssd_net_finalize(ssd_net* net, int max_batch) {
         if (rc) return rc;
     }
     rc = finalize_fused_weights(net, st);
+    if (!rc) rc = finalize_tensor_bounds(net, st);
+    if (!rc) rc = finalize_image_f16x2(net, st);
     if (!rc) rc = finalize_image_slabs(net, max_batch, st);
     if (!rc) rc = finalize_arena(net, max_batch, st);
     bool image_preset_ok = true;
@@ -1412,6 +1556,16 @@ int ssd_net_memory_bytes(const ssd_net* net, size_t out[4]) {
         if (l.kind == LK_CONV && l.split_k > 1) sk += align_up((size_t)l.split_k * net->max_batch * l.Ho * l.Wo * l.Cout, 64);
     out[3] = sk * sizeof(float);
     return SSD_OK;
+}
+
+// ... and on top of those, the fp16 weight planes of its whole-image blocks (option image_f16x2)
+size_t ssd_net_image_f16x2_bytes(const ssd_net* net) { return net && net->finalized ? net->iplane_bytes : 0; }
+
+// Static bound of a named tensor (finalize_tensor_bounds): max |x| over every input, from the weights alone; < 0: none known
+float ssd_net_tensor_bound(const ssd_net* net, const char* tensor) {
+    if (!net || !tensor || !net->finalized) return -1.f;
+    auto it = net->tensor_index.find(tensor);
+    return it == net->tensor_index.end() ? -1.f : net->tensors[it->second].bound;
 }
 
 int ssd_net_tuning_stats(const ssd_net* net, int* from_table, int* timed) {
@@ -1762,6 +1916,9 @@ static const OptionSpec kOptions[] = {
     {"image_v2", &ssd_net::image_v2, nullptr, 0, 1, 0},
     {"conv_dma", &ssd_net::conv_dma, nullptr, 0, 1, 1},         // LDS-DMA conv tiles over pre-split activation planes (default 1)
     {"conv_f16x2", &ssd_net::conv_f16x2, nullptr, 0, 1, 1},     // two-plane fp16 tiles "dmah_*" on ReLU6-bounded inputs (default 1); 0: such a table line runs its "dma3_*" twin
+    // whole-image blocks on the split route: the two-plane fp16 form where the input has a static bound (default 1); 0: the
+    // split-bf16 form everywhere (its fp16 weight planes are then not packed)
+    {"image_f16x2", &ssd_net::image_f16x2, nullptr, 0, 1, 1},
     {"plane_only", &ssd_net::plane_only, nullptr, 0, 1, 0},     // no fp32 copy of an activation whose readers all take its planes (default 1)
     {"use_graph", &ssd_net::use_graph, nullptr, 0, 1, 0},
 };
@@ -1911,6 +2068,15 @@ const char* ssd_net_layer_config(const ssd_net* net, int i) {
     else snprintf(buf, sizeof(buf), "%s", conv_config_name(l.cfg));
     return buf;
 }
+// Which form of the whole-image kernel runs layer i at batch B: -1 the layer is not routed to it, 0 the fp32 MFMA, 1 the
+// bf16 mode, 3 the split-bf16 form, 2 the two-plane fp16 form (the number of planes per matrix operand)
+int ssd_net_layer_image_form(const ssd_net* net, int i, int B) {
+    if (!net || i < 0 || i >= (int)net->layers.size() || B < 1) return -1;
+    const Layer& f = net->layers[i];
+    if (f.kind != LK_FUSED || (f.route != RT_IMAGE && f.route != RT_IMAGE_SPLIT)) return -1;
+    return fused_params(*net, f, B).bf16;
+}
+
 static double algorithmic_flops(const Layer& l, int B) {
     const double px = (double)B * l.Ho * l.Wo;
     if (l.kind == LK_CONV) return 2.0 * px * l.kh * l.kw * l.Cin * l.Cout;

@@ -14,7 +14,7 @@ import ssd_hip as _h
 # options that change which kernel configurations finalize may choose (the memo is per option set)
 _TABLE_OPTIONS = ("use_wino", "image_split", "conv_dma")
 # options that make the native net drop `finalized` (ssd_net_set_option): the Python handle must re-finalize too
-_REFINALIZE_OPTIONS = ("precision", "image_split", "use_wino", "conv_dma", "conv_f16x2")
+_REFINALIZE_OPTIONS = ("precision", "image_split", "use_wino", "conv_dma", "conv_f16x2", "image_f16x2")
 _STALE_WARNED = set()
 
 
@@ -370,7 +370,22 @@ class SSDModel(object):
         replica of ``get_decoder_model(..., lanes=n)`` holds the same again."""
         out = (ctypes.c_size_t * 4)()
         _h.check(_h.lib().ssd_net_memory_bytes(self._net, out), "ssd_net_memory_bytes")
-        return {"arena": int(out[0]), "planes": int(out[1]), "image_slabs": int(out[2]), "splitk_slabs": int(out[3])}
+        return {"arena": int(out[0]), "planes": int(out[1]), "image_slabs": int(out[2]), "splitk_slabs": int(out[3]),
+                "image_weight_planes": int(_h.lib().ssd_net_image_f16x2_bytes(self._net))}
+
+    def tensor_bound(self, name):
+        """Static bound of a named tensor of the finalized net (``ssd_net_tensor_bound``): max |x| over every input, from
+        the weights alone; ``None`` where none is known."""
+        b = float(_h.lib().ssd_net_tensor_bound(self._net, name.encode()))
+        return b if b >= 0 else None
+
+    def image_forms(self, B):
+        """Layer name -> form of the whole-image block kernel that runs it at batch ``B`` (``ssd_net_layer_image_form``):
+        0 fp32 MFMA, 1 bf16 mode, 3 split-bf16, 2 the two-plane fp16 form; layers on other kernels are left out."""
+        lib = _h.lib()
+        forms = {lib.ssd_net_layer_name(self._net, i).decode(): lib.ssd_net_layer_image_form(self._net, i, B)
+                 for i in range(lib.ssd_net_num_layers(self._net))}
+        return {k: v for k, v in forms.items() if v >= 0}
 
     def set_tuning(self, text):
         """Pin the kernel choices (a table from ``get_tuning()`` of another instance, or a file): the next

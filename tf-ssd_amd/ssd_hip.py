@@ -270,6 +270,13 @@ _SIGNATURES = {
     "ssd_net_set_tuning": (ctypes.c_int, [vp, ctypes.c_char_p]),
     "ssd_net_tuning_stats": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "ssd_net_memory_bytes": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_size_t)]),
+    "ssd_net_image_f16x2_bytes": (ctypes.c_size_t, [vp]),
+    "ssd_net_tensor_bound": (ctypes.c_float, [vp, ctypes.c_char_p]),
+    "ssd_block_output_interval": (ctypes.c_int, [c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_float_p, c_float_p,
+                                                 ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                                 ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "ssd_f16x2_input_exp": (ctypes.c_int, [ctypes.c_float, c_int_p]),
+    "ssd_net_layer_image_form": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
     "ssd_build_id": (ctypes.c_char_p, []),
     "ssd_stream_create": (vp, [ctypes.c_int]),
     "ssd_stream_create_masked": (vp, [ctypes.POINTER(ctypes.c_uint), ctypes.c_int]),

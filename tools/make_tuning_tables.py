@@ -17,6 +17,10 @@ included) is handed to finalize as it stands, so only those layers are raced -- 
 few layers and leaves every other kernel as it was.  `--restamp` (CPU) writes the current build id into the shipped
 tables WITHOUT measuring; re-measured tables are copied over them afterwards.  Only for a change that leaves every kernel
 the remaining tables can name as it was.
+
+A name given to `--retime` may also be a whole-block layer (`block_7_fused`: its `image 0|1|2` line is dropped, so finalize
+races the whole-image kernel's forms against the layer kernels for that block alone) or `image-blocks`, every such line of
+the table -- for a change to the whole-image kernel, such as a new form behind the same `image 2` line.
 """
 import argparse
 import collections
@@ -82,7 +86,10 @@ def generate(args):
             if shipped is None:
                 print("%-40s no shipped table to start from: skipped" % key, flush=True)
                 continue
-            preset = "".join(l + "\n" for l in tuning.body(shipped).splitlines() if l.split(" ")[0] not in args.retime)
+            def kept(l):
+                parts = l.split(" ")
+                return parts[0] not in args.retime and not ("image-blocks" in args.retime and len(parts) == 3 and parts[1] == "image")
+            preset = "".join(l + "\n" for l in tuning.body(shipped).splitlines() if kept(l))
         for r in range(args.repeats):
             m = SSDModel(bb, hp, max_batch=B, precision=prec)
             m.set_weights(w)
@@ -142,7 +149,7 @@ if __name__ == "__main__":
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--shapes", nargs="*", help="backbone:size:batch[:bf16] ...")
     ap.add_argument("--adopt")
-    ap.add_argument("--retime", nargs="*", help="conv layer names: race only these, keep the shipped table's other lines")
+    ap.add_argument("--retime", nargs="*", help="conv layer / whole-block layer names, or image-blocks: race only these, keep the shipped table's other lines")
     ap.add_argument("--restamp", action="store_true")
     a = ap.parse_args()
     restamp(a) if a.restamp else adopt(a) if a.adopt else generate(a)
