@@ -72,7 +72,7 @@ struct FusedBlockParams {
     int tiles_y, tiles_x;       // filled by the launcher
     // whole-image kernel (csrc/ssd_imgblock.hip): expanded-channel groups per image and their meeting point
     int bf16;                   // the net's precision-1 mode: bf16 forms of the band / whole-image kernels (operands rounded once to bf16, one MFMA per product)
-    int groups;                 // G >= 1 (filled by the caller from image_block_groups)
+    int groups;                 // G >= 1 (ImagePlan::groups)
     const short* we3;           // split-bf16 band kernel (csrc/ssd_band3.hip): bf16 planes of we [4][Ce][32] (h, m, l, r) ...
     const short* wp3;           // ... and of wp [4][npad_p][pairs][4][8]
     int bands;                  // row-band kernels (csrc/ssd_band_common.h): bands per image (filled by the launcher)
@@ -89,7 +89,7 @@ struct FusedBlockParams {
     int e_planes_np;            // ... of the expanded map's planes (its consumers may take another family than y's: 2 = the fp16 pair)
     int planes_only;            // whole-image kernel: bit 0 = y, bit 1 = the expanded map leave as planes ONLY (no fp32 store; every
                                 // consumer reads the planes).  The pointers y / e_out stay set: they also say which shapes a kernel takes
-    int form2;                  // whole-image kernel only: 1 = take the second form (csrc/ssd_imgblock2.hip) where it has a configuration.  The row-band kernels have one form and ignore it
+    int form2;                  // unused (kept: the struct is the kernels' argument); ImagePlan::second says which form runs
     // whole-image kernel, second form, bf16 == 2 -- the two-plane fp16 form (fp32 results, three fp16 MFMAs per product in
     // BOTH 1x1 GEMMs; ssd_bf16x3.h): we3 / wp3 are then the fp16 pairs [2][Ce][kpad_e] of 2^ke we and [2][npad_p][kpad_p] of
     // 2^kp wp, and these three exact powers of two: x is split as the pair of f16_xs x = 2^s x (s from the static bound of
@@ -130,8 +130,6 @@ bool dwproj_supported(const DwProjParams& p);
 int launch_dwproj(DwProjParams p, hipStream_t st);
 bool stem_supported(const StemParams& p);
 int launch_stem(StemParams p, hipStream_t st);
-bool image_block2_supported(const FusedBlockParams& p);
-int launch_image_block2(FusedBlockParams p, hipStream_t st);
 bool fused_block_supported(const FusedBlockParams& p);
 int launch_fused_block(FusedBlockParams p, hipStream_t st);
 bool band3_block_supported(const FusedBlockParams& p);
@@ -142,11 +140,35 @@ int launch_band3_pack(const float* we, int Ce, int Cin, int kpad_e, short* we3, 
 int launch_band3_block(FusedBlockParams p, hipStream_t st);
 bool band_block_supported(const FusedBlockParams& p);
 int launch_band_block(FusedBlockParams p, hipStream_t st);
-bool image_block_supported(const FusedBlockParams& p);
-bool image_block_split_fits(FusedBlockParams p);     // the split-bf16 form's LDS tiles fit at p.groups
-int image_block_groups(const FusedBlockParams& p, int B);
-size_t image_block_slab_floats(const FusedBlockParams& p, int B);
-int launch_image_block(FusedBlockParams p, hipStream_t st);
+// ---- whole-image kernel (ssd_imgblock.hip, ssd_imgblock2.hip): what the net asks for one block at one batch ...
+struct ImageAsk {
+    int precision;              // the net's: 0 fp32 results, 1 the bf16 mode
+    bool split;                 // fp32 net: the split-bf16 form (table line `image 2`)
+    bool second;                // option image_v2: the second code form where it has the block's geometry
+    bool pairs;                 // option image_f16x2 and the block's fp16 weight pairs exist: the two-plane fp16 form
+    bool ticket;                // option image_ticket: the groups combine inside the launch
+    bool slabs;                 // the slab workspace exists (without it: one group)
+    long lanes;                 // images in flight: B * lanes_hint
+};
+// ... and what runs: every choice between the kernels' forms is made by image_block_plan, nowhere else
+struct ImagePlan {
+    int form;                   // FusedBlockParams::bf16 as the kernel reads it: 0 fp32 MFMA, 1 bf16 mode, 2 fp16 pair, 3 split-bf16
+    bool second;                // the second code form (ssd_imgblock2.hip)
+    int groups;                 // expanded-channel groups per image
+    size_t lds;                 // dynamic LDS bytes
+    const void* fn;             // the kernel and its block size
+    int threads;
+    bool ticketed;              // groups > 1 meet at FusedBlockParams::tickets inside the launch ...
+    bool combine;               // ... or in image_combine_kernel, a second launch
+};
+bool image_block_supported(const FusedBlockParams& shape);
+int image_block_groups(const FusedBlockParams& shape, long lanes);
+size_t image_block_slab_floats(const FusedBlockParams& shape, int B);
+// `shape`: the block as fused_shape leaves it (bf16 = the net's precision).  SSD_E_UNSUPPORTED where no kernel takes it
+int image_block_plan(const FusedBlockParams& shape, const ImageAsk& ask, ImagePlan* plan);
+bool image_second_form(const FusedBlockParams& shape, int form, int groups, ImagePlan* plan);   // (image_block_plan's only)
+// launches `plan` on parameters filled from it (bf16, groups, tickets, the form's weight planes): no choice, no fallback
+int launch_image_block(const FusedBlockParams& p, const ImagePlan& plan, hipStream_t st);
 
 inline int round_up(int v, int a) { return (v + a - 1) / a * a; }
 inline int conv_kpad(int K) { return round_up(K, 32); }

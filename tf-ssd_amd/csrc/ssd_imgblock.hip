@@ -40,6 +40,7 @@ namespace {
 constexpr int kIC = 16;           // expanded channels per chunk
 constexpr int kILD = 24;          // LDS row stride (floats) of the E / Wp chunk tiles: 6 quads, conflict-free b128 fragments
 constexpr int kIThreads = 512;
+constexpr size_t kImageLdsMax = 160 * 1024;
 
 // write-through (sc1) 16-byte store: the slab lines do not stay dirty in this XCD's L2, so publishing
 // them needs no L2 write-back fence (cdna_hip_programming.md, in-launch split-K reduction)
@@ -686,10 +687,10 @@ const ImageCfg kImage[] = {
     ICFG2(96, 10, 3),   // block 13:     96 -> 576 -> 160, depthwise stride 2 (19x19 -> 10x10), E written out
 };
 
-size_t image_lds_bytes(const ImageCfg& c, const FusedBlockParams& p, int G) {
+size_t image_lds_bytes(const ImageCfg& c, const FusedBlockParams& p, int form, int G) {
     const int P = p.W + 1, npt = (p.H * P + 15) / 16, NE = npt * 16 + 2 * P + 2;
-    if (p.bf16) {
-        const int np = p.bf16 == 3 ? 3 : 1, ks = c.cin / 32;
+    if (form) {
+        const int np = form == 3 ? 3 : 1, ks = c.cin / 32;
         const size_t w = (size_t)(2 * np * 16 * (ks * 32 + 16) + np * c.nt * 16 * 32) * sizeof(short);      // Wes + Wps
         return ((size_t)2 * NE * kILD + (size_t)11 * (p.Ce / G) + 4) * sizeof(float) + w;
     }
@@ -698,6 +699,7 @@ size_t image_lds_bytes(const ImageCfg& c, const FusedBlockParams& p, int G) {
     return fl * sizeof(float);
 }
 
+// the first form's configuration of a block shape (p.bf16: the net's precision)
 const ImageCfg* pick_image(const FusedBlockParams& p) {
     if (p.Ce % kIC != 0 || p.Cout % 16 != 0 || p.kpad_e % 4 != 0 || p.kpad_p % 4 != 0) return nullptr;
     if (p.stride == 1 && (p.H != p.Ho || p.W != p.Wo)) return nullptr;
@@ -707,11 +709,9 @@ const ImageCfg* pick_image(const FusedBlockParams& p) {
     if (p.stride != 1 && p.stride != 2) return nullptr;
     if (p.residual && p.Cin != p.Cout) return nullptr;
     const int npt = (p.H * (p.W + 1) + 15) / 16;
-    FusedBlockParams q = p;
-    if (q.bf16 == 3) q.bf16 = 0;        // the split form falls back to the fp32 form where its weight tiles do not fit
     for (const auto& c : kImage)
         if (c.cin == p.Cin && c.nt * 16 == p.Cout && c.stride == p.stride && npt <= 8 * c.t && npt > 8 * (c.t == 3 ? 1 : 0) &&
-            image_lds_bytes(c, q, 1) <= 160 * 1024)
+            image_lds_bytes(c, p, p.bf16 ? 1 : 0, 1) <= kImageLdsMax)
             return &c;
     return nullptr;
 }
@@ -719,15 +719,10 @@ const ImageCfg* pick_image(const FusedBlockParams& p) {
 }  // namespace
 
 bool image_block_supported(const FusedBlockParams& p) { return pick_image(p) != nullptr; }
-bool image_block_split_fits(FusedBlockParams p) {
-    const ImageCfg* c = pick_image(p);
-    p.bf16 = 3;
-    return c && p.we3 && p.wp3 && image_lds_bytes(*c, p, p.groups < 1 ? 1 : p.groups) <= 160 * 1024;
-}
 
-// Number of expanded-channel groups for batch B: the smallest divisor of Ce / 16 that fills the
+// Number of expanded-channel groups for `lanes` images in flight: the smallest divisor of Ce / 16 that fills the
 // CUs (one workgroup per CU: 78-120 KB of LDS), at most 12.
-int image_block_groups(const FusedBlockParams& p, int B) {
+int image_block_groups(const FusedBlockParams& p, long lanes) {
     static int num_cu = 0;
     if (!num_cu) {
         int dev = 0;
@@ -740,7 +735,7 @@ int image_block_groups(const FusedBlockParams& p, int B) {
     for (int g = 1; g <= 12 && g <= units; ++g) {
         if (units % g) continue;
         best = g;
-        if ((long)B * g * 8 >= (long)num_cu * 7) break;
+        if (lanes * g * 8 >= (long)num_cu * 7) break;
     }
     return best;
 }
@@ -750,43 +745,55 @@ size_t image_block_slab_floats(const FusedBlockParams& p, int B) {
     return G > 1 ? (size_t)G * B * p.Ho * p.Wo * p.Cout : 0;
 }
 
-int launch_image_block(FusedBlockParams p, hipStream_t st) {
-    const ImageCfg* c = pick_image(p);
-    if (!c) {
-        set_error("image block: unsupported shape Cin=%d Ce=%d Cout=%d %dx%d stride=%d", p.Cin, p.Ce, p.Cout, p.H, p.W, p.stride);
-        return SSD_E_UNSUPPORTED;
+// The one decision between the forms of the whole-image kernel; every rule is a line here, in order of precedence.  No
+// rule changes a form because of LDS: every form of every block shape the tables hold fits at every group count
+// (enumerated in profiles/HISTORY.md, "One plan for the whole-image blocks"), so a form that does not fit is an error.
+int image_block_plan(const FusedBlockParams& s, const ImageAsk& ask, ImagePlan* plan) {
+    *plan = ImagePlan{};
+    const ImageCfg* c = pick_image(s);
+    SSD_UNSUPPORTED_IF(!c, "image block: unsupported shape Cin=%d Ce=%d Cout=%d %dx%d stride=%d", s.Cin, s.Ce, s.Cout, s.H, s.W, s.stride);
+    ImagePlan pl{};
+    pl.threads = kIThreads;
+    pl.groups = ask.slabs ? image_block_groups(s, ask.lanes) : 1;
+    // the numeric form: the bf16 net's one product; the fp32 net's split-bf16 where the table asks for it, else fp32 MFMAs
+    pl.form = ask.precision ? 1 : ask.split ? 3 : 0;
+    // (the first form's tiles of that form must fit even where the second form will run: as it always was)
+    pl.lds = image_lds_bytes(*c, s, pl.form, pl.groups);
+    SSD_UNSUPPORTED_IF(pl.lds > kImageLdsMax, "image block: needs %zu B of LDS", pl.lds);
+    pl.fn = (const void*)(pl.form == 3 ? c->fn3 : pl.form ? c->fn16 : c->fn);
+    // the second code form has the bf16-operand forms only, one geometry per block -- and alone the two-plane fp16 form,
+    // which replaces the split-bf16 form there wherever the weight pairs exist
+    const int form_v2 = pl.form == 3 && ask.pairs ? 2 : pl.form;
+    if (ask.second && form_v2 && image_second_form(s, form_v2, pl.groups, &pl)) {
+        pl.second = true;
+        pl.form = form_v2;
+        SSD_UNSUPPORTED_IF(pl.groups > s.Ce / 32, "image block (second form): %d groups of %d chunk pairs", pl.groups, s.Ce / 32);
+        SSD_UNSUPPORTED_IF(pl.lds > kImageLdsMax, "image block (second form): needs %zu B of LDS", pl.lds);
     }
+    // groups > 1 combine in a second launch: the launch boundary publishes the slabs and every CU takes part (B=64: 43 us per
+    // block 7 instead of 46).  Option image_ticket, the fp32-MFMA form only: the last arriving group of an image combines in the launch
+    pl.ticketed = ask.ticket && pl.form == 0;
+    pl.combine = pl.groups > 1 && !pl.ticketed;
+    *plan = pl;
+    return SSD_OK;
+}
+
+int launch_image_block(const FusedBlockParams& p, const ImagePlan& plan, hipStream_t st) {
     if (p.B == 0) return SSD_OK;
-    if (p.groups < 1) p.groups = 1;
+    SSD_CHECK_ARG(plan.fn && p.bf16 == plan.form && p.groups == plan.groups, "image block: the parameters are not the plan's");
     SSD_CHECK_ARG(!(p.planes_only & 1) || p.y_planes, "image block: plane-only y without planes");
     SSD_CHECK_ARG(!(p.planes_only & 2) || (p.e_out && p.e_planes), "image block: plane-only expanded map without planes");
     SSD_CHECK_ARG(!p.planes_only || !p.tickets, "image block: plane-only outputs combine by the second launch only");
     SSD_CHECK_ARG((p.Ce / kIC) % p.groups == 0, "image block: %d groups do not divide Ce/16 = %d", p.groups, p.Ce / kIC);
     SSD_CHECK_ARG(p.groups == 1 || p.slabs, "image block: %d groups need the slab workspace", p.groups);
-    // the two-plane fp16 form exists in the second form only: the caller asks for it where that form takes the block
-    SSD_UNSUPPORTED_IF(p.bf16 == 2 && !(p.form2 && !p.tickets && image_block2_supported(p)),
-                       "image block: the two-plane fp16 form has no kernel for Cin=%d Ce=%d Cout=%d %dx%d at %d groups", p.Cin, p.Ce, p.Cout, p.H, p.W, p.groups);
-    if (p.bf16 == 3 && image_lds_bytes(*c, p, p.groups) > 160 * 1024) p.bf16 = 0;      // split form's weight tiles do not fit: fp32 form
-    const size_t lds = image_lds_bytes(*c, p, p.groups);
-    SSD_UNSUPPORTED_IF(lds > 160 * 1024, "image block: needs %zu B of LDS", lds);
     SSD_CHECK_ARG(!p.bf16 || (p.we3 && p.wp3), "image block: the bf16 form needs the weights' bf16 planes");
     SSD_CHECK_ARG(!p.bf16 || !p.tickets, "image block: the bf16 form combines by the second launch only");
-    const image_kernel_t fn = p.bf16 == 3 ? c->fn3 : p.bf16 ? c->fn16 : c->fn;
-    const bool second = p.form2 && p.bf16 && !p.tickets && image_block2_supported(p);
-    if (second) {
-        const int rc = launch_image_block2(p, st);
-        if (rc) return rc;
-    }
-    if (lds > 64 * 1024 && !second)
-        SSD_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    // groups > 1: p.tickets == nullptr (default) combines the group slabs in a second launch -- the
-    // launch boundary publishes them and every CU takes part (B=64: 43 us per block 7 instead of 46);
-    // with tickets the last arriving group of each image combines inside the launch.
-    if (!second) {
-        hipLaunchKernelGGL(fn, dim3((unsigned)((long)p.B * p.groups)), dim3(kIThreads), lds, st, p);
-        SSD_LAUNCH_CHECK();
-    }
-    if (p.groups > 1 && !p.tickets) {
+    if (plan.lds > 64 * 1024)
+        SSD_HIP(hipFuncSetAttribute(plan.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
+    hipLaunchKernelGGL(reinterpret_cast<image_kernel_t>(const_cast<void*>(plan.fn)), dim3((unsigned)((long)p.B * p.groups)),
+                       dim3(plan.threads), plan.lds, st, p);
+    SSD_LAUNCH_CHECK();
+    if (plan.combine) {
         const long nvec = (long)p.B * p.Ho * p.Wo * p.Cout / 4;
         const int blocks = (int)((nvec + 255) / 256 < 4096 ? (nvec + 255) / 256 : 4096);
         hipLaunchKernelGGL(image_combine_kernel, dim3(blocks), dim3(256), 0, st, p.slabs, p.ph, p.residual ? p.x : nullptr, p.y,

@@ -349,17 +349,16 @@ const Image2Cfg kImage2[] = {       // (one loop form per shape)
     I2CFG(160, 20, 8, 1, 10, 10, 1),   // block 16:     160 -> 960 -> 320
 };
 
-
-size_t image2_lds_bytes(const Image2Cfg& c, const FusedBlockParams& p, int G) {
+size_t image2_lds_bytes(const Image2Cfg& c, int Ce, int form, int G) {
     const int P = c.w + 1, npix = c.nw * 16 * c.t, NE = npix + 2 * P + 2, row = c.stride == 2 ? 20 : (c.t & 1) ? 24 : 20;
-    const int np = p.bf16 == 3 ? 3 : p.bf16 == 2 ? 2 : 1, ks = c.cin / 32;
+    const int np = form == 3 ? 3 : form == 2 ? 2 : 1, ks = c.cin / 32;
     const size_t w = (size_t)(2 * np * ks + np * c.nt) * 1024;      // Wes (two stages) + Wps
-    const int pairs = p.Ce / (2 * kC), cmax = ((pairs + G - 1) / G) * 2 * kC;      // channels of the largest group
+    const int pairs = Ce / (2 * kC), cmax = ((pairs + G - 1) / G) * 2 * kC;      // channels of the largest group
     return ((size_t)2 * NE * row + (size_t)11 * cmax) * sizeof(float) + w;
 }
 
 const Image2Cfg* pick_image2(const FusedBlockParams& p) {
-    if (!p.bf16 || p.Ce % (2 * kC) != 0 || p.kpad_e % 32 != 0 || p.kpad_p % 32 != 0) return nullptr;
+    if (p.Ce % (2 * kC) != 0 || p.kpad_e % 32 != 0 || p.kpad_p % 32 != 0) return nullptr;
     if (p.stride == 1 && (p.e_out || p.H != p.Ho || p.W != p.Wo)) return nullptr;
     if (p.stride == 2 && (p.residual || p.Ho != (p.H + 1) / 2 || p.Wo != (p.W + 1) / 2 || p.pad_t < 0 || p.pad_t > 1 || p.pad_l < 0 || p.pad_l > 1)) return nullptr;
     if (p.stride != 1 && p.stride != 2) return nullptr;
@@ -371,31 +370,15 @@ const Image2Cfg* pick_image2(const FusedBlockParams& p) {
 
 }  // namespace
 
-bool image_block2_supported(const FusedBlockParams& p) {
-    const Image2Cfg* c = pick_image2(p);
-    const int G = p.groups < 1 ? 1 : p.groups;
-    return c && p.we3 && p.wp3 && G <= p.Ce / (2 * kC) && image2_lds_bytes(*c, p, G) <= 160 * 1024;
-}
-
-int launch_image_block2(FusedBlockParams p, hipStream_t st) {
-    const Image2Cfg* c = pick_image2(p);
-    if (!c) {
-        set_error("image block (second form): unsupported shape Cin=%d Ce=%d Cout=%d %dx%d stride=%d", p.Cin, p.Ce, p.Cout, p.H, p.W, p.stride);
-        return SSD_E_UNSUPPORTED;
-    }
-    if (p.B == 0) return SSD_OK;
-    if (p.groups < 1) p.groups = 1;
-    SSD_CHECK_ARG(p.groups <= p.Ce / (2 * kC), "image block (second form): %d groups of %d chunk pairs", p.groups, p.Ce / (2 * kC));
-    SSD_CHECK_ARG(p.groups == 1 || p.slabs, "image block: %d groups need the slab workspace", p.groups);
-    SSD_CHECK_ARG(p.we3 && p.wp3, "image block: the bf16 forms need the weights' bf16 planes");
-    const size_t lds = image2_lds_bytes(*c, p, p.groups);
-    SSD_UNSUPPORTED_IF(lds > 160 * 1024, "image block (second form): needs %zu B of LDS", lds);
-    const image2_kernel_t fn = p.bf16 == 3 ? c->fn3 : p.bf16 == 2 ? c->fn2 : c->fn1;
-    if (lds > 64 * 1024)
-        SSD_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(fn, dim3((unsigned)((long)p.B * p.groups)), dim3(c->nw * 64), lds, st, p);
-    SSD_LAUNCH_CHECK();
-    return SSD_OK;         // (groups > 1: the caller, launch_image_block, adds image_combine_kernel)
+// The second form's line of image_block_plan: its kernel, block size and LDS bytes of a numeric form (1, 2, 3) at `groups`
+// where kImage2 has the block's geometry; false where it has not (the first form runs)
+bool image_second_form(const FusedBlockParams& shape, int form, int groups, ImagePlan* plan) {
+    const Image2Cfg* c = pick_image2(shape);
+    if (!c) return false;
+    plan->fn = (const void*)(form == 3 ? c->fn3 : form == 2 ? c->fn2 : c->fn1);
+    plan->threads = c->nw * 64;
+    plan->lds = image2_lds_bytes(*c, shape.Ce, form, groups);
+    return true;
 }
 
 }  // namespace ssd

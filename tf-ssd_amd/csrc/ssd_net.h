@@ -20,6 +20,7 @@ static const char* kKindName[] = {"conv", "dw", "pool", "l2norm", "softmax", "fu
 // member of a fused layer that runs).  RT_LAYER: the layer's own kernel (conv / dw / pool / l2norm / softmax).  The
 // rest are the kernel families of an LK_FUSED layer; the precision suffix of their names follows ssd_net::precision.
 enum Route { RT_OFF = 0, RT_LAYER, RT_STEM, RT_DWPROJ, RT_TILE, RT_BAND, RT_BAND3, RT_IMAGE, RT_IMAGE_SPLIT };
+inline bool route_is_image(Route r) { return r == RT_IMAGE || r == RT_IMAGE_SPLIT; }     // the whole-image kernel, any form
 
 struct Param {
     std::string name;

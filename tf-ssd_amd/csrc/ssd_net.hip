@@ -370,39 +370,48 @@ static FusedBlockParams fused_shape(const ssd_net& net, const Layer& f, int B) {
         const Tensor& te = net.tensors[f.e_out];
         p.e_planes = te.planes; p.e_plane = te.plane_stride; p.e_planes_np = te.planes_np;
     }
-    if (f.route == RT_IMAGE || f.route == RT_IMAGE_SPLIT)     // plane-only outputs: no fp32 store (the pointers stay: they take part in the shape checks)
+    if (route_is_image(f.route))     // plane-only outputs: no fp32 store (the pointers stay: they take part in the shape checks)
         p.planes_only = (p.y_planes && net.tensors[f.out].plane_only ? 1 : 0) | (p.e_planes && net.tensors[f.e_out].plane_only ? 2 : 0);
     p.we3 = reinterpret_cast<const short*>(f.fz_we3);        // band kernel's plane layout (blocks 1-6) ...
     p.wp3 = reinterpret_cast<const short*>(f.fz_wp3);
     p.bf16 = net.precision;
-    p.form2 = net.image_v2 ? 1 : 0;          // whole-image kernel only: its second form (ssd_imgblock2.hip); the row-band kernels do not read it
     return p;
 }
 
-static FusedBlockParams fused_params(const ssd_net& net, const Layer& f, int B) {
-    FusedBlockParams p = fused_shape(net, f, B);
-    if (f.route == RT_IMAGE || f.route == RT_IMAGE_SPLIT) {
-        const Layer& le = net.layers[f.f_expand];
-        const Layer& lp = net.layers[f.f_project];
-        p.we3 = conv_split_planes(f.fz_we, le.Cin, le.Cout);  // ... whole-image kernel: plain [4][Ce][kpad_e] / [4][npad_p][kpad_p] planes
-        p.wp3 = conv_split_planes(f.fz_wp, lp.Cin, lp.Cout);
-        p.groups = net.img_slabs ? image_block_groups(p, B * net.lanes_hint) : 1;
-        p.slabs = net.img_slabs;
-        // (the in-launch ticketed combine exists for the fp32-MFMA form only: a no-op for the bf16 / split-bf16 forms)
-        p.tickets = net.image_ticket && !p.bf16 ? net.img_tickets : nullptr;
-        if (f.route == RT_IMAGE_SPLIT) { p.bf16 = 3; p.tickets = nullptr; }    // the split-bf16 form of the image kernel (fp32 results)
-        // ... or, with a statically bounded input (finalize_image_f16x2), its two-plane fp16 form where the second form
-        // takes the block at this group count
-        if (f.route == RT_IMAGE_SPLIT && net.image_f16x2 && net.image_v2 && f.fz_weh && f.fz_wph) {
-            FusedBlockParams q = p;
-            q.bf16 = 2;
-            q.we3 = reinterpret_cast<const short*>(f.fz_weh);
-            q.wp3 = reinterpret_cast<const short*>(f.fz_wph);
-            q.f16_xs = ldexpf(1.f, f.f16_s);
-            q.f16_es = ldexpf(1.f, -(f.f16_s + f.f16_ke));
-            q.f16_ps = ldexpf(1.f, -(8 + f.f16_kp));
-            if (image_block2_supported(q)) return q;
-        }
+// The whole-image kernel's plan for a block at batch B: image_block_plan's one caller (plan.fn == nullptr: no kernel takes
+// the shape, the error is set).  `probe_pairs`: finalize_image_f16x2's question before the fp16 pairs exist -- would the
+// split route with the second form allowed ever read them?
+static ImagePlan image_plan(const ssd_net& net, const Layer& f, int B, FusedBlockParams* shape = nullptr, bool probe_pairs = false) {
+    const FusedBlockParams s = fused_shape(net, f, B);
+    ImageAsk a{};
+    a.precision = net.precision; a.ticket = net.image_ticket; a.lanes = (long)B * net.lanes_hint;
+    a.split = probe_pairs || f.route == RT_IMAGE_SPLIT;
+    a.second = probe_pairs || net.image_v2;
+    a.pairs = probe_pairs || (net.image_f16x2 && f.fz_weh && f.fz_wph);
+    a.slabs = !probe_pairs && net.img_slabs;
+    ImagePlan plan;
+    (void)image_block_plan(s, a, &plan);
+    if (shape) *shape = s;
+    return plan;
+}
+
+// (the whole-image routes: the parameters are filled from `plan`, which the launcher takes beside them)
+static FusedBlockParams fused_params(const ssd_net& net, const Layer& f, int B, ImagePlan* plan = nullptr) {
+    if (!route_is_image(f.route)) return fused_shape(net, f, B);
+    FusedBlockParams p;
+    const ImagePlan pl = image_plan(net, f, B, &p);
+    if (plan) *plan = pl;
+    const Layer &le = net.layers[f.f_expand], &lp = net.layers[f.f_project];
+    p.bf16 = pl.form; p.groups = pl.groups;
+    p.slabs = net.img_slabs;
+    p.tickets = pl.ticketed ? net.img_tickets : nullptr;
+    // the form's weights: plain [4][Ce][kpad_e] / [4][npad_p][kpad_p] bf16 planes, or the fp16 pairs and their three scales
+    p.we3 = pl.form == 2 ? reinterpret_cast<const short*>(f.fz_weh) : conv_split_planes(f.fz_we, le.Cin, le.Cout);
+    p.wp3 = pl.form == 2 ? reinterpret_cast<const short*>(f.fz_wph) : conv_split_planes(f.fz_wp, lp.Cin, lp.Cout);
+    if (pl.form == 2) {
+        p.f16_xs = ldexpf(1.f, f.f16_s);
+        p.f16_es = ldexpf(1.f, -(f.f16_s + f.f16_ke));
+        p.f16_ps = ldexpf(1.f, -(8 + f.f16_kp));
     }
     return p;
 }
@@ -484,7 +493,11 @@ static int run_layer_kernels(ssd_net& net, const Layer& l, int B, float* deltas_
                 case RT_BAND: return launch_band_block(fused_params(net, l, B), st);
                 case RT_BAND3: return launch_band3_block(fused_params(net, l, B), st);
                 case RT_IMAGE:
-                case RT_IMAGE_SPLIT: return launch_image_block(fused_params(net, l, B), st);
+                case RT_IMAGE_SPLIT: {
+                    ImagePlan plan;
+                    const FusedBlockParams p = fused_params(net, l, B, &plan);
+                    return plan.fn ? launch_image_block(p, plan, st) : SSD_E_UNSUPPORTED;
+                }
                 default: break;
             }
             set_error("run_layer: no fused kernel is routed to layer %s", l.name.c_str());
@@ -498,7 +511,7 @@ static int run_layer_impl(ssd_net& net, const Layer& l, int B, float* deltas_out
     int rc = run_layer_kernels(net, l, B, deltas_out, probs_out, st, cfg_override);
     // convs, pools, the L2 normalisation and the whole-image block kernel write their planes themselves
     if (rc || l.kind == LK_CONV || l.kind == LK_POOL || l.kind == LK_L2NORM || l.kind == LK_SOFTMAX) return rc;
-    if ((l.route == RT_IMAGE || l.route == RT_IMAGE_SPLIT) && !net.image_ticket) return rc;
+    if (route_is_image(l.route) && !net.image_ticket) return rc;
     if (l.out >= 0 && net.tensors[l.out].planes_live) rc = planes_pass(net, l.out, B, st);
     if (!rc && l.kind == LK_FUSED && l.e_out >= 0 && net.tensors[l.e_out].planes_live) rc = planes_pass(net, l.e_out, B, st);
     return rc;
@@ -576,7 +589,7 @@ static std::vector<char> plane_only_candidates(const ssd_net& net, F reads_plane
         bar(l.res);
         if (l.kind == LK_FUSED && l.f_project >= 0) bar(net.layers[l.f_project].res);      // (the block's residual source)
         // the producer side
-        const bool image = l.kind == LK_FUSED && (l.route == RT_IMAGE || l.route == RT_IMAGE_SPLIT);
+        const bool image = l.kind == LK_FUSED && route_is_image(l.route);
         bool writes = image || l.kind == LK_POOL || l.kind == LK_L2NORM;
         if (l.kind == LK_CONV)
             writes = l.head_kind == 0 && (l.Cout & 3) == 0 && l.cfg >= 0 && conv_config_writes_planes(l.cfg, ConvParams{});
@@ -639,10 +652,7 @@ static int tune_image_blocks(ssd_net& net, int B, hipStream_t st) {
         for (int choice = 0; choice < nchoice && !rc; ++choice) {
             f.img_choice = choice;
             resolve_routes(net);
-            if (choice == 2) {          // (the form that will run: the fp16 pair where fused_params chose it, which then fits by construction)
-                const FusedBlockParams fp = fused_params(net, f, B);
-                if (fp.bf16 != 2 && !image_block_split_fits(fp)) continue;
-            }
+            if (choice == 2 && image_plan(net, f, B).form < 2) continue;     // (not raced: the plan is not the split-bf16 form or the fp16 pair it asks for)
             for (int trial = 0; trial < 4 && !rc; ++trial) {        // trial 0 warms up
                 (void)hipEventRecord(se0.e, st);
                 for (int r = 0; r < 4 && !rc; ++r)
@@ -1259,10 +1269,7 @@ static int finalize_image_f16x2(ssd_net* net, hipStream_t st) {
         if (f.kind != LK_FUSED || f.f_type != 0 || f.in < 0 || !image_kernel_takes(*net, f)) continue;
         int s = 0;
         if (!ssd_f16x2_input_exp(net->tensors[f.in].bound, &s)) continue;
-        FusedBlockParams q = fused_shape(*net, f, 1);
-        q.bf16 = 2; q.groups = q.Ce / 32;      // (the form's smallest LDS footprint: does the second form have the shape at all?)
-        q.we3 = q.wp3 = reinterpret_cast<const short*>(f.fz_we);
-        if (!image_block2_supported(q)) continue;
+        if (image_plan(*net, f, 1, nullptr, true).form != 2) continue;     // (the second form has no such shape)
         const Layer& le = net->layers[f.f_expand];
         const Layer& lp = net->layers[f.f_project];
         unsigned bits[2] = {0, 0};
@@ -2073,8 +2080,9 @@ const char* ssd_net_layer_config(const ssd_net* net, int i) {
 int ssd_net_layer_image_form(const ssd_net* net, int i, int B) {
     if (!net || i < 0 || i >= (int)net->layers.size() || B < 1) return -1;
     const Layer& f = net->layers[i];
-    if (f.kind != LK_FUSED || (f.route != RT_IMAGE && f.route != RT_IMAGE_SPLIT)) return -1;
-    return fused_params(*net, f, B).bf16;
+    if (f.kind != LK_FUSED || !route_is_image(f.route)) return -1;
+    const ImagePlan plan = image_plan(*net, f, B);
+    return plan.fn ? plan.form : -1;
 }
 
 static double algorithmic_flops(const Layer& l, int B) {
