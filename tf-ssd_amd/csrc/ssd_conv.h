@@ -212,6 +212,7 @@ extern const ConvFamily kConvDma3, kConvDmab, kConvDmah;     // ssd_convdma.hip:
 
 int conv_num_configs();
 const char* conv_config_name(int cfg);
+int conv_config_by_name(const char* name);                 // the config id a tuning table's word names; -1: none
 ConvFamilyId conv_config_family(int cfg);                  // (CF_NONE: no config id)
 // true if config `cfg` can run these parameters
 bool conv_config_valid(int cfg, const ConvParams& p);

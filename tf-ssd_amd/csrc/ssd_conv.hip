@@ -21,6 +21,8 @@
 //     SAME / ZeroPadding2D pads are explicit (pad_t, pad_l) and out-of-image taps load zeros.
 //   * The epilogue writes through (batch stride, pixel stride) so the SSD head convs store
 //     straight into the concatenated [B, N, K] buffers (reference models/header.py:34-41).
+#include <cstring>
+
 #include "ssd_conv.h"
 #include "ssd_conv_mfma.h"
 
@@ -369,6 +371,11 @@ int conv_num_configs() { return family_first()[kNumFamilies]; }
 const char* conv_config_name(int cfg) {
     const ConvRef r = conv_resolve(cfg);
     return r.fam ? r.fam->name(r.i) : "?";
+}
+int conv_config_by_name(const char* name) {
+    for (int c = 0; c < conv_num_configs(); ++c)
+        if (!strcmp(name, conv_config_name(c))) return c;
+    return -1;
 }
 ConvFamilyId conv_config_family(int cfg) {
     const ConvRef r = conv_resolve(cfg);

@@ -126,6 +126,30 @@ struct ScopedEvent {
     hipEvent_t e = nullptr;
     ~ScopedEvent() { if (e) (void)hipEventDestroy(e); }
 };
+// The one timing primitive of the on-device races and the layer profile: two events, created once, that time ONE window
+// (record, `reps` calls of `launch()`, record, synchronise, elapsed ms).  How many windows, which one warms up, how two
+// alternatives interleave and when a candidate is given up stay with the caller.  window() returns the first non-zero
+// launch() result (no synchronise then) or SSD_E_HIP from the synchronise, with *ms 0, for a caller that goes on regardless.
+struct EventPair {
+    ScopedEvent e0, e1;
+    int create() {
+        SSD_HIP(hipEventCreate(&e0.e));
+        SSD_HIP(hipEventCreate(&e1.e));
+        return SSD_OK;
+    }
+    template <class Launch>
+    int window(hipStream_t st, int reps, Launch launch, float* ms) {
+        *ms = 0.f;
+        int rc = SSD_OK;
+        (void)hipEventRecord(e0.e, st);
+        for (int r = 0; r < reps && !rc; ++r) rc = launch();
+        (void)hipEventRecord(e1.e, st);
+        if (rc) return rc;
+        SSD_HIP(hipEventSynchronize(e1.e));
+        (void)hipEventElapsedTime(ms, e0.e, e1.e);
+        return SSD_OK;
+    }
+};
 
 // One launch of the forward's plan (plan_steps, ssd_net.hip): a pure function of the graph, the options, the
 // routes and `timing`, built at the first forward that needs it and kept until ssd_net::drop_graphs().
@@ -257,3 +281,23 @@ struct ssd_net {
     }
 };
 
+namespace ssd {
+
+// ---- what the kernel-selection unit (ssd_tune.hip) needs of the graph runner (ssd_net.hip)
+ConvParams layer_conv_params(const ssd_net& net, const Layer& l, int B, const float* in, float* out, const float* res,
+                             float* deltas_out, float* probs_out);
+int run_layer(ssd_net& net, const Layer& l, int B, float* deltas_out, float* probs_out, hipStream_t st, int cfg_override = -1);
+void resolve_routes(ssd_net& net);
+inline bool layer_runs(const Layer& l) { return l.route != RT_OFF; }
+bool image_kernel_takes(const ssd_net& net, const Layer& f);
+ImagePlan image_plan(const ssd_net& net, const Layer& f, int B, FusedBlockParams* shape = nullptr, bool probe_pairs = false);
+std::vector<char> plane_only_candidates(const ssd_net& net);
+int dev_alloc(ssd_net& net, size_t floats, float** out);
+
+// ---- ... and ssd_net_finalize of that unit: the four steps that choose, in the order finalize takes them
+int finalize_apply_preset(ssd_net* net, int max_batch, bool* image_preset_ok);    // the table's lines, where they can run
+int autotune(ssd_net& net, int B, hipStream_t st);                                // conv layers without one: raced
+int tune_image_blocks(ssd_net& net, int B, hipStream_t st);                       // whole-image blocks without one: raced
+int tune_launch_mode(ssd_net* net, int B);                                        // graph replay or direct launches: read or raced
+
+}  // namespace ssd

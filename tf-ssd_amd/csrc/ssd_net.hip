@@ -1,7 +1,8 @@
 // Graph runner: builds the SSD300 MobileNetV2 / VGG16 forward graphs natively, owns the
 // parameters (Keras names + layouts at the boundary), folds BatchNorm, packs weights for
-// the MFMA kernels, plans the activation arena in HBM, autotunes the tile configuration of
-// every conv on the device, and replays the layer list on a HIP stream.
+// the MFMA kernels, plans the activation arena in HBM and replays the layer list on a HIP
+// stream.  Which kernel runs a layer -- the table's text, the on-device races, the per-tensor
+// storage decision -- is chosen in ssd_tune.hip, which ssd_net_finalize calls.
 //
 // Reference graphs: models/ssd_mobilenet_v2.py:7-35 (+ [3P] keras-applications 1.0.8
 // MobileNetV2), models/ssd_vgg16.py:33-97, models/header.py:43-67.
@@ -300,8 +301,8 @@ static void build_vgg16(ssd_net& net) {
     b.heads({l.out, conv7, conv8_2, conv9_2, conv10_2, conv11_2});
 }
 
-static ConvParams layer_conv_params(const ssd_net& net, const Layer& l, int B, const float* in, float* out,
-                                    const float* res, float* deltas_out, float* probs_out) {
+ConvParams layer_conv_params(const ssd_net& net, const Layer& l, int B, const float* in, float* out, const float* res,
+                             float* deltas_out, float* probs_out) {
     ConvParams p{};
     p.in = in;
     p.w = l.packed;
@@ -381,7 +382,7 @@ static FusedBlockParams fused_shape(const ssd_net& net, const Layer& f, int B) {
 // The whole-image kernel's plan for a block at batch B: image_block_plan's one caller (plan.fn == nullptr: no kernel takes
 // the shape, the error is set).  `probe_pairs`: finalize_image_f16x2's question before the fp16 pairs exist -- would the
 // split route with the second form allowed ever read them?
-static ImagePlan image_plan(const ssd_net& net, const Layer& f, int B, FusedBlockParams* shape = nullptr, bool probe_pairs = false) {
+ImagePlan image_plan(const ssd_net& net, const Layer& f, int B, FusedBlockParams* shape, bool probe_pairs) {
     const FusedBlockParams s = fused_shape(net, f, B);
     ImageAsk a{};
     a.precision = net.precision; a.ticket = net.image_ticket; a.lanes = (long)B * net.lanes_hint;
@@ -517,8 +518,7 @@ static int run_layer_impl(ssd_net& net, const Layer& l, int B, float* deltas_out
     return rc;
 }
 
-static int run_layer(ssd_net& net, const Layer& l, int B, float* deltas_out, float* probs_out, hipStream_t st,
-                     int cfg_override = -1) {
+int run_layer(ssd_net& net, const Layer& l, int B, float* deltas_out, float* probs_out, hipStream_t st, int cfg_override) {
     static const bool dbg_sync = getenv("SSD_HIP_DEBUG_SYNC") != nullptr;
     if (!dbg_sync) return run_layer_impl(net, l, B, deltas_out, probs_out, st, cfg_override);
     fprintf(stderr, "[ssd dbg] run %s\n", l.name.c_str());
@@ -531,7 +531,7 @@ static int run_layer(ssd_net& net, const Layer& l, int B, float* deltas_out, flo
 
 // Can the whole-image kernel run this whole-block layer?  (Blocks the row kernels take -- 1-6 -- never go to it.)
 static bool image_kernel_takes(const FusedBlockParams& p) { return !fused_block_supported(p) && image_block_supported(p); }
-static bool image_kernel_takes(const ssd_net& net, const Layer& f) {
+bool image_kernel_takes(const ssd_net& net, const Layer& f) {
     return f.kind == LK_FUSED && f.f_type == 0 && image_kernel_takes(fused_shape(net, f, 1));
 }
 
@@ -559,32 +559,29 @@ static Route fused_route(const ssd_net& net, const Layer& f) {
 // Fills Layer::route from the graph, the options, img_choice, the precision and the presence of the band3 planes.  Called
 // wherever one of those changes, so that everything else -- dispatch, weight layout, plane writers, launch plan, the
 // introspection entry points -- reads one decision.  (A fused layer precedes its members, a block its type-2 layer.)
-static void resolve_routes(ssd_net& net) {
+void resolve_routes(ssd_net& net) {
     for (Layer& l : net.layers) {
         const bool owned = (l.fused_by >= 0 && net.layers[l.fused_by].route != RT_OFF) ||
                            (l.fused_by2 >= 0 && net.layers[l.fused_by2].route != RT_OFF);
         l.route = l.kind == LK_FUSED ? fused_route(net, l) : owned ? RT_OFF : RT_LAYER;
     }
 }
-static bool layer_runs(const Layer& l) { return l.route != RT_OFF; }
 
-// Which activations can live as bf16 planes ALONE (Tensor::plane_only), under the current routes: `reads_planes(i)` says
-// whether conv layer i runs on an LDS-DMA tile.  A tensor qualifies when it has planes, EVERY running layer that reads it
-// (input or residual; a fused kernel reads fp32) is such a conv, and its running producer stores the planes from
+// Which activations can live as bf16 planes ALONE (Tensor::plane_only), under the current routes and the conv layers'
+// current configurations.  A tensor qualifies when it has planes, EVERY running layer that reads it
+// (input or residual; a fused kernel reads fp32) is a conv on an LDS-DMA tile, and its running producer stores the planes from
 // registers -- the shared conv epilogue (fp32-MFMA, split-bf16, bf16, LDS-DMA tiles) with a dense output, the pool / L2-norm
 // writers, the whole-image block kernel with the combine as its second launch -- not by a split pass over the fp32 copy.
 // The image (tensor 0) and the head outputs are not tensors of the arena: no network output ever qualifies.
-template <typename F>
-static std::vector<char> plane_only_candidates(const ssd_net& net, F reads_planes) {
+std::vector<char> plane_only_candidates(const ssd_net& net) {
     const int nt = (int)net.tensors.size();
     std::vector<char> ok(nt, 0), readers(nt, 0);
     if (!net.plane_only || net.image_ticket) return ok;
     for (int t = 1; t < nt; ++t) ok[t] = net.tensors[t].planes != nullptr;
     auto bar = [&](int t) { if (t >= 0) ok[t] = 0; };
-    for (int i = 0; i < (int)net.layers.size(); ++i) {
-        const Layer& l = net.layers[i];
+    for (const Layer& l : net.layers) {
         if (!layer_runs(l)) continue;
-        if (l.kind == LK_CONV && l.in >= 0 && reads_planes(i)) readers[l.in] = 1;
+        if (l.kind == LK_CONV && l.in >= 0 && conv_config_is_dma(l.cfg)) readers[l.in] = 1;
         else bar(l.in);
         bar(l.res);
         if (l.kind == LK_FUSED && l.f_project >= 0) bar(net.layers[l.f_project].res);      // (the block's residual source)
@@ -620,233 +617,17 @@ static bool tensor_relu6_bounded(const ssd_net& net, int t) {
     return any;
 }
 
-static int dev_alloc(ssd_net& net, size_t floats, float** out) {
+int dev_alloc(ssd_net& net, size_t floats, float** out) {
     *out = nullptr;
     if (floats == 0) return SSD_OK;
     SSD_HIP(hipMalloc((void**)out, floats * sizeof(float)));
     net.owned.push_back(*out);
     return SSD_OK;
 }
-
-// Whole-image block kernel vs the layer kernels (expand GEMM + depthwise/project kernel) of the
-// same block, timed on the device at batch B: at B = 64 the 4-way channel-group reduction costs
-// what the E round trip through HBM costs, at large batches (one group) the image kernel wins.
-static int tune_image_blocks(ssd_net& net, int B, hipStream_t st) {
-    ScopedEvent se0, se1;
-    SSD_HIP(hipEventCreate(&se0.e));
-    SSD_HIP(hipEventCreate(&se1.e));
-    struct ModeGuard {          // the race runs in "tuned choice" mode; early error returns restore the caller's mode too
-        ssd_net& n;
-        int mode;
-        ~ModeGuard() { n.fuse_image = mode; }
-    } guard{net, net.fuse_image};
-    net.fuse_image = 1;
-    int rc = SSD_OK;
-    for (size_t fi = 0; fi < net.layers.size() && !rc; ++fi) {
-        Layer& f = net.layers[fi];
-        if (f.kind != LK_FUSED || f.f_type != 0) continue;
-        if (!image_kernel_takes(net, f)) { f.img_choice = 0; continue; }
-        if (f.img_choice >= 0) continue;        // preset line
-        float ms[3] = {1e30f, 1e30f, 1e30f};
-        const int nchoice = net.precision == 0 && net.image_split ? 3 : 2;     // 2: the fp32 net's split-bf16 form
-        for (int choice = 0; choice < nchoice && !rc; ++choice) {
-            f.img_choice = choice;
-            resolve_routes(net);
-            if (choice == 2 && image_plan(net, f, B).form < 2) continue;     // (not raced: the plan is not the split-bf16 form or the fp16 pair it asks for)
-            for (int trial = 0; trial < 4 && !rc; ++trial) {        // trial 0 warms up
-                (void)hipEventRecord(se0.e, st);
-                for (int r = 0; r < 4 && !rc; ++r)
-                    for (int j = (int)fi; j <= f.f_project && !rc; ++j)
-                        if (layer_runs(net.layers[j])) rc = run_layer(net, net.layers[j], B, nullptr, nullptr, st);
-                (void)hipEventRecord(se1.e, st);
-                if (rc) break;
-                SSD_HIP(hipEventSynchronize(se1.e));
-                float t = 0.f;
-                (void)hipEventElapsedTime(&t, se0.e, se1.e);
-                if (trial && t < ms[choice]) ms[choice] = t;
-            }
-        }
-        f.img_choice = ms[2] < ms[1] && ms[2] < ms[0] ? 2 : ms[1] < ms[0] ? 1 : 0;
-    }
-    return rc;
-}
-
-// Time each valid (tile configuration, split-K factor) of every conv layer on the device and
-// keep the best.  Split-K is tried only where the plain grid cannot fill the 256 CUs.
-static int autotune(ssd_net& net, int B, hipStream_t st) {
-    ScopedEvent se0, se1;
-    SSD_HIP(hipEventCreate(&se0.e));
-    SSD_HIP(hipEventCreate(&se1.e));
-    hipEvent_t e0 = se0.e, e1 = se1.e;
-    ScopedDev sd, spr;                     // scratch outputs for the head convs
-    SSD_HIP(hipMalloc((void**)&sd.p, (size_t)B * net.num_priors * 4 * sizeof(float)));
-    SSD_HIP(hipMalloc((void**)&spr.p, (size_t)B * net.num_priors * net.L * sizeof(float)));
-    float *d = sd.p, *pr = spr.p;
-    // dense around small factors: the best split is the one whose M-blocks x split just fills a
-    // whole number of CU rounds (e.g. 100 M-blocks x 5 = 500 blocks on 512 slots for head 2)
-    static const int kSplits[] = {1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 32};
-    constexpr int kNumSplits = sizeof(kSplits) / sizeof(kSplits[0]);
-    // split-K workspace: the largest [split][M][Cout] slab any candidate may need
-    size_t ws_floats = 0;
-    for (auto& l : net.layers) {
-        if (l.kind != LK_CONV) continue;
-        const size_t mc = (size_t)B * l.Ho * l.Wo * l.Cout;
-        if (mc <= (size_t)4 << 20) ws_floats = std::max(ws_floats, mc * 32);
-    }
-    if (ws_floats > net.splitk_floats) {
-        if (net.splitk_ws) (void)hipFree(net.splitk_ws);
-        net.splitk_ws = nullptr;
-        SSD_HIP(hipMalloc((void**)&net.splitk_ws, ws_floats * sizeof(float)));
-        net.splitk_floats = ws_floats;
-    }
-    int rc = SSD_OK;
-    const bool dbg_sync = getenv("SSD_HIP_DEBUG_SYNC") != nullptr;   // name the launch a GPU fault belongs to
-    const bool dbg_tune = getenv("SSD_HIP_DEBUG_TUNE") != nullptr;
-    // the per-layer race keeps the best of EACH family -- fam 0: tiles that read the fp32 activation, fam 1: LDS-DMA tiles
-    // over its three bf16 planes ("dma3_*" / "dmab_*"), fam 2: LDS-DMA tiles over its fp16 pair ("dmah_*", layers with fp16
-    // weight planes only) -- because which of them a layer takes is decided per TENSOR below
-    struct Best {
-        float ms[3] = {1e30f, 1e30f, 1e30f}; int cfg[3] = {-1, -1, -1}; int split[3] = {1, 1, 1}; bool timed = false;
-        float ms_k64 = 1e30f, ms_k32 = 1e30f;        // (SSD_HIP_DEBUG_TUNE: fam 2's best with two / one k-step per barrier)
-    };
-    std::vector<Best> bests(net.layers.size());
-    constexpr int kReps = 4;
-    for (size_t li = 0; li < net.layers.size(); ++li) {
-        Layer& l = net.layers[li];
-        Best& bb = bests[li];
-        if (l.kind != LK_CONV) continue;
-        if (l.cfg >= 0) continue;           // chosen by a valid preset line (ssd_net_set_tuning)
-        bb.timed = true;
-        const float* in = net.tensors[l.in].dev;
-        float* out = l.out >= 0 ? net.tensors[l.out].dev : nullptr;
-        const float* res = l.res >= 0 ? net.tensors[l.res].dev : nullptr;
-        for (int c = 0; c < conv_num_configs() && !rc; ++c) {
-            const int fam = conv_config_reads(c);      // the best tile is kept per storage it reads: fp32, bf16 planes, fp16 pair
-            if (fam == CONV_READS_F16X2 && (!net.conv_f16x2 || !l.wh)) continue;
-            for (int si = 0; si < kNumSplits && !rc; ++si) {
-                const int split = kSplits[si];
-                l.split_k = split;
-                ConvParams p = layer_conv_params(net, l, B, in, out, res, d, pr);
-                if (fam == CONV_READS_F16X2) p.xp_np = 2;       // (timed on whatever the planes hold: the matrix unit's time does not depend on the data)
-                if (!conv_config_valid(c, p) || !conv_config_allowed(c, net.precision)) break;
-                const bool direct = conv_config_family(c) == CF_DIRECT;
-                if (direct && (bb.cfg[0] >= 0 || bb.cfg[1] >= 0 || split > 1)) break;     // direct only as a last resort
-                if (split > 1) {
-                    const long blocks = conv_grid_blocks(c, p);
-                    const int nkt = conv_k_tiles(c, p);
-                    if (blocks > 384 || nkt < 4 * split) break;
-                    if ((size_t)split * p.M * p.Cout > net.splitk_floats) break;
-                }
-                // min over 3 trials of 4 back-to-back launches: robust against clock ramps / noise
-                const int reps = kReps;
-                if (dbg_sync) fprintf(stderr, "[ssd dbg] tune %s %s split %d\n", l.name.c_str(), conv_config_name(c), split);
-                rc = conv_launch(p, c, st);     // warm-up
-                if (rc) break;
-                if (dbg_sync) SSD_HIP(hipStreamSynchronize(st));
-                float ms = 1e30f;
-                for (int trial = 0; trial < 3 && !rc; ++trial) {
-                    (void)hipEventRecord(e0, st);
-                    for (int r = 0; r < reps && !rc; ++r) rc = conv_launch(p, c, st);
-                    (void)hipEventRecord(e1, st);
-                    if (rc) break;
-                    SSD_HIP(hipEventSynchronize(e1));
-                    float t = 0.f;
-                    (void)hipEventElapsedTime(&t, e0, e1);
-                    ms = t < ms ? t : ms;
-                    if (trial == 0 && ms > 1.5f * bb.ms[fam]) break;      // clearly slower than its family's incumbent
-                }
-                if (rc) break;
-                if (ms < bb.ms[fam]) { bb.ms[fam] = ms; bb.cfg[fam] = c; bb.split[fam] = split; }
-                if (fam == CONV_READS_F16X2) {
-                    float& m2 = strstr(conv_config_name(c), "_ks2") ? bb.ms_k64 : bb.ms_k32;
-                    m2 = ms < m2 ? ms : m2;
-                }
-            }
-        }
-        if (rc) break;
-        if (bb.cfg[0] < 0 && bb.cfg[1] < 0) {
-            set_error("finalize: no conv kernel can run layer %s", l.name.c_str());
-            rc = SSD_E_UNSUPPORTED;
-            break;
-        }
-        const int f0 = bb.cfg[0] >= 0 ? 0 : 1;          // the fp32-reading family until the tensor decision below
-        l.cfg = bb.cfg[f0];
-        l.split_k = bb.split[f0];
-        if (dbg_tune)
-            fprintf(stderr, "[ssd] tune %s: %s/s%d %.4f ms | %s/s%d %.4f ms | %s/s%d %.4f ms\n", l.name.c_str(),
-                    bb.cfg[0] >= 0 ? conv_config_name(bb.cfg[0]) : "-", bb.split[0], bb.cfg[0] >= 0 ? bb.ms[0] / kReps : 0.f,
-                    bb.cfg[1] >= 0 ? conv_config_name(bb.cfg[1]) : "-", bb.split[1], bb.cfg[1] >= 0 ? bb.ms[1] / kReps : 0.f,
-                    bb.cfg[2] >= 0 ? conv_config_name(bb.cfg[2]) : "-", bb.split[2], bb.cfg[2] >= 0 ? bb.ms[2] / kReps : 0.f);
-        if (dbg_tune && bb.cfg[2] >= 0)
-            fprintf(stderr, "[ssd] tune %s: dmah best with one k-step per barrier %.4f ms, with two %.4f ms\n", l.name.c_str(),
-                    bb.ms_k32 / kReps, bb.ms_k64 < 1e29f ? bb.ms_k64 / kReps : 0.f);
-    }
-    if (rc) return rc;
-    // The family is a property of the TENSOR: LDS-DMA readers make its producer store the bf16 planes (2 * planes_np bytes per
-    // element), and when every reader takes them the producer drops the fp32 store (4 bytes per element back: plane-only,
-    // Tensor::plane_only).  So per tensor: the sum of its timed readers' best fp32-reading tiles against the sum of their
-    // best LDS-DMA tiles plus what the producer's store changes by, at the 3 TB/s the epilogues' stores reach; all timed
-    // readers flip together.  The whole-image kernel is taken to run wherever it can (its own race comes later; it wins in
-    // every shipped table): what it fuses away reads no tensor.
-    std::vector<int> img_saved;
-    for (auto& f : net.layers) {
-        img_saved.push_back(f.img_choice);
-        if (f.img_choice < 0 && image_kernel_takes(net, f)) f.img_choice = 1;
-    }
-    resolve_routes(net);
-    for (size_t t = 1; t < net.tensors.size(); ++t) {
-        const Tensor& tt = net.tensors[t];
-        std::vector<size_t> flip;
-        bool planes_anyway = false;
-        // the fp16 pair (fam 2) is open to the tensor only when every reader of its planes can take it: all the timed ones
-        // have a "dmah_*" best, and no other conv layer reads the planes through another family
-        bool pair_ok = net.conv_f16x2;
-        double sum0 = 0, sum1 = 0, sum2 = 0;
-        for (size_t li = 0; li < net.layers.size(); ++li) {
-            const Layer& l = net.layers[li];
-            if (l.kind != LK_CONV || l.in != (int)t) continue;
-            const Best& bb = bests[li];
-            if (!bb.timed) {
-                if (layer_runs(l) && conv_config_is_dma(l.cfg)) planes_anyway = true;
-                if (conv_config_is_dma(l.cfg) && !conv_config_is_dmah(l.cfg)) pair_ok = false;
-                continue;
-            }
-            if (bb.cfg[1] < 0) continue;                 // no LDS-DMA tile takes it: stays where it is
-            if (bb.cfg[0] < 0) { planes_anyway = true; pair_ok = false; continue; }      // ... only LDS-DMA tiles do: already there (three planes)
-            if (!layer_runs(l)) {       // fused away under these routes: reads nothing; on its own, with the full plane store charged
-                if (bb.ms[1] + kReps * ((double)B * tt.per_image * 2.0 * tt.planes_np / 3.0e12 * 1e3) < bb.ms[0]) {
-                    net.layers[li].cfg = bb.cfg[1];
-                    net.layers[li].split_k = bb.split[1];
-                    pair_ok = false;
-                }
-                continue;
-            }
-            flip.push_back(li);
-            sum0 += bb.ms[0];
-            sum1 += bb.ms[1];
-            sum2 += bb.ms[2];
-            if (bb.cfg[2] < 0) pair_ok = false;
-        }
-        if (flip.empty()) continue;
-        for (size_t li : flip) { net.layers[li].cfg = bests[li].cfg[1]; net.layers[li].split_k = bests[li].split[1]; }
-        const bool only = plane_only_candidates(net, [&](int i) { return conv_config_is_dma(net.layers[i].cfg); })[t];
-        // what the producer's store changes by, per element: np planes of 2 bytes more, 4 bytes less where the fp32 copy goes
-        auto store_ms_of = [&](int np) {
-            const double bytes = only ? 2.0 * np - 4.0 : planes_anyway ? 0.0 : 2.0 * np;
-            return kReps * ((double)B * tt.per_image * bytes / 3.0e12 * 1e3);
-        };
-        const double store_ms = store_ms_of(tt.planes_np), store2_ms = store_ms_of(2);
-        int take = sum1 + store_ms < sum0 ? 1 : 0;
-        if (pair_ok && sum2 + store2_ms < (take ? sum1 + store_ms : sum0)) take = 2;
-        for (size_t li : flip) { net.layers[li].cfg = bests[li].cfg[take]; net.layers[li].split_k = bests[li].split[take]; }
-        if (dbg_tune)
-            fprintf(stderr, "[ssd] tune tensor %s: fp32 readers %.4f ms, plane readers %.4f + store %+.4f ms, fp16-pair readers %.4f + store %+.4f ms%s (%s) -> %s\n",
-                    tt.name.c_str(), sum0 / kReps, sum1 / kReps, store_ms / kReps, sum2 / kReps, store2_ms / kReps, pair_ok ? "" : " [not open]",
-                    only ? "plane-only" : "both copies", take == 2 ? "fp16 pair" : take ? "planes" : "fp32");
-    }
-    for (size_t i = 0; i < net.layers.size(); ++i) net.layers[i].img_choice = img_saved[i];
-    resolve_routes(net);
-    return rc;
+// ... and one of them given back before the net goes
+static void dev_free(ssd_net& net, float* p) {
+    net.owned.erase(std::remove(net.owned.begin(), net.owned.end(), p), net.owned.end());
+    (void)hipFree(p);
 }
 
 }  // namespace ssd
@@ -991,62 +772,8 @@ int ssd_net_get_param(const ssd_net* net, const char* name, float* host_out, siz
     return SSD_OK;
 }
 
-// hipGraph replay vs direct launches of the whole forward, raced on the device at max_batch on a zero
-// image (measured at B=64: direct launches 1.950 ms, replay 1.972 ms per step on a non-default stream).
-// Skipped once "use_graph" was set explicitly.
-static int tune_launch_mode(ssd_net* net, int B) {
-    if (!net->use_graph_auto || net->timing) return SSD_OK;
-    {
-        auto it = net->preset.find("__launch");          // "__launch graph 0|1": the recorded outcome of this race
-        if (it != net->preset.end() && it->second.first == "graph") {
-            net->use_graph = it->second.second != 0;
-            net->launch_raced = true;
-            return SSD_OK;
-        }
-    }
-    ++net->n_autotuned;
-    const size_t n_img = (size_t)B * net->img_size * net->img_size * 3;
-    ScopedDev img, del, prb;
-    SSD_HIP(hipMalloc((void**)&img.p, n_img * sizeof(float)));
-    SSD_HIP(hipMalloc((void**)&del.p, (size_t)B * net->num_priors * 4 * sizeof(float)));
-    SSD_HIP(hipMalloc((void**)&prb.p, (size_t)B * net->num_priors * net->L * sizeof(float)));
-    SSD_HIP(hipMemset(img.p, 0, n_img * sizeof(float)));
-    hipStream_t st = nullptr;
-    SSD_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    ScopedEvent e0, e1;
-    int rc = SSD_OK;
-    float ms[2] = {1e30f, 1e30f};
-    if (hipEventCreate(&e0.e) != hipSuccess || hipEventCreate(&e1.e) != hipSuccess) rc = SSD_E_HIP;
-    for (int mode = 0; mode < 2 && !rc; ++mode) {        // warm both modes: eager run, capture, replay
-        net->use_graph = mode != 0;
-        for (int w = 0; w < 3 && !rc; ++w) rc = ssd_net_forward(net, img.p, B, del.p, prb.p, st);
-    }
-    for (int trial = 0; trial < 4 && !rc; ++trial)       // interleaved trials (clock drift cancels), best of 4 each
-        for (int mode = 0; mode < 2 && !rc; ++mode) {
-            net->use_graph = mode != 0;
-            (void)hipEventRecord(e0.e, st);
-            for (int r = 0; r < 6 && !rc; ++r) rc = ssd_net_forward(net, img.p, B, del.p, prb.p, st);
-            (void)hipEventRecord(e1.e, st);
-            if (rc || hipEventSynchronize(e1.e) != hipSuccess) { rc = rc ? rc : SSD_E_HIP; break; }
-            float t = 0.f;
-            (void)hipEventElapsedTime(&t, e0.e, e1.e);
-            if (t < ms[mode]) ms[mode] = t;
-        }
-    (void)hipStreamSynchronize(st);
-    net->drop_graphs();
-    (void)hipStreamDestroy(st);
-    net->tensors[0].dev = nullptr;
-    // the two are within ~1 % at B=64 and direct launches measured faster on real batches (heads overlap the
-    // backbone earlier): replay only where it is clearly ahead (small batches, launch-bound hosts)
-    net->use_graph = rc ? true : ms[1] < ms[0] * 0.99f;
-    net->launch_raced = !rc;
-    if (getenv("SSD_HIP_DEBUG_TUNE"))
-        fprintf(stderr, "[ssd] launch mode race at B=%d: direct %.4f ms, graph replay %.4f ms per forward -> %s\n", B, ms[0] / 6,
-                ms[1] / 6, net->use_graph ? "replay" : "direct");
-    return rc;
-}
-
-// ---- ssd_net_finalize, step by step (ssd_net_finalize below calls them in this order, all on one stream)
+// ---- ssd_net_finalize, step by step (ssd_net_finalize below calls them in this order, all on one stream; the four steps
+// that choose kernels -- the table, the three races -- are ssd_tune.hip's)
 
 // Packed weights of a conv layer, and its Winograd form where that applies.
 static int finalize_pack_conv(ssd_net* net, Layer& l, hipStream_t st) {
@@ -1356,60 +1083,6 @@ static int finalize_arena(ssd_net* net, int max_batch, hipStream_t st) {
     return SSD_OK;
 }
 
-// Preset lines (ssd_net_set_tuning) replace the on-device autotune LAYER BY LAYER: a layer whose line
-// is missing or names a configuration that cannot run it here is timed on the device, the others are
-// not -- a complete table means no timing at all and therefore the same kernels (and the same bits)
-// in every process that loads it.  *image_preset_ok: every block the image kernel can run has its line.
-static int finalize_apply_preset(ssd_net* net, int max_batch, bool* image_preset_ok) {
-    for (auto& l : net->layers) { l.cfg = -1; l.split_k = 1; }
-    size_t ws_need = 0;
-    int n_tuned = 0, n_preset = 0;
-    for (auto& l : net->layers) {
-        if (l.kind != LK_CONV) continue;
-        auto it = net->preset.find(l.name);
-        if (it == net->preset.end()) { ++n_tuned; continue; }
-        int cfg = -1;
-        for (int c = 0; c < conv_num_configs(); ++c)
-            if (it->second.first == conv_config_name(c)) cfg = c;
-        SSD_UNSUPPORTED_IF(cfg >= 0 && conv_config_is_dmah(cfg) && net->precision != 0,
-                           "finalize: the table puts layer %s on %s: the two-plane fp16 tiles are admitted in fp32 nets (precision 0) only",
-                           l.name.c_str(), conv_config_name(cfg));
-        // a "dmah_*" line where the form may not run -- option conv_f16x2 0, an input that is not ReLU6-bounded, non-finite
-        // weights -- runs its "dma3_*" twin: the same tile, the same split-K
-        if (cfg >= 0 && conv_config_is_dmah(cfg) && (!net->conv_f16x2 || !l.wh)) cfg = conv_dmah_twin(cfg);
-        if (cfg < 0 || !conv_config_allowed(cfg, net->precision)) { ++n_tuned; continue; }
-        l.cfg = cfg;
-        l.split_k = it->second.second;
-        ConvParams p = layer_conv_params(*net, l, max_batch, net->tensors[l.in].dev,
-                                         l.out >= 0 ? net->tensors[l.out].dev : nullptr, nullptr,
-                                         net->arena, net->arena);
-        if (conv_config_is_dmah(cfg)) p.xp_np = 2;         // (which form the tensor's planes take is settled below: finalize_resolve_f16x2)
-        const bool split_ok = l.split_k == 1 || conv_k_tiles(cfg, p) >= l.split_k;
-        if (l.split_k < 1 || !split_ok || !conv_config_valid(cfg, p)) { l.cfg = -1; l.split_k = 1; ++n_tuned; continue; }
-        ++n_preset;
-        if (l.split_k > 1) ws_need = std::max(ws_need, (size_t)l.split_k * p.M * p.Cout);
-    }
-    *image_preset_ok = true;
-    for (auto& f : net->layers) {       // whole-block layers the image kernel can run: "name image 0|1|2"
-        if (f.kind != LK_FUSED || f.f_type != 0) continue;
-        f.img_choice = -1;
-        if (!image_kernel_takes(*net, f)) continue;
-        auto it = net->preset.find(f.name);
-        if (it == net->preset.end() || it->second.first != "image") { *image_preset_ok = false; continue; }
-        f.img_choice = it->second.second < 0 ? 0 : it->second.second > 2 ? 2 : it->second.second;
-        if (f.img_choice == 2 && (net->precision != 0 || !net->image_split)) f.img_choice = 1;
-    }
-    if (ws_need > net->splitk_floats) {
-        if (net->splitk_ws) (void)hipFree(net->splitk_ws);
-        net->splitk_ws = nullptr;
-        SSD_HIP(hipMalloc((void**)&net->splitk_ws, ws_need * sizeof(float)));
-        net->splitk_floats = ws_need;
-    }
-    net->n_autotuned = n_tuned;
-    net->n_preset = n_preset;
-    return SSD_OK;
-}
-
 // The planes were allocated for the race; keep them only where a CHOSEN tile reads them (6 bytes per element in fp32 nets,
 // 2 in the bf16 mode: a table without LDS-DMA tiles leaves none).  A plane-only tensor keeps its fp32 arena slot too -- the
 // layout of the arena does not depend on the routing state, and option "plane_only" 0 writes it again -- so the planes
@@ -1425,9 +1098,7 @@ static int finalize_free_unread_planes(ssd_net* net, hipStream_t st) {
         if (!t.planes) continue;
         const size_t bytes = ((size_t)t.planes_cap * t.plane_stride / 2 + 64) * sizeof(float);
         if (read[i]) { net->plane_bytes += bytes; continue; }
-        float* pl = reinterpret_cast<float*>(t.planes);
-        net->owned.erase(std::remove(net->owned.begin(), net->owned.end(), pl), net->owned.end());
-        (void)hipFree(pl);
+        dev_free(*net, reinterpret_cast<float*>(t.planes));
         t.planes = nullptr; t.planes_np = t.planes_cap = 0; t.plane_stride = 0;
     }
     return SSD_OK;
@@ -1454,8 +1125,7 @@ static void finalize_resolve_f16x2(ssd_net* net) {
             net->tensors[l.in].planes_np = 2;
             net->wplane_bytes += (conv_f16x2_plane_shorts(l.kh * l.kw * l.Cin, l.Cout) + 1) / 2 * sizeof(float);
         } else if (l.wh) {
-            net->owned.erase(std::remove(net->owned.begin(), net->owned.end(), l.wh), net->owned.end());
-            (void)hipFree(l.wh);
+            dev_free(*net, l.wh);
             l.wh = nullptr;
         }
     }
@@ -1535,21 +1205,6 @@ int ssd_net_finalize(ssd_net* net, int max_batch) {
     return tune_launch_mode(net, max_batch);
 }
 
-// Tuning table as text, one "layer config split_k" line per conv layer.
-long ssd_net_get_tuning(const ssd_net* net, char* buf, size_t cap) {
-    if (!net) return SSD_E_INVALID;
-    std::string out;
-    for (const auto& l : net->layers)
-        if (l.kind == LK_CONV && l.cfg >= 0)
-            out += l.name + " " + conv_config_name(l.cfg) + " " + std::to_string(l.split_k) + "\n";
-    for (const auto& l : net->layers)
-        if (l.img_choice >= 0 && image_kernel_takes(*net, l)) out += l.name + " image " + std::to_string(l.img_choice) + "\n";
-    if (net->finalized && net->use_graph_auto && net->launch_raced)
-        out += std::string("__launch graph ") + (net->use_graph ? "1" : "0") + "\n";
-    if (buf && cap > out.size()) memcpy(buf, out.c_str(), out.size() + 1);
-    return (long)out.size();
-}
-
 // device memory the finalized net holds, in bytes: [0] activation arena, [1] bf16 planes of the activations its chosen LDS-DMA
 // tiles read, [2] whole-image kernel slabs, [3] split-K slabs
 int ssd_net_memory_bytes(const ssd_net* net, size_t out[4]) {
@@ -1575,35 +1230,6 @@ float ssd_net_tensor_bound(const ssd_net* net, const char* tensor) {
     return it == net->tensor_index.end() ? -1.f : net->tensors[it->second].bound;
 }
 
-int ssd_net_tuning_stats(const ssd_net* net, int* from_table, int* timed) {
-    SSD_CHECK_ARG(net != nullptr, "ssd_net_tuning_stats: net is NULL");
-    if (from_table) *from_table = net->n_preset;
-    if (timed) *timed = net->n_autotuned;
-    return SSD_OK;
-}
-
-int ssd_net_set_tuning(ssd_net* net, const char* text) {
-    SSD_CHECK_ARG(net && text, "ssd_net_set_tuning: NULL argument");
-    net->preset.clear();
-    std::string s(text);
-    size_t pos = 0;
-    while (pos < s.size()) {
-        size_t e = s.find('\n', pos);
-        if (e == std::string::npos) e = s.size();
-        const std::string line = s.substr(pos, e - pos);
-        pos = e + 1;
-        char name[128], cfg[128];
-        int split = 1;
-        if (line.empty() || line[0] == '#') continue;
-        const bool flag = sscanf(line.c_str(), "%127s %127s %d", name, cfg, &split) == 3 &&
-                          (std::string(cfg) == "image" || std::string(cfg) == "graph");
-        if (sscanf(line.c_str(), "%127s %127s %d", name, cfg, &split) == 3 && split >= (flag ? 0 : 1) && split <= 64)
-            net->preset[name] = {cfg, split};
-    }
-    net->finalized = false;
-    return SSD_OK;
-}
-
 int ssd_net_num_priors(const ssd_net* net) { return net ? net->num_priors : 0; }
 int ssd_net_feature_map_size(const ssd_net* net, int level) {
     return (net && level >= 0 && level < (int)net->fmap.size()) ? net->fmap[level] : 0;
@@ -1621,7 +1247,7 @@ static void plan_steps(ssd_net& net) {
             net.tensors[l.in].planes_live = true;
     // ... and which of them exist as planes ONLY
     {
-        const std::vector<char> only = plane_only_candidates(net, [&](int i) { return conv_config_is_dma(net.layers[i].cfg); });
+        const std::vector<char> only = plane_only_candidates(net);
         for (size_t t = 0; t < net.tensors.size(); ++t) net.tensors[t].plane_only = only[t] && net.tensors[t].planes_live;
     }
     const bool overlap = net.overlap_heads && !net.timing && net.side[0];
@@ -2140,18 +1766,12 @@ int ssd_net_profile_layers(ssd_net* net, const float* image_dev, int B, int reps
     SSD_HIP(hipMalloc((void**)&spr.p, (size_t)B * N * L * sizeof(float)));
     float *d = sd.p, *pr = spr.p;
     int rc = forward_impl(net, image_dev, B, d, pr, st);   // warm-up + valid inputs for each layer
-    ScopedEvent se0, se1;
-    SSD_HIP(hipEventCreate(&se0.e));
-    SSD_HIP(hipEventCreate(&se1.e));
-    hipEvent_t e0 = se0.e, e1 = se1.e;
-    for (size_t i = 0; i < net->layers.size() && !rc; ++i) {
-        (void)hipEventRecord(e0, st);
-        for (int r = 0; r < reps && !rc && layer_runs(net->layers[i]); ++r)
-            rc = run_layer(*net, net->layers[i], B, d, pr, st);
-        (void)hipEventRecord(e1, st);
-        (void)hipEventSynchronize(e1);
+    EventPair ev;
+    if (const int rce = ev.create()) return rce;
+    for (size_t i = 0; i < net->layers.size() && !rc; ++i) {       // one window of `reps` per layer (empty: the layer does not run)
+        const Layer& l = net->layers[i];
         float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
+        rc = ev.window(st, layer_runs(l) ? reps : 0, [&] { return run_layer(*net, l, B, d, pr, st); }, &ms);
         ms_out[i] = ms / reps;
     }
     return rc;

@@ -1151,7 +1151,7 @@ public:
 };
 static PickMemo& pick_memo() { static PickMemo m; return m; }
 
-// The one tile-timing loop: every candidate launches once untimed (a candidate whose launch fails is left out), then takes
+// The training step's tile race (windows: EventPair, ssd_net.h): every candidate launches once untimed (a candidate whose launch fails is left out), then takes
 // the minimum over 3 trials of `reps` back-to-back launches; a candidate whose first trial takes more than twice the
 // incumbent's time stops there.  `launch(c)` must be harmless to repeat.  false: the events could not be created.
 struct TimedPick {
@@ -1160,19 +1160,15 @@ struct TimedPick {
 };
 template <class Launch>
 static bool time_candidates(const std::vector<int>& candidates, int model, int reps, hipStream_t st, Launch launch, TimedPick* out) {
-    ScopedEvent e0, e1;
-    if (hipEventCreate(&e0.e) != hipSuccess || hipEventCreate(&e1.e) != hipSuccess) { (void)hipGetLastError(); return false; }
+    EventPair ev;
+    if (ev.create()) { (void)hipGetLastError(); return false; }
     *out = TimedPick{model, 1e30f, 0.f};
     for (const int c : candidates) {
         if (launch(c)) { (void)hipGetLastError(); continue; }
         float ms = 1e30f;
         for (int trial = 0; trial < 3; ++trial) {
-            (void)hipEventRecord(e0.e, st);
-            for (int r = 0; r < reps; ++r) (void)launch(c);
-            (void)hipEventRecord(e1.e, st);
-            (void)hipEventSynchronize(e1.e);
             float t = 0.f;
-            (void)hipEventElapsedTime(&t, e0.e, e1.e);
+            (void)ev.window(st, reps, [&] { (void)launch(c); return 0; }, &t);      // (launch errors inside a window are ignored)
             ms = t < ms ? t : ms;
             if (trial == 0 && ms > 2.0f * out->best_ms) break;
         }
