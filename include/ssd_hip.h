@@ -1095,6 +1095,9 @@ typedef struct ssd_conv_desc {
     int pad_t, pad_l, pad_b, pad_r;
     int act;                   /* enum ssd_act, applied after scale/shift  */
     int has_residual;          /* add residual [B,Ho,Wo,Cout] before store */
+    int dma_two_stage;         /* ssd_conv2d_planes_f16x2, "dmah_*" configs with one k-step per barrier: 0 (a zero-filled
+                                * tail) the three-stage LDS ring, non-zero the two-stage loop (the net option dma_ring 0);
+                                * the same bits either way.  Every other kernel ignores it */
 } ssd_conv_desc;
 
 /* TF SAME rule: out=ceil(in/s), p=max((out-1)*s+(k-1)*d+1-in,0),

@@ -50,6 +50,9 @@ struct ConvParams {
     // before anything else (split-K partials included); the input planes are then xp_np = 2
     const short* wh;
     float acc_scale;
+    // "dmah_*" with one k-step per barrier: 0 the three-stage ring (tiles whose three stages fit the LDS), 1 the two-stage
+    // loop (net option dma_ring 0; ssd_conv_desc::dma_two_stage)
+    int dma_two_stage;
 };
 // ConvParams::vec_store of these destinations: float4 stores into `out` are aligned
 inline int conv_vec_store(const ConvParams& p) {

@@ -512,6 +512,7 @@ int fill_conv_params(const ssd_conv_desc* d, ConvParams* p) {
     p->M = (long)d->B * Ho * Wo;
     p->act = d->act;
     p->split_k = 1;
+    p->dma_two_stage = d->dma_two_stage != 0;
     return SSD_OK;
 }
 

@@ -24,13 +24,15 @@
 //     by the exact 2^-(8 + k) before the epilogue.
 // Epilogue = conv_epilogue (ssd_conv_mfma.h): BN / bias, activation, residual, head routing, optional plane output.
 // Three tile families (kConvDma3 / kConvDmab / kConvDmah below): "dma3_*" (np = 3), "dmab_*" (np = 1), "dmah_*" / "dmah_*_ks2" (np = 2).
+#include <type_traits>
+
 #include "ssd_block_common.h"
 #include "ssd_conv_mfma.h"
 
 namespace ssd {
 
 // (the body is a __device__ function: a __global__ body that declares __amdgpu_buffer_rsrc_t objects loses its host stub)
-template <int MT, int NT, int WM, int WN, int NP, bool GEMM1X1, int KSH = 1>
+template <int MT, int NT, int WM, int WN, int NP, bool GEMM1X1, int KSH = 1, int NST = 2>
 __device__ __forceinline__ void conv_dma_body(const ConvParams& p, char* __restrict__ dsm) {
     constexpr int KS = NP == 1 ? 2 : NP == 2 ? KSH : 1;      // 32-wide k-steps per LDS stage (np = 2: either, by configuration)
     constexpr int WPL = NP == 1 ? 3 : 0;         // first weight plane: [h, m, l, r] (np = 2: the fp16 planes [h, l] of ConvParams::wh)
@@ -214,28 +216,119 @@ __device__ __forceinline__ void conv_dma_body(const ConvParams& p, char* __restr
         }
     };
 
-    int ns_cur = 1;
-    if (kt_begin < kt_end) {
-        tile_setup(kt_begin);
-        ns_cur = steps_here();
-        issue(0);
-    }
-    // the first tile's LDS-DMA has to have LANDED before any wave reads it: the copies count on vmcnt, and nothing in the
-    // workgroup-barrier contract makes hipcc drain vmcnt for them (ROCm 7.2 happens to) -- wait explicitly, as the stem does
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int kt = kt_begin; kt < kt_end; ++kt) {
-        const int stage = (kt - kt_begin) & 1;
-        int ns_next = 1;
-        if (kt + 1 < kt_end) {
-            tile_advance();
-            ns_next = steps_here();
-            issue(stage ^ 1);        // lands while this tile is multiplied; the stage was last read before the previous barrier
+    if constexpr (NST == 3) {
+        // ---- three-stage ring (np = 2, one k-step per stage): tile i + 2 is copied into the stage tile i - 1 was read from
+        // while tile i is multiplied, so a copy has a whole further tile to land.  Per iteration: the wave's first
+        // instructions after the barrier are fragment reads and MFMAs; its copies follow one output-channel group at a time
+        // behind that group's MFMAs; at the end it waits until all but its NEWEST tile's pieces have landed (a counted
+        // vmcnt: tile i + 1 is there, tile i + 2 stays in flight) and passes lds_barrier(), whose LDS-only wait leaves the
+        // copies alone (__syncthreads()'s fence would drain them).  A stage is read only after such a wait and a barrier,
+        // and refilled only after the barrier that closed the iteration which read it.
+        static_assert(NP == 2 && KS == 1, "the ring is the one-k-step fp16-pair loop");
+        static_assert(3 * STAGE <= 160 * 1024, "three stages of this tile do not fit the LDS");
+        constexpr int NPX = RPX * NP, NPC = (RPX + RPW) * NP;            // pieces of a tile per wave: X first, then W
+        // pieces a wave issues per tile: its row blocks past RBX / RBW are skipped (wave-uniform), padded taps do issue
+        const int skipped = (RBX % NW != 0 && wave + (RPX - 1) * NW >= RBX ? NP : 0) + (RBW % NW != 0 && wave + (RPW - 1) * NW >= RBW ? NP : 0);
+        auto piece = [&](char* sb, int q) {     // piece q (a constant after unrolling) of the tile described by the l_* state
+            if (q < NPX) {
+                const int j = q / NP, pl = q % NP, rb = wave + j * NW;
+                if (RBX % NW != 0 && rb >= RBX) return;
+                const bool ok = GEMM1X1 ? (xvalid[j] != 0) : (((xvalid[j] >> l_tap) & 1u) != 0);
+                const int vo = ok ? xoff[j] + l_xtile : (int)0x80000000;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs[pl], (lds_dst_t)(sb + (pl * BM + rb * 16) * 64), 16, vo, l_xs, 0, 0);
+            } else {
+                const int j = (q - NPX) / NP, pl = (q - NPX) % NP, rb = wave + j * NW;
+                if (RBW % NW != 0 && rb >= RBW) return;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_dst_t)(sb + XBYTES + (pl * BN + rb * 16) * 64), 16, woff[j],
+                                                         (int)(pl * wplane_b) + (l_k0 >> 5) * p.Npad * 64, 0, 0);
+            }
+        };
+        auto wait_newest = [&]() {              // all but the newest tile's pieces of this wave have landed
+            if (skipped == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPC) : "memory");
+            else if (skipped == NP) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPC - NP) : "memory");
+            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPC - 2 * NP) : "memory");
+        };
+        // tile in `rd`: the X fragments, then per output-channel group its W fragments (read one group ahead) and MFMAs, and
+        // behind them, with `copy`, that group's share of the pieces of the tile at l_* into `wr`
+        auto ring_tile = [&](const char* rd, char* wr, auto copy) {
+            const char* Wb = rd + XBYTES;
+            BP<NP> b[MT], a, an;
+#pragma unroll
+            for (int mi = 0; mi < MT; ++mi) {
+                const char* r = rd + ((wm * MT + mi) * 16 + frow) * 64 + fq;
+#pragma unroll
+                for (int pl = 0; pl < NP; ++pl) b[mi].p[pl] = *reinterpret_cast<const bf16x8*>(r + pl * BM * 64);
+            }
+#pragma unroll
+            for (int pl = 0; pl < NP; ++pl) a.p[pl] = *reinterpret_cast<const bf16x8*>(Wb + (wn * NT * 16 + frow) * 64 + fq + pl * BN * 64);
+#pragma unroll
+            for (int ni = 0; ni < NT; ++ni) {
+                if (ni + 1 < NT) {
+#pragma unroll
+                    for (int pl = 0; pl < NP; ++pl) an.p[pl] = *reinterpret_cast<const bf16x8*>(Wb + ((wn * NT + ni + 1) * 16 + frow) * 64 + fq + pl * BN * 64);
+                }
+#pragma unroll
+                for (int mi = 0; mi < MT; ++mi) acc[mi][ni] = mmaN<NP>(a, b[mi], acc[mi][ni]);
+                if constexpr (decltype(copy)::value) {
+#pragma unroll
+                    for (int q = ni * NPC / NT; q < (ni + 1) * NPC / NT; ++q) piece(wr, q);
+                }
+                a = an;
+            }
+        };
+        const int nt = max(kt_end - kt_begin, 0);       // (an empty split-K range: every wave still passes the barrier and writes zeros)
+        if (nt > 0) {
+            tile_setup(kt_begin);
+#pragma unroll
+            for (int q = 0; q < NPC; ++q) piece(dsm, q);
         }
-        mma_tile(stage, ns_cur);
-        ns_cur = ns_next;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the next tile's copies, before the barrier that publishes them
+        if (nt > 1) {
+            tile_advance();
+#pragma unroll
+            for (int q = 0; q < NPC; ++q) piece(dsm + STAGE, q);
+            wait_newest();
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        lds_barrier();
+        int st = 0, i = 0;                              // the stage of tile i
+        for (; i + 2 < nt; ++i) {
+            tile_advance();                             // -> tile i + 2, into the stage of tile i - 1
+            ring_tile(dsm + st * STAGE, dsm + (st == 0 ? 2 : st - 1) * STAGE, std::true_type{});
+            wait_newest();
+            lds_barrier();
+            st = st == 2 ? 0 : st + 1;
+        }
+        for (; i < nt; ++i) {                           // the last two tiles: nothing new to copy
+            ring_tile(dsm + st * STAGE, nullptr, std::false_type{});
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            lds_barrier();
+            st = st == 2 ? 0 : st + 1;
+        }
+    } else {        // two stages: the next tile is copied while this one is multiplied and waited for at its end
+        int ns_cur = 1;
+        if (kt_begin < kt_end) {
+            tile_setup(kt_begin);
+            ns_cur = steps_here();
+            issue(0);
+        }
+        // the first tile's LDS-DMA has to have LANDED before any wave reads it: the copies count on vmcnt, and nothing in the
+        // workgroup-barrier contract makes hipcc drain vmcnt for them (ROCm 7.2 happens to) -- wait explicitly, as the stem does
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
+        for (int kt = kt_begin; kt < kt_end; ++kt) {
+            const int stage = (kt - kt_begin) & 1;
+            int ns_next = 1;
+            if (kt + 1 < kt_end) {
+                tile_advance();
+                ns_next = steps_here();
+                issue(stage ^ 1);        // lands while this tile is multiplied; the stage was last read before the previous barrier
+            }
+            mma_tile(stage, ns_cur);
+            ns_cur = ns_next;
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the next tile's copies, before the barrier that publishes them
+            __syncthreads();
+        }
     }
     if constexpr (NP == 2) {         // back from the operands' scales 2^8 (activation) and 2^k (weights): exact, before anything else
 #pragma unroll
@@ -246,10 +339,10 @@ __device__ __forceinline__ void conv_dma_body(const ConvParams& p, char* __restr
     conv_epilogue<MT, NT>(p, acc, m0, n0, wm, wn, lane, HoWo);
 }
 
-template <int MT, int NT, int WM, int WN, int NP, bool GEMM1X1, int KSH = 1>
+template <int MT, int NT, int WM, int WN, int NP, bool GEMM1X1, int KSH = 1, int NST = 2>
 __global__ __launch_bounds__(64 * WM * WN) void conv_dma_kernel(const ConvParams p) {
     extern __shared__ __attribute__((aligned(1024))) char dsm_dma[];
-    conv_dma_body<MT, NT, WM, WN, NP, GEMM1X1, KSH>(p, dsm_dma);
+    conv_dma_body<MT, NT, WM, WN, NP, GEMM1X1, KSH, NST>(p, dsm_dma);
 }
 
 namespace {
@@ -262,7 +355,16 @@ struct ConvDCfg {
     const char* nameh2;      // ... and two ("_ks2"): only the tiles whose two stages fit 160 KB, BM + BN <= 320
     int BM, BN, threads;
     convd_kernel_t gemm3, general3, gemm1, general1, gemmh, generalh, gemmh2, generalh2;
+    convd_kernel_t gemmhr, generalhr;      // "dmah_*" with one k-step per barrier on the three-stage ring (nullptr: the tile keeps two stages)
 };
+// LDS stages of the one-k-step fp16-pair loop of a BM x BN tile: the ring wherever stages * 2 planes * (BM + BN) * 64 bytes
+// fit the 160 KB of a CU
+constexpr int dmah_stages(int BM, int BN) { return 3 * 2 * (BM + BN) * 64 <= 160 * 1024 ? 3 : 2; }
+template <int MT, int NT, int WM, int WN, bool GEMM1X1>
+constexpr convd_kernel_t dmah_ring_kernel() {
+    if constexpr (dmah_stages(16 * MT * WM, 16 * NT * WN) == 3) return conv_dma_kernel<MT, NT, WM, WN, 2, GEMM1X1, 1, 3>;
+    else return nullptr;
+}
 // (the k64 kernels of a tile that does not fit are never instantiated)
 template <int MT, int NT, int WM, int WN, bool GEMM1X1>
 constexpr convd_kernel_t dmah_ks2_kernel() {
@@ -275,7 +377,8 @@ constexpr convd_kernel_t dmah_ks2_kernel() {
      conv_dma_kernel<MT, NT, WM, WN, 3, true>, conv_dma_kernel<MT, NT, WM, WN, 3, false>,                       \
      conv_dma_kernel<MT, NT, WM, WN, 1, true>, conv_dma_kernel<MT, NT, WM, WN, 1, false>,                       \
      conv_dma_kernel<MT, NT, WM, WN, 2, true>, conv_dma_kernel<MT, NT, WM, WN, 2, false>,                       \
-     dmah_ks2_kernel<MT, NT, WM, WN, true>(), dmah_ks2_kernel<MT, NT, WM, WN, false>()}
+     dmah_ks2_kernel<MT, NT, WM, WN, true>(), dmah_ks2_kernel<MT, NT, WM, WN, false>(),                         \
+     dmah_ring_kernel<MT, NT, WM, WN, true>(), dmah_ring_kernel<MT, NT, WM, WN, false>()}
 const ConvDCfg kCfgD[] = {
     DCFG(4, 4, 4, 2),    // 256 x 128, 8 waves
     DCFG(2, 4, 4, 2),    // 128 x 128, 8 waves
@@ -381,13 +484,13 @@ long dma_grid_blocks(int i, const ConvParams& p) {
 int dma3_k_tiles(int, const ConvParams& p) { return (p.K + 31) / 32; }
 int dmab_k_tiles(int, const ConvParams& p) { return (p.K + 31) / 32 / 2; }
 
-// tile i as kernel `gemm` (a 1x1 GEMM) or `general`, `stage_planes` LDS planes of (BM + BN) x 32 per stage, two stages
-int dma_launch(const ConvParams& p, int i, convd_kernel_t gemm, convd_kernel_t general, int stage_planes, hipStream_t st) {
+// tile i as kernel `gemm` (a 1x1 GEMM) or `general`, `stage_planes` LDS planes of (BM + BN) x 32 per stage, `stages` of them
+int dma_launch(const ConvParams& p, int i, convd_kernel_t gemm, convd_kernel_t general, int stage_planes, hipStream_t st, int stages = 2) {
     const long blocks = dma_grid_blocks(i, p);
     SSD_UNSUPPORTED_IF(blocks > 0x7fffffffL, "conv2d: grid too large");
     const ConvDCfg& g = kCfgD[i];
     const convd_kernel_t fn = conv_is_gemm1x1(p) ? gemm : general;
-    const int lds = 2 * stage_planes * (g.BM + g.BN) * 64;
+    const int lds = stages * stage_planes * (g.BM + g.BN) * 64;
     if (lds > 64 * 1024) SSD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     dim3 grid((unsigned)blocks, p.split_k > 1 ? p.split_k : 1);
     hipLaunchKernelGGL(fn, grid, dim3(g.threads), lds, st, p);
@@ -415,6 +518,7 @@ int dmah_k_tiles(int j, const ConvParams& p) {
 int dmah_launch(const ConvParams& p, int j, hipStream_t st) {
     const ConvDCfg& g = kCfgD[dmah_list().tile[j]];
     if (dmah_list().ks[j] == 2) return dma_launch(p, dmah_list().tile[j], g.gemmh2, g.generalh2, 4, st);
+    if (!p.dma_two_stage && g.gemmhr) return dma_launch(p, dmah_list().tile[j], g.gemmhr, g.generalhr, 2, st, 3);
     return dma_launch(p, dmah_list().tile[j], g.gemmh, g.generalh, 2, st);
 }
 

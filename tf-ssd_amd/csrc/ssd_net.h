@@ -189,6 +189,7 @@ struct ssd_net {
     bool image_v2 = true;           // whole-image kernel only (the row-band kernels of blocks 1-6 have one form): the second form (ssd_imgblock2.hip: compile-time geometry, adjacent pixels per lane) where it has a configuration; 0 = the first form (A/B; equal within tolerance, not bitwise: the k-slot order inside the project MFMAs differs)
     bool conv_dma = true;           // offer the LDS-DMA tiles over pre-split activation planes (ssd_convdma.hip) to the autotune / accept them from tables
     bool conv_f16x2 = true;         // accept the two-plane fp16 tiles ("dmah_*") from tables / offer them to the autotune; 0: a "dmah_*" line runs its "dma3_*" twin (the same tile and split-K)
+    bool dma_ring = true;           // "dmah_*" tiles with one k-step per barrier run the three-stage LDS ring (ssd_convdma.hip); 0: the two-stage loop, the same bits
     bool image_f16x2 = true;        // whole-image blocks of fp32 nets on the split route (img_choice 2): the two-plane fp16 form (three fp16 MFMAs per product in both 1x1 GEMMs) where the block's input has a static bound (Tensor::bound); 0: the split-bf16 form everywhere
     bool plane_only = true;         // drop the fp32 copy of an activation whose readers all take its bf16 planes (Tensor::plane_only); 0: store both
     bool image_ticket = false;      // combine the channel-group slabs inside the launch (arrival ticket) instead of by a second launch

@@ -312,6 +312,7 @@ ConvParams layer_conv_params(const ssd_net& net, const Layer& l, int B, const fl
         p.wh = reinterpret_cast<const short*>(l.wh);
         p.acc_scale = ldexpf(1.f, -(8 + l.wh_k));
     }
+    p.dma_two_stage = !net.dma_ring;
     if (l.in >= 0 && net.tensors[l.in].planes) {       // the LDS-DMA tiles read the input's bf16 planes
         const Tensor& ti = net.tensors[l.in];
         p.xp = ti.planes; p.xp_plane = ti.plane_stride; p.xp_np = ti.planes_np;
@@ -1552,6 +1553,8 @@ static const OptionSpec kOptions[] = {
     // whole-image blocks on the split route: the two-plane fp16 form where the input has a static bound (default 1); 0: the
     // split-bf16 form everywhere (its fp16 weight planes are then not packed)
     {"image_f16x2", &ssd_net::image_f16x2, nullptr, 0, 1, 1},
+    // "dmah_*" lines with one k-step per barrier: the three-stage LDS ring (default 1) / the two-stage loop (0); the same bits
+    {"dma_ring", &ssd_net::dma_ring, nullptr, 0, 1, 0},
     {"plane_only", &ssd_net::plane_only, nullptr, 0, 1, 0},     // no fp32 copy of an activation whose readers all take its planes (default 1)
     {"use_graph", &ssd_net::use_graph, nullptr, 0, 1, 0},
 };

@@ -50,7 +50,7 @@ class ConvDesc(ctypes.Structure):
     """struct ssd_conv_desc (include/ssd_hip.h)."""
     _fields_ = [(n, ctypes.c_int) for n in (
         "B", "H", "W", "Cin", "Cout", "kh", "kw", "stride", "dilation",
-        "pad_t", "pad_l", "pad_b", "pad_r", "act", "has_residual")]
+        "pad_t", "pad_l", "pad_b", "pad_r", "act", "has_residual", "dma_two_stage")]
 
 
 class ResizeDesc(ctypes.Structure):
