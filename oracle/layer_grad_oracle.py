@@ -46,6 +46,11 @@ and of six subtly wrong forwards built from the reference formulas alone (each h
     deltas 282, probs 101 (K = 288)      istd without eps: out 1.4e4      residual added before the activation: out 1.4e7
     ReLU in place of ReLU6: out 8.3e6      head halves swapped at the split column: probs 3.6e9, deltas 2.9e7
 
+Beside the max of E, ``e_stats`` / ``Report`` carry its root mean square over the compared elements with A > 0: at long K
+(the inference graphs reach 9216) operands rounded to 16 significand bits score a max E below 16, while the RMS keeps a
+factor >= 37 over the fp32 restatement's.  ``forward_yardstick`` gives both reference-only yardsticks of a dense conv or head
+on the input of the comparison (tests/test_layer_infer_cpu.py, tests/test_layer_infer_gpu.py).
+
 Layouts: activations NHWC, kernels HWIO, depthwise kernels [3,3,C,1] (Keras).  Only tests/ imports
 this module."""
 import numpy as np
@@ -462,8 +467,9 @@ def moving_update(moving_mean, moving_var, mean, var, M):
 
 
 # ------------------------------------------------------------------ the metric
-def e_metric(got, ref, A, exclude=None):
-    """max E over the elements, its flat index, and the count of NaN / A == 0 mismatches (E = inf there)."""
+def e_stats(got, ref, A, exclude=None):
+    """max E over the elements, its flat index, and the root mean square of E over the compared elements with A > 0
+    (excluded elements left out).  NaN / A == 0 mismatches count as E = inf in the max (and, where A > 0, in the RMS)."""
     got = np.asarray(got, np.float64).reshape(-1)
     ref = ref.detach().numpy().reshape(-1) if isinstance(ref, torch.Tensor) else np.asarray(ref, np.float64).reshape(-1)
     A = A.detach().numpy().reshape(-1) if isinstance(A, torch.Tensor) else np.asarray(A, np.float64).reshape(-1)
@@ -472,32 +478,51 @@ def e_metric(got, ref, A, exclude=None):
     with np.errstate(divide="ignore", invalid="ignore"):
         E = np.where(A > 0, err / (U * A), np.where(err == 0, 0.0, np.inf))
     E[~np.isfinite(got)] = np.inf                     # NaN / inf read back: an unwritten or broken element
+    keep = A > 0
     if exclude is not None:
         ex = exclude.numpy().reshape(-1) if isinstance(exclude, torch.Tensor) else np.asarray(exclude).reshape(-1)
         E = np.where(ex, 0.0, E)
+        keep = keep & ~ex.astype(bool)
     if E.size == 0:
-        return 0.0, -1
+        return 0.0, -1, 0.0
     i = int(np.argmax(E))
-    return float(E[i]), i
+    with np.errstate(over="ignore", invalid="ignore"):
+        rms = float(np.sqrt(np.mean(E[keep] ** 2))) if keep.any() else 0.0
+    return float(E[i]), i, rms
+
+
+def e_metric(got, ref, A, exclude=None):
+    """max E over the elements, its flat index, and the count of NaN / A == 0 mismatches (E = inf there)."""
+    return e_stats(got, ref, A, exclude)[:2]
+
+
+def e_rms(got, ref, A, exclude=None):
+    """The RMS companion of ``e_metric``: sqrt(mean E^2) over the compared elements with A > 0."""
+    return e_stats(got, ref, A, exclude)[2]
 
 
 class Report(object):
-    """Worst E per layer kind and where; ``fails`` lists everything above the bar."""
+    """Worst E per layer kind and where, the largest RMS of E of that kind next to it; ``fails`` lists everything above
+    the bar; ``stats`` holds (max E, RMS of E) of every compared tensor under (layer, what)."""
     def __init__(self, bar=E_BAR):
-        self.bar, self.worst, self.fails, self.compared = bar, {}, [], 0
+        self.bar, self.worst, self.worst_rms, self.stats, self.fails, self.compared = bar, {}, {}, {}, [], 0
 
     def add(self, kind, layer, what, got, ref, A, exclude=None):
-        E, i = e_metric(got, ref, A, exclude)
+        E, i, rms = e_stats(got, ref, A, exclude)
         self.compared += 1
+        self.stats[(layer, what)] = (E, rms)
         key = "%s: %s" % (kind, what.split(":")[0])
         if key not in self.worst or E > self.worst[key][0]:
             self.worst[key] = (E, layer, what)
+        if key not in self.worst_rms or rms > self.worst_rms[key][0]:
+            self.worst_rms[key] = (rms, layer, what)
         if not E <= self.bar:
             self.fails.append("%s %s: E = %.3g at flat index %d" % (layer, what, E, i))
         return E
 
     def lines(self):
-        return ["worst E %-44s %8.3f  (%s %s)" % (k, v[0], v[1], v[2]) for k, v in sorted(self.worst.items())]
+        return ["worst E %-44s %8.3f  (%s %s)   rms %.3f (%s)" % (k, v[0], v[1], v[2], self.worst_rms[k][0], self.worst_rms[k][1])
+                for k, v in sorted(self.worst.items())]
 
 
 # ------------------------------------------------------------------ a whole graph, teacher forced
@@ -505,6 +530,50 @@ def bf16_rne(a):
     """fp32 value (the argument is first rounded to float32, as the checked implementation holds it) -> nearest
     bfloat16, ties to even; returned as a float64 tensor.  |x| rounds to |round(x)|: the same function serves A."""
     return _t(a, torch.float32).to(torch.bfloat16).to(torch.float64)
+
+
+def cut16(a, rounded=False):
+    """fp32 value -> its leading 16 significand bits, as a float32 tensor: truncated (what a three-way bf16 split that lost
+    its third plane multiplies) or, ``rounded``, rounded to nearest with ties to even (the weaker cut: half the error)."""
+    i = _t(a, torch.float32).contiguous().view(torch.int32)
+    if rounded:
+        i = i + 0x7F + ((i >> 8) & 1)            # sign-magnitude bits: the same addition serves both signs
+    return (i & -256).view(torch.float32)
+
+
+def rne16(a):
+    """``cut16(a, rounded=True)`` as a float64 tensor: a ``round_ops`` of conv_forward.  |x| rounds to |round(x)|."""
+    return cut16(a, rounded=True).to(torch.float64)
+
+
+TWO_PLANE_A = 2.0 ** -33 / U
+
+
+def two_plane_allowance(ref):
+    """What A grows by for a tensor kept as the two-plane fp16 pair only: the pair holds x within 2^-22 |x| + 2^-33
+    (csrc/ssd_bf16x3.h), i.e. within u (4 |x| + 2^-9)."""
+    return 4.0 * ref.abs() + TWO_PLANE_A
+
+
+def forward_yardstick(spec, t, round_ops=None, ref=None, A=None):
+    """Reference-only yardsticks of one dense conv / head layer on the input of the comparison, per output key:
+      "r32": (max E, RMS E) of ``layer_forward(..., dtype=torch.float32)`` -- the plain fp32 restatement (in the form
+             ``round_ops`` names, so that a bf16-mode layer is measured against its own definition);
+      "r16": the same for the float64 forward with both matrix operands ROUNDED to nearest to 16 significand bits
+             (always on the unrounded form: under bf16 operands the cut is the identity).
+    Both against the float64 forward and its A (``ref`` / ``A``: those of the form ``round_ops``, where the caller has them)."""
+    assert spec["kind"] in ("conv", "head"), spec["kind"]
+    if ref is None:
+        ref, A = layer_forward(spec, t, round_ops=round_ops), layer_forward(spec, t, absolute=True, round_ops=round_ops)
+    f32 = layer_forward(spec, t, dtype=torch.float32, round_ops=round_ops)
+    if round_ops is not None:
+        ref16, A16 = layer_forward(spec, t), layer_forward(spec, t, absolute=True)
+    else:
+        ref16, A16 = ref, A
+    c16 = layer_forward(spec, t, round_ops=rne16)
+    keys = [k for k in ref if k != "pre"] if "moving_var" in t or not spec.get("bn") else ["pre"]
+    return {k: {"r32": e_stats(f32[k].numpy(), ref[k], A[k])[::2], "r16": e_stats(c16[k].numpy(), ref16[k], A16[k])[::2]}
+            for k in keys}
 
 
 def check_graph(specs, fetch, weights, grads, hyper_params, B, report, moving_after=None,
@@ -615,7 +684,8 @@ def check_graph(specs, fetch, weights, grads, hyper_params, B, report, moving_af
     return {"layers": n_layers, "pool_excluded": pool_tied / pool_cells if pool_cells else 0.0}
 
 
-def check_forward_graph(specs, fetch, weights, hyper_params, B, report, only=None, frozen=(), round_ops=None):
+def check_forward_graph(specs, fetch, weights, hyper_params, B, report, only=None, frozen=(), round_ops=None,
+                        yardstick=None, planes=None):
     """Hold the training FORWARD of another implementation to the float64 layer oracle: every layer's outputs
     (layer_forward) recomputed from the implementation's own input tensor ``fetch(s["tin"])`` and compared through
     ``report.add``.  ``fetch`` as in check_graph, plus "probs" [B,N,L] and "deltas" [B,N,4] (a head's slices are taken at
@@ -624,6 +694,10 @@ def check_forward_graph(specs, fetch, weights, hyper_params, B, report, only=Non
     layer never writes them).  round_ops: the bf16 mode -- a dense conv's outputs are admitted in two forms, both operands
     rounded once or neither (the same conv on an fp32 tile); one launch writes all outputs of a layer, so ONE form must
     meet the bar for all of them (the form with the smaller worst E is the one reported).
+    yardstick: a dict that receives, per dense conv / head layer, ``forward_yardstick`` of the reported form on the same
+    input, {layer: {key: {"r32": (max, rms), "r16": (max, rms)}}}.  planes: {tensor name: number of planes} of the output
+    tensors the implementation keeps as planes ONLY -- 3 (the exact split) needs nothing; 2 (the fp16 pair): the tensor's A
+    grows by ``two_plane_allowance`` of the reference.
     Returns {"layers": n, "clamps": {ReLU6 layer: (share of sixes, share of zeros) of the ORACLE's out}}."""
     fm = hyper_params["feature_map_shapes"]
     lvl_off = np.cumsum([0] + [f * f * (len(a) + 1) for f, a in zip(fm, hyper_params["aspect_ratios"])])
@@ -664,12 +738,18 @@ def check_forward_graph(specs, fetch, weights, hyper_params, B, report, only=Non
                         t[k] = fetch(k + ":" + s["name"])
                     got["pre"] = t["pre"]
         forms = [(layer_forward(s, t, round_ops=round_ops), layer_forward(s, t, absolute=True, round_ops=round_ops))]
+        form_ops = round_ops if s["kind"] in ("conv", "head") else None
         if round_ops and s["kind"] in ("conv", "head"):
             forms.append((layer_forward(s, t), layer_forward(s, t, absolute=True)))
             worst = [max(e_metric(got[k], ref[k], A[k])[0] for k in got) for ref, A in forms]
-            forms = [forms[int(np.argmin(worst))]]
+            if int(np.argmin(worst)) == 1:
+                forms, form_ops = forms[1:], None
         ref, A = forms[0]
         assert set(ref) == set(got), (s["name"], sorted(ref), sorted(got))
+        if yardstick is not None and s["kind"] in ("conv", "head"):
+            yardstick[s["name"]] = forward_yardstick(s, t, round_ops=form_ops, ref=ref, A=A)
+        if planes and s["tout"] and planes.get(s["tout"]) == 2:
+            A = dict(A, out=A["out"] + two_plane_allowance(ref["out"]))
         for k in sorted(got):
             report.add(kind, s["name"], k + ":" + (s["tout"] or s["name"]), got[k], ref[k], A[k])
         if s.get("act") == "relu6":

@@ -125,10 +125,7 @@ def _dense_bn_case():
     return ("dense_bn", _spec(bn="bn", act="relu6"), 2, 9, 8, 16, 24)          # K = 144
 
 
-def _cut16(a):
-    """fp32 -> its leading 16 significand bits (truncated): what a three-plane bf16 split that lost its third plane
-    multiplies."""
-    return (a.to(torch.float32).contiguous().view(torch.int32) & -256).view(torch.float32)
+_cut16 = lg.cut16      # fp32 -> its leading 16 significand bits (truncated): the oracle's helper, shared with tests/test_layer_infer_cpu.py
 
 
 def _e(got, ref, A):
