@@ -53,7 +53,7 @@ compile ssd_png_dec.hip -ffp-contract=off
 compile ssd_png_inflate.hip -ffp-contract=off
 # drawing: array_to_img's fp32 steps round separately too (byte-exact against Keras + Pillow)
 compile ssd_draw.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
-for s in ssd_conv.hip ssd_conv3.hip ssd_convdma.hip ssd_wino.hip ssd_skinny.hip ssd_ops.hip ssd_fused.hip ssd_bandblock.hip ssd_band3.hip ssd_imgblock.hip ssd_imgblock2.hip ssd_dwproj.hip ssd_net.hip ssd_tune.hip ssd_train.hip ssd_optim.hip; do
+for s in ssd_conv.hip ssd_conv3.hip ssd_convdma.hip ssd_wino.hip ssd_skinny.hip ssd_ops.hip ssd_fused.hip ssd_bandblock.hip ssd_band3.hip ssd_imgblock.hip ssd_imgblock2.hip ssd_dwproj.hip ssd_net.hip ssd_storage.hip ssd_tune.hip ssd_train.hip ssd_optim.hip; do
   [ -f "$s" ] && compile "$s"
 done
 wait

@@ -22,6 +22,11 @@ static const char* kKindName[] = {"conv", "dw", "pool", "l2norm", "softmax", "fu
 enum Route { RT_OFF = 0, RT_LAYER, RT_STEM, RT_DWPROJ, RT_TILE, RT_BAND, RT_BAND3, RT_IMAGE, RT_IMAGE_SPLIT };
 inline bool route_is_image(Route r) { return r == RT_IMAGE || r == RT_IMAGE_SPLIT; }     // the whole-image kernel, any form
 
+// Who writes the planes of a layer's output while they are live (plane_writer, ssd_storage.hip).  PW_NONE: nobody, they
+// are not live.  PW_KERNEL: the layer's own kernel, from registers.  PW_PASS: a split pass over the fp32 copy behind it.
+enum PlaneWriter { PW_NONE = 0, PW_KERNEL, PW_PASS };
+enum PlaneOutput { PO_OUT = 0, PO_E_OUT };     // Layer::out / Layer::e_out
+
 struct Param {
     std::string name;
     std::vector<int> shape;
@@ -38,17 +43,18 @@ struct Tensor {
     float* dev = nullptr;     // arena slot, max_batch images
     // the same activation as bf16 planes [planes_np][plane_stride] for the LDS-DMA conv tiles of its consumers
     // (csrc/ssd_convdma.hip): allocated at finalize for every tensor a dense conv with Cin % 32 == 0 reads (option
-    // "conv_dma"), WRITTEN -- by the producer's epilogue or by split_planes_kernel -- only while a running consumer's
-    // chosen configuration is an LDS-DMA tile (planes_live, recomputed with the launch plan)
+    // "conv_dma", finalize_planes), kept where a chosen tile reads them (finalize_free_unread_planes), WRITTEN -- by the
+    // producer's kernel or by a split pass, Layer::w_out -- only while a running consumer's chosen configuration is an
+    // LDS-DMA tile: planes_live.  planes_live and plane_only are written by resolve_storage (ssd_storage.hip) alone
     short* planes = nullptr;
     long plane_stride = 0;    // elements between planes
     int planes_np = 0;        // 3: exact split h, m, l (fp32 nets); 1: bf16 rounding (the bf16 mode); 2: the fp16 pair of 2^8 x (fp32 nets, a
-                              // ReLU6-bounded tensor whose plane readers all chose "dmah_*" tiles: finalize_resolve_f16x2, ssd_net.hip)
+                              // ReLU6-bounded tensor whose plane readers all chose "dmah_*" tiles: finalize_resolve_f16x2, ssd_storage.hip)
     int planes_cap = 0;       // planes the allocation holds (planes_np <= planes_cap)
     bool planes_live = false;
-    // the planes ARE the tensor: its producer skips the fp32 store into `dev` (the arena slot stays, unwritten).  Decided with
-    // the launch plan (plan_steps, ssd_net.hip): planes live, every running reader a dense conv on an LDS-DMA tile, the
-    // producer a kernel whose plane store needs no fp32 copy, option "plane_only" 1.  Inference only: the training step
+    // the planes ARE the tensor: its producer skips the fp32 store into `dev` (the arena slot stays, unwritten).  Decided by
+    // plan_storage (ssd_storage.hip): planes live, every running reader a dense conv on an LDS-DMA tile, the producer a
+    // kernel whose plane store needs no fp32 copy (PW_KERNEL), option "plane_only" 1.  Inference only: the training step
     // keeps activations of its own.  ssd_net_fetch_activation joins the planes (h + m + l is exact)
     bool plane_only = false;
     // static bound of the tensor, from the weights alone (finalize_tensor_bounds, ssd_net.hip): every value any input can
@@ -91,6 +97,7 @@ struct Layer {
     int img_choice = -1;            // whole-block LK_FUSED layers the image kernel can run: 1 / 2 = its fp32-MFMA / split-bf16 form (with option image_f16x2 and a statically bounded input: the two-plane fp16 form in its place, same table line) won the finalize-time race against the layer kernels, 0 = it lost, -1 = not timed
     int fused_by2 = -1;             // depthwise / project members: their type-2 LK_FUSED layer
     Route route = RT_OFF;           // what runs this layer under the current options and tuning choices (resolve_routes, ssd_net.hip)
+    PlaneWriter w_out = PW_NONE, w_e_out = PW_NONE;     // who writes the planes of `out` / `e_out` (resolve_storage, ssd_storage.hip, alone)
     float* splitk_part = nullptr;   // this layer's own split-K slab (layers may run concurrently)
     // LK_FUSED: weight copies with the folded BatchNorm scale multiplied in (per output channel)
     float *fz_we = nullptr, *fz_wd = nullptr, *fz_wp = nullptr;
@@ -151,8 +158,9 @@ struct EventPair {
     }
 };
 
-// One launch of the forward's plan (plan_steps, ssd_net.hip): a pure function of the graph, the options, the
-// routes and `timing`, built at the first forward that needs it and kept until ssd_net::drop_graphs().
+// One launch of the forward's plan (plan_steps, ssd_net.hip, the fields' one writer): order, stream and cross-stream
+// waits -- nothing about storage.  A pure function of the graph, the options, the routes and `timing`, built at the
+// first forward that needs it and kept until ssd_net::drop_graphs().
 struct Step {
     int layer = -1;
     int sid = -1;                   // stream: -1 the caller's (main), 0 / 1 ssd_net::side[]
@@ -285,20 +293,37 @@ struct ssd_net {
 namespace ssd {
 
 // ---- what the kernel-selection unit (ssd_tune.hip) needs of the graph runner (ssd_net.hip)
+// (as_read_by: a CONV_READS_* family that is to read the input's planes whatever form they have now; -1: as they stand)
 ConvParams layer_conv_params(const ssd_net& net, const Layer& l, int B, const float* in, float* out, const float* res,
-                             float* deltas_out, float* probs_out);
+                             float* deltas_out, float* probs_out, int as_read_by = -1);
 int run_layer(ssd_net& net, const Layer& l, int B, float* deltas_out, float* probs_out, hipStream_t st, int cfg_override = -1);
 void resolve_routes(ssd_net& net);
 inline bool layer_runs(const Layer& l) { return l.route != RT_OFF; }
 bool image_kernel_takes(const ssd_net& net, const Layer& f);
 ImagePlan image_plan(const ssd_net& net, const Layer& f, int B, FusedBlockParams* shape = nullptr, bool probe_pairs = false);
-std::vector<char> plane_only_candidates(const ssd_net& net);
 int dev_alloc(ssd_net& net, size_t floats, float** out);
+void dev_free(ssd_net& net, float* p);
 
 // ---- ... and ssd_net_finalize of that unit: the four steps that choose, in the order finalize takes them
 int finalize_apply_preset(ssd_net* net, int max_batch, bool* image_preset_ok);    // the table's lines, where they can run
 int autotune(ssd_net& net, int B, hipStream_t st);                                // conv layers without one: raced
 int tune_image_blocks(ssd_net& net, int B, hipStream_t st);                       // whole-image blocks without one: raced
 int tune_launch_mode(ssd_net* net, int B);                                        // graph replay or direct launches: read or raced
+
+// ---- the activation-storage unit (ssd_storage.hip): its rule, its pure resolver and the one writer of the resolved fields
+struct StoragePlan {
+    std::vector<char> live, only;               // per tensor: Tensor::planes_live, Tensor::plane_only
+    std::vector<PlaneWriter> w_out, w_e_out;    // per layer: Layer::w_out, Layer::w_e_out
+};
+PlaneWriter plane_writer(const ssd_net& net, const Layer& l, int cfg, PlaneOutput which);
+StoragePlan plan_storage(const ssd_net& net);
+void resolve_storage(ssd_net& net);             // beside resolve_routes: ssd_net_create, ssd_net_set_option, the end of ssd_net_finalize
+int planes_pass(ssd_net& net, int tensor, int B, hipStream_t st);
+bool tensor_relu6_bounded(const ssd_net& net, int t);
+int dmah_or_twin(const ssd_net& net, const Layer& l, int cfg, bool pair = true);
+int finalize_planes(ssd_net* net, int max_batch, hipStream_t st);     // ... and its finalize steps, in the order finalize takes them
+void finalize_resolve_f16x2(ssd_net* net);
+int finalize_free_unread_planes(ssd_net* net, hipStream_t st);
+long fetch_tensor(ssd_net* net, const char* who, const char* layer, float* host_out, size_t cap, bool want_planes, int* planes_out);
 
 }  // namespace ssd

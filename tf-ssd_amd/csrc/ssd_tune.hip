@@ -88,16 +88,13 @@ int finalize_apply_preset(ssd_net* net, int max_batch, bool* image_preset_ok) {
         SSD_UNSUPPORTED_IF(cfg >= 0 && conv_config_is_dmah(cfg) && net->precision != 0,
                            "finalize: the table puts layer %s on %s: the two-plane fp16 tiles are admitted in fp32 nets (precision 0) only",
                            l.name.c_str(), conv_config_name(cfg));
-        // a "dmah_*" line where the form may not run -- option conv_f16x2 0, an input that is not ReLU6-bounded, non-finite
-        // weights -- runs its "dma3_*" twin: the same tile, the same split-K
-        if (cfg >= 0 && conv_config_is_dmah(cfg) && (!net->conv_f16x2 || !l.wh)) cfg = conv_dmah_twin(cfg);
+        cfg = dmah_or_twin(*net, l, cfg);       // a "dmah_*" line where the form may not run: its "dma3_*" twin
         if (cfg < 0 || !conv_config_allowed(cfg, net->precision)) { ++n_tuned; continue; }
         l.cfg = cfg;
         l.split_k = it->second.second;
-        ConvParams p = layer_conv_params(*net, l, max_batch, net->tensors[l.in].dev,
-                                         l.out >= 0 ? net->tensors[l.out].dev : nullptr, nullptr,
-                                         net->arena, net->arena);
-        if (conv_config_is_dmah(cfg)) p.xp_np = 2;         // (which form the tensor's planes take is settled below: finalize_resolve_f16x2)
+        const ConvParams p = layer_conv_params(*net, l, max_batch, net->tensors[l.in].dev,
+                                               l.out >= 0 ? net->tensors[l.out].dev : nullptr, nullptr,
+                                               net->arena, net->arena, conv_config_reads(cfg));
         const bool split_ok = l.split_k == 1 || conv_k_tiles(cfg, p) >= l.split_k;
         if (l.split_k < 1 || !split_ok || !conv_config_valid(cfg, p)) { l.cfg = -1; l.split_k = 1; ++n_tuned; continue; }
         ++n_preset;
@@ -153,8 +150,8 @@ static int race_conv_layer(ConvRace& r, Layer& l, Best* best, std::vector<Timed>
         if (fam == CONV_READS_F16X2 && (!net.conv_f16x2 || !l.wh)) continue;
         for (const int split : kSplits) {
             l.split_k = split;
-            ConvParams p = layer_conv_params(net, l, r.B, in, out, res, r.deltas.p, r.probs.p);
-            if (fam == CONV_READS_F16X2) p.xp_np = 2;       // (timed on whatever the planes hold: the matrix unit's time does not depend on the data)
+            // (a pair tile is timed on whatever the planes hold: the matrix unit's time does not depend on the data)
+            const ConvParams p = layer_conv_params(net, l, r.B, in, out, res, r.deltas.p, r.probs.p, fam);
             if (!conv_config_valid(c, p) || !conv_config_allowed(c, net.precision)) break;
             const bool direct = conv_config_family(c) == CF_DIRECT;
             if (direct && (bb.cfg[0] >= 0 || bb.cfg[1] >= 0 || split > 1)) break;     // direct only as a last resort
@@ -237,7 +234,7 @@ static void decide_tensor(ssd_net& net, int t, int B, const std::vector<Best>& b
     }
     if (flip.empty()) return;
     for (size_t li : flip) take_family(net.layers[li], bests[li], 1);
-    const bool only = plane_only_candidates(net)[t];
+    const bool only = plan_storage(net).only[t];          // ... under the readers' LDS-DMA tiles: would the fp32 copy go?
     // what the producer's store changes by, per element: np planes of 2 bytes more, 4 bytes less where the fp32 copy goes
     auto store_ms_of = [&](int np) { return store_cost_ms(tt, B, only ? 2.0 * np - 4.0 : planes_anyway ? 0.0 : 2.0 * np); };
     const double store_ms = store_ms_of(tt.planes_np), store2_ms = store_ms_of(2);
@@ -251,7 +248,8 @@ static void decide_tensor(ssd_net& net, int t, int B, const std::vector<Best>& b
 }
 
 // ... for every tensor.  The whole-image kernel is taken to run wherever it can (its own race comes later; it wins in
-// every shipped table): what it fuses away reads no tensor.  The assumption is undone afterwards.
+// every shipped table): what it fuses away reads no tensor.  The assumption is undone afterwards.  (Routes only: the
+// stored storage state stays empty until the end of finalize; decide_tensor asks the pure plan_storage.)
 static void decide_storage(ssd_net& net, int B, const std::vector<Best>& bests, bool dbg_tune) {
     std::vector<int> img_saved;
     for (auto& f : net.layers) {
@@ -299,6 +297,8 @@ int autotune(ssd_net& net, int B, hipStream_t st) {
 // Whole-image block kernel vs the layer kernels (expand GEMM + depthwise/project kernel) of the
 // same block, timed on the device at batch B: at B = 64 the 4-way channel-group reduction costs
 // what the E round trip through HBM costs, at large batches (one group) the image kernel wins.
+// The race moves the routes alone (resolve_routes): storage is not resolved before the end of finalize, so no planes are
+// live here and both sides are timed without their plane stores or split passes -- as they always were.
 int tune_image_blocks(ssd_net& net, int B, hipStream_t st) {
     EventPair ev;
     if (const int rc = ev.create()) return rc;
