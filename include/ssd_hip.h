@@ -119,7 +119,7 @@ int ssd_combined_nms(const float* boxes_dev, const float* scores_dev, int B, int
  * does); ssd_combined_nms_cfg honours it.
  *
  * SSD_NMS_HARD with class_agnostic == 0 IS ssd_decode_nms / ssd_combined_nms: the same launches, the same bits.  Everything
- * else runs the selection kernel (csrc/ssd_bbox.hip soft_nms_kernel): lists of up to ssd_nms_lds_candidates() candidates are
+ * else runs the selection kernel (csrc/ssd_decode.hip soft_nms_kernel): lists of up to ssd_nms_lds_candidates() candidates are
  * held in LDS, longer ones in the workspace.  SSD_E_INVALID: an unknown method, SSD_NMS_GAUSSIAN with sigma not finite or
  * <= 0, iou_threshold NaN or outside [0,1], and the size checks of ssd_decode_nms; its LDS limit on max_per_class still
  * answers SSD_E_UNSUPPORTED. */

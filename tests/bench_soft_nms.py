@@ -1,4 +1,4 @@
-"""Diagnostics script (not a test): the decoder behind an ``ssd_nms_config`` (``ssd_decode_nms_cfg``, csrc/ssd_bbox.hip
+"""Diagnostics script (not a test): the decoder behind an ``ssd_nms_config`` (``ssd_decode_nms_cfg``, csrc/ssd_decode.hip
 ``soft_nms_kernel``) beside ``ssd_decode_nms`` at the shape of the benchmark's inference step, B = 64, N = 2268, L = 21
 (``helpers.decoder_inputs``, the SSD300-MobileNetV2 priors), at the score thresholds 0.5 (the reference's) and 0.01 (the
 evaluation protocols').  Subjects: ``ssd_decode_nms``; hard per class through ``_cfg`` (the same launches); Gaussian and

@@ -1,4 +1,4 @@
-"""Cases and oracle for Soft-NMS and class-agnostic suppression (csrc/ssd_bbox.hip ``soft_nms_kernel``, ``ssd_decode_nms_cfg`` /
+"""Cases and oracle for Soft-NMS and class-agnostic suppression (csrc/ssd_decode.hip ``soft_nms_kernel``, ``ssd_decode_nms_cfg`` /
 ``ssd_combined_nms_cfg`` / ``ssd_net_predict_cfg``); needs no GPU.
 
 include/ssd_hip.h states the arithmetic (``ssd_nms_config``): the candidates of the hard NMS, then per list "take the largest

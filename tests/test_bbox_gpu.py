@@ -113,6 +113,73 @@ def test_decoder_many_candidates_per_class():
         np.testing.assert_allclose(_np(b), rb, atol=TOL, rtol=0)
 
 
+def unstaged_inputs():
+    """B = 2, N = 300, L = 100: a [256, L] score slab of 100 KiB is past what the compaction stages in LDS, so its lanes
+    read their rows from HBM.  Heavily overlapping priors, 60 % of the anchors boosted on one of three classes (the last
+    class among them): a few long lists, most of their candidates suppressed."""
+    rng = np.random.default_rng(61)
+    B, N, L = 2, 300, 100
+    c = rng.uniform(0.2, 0.8, (N, 2)); sz = rng.uniform(0.1, 0.4, (N, 2))
+    p = np.clip(np.concatenate([c - sz / 2, c + sz / 2], -1), 0, 1).astype(np.float32)
+    d = rng.standard_normal((B, N, 4)).astype(np.float32)
+    logits = rng.standard_normal((B, N, L)).astype(np.float32)
+    bi, ni = np.nonzero(rng.random((B, N)) < 0.6)
+    logits[bi, ni, rng.choice([3, 57, L - 1], bi.size)] += np.float32(8.0)
+    e = np.exp(logits - logits.max(-1, keepdims=True))
+    return p, d, (e / e.sum(-1, keepdims=True)).astype(np.float32)
+
+
+def test_decoder_unstaged_scores(bbox_utils):
+    """L = 100, decoder and raw form (L = 91 in test_decoder_vs_c_oracle still stages its slab)."""
+    from models.decoder import SSDDecoder
+    p, d, pr = unstaged_inputs()
+    dec = SSDDecoder(p, helpers.VARIANCES)
+    b, l, s = dec.call([d, pr], return_indices=True)
+    rb, rl, rs, rv, ri = co.decode_nms(d, pr, p, helpers.VARIANCES)
+    assert rv.min() > 1 and rv.sum() < (pr[..., 1:].max(-1) > 0.5).sum(), "nothing kept or nothing suppressed"
+    np.testing.assert_array_equal(_np(dec.last_valid_detections), rv)
+    np.testing.assert_array_equal(_np(dec.last_kept_indices), ri)
+    np.testing.assert_array_equal(_np(l), rl)
+    np.testing.assert_array_equal(_np(s), rs)
+    np.testing.assert_allclose(_np(b), rb, atol=TOL, rtol=0)
+    boxes = np.broadcast_to(p, d.shape).copy()
+    ob, osc, oc, v = bbox_utils.non_max_suppression(boxes[:, :, None, :], pr, max_output_size_per_class=200,
+                                                    max_total_size=200, score_threshold=0.5)
+    rb, rs, rc, rv = bo.combined_non_max_suppression(boxes, pr, 200, 200, 0.5, 0.5)
+    assert rv.min() > 1 and rv.sum() < (pr > 0.5).sum(), "nothing kept or nothing suppressed"
+    np.testing.assert_array_equal(_np(v), rv)
+    np.testing.assert_array_equal(_np(oc), rc)
+    np.testing.assert_array_equal(_np(osc), rs)
+    np.testing.assert_array_equal(_np(ob), rb)
+
+
+def test_decoder_max_per_class_past_64k_of_lds():
+    """max_per_class = 1700: the per-class kernel's kept-box list takes its LDS (16 * 1700 + 38,976 B) past 64 KiB, with
+    fewer than 4096 candidates.  N = 2000, L = 2: one class of small boxes on a 45 x 45 grid, every 40th a copy of its
+    left neighbour (suppressed); more survive than max_per_class keeps."""
+    from models.decoder import SSDDecoder
+    N, L, T = 2000, 2, 1700
+    rng = np.random.default_rng(62)
+    cell = np.stack(np.divmod(np.arange(N), 45), -1) / 45.0
+    p = np.concatenate([cell + 0.004, cell + 0.018], -1).astype(np.float32)
+    p[40::40] = p[39::40][:p[40::40].shape[0]]
+    d = (rng.standard_normal((1, N, 4)) * 0.05).astype(np.float32)
+    d[0, 40::40] = d[0, 39::40][:d[0, 40::40].shape[0]]
+    pr = np.zeros((1, N, L), np.float32)
+    pr[0, :, 1] = rng.uniform(0.5001, 0.999, N).astype(np.float32)
+    pr[0, :, 0] = 1 - pr[0, :, 1]
+    dec = SSDDecoder(p, helpers.VARIANCES, max_total_size=T)
+    b, l, s = dec.call([d, pr], return_indices=True)
+    rb, rl, rs, rv, ri = co.decode_nms(d, pr, p, helpers.VARIANCES, max_per_class=T, max_total=T)
+    full = co.decode_nms(d, pr, p, helpers.VARIANCES, max_per_class=N, max_total=N)[3]
+    assert rv[0] == T and T < full[0] < N, "the limit does not bind or nothing is suppressed"
+    np.testing.assert_array_equal(_np(dec.last_valid_detections), rv)
+    np.testing.assert_array_equal(_np(dec.last_kept_indices), ri)
+    np.testing.assert_array_equal(_np(l), rl)
+    np.testing.assert_array_equal(_np(s), rs)
+    np.testing.assert_allclose(_np(b), rb, atol=TOL, rtol=0)
+
+
 def test_decoder_empty_and_errors():
     from models.decoder import SSDDecoder
     p = np.load(os.path.join(GOLD, "priors.npz"))["mobilenet_v2"]

@@ -405,7 +405,7 @@ def test_uint8_pinned_batches_are_converted_on_the_lane():
 
 def test_predict_fused_softmax_matches_the_layered_decoder_across_batch_sizes():
     """``ssd_net_predict`` folds the softmax into the decoder's compaction kernel and keeps its candidate counters zero
-    between calls without a memset (csrc/ssd_bbox.hip): bitwise the detections of forward (softmax layer) +
+    between calls without a memset (csrc/ssd_decode.hip): bitwise the detections of forward (softmax layer) +
     ``SSDDecoder`` for a sequence of DIFFERENT batch sizes on one net (the workspace is carved once, for max_batch --
     a per-call layout once let a small batch's kept counts land on a larger batch's candidate counters), and with the
     option off."""

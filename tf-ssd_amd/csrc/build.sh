@@ -29,6 +29,8 @@ if cmp -s build/build_id.h.new build/build_id.h; then rm build/build_id.h.new; e
 # box math: separately-rounded fp32 ops (bit-exact indices vs the oracle)
 compile ssd_core.hip
 compile ssd_bbox.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
+# the detection post-processor: the same arithmetic (box_math.h), the same flags
+compile ssd_decode.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
 # target assignment strategies: ssd_bbox.hip's IoU bits (box_math.h), one rounding per operation in ATSS's statistics
 compile ssd_match.hip -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
 # loss: separately rounded ops too (the hard-negative RANK depends on the per-anchor CE values)

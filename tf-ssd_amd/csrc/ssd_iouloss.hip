@@ -44,7 +44,7 @@ struct Box {
     float h, w;             // the decoded sizes exp(d * var) * prior size (y2 = h + y1, x2 = w + x1)
 };
 
-// utils/bbox_utils.py:61-85 on deltas * variances (models/decoder.py:41): ssd_bbox.hip's decode_box, the sizes kept
+// utils/bbox_utils.py:61-85 on deltas * variances (models/decoder.py:41): box_math.h's decode_box, the sizes kept
 __device__ __forceinline__ Box decode(const float4 p, const float4 d, const float4 var, float& ph, float& pw) {
 #pragma clang fp contract(off)
     const float dy = d.x * var.x, dx = d.y * var.y, dh = d.z * var.z, dw = d.w * var.w;

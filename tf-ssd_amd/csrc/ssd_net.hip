@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "ssd_decode.h"
 #include "ssd_net.h"
 
 using namespace ssd;
@@ -1287,6 +1288,9 @@ int ssd_net_forward(ssd_net* net, const float* image_dev, int B, float* deltas_o
                        [&]() { return forward_impl(net, image_dev, B, deltas_out_dev, probs_out_dev, st); });
 }
 
+// a float's bits as a word of a graph key
+static const void* float_key(const float f) { union { float f; intptr_t i; } k{}; k.f = f; return (const void*)k.i; }
+
 // ssd_net_predict (cfg == NULL: hard per-class NMS, max_per_class = max_total) and ssd_net_predict_cfg behind one body.
 // Whatever the config, a call leaves every candidate counter it used at zero (nms_class_kernel / soft_nms_kernel reset
 // their own list's), so calls of different configs may alternate on one workspace; the carve depends on max_per_class
@@ -1337,18 +1341,14 @@ static int predict_impl(ssd_net* net, const float* image_dev, int B, const float
     hipStream_t st = (hipStream_t)stream;
     SSD_CHECK_ARG(var != nullptr, "ssd_net_predict: variances pointer is NULL");
     const float v4[4] = {var[0], var[1], var[2], var[3]};
-    union { float f; intptr_t i; } k1{}, k2{};
-    k1.f = iou_thr; k2.f = score_thr;
     std::vector<const void*> key = {image_dev, priors_dev, boxes_dev, labels_dev, scores_dev, valid_dev,
                                     (const void*)(intptr_t)B, (const void*)(intptr_t)max_total,
-                                    (const void*)k1.i, (const void*)k2.i, (const void*)(intptr_t)(cfg ? 3 : 2)};
-    for (int i = 0; i < 4; ++i) { union { float f; intptr_t i; } k{}; k.f = v4[i]; key.push_back((const void*)k.i); }
+                                    float_key(iou_thr), float_key(score_thr), (const void*)(intptr_t)(cfg ? 3 : 2)};
+    for (int i = 0; i < 4; ++i) key.push_back(float_key(v4[i]));
     if (cfg) {      // every field of the config (max_total, the two thresholds: above)
-        union { float f; intptr_t i; } ks{};
-        ks.f = cfg->sigma;
         for (const int v : {cfg->method, cfg->class_agnostic != 0 ? 1 : 0, cfg->max_per_class, cfg->clip_boxes})
             key.push_back((const void*)(intptr_t)v);
-        key.push_back((const void*)ks.i);
+        key.push_back(float_key(cfg->sigma));
     }
     // softmax folded into the decoder's compaction (one pass over the [B, N, L] buffer and two launches -- softmax, counter
     // memset -- less); option "fuse_softmax" 0 keeps the layer-by-layer form
@@ -1356,18 +1356,15 @@ static int predict_impl(ssd_net* net, const float* image_dev, int B, const float
     int rc = run_graphed(net, key, st, [&]() {
         int r = forward_impl(net, image_dev, B, net->deltas, net->probs, st, fused_sm);
         if (r) return r;
-        if (cfg && fused_sm)
-            return decode_nms_fused_cfg(net->deltas, net->probs, priors_dev, v4, B, N, L, cfg, boxes_dev, labels_dev, scores_dev,
-                                        valid_dev, net->nms_ws, net->nms_ws_bytes, net->nms_ws_batch, st);
-        if (cfg)
-            return ssd_decode_nms_cfg(net->deltas, net->probs, priors_dev, v4, B, N, L, cfg, boxes_dev, labels_dev, scores_dev,
-                                      valid_dev, nullptr, net->nms_ws, net->nms_ws_bytes, (void*)st);
-        if (fused_sm)
-            return decode_nms_fused(net->deltas, net->probs, priors_dev, v4, B, N, L, max_total, max_total, iou_thr, score_thr,
-                                    boxes_dev, labels_dev, scores_dev, valid_dev, net->nms_ws, net->nms_ws_bytes, net->nms_ws_batch, st);
-        return ssd_decode_nms(net->deltas, net->probs, priors_dev, v4, B, N, L, max_total, max_total, iou_thr,
-                              score_thr, boxes_dev, labels_dev, scores_dev, valid_dev, nullptr, net->nms_ws,
-                              net->nms_ws_bytes, (void*)st);
+        // fused: head LOGITS in, counters known clean, the carve of nms_ws_batch images; otherwise the layer-by-layer
+        // decoder on the softmax layer's output, carved per call
+        NmsCall c = {.deltas = net->deltas, .scores = net->probs, .priors_or_boxes = priors_dev, .var = v4, .B = B, .N = N,
+                     .L = L, .decode = true, .logits = fused_sm, .counts_clean = fused_sm,
+                     .cfg = {SSD_NMS_HARD, 0, max_total, max_total, 1, iou_thr, score_thr, 0.0f}, .boxes_out = boxes_dev,
+                     .labels_out = labels_dev, .scores_out = scores_dev, .valid_out = valid_dev, .ws = net->nms_ws,
+                     .ws_bytes = net->nms_ws_bytes, .ws_batch = fused_sm ? net->nms_ws_batch : 0};
+        if (cfg && (r = nms_set_config(&c, cfg))) return r;
+        return decode_nms(c, cfg ? "ssd_decode_nms_cfg" : "ssd_decode_nms", st);
     });
     if (rc && fused_sm && net->nms_ws) {
         // a step that failed between the compaction and the per-class kernel leaves candidate counters behind: the next

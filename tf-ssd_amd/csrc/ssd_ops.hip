@@ -180,7 +180,7 @@ int launch_l2norm(const float* in, long pixels, int C, const float* gamma, float
 }
 
 // ------------------------------------------------------------------ softmax over the last dim
-// (the LDS-staged kernel lives in ssd_bbox.hip beside the fused decoder, which shares its row function: same bits)
+// (the LDS-staged kernel lives in ssd_decode.hip beside the fused decoder, which shares its row function: same bits)
 int launch_softmax_lds(const float* in, long rows, int L, float* out, hipStream_t st);
 
 __global__ void softmax_direct_kernel(const float* __restrict__ in, const long rows, const int L,
